@@ -14,7 +14,18 @@ Other workloads (`--workload`), same contract, used for profiling the other rows
       + per-tx reduce (K3/K4/K1/K5); 10^7 / 8 txs per GPU by default.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; rank 0 prints ONE
-JSON line. N > 1 runs one rank per GPU: under torch.distributed.run (WORLD_SIZE
+JSON line. A plain run does only what the headline needs: corpus, W warmup
+steps, K timed steps, the line (value, ms_per_step, the roofline fields derived
+from the timed steps and the committed PMC files). `--full` adds the legs that
+take runs of their own after the timed steps: `verdict_check` (every status
+against the corpus construction and the C oracle; the all-gather check when
+N > 1), the shader-clock sampling step (`clock`, `clock_ghz`, `verifs_per_mclk`
+and the clock-based peak) and `cpu_baseline`. `--dump-outputs DIR` writes what
+the last timed step left in the caller's arrays (statuses, verdict words as
+32-bit halves, tx ids, ...) as DIR/<name>.npy, float32 / float64, at most 64 MB:
+larger arrays as a fixed seeded sample of rows. The corpora are seeded, so two
+runs with the same arguments see the same inputs.
+N > 1 runs one rank per GPU: under torch.distributed.run (WORLD_SIZE
 set, and it must equal N), or -- when WORLD_SIZE is unset -- bench.py starts
 the N ranks itself as a child `torch.distributed.run` before anything touches
 the GPU, relays rank 0's line and exits non-zero if any rank fails. Every rank
@@ -181,6 +192,9 @@ class C2:
         self.eng.ed25519_verify_device(self.pubs, self.sigs, self.msgs, self.status, self.verdict, device=0,
                                        stream=self.stream)
 
+    def outputs(self):
+        return {"status": self.status, "verdict_words": _words_u32(self.verdict)}
+
     def check(self):
         # every lane is checked: lanes whose status the corpus construction fixes
         # against it, the construction-open ones (S + kL, slide()-dependent) against
@@ -319,6 +333,9 @@ class C3:
     def step(self):
         self.eng.ecdsa_verify_device(self.scheme, self.keys, self.key_len, self.sigs, self.sig_len, self.msgs,
                                      self.status, self.verdict, device=0, stream=self.stream)
+
+    def outputs(self):
+        return {"status": self.status, "verdict_words": _words_u32(self.verdict)}
 
     def check(self):
         # exact-status lanes vs the construction; REJECT_ANY lanes (bit flips whose
@@ -501,6 +518,10 @@ class C4:
                                                  self.keys, self.sigs, self.txid, self.tx_status, self.first_bad,
                                                  self.sig_status, device=0, stream=self.stream)
 
+    def outputs(self):
+        return {"txid": self.txid, "tx_status": self.tx_status, "first_bad_sig": self.first_bad,
+                "sig_status": self.sig_status}
+
     def check(self):
         out = {"mismatches_vs_construction": int((self.tx_status != self.exp_status).sum())
                + int((self.first_bad != self.exp_bad).sum()),
@@ -623,6 +644,9 @@ class C5:
         t = self.torch
         st = t.cat([self.ed[3], self.ec[6]]).to(self.device, non_blocking=True)
         return _pack_verdict(st)
+
+    def outputs(self):
+        return {"ed25519_status": self.ed[3], "ecdsa_status": self.ec[6]}
 
     def check(self):
         t = self.torch
@@ -767,6 +791,9 @@ class C2H(C2):
     def drain(self):
         self.hb.drain(self.eng)
 
+    def outputs(self):  # the last completed call's arrays
+        return {"status": self.hb.status, "verdict_words": _words_u32(self.hb.verdict)}
+
     def check(self):
         import torch
         st = self.hb.status
@@ -820,6 +847,9 @@ class C3H(C3):
     def drain(self):
         self.hb.drain(self.eng)
 
+    def outputs(self):  # the last completed call's arrays
+        return {"status": self.hb.status, "verdict_words": _words_u32(self.hb.verdict)}
+
     def check(self):
         self.status = self.hb.status
         dev = (self.scheme, self.keys, self.key_len, self.sigs, self.sig_len, self.msgs, self.expected)
@@ -869,6 +899,7 @@ class C4H(C4):
         self.h_txid, self.h_txst, self.h_sst, self.h_fb = self.outs[0]
         self.pending = []  # (ticket, slot), oldest first
         self.next_slot = 0
+        self.last_slot = 0  # the slot of the last completed call
         self.bs = []
         if self.components:
             # what the JVM hands over instead of leaves: the Kryo items (data = offsets into the
@@ -916,7 +947,7 @@ class C4H(C4):
     def _wait_oldest(self):
         import ctypes  # noqa: F401
         from corda_amd._lib import check, lib
-        t, _ = self.pending.pop(0)
+        t, self.last_slot = self.pending.pop(0)
         check(lib().cordahip_wait(self.eng.ctx, t, -1), "cordahip_wait")
 
     def step(self):
@@ -934,6 +965,10 @@ class C4H(C4):
     def drain(self):
         while self.pending:
             self._wait_oldest()
+
+    def outputs(self):  # the last completed call's arrays
+        txid, txst, sst, fb = self.outs[self.last_slot]
+        return {"txid": txid, "tx_status": txst, "first_bad_sig": fb, "sig_status": sst}
 
     def check(self):
         import torch  # noqa: F401
@@ -959,6 +994,35 @@ class C4H(C4):
     def cpu_baseline(self, sample):
         self.sig_status = self.h_sst
         return C4.cpu_baseline(self, sample)
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: the .npy payloads together stay under this
+
+
+def _words_u32(t):
+    """64-bit verdict words -> [n, 2] (low, high) 32-bit halves, each exact in float64."""
+    a = t.detach().cpu().contiguous().numpy() if hasattr(t, "detach") else np.ascontiguousarray(t)
+    return a.view(np.uint32).reshape(-1, 2).astype(np.int64)
+
+
+def _dump_outputs(path, outs):
+    """Write a workload's outputs() as path/<name>.npy: 8- and 16-bit integers as
+    float32, everything else as float64 (outputs() hands over nothing wider than
+    32 bits). An array larger than its share of DUMP_BYTES is cut to a fixed,
+    seeded sample of its rows (sorted row indices, the same for every run)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(outs))
+    for name, t in outs.items():
+        if not hasattr(t, "detach"):
+            t = torch.from_numpy(np.ascontiguousarray(t))
+        dt = np.float32 if t.element_size() <= 2 else np.float64
+        row_bytes = np.dtype(dt).itemsize * max(1, t[0].numel() if t.dim() > 1 else 1)
+        rows = t.shape[0]
+        if rows * row_bytes > share:
+            idx = np.sort(np.random.default_rng(0xC0DAD0).choice(rows, share // row_bytes, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy().astype(dt))
 
 
 def _pack_verdict(status):
@@ -996,6 +1060,9 @@ class Stub:
 
     def step(self):
         self.hashlib.sha256(self.buf).digest()
+
+    def outputs(self):
+        return {"status": self.status, "verdict_words": _words_u32(self.verdict)}
 
     def check(self):
         return {"mismatches_vs_construction": 0, "lanes": self.n, "accepted": int((self.status == 0).sum())}
@@ -1102,12 +1169,20 @@ def parse_args(argv=None):
     ap.add_argument("--inflight", type=int, default=1,
                     help="c4h, c2h, c3h: calls outstanding at once (consecutive batches overlap on the device); "
                          "give --warmup >= K so every transaction set has grown its stages before timing")
-    ap.add_argument("--cpu-sample", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-clock", action="store_true", help="skip the shader-clock sampling step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the verdict check "
+                         "against the construction and the C oracle, the all-gather check (N > 1), the shader-clock "
+                         "sampling step and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="--full: tuples of the CPU baseline's sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-clock", action="store_true", help="--full: skip the shader-clock sampling step")
     ap.add_argument("--global-log2", type=int, default=None,
                     help="C5 only: strong scaling over a fixed 2^G global batch (SURVEY 8d C5: G = 28)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.inflight > 1 and args.warmup < args.inflight:
         # with fewer warmup calls than calls in flight, a transaction set would grow its
         # pinned stages (GBs of page-locked memory) inside the timed steps
@@ -1224,24 +1299,29 @@ def main():
     else:
         kernel_ms = sum(a.elapsed_time(b) for a, b in evs) / args.steps
 
-    # after the timed region: the verdict all-gather reassembles every rank's mask
-    gather = None
-    verdict = getattr(wl, "verdict", None)
-    if world > 1 and verdict is not None:
-        g = gather_verdicts(verdict, world)
-        nv = verdict.numel()
-        gather = bool(torch.equal(g[rank * nv:(rank + 1) * nv], verdict))
-    # the shader clock this box holds under this workload (one more, untimed step)
-    clock = None
-    if not stub and not args.no_clock:
-        clock = _clock_under_load(local_rank, step, sync_all, elapsed * 1e3 / args.steps)
-    chk = wl.check()
+    # what the last timed step left in the caller's arrays, before any later leg runs
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, wl.outputs())
+
+    gather, clock, chk = None, None, None
+    if args.full:
+        # after the timed region: the verdict all-gather reassembles every rank's mask
+        verdict = getattr(wl, "verdict", None)
+        if world > 1 and verdict is not None:
+            g = gather_verdicts(verdict, world)
+            nv = verdict.numel()
+            gather = bool(torch.equal(g[rank * nv:(rank + 1) * nv], verdict))
+        # the shader clock this box holds under this workload (one more, untimed step)
+        if not stub and not args.no_clock:
+            clock = _clock_under_load(local_rank, step, sync_all, elapsed * 1e3 / args.steps)
+        chk = wl.check()
     elapsed = max_over_ranks(elapsed, device)
-    for key in ("mismatches_vs_construction", "mismatches_vs_oracle_open_lanes"):
-        if key in chk:
-            chk[key] = int(max_over_ranks(float(chk[key]), device))
-    if gather is not None:
-        chk["verdict_allgather_ok_all_ranks"] = max_over_ranks(0.0 if gather else 1.0, device) == 0.0
+    if chk is not None:
+        for key in ("mismatches_vs_construction", "mismatches_vs_oracle_open_lanes"):
+            if key in chk:
+                chk[key] = int(max_over_ranks(float(chk[key]), device))
+        if gather is not None:
+            chk["verdict_allgather_ok_all_ranks"] = max_over_ranks(0.0 if gather else 1.0, device) == 0.0
     numa_nodes = _gather_ints(_NUMA.get("numa_node"), world, device)
 
     if rank == 0:
@@ -1316,9 +1396,11 @@ def main():
                          "work_per_unit": "%d limb-MACs per verification (SURVEY §8d)" % wl.macs},
             "int_alu_peak_frac": achieved / INT_MAC_PEAK_T,
             "valu_busy": valu_busy,
-            "verdict_check": chk,
             "corpus_gen_s": t_gen,
+            "full": args.full,
         }
+        if chk is not None:
+            out["verdict_check"] = chk
         if eng is not None:
             # the library's device memory after the run (cordahip_device_mem): what this workload
             # held at its peak against the budget (CORDAHIP_DEVICE_MEM_BUDGET); torch's corpus
@@ -1351,7 +1433,7 @@ def main():
                                        (1024 * kernel_ms * 1e-3 * clock["clock_ghz"] * 1e9))
                     vb["valu_busy_basis"] = ("PMC wave instructions per unit x units x 4 SIMD-cycles / "
                                              "(1024 SIMDs x kernel_ms x clock_ghz) of this run")
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             # bounded samples sized for ~10 s of 16-thread CPU work each (C1: its whole 2^20 set)
             sample = args.cpu_sample or {"c1": 1 << 20, "c2": 1 << 22, "c3": 1 << 20, "c4": 1 << 20, "c5": 1 << 21,
                                          "c2h": 1 << 22, "c3h": 1 << 20, "c4h": 1 << 20}[args.workload]

@@ -30,7 +30,7 @@ def _bench(args, env, timeout=240):
 
 
 def test_launcher_two_ranks_one_line():
-    r = _bench(["--gpus", "2", "--workload", "stub", "--steps", "3", "--warmup", "1"], _env())
+    r = _bench(["--gpus", "2", "--workload", "stub", "--steps", "3", "--warmup", "1", "--full"], _env())
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -43,13 +43,45 @@ def test_launcher_two_ranks_one_line():
 
 
 def test_single_gpu_stays_in_process():
-    r = _bench(["--gpus", "1", "--workload", "stub", "--steps", "2", "--warmup", "0"], _env())
+    r = _bench(["--gpus", "1", "--workload", "stub", "--steps", "2", "--warmup", "0", "--full"], _env())
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["config"]["launcher"] == "in-process"
     assert "verdict_allgather_ok_all_ranks" not in out["verdict_check"]
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline and none of the legs that take
+    runs of their own; --dump-outputs writes float arrays that two runs with the
+    same arguments reproduce."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        r = _bench(["--gpus", "1", "--workload", "stub", "--steps", "4", "--warmup", "1",
+                    "--dump-outputs", str(tmp_path / d)], _env())
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert out["steps"] == 4 and out["warmup"] == 1 and out["full"] is False
+    assert out["ms_per_step"] > 0 and out["value"] > 0
+    lanes = out["config"]["batch_per_gpu"]  # value = lanes per step / the time of one timed step
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - lanes) < 1e-6 * lanes
+    for key in ("verdict_check", "cpu_baseline", "clock", "clock_ghz"):
+        assert key not in out
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["status.npy", "verdict_words.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0
+        assert np.array_equal(a, b)
+    st, vw = np.load(tmp_path / "a" / "status.npy"), np.load(tmp_path / "a" / "verdict_words.npy")
+    words = vw[:, 0].astype(np.uint64) | (vw[:, 1].astype(np.uint64) << np.uint64(32))
+    ok = (st == 0).reshape(-1, 64).astype(np.uint64) << np.arange(64, dtype=np.uint64)
+    assert np.array_equal(words, ok.sum(axis=1, dtype=np.uint64))
 
 
 def test_failing_rank_fails_the_launch():

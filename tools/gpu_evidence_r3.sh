@@ -6,7 +6,7 @@ O=$R/gpurun_out/ev3
 mkdir -p $O
 cd $R
 for wl in ${WLS:-c2 c3 c4 c5 c1 c2h c3h c4h}; do
-  timeout -k 10 420 python -u bench.py --workload $wl > $O/bench_$wl.json 2> $O/bench_$wl.err || { echo "bench $wl failed"; tail -20 $O/bench_$wl.err; exit 1; }
+  timeout -k 10 420 python -u bench.py --full --workload $wl > $O/bench_$wl.json 2> $O/bench_$wl.err || { echo "bench $wl failed"; tail -20 $O/bench_$wl.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench_$wl.json'));c=d['verdict_check'];print('$wl', round(d['value']/1e6,2), 'M/s', round(d['roofline']['kernel_ms'],2), 'ms frac', round(d['roofline']['frac'],3), 'traffic', d['roofline']['traffic'] is not None, 'mism', c.get('mismatches_vs_construction'), c.get('mismatches_vs_oracle_open_lanes'), 'cpu', round(d.get('cpu_baseline',{}).get('value',0)))"
 done
 for wl in ${PROF:-c2 c3 c4 c5}; do

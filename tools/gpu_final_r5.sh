@@ -9,11 +9,11 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -1 $O/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 600 python -u bench.py > $O/bench_c2.json 2> $O/bench_c2.err || { echo "bench c2 failed"; tail -20 $O/bench_c2.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err || { echo "bench c2 failed"; tail -20 $O/bench_c2.err; exit 1; }
 python3 -c "import json;d=json.load(open('$O/bench_c2.json'));print('c2', round(d['value']/1e6,2), d['ms_per_step'], d['clock']['clock_ghz'], d['roofline']['frac'])"
 for wl in "c1" "c3" "c4" "c5" "c2h" "c3h" "c4h" "c4h --components" "c4 --device-encode"; do
   t=$(echo $wl | tr -d ' -')
-  timeout -k 10 600 python -u bench.py --workload $wl > $O/bench_$t.json 2> $O/bench_$t.err || { echo "bench $wl failed"; tail -20 $O/bench_$t.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full --workload $wl > $O/bench_$t.json 2> $O/bench_$t.err || { echo "bench $wl failed"; tail -20 $O/bench_$t.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench_$t.json'));print('$t', round(d['value']/1e6,2), d['clock']['clock_ghz'], {k: v for k, v in d['verdict_check'].items() if 'mismatch' in k})"
 done
 cd /tmp && export TMPDIR=/tmp

@@ -8,7 +8,7 @@ mkdir -p $O
 cd $R
 line() {
   t=$1; shift
-  timeout -k 10 600 python -u bench.py "$@" > $O/bench_$t.json 2> $O/bench_$t.err || { echo "bench $t failed"; tail -20 $O/bench_$t.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full "$@" > $O/bench_$t.json 2> $O/bench_$t.err || { echo "bench $t failed"; tail -20 $O/bench_$t.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench_$t.json'));print('$t', round(d['value']/1e6,2), round(d['ms_per_step'],2), d.get('clock_ghz') and round(d['clock_ghz'],3), d.get('valu_busy') and round(d['valu_busy']['valu_busy'],3), d.get('device_mem_gb'), {k: v for k, v in d['verdict_check'].items() if 'mismatch' in k})"
 }
 line c4 --workload c4 && line c4h2 --workload c4h --inflight 2 --steps 40 --warmup 6 && \
