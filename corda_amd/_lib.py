@@ -36,6 +36,7 @@ EXPORTS = [
     "cordahip_tx_submit", "cordahip_txid_submit", "cordahip_filtered_tx_submit", "cordahip_shard_range",
     "cordahip_kryo_encode", "cordahip_kryo_encode_device", "cordahip_signed_txcomp_verify", "cordahip_txcomp_submit",
     "cordahip_signed_txcomp_verify_ed25519_device", "cordahip_device_mem", "cordahip_trim",
+    "cordahip_rsa_public_op_device", "cordahip_rsa_pss_verify_device",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
@@ -44,6 +45,8 @@ KRYO_KINDS = {"raw": 0, "char": 1, "short": 2, "int": 3, "long": 4, "byte": 5, "
               "issue_command": 14, "cash_state": 15}
 ABI_VERSION = 4
 FLAG_IS_VALID = 1  # CORDAHIP_FLAG_IS_VALID: Crypto.isValid semantics (no emptiness checks)
+FLAG_RSA_ON_DEVICE = 2  # CORDAHIP_FLAG_RSA_ON_DEVICE: RSA_SHA256 lanes verified on the GPU, not UNSUPPORTED
+RSA_GROUP_LANES = 8  # lanes that share one signature in rsa_modexp_kernel (corda_amd/csrc/rsa.hip kT)
 TX_NO_LEAVES, TX_NO_SIGNATURES, TX_BAD_TREE, TX_BAD_COMPONENT = 6, 7, 8, 9
 
 
@@ -201,6 +204,8 @@ def lib() -> ctypes.CDLL:
                                                                vp, vp, vp, vp, vp]),
         "cordahip_device_mem": (i32, [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "cordahip_trim": (i32, [vp]),
+        "cordahip_rsa_public_op_device": (i32, [vp, i32, vp, vp, vp, u32, u64, vp, vp]),
+        "cordahip_rsa_pss_verify_device": (i32, [vp, i32, vp, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(l, name)

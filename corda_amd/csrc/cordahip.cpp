@@ -336,6 +336,31 @@ hipError_t ec_verify_enqueue(Device& d, const uint8_t* scheme, const uint8_t* ke
   return e;
 }
 
+// Enqueue RSASSA-PSS verification of n rows of one width class on stream s (device
+// current, d.rsa_mu held). The workspace holds at most kRsaWsRows rows (the
+// launches loop over it) and is reused only after its previous user's kernels.
+constexpr uint64_t kRsaWsRows = 1ull << 17;  // x 518 B (4096-bit rows) = 68 MB at most
+hipError_t rsa_verify_enqueue(Device& d, const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
+                              const uint16_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len,
+                              uint32_t W, uint64_t n, const uint8_t* pre, uint8_t* status,
+                              unsigned long long* verdict, uint32_t flags, hipStream_t s) {
+  RsaWork& w = d.rsa;
+  const uint64_t rows = std::min<uint64_t>(kRsaWsRows, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
+  const size_t rb = rsa_ws_row_bytes(W);
+  if (w.ws.cap < rows * rb) {
+    hipError_t e = w.ev ? hipEventSynchronize(w.ev) : hipSuccess;  // a smaller buffer may still be in use
+    if (e != hipSuccess) return e;
+    if (w.ws.ensure(rows * rb)) return hipErrorOutOfMemory;
+  }
+  if (!w.ev && hipEventCreateWithFlags(&w.ev, hipEventDisableTiming) != hipSuccess) return hipErrorUnknown;
+  hipError_t e = hipStreamWaitEvent(s, w.ev, 0);
+  e = e ? e
+        : launch_rsa_pss_verify(mod, exp, sigs, sig_len, msgs, msg_off, msg_len, W, n, pre, status, verdict,
+                                w.ws.as<uint8_t>(), w.ws.cap / rb / 64 * 64, flags, s);
+  e = e ? e : hipEventRecord(w.ev, s);
+  return e;
+}
+
 // Enqueue Ed25519 verification of n dense lanes on stream s (device already current).
 hipError_t ed_verify_enqueue(Device& d, const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs,
                              uint32_t msg_len, uint64_t n, const uint8_t* pre, uint8_t* status,
@@ -442,16 +467,20 @@ void device_budget(Device& d) {  // device current
 
 // Free an idle device's grow-only buffers (the idle release, cordahip_trim): both
 // buffer sets and every lock that guards a buffer, in an order every path keeps
-// (sets, then kryo_mu, stream_mu, ped_mu, ed_mu, ec_mu, each slot in order); the events that fence
+// (sets, then kryo_mu, stream_mu, ped_mu, ed_mu, ec_mu, each slot in order, rsa_mu); the events that fence
 // device-path users (kernels on caller streams) synchronised first. The fixed
 // tables and the encoder's shape table stay (derived data, 18 MB).
 void trim_device(Device& d) {
   SetLease l0(d, 0, true), l1(d, 1, true);
   std::lock_guard<std::mutex> gk(d.kryo_mu), gs(d.stream_mu), gp(d.ped_mu), ge0(d.ed_mu[0]), ge1(d.ed_mu[1]),
-      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]);
+      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu);
   if (hipSetDevice(d.id) != hipSuccess) return;
-  for (hipEvent_t ev : {d.ed_ev[0], d.ed_ev[1], d.ec[0].ev, d.ec[1].ev, d.kryo_ev, d.set[0].tx_ev, d.set[1].tx_ev})
+  for (hipEvent_t ev : {d.ed_ev[0], d.ed_ev[1], d.ec[0].ev, d.ec[1].ev, d.kryo_ev, d.set[0].tx_ev, d.set[1].tx_ev,
+                        d.rsa.ev})
     if (ev) (void)hipEventSynchronize(ev);
+  d.rsa.ws.release();
+  for (auto& b : d.rsa.h) b.release();
+  for (auto& b : d.rsa.d) b.release();
   for (auto& w : d.ed_ws) w.release();
   for (EcWork& w : d.ec) {
     w.ws.release();
@@ -1546,6 +1575,11 @@ void free_device(Device& d) {
                     &d.kryo_sizes, &d.kryo_temp, &d.kryo_ws, &d.kryo_fixed, &d.kryo_items})
     b->release();
   for (auto& w : d.ed_ws) w.release();
+  d.rsa.ws.release();
+  for (auto& b : d.rsa.h) b.release();
+  for (auto& b : d.rsa.d) b.release();
+  if (d.rsa.ev) (void)hipEventDestroy(d.rsa.ev);
+  if (d.s_rsa) (void)hipStreamDestroy(d.s_rsa);
   if (d.kryo_usage) (void)hipHostFree(d.kryo_usage);
   d.kryo_usage = d.kryo_usage_dev = nullptr;
   for (hipEvent_t ev : {d.ec[0].ev, d.ec[1].ev, d.ed_ev[0], d.ed_ev[1], d.kryo_ev})
@@ -1910,6 +1944,51 @@ int cordahip_ecdsa_verify_device(cordahip_ctx* ctx, int device, const void* d_sc
                                    static_cast<const uint8_t*>(d_sig_len), static_cast<const uint8_t*>(d_msgs), nullptr,
                                    msg_len, n, nullptr, static_cast<uint8_t*>(d_status),
                                    static_cast<unsigned long long*>(d_verdict), 0u, s);
+  e = e ? e : hipEventRecord(tc->b, s);
+  return hip_err(e);
+}
+
+int cordahip_rsa_public_op_device(cordahip_ctx* ctx, int device, const void* d_mod, const void* d_exp,
+                                  const void* d_in, uint32_t mod_words, uint64_t n, void* d_out, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || (mod_words != 64 && mod_words != 96 && mod_words != 128) || (n && (!d_mod || !d_exp || !d_in || !d_out)))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_mod) | reinterpret_cast<uintptr_t>(d_exp) | reinterpret_cast<uintptr_t>(d_in) |
+       reinterpret_cast<uintptr_t>(d_out)) & 3)
+    return CORDAHIP_ERR_INVALID_ARG;
+  const Activity act(*d);
+  if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  TimedCall* tc = timed_begin(*d, s);
+  if (!tc) return CORDAHIP_ERR_HIP;
+  hipError_t e = launch_rsa_public_op(static_cast<const uint32_t*>(d_mod), static_cast<const uint32_t*>(d_exp),
+                                      static_cast<const uint32_t*>(d_in), mod_words, n, static_cast<uint32_t*>(d_out),
+                                      s);
+  e = e ? e : hipEventRecord(tc->b, s);
+  return hip_err(e);
+}
+
+int cordahip_rsa_pss_verify_device(cordahip_ctx* ctx, int device, const void* d_mod, const void* d_exp,
+                                   const void* d_sigs, const void* d_sig_len, const void* d_msgs, uint32_t msg_len,
+                                   uint32_t mod_words, uint64_t n, void* d_status, void* d_verdict, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || (mod_words != 64 && mod_words != 96 && mod_words != 128) ||
+      (n && (!d_mod || !d_exp || !d_sigs || !d_sig_len || !d_status || (msg_len && !d_msgs))))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_mod) | reinterpret_cast<uintptr_t>(d_exp)) & 3 ||
+      reinterpret_cast<uintptr_t>(d_sig_len) & 1)
+    return CORDAHIP_ERR_INVALID_ARG;
+  const Activity act(*d);
+  std::lock_guard<std::mutex> g(d->rsa_mu);
+  if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  TimedCall* tc = timed_begin(*d, s);
+  if (!tc) return CORDAHIP_ERR_HIP;
+  hipError_t e = rsa_verify_enqueue(*d, static_cast<const uint32_t*>(d_mod), static_cast<const uint32_t*>(d_exp),
+                                    static_cast<const uint8_t*>(d_sigs), static_cast<const uint16_t*>(d_sig_len),
+                                    static_cast<const uint8_t*>(d_msgs), nullptr, msg_len, mod_words, n, nullptr,
+                                    static_cast<uint8_t*>(d_status), static_cast<unsigned long long*>(d_verdict), 0u,
+                                    s);
   e = e ? e : hipEventRecord(tc->b, s);
   return hip_err(e);
 }

@@ -180,6 +180,80 @@ int ed_pipeline(cordahip_ctx* ctx, Device& d, const std::vector<Unit>& units, co
   return (e || e1 || e2) ? CORDAHIP_ERR_HIP : CORDAHIP_SUCCESS;
 }
 
+// The RSA section of one device's shard [lo, hi) of a generic batch
+// (CORDAHIP_FLAG_RSA_ON_DEVICE): the RSA_SHA256 lanes whose verdict needs the
+// arithmetic (pack_rows.hpp rsa_lane_pre; the others get their status from
+// classify), packed by width class into the device's single RSA stage and run in
+// launches of at most kRsaLaunchRows rows on s_rsa, beside the shard's Ed25519 /
+// ECDSA chunks. It runs on a thread of its own (sig_pipeline starts it first and
+// joins it last) and touches none of the caller's outputs: the statuses come back
+// in `lanes` / `status` and sig_pipeline scatters them, verdict bits included.
+// A shard without such a lane allocates nothing.
+constexpr uint64_t kRsaLaunchRows = 1ull << 15;
+struct RsaResult {
+  std::vector<uint64_t> lanes;
+  std::vector<uint8_t> status;
+};
+int rsa_section(cordahip_ctx* ctx, Device& d, const cordahip_sig_batch* b, const MsgView& mv, uint64_t lo, uint64_t hi,
+                RsaResult& out) {
+  const bool do_verify = !(b->flags & CORDAHIP_FLAG_IS_VALID);
+  std::vector<uint64_t> cl[3];  // lanes by class: 64, 96, 128 words
+  {
+    rsa::PublicKey pk;
+    for (uint64_t i = lo; i < hi; i++) {
+      if (b->scheme[i] != CORDAHIP_SCHEME_RSA_SHA256) continue;
+      if (!lane_ranges_ok(b, mv, i)) return CORDAHIP_ERR_INVALID_ARG;  // as classify will find too
+      if (rsa_lane_pre(b, mv, do_verify, i, pk) == kRsaToDevice) cl[pk.words / 32 - 2].push_back(i);
+    }
+  }
+  if (cl[0].empty() && cl[1].empty() && cl[2].empty()) return CORDAHIP_SUCCESS;
+  std::lock_guard<std::mutex> g(d.rsa_mu);
+  const Activity act(d);
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  if (!d.s_rsa && hipStreamCreateWithFlags(&d.s_rsa, hipStreamNonBlocking) != hipSuccess) return CORDAHIP_ERR_HIP;
+  HostPool& pool = pool_of(ctx, d);
+  RsaWork& w = d.rsa;
+  std::vector<uint64_t> mo;
+  for (int c = 0; c < 3; c++) {
+    const uint32_t W = 64 + 32 * (uint32_t)c;
+    for (uint64_t r0 = 0; r0 < cl[c].size(); r0 += kRsaLaunchRows) {
+      const uint64_t m = std::min<uint64_t>(kRsaLaunchRows, cl[c].size() - r0);
+      const uint64_t* lanes = cl[c].data() + r0;
+      mo.resize(m + 1);
+      mo[0] = 0;
+      for (uint64_t r = 0; r < m; r++) mo[r + 1] = mo[r] + mv.len(lanes[r]);
+      const size_t sz[7] = {m * 4 * W, m * 4, m * 4 * W, m * 2, std::max<uint64_t>(mo[m], 16), (m + 1) * 8, m};
+      for (int q = 0; q < 7; q++)
+        if (w.h[q].ensure(sz[q]) != hipSuccess || w.d[q].ensure(sz[q]) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+      std::memcpy(w.h[5].p, mo.data(), (m + 1) * 8);
+      pool.parallel_for(m, 256, [&](uint64_t x, uint64_t y) {
+        rsa::PublicKey pk;
+        for (uint64_t r = x; r < y; r++) {
+          const uint64_t i = lanes[r];
+          (void)rsa_lane_pre(b, mv, do_verify, i, pk);
+          pack_rsa_row(b, i, pk, W, r, w.h[0].as<uint32_t>(), w.h[1].as<uint32_t>(), w.h[2].as<uint8_t>(),
+                       w.h[3].as<uint16_t>());
+          std::memcpy(w.h[4].as<uint8_t>() + mo[r], mv.ptr(i), mo[r + 1] - mo[r]);
+        }
+      });
+      hipError_t e = hipSuccess;
+      for (int q = 0; q < 6; q++)
+        e = e ? e : hipMemcpyAsync(w.d[q].p, w.h[q].p, q == 4 ? mo[m] : sz[q], hipMemcpyHostToDevice, d.s_rsa);
+      e = e ? e
+            : rsa_verify_enqueue(d, w.d[0].as<uint32_t>(), w.d[1].as<uint32_t>(), w.d[2].as<uint8_t>(),
+                                 w.d[3].as<uint16_t>(), w.d[4].as<uint8_t>(), w.d[5].as<uint64_t>(), 0, W, m, nullptr,
+                                 w.d[6].as<uint8_t>(), nullptr, b->flags & CORDAHIP_FLAG_IS_VALID, d.s_rsa);
+      e = e ? e : hipMemcpyAsync(w.h[6].p, w.d[6].p, m, hipMemcpyDeviceToHost, d.s_rsa);
+      // the stage is single: its statuses are read before the next launch packs into it
+      const hipError_t e2 = hipStreamSynchronize(d.s_rsa);
+      if (e != hipSuccess || e2 != hipSuccess) return CORDAHIP_ERR_HIP;
+      out.lanes.insert(out.lanes.end(), lanes, lanes + m);
+      out.status.insert(out.status.end(), w.h[6].as<uint8_t>(), w.h[6].as<uint8_t>() + m);
+    }
+  }
+  return CORDAHIP_SUCCESS;
+}
+
 // Per-piece results of the classification pass of one chunk.
 struct PieceInfo {
   std::vector<std::pair<uint64_t, uint64_t>> ed;  // (message length, lanes), piece-local group order
@@ -224,6 +298,11 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
     for (hipEvent_t* pe : {&st.copied, &st.ed_done, &st.ec_done})
       if (!*pe && hipEventCreateWithFlags(pe, hipEventDisableTiming) != hipSuccess) return CORDAHIP_ERR_HIP;
   HostPool& pool = pool_of(ctx, d);
+  // the shard's RSA lanes, beside the chunks below (joined after they have drained)
+  RsaResult rsa_out;
+  std::future<int> rsa_job;
+  if (rsa_on_device(b, mv))
+    rsa_job = std::async(std::launch::async, [&, lo, hi] { return rsa_section(ctx, d, b, mv, lo, hi, rsa_out); });
   // Chunks whose rows are the lanes in order (one message length, Ed25519 only:
   // the common JVM batch) skip the host scatter: a kernel stores the statuses
   // straight into the caller's status array and the wave-ballot verdict words
@@ -306,6 +385,8 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
           if (c == kBadCsr) {
             P.bad_csr = true;
             c = kDirect;  // not packed: the chunk is not enqueued
+          } else if (c == kRsa) {
+            c = kDirect;  // not a row of the chunk: the RSA section owns the lane
           } else if (c == kEc) {
             P.ec++;
             P.ec_bytes += mlen;
@@ -563,6 +644,22 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
     for (BatchStage& st : set.pb)
       for (hipEvent_t ev : {st.copied, st.ed_done, st.ec_done}) (void)hipEventSynchronize(ev);
   }
+  if (rsa_job.valid()) {
+    // the RSA lanes' statuses, and their bits of the verdict words the chunks wrote
+    // before these statuses were known (shards own whole words)
+    const int rrc = rsa_job.get();
+    if (rc == CORDAHIP_SUCCESS) rc = rrc;
+    if (rc == CORDAHIP_SUCCESS && e == hipSuccess)
+      for (size_t r = 0; r < rsa_out.lanes.size(); r++) {
+        const uint64_t i = rsa_out.lanes[r];
+        b->status[i] = rsa_out.status[r];
+        if (b->verdict) {
+          const uint64_t bit = 1ull << (i & 63);
+          if (rsa_out.status[r] == CORDAHIP_STATUS_OK) b->verdict[i >> 6] |= bit;
+          else b->verdict[i >> 6] &= ~bit;
+        }
+      }
+  }
   if (tracing()) fprintf(stderr, "[cordahip] dev %d: shard done at %.1f ms\n", d.id, now_ms() - t_start);
   if (rc != CORDAHIP_SUCCESS) return rc;
   return e ? CORDAHIP_ERR_HIP : CORDAHIP_SUCCESS;
@@ -604,7 +701,7 @@ int sig_verify_range(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_si
 int sig_verify_impl(cordahip_ctx* ctx, const cordahip_sig_batch* b) {
   if (b->n == 0) return CORDAHIP_SUCCESS;
   if (!b->scheme || !b->key || !b->key_off || !b->sig || !b->sig_off || !b->msg || !b->msg_off || !b->status ||
-      (b->flags & ~CORDAHIP_FLAG_IS_VALID))
+      (b->flags & ~(CORDAHIP_FLAG_IS_VALID | CORDAHIP_FLAG_RSA_ON_DEVICE)))
     return CORDAHIP_ERR_INVALID_ARG;
   // every lane's ranges are checked as its chunk is classified (pack_rows.hpp classify)
   return sig_verify_msgs(ctx, b, MsgView{b->msg, b->msg_off, nullptr});

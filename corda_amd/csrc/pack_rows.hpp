@@ -12,6 +12,7 @@
 
 #include "../../include/cordahip.h"
 #include "der.hpp"
+#include "rsa_key.hpp"
 
 namespace cordahip {
 namespace rt {
@@ -39,17 +40,59 @@ inline void pack_ed_row(const cordahip_sig_batch* b, const MV& mv, bool do_verif
 // engines (statuses decided here are written at once). kBadCsr: the lane's CSR
 // ranges are not inside the batch's buffers (csr_check.hpp: the batch fails with
 // CORDAHIP_ERR_INVALID_ARG before its chunk is packed).
-enum : uint16_t { kDirect = 0, kEc = 1, kEdBase = 2, kBadCsr = 0xffff };
+// kRsa: an RSA_SHA256 lane the GPU verifies (CORDAHIP_FLAG_RSA_ON_DEVICE): not a row
+// of the chunk, its status comes from the batch's RSA section (host_batch.cpp).
+enum : uint16_t { kDirect = 0, kEc = 1, kEdBase = 2, kRsa = 0xfffe, kBadCsr = 0xffff };
+
+// the lane's ranges, before any byte of it is read: non-decreasing and inside
+// the declared buffers (key_off[i + 1] <= key_bytes, ...; messages of a signed-tx
+// batch are its transactions' ids, checked with the transactions)
+template <class MV>
+inline bool lane_ranges_ok(const cordahip_sig_batch* b, const MV& mv, uint64_t i) {
+  const uint64_t k0 = b->key_off[i], k1 = b->key_off[i + 1], s0 = b->sig_off[i], s1 = b->sig_off[i + 1];
+  if (k1 < k0 || k1 > b->key_bytes || s1 < s0 || s1 > b->sig_bytes) return false;
+  return mv.tx_of || (mv.off[i + 1] >= mv.off[i] && mv.off[i + 1] <= b->msg_bytes);
+}
+
+// does the batch route its RSA_SHA256 lanes to the GPU? (signed-tx batches carry no flags)
+template <class MV>
+inline bool rsa_on_device(const cordahip_sig_batch* b, const MV& mv) {
+  return (b->flags & CORDAHIP_FLAG_RSA_ON_DEVICE) && !mv.tx_of;
+}
+
+// What the host decides of RSA lane i (ranges checked): BAD_KEY / UNSUPPORTED from
+// the key (rsa_key.hpp parse_public_key), then EMPTY under doVerify rules, then
+// BAD_SIG for a signature longer than the modulus (PSSSigner: false); kRsaToDevice
+// with pk filled for the lanes whose verdict needs the arithmetic.
+constexpr uint8_t kRsaToDevice = 0xff;
+template <class MV>
+inline uint8_t rsa_lane_pre(const cordahip_sig_batch* b, const MV& mv, bool do_verify, uint64_t i,
+                            rsa::PublicKey& pk) {
+  const uint8_t ks = rsa::parse_public_key(b->key + b->key_off[i], b->key_off[i + 1] - b->key_off[i], pk);
+  if (ks != rsa::kOk) return ks;
+  const uint64_t sl = b->sig_off[i + 1] - b->sig_off[i];
+  if (do_verify && (sl == 0 || mv.len(i) == 0)) return CORDAHIP_STATUS_EMPTY;  // Crypto.kt:475-476
+  if (sl > (pk.bits + 7) / 8) return CORDAHIP_STATUS_BAD_SIG;
+  return kRsaToDevice;
+}
+
+// RSA row r of a class-W stage: the modulus padded to W words, e, the signature
+// right as it came (big-endian, at most 4 W bytes) and its length
+inline void pack_rsa_row(const cordahip_sig_batch* b, uint64_t i, const rsa::PublicKey& pk, uint32_t W, uint64_t r,
+                         uint32_t* hmod, uint32_t* hexp, uint8_t* hsig, uint16_t* hsl) {
+  std::memcpy(hmod + r * W, pk.n, 4ull * W);
+  hexp[r] = pk.e;
+  const uint64_t sl = b->sig_off[i + 1] - b->sig_off[i];  // <= ceil(bits / 8) <= 4 W (rsa_lane_pre)
+  std::memcpy(hsig + r * 4ull * W, b->sig + b->sig_off[i], sl);
+  std::memset(hsig + r * 4ull * W + sl, 0, 4ull * W - sl);
+  hsl[r] = (uint16_t)sl;
+}
 
 template <class MV>
 inline uint16_t classify(const cordahip_sig_batch* b, const MV& mv, uint64_t i, uint64_t& mlen) {
-  // the lane's ranges first, before any byte of it is read: non-decreasing and inside
-  // the declared buffers (key_off[i + 1] <= key_bytes, ...; messages of a signed-tx
-  // batch are its transactions' ids, checked with the transactions)
-  const uint64_t k0 = b->key_off[i], k1 = b->key_off[i + 1], s0 = b->sig_off[i], s1 = b->sig_off[i + 1];
   mlen = 0;
-  if (k1 < k0 || k1 > b->key_bytes || s1 < s0 || s1 > b->sig_bytes) return kBadCsr;
-  if (!mv.tx_of && (mv.off[i + 1] < mv.off[i] || mv.off[i + 1] > b->msg_bytes)) return kBadCsr;
+  if (!lane_ranges_ok(b, mv, i)) return kBadCsr;
+  const uint64_t k0 = b->key_off[i], k1 = b->key_off[i + 1];
   const uint8_t sch = b->scheme[i];
   const uint64_t kl = k1 - k0;
   mlen = mv.len(i);
@@ -59,6 +102,13 @@ inline uint16_t classify(const cordahip_sig_batch* b, const MV& mv, uint64_t i, 
       return kDirect;
     }
     return kEc;
+  }
+  if (sch == CORDAHIP_SCHEME_RSA_SHA256 && rsa_on_device(b, mv)) {
+    rsa::PublicKey pk;
+    const uint8_t st = rsa_lane_pre(b, mv, !(b->flags & CORDAHIP_FLAG_IS_VALID), i, pk);
+    if (st == kRsaToDevice) return kRsa;
+    b->status[i] = st;
+    return kDirect;
   }
   if (sch != CORDAHIP_SCHEME_EDDSA_ED25519_SHA512) {
     b->status[i] = CORDAHIP_STATUS_UNSUPPORTED;  // Crypto.kt:474 require(isSupportedSignatureScheme)

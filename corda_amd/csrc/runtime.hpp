@@ -100,6 +100,18 @@ hipError_t launch_ecdsa_verify(const uint8_t* scheme, const uint8_t* keys, const
                                unsigned long long* verdict, unsigned int* counters6, unsigned int* perm,
                                uint32_t* ws, uint64_t ws_slots, uint32_t flags, hipStream_t s);
 size_t ecdsa_ws_slot_bytes();
+// rsa.hip: rows of W = 64 / 96 / 128 little-endian words, one width per launch
+uint32_t rsa_group_lanes();  // lanes that share one signature in rsa_modexp_kernel
+hipError_t launch_rsa_public_op(const uint32_t* mod, const uint32_t* exp, const uint32_t* in, uint32_t W, uint64_t n,
+                                uint32_t* out, hipStream_t s);
+size_t rsa_ws_row_bytes(uint32_t W);
+// msg_off != nullptr: CSR messages (msg_off[n + 1] into msgs), else n * msg_len dense;
+// ws: ws_rows * rsa_ws_row_bytes(W) bytes, the launches loop over it
+hipError_t launch_rsa_pss_verify(const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
+                                 const uint16_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off,
+                                 uint32_t msg_len, uint32_t W, uint64_t n, const uint8_t* pre, uint8_t* status,
+                                 unsigned long long* verdict, uint8_t* ws, uint64_t ws_rows, uint32_t flags,
+                                 hipStream_t s);
 hipError_t launch_ecdsa_sign(const uint8_t* scheme, const uint8_t* seeds, const uint8_t* msgs, uint32_t msg_len,
                              uint64_t n, const uint32_t* gk1, const uint32_t* gr1, uint8_t* keys, uint8_t* key_len,
                              uint8_t* sigs, uint8_t* sig_len, hipStream_t s);
@@ -263,6 +275,17 @@ struct EcWork {  // device buffers of the ECDSA paths (grow-only)
   hipEvent_t ev = nullptr;   // last enqueued user of counters/perm/ws (cross-stream reuse)
 };
 
+// RSA (rsa.hip): the verify launches' workspace and the single stage of the
+// generic batches' RSA section (h/d[0..6]: moduli, exponents, signatures,
+// signature lengths, messages, message offsets, statuses). Nothing here is
+// allocated before a device's first RSA lane.
+struct RsaWork {
+  DevBuf ws;
+  hipEvent_t ev = nullptr;  // last enqueued user of ws (cross-stream reuse)
+  PinBuf h[7];
+  DevBuf d[7];
+};
+
 // Per-call timing of the *_device entry points: a ring of event pairs per
 // device, one pair per call, so concurrent callers never share events; a
 // slot's generation tells a reader whether its call's events are still there.
@@ -300,6 +323,12 @@ struct Device {
   std::mutex ec_mu[2];
   EcWork ec[2];
   std::atomic<uint32_t> ec_turn{0};
+  // RSA lanes: rsa_mu orders the users of the workspace (the dense device calls hold
+  // it while they enqueue, a generic batch's RSA section for its whole run, stage
+  // included); s_rsa is that section's stream, created with its first lane
+  std::mutex rsa_mu;
+  RsaWork rsa;
+  hipStream_t s_rsa = nullptr;
   hipStream_t stream = nullptr;  // context stream (init-time work and host tx paths)
   std::mutex tmu;
   TimedCall ring[kTimingRing];
@@ -496,6 +525,11 @@ hipError_t ec_verify_enqueue(Device& d, const uint8_t* scheme, const uint8_t* ke
                              const uint8_t* sigs, const uint8_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off,
                              uint32_t msg_len, uint64_t n, const uint8_t* pre, uint8_t* status,
                              unsigned long long* verdict, uint32_t flags, hipStream_t s, int slot = 0);
+// d.rsa_mu must be held; one width class per call (rsa.hip launch_rsa_pss_verify)
+hipError_t rsa_verify_enqueue(Device& d, const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
+                              const uint16_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len,
+                              uint32_t W, uint64_t n, const uint8_t* pre, uint8_t* status,
+                              unsigned long long* verdict, uint32_t flags, hipStream_t s);
 void shard_range(uint64_t n, uint64_t nshards, uint64_t shard, uint64_t align, uint64_t& lo, uint64_t& hi);
 uint64_t env_lanes(const char* name, uint64_t dflt);
 

@@ -55,10 +55,12 @@ class Engine:
         return np.ascontiguousarray(blob), off
 
     def verify_batch(self, schemes: Sequence[int], keys: Sequence[bytes], sigs: Sequence[bytes],
-                     msgs: Sequence[bytes], async_: bool = False, is_valid: bool = False):
+                     msgs: Sequence[bytes], async_: bool = False, is_valid: bool = False, rsa: bool = False):
         """Per-lane statuses for (scheme, key, sig, msg) tuples; returns (status, verdict).
         is_valid=False: Crypto.doVerify semantics (empty sig / clear data -> EMPTY);
-        is_valid=True: Crypto.isValid semantics (no emptiness checks)."""
+        is_valid=True: Crypto.isValid semantics (no emptiness checks).
+        rsa=True: RSA_SHA256 lanes (key = DER RSAPublicKey) are verified on the GPU
+        (CORDAHIP_FLAG_RSA_ON_DEVICE); otherwise they are UNSUPPORTED."""
         n = len(keys)
         sch = np.ascontiguousarray(np.asarray(schemes, dtype=np.uint8))
         kb, ko = self._csr(list(keys))
@@ -67,7 +69,9 @@ class Engine:
         status = np.zeros(max(n, 1), dtype=np.uint8)
         verdict = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
         b = SigBatch(n, _ptr(sch), _ptr(kb), _ptr(ko), _ptr(sb), _ptr(so), _ptr(mb), _ptr(mo),
-                     _ptr(status), _ptr(verdict), _lib.FLAG_IS_VALID if is_valid else 0, kb.size, sb.size, mb.size)
+                     _ptr(status), _ptr(verdict),
+                     (_lib.FLAG_IS_VALID if is_valid else 0) | (_lib.FLAG_RSA_ON_DEVICE if rsa else 0),
+                     kb.size, sb.size, mb.size)
         keep = (sch, kb, ko, sb, so, mb, mo, status, verdict, b)
         if async_:
             t = ctypes.c_uint64()
@@ -296,6 +300,26 @@ class Engine:
             self._ctx, device, scheme.data_ptr(), keys.data_ptr(), key_len.data_ptr(), sigs.data_ptr(),
             sig_len.data_ptr(), msgs.data_ptr(), msgs.shape[1], scheme.shape[0], status.data_ptr(),
             verdict.data_ptr() if verdict is not None else None, s), "cordahip_ecdsa_verify_device")
+
+    def rsa_public_op_device(self, mod, exp, inp, out, device: int = 0, stream=None):
+        """out = inp^exp mod mod per row. Device tensors: mod / inp / out [n, W] int32 (little-endian
+        words, W = 64, 96 or 128), exp [n] int32. Needs an odd modulus, exp >= 1 and inp < mod;
+        a row that breaks this comes back zero."""
+        s = stream.cuda_stream if stream is not None else 0
+        check(lib().cordahip_rsa_public_op_device(self._ctx, device, mod.data_ptr(), exp.data_ptr(), inp.data_ptr(),
+                                                  mod.shape[1], mod.shape[0], out.data_ptr(), s),
+              "cordahip_rsa_public_op_device")
+
+    def rsa_pss_verify_device(self, mod, exp, sigs, sig_len, msgs, status, verdict=None, device: int = 0,
+                              stream=None):
+        """Dense RSASSA-PSS batch in HBM: mod [n, W] int32 little-endian words, exp [n] int32,
+        sigs [n, 4 W] uint8 big-endian + sig_len [n] int16, msgs [n, L] uint8; doVerify statuses."""
+        s = stream.cuda_stream if stream is not None else 0
+        check(lib().cordahip_rsa_pss_verify_device(
+            self._ctx, device, mod.data_ptr(), exp.data_ptr(), sigs.data_ptr(), sig_len.data_ptr(),
+            msgs.data_ptr() if msgs.shape[1] else None, msgs.shape[1], mod.shape[1], mod.shape[0],
+            status.data_ptr(), verdict.data_ptr() if verdict is not None else None, s),
+            "cordahip_rsa_pss_verify_device")
 
     # ---- FilteredTransaction.verify / PartialMerkleTree.verify ----------------
     def filtered_tx_verify(self, ftxs, async_: bool = False):

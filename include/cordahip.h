@@ -68,7 +68,7 @@ extern "C" {
 /* -8 CORDAHIP_ERR_BUFFER_TOO_SMALL: see cordahip_kryo_encode */
 
 /* ---- signature schemes = Corda SignatureScheme.schemeNumberID ------------ */
-#define CORDAHIP_SCHEME_RSA_SHA256 1             /* Crypto.kt:77  (not on GPU -> UNSUPPORTED lane) */
+#define CORDAHIP_SCHEME_RSA_SHA256 1             /* Crypto.kt:77  (UNSUPPORTED lane unless CORDAHIP_FLAG_RSA_ON_DEVICE) */
 #define CORDAHIP_SCHEME_ECDSA_SECP256K1_SHA256 2 /* Crypto.kt:92  */
 #define CORDAHIP_SCHEME_ECDSA_SECP256R1_SHA256 3 /* Crypto.kt:106 */
 #define CORDAHIP_SCHEME_EDDSA_ED25519_SHA512 4   /* Crypto.kt:120 */
@@ -121,8 +121,23 @@ int cordahip_free_pinned(cordahip_ctx* ctx, void* host);
  * (Crypto.kt:534-541: no emptiness checks; an empty clear data is hashed like
  * any other message and may verify, an empty signature is MALFORMED_SIG at the
  * engine). Lanes are sharded over every context device (contiguous, 64-aligned
- * shards of each scheme's lanes; cordahip_shard_range).                      */
+ * shards of each scheme's lanes; cordahip_shard_range).
+ * CORDAHIP_FLAG_RSA_ON_DEVICE (may be or-ed in): RSA_SHA256 lanes are verified
+ * on the GPU instead of answered UNSUPPORTED. The scheme is RSASSA-PSS
+ * ("SHA256WITHRSAANDMGF1", Crypto.kt:77-88: SHA-256, MGF1-SHA-256, salt 32,
+ * trailer 0xBC) by BouncyCastle 1.57's PSSSigner rules (parity
+ * unpinned). The key is the SPKI BIT STRING payload, DER RSAPublicKey ::=
+ * SEQUENCE { modulus INTEGER, publicExponent INTEGER }, decoded strictly:
+ * anything else, or n <= 0 / e <= 0, is BAD_KEY. A key that decodes and that
+ * the GPU path declines is UNSUPPORTED and stays with the JVM: an even modulus,
+ * a modulus outside 1024..4096 bits, an even e, e < 3, e >= 2^32. Then EMPTY
+ * (doVerify rules only); every other failure is BAD_SIG (the PSS engine never
+ * throws, so MALFORMED_SIG does not occur for this scheme). Without the flag
+ * such lanes are UNSUPPORTED as before, and a context that never sees it
+ * allocates nothing for them. The signed-transaction and streaming entry
+ * points have no flags: RSA lanes there stay UNSUPPORTED.                     */
 #define CORDAHIP_FLAG_IS_VALID 1u
+#define CORDAHIP_FLAG_RSA_ON_DEVICE 2u
 typedef struct {
   uint64_t n;
   const uint8_t* scheme; /* [n] CORDAHIP_SCHEME_* */
@@ -181,6 +196,30 @@ int cordahip_ed25519_verify_host(cordahip_ctx* ctx, const uint8_t* keys, const u
 int cordahip_ecdsa_verify_device(cordahip_ctx* ctx, int device, const void* d_scheme, const void* d_keys,
                                  const void* d_key_len, const void* d_sigs, const void* d_sig_len, const void* d_msgs,
                                  uint32_t msg_len, uint64_t n, void* d_status, void* d_verdict, void* hip_stream);
+
+/* ---- dense RSA paths (device memory on `device`, enqueued on hip_stream) ------ *
+ * Rows of mod_words = 64, 96 or 128 little-endian uint32 words (moduli of up to
+ * 2048 / 3072 / 4096 bits, zero-padded to the row), one width per call; other
+ * widths are CORDAHIP_ERR_INVALID_ARG. d_exp: uint32[n]. Pointers 4-byte aligned.
+ *
+ * cordahip_rsa_public_op_device: out = in^e mod n per row, the raw public
+ * operation (a caller can build PKCS#1 v1.5 certificate checks on it). The
+ * call requires an odd modulus, e >= 1 and in < modulus; a row that violates
+ * this yields a ZERO ROW. d_out may be d_in.
+ *
+ * cordahip_rsa_pss_verify_device: RSASSA-PSS verification (the rules of
+ * CORDAHIP_FLAG_RSA_ON_DEVICE above), shaped like cordahip_ecdsa_verify_device:
+ * signatures big-endian in 4*mod_words-byte slots + sig_len[n] (uint16),
+ * messages n*msg_len. Statuses by doVerify rules (EMPTY for an empty signature
+ * or msg_len 0). A sig_len beyond the slot is BAD_SIG without reading past the
+ * slot (such a signature is longer than the modulus: parity-exact). Rows whose
+ * modulus is even or below 1024 bits, or whose exponent is even or below 3,
+ * are UNSUPPORTED. d_verdict may be NULL. */
+int cordahip_rsa_public_op_device(cordahip_ctx* ctx, int device, const void* d_mod, const void* d_exp,
+                                  const void* d_in, uint32_t mod_words, uint64_t n, void* d_out, void* hip_stream);
+int cordahip_rsa_pss_verify_device(cordahip_ctx* ctx, int device, const void* d_mod, const void* d_exp,
+                                   const void* d_sigs, const void* d_sig_len, const void* d_msgs, uint32_t msg_len,
+                                   uint32_t mod_words, uint64_t n, void* d_status, void* d_verdict, void* hip_stream);
 
 /* ---- streaming mixed-scheme drain (verifier-module queue) ----- *
  * Replaces the per-request Crypto.isValid calls a verifier would make for a

@@ -1,0 +1,189 @@
+"""RSA_SHA256 (RSASSA-PSS) throughput of the dense device path on one GPU.
+
+2^18 resident 3072-bit rows (cordahip_rsa_pss_verify_device; a handful of distinct keys,
+256 distinct CRT-made signatures tiled over the rows, 1 % of the rows corrupted), timed
+with device events over >= 20 steps after warm-up. Prints ONE JSON line:
+  verifs_per_s          rows / median step time of the whole verification
+  verify_ms             median device time of one step (prep + modexp + check kernels)
+  modexp_ms             the modular exponentiation alone (cordahip_rsa_public_op_device over
+                        the same moduli, exponents and signatures), its own timed steps
+  prep_check_ms         verify_ms - modexp_ms: the prep and PSS check kernels
+  limb_macs_per_s, fraction_of_peak
+                        32x32-bit multiply-accumulates the algorithm needs (2 W^2 per
+                        Montgomery product; products = squarings for R^2, to and from
+                        Montgomery form, one per exponent bit below the top, one per set
+                        bit below the top) over modexp_ms, against the 39.3 T limb-MAC/s
+                        peak DESIGN.md §4 uses
+  clock                 shader clock sampled beside one extra untimed step (bench.py's sampler)
+  cpu                   16 threads of OpenSSL libcrypto verifying the same rows on this box
+                        (through ctypes: the threads share the interpreter between calls, so this
+                        is a floor for the CPU, not its best), or the reason it could not run
+A run without a GPU fails; nothing falls back.
+  python tools/rsa_bench.py [--rows-log2 18] [--steps 20] [--warmup 3] [--out profiles/NAME.json]
+"""
+import argparse
+import json
+import os
+import random
+import sys
+import threading
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+
+PEAK_LIMB_MACS = 39.3e12  # 256 CU x 64 lane-MACs per CU-cycle x 2.4 GHz
+W = 96
+
+
+def products(e):
+    """Montgomery products rsa_modexp_kernel<96> runs for a wave of exponent e."""
+    sq = (32 * W & -(32 * W)).bit_length() - 1  # squarings from 2^s R to R^2 (32 W = s 2^sq)
+    top = e.bit_length() - 1
+    return sq + 1 + top + bin(e).count("1") - 1 + 1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows-log2", type=int, default=18)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--distinct", type=int, default=256)
+    ap.add_argument("--cpu-threads", type=int, default=16)
+    ap.add_argument("--cpu-rows", type=int, default=1 << 14)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+
+    import torch
+    if not torch.cuda.is_available():
+        print("rsa_bench.py: no GPU", file=sys.stderr)
+        return 2
+    import bc_rsa_pss as bc
+    from corda_amd.engine import Engine
+
+    with open(os.path.join(ROOT, "tests", "golden", "rsa_pss_vectors.json")) as f:
+        g = json.load(f)
+    keys = []
+    for k in g["keys"]:
+        if "d" in k and int(k["e"], 16) == 65537 and 2048 < int(k["n"], 16).bit_length() <= 3072:
+            keys.append({f: int(k[f], 16) for f in ("n", "e", "d", "p", "q")})
+    try:
+        import openssl_rsa_pss as ossl
+        for _ in range(2):  # a handful of keys: two more from OpenSSL where it loads
+            h, k = ossl.keygen(3072)
+            ossl.free_key(h)
+            keys.append(k)
+    except (OSError, AttributeError, AssertionError) as exc:
+        ossl = None
+        ossl_error = str(exc)
+    rng = random.Random(0xBE7C)
+    n = 1 << a.rows_log2
+    dist = []
+    for i in range(a.distinct):
+        k = keys[i % len(keys)]
+        m = rng.randbytes(32)
+        em = bc.encode_em(m, k["n"].bit_length(), rng.randbytes(32))
+        sig = bc.sign_crt(em, k["p"], k["q"], k["d"]).to_bytes((k["n"].bit_length() + 7) // 8, "big")
+        dist.append((k, sig, m))
+    mod = np.zeros((a.distinct, W), np.uint32)
+    exp = np.zeros(a.distinct, np.uint32)
+    sigs = np.zeros((a.distinct, 4 * W), np.uint8)
+    sl = np.zeros(a.distinct, np.uint16)
+    msgs = np.zeros((a.distinct, 32), np.uint8)
+    words = np.zeros((a.distinct, W), np.uint32)
+    for i, (k, sig, m) in enumerate(dist):
+        mod[i] = np.frombuffer(k["n"].to_bytes(4 * W, "little"), "<u4")
+        exp[i] = k["e"]
+        sigs[i, :len(sig)] = np.frombuffer(sig, np.uint8)
+        sl[i] = len(sig)
+        msgs[i] = np.frombuffer(m, np.uint8)
+        words[i] = np.frombuffer(int.from_bytes(sig, "big").to_bytes(4 * W, "little"), "<u4")
+    idx = np.arange(n) % a.distinct
+    bad = np.zeros(n, bool)
+    bad[rng.sample(range(n), n // 100)] = True
+    rows_sig = sigs[idx]
+    rows_sig[bad, 100] ^= 0x10  # 1 % corrupted
+    dev = torch.device("cuda:0")
+    t = lambda x, ty: torch.from_numpy(np.ascontiguousarray(x).view(ty)).to(dev)  # noqa: E731
+    tm, te, tw = t(mod[idx], np.int32), t(exp[idx], np.int32), t(words[idx], np.int32)
+    ts, tl, tg = t(rows_sig, np.uint8), t(sl[idx], np.int16), t(msgs[idx], np.uint8)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    verdict = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev)
+    out = torch.empty((n, W), dtype=torch.int32, device=dev)
+    stream = torch.cuda.Stream(device=dev)
+    res = {"workload": "rsa_pss_verify_device", "rows": n, "modulus_bits": 3072, "mod_words": W,
+           "distinct_signatures": a.distinct, "keys": len(keys), "corrupted_rows": int(bad.sum()),
+           "steps": a.steps, "warmup": a.warmup}
+    with Engine(1) as eng:
+        def verify():
+            eng.rsa_pss_verify_device(tm, te, ts, tl, tg, status, verdict, stream=stream)
+
+        def modexp():
+            eng.rsa_public_op_device(tm, te, tw, out, stream=stream)
+
+        def timed(fn):
+            for _ in range(a.warmup):
+                fn()
+            stream.synchronize()
+            ms = []
+            for _ in range(a.steps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                fn()
+                e1.record(stream)
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            return ms
+        vms = timed(verify)
+        got = status.cpu().numpy()
+        assert int((got == 0).sum()) == n - int(bad.sum()) and (got[bad] == 1).all(), "wrong statuses"
+        mms = timed(modexp)
+        v, m = float(np.median(vms)), float(np.median(mms))
+        macs = n * products(65537) * 2 * W * W
+        res.update({"verify_ms": v, "verify_ms_min": min(vms), "verify_ms_max": max(vms), "modexp_ms": m,
+                    "modexp_ms_min": min(mms), "modexp_ms_max": max(mms), "prep_check_ms": v - m,
+                    "verifs_per_s": n / (v * 1e-3), "products_per_row": products(65537),
+                    "limb_macs_per_row": products(65537) * 2 * W * W, "limb_macs_per_s": macs / (m * 1e-3),
+                    "fraction_of_peak": macs / (m * 1e-3) / PEAK_LIMB_MACS, "peak_limb_macs_per_s": PEAK_LIMB_MACS})
+        import bench
+        res["clock"] = bench._clock_under_load(0, verify, stream.synchronize, v)
+    # the same rows on the CPU: OpenSSL libcrypto on cpu-threads threads
+    if ossl is None:
+        res["cpu"] = {"error": "libcrypto did not load: " + ossl_error}
+    else:
+        per = max(1, a.cpu_rows // a.cpu_threads)
+        work = []
+        for th in range(a.cpu_threads):
+            k, _, _ = dist[th % len(dist)]
+            der = bc.encode_key(k["n"], k["e"])
+            mine = np.nonzero(idx % len(keys) == th % len(keys))[0][:per]  # this thread's key's rows
+            rows = [(bytes(rows_sig[r, :sl[idx[r]]]), bytes(msgs[idx[r]])) for r in mine]
+            work.append((der, rows))
+        counts = [0] * a.cpu_threads
+
+        def run(th):
+            counts[th] = ossl.verify_rows(*work[th])
+        threads = [threading.Thread(target=run, args=(th,)) for th in range(a.cpu_threads)]
+        t0 = time.perf_counter()
+        for th in threads:
+            th.start()
+        for th in threads:
+            th.join()
+        dt = time.perf_counter() - t0
+        total = sum(len(w[1]) for w in work)
+        res["cpu"] = {"threads": a.cpu_threads, "rows": total, "seconds": dt, "verifs_per_s": total / dt,
+                      "verified": int(sum(counts)), "library": "OpenSSL libcrypto EVP_DigestVerify through ctypes"}
+        res["gpu_over_cpu"] = res["verifs_per_s"] / res["cpu"]["verifs_per_s"]
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
