@@ -37,6 +37,8 @@ EXPORTS = [
     "cordahip_kryo_encode", "cordahip_kryo_encode_device", "cordahip_signed_txcomp_verify", "cordahip_txcomp_submit",
     "cordahip_signed_txcomp_verify_ed25519_device", "cordahip_device_mem", "cordahip_trim",
     "cordahip_rsa_public_op_device", "cordahip_rsa_pss_verify_device",
+    "cordahip_cover_eval_host", "cordahip_signed_tx_verify_covered", "cordahip_tx_submit_covered",
+    "cordahip_signed_txcomp_verify_covered", "cordahip_txcomp_submit_covered", "cordahip_tx_cover_device",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
@@ -48,6 +50,9 @@ FLAG_IS_VALID = 1  # CORDAHIP_FLAG_IS_VALID: Crypto.isValid semantics (no emptin
 FLAG_RSA_ON_DEVICE = 2  # CORDAHIP_FLAG_RSA_ON_DEVICE: RSA_SHA256 lanes verified on the GPU, not UNSUPPORTED
 RSA_GROUP_LANES = 8  # lanes that share one signature in rsa_modexp_kernel (corda_amd/csrc/rsa.hip kT)
 TX_NO_LEAVES, TX_NO_SIGNATURES, TX_BAD_TREE, TX_BAD_COMPONENT = 6, 7, 8, 9
+# required-signer coverage (cordahip_cover): tx statuses and req_status values
+TX_SIGNATURES_MISSING, TX_BAD_COVER = 10, 11
+REQ_FULFILLED, REQ_MISSING, REQ_MISSING_ALLOWED, REQ_NOT_EVALUATED, REQ_MALFORMED = 0, 1, 2, 3, 4
 
 
 class EngineUnavailable(RuntimeError):
@@ -134,6 +139,26 @@ class FilteredTxBatch(ctypes.Structure):
     ]
 
 
+class CoverTok(ctypes.Structure):
+    _fields_ = [("nchild", ctypes.c_uint32), ("weight", ctypes.c_uint32), ("threshold", ctypes.c_uint32),
+                ("key", ctypes.c_uint32)]
+
+
+class Cover(ctypes.Structure):
+    _fields_ = [
+        ("tx_req_off", ctypes.c_void_p), ("req_tok_off", ctypes.c_void_p), ("tok", ctypes.c_void_p),
+        ("req_flags", ctypes.c_void_p),
+        ("ckey_scheme", ctypes.c_void_p), ("ckey", ctypes.c_void_p), ("ckey_off", ctypes.c_void_p),
+        ("req_status", ctypes.c_void_p), ("first_missing", ctypes.c_void_p),
+        ("nreq", ctypes.c_uint64), ("ntok", ctypes.c_uint64), ("nckey", ctypes.c_uint64),
+        ("ckey_bytes", ctypes.c_uint64),
+    ]
+
+
+# numpy image of cordahip_cover_tok (16 bytes)
+COVER_TOK_DTYPE = np.dtype([("nchild", "<u4"), ("weight", "<u4"), ("threshold", "<u4"), ("key", "<u4")])
+
+
 class StreamBatch(ctypes.Structure):
     _fields_ = [
         ("n_ed", ctypes.c_uint64),
@@ -206,6 +231,15 @@ def lib() -> ctypes.CDLL:
         "cordahip_trim": (i32, [vp]),
         "cordahip_rsa_public_op_device": (i32, [vp, i32, vp, vp, vp, u32, u64, vp, vp]),
         "cordahip_rsa_pss_verify_device": (i32, [vp, i32, vp, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp]),
+        "cordahip_cover_eval_host": (i32, [ctypes.POINTER(Cover), u64, vp, vp, vp, vp, vp, u64, u64]),
+        "cordahip_signed_tx_verify_covered": (i32, [vp, ctypes.POINTER(SignedTxBatch), ctypes.POINTER(Cover)]),
+        "cordahip_tx_submit_covered": (i32, [vp, ctypes.POINTER(SignedTxBatch), ctypes.POINTER(Cover),
+                                             ctypes.POINTER(u64)]),
+        "cordahip_signed_txcomp_verify_covered": (i32, [vp, ctypes.POINTER(SignedTxcompBatch),
+                                                        ctypes.POINTER(Cover)]),
+        "cordahip_txcomp_submit_covered": (i32, [vp, ctypes.POINTER(SignedTxcompBatch), ctypes.POINTER(Cover),
+                                                 ctypes.POINTER(u64)]),
+        "cordahip_tx_cover_device": (i32, [vp, i32, u64, vp, vp, vp, vp, vp, ctypes.POINTER(Cover), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(l, name)

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "cover_core.hpp"
 #include "csr_check.hpp"
 #include "der.hpp"
 #include "kryo_core.hpp"
@@ -467,17 +468,18 @@ void device_budget(Device& d) {  // device current
 
 // Free an idle device's grow-only buffers (the idle release, cordahip_trim): both
 // buffer sets and every lock that guards a buffer, in an order every path keeps
-// (sets, then kryo_mu, stream_mu, ped_mu, ed_mu, ec_mu, each slot in order, rsa_mu); the events that fence
+// (sets, then kryo_mu, stream_mu, ped_mu, ed_mu, ec_mu, each slot in order, rsa_mu, cover_mu); the events that fence
 // device-path users (kernels on caller streams) synchronised first. The fixed
 // tables and the encoder's shape table stay (derived data, 18 MB).
 void trim_device(Device& d) {
   SetLease l0(d, 0, true), l1(d, 1, true);
   std::lock_guard<std::mutex> gk(d.kryo_mu), gs(d.stream_mu), gp(d.ped_mu), ge0(d.ed_mu[0]), ge1(d.ed_mu[1]),
-      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu);
+      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu), gv(d.cover_mu);
   if (hipSetDevice(d.id) != hipSuccess) return;
   for (hipEvent_t ev : {d.ed_ev[0], d.ed_ev[1], d.ec[0].ev, d.ec[1].ev, d.kryo_ev, d.set[0].tx_ev, d.set[1].tx_ev,
-                        d.rsa.ev})
+                        d.rsa.ev, d.cover_ev})
     if (ev) (void)hipEventSynchronize(ev);
+  d.cover_stack.release();
   d.rsa.ws.release();
   for (auto& b : d.rsa.h) b.release();
   for (auto& b : d.rsa.d) b.release();
@@ -931,7 +933,16 @@ hipError_t tx_ids_enqueue(Device& d, TxSet& S, int set_idx, const cordahip_txid_
 // signature statuses (SignedTransaction.verifySignaturesExcept -> the first
 // signature that fails, SignedTransaction.kt:95-100): first_bad_sig, and the
 // tx status becomes that signature's status.
-void reduce_txs(HostPool& pool, const cordahip_signed_tx_batch* b, uint64_t t0, uint64_t t1) {
+//
+// cover != nullptr (the _covered calls): the same worker then runs the
+// required-signer coverage of its transactions (cover_core.hpp tx_eval: the
+// second half of verifySignatures, getMissingSignatures :102-108) -- their
+// statuses and signature keys are in its cache, and the cover arrays never
+// cross PCIe to bring back one byte. A transaction is reduced exactly once
+// (the chunks' ranges and the final sweep are disjoint), which coverage needs:
+// it reads the status it may then overwrite.
+void reduce_txs(HostPool& pool, const cordahip_signed_tx_batch* b, uint64_t t0, uint64_t t1,
+                const cordahip_cover* cover = nullptr, std::atomic<bool>* cover_oom = nullptr) {
   if (t0 >= t1) return;
   pool.parallel_for(t1 - t0, 4096, [&](uint64_t x, uint64_t y) {
     for (uint64_t t = t0 + x; t < t0 + y; t++) {
@@ -952,6 +963,11 @@ void reduce_txs(HostPool& pool, const cordahip_signed_tx_batch* b, uint64_t t0, 
           break;
         }
     }
+    if (!cover) return;
+    const cover::SigKeysCsr sig{b->scheme, b->key, b->key_off};
+    cover::LocalStack stack;  // inline for trees of up to 64 tokens, the heap beyond
+    for (uint64_t t = t0 + x; t < t0 + y; t++) cover::tx_eval(*cover, t, b->tx.tx_status, b->tx_sig_off, sig, stack);
+    if (stack.failed && cover_oom) cover_oom->store(true);
   });
 }
 
@@ -987,7 +1003,7 @@ constexpr int kRedoFull = -1000;  // a templates-only component call missed: run
 
 int signed_tx_device_once(cordahip_ctx* ctx, Device& d, const cordahip_signed_tx_batch* b, uint64_t* tx_of,
                           uint64_t lo, uint64_t hi, uint64_t slices, const cordahip_txcomp_batch* comps,
-                          bool templates_only) {
+                          bool templates_only, const cordahip_cover* cover) {
   SetLease lease(d);  // S.tx (the ids) and S.pb stay ours until every gather has run
   TxSet& S = lease.get();
   const int set_idx = lease.index();
@@ -1010,6 +1026,7 @@ int signed_tx_device_once(cordahip_ctx* ctx, Device& d, const cordahip_signed_tx
     r = CORDAHIP_ERR_HIP;  // an earlier cordahip_kryo_encode_device still using the scratch
   if (r != CORDAHIP_SUCCESS) return r;
   DeviceIds di;
+  std::atomic<bool> cover_oom{false};  // a coverage worker could not get its stack (reduce_txs)
   const uint64_t s0 = b->tx_sig_off[lo], s1 = b->tx_sig_off[hi];
   // signature chunks of whole full-occupancy rounds of the Ed25519 ladder
   // (2^17 lanes: 2 waves x 1,024 SIMDs x 64), each waiting on device for the
@@ -1148,7 +1165,7 @@ int signed_tx_device_once(cordahip_ctx* ctx, Device& d, const cordahip_signed_tx
         if (hipError_t x = blocked("ids on the host", [&] { return hipEventSynchronize(ev[j]); })) return x;
       }
       const double tr = tracing() ? now_ms() : 0;
-      reduce_txs(pool_of(ctx, d), b, t0, t1);
+      reduce_txs(pool_of(ctx, d), b, t0, t1, cover, &cover_oom);
       if (tracing() && now_ms() - tr > 1.0) fprintf(stderr, "[cordahip] reduce of %llu txs %.2f ms\n",
                                                     (unsigned long long)(t1 - t0), now_ms() - tr);
       reduced.push_back({t0, t1});
@@ -1208,10 +1225,11 @@ int signed_tx_device_once(cordahip_ctx* ctx, Device& d, const cordahip_signed_tx
   std::sort(reduced.begin(), reduced.end());
   uint64_t t = lo;
   for (const auto& rg : reduced) {
-    reduce_txs(pool_of(ctx, d), b, t, rg.first);
+    reduce_txs(pool_of(ctx, d), b, t, rg.first, cover, &cover_oom);
     t = std::max(t, rg.second);
   }
-  reduce_txs(pool_of(ctx, d), b, t, hi);
+  reduce_txs(pool_of(ctx, d), b, t, hi, cover, &cover_oom);
+  if (cover_oom.load()) r = CORDAHIP_ERR_OUT_OF_MEMORY;
   if (tracing())
     fprintf(stderr, "[cordahip] dev %d signed tx tail: id streams drained %.2f ms, edge reduce %.2f ms\n", d.id,
             tr1 - tr0, now_ms() - tr1);
@@ -1227,19 +1245,21 @@ int signed_tx_device_once(cordahip_ctx* ctx, Device& d, const cordahip_signed_tx
 // then runs again with the full chain (its results overwrite every output).
 // CORDAHIP_KRYO_TEMPLATES_ONLY=0 always runs the full chain.
 int signed_tx_device(cordahip_ctx* ctx, Device& d, const cordahip_signed_tx_batch* b, uint64_t* tx_of, uint64_t lo,
-                     uint64_t hi, uint64_t slices, const cordahip_txcomp_batch* comps) {
+                     uint64_t hi, uint64_t slices, const cordahip_txcomp_batch* comps, const cordahip_cover* cover) {
   static const bool spec = [] {
     const char* v = getenv("CORDAHIP_KRYO_TEMPLATES_ONLY");
     return !(v && v[0] == '0');
   }();
-  const int r = signed_tx_device_once(ctx, d, b, tx_of, lo, hi, slices, comps, comps && spec);
+  const int r = signed_tx_device_once(ctx, d, b, tx_of, lo, hi, slices, comps, comps && spec, cover);
   if (r == kRedoFull && tracing())
     fprintf(stderr, "[cordahip] dev %d component call: templates-only chain missed, redone with the full encoder\n",
             d.id);
-  return r == kRedoFull ? signed_tx_device_once(ctx, d, b, tx_of, lo, hi, slices, comps, false) : r;
+  return r == kRedoFull ? signed_tx_device_once(ctx, d, b, tx_of, lo, hi, slices, comps, false, cover) : r;
 }
 
-int signed_tx_impl(cordahip_ctx* ctx, const cordahip_signed_tx_batch* b, const cordahip_txcomp_batch* comps = nullptr) {
+// cover != nullptr: the _covered forms (required-signer coverage after each reduce)
+int signed_tx_impl(cordahip_ctx* ctx, const cordahip_signed_tx_batch* b, const cordahip_txcomp_batch* comps = nullptr,
+                   const cordahip_cover* cover = nullptr) {
   const uint64_t ntx = b->tx.ntx;
   if (ntx == 0) return CORDAHIP_SUCCESS;
   if (!b->tx_sig_off || !b->first_bad_sig || !b->sig_status) return CORDAHIP_ERR_INVALID_ARG;
@@ -1256,6 +1276,7 @@ int signed_tx_impl(cordahip_ctx* ctx, const cordahip_signed_tx_batch* b, const c
   if (comps ? !check_txcomp_batch(par, comps) : !check_txid_batch(par, &b->tx)) return CORDAHIP_ERR_INVALID_ARG;
   if (!check_sig_level(par, ntx, b->tx_sig_off, b->nsig, b->key_off, b->key_bytes, b->sig_off, b->sig_bytes))
     return CORDAHIP_ERR_INVALID_ARG;
+  if (cover && !check_cover(par, cover, ntx)) return CORDAHIP_ERR_INVALID_ARG;
   const uint64_t nsig = b->tx_sig_off[ntx];
   if (nsig && (!b->scheme || !b->key || !b->key_off || !b->sig || !b->sig_off)) return CORDAHIP_ERR_INVALID_ARG;
   const double t0 = tracing() ? now_ms() : 0;
@@ -1296,7 +1317,7 @@ int signed_tx_impl(cordahip_ctx* ctx, const cordahip_signed_tx_batch* b, const c
   uint64_t slices = 0;
   if (const char* v = getenv("CORDAHIP_TX_SLICES")) slices = std::max<uint64_t>(1, strtoull(v, nullptr, 10));
   const int rc = for_shards(ctx->devs, ntx, 1, [&](Device& d, uint64_t lo, uint64_t hi) {
-    return signed_tx_device(ctx, d, b, tx_of, lo, hi, slices, comps);
+    return signed_tx_device(ctx, d, b, tx_of, lo, hi, slices, comps, cover);
   });
   const double t_ids = tracing() ? now_ms() : 0;
   if (rc != CORDAHIP_SUCCESS) return rc;
@@ -1309,7 +1330,7 @@ int signed_tx_impl(cordahip_ctx* ctx, const cordahip_signed_tx_batch* b, const c
 
 // cordahip_signed_txcomp_batch as the leaf-batch descriptor the pipeline reads
 // (no leaf bytes: the slices encode them on the device), plus the components
-int signed_txcomp_impl(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* cb) {
+int signed_txcomp_impl(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* cb, const cordahip_cover* cover = nullptr) {
   cordahip_signed_tx_batch b{};
   b.tx.ntx = cb->tx.ntx;
   b.tx.tx_leaf_off = cb->tx.tx_item_off;  // one leaf per component
@@ -1326,7 +1347,7 @@ int signed_txcomp_impl(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* cb
   b.nsig = cb->nsig;
   b.key_bytes = cb->key_bytes;
   b.sig_bytes = cb->sig_bytes;
-  return signed_tx_impl(ctx, &b, &cb->tx);
+  return signed_tx_impl(ctx, &b, &cb->tx, cover);
 }
 
 // C5: one device's contiguous shard of both sections, [e0, e1) Ed25519 and
@@ -1579,6 +1600,8 @@ void free_device(Device& d) {
   for (auto& b : d.rsa.h) b.release();
   for (auto& b : d.rsa.d) b.release();
   if (d.rsa.ev) (void)hipEventDestroy(d.rsa.ev);
+  d.cover_stack.release();
+  if (d.cover_ev) (void)hipEventDestroy(d.cover_ev);
   if (d.s_rsa) (void)hipStreamDestroy(d.s_rsa);
   if (d.kryo_usage) (void)hipHostFree(d.kryo_usage);
   d.kryo_usage = d.kryo_usage_dev = nullptr;
@@ -1854,6 +1877,40 @@ int cordahip_signed_txcomp_verify(cordahip_ctx* ctx, const cordahip_signed_txcom
   return guarded([&] { return signed_txcomp_impl(ctx, batch); });
 }
 
+int cordahip_signed_tx_verify_covered(cordahip_ctx* ctx, const cordahip_signed_tx_batch* batch,
+                                      const cordahip_cover* cover) {
+  if (!ctx || !batch || !cover) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return signed_tx_impl(ctx, batch, nullptr, cover); });
+}
+
+int cordahip_tx_submit_covered(cordahip_ctx* ctx, const cordahip_signed_tx_batch* batch, const cordahip_cover* cover,
+                               uint64_t* ticket) {
+  if (!ctx || !batch || !cover || !ticket) return CORDAHIP_ERR_INVALID_ARG;
+  const cordahip_signed_tx_batch copy = *batch;
+  const cordahip_cover ccopy = *cover;  // both descriptors by value; their arrays stay caller-owned
+  return guarded([&] {
+    *ticket = submit_job(ctx, [ctx, copy, ccopy] { return signed_tx_impl(ctx, &copy, nullptr, &ccopy); });
+    return CORDAHIP_SUCCESS;
+  });
+}
+
+int cordahip_signed_txcomp_verify_covered(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* batch,
+                                          const cordahip_cover* cover) {
+  if (!ctx || !batch || !cover) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return signed_txcomp_impl(ctx, batch, cover); });
+}
+
+int cordahip_txcomp_submit_covered(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* batch,
+                                   const cordahip_cover* cover, uint64_t* ticket) {
+  if (!ctx || !batch || !cover || !ticket) return CORDAHIP_ERR_INVALID_ARG;
+  const cordahip_signed_txcomp_batch copy = *batch;
+  const cordahip_cover ccopy = *cover;
+  return guarded([&] {
+    *ticket = submit_job(ctx, [ctx, copy, ccopy] { return signed_txcomp_impl(ctx, &copy, &ccopy); });
+    return CORDAHIP_SUCCESS;
+  });
+}
+
 int cordahip_txid_submit(cordahip_ctx* ctx, const cordahip_txid_batch* batch, uint64_t* ticket) {
   if (!ctx || !batch || !ticket) return CORDAHIP_ERR_INVALID_ARG;
   const cordahip_txid_batch copy = *batch;
@@ -1991,6 +2048,46 @@ int cordahip_rsa_pss_verify_device(cordahip_ctx* ctx, int device, const void* d_
                                     s);
   e = e ? e : hipEventRecord(tc->b, s);
   return hip_err(e);
+}
+
+int cordahip_tx_cover_device(cordahip_ctx* ctx, int device, uint64_t ntx, void* d_tx_status,
+                             const void* d_tx_sig_off, const void* d_sig_scheme, const void* d_sig_key,
+                             const void* d_sig_key_off, const cordahip_cover* cover, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || !cover) return CORDAHIP_ERR_INVALID_ARG;
+  if (ntx && (!d_tx_status || !d_tx_sig_off || !cover->tx_req_off || !cover->first_missing))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if (ntx && cover->nreq && (!cover->req_tok_off || !cover->req_status || (cover->ntok && !cover->tok)))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if (ntx && cover->nckey && (!cover->ckey_scheme || !cover->ckey_off || (cover->ckey_bytes && !cover->ckey)))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if (!d_sig_key_off && (reinterpret_cast<uintptr_t>(d_sig_key) & 15)) return CORDAHIP_ERR_INVALID_ARG;  // dense rows
+  return guarded([&]() -> int {
+    const Activity act(*d);
+    // the trees' evaluation stacks, one 8-byte slot per token (shared scratch:
+    // cover_mu orders the enqueues, cover_ev fences its reuse across streams)
+    std::lock_guard<std::mutex> g(d->cover_mu);
+    if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
+    if (!d->cover_ev && hipEventCreateWithFlags(&d->cover_ev, hipEventDisableTiming) != hipSuccess)
+      return CORDAHIP_ERR_HIP;
+    const uint64_t need = std::max<uint64_t>(cover->ntok, 1) * 8;
+    if (d->cover_stack.cap < need) {
+      // growing frees the old buffer: the previous user's kernel must be done
+      if (hipEventSynchronize(d->cover_ev) != hipSuccess) return CORDAHIP_ERR_HIP;
+      if (d->cover_stack.ensure(need)) return CORDAHIP_ERR_OUT_OF_MEMORY;
+    }
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    TimedCall* tc = timed_begin(*d, s);
+    if (!tc) return CORDAHIP_ERR_HIP;
+    hipError_t e = hipStreamWaitEvent(s, d->cover_ev, 0);  // the previous user of the scratch is done
+    e = e ? e : launch_tx_cover(*cover, ntx, static_cast<uint8_t*>(d_tx_status),
+                                static_cast<const uint64_t*>(d_tx_sig_off), static_cast<const uint8_t*>(d_sig_scheme),
+                                static_cast<const uint8_t*>(d_sig_key), static_cast<const uint64_t*>(d_sig_key_off),
+                                d->cover_stack.as<uint64_t>(), s);
+    e = e ? e : hipEventRecord(d->cover_ev, s);
+    e = e ? e : hipEventRecord(tc->b, s);
+    return hip_err(e);
+  });
 }
 
 double cordahip_last_kernel_ms(cordahip_ctx* ctx, int device) {

@@ -81,5 +81,23 @@ bool check_filtered_batch(Par&& par, const cordahip_filtered_tx_batch* b) {
   return csr_ok(par, b->tx_tok_off, 0, b->ntx, b->ntok);
 }
 
+// a cover (required-signer coverage): tx_req_off[0..ntx] non-decreasing and
+// within nreq, req_tok_off over the required keys it spans within ntok, the
+// whole key table's ckey_off[0..nckey] within ckey_bytes (any leaf may name any
+// entry). Token contents are data: cover_core.hpp judges them per required key.
+template <class Par>
+bool check_cover(Par&& par, const cordahip_cover* c, uint64_t ntx) {
+  if (ntx == 0) return true;
+  if (!c->tx_req_off || !c->first_missing) return false;
+  if (!csr_ok(par, c->tx_req_off, 0, ntx, c->nreq)) return false;
+  const uint64_t r0 = c->tx_req_off[0], r1 = c->tx_req_off[ntx];
+  if (r0 == r1) return true;  // no required keys: nothing else is read
+  if (!c->req_status || !c->req_tok_off || !csr_ok(par, c->req_tok_off, r0, r1, c->ntok)) return false;
+  if (c->req_tok_off[r0] != c->req_tok_off[r1] && !c->tok) return false;
+  if (c->nckey == 0) return true;  // every leaf is malformed; the table is not read
+  if (!c->ckey_scheme || !c->ckey_off || (c->ckey_bytes && !c->ckey)) return false;
+  return csr_ok(par, c->ckey_off, 0, c->nckey, c->ckey_bytes);
+}
+
 }  // namespace rt
 }  // namespace cordahip

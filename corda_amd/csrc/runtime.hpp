@@ -88,6 +88,11 @@ hipError_t launch_kryo_hash_chain(const cordahip_kryo_item* items, const uint8_t
 hipError_t launch_gather_rows32(const uint8_t* txid, const uint32_t* idx, uint64_t n, uint8_t* rows, hipStream_t s);
 hipError_t launch_tx_reduce(uint8_t* sig_status, const uint64_t* tx_sig_off, uint64_t ntx, int64_t* first_bad,
                             uint8_t* tx_status, hipStream_t s);
+// K9 (tx.hip): required-signer coverage, one lane per transaction; `c` holds device pointers.
+// sig_scheme nullptr: all Ed25519; sig_key_off nullptr: dense 32-byte key rows
+hipError_t launch_tx_cover(const cordahip_cover& c, uint64_t ntx, uint8_t* tx_status, const uint64_t* tx_sig_off,
+                           const uint8_t* sig_scheme, const uint8_t* sig_key, const uint64_t* sig_key_off,
+                           uint64_t* stack, hipStream_t s);
 hipError_t launch_pmt_verify(const uint32_t* leaf_hashes, const uint64_t* tx_leaf_off, const uint8_t* tok,
                              const uint8_t* tok_hash, const uint64_t* tx_tok_off, const uint8_t* root, uint64_t ntx,
                              uint32_t* stack, uint8_t* tx_status, hipStream_t s);
@@ -390,6 +395,11 @@ struct Device {
   uint64_t kryo_gen = 0;           // table clears so far (kryo_mu): a call's end updates kryo_templates_ok
                                    // only if no clear came after its start
   hipEvent_t kryo_ev = nullptr;
+  // cordahip_tx_cover_device: the trees' evaluation stacks (8 B per token);
+  // cover_mu orders the enqueues, cover_ev fences the scratch across streams
+  std::mutex cover_mu;
+  DevBuf cover_stack;
+  hipEvent_t cover_ev = nullptr;
 };
 
 // Fork-join pool for host-side packing and scattering. parallel_for splits

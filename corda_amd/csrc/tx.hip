@@ -1,6 +1,8 @@
 // Transaction ids and per-transaction signature verdicts for gfx950 —
 // kernels K3 (leaf hashes), K4 (Merkle roots) and K5 (per-tx reduction).
 //
+// K6 (FilteredTransaction.verify) and K9 (required-signer coverage) follow them.
+//
 // Reference path:
 //   WireTransaction.id = MerkleTree.getMerkleTree(availableComponentHashes).hash
 //     WireTransaction.kt:48,120; MerkleTransaction.kt:69
@@ -16,6 +18,7 @@
 #include <algorithm>
 #include <stdint.h>
 
+#include "cover_core.hpp"
 #include "sha2_device.hpp"
 #include "status.hpp"
 
@@ -462,6 +465,42 @@ hipError_t launch_pmt_verify(const uint32_t* leaf_hashes, const uint64_t* tx_lea
   if (!ntx) return hipSuccess;
   hipLaunchKernelGGL(pmt_verify_kernel, dim3((uint32_t)((ntx + 255) / 256)), dim3(256), 0, s, leaf_hashes,
                      tx_leaf_off, tok, tok_hash, tx_tok_off, root, ntx, stack, tx_status);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// K9: required-signer coverage, the second half of verifySignatures
+// (getMissingSignatures, SignedTransaction.kt:102-108; CompositeKey.isFulfilledBy,
+// CompositeKey.kt:186-209), launched after K5 on the same stream: one lane per
+// transaction evaluates its required keys' post-order token streams against
+// its signatures' keys (cover_core.hpp tx_eval, the code the host calls run).
+// A lane whose transaction K5 left failed only marks its entries NOT_EVALUATED.
+// A tree's evaluation stack is its own slice of `stack` (8 B per token) -- no
+// private array; a plain key (one leaf token) does not touch it. Lanes read
+// their table keys and signature keys wherever they lie: scattered 32-byte
+// reads, which is what bounds the kernel.
+template <class Sig>
+__global__ void __launch_bounds__(256) tx_cover_kernel(const cordahip_cover c, uint64_t ntx,
+                                                      uint8_t* __restrict__ tx_status,
+                                                      const uint64_t* __restrict__ tx_sig_off, const Sig sig,
+                                                      uint64_t* __restrict__ stack) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ntx) return;
+  cover::SliceStack stk{stack};
+  cover::tx_eval(c, t, tx_status, tx_sig_off, sig, stk);
+}
+
+hipError_t launch_tx_cover(const cordahip_cover& c, uint64_t ntx, uint8_t* tx_status, const uint64_t* tx_sig_off,
+                           const uint8_t* sig_scheme, const uint8_t* sig_key, const uint64_t* sig_key_off,
+                           uint64_t* stack, hipStream_t s) {
+  if (!ntx) return hipSuccess;
+  const dim3 grid((uint32_t)((ntx + 255) / 256)), block(256);
+  if (sig_key_off)
+    hipLaunchKernelGGL(tx_cover_kernel<cover::SigKeysCsr>, grid, block, 0, s, c, ntx, tx_status, tx_sig_off,
+                       cover::SigKeysCsr{sig_scheme, sig_key, sig_key_off}, stack);
+  else
+    hipLaunchKernelGGL(tx_cover_kernel<cover::SigKeysDense32>, grid, block, 0, s, c, ntx, tx_status, tx_sig_off,
+                       cover::SigKeysDense32{sig_scheme, sig_key}, stack);
   return hipGetLastError();
 }
 

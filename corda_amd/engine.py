@@ -141,9 +141,10 @@ class Engine:
         return res()
 
     def signed_tx_verify(self, txs: Sequence[Sequence[bytes]], sigs: Sequence[Sequence[tuple]],
-                         async_: bool = False):
+                         async_: bool = False, cover=None):
         """sigs[t] = [(scheme, key, sig), ...] in list order. Returns (ids, tx_status, first_bad, sig_status)
-        (or, async_, a Ticket from cordahip_tx_submit whose wait() returns them)."""
+        (or, async_, a Ticket from cordahip_tx_submit whose wait() returns them). cover: see
+        signed_tx_verify_covered."""
         b, keep = self._tx_arrays(txs)
         flat = [x for per in sigs for x in per]
         so = np.zeros(len(txs) + 1, dtype=np.uint64)
@@ -158,14 +159,53 @@ class Engine:
                                len(flat), kb.size, sb.size)
         n = len(txs)
         res = lambda: (keep[3][:n], keep[4][:n], fb[:n], sst[:len(flat)])  # noqa: E731
+        hold = (keep, so, sch, kb, ko, sb, sgo, sst, fb, sbatch)
+        if cover is not None:
+            assert cover.ntx == n
+            cs = cover.struct()
+            res = lambda: (keep[3][:n], keep[4][:n], fb[:n], sst[:len(flat)],  # noqa: E731
+                           cover.req_status, cover.first_missing[:n])
+            if async_:
+                t = ctypes.c_uint64()
+                check(lib().cordahip_tx_submit_covered(self._ctx, ctypes.byref(sbatch), ctypes.byref(cs),
+                                                       ctypes.byref(t)), "cordahip_tx_submit_covered")
+                return Ticket(self, t.value, res, (hold, cover))  # the descriptor was copied at submit
+            check(lib().cordahip_signed_tx_verify_covered(self._ctx, ctypes.byref(sbatch), ctypes.byref(cs)),
+                  "cordahip_signed_tx_verify_covered")
+            return res()
         if async_:
             t = ctypes.c_uint64()
             check(lib().cordahip_tx_submit(self._ctx, ctypes.byref(sbatch), ctypes.byref(t)), "cordahip_tx_submit")
-            return Ticket(self, t.value, res, (keep, so, sch, kb, ko, sb, sgo, sst, fb, sbatch))
+            return Ticket(self, t.value, res, hold)
         check(lib().cordahip_signed_tx_verify(self._ctx, ctypes.byref(sbatch)), "cordahip_signed_tx_verify")
         return res()
 
-    def signed_txcomp_verify(self, txs, sigs, async_: bool = False):
+    def signed_tx_verify_covered(self, txs, sigs, cover, async_: bool = False):
+        """cordahip_signed_tx_verify_covered / cordahip_tx_submit_covered: signed_tx_verify followed by
+        the required-signer coverage of `cover` (a cover.CoverArrays, e.g. cover.flatten(must_sign,
+        sigs)) -- the whole of verifySignatures. Returns (ids, tx_status, first_bad, sig_status,
+        req_status, first_missing); the last two are cover's own output arrays."""
+        return self.signed_tx_verify(txs, sigs, async_=async_, cover=cover)
+
+    def signed_txcomp_verify_covered(self, txs, sigs, cover, async_: bool = False):
+        """cordahip_signed_txcomp_verify_covered / cordahip_txcomp_submit_covered: as
+        signed_tx_verify_covered, over components (signed_txcomp_verify's txs)."""
+        return self.signed_txcomp_verify(txs, sigs, async_=async_, cover=cover)
+
+    def tx_cover_device(self, ntx: int, tx_status, tx_sig_off, sig_key, cover_struct, sig_scheme=None,
+                        sig_key_off=None, device: int = 0, stream=None):
+        """cordahip_tx_cover_device: the coverage kernel on `stream`, after a *_ed25519_device
+        signed-tx call that left tx_status / tx_sig_off / its keys (sig_key) in HBM. cover_struct: a
+        _lib.Cover with device pointers (CoverArrays.to_device). sig_scheme None: all Ed25519;
+        sig_key_off None: sig_key holds dense 32-byte rows."""
+        s = stream.cuda_stream if stream is not None else 0
+        check(lib().cordahip_tx_cover_device(
+            self._ctx, device, ntx, tx_status.data_ptr(), tx_sig_off.data_ptr(),
+            sig_scheme.data_ptr() if sig_scheme is not None else None, sig_key.data_ptr(),
+            sig_key_off.data_ptr() if sig_key_off is not None else None, ctypes.byref(cover_struct), s),
+            "cordahip_tx_cover_device")
+
+    def signed_txcomp_verify(self, txs, sigs, async_: bool = False, cover=None):
         """cordahip_signed_txcomp_verify / cordahip_txcomp_submit: txs[t] = the transaction's components
         as (kind, value, class_id) tuples (_lib.kryo_pack's form, availableComponents order) -- the GPU
         writes their leaves; sigs as in signed_tx_verify. Returns (ids, tx_status, first_bad, sig_status)."""
@@ -176,10 +216,11 @@ class Engine:
         tio = np.zeros(len(txs) + 1, dtype=np.uint64)
         if txs:
             tio[1:] = np.cumsum([len(tx) for tx in txs], dtype=np.uint64)
-        return self.signed_txcomp_verify_arrays(np.ascontiguousarray(blob), items, tio, sigs, async_=async_)
+        return self.signed_txcomp_verify_arrays(np.ascontiguousarray(blob), items, tio, sigs, async_=async_,
+                                                cover=cover)
 
     def signed_txcomp_verify_arrays(self, payload, items, tx_item_off, sigs, async_: bool = False,
-                                    pinned_out: bool = False):
+                                    pinned_out: bool = False, cover=None):
         """The array form: payload uint8, items KRYO_ITEM_DTYPE whose `data` are offsets into payload,
         tx_item_off uint64[ntx + 1]; sigs[t] = [(scheme, key, sig), ...]. pinned_out: txid and
         tx_status in page-locked memory (the library's kernels then store them through their
@@ -212,6 +253,19 @@ class Engine:
                                    _ptr(fb), len(flat), kb.size, sb.size)
         res = lambda: (txid[:n], st[:n], fb[:n], sst[:len(flat)])  # noqa: E731
         keep = (payload, items, tio, txid, st, so, sch, kb, ko, sb, sgo, sst, fb, tb, sbatch, pins)
+        if cover is not None:  # the _covered forms: results grow by (req_status, first_missing)
+            assert cover.ntx == n
+            cs = cover.struct()
+            res = lambda: (txid[:n], st[:n], fb[:n], sst[:len(flat)],  # noqa: E731
+                           cover.req_status, cover.first_missing[:n])
+            if async_:
+                t = ctypes.c_uint64()
+                check(lib().cordahip_txcomp_submit_covered(self._ctx, ctypes.byref(sbatch), ctypes.byref(cs),
+                                                           ctypes.byref(t)), "cordahip_txcomp_submit_covered")
+                return Ticket(self, t.value, res, (keep, cover))
+            check(lib().cordahip_signed_txcomp_verify_covered(self._ctx, ctypes.byref(sbatch), ctypes.byref(cs)),
+                  "cordahip_signed_txcomp_verify_covered")
+            return res()
         if async_:
             t = ctypes.c_uint64()
             check(lib().cordahip_txcomp_submit(self._ctx, ctypes.byref(sbatch), ctypes.byref(t)),

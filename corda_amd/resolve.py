@@ -30,6 +30,8 @@ from typing import Callable, List, Optional, Sequence, Tuple, Union
 # per-lane statuses of include/cordahip.h
 OK, BAD_SIG, MALFORMED_SIG, BAD_KEY, UNSUPPORTED, EMPTY = 0, 1, 2, 3, 4, 5
 TX_NO_LEAVES, TX_NO_SIGNATURES = 6, 7
+TX_SIGNATURES_MISSING, TX_BAD_COVER = 10, 11  # required-signer coverage (cordahip_cover)
+REQ_MISSING = 1
 
 
 class SignatureException(Exception):
@@ -158,6 +160,41 @@ def verify_signatures_batch(engine, stxs: Sequence[SignedTx], allowed_to_be_miss
             out.append(Outcome(tid, SignaturesMissingException(needed, missing_key_descriptions(stx, needed), tid)))
             continue
         out.append(Outcome(tid, None))
+    return out
+
+
+def verify_signatures_batch_covered(engine, stxs: Sequence[SignedTx], allowed_to_be_missing=()) -> List[Outcome]:
+    """verify_signatures_batch with getMissingSignatures (:102-108) done by the library too
+    (engine.signed_tx_verify_covered: one call is the whole of verifySignatures). Only the set
+    semantics (.toSet(), list order kept) and the descriptions are rebuilt here, from
+    req_status. A required key that CompositeKey.checkValidity (CompositeKey.kt:110-122)
+    rejects is an IllegalArgumentException, thrown before any missing set exists."""
+    if not stxs:
+        return []
+    from . import cover as C
+    cov = C.flatten([s.must_sign for s in stxs], [s.sigs for s in stxs], allowed_to_be_missing)
+    ids, tx_st, first_bad, _, req_st, _ = engine.signed_tx_verify_covered([s.components for s in stxs],
+                                                                         [s.sigs for s in stxs], cov)
+    out = []
+    for t, stx in enumerate(stxs):
+        st = int(tx_st[t])
+        if st == TX_NO_SIGNATURES:
+            out.append(Outcome(None, IllegalArgumentException("Failed requirement.")))
+            continue
+        if st == TX_NO_LEAVES:
+            out.append(Outcome(None, MerkleTreeException("Cannot calculate Merkle root on empty hash list.")))
+            continue
+        tid = bytes(ids[t])
+        if st == TX_BAD_COVER:
+            out.append(Outcome(tid, IllegalArgumentException("invalid CompositeKey")))
+        elif st == TX_SIGNATURES_MISSING:
+            r0 = int(cov.tx_req_off[t])
+            needed = list(dict.fromkeys(k for i, k in enumerate(stx.must_sign) if req_st[r0 + i] == REQ_MISSING))
+            out.append(Outcome(tid, SignaturesMissingException(needed, missing_key_descriptions(stx, needed), tid)))
+        elif st != OK:
+            out.append(Outcome(tid, _lane_exception(st), int(first_bad[t])))
+        else:
+            out.append(Outcome(tid, None))
     return out
 
 

@@ -21,10 +21,14 @@
  *   cordahip_signed_tx_verify / cordahip_tx_submit
  *       -> SignedTransaction.checkSignaturesAreValid (SignedTransaction.kt:95-100)
  *          + the tx.id recomputation of verifySignatures (:70-85); signer coverage
- *          (getMissingSignatures :102-108) stays with the caller, see INTEGRATION.md.
+ *          (getMissingSignatures :102-108) is the _covered forms below.
  *          The _submit forms return a ticket at once: the caller (a Quasar fiber in
  *          ResolveTransactionsFlow.call, ResolveTransactionsFlow.kt:97-122, on the
  *          single Node thread) suspends on it instead of blocking the thread.
+ *   cordahip_*_covered / cordahip_tx_cover_device / cordahip_cover_eval_host
+ *       -> SignedTransaction.getMissingSignatures (SignedTransaction.kt:102-108),
+ *          CompositeKey.isFulfilledBy (CompositeKey.kt:186-209) and the
+ *          SignaturesMissingException decision of verifySignatures (:76-82)
  *
  * Result contract: a return value < 0 means the whole call failed (the caller
  * falls back to the JVM path for that batch); per-lane outcomes are DATA in
@@ -292,7 +296,8 @@ int cordahip_tx_ids(cordahip_ctx* ctx, const cordahip_txid_batch* batch);
  * signature is verified over its transaction's recomputed id; first_bad_sig[t]
  * is the index (within tx t, list order) of the signature whose exception the
  * reference would throw first, -1 if none. Signer coverage
- * (getMissingSignatures, CompositeKey.isFulfilledBy) stays with the caller. */
+ * (getMissingSignatures, CompositeKey.isFulfilledBy): the _covered forms and
+ * cordahip_tx_cover_device below ("required-signer coverage"). */
 typedef struct {
   cordahip_txid_batch tx;
   const uint64_t* tx_sig_off; /* [ntx+1] signatures of tx t */
@@ -544,6 +549,138 @@ int cordahip_signed_txcomp_verify_ed25519_device(cordahip_ctx* ctx, int device, 
                                                  const void* d_tx_sig_off, const void* d_keys, const void* d_sigs,
                                                  uint64_t nsig, void* d_txid, void* d_tx_status, void* d_first_bad,
                                                  void* d_sig_status, void* hip_stream);
+
+/* ---- required-signer coverage (the second half of verifySignatures) ---------- *
+ * SignedTransaction.verifySignatures (SignedTransaction.kt:70-85) is
+ * checkSignaturesAreValid (:95-100, the calls above) and then
+ *   getMissingSignatures (:102-108): tx.mustSign.filter { !it.isFulfilledBy(sigKeys) }
+ *   PublicKey.isFulfilledBy          CryptoUtils.kt:79-82
+ *   CompositeKey.isFulfilledBy       CompositeKey.kt:186-209 (threshold trees)
+ *   missing - allowedToBeMissing, SignaturesMissingException (:76-82).
+ * A cordahip_cover carries every transaction's required keys (tx.mustSign, list
+ * order); the library answers per required key (req_status) and per transaction
+ * (tx_status, first_missing). The .toSet() de-duplication of the missing keys
+ * and getMissingKeyDescriptions (:114-124) stay with the caller: both are read
+ * off req_status.
+ *
+ * A required key is a POST-ORDER token stream: a leaf pushes one value, a node
+ * with nchild children takes the nchild values before it. A plain PublicKey is
+ * one leaf token. Leaves index a key table (ckey_scheme / ckey / ckey_off) whose
+ * entries any number of leaves, of any transaction, may share.
+ *
+ * Leaf fulfilment: a leaf is fulfilled iff some signature of the SAME
+ * transaction has the same scheme byte, the same key length and the same key
+ * bytes (keysToCheck.contains(node), CompositeKey.kt:192). The scheme takes part
+ * in the comparison: the same 33 or 65 bytes under secp256k1 and secp256r1 are
+ * different keys. The caller supplies ONE canonical encoding on both sides (the
+ * signature's key and the table's): the compressed and the uncompressed SEC1
+ * form of one point are equal for BCECPublicKey.equals but NOT here.
+ * Node fulfilment: a node is fulfilled iff the summed weights of its fulfilled
+ * children are >= threshold (checkFulfilledBy, CompositeKey.kt:186-196).
+ * The root's own weight is ignored.
+ *
+ * A required key is CORDAHIP_REQ_MALFORMED when CompositeKey.checkValidity
+ * (:110-122) would throw from checkConstraints (:73-85) / totalWeight
+ * (:126-133), or when the stream is no tree:
+ *   - an empty token range;
+ *   - a stream that does not reduce to exactly one value;
+ *   - a node with nchild == 1 (:77), or with more children than there are
+ *     values before it;
+ *   - a threshold of 0 (:79), or above the children's total weight (:82);
+ *   - a child weight of 0 (:129); a weight or threshold above 2^31 - 1 is not a
+ *     Java positive Int and counts as non-positive;
+ *   - a total weight above 2^31 - 1 (Math.addExact, :130);
+ *   - a leaf whose key >= nckey.
+ * Duplicate children (:74) are NOT looked for: that needs structural subtree
+ * equality, and the JVM's CompositeKey constructor has already enforced it.
+ * Cycles cannot be expressed in a token stream.
+ *
+ * Per transaction, in this order:
+ *   1. tx_status[t] != OK on entry (NO_SIGNATURES, NO_LEAVES, BAD_COMPONENT or
+ *      any signature's status): its entries are NOT_EVALUATED, tx_status[t] is
+ *      unchanged, first_missing[t] = -1.
+ *   2. Otherwise every entry is evaluated on its own.
+ *   3. Any MALFORMED entry: tx_status[t] = CORDAHIP_TX_BAD_COVER and
+ *      first_missing[t] = the first malformed entry (filter runs to the end, so
+ *      the first invalid key throws before any missing set is built).
+ *   4. Otherwise any MISSING entry: CORDAHIP_TX_SIGNATURES_MISSING and
+ *      first_missing[t] = the first MISSING entry; MISSING_ALLOWED entries do
+ *      not count.
+ *   5. Otherwise OK. A transaction without required keys is OK.
+ * tx_req_off, req_tok_off and ckey_off are CSR arrays, checked as every CSR array
+ * of this header is (within nreq / ntok / ckey_bytes, non-decreasing, whole,
+ * before any enqueue: CORDAHIP_ERR_INVALID_ARG, the context stays usable).     */
+#define CORDAHIP_TX_SIGNATURES_MISSING 10 /* SignaturesMissingException (SignedTransaction.kt:81) */
+#define CORDAHIP_TX_BAD_COVER 11          /* IllegalArgumentException from CompositeKey.checkValidity (:110-122) */
+
+/* req_status[r] */
+#define CORDAHIP_REQ_FULFILLED 0
+#define CORDAHIP_REQ_MISSING 1
+#define CORDAHIP_REQ_MISSING_ALLOWED 2 /* missing, but the caller flagged it allowedToBeMissing */
+#define CORDAHIP_REQ_NOT_EVALUATED 3   /* the tx had already failed (id or a signature) */
+#define CORDAHIP_REQ_MALFORMED 4
+
+typedef struct {      /* 16 bytes; one required key = a POST-ORDER token stream */
+  uint32_t nchild;    /* 0: leaf; >= 2: CompositeKey node over the nchild subtrees before it */
+  uint32_t weight;    /* this node's weight in its parent (ignored at the root) */
+  uint32_t threshold; /* nodes only */
+  uint32_t key;       /* leaves only: index into the cover key table */
+} cordahip_cover_tok;
+
+typedef struct {
+  const uint64_t* tx_req_off;    /* [ntx+1] required keys (tx.mustSign entries, list order) of tx t */
+  const uint64_t* req_tok_off;   /* [nreq+1] tokens of required key r */
+  const cordahip_cover_tok* tok; /* [ntok] */
+  const uint8_t* req_flags;      /* [nreq] bit 0: allowed to be missing; NULL = none */
+  const uint8_t* ckey_scheme;    /* [nckey] CORDAHIP_SCHEME_* */
+  const uint8_t* ckey;           /* key table, CSR; entries may be shared by any number of leaves */
+  const uint64_t* ckey_off;      /* [nckey+1] */
+  uint8_t* req_status;           /* [nreq] out */
+  int64_t* first_missing;        /* [ntx] out: index within tx t's required keys, -1 if none */
+  uint64_t nreq, ntok, nckey, ckey_bytes;
+} cordahip_cover;
+
+/* The rule alone, on the host: no context, no device work (the JVM's fallback
+ * path, and what the device kernel is tested against). tx_status [ntx] in/out
+ * as described above; the signature keys as in cordahip_signed_tx_batch
+ * (tx_sig_off [ntx+1] within nsig, scheme [nsig], key / key_off CSR within
+ * key_bytes), checked like the cover's own arrays. */
+int cordahip_cover_eval_host(const cordahip_cover* cover, uint64_t ntx, uint8_t* tx_status,
+                             const uint64_t* tx_sig_off, const uint8_t* scheme, const uint8_t* key,
+                             const uint64_t* key_off, uint64_t nsig, uint64_t key_bytes);
+
+/* cordahip_signed_tx_verify / cordahip_tx_submit / cordahip_signed_txcomp_verify
+ * / cordahip_txcomp_submit followed by the coverage rule: the whole of
+ * verifySignatures in one call. Coverage runs on the host threads next to each
+ * device, over the same transaction ranges and directly after the
+ * per-transaction reduce -- the signature keys and statuses are in host memory
+ * there already. The ticketed forms copy the cover descriptor at submit, as
+ * they copy the batch descriptor; its arrays stay the caller's until wait. */
+int cordahip_signed_tx_verify_covered(cordahip_ctx* ctx, const cordahip_signed_tx_batch* batch,
+                                      const cordahip_cover* cover);
+int cordahip_tx_submit_covered(cordahip_ctx* ctx, const cordahip_signed_tx_batch* batch, const cordahip_cover* cover,
+                               uint64_t* ticket);
+int cordahip_signed_txcomp_verify_covered(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* batch,
+                                          const cordahip_cover* cover);
+int cordahip_txcomp_submit_covered(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* batch,
+                                   const cordahip_cover* cover, uint64_t* ticket);
+
+/* The device-resident form: `cover` is a HOST struct whose pointers are DEVICE
+ * memory on `device`, d_tx_status [ntx] in/out. Stream-ordered: enqueue it on
+ * the stream of cordahip_signed_tx_verify_ed25519_device /
+ * cordahip_signed_txcomp_verify_ed25519_device right after that call, with the
+ * same d_tx_status / d_tx_sig_off / d_keys, and the verdict of verifySignatures
+ * never leaves the device. d_sig_scheme NULL: every signature is Ed25519;
+ * d_sig_key_off NULL: d_sig_key holds dense 32-byte rows (16-byte aligned),
+ * else CSR keys. One lane per transaction; lanes do scattered reads of their
+ * keys. The offset arrays in device memory are the caller's contract, as for
+ * the other device calls (an offset beyond its level's declared count makes
+ * the transaction BAD_COVER rather than a read outside the arrays); token
+ * contents are data and checked. Device scratch (grow-only, per device,
+ * released by cordahip_trim and the idle release): 8 B per token. */
+int cordahip_tx_cover_device(cordahip_ctx* ctx, int device, uint64_t ntx, void* d_tx_status,
+                             const void* d_tx_sig_off, const void* d_sig_scheme, const void* d_sig_key,
+                             const void* d_sig_key_off, const cordahip_cover* cover, void* hip_stream);
 
 /* Device time (ms) of the calling thread's most recent *_device call on
  * `device`, from HIP events recorded around its launches on the stream it ran
