@@ -11,16 +11,17 @@
 // worker pool. The fixed-base tables are built once per device at init by a
 // kernel. There is no CPU verification fallback: a HIP failure is returned to
 // the caller as CORDAHIP_ERR_HIP. The generic CSR signature batch lives in
-// host_batch.cpp; the shared runtime types in runtime.hpp.
+// host_batch.cpp; the shared runtime types in runtime.hpp; the per-device runtime
+// (pools, streams, budget, enqueue helpers, idle release, init / shutdown) in
+// runtime.cpp.
 #include <hip/hip_runtime.h>
-#include <pthread.h>
-#include <sched.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <tuple>
 
 #include "cover_core.hpp"
 #include "csr_check.hpp"
@@ -32,236 +33,18 @@
 using namespace cordahip;
 using namespace cordahip::rt;
 
-namespace cordahip {
-namespace rt {
-
-// ---- host fork-join pool -----------------------------------------------------
-HostPool::HostPool(int nthreads, const std::vector<int>& cpus) {
-  for (int i = 1; i < nthreads; i++) {
-    threads_.emplace_back([this] { worker(); });
-    if (!cpus.empty()) {  // the device's node: its rows are packed next to its GPU
-      cpu_set_t cs;
-      CPU_ZERO(&cs);
-      for (int c : cpus)
-        if (c >= 0 && c < CPU_SETSIZE) CPU_SET(c, &cs);
-      (void)pthread_setaffinity_np(threads_.back().native_handle(), sizeof(cs), &cs);
-    }
-  }
-}
-
-NodeBind::NodeBind(const Device& d) {
-  if (d.place.cpus.empty()) return;
-  cpu_set_t old, cs;
-  if (pthread_getaffinity_np(pthread_self(), sizeof(old), &old) != 0) return;
-  CPU_ZERO(&cs);
-  for (int c : d.place.cpus)
-    if (c >= 0 && c < CPU_SETSIZE) CPU_SET(c, &cs);
-  if (CPU_EQUAL(&cs, &old) || pthread_setaffinity_np(pthread_self(), sizeof(cs), &cs) != 0) return;
-  saved_.assign(reinterpret_cast<unsigned char*>(&old), reinterpret_cast<unsigned char*>(&old) + sizeof(old));
-  bound_ = true;
-}
-
-NodeBind::~NodeBind() {
-  if (bound_) (void)pthread_setaffinity_np(pthread_self(), sizeof(cpu_set_t), reinterpret_cast<cpu_set_t*>(saved_.data()));
-}
-
-HostPool& pool_of(cordahip_ctx* ctx, Device& d) { return d.pool ? *d.pool : *ctx->host; }
-
-MemAcct& mem_acct(int dev) {
-  static MemAcct acct[kMaxHipDevices];
-  return acct[dev >= 0 && dev < kMaxHipDevices ? dev : 0];
-}
-
-HostPool::~HostPool() {
-  {
-    std::lock_guard<std::mutex> g(m_);
-    stop_ = true;
-  }
-  cv_.notify_all();
-  for (auto& t : threads_) t.join();
-}
-
-void HostPool::run_pieces(Job& j) {
-  for (;;) {
-    const uint64_t k = j.next.fetch_add(1);
-    if (k >= j.npieces) return;
-    const uint64_t lo = k * j.piece, hi = std::min(j.n, lo + j.piece);
-    (*j.fn)(lo, hi);
-    if (j.done.fetch_add(1) + 1 == j.npieces) {
-      std::lock_guard<std::mutex> g(j.m);
-      j.cv.notify_all();
-    }
-  }
-}
-
-void HostPool::worker() {
-  for (;;) {
-    std::shared_ptr<Job> j;
-    {
-      std::unique_lock<std::mutex> g(m_);
-      for (;;) {
-        while (!q_.empty() && q_.front()->next.load() >= q_.front()->npieces) q_.pop_front();  // exhausted
-        if (!q_.empty()) {
-          j = q_.front();
-          break;
-        }
-        if (stop_) return;
-        cv_.wait(g);
-      }
-    }
-    run_pieces(*j);
-  }
-}
-
-void HostPool::parallel_for(uint64_t n, uint64_t grain, const std::function<void(uint64_t, uint64_t)>& fn) {
-  if (n == 0) return;
-  grain = std::max<uint64_t>(grain, 1);
-  const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>((n + grain - 1) / grain, 4 * (uint64_t)threads()));
-  if (want == 1 || threads_.empty()) {
-    fn(0, n);
-    return;
-  }
-  auto j = std::make_shared<Job>();
-  j->fn = &fn;
-  j->n = n;
-  j->piece = (n + want - 1) / want;
-  j->npieces = (n + j->piece - 1) / j->piece;
-  {
-    std::lock_guard<std::mutex> g(m_);
-    q_.push_back(j);
-  }
-  cv_.notify_all();
-  run_pieces(*j);
-  {
-    std::unique_lock<std::mutex> g(j->m);
-    j->cv.wait(g, [&] { return j->done.load() == j->npieces; });
-  }
-  std::lock_guard<std::mutex> g(m_);  // drop it if no worker got to pop it
-  for (auto it = q_.begin(); it != q_.end(); ++it)
-    if (*it == j) {
-      q_.erase(it);
-      break;
-    }
-}
-
-// ---- ticket pool ---------------------------------------------------------------
-WorkerPool::WorkerPool(int nthreads) {
-  for (int i = 0; i < nthreads; i++) threads_.emplace_back([this] { run(); });
-}
-
-WorkerPool::~WorkerPool() {
-  {
-    std::lock_guard<std::mutex> g(m_);
-    stop_ = true;
-  }
-  cv_.notify_all();
-  for (auto& t : threads_) t.join();
-}
-
-void WorkerPool::push(std::shared_ptr<JobState> st, std::function<int()> fn) {
-  {
-    std::lock_guard<std::mutex> g(m_);
-    q_.emplace_back(std::move(st), std::move(fn));
-  }
-  cv_.notify_one();
-}
-
-void WorkerPool::run() {
-  for (;;) {
-    std::pair<std::shared_ptr<JobState>, std::function<int()>> job;
-    {
-      std::unique_lock<std::mutex> g(m_);
-      cv_.wait(g, [this] { return stop_ || !q_.empty(); });
-      if (q_.empty()) return;  // stop_ and drained: queued jobs always run
-      job = std::move(q_.front());
-      q_.pop_front();
-    }
-    int rc;
-    try {
-      rc = job.second();
-    } catch (...) {
-      rc = CORDAHIP_ERR_OUT_OF_MEMORY;  // std::bad_alloc from host staging vectors
-    }
-    {
-      std::lock_guard<std::mutex> g(job.first->m);
-      job.first->rc = rc;
-      job.first->done = true;
-    }
-    job.first->cv.notify_all();
-  }
-}
-
-int hip_err(hipError_t e) { return e == hipSuccess ? CORDAHIP_SUCCESS : CORDAHIP_ERR_HIP; }
-
-hipError_t ensure_streams(Device& d) {
-  std::lock_guard<std::mutex> g(d.streams_mu);
-  if (d.s_copy) return hipSuccess;
-  // Every pipeline stream needs a hardware queue of its own: streams sharing a
-  // queue serialise, and a copy enqueued early (the tx-id slices' leaf bytes,
-  // a C5 chunk waiting for its stage) then holds back every later kernel of the
-  // other stream. HIP hands out pool queues (GPU_MAX_HW_QUEUES, 4 on the box)
-  // round-robin over every stream of the process, so a 4th pipeline stream
-  // shared one with s_ed or s_copy depending on creation order (c4h 45.1 M
-  // sigs/s, or C5 84.6 instead of 95.8 M/s: profiles/r03_stream_queues.json). A
-  // stream created with a CU mask (here: all CUs) gets a dedicated queue; the
-  // ECDSA stream keeps the higher priority, which also gives it a queue of its
-  // own (at normal priority it shared s_ed's and the two sections ran back to back).
-  int lo = 0, hi = 0, ncu = 0;
-  hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-  e = e ? e : hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d.id);
-  std::vector<uint32_t> all((std::max(ncu, 1) + 31) / 32, 0xffffffffu);
-  auto dedicated = [&](hipStream_t* st) { return hipExtStreamCreateWithCUMask(st, (uint32_t)all.size(), all.data()); };
-  hipStream_t c = nullptr, x = nullptr, y = nullptr, z = nullptr, x2 = nullptr;
-  e = e ? e : dedicated(&c);
-  e = e ? e : dedicated(&x);
-  e = e ? e : hipStreamCreateWithPriority(&y, hipStreamNonBlocking, hi);
-  e = e ? e : dedicated(&z);
-  e = e ? e : dedicated(&x2);
-  if (e != hipSuccess) {
-    for (hipStream_t s : {c, x, y, z, x2})
-      if (s) (void)hipStreamDestroy(s);
-    return e;
-  }
-  d.s_ed = x;
-  d.s_ed2 = x2;
-  d.s_ec = y;
-  // generic batches' alternate ECDSA chunks run on the id-copy stream, idle in those
-  // batches (no sixth hardware queue)
-  d.s_ec2 = z;
-  d.s_idcopy = z;
-  d.s_copy = c;
-  return hipSuccess;
-}
-
-// Launch-pair sizes of the split kernels = the largest workspace per device.
-// Bigger launches pay fewer end-of-grid tails (C2, measured: 2^18 91.5, 2^20
-// 93.2, 2^22 96.4, 2^24 97.2 M verifs/s): a 2^24-lane batch runs as ONE
-// prep/ladder pair over 54 GB of HBM (19% of the MI355X's 288 GB). Smaller
-// batches allocate only what they use (grow-only, from 2^18 lanes up).
-constexpr uint64_t kEdWsLanes = 1ull << 24;  // x 3,200 B = 54 GB of Ed25519 workspace at most
-constexpr uint64_t kEcWsSlots = 1ull << 24;  // x 1,120 B = 18.8 GB of ECDSA workspace at most
-constexpr uint64_t kWsMinLanes = 1ull << 18;
-
-// Workspace-size overrides (multiples of 64): tests use them to force the
-// multi-chunk paths (several prep/ladder launch sets per batch) at small sizes.
-uint64_t env_lanes(const char* name, uint64_t dflt) {
-  const char* v = getenv(name);
-  const uint64_t x = v ? strtoull(v, nullptr, 10) : 0;
-  return x >= 64 ? x / 64 * 64 : dflt;
-}
+namespace {
 
 // a zeroed 64-byte host-mapped buffer (the encoder's usage reports)
-hipError_t usage_buffer(uint32_t*& h, uint32_t*& dp) {
-  if (h) return hipSuccess;
-  void* hp = nullptr;
+hipError_t usage_buffer(PinBuf& h, uint32_t*& dp) {
+  if (h.p) return hipSuccess;
   void* dv = nullptr;
-  if (hipHostMalloc(&hp, 64, hipHostMallocMapped) != hipSuccess) return hipErrorOutOfMemory;
-  if (hipHostGetDevicePointer(&dv, hp, 0) != hipSuccess) {
-    (void)hipHostFree(hp);
+  if (h.ensure(64, hipHostMallocMapped) != hipSuccess) return hipErrorOutOfMemory;
+  if (hipHostGetDevicePointer(&dv, h.p, 0) != hipSuccess) {
+    h.release();
     return hipErrorUnknown;
   }
-  std::memset(hp, 0, 64);
-  h = static_cast<uint32_t*>(hp);
+  std::memset(h.p, 0, 64);
   dp = static_cast<uint32_t*>(dv);
   return hipSuccess;
 }
@@ -277,10 +60,9 @@ hipError_t usage_buffer(uint32_t*& h, uint32_t*& dp) {
 hipError_t kryo_state_ready(Device& d, hipStream_t s) {
   if (hipError_t e = usage_buffer(d.kryo_usage, d.kryo_usage_dev)) return e;
   uint32_t templates = 0, slots = 0;
-  for (const uint32_t* p : {(const uint32_t*)d.kryo_usage, (const uint32_t*)d.set[0].kryo_usage,
-                            (const uint32_t*)d.set[1].kryo_usage})
-    if (p) {
-      const volatile uint32_t* u = p;
+  for (const PinBuf* b : {&d.kryo_usage, &d.set[0].kryo_usage, &d.set[1].kryo_usage})
+    if (b->p) {
+      const volatile uint32_t* u = b->as<uint32_t>();
       templates = std::max<uint32_t>(templates, (uint32_t)u[0]);
       slots = std::max<uint32_t>(slots, (uint32_t)u[1]);
     }
@@ -288,8 +70,8 @@ hipError_t kryo_state_ready(Device& d, hipStream_t s) {
     d.kryo_fresh = false;
     d.kryo_templates_ok = false;  // an empty table: the next component batch builds its shapes
     d.kryo_gen++;                 // a call that started before the clear does not vouch for the new table
-    for (uint32_t* p : {d.kryo_usage, d.set[0].kryo_usage, d.set[1].kryo_usage})
-      if (p) p[0] = p[1] = 0;
+    for (const PinBuf* b : {&d.kryo_usage, &d.set[0].kryo_usage, &d.set[1].kryo_usage})
+      if (uint32_t* p = b->as<uint32_t>()) p[0] = p[1] = 0;
     return kryo_clear(d.kryo_fixed.as<uint8_t>(), s);
   }
   return hipSuccess;
@@ -300,240 +82,23 @@ hipError_t kryo_usage_report(Device& d, TxSet* set, hipStream_t s) {
   return launch_store_to_host(kryo_usage_src(d.kryo_fixed.as<uint8_t>()),
                               set ? set->kryo_usage_dev : d.kryo_usage_dev, kKryoUsageBytes, s);
 }
-// grows kryo_fixed if needed (once: its size is fixed), marking it fresh
-hipError_t kryo_fixed_ensure(Device& d) {
-  if (d.kryo_fixed.cap >= kryo_fixed_scratch_bytes()) return hipSuccess;
-  d.kryo_fresh = true;
-  return d.kryo_fixed.ensure(kryo_fixed_scratch_bytes());
+// The encoder's scratch for n items (kryo_mu held, device current): leaf sizes, item
+// slots, the direct writers' level buffers, the fixed part (once: its size is fixed;
+// marked fresh) and, for the calls that write leaves, temp_bytes of scan storage
+// (0: left as it is). kryo_ev fences all of it.
+constexpr uint64_t kKryoDirectWriters = 1u << 13;  // 2^13 threads, 7 KB of level buffers each (56 MB)
+hipError_t kryo_scratch_ensure(Device& d, uint64_t n, size_t temp_bytes) {
+  const size_t ws = kryo_direct_ws_bytes(kKryoDirectWriters), fixed = kryo_fixed_scratch_bytes();
+  const bool grow = d.kryo_sizes.cap < (n + 1) * 8 || d.kryo_temp.cap < temp_bytes || d.kryo_items.cap < n * 8 + 8 ||
+                    d.kryo_ws.cap < ws || d.kryo_fixed.cap < fixed;
+  return d.kryo_ev.grow(grow, [&] {
+    if (d.kryo_fixed.cap < fixed) d.kryo_fresh = true;
+    return d.kryo_sizes.ensure((n + 1) * 8) || d.kryo_temp.ensure(temp_bytes) ||
+                   d.kryo_items.ensure(n * 8 + 8) || d.kryo_ws.ensure(ws) || d.kryo_fixed.ensure(fixed)
+               ? hipErrorOutOfMemory
+               : hipSuccess;
+  });
 }
-
-// Enqueue ECDSA verification of n slot-layout lanes on stream s (device current,
-// d.ec_mu[slot] held): the slot's work buffers are reused only after their previous
-// user's kernels (on whatever stream) have finished.
-hipError_t ec_verify_enqueue(Device& d, const uint8_t* scheme, const uint8_t* keys, const uint8_t* key_len,
-                             const uint8_t* sigs, const uint8_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off,
-                             uint32_t msg_len, uint64_t n, const uint8_t* pre, uint8_t* status,
-                             unsigned long long* verdict, uint32_t flags, hipStream_t s, int slot) {
-  EcWork& w = d.ec[slot];
-  // the budget's ECDSA share (cordahip_init); slot 1 serves the host pipelines'
-  // alternate chunks and holds at most half of slot 0
-  const uint64_t ws_slots = slot ? std::max<uint64_t>(64, d.ec_ws_slots / 2 / 64 * 64) : d.ec_ws_slots;
-  const uint64_t slots = std::min<uint64_t>(ws_slots, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
-  if (w.ws.cap < slots * ecdsa_ws_slot_bytes() || w.perm.cap < std::max<uint64_t>(n, 1) * 4) {
-    hipError_t e = w.ev ? hipEventSynchronize(w.ev) : hipSuccess;  // a smaller buffer may still be in use
-    if (e != hipSuccess) return e;
-    if (w.ws.ensure(std::max<uint64_t>(slots, std::min<uint64_t>(ws_slots, kWsMinLanes)) * ecdsa_ws_slot_bytes()) ||
-        w.perm.ensure(std::max<uint64_t>(n, 1) * 4))
-      return hipErrorOutOfMemory;
-  }
-  if (w.counters.ensure(64)) return hipErrorOutOfMemory;
-  if (!w.ev && hipEventCreateWithFlags(&w.ev, hipEventDisableTiming) != hipSuccess) return hipErrorUnknown;
-  hipError_t e = hipStreamWaitEvent(s, w.ev, 0);
-  e = e ? e
-        : launch_ecdsa_verify(scheme, keys, key_len, sigs, sig_len, msgs, msg_off, msg_len, n, d.gtab_k1, d.gtab_r1,
-                              pre, status, verdict, w.counters.as<unsigned int>(), w.perm.as<unsigned int>(),
-                              w.ws.as<uint32_t>(), w.ws.cap / ecdsa_ws_slot_bytes() / 64 * 64, flags, s);
-  e = e ? e : hipEventRecord(w.ev, s);
-  return e;
-}
-
-// Enqueue RSASSA-PSS verification of n rows of one width class on stream s (device
-// current, d.rsa_mu held). The workspace holds at most kRsaWsRows rows (the
-// launches loop over it) and is reused only after its previous user's kernels.
-constexpr uint64_t kRsaWsRows = 1ull << 17;  // x 518 B (4096-bit rows) = 68 MB at most
-hipError_t rsa_verify_enqueue(Device& d, const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
-                              const uint16_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len,
-                              uint32_t W, uint64_t n, const uint8_t* pre, uint8_t* status,
-                              unsigned long long* verdict, uint32_t flags, hipStream_t s) {
-  RsaWork& w = d.rsa;
-  const uint64_t rows = std::min<uint64_t>(kRsaWsRows, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
-  const size_t rb = rsa_ws_row_bytes(W);
-  if (w.ws.cap < rows * rb) {
-    hipError_t e = w.ev ? hipEventSynchronize(w.ev) : hipSuccess;  // a smaller buffer may still be in use
-    if (e != hipSuccess) return e;
-    if (w.ws.ensure(rows * rb)) return hipErrorOutOfMemory;
-  }
-  if (!w.ev && hipEventCreateWithFlags(&w.ev, hipEventDisableTiming) != hipSuccess) return hipErrorUnknown;
-  hipError_t e = hipStreamWaitEvent(s, w.ev, 0);
-  e = e ? e
-        : launch_rsa_pss_verify(mod, exp, sigs, sig_len, msgs, msg_off, msg_len, W, n, pre, status, verdict,
-                                w.ws.as<uint8_t>(), w.ws.cap / rb / 64 * 64, flags, s);
-  e = e ? e : hipEventRecord(w.ev, s);
-  return e;
-}
-
-// Enqueue Ed25519 verification of n dense lanes on stream s (device already current).
-hipError_t ed_verify_enqueue(Device& d, const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs,
-                             uint32_t msg_len, uint64_t n, const uint8_t* pre, uint8_t* status,
-                             unsigned long long* verdict, uint32_t flags, hipStream_t s, int slot,
-                             const std::function<hipError_t()>* before_msgs) {
-  std::lock_guard<std::mutex> g(d.ed_mu[slot]);
-  DevBuf& ws = d.ed_ws[slot];
-  hipEvent_t& ev = d.ed_ev[slot];
-  // the budget's Ed25519 shares (cordahip_init, device_budget): slot 1 only serves the
-  // alternating chunks of the pipelines (host batches, streams, signed-tx chunks) and
-  // holds at most half of slot 0. The launch loops over whatever the workspace holds,
-  // so a smaller one only costs extra launch pairs.
-  const uint64_t cap_lanes = d.ed_ws_lanes[slot ? 1 : 0];
-  const uint64_t lanes = std::min<uint64_t>(cap_lanes, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
-  const uint64_t lane_bytes = ed25519_ws_lane_bytes();
-  if (ws.cap < lanes * lane_bytes) {
-    // a smaller buffer may still be in use by an earlier stream
-    hipError_t e = ev ? hipEventSynchronize(ev) : hipSuccess;
-    if (e != hipSuccess) return e;
-    uint64_t want = std::max<uint64_t>(lanes, std::min<uint64_t>(cap_lanes, kWsMinLanes));
-    const uint64_t had = ws.cap / lane_bytes / 64 * 64;  // ensure() frees it before allocating
-    e = ws.ensure(want * lane_bytes);
-    // HBM shared with other work: halve the request until it fits (at least
-    // what the slot held before, or one wave's lanes) instead of failing the call
-    while (e == hipErrorOutOfMemory && want > std::max<uint64_t>(64, had)) {
-      (void)hipGetLastError();
-      want = std::max<uint64_t>(std::max<uint64_t>(64, had), want / 2 / 64 * 64);
-      e = ws.ensure(want * lane_bytes);
-    }
-    if (e != hipSuccess) return e;
-  }
-  if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return hipErrorUnknown;
-  hipError_t e = hipStreamWaitEvent(s, ev, 0);
-  e = e ? e
-        : launch_ed25519_verify(keys, sigs, msgs, msg_len, n, d.btab, pre, status, verdict, ws.as<uint32_t>(),
-                                ws.cap / ed25519_ws_lane_bytes() / 64 * 64, flags, s, before_msgs);
-  e = e ? e : hipEventRecord(ev, s);
-  return e;
-}
-
-// The Ed25519 section of a device signed-tx call (32-byte messages in HBM, on the
-// caller's stream s): chunks of CORDAHIP_DEVICE_ED_CHUNK signatures (default
-// 98,304 = 0.75 of a ladder round of 2 waves x 1,024 SIMDs x 64 lanes; 0: one
-// launch pair) alternate between s with workspace slot 0 and the device's s_ed2
-// with slot 1, the short remainder first. Every ladder wave takes about the same
-// time, so one launch over C4's 2.5 M signatures (19.07 rounds) ran 20 rounds, its
-// last with 7% of the CUs; alternating chunks let chunk k + 1's prep fill chunk k's
-// ladder tail, as the host pipelines do. Two streams hold two chunks, so a chunk
-// below half a round leaves CUs idle (2^15: C4 64.7 M sig/s). One box
-// (profiles/r06_device_ed_chunk_ab/): C4 93.4-94.5 with one launch pair, 95.1-96.4
-// at 2^17, 95.8-96.7 at 2^16, 97.0-97.7 at 98,304; C4 --device-encode 87.1-87.2,
-// 88.7-89.2, 89.3-89.4, 89.2-89.2.
-hipError_t ed_verify_device_chunks(Device& d, TxSet& S, const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs,
-                                   uint64_t n, uint8_t* status, hipStream_t s) {
-  static const uint64_t chunk = [] {
-    const char* v = getenv("CORDAHIP_DEVICE_ED_CHUNK");
-    return v ? (uint64_t)strtoull(v, nullptr, 10) / 64 * 64 : (uint64_t)98304;
-  }();
-  if (!chunk || n <= chunk || !d.s_ed2)
-    return ed_verify_enqueue(d, keys, sigs, msgs, 32, n, nullptr, status, nullptr, 0u, s, 0, nullptr);
-  hipError_t e = hipEventRecord(S.ed_fork, s);
-  e = e ? e : hipStreamWaitEvent(d.s_ed2, S.ed_fork, 0);
-  const uint64_t r = n % chunk;
-  uint64_t lo = 0;
-  for (int k = 0; lo < n && e == hipSuccess; k++) {
-    const uint64_t hi = lo + (k == 0 && r ? r : chunk);
-    e = ed_verify_enqueue(d, keys + lo * 32, sigs + lo * 64, msgs + lo * 32, 32, hi - lo, nullptr, status + lo,
-                          nullptr, 0u, k % 2 ? d.s_ed2 : s, k % 2, nullptr);
-    lo = hi;
-  }
-  e = e ? e : hipEventRecord(S.ed_join, d.s_ed2);
-  return e ? e : hipStreamWaitEvent(s, S.ed_join, 0);
-}
-
-// CORDAHIP_DEVICE_MEM_BUDGET (bytes, K/M/G suffixes; default 128 GiB, at most 90%
-// of the device): the workspaces it sizes -- Ed25519 slot 0 45% of it, slot 1 20%
-// (and half of slot 0 at most), ECDSA 15% -- each also capped by its r05 maximum
-// (2^24 lanes / slots, CORDAHIP_ED25519_WS_LANES / CORDAHIP_ECDSA_WS_SLOTS). The
-// default therefore keeps C2's single 2^24-lane launch pair (53.7 GB) and the
-// r05 peak: 53.7 + 26.8 + 18.8 GB of workspaces. The other buffers follow the
-// batches (the id and signature stages, component slices, C5's stages) and are
-// not split. A smaller budget costs extra launch pairs, never a failed batch.
-uint64_t parse_bytes(const char* v, uint64_t dflt) {
-  if (!v || !*v) return dflt;
-  char* end = nullptr;
-  const double x = strtod(v, &end);
-  if (end == v || x <= 0) return dflt;
-  const char u = end ? (char)toupper((unsigned char)*end) : 0;
-  const double m = u == 'K' ? 1024.0 : u == 'M' ? 1048576.0 : u == 'G' ? 1073741824.0 : 1.0;
-  return (uint64_t)(x * m);
-}
-
-void device_budget(Device& d) {  // device current
-  uint64_t b = parse_bytes(getenv("CORDAHIP_DEVICE_MEM_BUDGET"), 128ull << 30);
-  size_t fr = 0, tot = 0;
-  if (hipMemGetInfo(&fr, &tot) == hipSuccess && tot) b = std::min<uint64_t>(b, (uint64_t)tot / 10 * 9);
-  d.mem_budget = b;
-  auto lanes = [](uint64_t bytes, uint64_t per) { return std::max<uint64_t>(64, bytes / per / 64 * 64); };
-  const uint64_t lb = ed25519_ws_lane_bytes(), sb = ecdsa_ws_slot_bytes();
-  d.ed_ws_lanes[0] = std::min(env_lanes("CORDAHIP_ED25519_WS_LANES", kEdWsLanes), lanes(b / 100 * 45, lb));
-  d.ed_ws_lanes[1] = std::min(std::max<uint64_t>(64, d.ed_ws_lanes[0] / 2 / 64 * 64), lanes(b / 5, lb));
-  d.ec_ws_slots = std::min(env_lanes("CORDAHIP_ECDSA_WS_SLOTS", kEcWsSlots), lanes(b / 100 * 15, sb));
-}
-
-// Free an idle device's grow-only buffers (the idle release, cordahip_trim): both
-// buffer sets and every lock that guards a buffer, in an order every path keeps
-// (sets, then kryo_mu, stream_mu, ped_mu, ed_mu, ec_mu, each slot in order, rsa_mu, cover_mu); the events that fence
-// device-path users (kernels on caller streams) synchronised first. The fixed
-// tables and the encoder's shape table stay (derived data, 18 MB).
-void trim_device(Device& d) {
-  SetLease l0(d, 0, true), l1(d, 1, true);
-  std::lock_guard<std::mutex> gk(d.kryo_mu), gs(d.stream_mu), gp(d.ped_mu), ge0(d.ed_mu[0]), ge1(d.ed_mu[1]),
-      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu), gv(d.cover_mu);
-  if (hipSetDevice(d.id) != hipSuccess) return;
-  for (hipEvent_t ev : {d.ed_ev[0], d.ed_ev[1], d.ec[0].ev, d.ec[1].ev, d.kryo_ev, d.set[0].tx_ev, d.set[1].tx_ev,
-                        d.rsa.ev, d.cover_ev})
-    if (ev) (void)hipEventSynchronize(ev);
-  d.cover_stack.release();
-  d.rsa.ws.release();
-  for (auto& b : d.rsa.h) b.release();
-  for (auto& b : d.rsa.d) b.release();
-  for (auto& w : d.ed_ws) w.release();
-  for (EcWork& w : d.ec) {
-    w.ws.release();
-    w.perm.release();
-  }
-  for (TxSet& S : d.set) {
-    TxWork& w = S.tx;
-    for (DevBuf* b : {&w.leaf_bytes, &w.leaf_off, &w.tx_leaf_off, &w.hashes, &w.txid, &w.tx_status, &w.tx_sig_off,
-                      &w.msgs, &w.comp_items, &w.payload, &w.comp_status, &w.tok, &w.tok_hash, &w.tx_tok_off, &w.root,
-                      &w.stack})
-      b->release();
-    for (BatchStage& st : S.pb) {
-      for (hipEvent_t ev : {st.copied, st.ed_done, st.ec_done})
-        if (ev) (void)hipEventSynchronize(ev);
-      for (auto& b : st.h) b.release();
-      for (auto& b : st.d) b.release();
-      for (auto& b : st.hidx) b.release();
-      for (auto& b : st.didx) b.release();
-      st.dverdict.release();
-    }
-  }
-  for (auto& st : d.sstage)
-    for (DevBuf* b : {&st.ed_keys, &st.ed_sigs, &st.ed_msgs, &st.ed_status, &st.ec_scheme, &st.ec_keys,
-                      &st.ec_key_len, &st.ec_sigs, &st.ec_sig_len, &st.ec_msgs, &st.ec_status})
-      b->release();
-  for (PackStage& st : d.ped) {
-    for (auto& b : st.h) b.release();
-    for (auto& b : st.d) b.release();
-  }
-  for (DevBuf* b : {&d.kryo_sizes, &d.kryo_temp, &d.kryo_ws, &d.kryo_items}) b->release();
-  if (tracing()) fprintf(stderr, "[cordahip] dev %d: idle buffers released\n", d.id);
-}
-
-// the in-process partition rule (cordahip_shard_range)
-void shard_range(uint64_t n, uint64_t nshards, uint64_t shard, uint64_t align, uint64_t& lo, uint64_t& hi) {
-  if (nshards == 0 || shard >= nshards) {
-    lo = hi = n;
-    return;
-  }
-  align = align ? align : 1;
-  const uint64_t per = ((n + nshards - 1) / nshards + align - 1) / align * align;
-  lo = std::min(n, shard * per);
-  hi = std::min(n, lo + per);
-}
-
-}  // namespace rt
-}  // namespace cordahip
-
-namespace {
-
-std::atomic<uint64_t> g_device_uid{1};
 
 // the context's host pool as csr_check.hpp's parallel runner
 struct PoolPar {
@@ -559,6 +124,19 @@ uint64_t submit_job(cordahip_ctx* ctx, std::function<int()> fn) {
   return t;
 }
 
+// A *_submit call: its descriptors by value (their arrays stay caller-owned) into a
+// queued job that runs impl(ctx, &copy...); the ticket.
+template <class F, class... D>
+int submit(cordahip_ctx* ctx, uint64_t* ticket, F impl, const D*... desc) {
+  if (!ctx || !ticket || (... || !desc)) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] {
+    *ticket = submit_job(ctx, [ctx, impl, copies = std::make_tuple(*desc...)] {
+      return std::apply([&](const D&... c) { return impl(ctx, &c...); }, copies);
+    });
+    return (int)CORDAHIP_SUCCESS;
+  });
+}
+
 // timing slot for one *_device call (records `a` now on stream s); the slot's
 // generation is the call's sequence number, so a reader whose slot was reused
 // by a later call (more than kTimingRing calls in between) can tell
@@ -573,11 +151,96 @@ TimedCall* timed_begin(Device& d, hipStream_t s) {
   return tc;
 }
 
+// A *_device entry point once its arguments are checked: the call counts as activity
+// on the device, the device is current, `prepare` grows what the call needs (device
+// memory it could not get is CORDAHIP_ERR_OUT_OF_MEMORY), and the call's timing pair
+// brackets what `enqueue` puts on the caller's stream (NULL: the device's null stream).
+template <class P, class F>
+int device_call(Device& d, void* hip_stream, P&& prepare, F&& enqueue) {
+  const Activity act(d);
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  if (const hipError_t e = prepare()) return e == hipErrorOutOfMemory ? CORDAHIP_ERR_OUT_OF_MEMORY : CORDAHIP_ERR_HIP;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  TimedCall* tc = timed_begin(d, s);
+  if (!tc) return CORDAHIP_ERR_HIP;
+  hipError_t e = enqueue(s);
+  e = e ? e : hipEventRecord(tc->b, s);
+  return hip_err(e);
+}
+template <class F>
+int device_call(Device& d, void* hip_stream, F&& enqueue) {
+  return device_call(d, hip_stream, [] { return hipSuccess; }, enqueue);
+}
+
+// What the two device signed-tx entry points share (leaves or components in HBM,
+// Ed25519 signatures, everything on the caller's stream s): the set's buffers, the
+// fork of the id chain, and -- once the caller has enqueued its id chain on x -- the
+// signatures over the ids and the per-transaction reduce.
+// CORDAHIP_DEVICE_SPLIT=1: the id chain forks onto the device's id stream and runs
+// beside the key half of the Ed25519 prep (key and R decoding: no dependence on the
+// ids) on s, which joins it before the message half. Off by default: the split prep's
+// two launches cost more than the overlap gains (c4 --device-encode 87.3-87.4 against
+// 89.1-89.2 M sig/s, c4 95.6-95.9 against 96.1-96.5; profiles/r06_device_split_ab/).
+struct DeviceSignedTx {
+  Device& d;
+  TxSet& S;
+  uint64_t ntx;
+  const void *d_tx_sig_off, *d_keys, *d_sigs;
+  uint64_t nsig;
+  void *d_txid, *d_tx_status, *d_first_bad, *d_sig_status;
+  static bool split() {
+    static const bool on = getenv("CORDAHIP_DEVICE_SPLIT") && getenv("CORDAHIP_DEVICE_SPLIT")[0] == '1';
+    return on;
+  }
+  // the set's leaf hashes and message rows (component calls: their statuses too), the streams
+  hipError_t prepare(uint64_t nleaves, bool comp_status) const {
+    TxWork& w = S.tx;
+    const uint64_t hb = std::max<uint64_t>(nleaves, 1) * 32, mb = std::max<uint64_t>(nsig, 1) * 32,
+                   cb = comp_status ? std::max<uint64_t>(nleaves, 1) : 0;
+    const hipError_t e = S.tx_ev.grow(w.hashes.cap < hb || w.msgs.cap < mb || w.comp_status.cap < cb, [&] {
+      return w.hashes.ensure(hb) || w.msgs.ensure(mb) || w.comp_status.ensure(cb) ? hipErrorOutOfMemory : hipSuccess;
+    });
+    return e ? e : ensure_streams(d);
+  }
+  // s waits for the set's previous user; x: the stream of the id chain
+  hipError_t fork(hipStream_t s, hipStream_t& x) const {
+    x = split() ? d.s_idcopy : s;
+    hipError_t e = S.tx_ev.wait(s);
+    if (split()) {
+      e = e ? e : hipEventRecord(S.fork, s);
+      e = e ? e : hipStreamWaitEvent(x, S.fork, 0);
+    }
+    return e;
+  }
+  hipError_t join_and_verify(hipStream_t s, hipStream_t x) const {
+    TxWork& w = S.tx;
+    const uint8_t *keys = static_cast<const uint8_t*>(d_keys), *sigs = static_cast<const uint8_t*>(d_sigs);
+    uint8_t* sig_status = static_cast<uint8_t*>(d_sig_status);
+    hipError_t e = split() ? hipEventRecord(S.ids, x) : hipSuccess;
+    const std::function<hipError_t()> join = [&]() -> hipError_t {  // the ids, then the signatures' messages
+      hipError_t r = split() ? hipStreamWaitEvent(s, S.ids, 0) : hipSuccess;
+      return r ? r : launch_gather_txid(static_cast<const uint8_t*>(d_txid), static_cast<const uint64_t*>(d_tx_sig_off),
+                                        ntx, w.msgs.as<uint8_t>(), s);
+    };
+    // unforked, the ids come first and the prep runs fused (its key and message halves
+    // as two launches cost ~0.6 ms more per 2.5 M signatures with nothing beside them)
+    if (nsig == 0 || !split()) e = e ? e : join();
+    if (split())
+      e = e ? e : ed_verify_enqueue(d, keys, sigs, w.msgs.as<uint8_t>(), 32, nsig, nullptr, sig_status, nullptr, 0u, s,
+                                    0, nsig ? &join : nullptr);
+    else
+      e = e ? e : ed_verify_device_chunks(d, S, keys, sigs, w.msgs.as<uint8_t>(), nsig, sig_status, s);
+    e = e ? e : S.tx_ev.record(s);  // fences the set's buffers for the next user
+    return e ? e : launch_tx_reduce(sig_status, static_cast<const uint64_t*>(d_tx_sig_off), ntx,
+                                    static_cast<int64_t*>(d_first_bad), static_cast<uint8_t*>(d_tx_status), s);
+  }
+};
+
 // A leased set's buffers for a host tx path: the last device-path user of the
 // set may still be running kernels on its own stream.
 int tx_acquire_host(Device& d, TxSet& set) {
   if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  if (hipEventSynchronize(set.tx_ev) != hipSuccess) return CORDAHIP_ERR_HIP;
+  if (set.tx_ev.sync() != hipSuccess) return CORDAHIP_ERR_HIP;
   return CORDAHIP_SUCCESS;
 }
 
@@ -613,8 +276,8 @@ int tx_ids_shard(cordahip_ctx* ctx, Device& d, const cordahip_txid_batch* b, uin
                                  w.tx_status.as<uint8_t>(), s);
   e = e ? e : hipMemcpyAsync(b->txid + t0 * 32, w.txid.p, ntx * 32, hipMemcpyDeviceToHost, s);
   e = e ? e : hipMemcpyAsync(b->tx_status + t0, w.tx_status.p, ntx, hipMemcpyDeviceToHost, s);
-  e = e ? e : hipEventRecord(S.tx_ev, s);
-  e = e ? e : hipEventSynchronize(S.tx_ev);
+  e = e ? e : S.tx_ev.record(s);
+  e = e ? e : S.tx_ev.sync();
   if (e != hipSuccess) (void)hipStreamSynchronize(s);
   return hip_err(e);
 }
@@ -673,7 +336,7 @@ struct CompPlan {
   uint64_t copied = 0;            // high window enqueued up to here (from high_min)
   bool low_copied = false;
   bool templates_only = false;    // the steady-state encoder chain (misses redo the call)
-  static constexpr uint64_t kDirectWriters = 1u << 13;  // the direct encoder's writers (rarely any work)
+  static constexpr uint64_t kDirectWriters = kKryoDirectWriters;  // the direct encoder's writers (rarely any work)
 };
 
 hipError_t tx_ids_prepare(cordahip_ctx* ctx, Device& d, TxSet& S, int set_idx, const cordahip_txid_batch* b,
@@ -770,14 +433,7 @@ hipError_t tx_ids_prepare(cordahip_ctx* ctx, Device& d, TxSet& S, int set_idx, c
     const uint64_t n = cp->max_items;
     size_t temp_bytes = 0;
     if (hipError_t e = kryo_scan_bytes(temp_bytes, n + 1, d.stream)) return e;
-    if (d.kryo_sizes.cap < (n + 1) * 8 || d.kryo_temp.cap < temp_bytes || d.kryo_items.cap < n * 8 + 8 ||
-        d.kryo_ws.cap < kryo_direct_ws_bytes(CompPlan::kDirectWriters) || d.kryo_fixed.cap < kryo_fixed_scratch_bytes()) {
-      if (d.kryo_ev && hipEventSynchronize(d.kryo_ev) != hipSuccess) return hipErrorUnknown;
-      if (d.kryo_sizes.ensure((n + 1) * 8) || d.kryo_temp.ensure(std::max<size_t>(temp_bytes, 16)) ||
-          d.kryo_items.ensure(n * 8 + 8) || d.kryo_ws.ensure(kryo_direct_ws_bytes(CompPlan::kDirectWriters)) ||
-          kryo_fixed_ensure(d))
-        return hipErrorOutOfMemory;
-    }
+    if (hipError_t e = kryo_scratch_ensure(d, n, std::max<size_t>(temp_bytes, 16))) return e;
     if (hipError_t e = usage_buffer(S.kryo_usage, S.kryo_usage_dev)) return e;
     if (hipError_t e = kryo_state_ready(d, d.stream)) return e;
     if (hipError_t e = kryo_reset_misses(d.kryo_fixed.as<uint8_t>(), (uint32_t)set_idx, d.stream)) return e;
@@ -786,7 +442,8 @@ hipError_t tx_ids_prepare(cordahip_ctx* ctx, Device& d, TxSet& S, int set_idx, c
     leaf_buf = cp->templates_only ? 0 : cp->slice_cap;
     if (tracing())
       fprintf(stderr, "[cordahip] dev %d set %d component call: %s chain (templates %u, slots %u in use)\n", d.id,
-              set_idx, cp->templates_only ? "templates-only" : "full encoder", S.kryo_usage[0], S.kryo_usage[1]);
+              set_idx, cp->templates_only ? "templates-only" : "full encoder", S.kryo_usage.as<uint32_t>()[0],
+              S.kryo_usage.as<uint32_t>()[1]);
   } else {
     leaf_buf = b->leaf_off[l1] - b->leaf_off[l0];
   }
@@ -920,11 +577,8 @@ hipError_t tx_ids_enqueue(Device& d, TxSet& S, int set_idx, const cordahip_txid_
     // buffers (S.tx_ev: the call's drain waits on it) and of the encoder's
     // scratch (d.kryo_*)
     if (cp) e = kryo_usage_report(d, &S, s);
-    e = e ? e : hipEventRecord(S.tx_ev, s);
-    if (cp && e == hipSuccess) {
-      if (!d.kryo_ev) e = e ? e : hipEventCreateWithFlags(&d.kryo_ev, hipEventDisableTiming);
-      e = e ? e : hipEventRecord(d.kryo_ev, s);
-    }
+    e = e ? e : S.tx_ev.record(s);
+    if (cp) e = e ? e : d.kryo_ev.record(s);
   }
   return e;
 }
@@ -1022,7 +676,7 @@ int signed_tx_device_once(cordahip_ctx* ctx, Device& d, const cordahip_signed_tx
   }
   int r = tx_acquire_host(d, S);
   if (r == CORDAHIP_SUCCESS && ensure_streams(d) != hipSuccess) r = CORDAHIP_ERR_HIP;
-  if (r == CORDAHIP_SUCCESS && cp && d.kryo_ev && hipStreamWaitEvent(d.stream, d.kryo_ev, 0) != hipSuccess)
+  if (r == CORDAHIP_SUCCESS && cp && d.kryo_ev.wait(d.stream) != hipSuccess)
     r = CORDAHIP_ERR_HIP;  // an earlier cordahip_kryo_encode_device still using the scratch
   if (r != CORDAHIP_SUCCESS) return r;
   DeviceIds di;
@@ -1200,7 +854,7 @@ int signed_tx_device_once(cordahip_ctx* ctx, Device& d, const cordahip_signed_tx
   // s_idcopy precede their slices' kernels. After an error the streams
   // themselves are drained.
   hipError_t e1 = hipSuccess;
-  if (r == CORDAHIP_SUCCESS) e1 = hipEventSynchronize(S.tx_ev);
+  if (r == CORDAHIP_SUCCESS) e1 = S.tx_ev.sync();
   if (r != CORDAHIP_SUCCESS || e1 != hipSuccess) {
     (void)hipStreamSynchronize(d.s_idcopy ? d.s_idcopy : d.stream);
     (void)hipStreamSynchronize(d.stream);
@@ -1212,7 +866,7 @@ int signed_tx_device_once(cordahip_ctx* ctx, Device& d, const cordahip_signed_tx
     // the encoder's misses in this call (this set's counter, reported after its last
     // slice, drained above): a templates-only call with any is void; a full call
     // without any lets the next call on this device take the templates-only chain
-    const uint32_t misses = static_cast<const volatile uint32_t*>(S.kryo_usage)[2 + set_idx];
+    const uint32_t misses = static_cast<const volatile uint32_t*>(S.kryo_usage.as<uint32_t>())[2 + set_idx];
     if (tracing()) fprintf(stderr, "[cordahip] dev %d set %d component call: %u encoder misses\n", d.id, set_idx, misses);
     std::lock_guard<std::mutex> g(d.kryo_mu);
     if (cp->templates_only && misses) {
@@ -1532,8 +1186,8 @@ int filtered_tx_shard(Device& d, const cordahip_filtered_tx_batch* b, uint64_t t
                                 w.tok_hash.as<uint8_t>(), w.tx_tok_off.as<uint64_t>(), w.root.as<uint8_t>(), ntx,
                                 w.stack.as<uint32_t>(), w.tx_status.as<uint8_t>(), s);
   e = e ? e : hipMemcpyAsync(b->tx_status + t0, w.tx_status.p, ntx, hipMemcpyDeviceToHost, s);
-  e = e ? e : hipEventRecord(S.tx_ev, s);
-  e = e ? e : hipEventSynchronize(S.tx_ev);
+  e = e ? e : S.tx_ev.record(s);
+  e = e ? e : S.tx_ev.sync();
   if (e != hipSuccess) (void)hipStreamSynchronize(s);
   return hip_err(e);
 }
@@ -1553,84 +1207,7 @@ Device* dev_at(cordahip_ctx* ctx, int device) {
   return ctx->devs[device].get();
 }
 
-void free_device(Device& d) {
-  (void)hipSetDevice(d.id);
-  for (PackStage& st : d.ped) {
-    for (auto& b : st.h) b.release();
-    for (auto& b : st.d) b.release();
-    for (hipEvent_t ev : {st.copied, st.done})
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  for (TxSet& S : d.set) {
-    for (BatchStage& st : S.pb) {
-      for (auto& b : st.h) b.release();
-      for (auto& b : st.d) b.release();
-      for (auto& b : st.hidx) b.release();
-      for (auto& b : st.didx) b.release();
-      st.dverdict.release();
-      for (hipEvent_t ev : {st.copied, st.ed_done, st.ec_done})
-        if (ev) (void)hipEventDestroy(ev);
-    }
-    TxWork& w = S.tx;
-    for (DevBuf* b : {&w.leaf_bytes, &w.leaf_off, &w.tx_leaf_off, &w.hashes, &w.txid, &w.tx_status, &w.tx_sig_off,
-                      &w.msgs, &w.comp_items, &w.payload, &w.comp_status, &w.tok, &w.tok_hash, &w.tx_tok_off, &w.root,
-                      &w.stack})
-      b->release();
-    if (S.kryo_usage) (void)hipHostFree(S.kryo_usage);
-    S.kryo_usage = S.kryo_usage_dev = nullptr;
-    for (hipEvent_t* pe : {&S.tx_ev, &S.fork, &S.ids, &S.ed_fork, &S.ed_join}) {
-      if (*pe) (void)hipEventDestroy(*pe);
-      *pe = nullptr;
-    }
-  }
-  for (auto& st : d.sstage) {
-    for (DevBuf* b : {&st.ed_keys, &st.ed_sigs, &st.ed_msgs, &st.ed_status, &st.ec_scheme, &st.ec_keys,
-                      &st.ec_key_len, &st.ec_sigs, &st.ec_sig_len, &st.ec_msgs, &st.ec_status})
-      b->release();
-    for (hipEvent_t ev : {st.ed_copied, st.ec_copied, st.ed_done, st.ec_done})
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  for (hipStream_t ss : {d.s_copy, d.s_ed, d.s_ec, d.s_idcopy, d.s_ed2})  // s_ec2 is s_idcopy
-    if (ss) (void)hipStreamDestroy(ss);
-  for (DevBuf* b : {&d.ec[0].counters, &d.ec[0].perm, &d.ec[0].ws, &d.ec[1].counters, &d.ec[1].perm, &d.ec[1].ws,
-                    &d.kryo_sizes, &d.kryo_temp, &d.kryo_ws, &d.kryo_fixed, &d.kryo_items})
-    b->release();
-  for (auto& w : d.ed_ws) w.release();
-  d.rsa.ws.release();
-  for (auto& b : d.rsa.h) b.release();
-  for (auto& b : d.rsa.d) b.release();
-  if (d.rsa.ev) (void)hipEventDestroy(d.rsa.ev);
-  d.cover_stack.release();
-  if (d.cover_ev) (void)hipEventDestroy(d.cover_ev);
-  if (d.s_rsa) (void)hipStreamDestroy(d.s_rsa);
-  if (d.kryo_usage) (void)hipHostFree(d.kryo_usage);
-  d.kryo_usage = d.kryo_usage_dev = nullptr;
-  for (hipEvent_t ev : {d.ec[0].ev, d.ec[1].ev, d.ed_ev[0], d.ed_ev[1], d.kryo_ev})
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& tc : d.ring)
-    for (hipEvent_t ev : {tc.a, tc.b})
-      if (ev) (void)hipEventDestroy(ev);
-  if (d.btab && d.gtab_k1 && d.gtab_r1) mem_acct(d.id).sub(ed25519_btable_bytes() + 2 * ecdsa_gtable_bytes());
-  if (d.gtab_k1) (void)hipFree(d.gtab_k1);
-  if (d.gtab_r1) (void)hipFree(d.gtab_r1);
-  if (d.btab) (void)hipFree(d.btab);
-  if (d.stream) (void)hipStreamDestroy(d.stream);
-}
-
 }  // namespace
-
-// Synchronous entry points run host code that allocates (staging vectors,
-// worker threads): no C++ exception may cross the C ABI into the JVM.
-template <class F>
-int guarded(F&& f) noexcept {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return CORDAHIP_ERR_OUT_OF_MEMORY;
-  } catch (...) {
-    return CORDAHIP_ERR_HIP;
-  }
-}
 
 extern "C" {
 
@@ -1657,157 +1234,6 @@ void cordahip_shard_range(uint64_t n, uint32_t nshards, uint32_t shard, uint64_t
   if (hi) *hi = b;
 }
 
-static int init_impl(uint32_t device_mask, cordahip_ctx** out);
-
-int cordahip_init(uint32_t device_mask, cordahip_ctx** out) {
-  if (!out) return CORDAHIP_ERR_INVALID_ARG;
-  *out = nullptr;
-  return guarded([&] { return init_impl(device_mask, out); });
-}
-
-static int init_impl(uint32_t device_mask, cordahip_ctx** out) {
-  *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return CORDAHIP_ERR_NO_DEVICE;
-  auto ctx = std::make_unique<cordahip_ctx>();
-  int rc = CORDAHIP_SUCCESS;
-  // Test-only: CORDAHIP_TEST_DEVICE_REPLICAS=k gives the context k Device
-  // objects per selected HIP device (each with its own streams, buffers and
-  // tables), so the N-device code -- shard split, per-device workers, tails,
-  // verdict reassembly -- runs on a one-GPU box. Unset in production.
-  int replicas = 1;
-  if (const char* v = getenv("CORDAHIP_TEST_DEVICE_REPLICAS")) replicas = std::max(1, std::min(8, atoi(v)));
-  std::vector<int> ids;
-  for (int d = 0; d < count && d < 32; d++)
-    if (!device_mask || ((device_mask >> d) & 1u))
-      for (int r = 0; r < replicas; r++) ids.push_back(d);
-  for (int d : ids) {
-    if (rc != CORDAHIP_SUCCESS) break;
-    ctx->devs.push_back(std::make_unique<Device>());
-    Device& dev = *ctx->devs.back();
-    dev.id = d;
-    dev.uid = g_device_uid.fetch_add(1);
-    if (hipSetDevice(d) != hipSuccess || hipStreamCreateWithFlags(&dev.stream, hipStreamNonBlocking) != hipSuccess) {
-      rc = CORDAHIP_ERR_HIP;
-      break;
-    }
-    for (TxSet& S : dev.set)
-      for (hipEvent_t* pe : {&S.tx_ev, &S.fork, &S.ids, &S.ed_fork, &S.ed_join})
-        if (hipEventCreateWithFlags(pe, hipEventDisableTiming) != hipSuccess) rc = CORDAHIP_ERR_HIP;
-    if (rc != CORDAHIP_SUCCESS) break;
-    for (auto& tc : dev.ring)
-      if (hipEventCreate(&tc.a) != hipSuccess || hipEventCreate(&tc.b) != hipSuccess) rc = CORDAHIP_ERR_HIP;
-    if (rc != CORDAHIP_SUCCESS) break;
-    if (hipMalloc(reinterpret_cast<void**>(&dev.btab), ed25519_btable_bytes()) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&dev.gtab_k1), ecdsa_gtable_bytes()) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&dev.gtab_r1), ecdsa_gtable_bytes()) != hipSuccess) {
-      rc = CORDAHIP_ERR_OUT_OF_MEMORY;
-      break;
-    }
-    mem_acct(d).add(ed25519_btable_bytes() + 2 * ecdsa_gtable_bytes());
-    device_budget(dev);
-    static const bool id_prio = !(getenv("CORDAHIP_ID_PRIO") && getenv("CORDAHIP_ID_PRIO")[0] == '0');
-    if (!id_prio && (tx_set_id_priority(0) != hipSuccess || kryo_set_priority(0) != hipSuccess)) {
-      rc = CORDAHIP_ERR_HIP;
-      break;
-    }
-    if (launch_ed25519_btable(dev.btab, dev.stream) != hipSuccess ||
-        launch_ecdsa_gtables(dev.gtab_k1, dev.gtab_r1, dev.stream) != hipSuccess ||
-        hipStreamSynchronize(dev.stream) != hipSuccess)
-      rc = CORDAHIP_ERR_HIP;
-  }
-  if (rc == CORDAHIP_SUCCESS && ctx->devs.empty()) rc = CORDAHIP_ERR_NO_DEVICE;
-  if (rc != CORDAHIP_SUCCESS) {
-    for (auto& d : ctx->devs) free_device(*d);
-    return rc;
-  }
-  ctx->pool = std::make_unique<WorkerPool>((int)std::max<size_t>(2, 2 * ctx->devs.size()));
-  // host threads. Per device (numa_place.hpp): a pool bound to CPUs of the GPU's
-  // NUMA node -- the devices of one node split its CPUs -- of CORDAHIP_HOST_THREADS
-  // threads at most (default 16: the pipelines are PCIe / kernel bound beyond that,
-  // tools/pack_bench.cpp); CORDAHIP_NUMA=0 leaves them unbound. Context-wide: a
-  // pool for the batch-level passes (CSR checks, verdict words) of at most 16.
-  int cap = 16;
-  if (const char* v = getenv("CORDAHIP_HOST_THREADS")) cap = std::max(1, std::min(256, atoi(v)));
-  std::vector<int> allowed;
-  {
-    cpu_set_t cs;
-    if (sched_getaffinity(0, sizeof(cs), &cs) == 0)
-      for (int c = 0; c < CPU_SETSIZE; c++)
-        if (CPU_ISSET(c, &cs)) allowed.push_back(c);
-  }
-  if (allowed.empty())
-    for (int c = 0; c < (int)std::max(1u, std::thread::hardware_concurrency()); c++) allowed.push_back(c);
-  std::vector<std::string> pci(ctx->devs.size());
-  const bool numa = !(getenv("CORDAHIP_NUMA") && getenv("CORDAHIP_NUMA")[0] == '0');
-  for (size_t i = 0; i < ctx->devs.size() && numa; i++) {
-    char bus[64] = {0};
-    if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus) - 1, ctx->devs[i]->id) == hipSuccess) {
-      pci[i] = bus;
-      for (char& ch : pci[i]) ch = (char)tolower((unsigned char)ch);
-    }
-  }
-  const char* root = getenv("CORDAHIP_SYSFS_ROOT");  // tests: a fake tree
-  const std::vector<NumaPlace> plan = numa_plan(root ? root : "/sys", pci, allowed, cap);
-  for (size_t i = 0; i < ctx->devs.size(); i++) {
-    Device& d = *ctx->devs[i];
-    d.place = plan[i];
-    if (!numa) d.place.cpus.clear();
-    d.pool = std::make_unique<HostPool>(d.place.threads, d.place.cpus);
-    if (tracing())
-      fprintf(stderr, "[cordahip] dev %d (%s): NUMA node %d, %zu CPUs, %d host threads%s%s\n", d.id, pci[i].c_str(),
-              d.place.node, d.place.cpus.size(), d.place.threads, d.place.why.empty() ? "" : ": ",
-              d.place.why.c_str());
-  }
-  ctx->host = std::make_unique<HostPool>(std::max(1, std::min<int>((int)allowed.size(), 16)));
-  // the idle release: a device with no call for CORDAHIP_IDLE_RELEASE_MS (default 30 s;
-  // 0: never) gives its grow-only buffers back (trim_device)
-  const char* iv = getenv("CORDAHIP_IDLE_RELEASE_MS");
-  const int64_t idle_ms = iv ? strtoll(iv, nullptr, 10) : 30000;
-  if (idle_ms > 0) {
-    cordahip_ctx* c = ctx.get();
-    c->reaper = std::thread([c, idle_ms] {
-      std::vector<int64_t> trimmed_at(c->devs.size(), 0);  // the last call's end when last trimmed
-      std::unique_lock<std::mutex> g(c->reaper_mu);
-      while (!c->reaper_stop) {
-        c->reaper_cv.wait_for(g, std::chrono::milliseconds(std::min<int64_t>(250, idle_ms)));
-        if (c->reaper_stop) break;
-        for (size_t i = 0; i < c->devs.size(); i++) {
-          Device& d = *c->devs[i];
-          const int64_t last = d.last_use_ms.load();
-          if (d.active.load() > 0 || last == 0 || last == trimmed_at[i] || (int64_t)now_ms() - last < idle_ms)
-            continue;
-          g.unlock();
-          trim_device(d);
-          g.lock();
-          trimmed_at[i] = last;
-        }
-      }
-    });
-  }
-  *out = ctx.release();
-  return CORDAHIP_SUCCESS;
-}
-
-void cordahip_shutdown(cordahip_ctx* ctx) {
-  if (!ctx) return;
-  if (ctx->reaper.joinable()) {
-    {
-      std::lock_guard<std::mutex> g(ctx->reaper_mu);
-      ctx->reaper_stop = true;
-    }
-    ctx->reaper_cv.notify_all();
-    ctx->reaper.join();
-  }
-  ctx->pool.reset();  // runs every queued job to completion, joins the workers
-  ctx->host.reset();
-  {
-    std::lock_guard<std::mutex> g(ctx->mu);
-    ctx->jobs.clear();
-  }
-  for (auto& d : ctx->devs) free_device(*d);
-  delete ctx;
-}
 
 int cordahip_device_count(const cordahip_ctx* ctx) { return ctx ? (int)ctx->devs.size() : 0; }
 
@@ -1846,30 +1272,17 @@ int cordahip_sig_verify(cordahip_ctx* ctx, const cordahip_sig_batch* batch) {
 }
 
 int cordahip_sig_submit(cordahip_ctx* ctx, const cordahip_sig_batch* batch, uint64_t* ticket) {
-  if (!ctx || !batch || !ticket) return CORDAHIP_ERR_INVALID_ARG;
-  const cordahip_sig_batch copy = *batch;  // descriptor by value; buffers stay caller-owned
-  return guarded([&] {
-    *ticket = submit_job(ctx, [ctx, copy] { return sig_verify_impl(ctx, &copy); });
-    return CORDAHIP_SUCCESS;
-  });
+  return submit(ctx, ticket, sig_verify_impl, batch);
 }
 
 int cordahip_tx_submit(cordahip_ctx* ctx, const cordahip_signed_tx_batch* batch, uint64_t* ticket) {
-  if (!ctx || !batch || !ticket) return CORDAHIP_ERR_INVALID_ARG;
-  const cordahip_signed_tx_batch copy = *batch;
-  return guarded([&] {
-    *ticket = submit_job(ctx, [ctx, copy] { return signed_tx_impl(ctx, &copy); });
-    return CORDAHIP_SUCCESS;
-  });
+  return submit(ctx, ticket, [](cordahip_ctx* c, const cordahip_signed_tx_batch* b) { return signed_tx_impl(c, b); },
+                batch);
 }
 
 int cordahip_txcomp_submit(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* batch, uint64_t* ticket) {
-  if (!ctx || !batch || !ticket) return CORDAHIP_ERR_INVALID_ARG;
-  const cordahip_signed_txcomp_batch copy = *batch;
-  return guarded([&] {
-    *ticket = submit_job(ctx, [ctx, copy] { return signed_txcomp_impl(ctx, &copy); });
-    return CORDAHIP_SUCCESS;
-  });
+  return submit(ctx, ticket,
+                [](cordahip_ctx* c, const cordahip_signed_txcomp_batch* b) { return signed_txcomp_impl(c, b); }, batch);
 }
 
 int cordahip_signed_txcomp_verify(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* batch) {
@@ -1885,13 +1298,9 @@ int cordahip_signed_tx_verify_covered(cordahip_ctx* ctx, const cordahip_signed_t
 
 int cordahip_tx_submit_covered(cordahip_ctx* ctx, const cordahip_signed_tx_batch* batch, const cordahip_cover* cover,
                                uint64_t* ticket) {
-  if (!ctx || !batch || !cover || !ticket) return CORDAHIP_ERR_INVALID_ARG;
-  const cordahip_signed_tx_batch copy = *batch;
-  const cordahip_cover ccopy = *cover;  // both descriptors by value; their arrays stay caller-owned
-  return guarded([&] {
-    *ticket = submit_job(ctx, [ctx, copy, ccopy] { return signed_tx_impl(ctx, &copy, nullptr, &ccopy); });
-    return CORDAHIP_SUCCESS;
-  });
+  return submit(ctx, ticket, [](cordahip_ctx* c, const cordahip_signed_tx_batch* b, const cordahip_cover* v) {
+    return signed_tx_impl(c, b, nullptr, v);
+  }, batch, cover);
 }
 
 int cordahip_signed_txcomp_verify_covered(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* batch,
@@ -1902,42 +1311,30 @@ int cordahip_signed_txcomp_verify_covered(cordahip_ctx* ctx, const cordahip_sign
 
 int cordahip_txcomp_submit_covered(cordahip_ctx* ctx, const cordahip_signed_txcomp_batch* batch,
                                    const cordahip_cover* cover, uint64_t* ticket) {
-  if (!ctx || !batch || !cover || !ticket) return CORDAHIP_ERR_INVALID_ARG;
-  const cordahip_signed_txcomp_batch copy = *batch;
-  const cordahip_cover ccopy = *cover;
-  return guarded([&] {
-    *ticket = submit_job(ctx, [ctx, copy, ccopy] { return signed_txcomp_impl(ctx, &copy, &ccopy); });
-    return CORDAHIP_SUCCESS;
-  });
+  return submit(ctx, ticket, [](cordahip_ctx* c, const cordahip_signed_txcomp_batch* b, const cordahip_cover* v) {
+    return signed_txcomp_impl(c, b, v);
+  }, batch, cover);
 }
 
 int cordahip_txid_submit(cordahip_ctx* ctx, const cordahip_txid_batch* batch, uint64_t* ticket) {
-  if (!ctx || !batch || !ticket) return CORDAHIP_ERR_INVALID_ARG;
-  const cordahip_txid_batch copy = *batch;
-  return guarded([&] {
-    *ticket = submit_job(ctx, [ctx, copy] { return tx_ids_impl(ctx, &copy); });
-    return CORDAHIP_SUCCESS;
-  });
+  return submit(ctx, ticket, tx_ids_impl, batch);
 }
 
 int cordahip_filtered_tx_submit(cordahip_ctx* ctx, const cordahip_filtered_tx_batch* batch, uint64_t* ticket) {
-  if (!ctx || !batch || !ticket) return CORDAHIP_ERR_INVALID_ARG;
-  const cordahip_filtered_tx_batch copy = *batch;
-  return guarded([&] {
-    *ticket = submit_job(ctx, [ctx, copy] { return filtered_tx_impl(ctx, &copy); });
-    return CORDAHIP_SUCCESS;
-  });
+  return submit(ctx, ticket, filtered_tx_impl, batch);
+}
+
+// a ticket's job (nullptr: unknown, or already waited for)
+static std::shared_ptr<JobState> job_of(cordahip_ctx* ctx, uint64_t ticket) {
+  std::lock_guard<std::mutex> g(ctx->mu);
+  auto it = ctx->jobs.find(ticket);
+  return it == ctx->jobs.end() ? nullptr : it->second;
 }
 
 int cordahip_wait(cordahip_ctx* ctx, uint64_t ticket, int64_t timeout_ns) {
   if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  std::shared_ptr<JobState> st;
-  {
-    std::lock_guard<std::mutex> g(ctx->mu);
-    auto it = ctx->jobs.find(ticket);
-    if (it == ctx->jobs.end()) return CORDAHIP_ERR_UNKNOWN_TICKET;
-    st = it->second;
-  }
+  const std::shared_ptr<JobState> st = job_of(ctx, ticket);
+  if (!st) return CORDAHIP_ERR_UNKNOWN_TICKET;
   int rc;
   {
     std::unique_lock<std::mutex> g(st->m);
@@ -1953,13 +1350,8 @@ int cordahip_wait(cordahip_ctx* ctx, uint64_t ticket, int64_t timeout_ns) {
 
 int cordahip_poll(cordahip_ctx* ctx, uint64_t ticket) {
   if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  std::shared_ptr<JobState> st;
-  {
-    std::lock_guard<std::mutex> g(ctx->mu);
-    auto it = ctx->jobs.find(ticket);
-    if (it == ctx->jobs.end()) return CORDAHIP_ERR_UNKNOWN_TICKET;
-    st = it->second;
-  }
+  const std::shared_ptr<JobState> st = job_of(ctx, ticket);
+  if (!st) return CORDAHIP_ERR_UNKNOWN_TICKET;
   std::lock_guard<std::mutex> g(st->m);
   return st->done ? 1 : 0;
 }
@@ -1972,16 +1364,11 @@ int cordahip_ed25519_verify_device(cordahip_ctx* ctx, int device, const void* d_
   if ((reinterpret_cast<uintptr_t>(d_keys) | reinterpret_cast<uintptr_t>(d_sigs)) & 15)
     return CORDAHIP_ERR_INVALID_ARG;
   if (msg_len == 32 && (reinterpret_cast<uintptr_t>(d_msgs) & 15)) return CORDAHIP_ERR_INVALID_ARG;
-  const Activity act(*d);
-  if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);  // NULL = the device's null stream
-  TimedCall* tc = timed_begin(*d, s);
-  if (!tc) return CORDAHIP_ERR_HIP;
-  hipError_t e = ed_verify_enqueue(*d, static_cast<const uint8_t*>(d_keys), static_cast<const uint8_t*>(d_sigs),
-                                   static_cast<const uint8_t*>(d_msgs), msg_len, n, nullptr,
-                                   static_cast<uint8_t*>(d_status), static_cast<unsigned long long*>(d_verdict), 0u, s);
-  e = e ? e : hipEventRecord(tc->b, s);
-  return hip_err(e);
+  return device_call(*d, hip_stream, [&](hipStream_t s) {
+    return ed_verify_enqueue(*d, static_cast<const uint8_t*>(d_keys), static_cast<const uint8_t*>(d_sigs),
+                             static_cast<const uint8_t*>(d_msgs), msg_len, n, nullptr, static_cast<uint8_t*>(d_status),
+                             static_cast<unsigned long long*>(d_verdict), 0u, s);
+  });
 }
 
 int cordahip_ecdsa_verify_device(cordahip_ctx* ctx, int device, const void* d_scheme, const void* d_keys,
@@ -1990,19 +1377,14 @@ int cordahip_ecdsa_verify_device(cordahip_ctx* ctx, int device, const void* d_sc
   Device* d = dev_at(ctx, device);
   if (!d || (n && (!d_scheme || !d_keys || !d_key_len || !d_sigs || !d_sig_len || !d_status || (msg_len && !d_msgs))))
     return CORDAHIP_ERR_INVALID_ARG;
-  const Activity act(*d);
   std::lock_guard<std::mutex> g(d->ec_mu[0]);
-  if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  TimedCall* tc = timed_begin(*d, s);
-  if (!tc) return CORDAHIP_ERR_HIP;
-  hipError_t e = ec_verify_enqueue(*d, static_cast<const uint8_t*>(d_scheme), static_cast<const uint8_t*>(d_keys),
-                                   static_cast<const uint8_t*>(d_key_len), static_cast<const uint8_t*>(d_sigs),
-                                   static_cast<const uint8_t*>(d_sig_len), static_cast<const uint8_t*>(d_msgs), nullptr,
-                                   msg_len, n, nullptr, static_cast<uint8_t*>(d_status),
-                                   static_cast<unsigned long long*>(d_verdict), 0u, s);
-  e = e ? e : hipEventRecord(tc->b, s);
-  return hip_err(e);
+  return device_call(*d, hip_stream, [&](hipStream_t s) {
+    return ec_verify_enqueue(*d, static_cast<const uint8_t*>(d_scheme), static_cast<const uint8_t*>(d_keys),
+                             static_cast<const uint8_t*>(d_key_len), static_cast<const uint8_t*>(d_sigs),
+                             static_cast<const uint8_t*>(d_sig_len), static_cast<const uint8_t*>(d_msgs), nullptr,
+                             msg_len, n, nullptr, static_cast<uint8_t*>(d_status),
+                             static_cast<unsigned long long*>(d_verdict), 0u, s);
+  });
 }
 
 int cordahip_rsa_public_op_device(cordahip_ctx* ctx, int device, const void* d_mod, const void* d_exp,
@@ -2013,16 +1395,10 @@ int cordahip_rsa_public_op_device(cordahip_ctx* ctx, int device, const void* d_m
   if ((reinterpret_cast<uintptr_t>(d_mod) | reinterpret_cast<uintptr_t>(d_exp) | reinterpret_cast<uintptr_t>(d_in) |
        reinterpret_cast<uintptr_t>(d_out)) & 3)
     return CORDAHIP_ERR_INVALID_ARG;
-  const Activity act(*d);
-  if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  TimedCall* tc = timed_begin(*d, s);
-  if (!tc) return CORDAHIP_ERR_HIP;
-  hipError_t e = launch_rsa_public_op(static_cast<const uint32_t*>(d_mod), static_cast<const uint32_t*>(d_exp),
-                                      static_cast<const uint32_t*>(d_in), mod_words, n, static_cast<uint32_t*>(d_out),
-                                      s);
-  e = e ? e : hipEventRecord(tc->b, s);
-  return hip_err(e);
+  return device_call(*d, hip_stream, [&](hipStream_t s) {
+    return launch_rsa_public_op(static_cast<const uint32_t*>(d_mod), static_cast<const uint32_t*>(d_exp),
+                                static_cast<const uint32_t*>(d_in), mod_words, n, static_cast<uint32_t*>(d_out), s);
+  });
 }
 
 int cordahip_rsa_pss_verify_device(cordahip_ctx* ctx, int device, const void* d_mod, const void* d_exp,
@@ -2035,19 +1411,13 @@ int cordahip_rsa_pss_verify_device(cordahip_ctx* ctx, int device, const void* d_
   if ((reinterpret_cast<uintptr_t>(d_mod) | reinterpret_cast<uintptr_t>(d_exp)) & 3 ||
       reinterpret_cast<uintptr_t>(d_sig_len) & 1)
     return CORDAHIP_ERR_INVALID_ARG;
-  const Activity act(*d);
   std::lock_guard<std::mutex> g(d->rsa_mu);
-  if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  TimedCall* tc = timed_begin(*d, s);
-  if (!tc) return CORDAHIP_ERR_HIP;
-  hipError_t e = rsa_verify_enqueue(*d, static_cast<const uint32_t*>(d_mod), static_cast<const uint32_t*>(d_exp),
-                                    static_cast<const uint8_t*>(d_sigs), static_cast<const uint16_t*>(d_sig_len),
-                                    static_cast<const uint8_t*>(d_msgs), nullptr, msg_len, mod_words, n, nullptr,
-                                    static_cast<uint8_t*>(d_status), static_cast<unsigned long long*>(d_verdict), 0u,
-                                    s);
-  e = e ? e : hipEventRecord(tc->b, s);
-  return hip_err(e);
+  return device_call(*d, hip_stream, [&](hipStream_t s) {
+    return rsa_verify_enqueue(*d, static_cast<const uint32_t*>(d_mod), static_cast<const uint32_t*>(d_exp),
+                              static_cast<const uint8_t*>(d_sigs), static_cast<const uint16_t*>(d_sig_len),
+                              static_cast<const uint8_t*>(d_msgs), nullptr, msg_len, mod_words, n, nullptr,
+                              static_cast<uint8_t*>(d_status), static_cast<unsigned long long*>(d_verdict), 0u, s);
+  });
 }
 
 int cordahip_tx_cover_device(cordahip_ctx* ctx, int device, uint64_t ntx, void* d_tx_status,
@@ -2063,30 +1433,25 @@ int cordahip_tx_cover_device(cordahip_ctx* ctx, int device, uint64_t ntx, void* 
     return CORDAHIP_ERR_INVALID_ARG;
   if (!d_sig_key_off && (reinterpret_cast<uintptr_t>(d_sig_key) & 15)) return CORDAHIP_ERR_INVALID_ARG;  // dense rows
   return guarded([&]() -> int {
-    const Activity act(*d);
     // the trees' evaluation stacks, one 8-byte slot per token (shared scratch:
     // cover_mu orders the enqueues, cover_ev fences its reuse across streams)
     std::lock_guard<std::mutex> g(d->cover_mu);
-    if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
-    if (!d->cover_ev && hipEventCreateWithFlags(&d->cover_ev, hipEventDisableTiming) != hipSuccess)
-      return CORDAHIP_ERR_HIP;
     const uint64_t need = std::max<uint64_t>(cover->ntok, 1) * 8;
-    if (d->cover_stack.cap < need) {
-      // growing frees the old buffer: the previous user's kernel must be done
-      if (hipEventSynchronize(d->cover_ev) != hipSuccess) return CORDAHIP_ERR_HIP;
-      if (d->cover_stack.ensure(need)) return CORDAHIP_ERR_OUT_OF_MEMORY;
-    }
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    TimedCall* tc = timed_begin(*d, s);
-    if (!tc) return CORDAHIP_ERR_HIP;
-    hipError_t e = hipStreamWaitEvent(s, d->cover_ev, 0);  // the previous user of the scratch is done
-    e = e ? e : launch_tx_cover(*cover, ntx, static_cast<uint8_t*>(d_tx_status),
-                                static_cast<const uint64_t*>(d_tx_sig_off), static_cast<const uint8_t*>(d_sig_scheme),
-                                static_cast<const uint8_t*>(d_sig_key), static_cast<const uint64_t*>(d_sig_key_off),
-                                d->cover_stack.as<uint64_t>(), s);
-    e = e ? e : hipEventRecord(d->cover_ev, s);
-    e = e ? e : hipEventRecord(tc->b, s);
-    return hip_err(e);
+    return device_call(
+        *d, hip_stream,
+        [&] {
+          return d->cover_ev.grow(d->cover_stack.cap < need,
+                                  [&] { return d->cover_stack.ensure(need) ? hipErrorOutOfMemory : hipSuccess; });
+        },
+        [&](hipStream_t s) {
+          hipError_t e = d->cover_ev.wait(s);  // the previous user of the scratch is done
+          e = e ? e
+                : launch_tx_cover(*cover, ntx, static_cast<uint8_t*>(d_tx_status),
+                                  static_cast<const uint64_t*>(d_tx_sig_off), static_cast<const uint8_t*>(d_sig_scheme),
+                                  static_cast<const uint8_t*>(d_sig_key), static_cast<const uint64_t*>(d_sig_key_off),
+                                  d->cover_stack.as<uint64_t>(), s);
+          return e ? e : d->cover_ev.record(s);
+        });
   });
 }
 
@@ -2135,7 +1500,7 @@ int cordahip_ed25519_sign_device(cordahip_ctx* ctx, int device, const void* d_se
   if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);  // NULL = the device's null stream
   return hip_err(launch_ed25519_sign(static_cast<const uint8_t*>(d_seeds), static_cast<const uint8_t*>(d_msgs),
-                                     msg_len, n, d->btab, static_cast<uint8_t*>(d_pubs),
+                                     msg_len, n, d->btab.as<uint32_t>(), static_cast<uint8_t*>(d_pubs),
                                      static_cast<uint8_t*>(d_sigs), s));
 }
 
@@ -2147,7 +1512,7 @@ int cordahip_ecdsa_sign_device(cordahip_ctx* ctx, int device, const void* d_sche
     return CORDAHIP_ERR_INVALID_ARG;
   if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
   return hip_err(launch_ecdsa_sign(static_cast<const uint8_t*>(d_scheme), static_cast<const uint8_t*>(d_seeds),
-                                   static_cast<const uint8_t*>(d_msgs), msg_len, n, d->gtab_k1, d->gtab_r1,
+                                   static_cast<const uint8_t*>(d_msgs), msg_len, n, d->gtab_k1.as<uint32_t>(), d->gtab_r1.as<uint32_t>(),
                                    static_cast<uint8_t*>(d_keys), static_cast<uint8_t*>(d_key_len),
                                    static_cast<uint8_t*>(d_sigs), static_cast<uint8_t*>(d_sig_len),
                                    static_cast<hipStream_t>(hip_stream)));
@@ -2174,55 +1539,21 @@ int cordahip_signed_tx_verify_ed25519_device(cordahip_ctx* ctx, int device, cons
     return CORDAHIP_ERR_INVALID_ARG;
   // a buffer set for the enqueue; its event then fences the set's hashes / msgs
   // until these kernels finish (the next holder waits on it)
-  const Activity act(*d);
   SetLease lease(*d);
   TxSet& S = lease.get();
-  if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
   TxWork& w = S.tx;
-  if (w.hashes.cap < std::max<uint64_t>(nleaves, 1) * 32 || w.msgs.cap < std::max<uint64_t>(nsig, 1) * 32) {
-    // growing frees the old buffers: the previous user's kernels must be done
-    if (hipEventSynchronize(S.tx_ev) != hipSuccess) return CORDAHIP_ERR_HIP;
-    if (w.hashes.ensure(std::max<uint64_t>(nleaves, 1) * 32) || w.msgs.ensure(std::max<uint64_t>(nsig, 1) * 32))
-      return CORDAHIP_ERR_OUT_OF_MEMORY;
-  }
-  if (ensure_streams(*d) != hipSuccess) return CORDAHIP_ERR_HIP;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  // CORDAHIP_DEVICE_SPLIT=1: the id kernels fork onto the device's id stream beside the
-  // key half of the Ed25519 prep on s (off by default: slower, see the component call)
-  static const bool split = getenv("CORDAHIP_DEVICE_SPLIT") && getenv("CORDAHIP_DEVICE_SPLIT")[0] == '1';
-  hipStream_t x = split ? d->s_idcopy : s;
-  TimedCall* tc = timed_begin(*d, s);
-  if (!tc) return CORDAHIP_ERR_HIP;
-  hipError_t e = hipStreamWaitEvent(s, S.tx_ev, 0);  // the previous user of w.hashes / w.msgs is done
-  if (split) {
-    e = e ? e : hipEventRecord(S.fork, s);
-    e = e ? e : hipStreamWaitEvent(x, S.fork, 0);
-  }
-  e = e ? e : launch_sha256_leaves(static_cast<const uint8_t*>(d_leaf_bytes), static_cast<const uint64_t*>(d_leaf_off),
-                                   nleaves, w.hashes.as<uint32_t>(), x);
-  e = e ? e : launch_merkle_root(w.hashes.as<uint32_t>(), static_cast<const uint64_t*>(d_tx_leaf_off), ntx,
-                                 static_cast<uint8_t*>(d_txid), static_cast<uint8_t*>(d_tx_status), x);
-  if (split) e = e ? e : hipEventRecord(S.ids, x);
-  const std::function<hipError_t()> join = [&]() -> hipError_t {  // the ids, then the signatures' messages
-    hipError_t r = split ? hipStreamWaitEvent(s, S.ids, 0) : hipSuccess;
-    return r ? r : launch_gather_txid(static_cast<const uint8_t*>(d_txid), static_cast<const uint64_t*>(d_tx_sig_off),
-                                      ntx, w.msgs.as<uint8_t>(), s);
-  };
-  // unforked, the ids come first and the prep runs fused (its key and message halves
-  // as two launches cost ~0.6 ms more per 2.5 M signatures with nothing beside them)
-  if (nsig == 0 || !split) e = e ? e : join();
-  if (split)
-    e = e ? e : ed_verify_enqueue(*d, static_cast<const uint8_t*>(d_keys), static_cast<const uint8_t*>(d_sigs),
-                                  w.msgs.as<uint8_t>(), 32, nsig, nullptr, static_cast<uint8_t*>(d_sig_status), nullptr,
-                                  0u, s, 0, nsig ? &join : nullptr);
-  else
-    e = e ? e : ed_verify_device_chunks(*d, S, static_cast<const uint8_t*>(d_keys), static_cast<const uint8_t*>(d_sigs),
-                                        w.msgs.as<uint8_t>(), nsig, static_cast<uint8_t*>(d_sig_status), s);
-  e = e ? e : hipEventRecord(S.tx_ev, s);  // fences w.hashes / w.msgs for the next user
-  e = e ? e : launch_tx_reduce(static_cast<uint8_t*>(d_sig_status), static_cast<const uint64_t*>(d_tx_sig_off),
-                               ntx, static_cast<int64_t*>(d_first_bad), static_cast<uint8_t*>(d_tx_status), s);
-  e = e ? e : hipEventRecord(tc->b, s);
-  return hip_err(e);
+  const DeviceSignedTx c{*d, S, ntx, d_tx_sig_off, d_keys, d_sigs, nsig, d_txid, d_tx_status, d_first_bad, d_sig_status};
+  return device_call(
+      *d, hip_stream, [&] { return c.prepare(nleaves, false); },
+      [&](hipStream_t s) {
+        hipStream_t x = nullptr;
+        hipError_t e = c.fork(s, x);
+        e = e ? e : launch_sha256_leaves(static_cast<const uint8_t*>(d_leaf_bytes),
+                                         static_cast<const uint64_t*>(d_leaf_off), nleaves, w.hashes.as<uint32_t>(), x);
+        e = e ? e : launch_merkle_root(w.hashes.as<uint32_t>(), static_cast<const uint64_t*>(d_tx_leaf_off), ntx,
+                                       static_cast<uint8_t*>(d_txid), static_cast<uint8_t*>(d_tx_status), x);
+        return e ? e : c.join_and_verify(s, x);
+      });
 }
 
 int cordahip_kryo_encode_device(cordahip_ctx* ctx, int device, const void* d_items, uint64_t n, uint32_t group,
@@ -2231,41 +1562,27 @@ int cordahip_kryo_encode_device(cordahip_ctx* ctx, int device, const void* d_ite
   if (!d || !d_off || (n && (!d_items || !d_status))) return CORDAHIP_ERR_INVALID_ARG;
   if (n >= (1ull << 31) - 1) return CORDAHIP_ERR_INVALID_ARG;  // the scan counts items in an int
   return guarded([&]() -> int {
-    const Activity act(*d);
     std::lock_guard<std::mutex> g(d->kryo_mu);
-    if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
-    if (!d->kryo_ev && hipEventCreateWithFlags(&d->kryo_ev, hipEventDisableTiming) != hipSuccess)
-      return CORDAHIP_ERR_HIP;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    // the direct encoder's writers (items without a template): 2^13 threads,
-    // 7 KB of level buffers each (56 MB)
-    const uint64_t dwriters = 1u << 13;
-    size_t temp_bytes = 0;
-    if (kryo_scan_bytes(temp_bytes, n + 1, s) != hipSuccess) return CORDAHIP_ERR_HIP;
-    if (d->kryo_sizes.cap < (n + 1) * 8 || d->kryo_temp.cap < temp_bytes || d->kryo_items.cap < n * 8 + 8 ||
-        d->kryo_ws.cap < kryo_direct_ws_bytes(dwriters) || d->kryo_fixed.cap < kryo_fixed_scratch_bytes()) {
-      // growing frees the old buffers: the previous user's kernels must be done
-      if (hipEventSynchronize(d->kryo_ev) != hipSuccess) return CORDAHIP_ERR_HIP;
-      if (d->kryo_sizes.ensure((n + 1) * 8) || d->kryo_temp.ensure(std::max<size_t>(temp_bytes, 16)) ||
-          d->kryo_items.ensure(n * 8 + 8) || d->kryo_ws.ensure(kryo_direct_ws_bytes(dwriters)) ||
-          kryo_fixed_ensure(*d))
-        return CORDAHIP_ERR_OUT_OF_MEMORY;
-    }
-    TimedCall* tc = timed_begin(*d, s);
-    if (!tc) return CORDAHIP_ERR_HIP;
-    uint32_t* slots = d->kryo_items.as<uint32_t>();
-    hipError_t e = hipStreamWaitEvent(s, d->kryo_ev, 0);  // the previous user of the scratch is done
-    e = e ? e : kryo_state_ready(*d, s);
-    e = e ? e
-          : launch_kryo_encode(static_cast<const cordahip_kryo_item*>(d_items), nullptr, 0, n, group,
-                               d->kryo_fixed.as<uint8_t>(),
-                               slots, slots + n, d->kryo_sizes.as<uint64_t>(), static_cast<uint64_t*>(d_off),
-                               static_cast<uint8_t*>(d_out), d_out ? cap : 0, static_cast<uint8_t*>(d_status),
-                               d->kryo_ws.as<uint8_t>(), dwriters, d->kryo_temp.p, d->kryo_temp.cap, s);
-    e = e ? e : kryo_usage_report(*d, nullptr, s);
-    e = e ? e : hipEventRecord(d->kryo_ev, s);
-    e = e ? e : hipEventRecord(tc->b, s);
-    return hip_err(e);
+    return device_call(
+        *d, hip_stream,
+        [&] {
+          size_t temp_bytes = 0;
+          const hipError_t e = kryo_scan_bytes(temp_bytes, n + 1, static_cast<hipStream_t>(hip_stream));
+          return e ? e : kryo_scratch_ensure(*d, n, std::max<size_t>(temp_bytes, 16));
+        },
+        [&](hipStream_t s) {
+          uint32_t* slots = d->kryo_items.as<uint32_t>();
+          hipError_t e = d->kryo_ev.wait(s);  // the previous user of the scratch is done
+          e = e ? e : kryo_state_ready(*d, s);
+          e = e ? e
+                : launch_kryo_encode(static_cast<const cordahip_kryo_item*>(d_items), nullptr, 0, n, group,
+                                     d->kryo_fixed.as<uint8_t>(), slots, slots + n, d->kryo_sizes.as<uint64_t>(),
+                                     static_cast<uint64_t*>(d_off), static_cast<uint8_t*>(d_out), d_out ? cap : 0,
+                                     static_cast<uint8_t*>(d_status), d->kryo_ws.as<uint8_t>(), kKryoDirectWriters,
+                                     d->kryo_temp.p, d->kryo_temp.cap, s);
+          e = e ? e : kryo_usage_report(*d, nullptr, s);
+          return e ? e : d->kryo_ev.record(s);
+        });
   });
 }
 
@@ -2284,82 +1601,39 @@ int cordahip_signed_txcomp_verify_ed25519_device(cordahip_ctx* ctx, int device, 
   return guarded([&]() -> int {
     // a buffer set for the enqueue (its hashes, messages and component statuses, fenced
     // by its event until these kernels finish) and the encoder's scratch (kryo_mu, kryo_ev)
-    const Activity act(*d);
     SetLease lease(*d);
     TxSet& S = lease.get();
     std::lock_guard<std::mutex> gk(d->kryo_mu);
-    if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
-    if (!d->kryo_ev && hipEventCreateWithFlags(&d->kryo_ev, hipEventDisableTiming) != hipSuccess) return CORDAHIP_ERR_HIP;
     TxWork& w = S.tx;
-    const uint64_t dwriters = CompPlan::kDirectWriters;
-    if (w.hashes.cap < std::max<uint64_t>(n_items, 1) * 32 || w.msgs.cap < std::max<uint64_t>(nsig, 1) * 32 ||
-        w.comp_status.cap < std::max<uint64_t>(n_items, 1)) {
-      // growing frees the old buffers: the set's previous user must be done
-      if (hipEventSynchronize(S.tx_ev) != hipSuccess) return CORDAHIP_ERR_HIP;
-      if (w.hashes.ensure(std::max<uint64_t>(n_items, 1) * 32) || w.msgs.ensure(std::max<uint64_t>(nsig, 1) * 32) ||
-          w.comp_status.ensure(std::max<uint64_t>(n_items, 1)))
-        return CORDAHIP_ERR_OUT_OF_MEMORY;
-    }
-    if (d->kryo_sizes.cap < (n_items + 1) * 8 || d->kryo_items.cap < n_items * 8 + 8 ||
-        d->kryo_ws.cap < kryo_direct_ws_bytes(dwriters) || d->kryo_fixed.cap < kryo_fixed_scratch_bytes()) {
-      if (hipEventSynchronize(d->kryo_ev) != hipSuccess) return CORDAHIP_ERR_HIP;
-      if (d->kryo_sizes.ensure((n_items + 1) * 8) || d->kryo_items.ensure(n_items * 8 + 8) ||
-          d->kryo_ws.ensure(kryo_direct_ws_bytes(dwriters)) || kryo_fixed_ensure(*d))
-        return CORDAHIP_ERR_OUT_OF_MEMORY;
-    }
-    if (ensure_streams(*d) != hipSuccess) return CORDAHIP_ERR_HIP;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    // CORDAHIP_DEVICE_SPLIT=1: the id chain forks onto the device's id stream and runs
-    // beside the key half of the Ed25519 prep (key and R decoding: no dependence on the
-    // ids) on s, which joins it before the message half. Off: the split prep's two
-    // launches cost more than the overlap gains (c4 --device-encode 87.3-87.4 against
-    // 89.1-89.2 M sig/s, c4 95.6-95.9 against 96.1-96.5; profiles/r06_device_split_ab/)
-    static const bool split = getenv("CORDAHIP_DEVICE_SPLIT") && getenv("CORDAHIP_DEVICE_SPLIT")[0] == '1';
-    hipStream_t x = split ? d->s_idcopy : s;
-    TimedCall* tc = timed_begin(*d, s);
-    if (!tc) return CORDAHIP_ERR_HIP;
-    uint32_t* slots = d->kryo_items.as<uint32_t>();
-    hipError_t e = hipStreamWaitEvent(s, S.tx_ev, 0);  // the previous users of the set's buffers
-    e = e ? e : hipStreamWaitEvent(s, d->kryo_ev, 0);  // and of the encoder's scratch are done
-    if (split) {
-      e = e ? e : hipEventRecord(S.fork, s);
-      e = e ? e : hipStreamWaitEvent(x, S.fork, 0);
-    }
-    e = e ? e : kryo_state_ready(*d, x);
-    // leaf hashes from the templates (misses impossible: new shapes are built, the rest
-    // hashed by the direct encoder), then the ids, with a rejected component making its
-    // transaction CORDAHIP_TX_BAD_COMPONENT
-    e = e ? e
-          : launch_kryo_hash_chain(static_cast<const cordahip_kryo_item*>(d_items),
-                                   static_cast<const uint8_t*>(d_payload), payload_len, n_items, group,
-                                   d->kryo_fixed.as<uint8_t>(), slots, slots + n_items, d->kryo_sizes.as<uint64_t>(),
-                                   w.comp_status.as<uint8_t>(), w.hashes.as<uint32_t>(), d->kryo_ws.as<uint8_t>(),
-                                   dwriters, x);
-    e = e ? e : kryo_usage_report(*d, nullptr, x);
-    e = e ? e : hipEventRecord(d->kryo_ev, x);
-    e = e ? e : launch_merkle_root(w.hashes.as<uint32_t>(), static_cast<const uint64_t*>(d_tx_item_off), ntx,
-                                   static_cast<uint8_t*>(d_txid), static_cast<uint8_t*>(d_tx_status), x,
-                                   w.comp_status.as<uint8_t>());
-    if (split) e = e ? e : hipEventRecord(S.ids, x);
-    const std::function<hipError_t()> join = [&]() -> hipError_t {  // the ids, then the signatures' messages
-      hipError_t r = split ? hipStreamWaitEvent(s, S.ids, 0) : hipSuccess;
-      return r ? r : launch_gather_txid(static_cast<const uint8_t*>(d_txid), static_cast<const uint64_t*>(d_tx_sig_off),
-                                        ntx, w.msgs.as<uint8_t>(), s);
-    };
-    if (nsig == 0 || !split) e = e ? e : join();  // unforked: ids first, then the fused prep
-    if (split)
-      e = e ? e : ed_verify_enqueue(*d, static_cast<const uint8_t*>(d_keys), static_cast<const uint8_t*>(d_sigs),
-                                    w.msgs.as<uint8_t>(), 32, nsig, nullptr, static_cast<uint8_t*>(d_sig_status),
-                                    nullptr, 0u, s, 0, nsig ? &join : nullptr);
-    else
-      e = e ? e : ed_verify_device_chunks(*d, S, static_cast<const uint8_t*>(d_keys),
-                                          static_cast<const uint8_t*>(d_sigs), w.msgs.as<uint8_t>(), nsig,
-                                          static_cast<uint8_t*>(d_sig_status), s);
-    e = e ? e : hipEventRecord(S.tx_ev, s);  // fences the set's buffers for the next user
-    e = e ? e : launch_tx_reduce(static_cast<uint8_t*>(d_sig_status), static_cast<const uint64_t*>(d_tx_sig_off), ntx,
-                                 static_cast<int64_t*>(d_first_bad), static_cast<uint8_t*>(d_tx_status), s);
-    e = e ? e : hipEventRecord(tc->b, s);
-    return hip_err(e);
+    const DeviceSignedTx c{*d, S, ntx, d_tx_sig_off, d_keys, d_sigs, nsig, d_txid, d_tx_status, d_first_bad, d_sig_status};
+    return device_call(
+        *d, hip_stream,
+        [&] {
+          const hipError_t e = c.prepare(n_items, true);
+          return e ? e : kryo_scratch_ensure(*d, n_items, 0);
+        },
+        [&](hipStream_t s) {
+          uint32_t* slots = d->kryo_items.as<uint32_t>();
+          hipStream_t x = nullptr;
+          hipError_t e = d->kryo_ev.wait(s);  // the previous users of the encoder's scratch are done
+          e = e ? e : c.fork(s, x);
+          e = e ? e : kryo_state_ready(*d, x);
+          // leaf hashes from the templates (misses impossible: new shapes are built, the rest
+          // hashed by the direct encoder), then the ids, with a rejected component making its
+          // transaction CORDAHIP_TX_BAD_COMPONENT
+          e = e ? e
+                : launch_kryo_hash_chain(static_cast<const cordahip_kryo_item*>(d_items),
+                                         static_cast<const uint8_t*>(d_payload), payload_len, n_items, group,
+                                         d->kryo_fixed.as<uint8_t>(), slots, slots + n_items,
+                                         d->kryo_sizes.as<uint64_t>(), w.comp_status.as<uint8_t>(),
+                                         w.hashes.as<uint32_t>(), d->kryo_ws.as<uint8_t>(), kKryoDirectWriters, x);
+          e = e ? e : kryo_usage_report(*d, nullptr, x);
+          e = e ? e : d->kryo_ev.record(x);
+          e = e ? e : launch_merkle_root(w.hashes.as<uint32_t>(), static_cast<const uint64_t*>(d_tx_item_off), ntx,
+                                         static_cast<uint8_t*>(d_txid), static_cast<uint8_t*>(d_tx_status), x,
+                                         w.comp_status.as<uint8_t>());
+          return e ? e : c.join_and_verify(s, x);
+        });
   });
 }
 

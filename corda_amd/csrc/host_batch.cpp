@@ -684,7 +684,7 @@ int sig_verify_msgs(cordahip_ctx* ctx, const cordahip_sig_batch* b, const MsgVie
   // contiguous 64-aligned input shards, one pipeline per device
   const int rc = for_shards(ctx->devs, n, 64, [&](Device& d, uint64_t lo, uint64_t hi) {
     SetLease lease(d);
-    if (hipSetDevice(d.id) != hipSuccess || hipEventSynchronize(lease.get().tx_ev) != hipSuccess)
+    if (hipSetDevice(d.id) != hipSuccess || lease.get().tx_ev.sync() != hipSuccess)
       return (int)CORDAHIP_ERR_HIP;
     return sig_pipeline(ctx, d, lease.get(), b, mv, lo, hi);
   });

@@ -1,0 +1,556 @@
+// libcordahip.so per-device runtime: the host pools, the pipeline streams, the
+// device-memory budget, the enqueue helpers of the three signature schemes (their
+// workspaces and reuse fences), the idle release, and context init / shutdown.
+// What a Device owns and how it is released is in runtime.hpp.
+#include <hip/hip_runtime.h>
+#include <pthread.h>
+#include <sched.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "runtime.hpp"
+
+using namespace cordahip;
+using namespace cordahip::rt;
+
+namespace cordahip {
+namespace rt {
+
+// ---- host fork-join pool -----------------------------------------------------
+HostPool::HostPool(int nthreads, const std::vector<int>& cpus) {
+  for (int i = 1; i < nthreads; i++) {
+    threads_.emplace_back([this] { worker(); });
+    if (!cpus.empty()) {  // the device's node: its rows are packed next to its GPU
+      cpu_set_t cs;
+      CPU_ZERO(&cs);
+      for (int c : cpus)
+        if (c >= 0 && c < CPU_SETSIZE) CPU_SET(c, &cs);
+      (void)pthread_setaffinity_np(threads_.back().native_handle(), sizeof(cs), &cs);
+    }
+  }
+}
+
+NodeBind::NodeBind(const Device& d) {
+  if (d.place.cpus.empty()) return;
+  cpu_set_t old, cs;
+  if (pthread_getaffinity_np(pthread_self(), sizeof(old), &old) != 0) return;
+  CPU_ZERO(&cs);
+  for (int c : d.place.cpus)
+    if (c >= 0 && c < CPU_SETSIZE) CPU_SET(c, &cs);
+  if (CPU_EQUAL(&cs, &old) || pthread_setaffinity_np(pthread_self(), sizeof(cs), &cs) != 0) return;
+  saved_.assign(reinterpret_cast<unsigned char*>(&old), reinterpret_cast<unsigned char*>(&old) + sizeof(old));
+  bound_ = true;
+}
+
+NodeBind::~NodeBind() {
+  if (bound_) (void)pthread_setaffinity_np(pthread_self(), sizeof(cpu_set_t), reinterpret_cast<cpu_set_t*>(saved_.data()));
+}
+
+HostPool& pool_of(cordahip_ctx* ctx, Device& d) { return d.pool ? *d.pool : *ctx->host; }
+
+HostPool::~HostPool() {
+  {
+    std::lock_guard<std::mutex> g(m_);
+    stop_ = true;
+  }
+  cv_.notify_all();
+  for (auto& t : threads_) t.join();
+}
+
+void HostPool::run_pieces(Job& j) {
+  for (;;) {
+    const uint64_t k = j.next.fetch_add(1);
+    if (k >= j.npieces) return;
+    const uint64_t lo = k * j.piece, hi = std::min(j.n, lo + j.piece);
+    (*j.fn)(lo, hi);
+    if (j.done.fetch_add(1) + 1 == j.npieces) {
+      std::lock_guard<std::mutex> g(j.m);
+      j.cv.notify_all();
+    }
+  }
+}
+
+void HostPool::worker() {
+  for (;;) {
+    std::shared_ptr<Job> j;
+    {
+      std::unique_lock<std::mutex> g(m_);
+      for (;;) {
+        while (!q_.empty() && q_.front()->next.load() >= q_.front()->npieces) q_.pop_front();  // exhausted
+        if (!q_.empty()) {
+          j = q_.front();
+          break;
+        }
+        if (stop_) return;
+        cv_.wait(g);
+      }
+    }
+    run_pieces(*j);
+  }
+}
+
+void HostPool::parallel_for(uint64_t n, uint64_t grain, const std::function<void(uint64_t, uint64_t)>& fn) {
+  if (n == 0) return;
+  grain = std::max<uint64_t>(grain, 1);
+  const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>((n + grain - 1) / grain, 4 * (uint64_t)threads()));
+  if (want == 1 || threads_.empty()) {
+    fn(0, n);
+    return;
+  }
+  auto j = std::make_shared<Job>();
+  j->fn = &fn;
+  j->n = n;
+  j->piece = (n + want - 1) / want;
+  j->npieces = (n + j->piece - 1) / j->piece;
+  {
+    std::lock_guard<std::mutex> g(m_);
+    q_.push_back(j);
+  }
+  cv_.notify_all();
+  run_pieces(*j);
+  {
+    std::unique_lock<std::mutex> g(j->m);
+    j->cv.wait(g, [&] { return j->done.load() == j->npieces; });
+  }
+  std::lock_guard<std::mutex> g(m_);  // drop it if no worker got to pop it
+  for (auto it = q_.begin(); it != q_.end(); ++it)
+    if (*it == j) {
+      q_.erase(it);
+      break;
+    }
+}
+
+// ---- ticket pool ---------------------------------------------------------------
+WorkerPool::WorkerPool(int nthreads) {
+  for (int i = 0; i < nthreads; i++) threads_.emplace_back([this] { run(); });
+}
+
+WorkerPool::~WorkerPool() {
+  {
+    std::lock_guard<std::mutex> g(m_);
+    stop_ = true;
+  }
+  cv_.notify_all();
+  for (auto& t : threads_) t.join();
+}
+
+void WorkerPool::push(std::shared_ptr<JobState> st, std::function<int()> fn) {
+  {
+    std::lock_guard<std::mutex> g(m_);
+    q_.emplace_back(std::move(st), std::move(fn));
+  }
+  cv_.notify_one();
+}
+
+void WorkerPool::run() {
+  for (;;) {
+    std::pair<std::shared_ptr<JobState>, std::function<int()>> job;
+    {
+      std::unique_lock<std::mutex> g(m_);
+      cv_.wait(g, [this] { return stop_ || !q_.empty(); });
+      if (q_.empty()) return;  // stop_ and drained: queued jobs always run
+      job = std::move(q_.front());
+      q_.pop_front();
+    }
+    int rc;
+    try {
+      rc = job.second();
+    } catch (...) {
+      rc = CORDAHIP_ERR_OUT_OF_MEMORY;  // std::bad_alloc from host staging vectors
+    }
+    {
+      std::lock_guard<std::mutex> g(job.first->m);
+      job.first->rc = rc;
+      job.first->done = true;
+    }
+    job.first->cv.notify_all();
+  }
+}
+
+int hip_err(hipError_t e) { return e == hipSuccess ? CORDAHIP_SUCCESS : CORDAHIP_ERR_HIP; }
+
+hipError_t ensure_streams(Device& d) {
+  std::lock_guard<std::mutex> g(d.streams_mu);
+  if (d.s_copy) return hipSuccess;
+  // Every pipeline stream needs a hardware queue of its own: streams sharing a
+  // queue serialise, and a copy enqueued early (the tx-id slices' leaf bytes,
+  // a C5 chunk waiting for its stage) then holds back every later kernel of the
+  // other stream. HIP hands out pool queues (GPU_MAX_HW_QUEUES, 4 on the box)
+  // round-robin over every stream of the process, so a 4th pipeline stream
+  // shared one with s_ed or s_copy depending on creation order (c4h 45.1 M
+  // sigs/s, or C5 84.6 instead of 95.8 M/s: profiles/r03_stream_queues.json). A
+  // stream created with a CU mask (here: all CUs) gets a dedicated queue; the
+  // ECDSA stream keeps the higher priority, which also gives it a queue of its
+  // own (at normal priority it shared s_ed's and the two sections ran back to back).
+  int lo = 0, hi = 0, ncu = 0;
+  hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
+  e = e ? e : hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d.id);
+  std::vector<uint32_t> all((std::max(ncu, 1) + 31) / 32, 0xffffffffu);
+  auto dedicated = [&](hipStream_t* st) { return hipExtStreamCreateWithCUMask(st, (uint32_t)all.size(), all.data()); };
+  hipStream_t c = nullptr, x = nullptr, y = nullptr, z = nullptr, x2 = nullptr;
+  e = e ? e : dedicated(&c);
+  e = e ? e : dedicated(&x);
+  e = e ? e : hipStreamCreateWithPriority(&y, hipStreamNonBlocking, hi);
+  e = e ? e : dedicated(&z);
+  e = e ? e : dedicated(&x2);
+  if (e != hipSuccess) {
+    for (hipStream_t s : {c, x, y, z, x2})
+      if (s) (void)hipStreamDestroy(s);
+    return e;
+  }
+  d.s_ed = x;
+  d.s_ed2 = x2;
+  d.s_ec = y;
+  // generic batches' alternate ECDSA chunks run on the id-copy stream, idle in those
+  // batches (no sixth hardware queue)
+  d.s_ec2 = z;
+  d.s_idcopy = z;
+  d.s_copy = c;
+  return hipSuccess;
+}
+
+// Launch-pair sizes of the split kernels = the largest workspace per device.
+// Bigger launches pay fewer end-of-grid tails (C2, measured: 2^18 91.5, 2^20
+// 93.2, 2^22 96.4, 2^24 97.2 M verifs/s): a 2^24-lane batch runs as ONE
+// prep/ladder pair over 54 GB of HBM (19% of the MI355X's 288 GB). Smaller
+// batches allocate only what they use (grow-only, from 2^18 lanes up).
+constexpr uint64_t kEdWsLanes = 1ull << 24;  // x 3,200 B = 54 GB of Ed25519 workspace at most
+constexpr uint64_t kEcWsSlots = 1ull << 24;  // x 1,120 B = 18.8 GB of ECDSA workspace at most
+constexpr uint64_t kWsMinLanes = 1ull << 18;
+
+// Workspace-size overrides (multiples of 64): tests use them to force the
+// multi-chunk paths (several prep/ladder launch sets per batch) at small sizes.
+uint64_t env_lanes(const char* name, uint64_t dflt) {
+  const char* v = getenv(name);
+  const uint64_t x = v ? strtoull(v, nullptr, 10) : 0;
+  return x >= 64 ? x / 64 * 64 : dflt;
+}
+
+// Enqueue ECDSA verification of n slot-layout lanes on stream s (device current,
+// d.ec_mu[slot] held): the slot's work buffers are reused only after their previous
+// user's kernels (on whatever stream) have finished.
+hipError_t ec_verify_enqueue(Device& d, const uint8_t* scheme, const uint8_t* keys, const uint8_t* key_len,
+                             const uint8_t* sigs, const uint8_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off,
+                             uint32_t msg_len, uint64_t n, const uint8_t* pre, uint8_t* status,
+                             unsigned long long* verdict, uint32_t flags, hipStream_t s, int slot) {
+  EcWork& w = d.ec[slot];
+  // the budget's ECDSA share (cordahip_init); slot 1 serves the host pipelines'
+  // alternate chunks and holds at most half of slot 0
+  const uint64_t ws_slots = slot ? std::max<uint64_t>(64, d.ec_ws_slots / 2 / 64 * 64) : d.ec_ws_slots;
+  const uint64_t slots = std::min<uint64_t>(ws_slots, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
+  const uint64_t perm_bytes = std::max<uint64_t>(n, 1) * 4;
+  hipError_t e = w.ev.grow(w.ws.cap < slots * ecdsa_ws_slot_bytes() || w.perm.cap < perm_bytes, [&] {
+    const uint64_t want = std::max<uint64_t>(slots, std::min<uint64_t>(ws_slots, kWsMinLanes));
+    return w.ws.ensure(want * ecdsa_ws_slot_bytes()) || w.perm.ensure(perm_bytes) ? hipErrorOutOfMemory : hipSuccess;
+  });
+  if (e != hipSuccess) return e;
+  if (w.counters.ensure(64)) return hipErrorOutOfMemory;
+  e = w.ev.wait(s);
+  e = e ? e
+        : launch_ecdsa_verify(scheme, keys, key_len, sigs, sig_len, msgs, msg_off, msg_len, n,
+                              d.gtab_k1.as<uint32_t>(), d.gtab_r1.as<uint32_t>(), pre, status, verdict,
+                              w.counters.as<unsigned int>(), w.perm.as<unsigned int>(), w.ws.as<uint32_t>(),
+                              w.ws.cap / ecdsa_ws_slot_bytes() / 64 * 64, flags, s);
+  return e ? e : w.ev.record(s);
+}
+
+// Enqueue RSASSA-PSS verification of n rows of one width class on stream s (device
+// current, d.rsa_mu held). The workspace holds at most kRsaWsRows rows (the
+// launches loop over it) and is reused only after its previous user's kernels.
+constexpr uint64_t kRsaWsRows = 1ull << 17;  // x 518 B (4096-bit rows) = 68 MB at most
+hipError_t rsa_verify_enqueue(Device& d, const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
+                              const uint16_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len,
+                              uint32_t W, uint64_t n, const uint8_t* pre, uint8_t* status,
+                              unsigned long long* verdict, uint32_t flags, hipStream_t s) {
+  RsaWork& w = d.rsa;
+  const uint64_t rows = std::min<uint64_t>(kRsaWsRows, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
+  const size_t rb = rsa_ws_row_bytes(W);
+  hipError_t e = w.ev.grow(w.ws.cap < rows * rb,
+                           [&] { return w.ws.ensure(rows * rb) ? hipErrorOutOfMemory : hipSuccess; });
+  e = e ? e : w.ev.wait(s);
+  e = e ? e
+        : launch_rsa_pss_verify(mod, exp, sigs, sig_len, msgs, msg_off, msg_len, W, n, pre, status, verdict,
+                                w.ws.as<uint8_t>(), w.ws.cap / rb / 64 * 64, flags, s);
+  return e ? e : w.ev.record(s);
+}
+
+// Enqueue Ed25519 verification of n dense lanes on stream s (device already current).
+hipError_t ed_verify_enqueue(Device& d, const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs,
+                             uint32_t msg_len, uint64_t n, const uint8_t* pre, uint8_t* status,
+                             unsigned long long* verdict, uint32_t flags, hipStream_t s, int slot,
+                             const std::function<hipError_t()>* before_msgs) {
+  std::lock_guard<std::mutex> g(d.ed_mu[slot]);
+  DevBuf& ws = d.ed_ws[slot];
+  Fence& ev = d.ed_ev[slot];
+  // the budget's Ed25519 shares (cordahip_init, device_budget): slot 1 only serves the
+  // alternating chunks of the pipelines (host batches, streams, signed-tx chunks) and
+  // holds at most half of slot 0. The launch loops over whatever the workspace holds,
+  // so a smaller one only costs extra launch pairs.
+  const uint64_t cap_lanes = d.ed_ws_lanes[slot ? 1 : 0];
+  const uint64_t lanes = std::min<uint64_t>(cap_lanes, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
+  const uint64_t lane_bytes = ed25519_ws_lane_bytes();
+  hipError_t e = ev.grow(ws.cap < lanes * lane_bytes, [&] {
+    uint64_t want = std::max<uint64_t>(lanes, std::min<uint64_t>(cap_lanes, kWsMinLanes));
+    const uint64_t had = ws.cap / lane_bytes / 64 * 64;  // ensure() frees it before allocating
+    hipError_t g = ws.ensure(want * lane_bytes);
+    // HBM shared with other work: halve the request until it fits (at least
+    // what the slot held before, or one wave's lanes) instead of failing the call
+    while (g == hipErrorOutOfMemory && want > std::max<uint64_t>(64, had)) {
+      (void)hipGetLastError();
+      want = std::max<uint64_t>(std::max<uint64_t>(64, had), want / 2 / 64 * 64);
+      g = ws.ensure(want * lane_bytes);
+    }
+    return g;
+  });
+  e = e ? e : ev.wait(s);
+  e = e ? e
+        : launch_ed25519_verify(keys, sigs, msgs, msg_len, n, d.btab.as<uint32_t>(), pre, status, verdict,
+                                ws.as<uint32_t>(), ws.cap / lane_bytes / 64 * 64, flags, s, before_msgs);
+  return e ? e : ev.record(s);
+}
+
+// The Ed25519 section of a device signed-tx call (32-byte messages in HBM, on the
+// caller's stream s): chunks of CORDAHIP_DEVICE_ED_CHUNK signatures (default
+// 98,304 = 0.75 of a ladder round of 2 waves x 1,024 SIMDs x 64 lanes; 0: one
+// launch pair) alternate between s with workspace slot 0 and the device's s_ed2
+// with slot 1, the short remainder first. Every ladder wave takes about the same
+// time, so one launch over C4's 2.5 M signatures (19.07 rounds) ran 20 rounds, its
+// last with 7% of the CUs; alternating chunks let chunk k + 1's prep fill chunk k's
+// ladder tail, as the host pipelines do. Two streams hold two chunks, so a chunk
+// below half a round leaves CUs idle (2^15: C4 64.7 M sig/s). One box
+// (profiles/r06_device_ed_chunk_ab/): C4 93.4-94.5 with one launch pair, 95.1-96.4
+// at 2^17, 95.8-96.7 at 2^16, 97.0-97.7 at 98,304; C4 --device-encode 87.1-87.2,
+// 88.7-89.2, 89.3-89.4, 89.2-89.2.
+hipError_t ed_verify_device_chunks(Device& d, TxSet& S, const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs,
+                                   uint64_t n, uint8_t* status, hipStream_t s) {
+  static const uint64_t chunk = [] {
+    const char* v = getenv("CORDAHIP_DEVICE_ED_CHUNK");
+    return v ? (uint64_t)strtoull(v, nullptr, 10) / 64 * 64 : (uint64_t)98304;
+  }();
+  if (!chunk || n <= chunk || !d.s_ed2)
+    return ed_verify_enqueue(d, keys, sigs, msgs, 32, n, nullptr, status, nullptr, 0u, s, 0, nullptr);
+  hipError_t e = hipEventRecord(S.ed_fork, s);
+  e = e ? e : hipStreamWaitEvent(d.s_ed2, S.ed_fork, 0);
+  const uint64_t r = n % chunk;
+  uint64_t lo = 0;
+  for (int k = 0; lo < n && e == hipSuccess; k++) {
+    const uint64_t hi = lo + (k == 0 && r ? r : chunk);
+    e = ed_verify_enqueue(d, keys + lo * 32, sigs + lo * 64, msgs + lo * 32, 32, hi - lo, nullptr, status + lo,
+                          nullptr, 0u, k % 2 ? d.s_ed2 : s, k % 2, nullptr);
+    lo = hi;
+  }
+  e = e ? e : hipEventRecord(S.ed_join, d.s_ed2);
+  return e ? e : hipStreamWaitEvent(s, S.ed_join, 0);
+}
+
+// CORDAHIP_DEVICE_MEM_BUDGET (bytes, K/M/G suffixes; default 128 GiB, at most 90%
+// of the device): the workspaces it sizes -- Ed25519 slot 0 45% of it, slot 1 20%
+// (and half of slot 0 at most), ECDSA 15% -- each also capped by its r05 maximum
+// (2^24 lanes / slots, CORDAHIP_ED25519_WS_LANES / CORDAHIP_ECDSA_WS_SLOTS). The
+// default therefore keeps C2's single 2^24-lane launch pair (53.7 GB) and the
+// r05 peak: 53.7 + 26.8 + 18.8 GB of workspaces. The other buffers follow the
+// batches (the id and signature stages, component slices, C5's stages) and are
+// not split. A smaller budget costs extra launch pairs, never a failed batch.
+uint64_t parse_bytes(const char* v, uint64_t dflt) {
+  if (!v || !*v) return dflt;
+  char* end = nullptr;
+  const double x = strtod(v, &end);
+  if (end == v || x <= 0) return dflt;
+  const char u = end ? (char)toupper((unsigned char)*end) : 0;
+  const double m = u == 'K' ? 1024.0 : u == 'M' ? 1048576.0 : u == 'G' ? 1073741824.0 : 1.0;
+  return (uint64_t)(x * m);
+}
+
+void device_budget(Device& d) {  // device current
+  uint64_t b = parse_bytes(getenv("CORDAHIP_DEVICE_MEM_BUDGET"), 128ull << 30);
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) == hipSuccess && tot) b = std::min<uint64_t>(b, (uint64_t)tot / 10 * 9);
+  d.mem_budget = b;
+  auto lanes = [](uint64_t bytes, uint64_t per) { return std::max<uint64_t>(64, bytes / per / 64 * 64); };
+  const uint64_t lb = ed25519_ws_lane_bytes(), sb = ecdsa_ws_slot_bytes();
+  d.ed_ws_lanes[0] = std::min(env_lanes("CORDAHIP_ED25519_WS_LANES", kEdWsLanes), lanes(b / 100 * 45, lb));
+  d.ed_ws_lanes[1] = std::min(std::max<uint64_t>(64, d.ed_ws_lanes[0] / 2 / 64 * 64), lanes(b / 5, lb));
+  d.ec_ws_slots = std::min(env_lanes("CORDAHIP_ECDSA_WS_SLOTS", kEcWsSlots), lanes(b / 100 * 15, sb));
+}
+
+// Free an idle device's grow-only buffers (the idle release, cordahip_trim): both
+// buffer sets and every lock that guards a buffer, in an order every path keeps;
+// Device::release_idle then waits for the fences of the device-path users (kernels
+// on caller streams) and frees what it does not keep (the fixed tables, the
+// encoder's shape table and the ECDSA counters stay: derived data, 18 MB).
+void trim_device(Device& d) {
+  SetLease l0(d, 0, true), l1(d, 1, true);
+  std::lock_guard<std::mutex> gk(d.kryo_mu), gs(d.stream_mu), gp(d.ped_mu), ge0(d.ed_mu[0]), ge1(d.ed_mu[1]),
+      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu), gv(d.cover_mu);
+  if (hipSetDevice(d.id) != hipSuccess) return;
+  d.release_idle();
+  if (tracing()) fprintf(stderr, "[cordahip] dev %d: idle buffers released\n", d.id);
+}
+
+// the in-process partition rule (cordahip_shard_range)
+void shard_range(uint64_t n, uint64_t nshards, uint64_t shard, uint64_t align, uint64_t& lo, uint64_t& hi) {
+  if (nshards == 0 || shard >= nshards) {
+    lo = hi = n;
+    return;
+  }
+  align = align ? align : 1;
+  const uint64_t per = ((n + nshards - 1) / nshards + align - 1) / align * align;
+  lo = std::min(n, shard * per);
+  hi = std::min(n, lo + per);
+}
+
+}  // namespace rt
+}  // namespace cordahip
+
+static std::atomic<uint64_t> g_device_uid{1};
+
+extern "C" {
+
+static int init_impl(uint32_t device_mask, cordahip_ctx** out) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return CORDAHIP_ERR_NO_DEVICE;
+  auto ctx = std::make_unique<cordahip_ctx>();
+  int rc = CORDAHIP_SUCCESS;
+  // Test-only: CORDAHIP_TEST_DEVICE_REPLICAS=k gives the context k Device
+  // objects per selected HIP device (each with its own streams, buffers and
+  // tables), so the N-device code -- shard split, per-device workers, tails,
+  // verdict reassembly -- runs on a one-GPU box. Unset in production.
+  int replicas = 1;
+  if (const char* v = getenv("CORDAHIP_TEST_DEVICE_REPLICAS")) replicas = std::max(1, std::min(8, atoi(v)));
+  std::vector<int> ids;
+  for (int d = 0; d < count && d < kMaxHipDevices; d++)
+    if (!device_mask || ((device_mask >> d) & 1u))
+      for (int r = 0; r < replicas; r++) ids.push_back(d);
+  for (int d : ids) {
+    if (rc != CORDAHIP_SUCCESS) break;
+    ctx->devs.push_back(std::make_unique<Device>());
+    Device& dev = *ctx->devs.back();
+    dev.bind(d);
+    dev.uid = g_device_uid.fetch_add(1);
+    if (hipSetDevice(d) != hipSuccess || hipStreamCreateWithFlags(&dev.stream, hipStreamNonBlocking) != hipSuccess) {
+      rc = CORDAHIP_ERR_HIP;
+      break;
+    }
+    for (TxSet& S : dev.set)
+      for (hipEvent_t* pe : {&S.fork, &S.ids, &S.ed_fork, &S.ed_join})
+        if (hipEventCreateWithFlags(pe, hipEventDisableTiming) != hipSuccess) rc = CORDAHIP_ERR_HIP;
+    if (rc != CORDAHIP_SUCCESS) break;
+    for (auto& tc : dev.ring)
+      if (hipEventCreate(&tc.a) != hipSuccess || hipEventCreate(&tc.b) != hipSuccess) rc = CORDAHIP_ERR_HIP;
+    if (rc != CORDAHIP_SUCCESS) break;
+    if (dev.btab.ensure(ed25519_btable_bytes()) || dev.gtab_k1.ensure(ecdsa_gtable_bytes()) ||
+        dev.gtab_r1.ensure(ecdsa_gtable_bytes())) {
+      rc = CORDAHIP_ERR_OUT_OF_MEMORY;
+      break;
+    }
+    device_budget(dev);
+    static const bool id_prio = !(getenv("CORDAHIP_ID_PRIO") && getenv("CORDAHIP_ID_PRIO")[0] == '0');
+    if (!id_prio && (tx_set_id_priority(0) != hipSuccess || kryo_set_priority(0) != hipSuccess)) {
+      rc = CORDAHIP_ERR_HIP;
+      break;
+    }
+    if (launch_ed25519_btable(dev.btab.as<uint32_t>(), dev.stream) != hipSuccess ||
+        launch_ecdsa_gtables(dev.gtab_k1.as<uint32_t>(), dev.gtab_r1.as<uint32_t>(), dev.stream) != hipSuccess ||
+        hipStreamSynchronize(dev.stream) != hipSuccess)
+      rc = CORDAHIP_ERR_HIP;
+  }
+  if (rc == CORDAHIP_SUCCESS && ctx->devs.empty()) rc = CORDAHIP_ERR_NO_DEVICE;
+  if (rc != CORDAHIP_SUCCESS) return rc;  // ~Device frees what the devices got
+  ctx->pool = std::make_unique<WorkerPool>((int)std::max<size_t>(2, 2 * ctx->devs.size()));
+  // host threads. Per device (numa_place.hpp): a pool bound to CPUs of the GPU's
+  // NUMA node -- the devices of one node split its CPUs -- of CORDAHIP_HOST_THREADS
+  // threads at most (default 16: the pipelines are PCIe / kernel bound beyond that,
+  // tools/pack_bench.cpp); CORDAHIP_NUMA=0 leaves them unbound. Context-wide: a
+  // pool for the batch-level passes (CSR checks, verdict words) of at most 16.
+  int cap = 16;
+  if (const char* v = getenv("CORDAHIP_HOST_THREADS")) cap = std::max(1, std::min(256, atoi(v)));
+  std::vector<int> allowed;
+  {
+    cpu_set_t cs;
+    if (sched_getaffinity(0, sizeof(cs), &cs) == 0)
+      for (int c = 0; c < CPU_SETSIZE; c++)
+        if (CPU_ISSET(c, &cs)) allowed.push_back(c);
+  }
+  if (allowed.empty())
+    for (int c = 0; c < (int)std::max(1u, std::thread::hardware_concurrency()); c++) allowed.push_back(c);
+  std::vector<std::string> pci(ctx->devs.size());
+  const bool numa = !(getenv("CORDAHIP_NUMA") && getenv("CORDAHIP_NUMA")[0] == '0');
+  for (size_t i = 0; i < ctx->devs.size() && numa; i++) {
+    char bus[64] = {0};
+    if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus) - 1, ctx->devs[i]->id) == hipSuccess) {
+      pci[i] = bus;
+      for (char& ch : pci[i]) ch = (char)tolower((unsigned char)ch);
+    }
+  }
+  const char* root = getenv("CORDAHIP_SYSFS_ROOT");  // tests: a fake tree
+  const std::vector<NumaPlace> plan = numa_plan(root ? root : "/sys", pci, allowed, cap);
+  for (size_t i = 0; i < ctx->devs.size(); i++) {
+    Device& d = *ctx->devs[i];
+    d.place = plan[i];
+    if (!numa) d.place.cpus.clear();
+    d.pool = std::make_unique<HostPool>(d.place.threads, d.place.cpus);
+    if (tracing())
+      fprintf(stderr, "[cordahip] dev %d (%s): NUMA node %d, %zu CPUs, %d host threads%s%s\n", d.id, pci[i].c_str(),
+              d.place.node, d.place.cpus.size(), d.place.threads, d.place.why.empty() ? "" : ": ",
+              d.place.why.c_str());
+  }
+  ctx->host = std::make_unique<HostPool>(std::max(1, std::min<int>((int)allowed.size(), 16)));
+  // the idle release: a device with no call for CORDAHIP_IDLE_RELEASE_MS (default 30 s;
+  // 0: never) gives its grow-only buffers back (trim_device)
+  const char* iv = getenv("CORDAHIP_IDLE_RELEASE_MS");
+  const int64_t idle_ms = iv ? strtoll(iv, nullptr, 10) : 30000;
+  if (idle_ms > 0) {
+    cordahip_ctx* c = ctx.get();
+    c->reaper = std::thread([c, idle_ms] {
+      std::vector<int64_t> trimmed_at(c->devs.size(), 0);  // the last call's end when last trimmed
+      std::unique_lock<std::mutex> g(c->reaper_mu);
+      while (!c->reaper_stop) {
+        c->reaper_cv.wait_for(g, std::chrono::milliseconds(std::min<int64_t>(250, idle_ms)));
+        if (c->reaper_stop) break;
+        for (size_t i = 0; i < c->devs.size(); i++) {
+          Device& d = *c->devs[i];
+          const int64_t last = d.last_use_ms.load();
+          if (d.active.load() > 0 || last == 0 || last == trimmed_at[i] || (int64_t)now_ms() - last < idle_ms)
+            continue;
+          g.unlock();
+          trim_device(d);
+          g.lock();
+          trimmed_at[i] = last;
+        }
+      }
+    });
+  }
+  *out = ctx.release();
+  return CORDAHIP_SUCCESS;
+}
+
+int cordahip_init(uint32_t device_mask, cordahip_ctx** out) {
+  if (!out) return CORDAHIP_ERR_INVALID_ARG;
+  *out = nullptr;
+  return guarded([&] { return init_impl(device_mask, out); });
+}
+
+void cordahip_shutdown(cordahip_ctx* ctx) {
+  if (!ctx) return;
+  if (ctx->reaper.joinable()) {
+    {
+      std::lock_guard<std::mutex> g(ctx->reaper_mu);
+      ctx->reaper_stop = true;
+    }
+    ctx->reaper_cv.notify_all();
+    ctx->reaper.join();
+  }
+  ctx->pool.reset();  // runs every queued job to completion, joins the workers
+  ctx->host.reset();
+  {
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ctx->jobs.clear();
+  }
+  delete ctx;  // ~Device frees each device's buffers, events and streams
+}
+
+}  // extern "C"

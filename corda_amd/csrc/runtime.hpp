@@ -1,12 +1,13 @@
-// libcordahip's internal runtime types (not ABI): per-device state, buffers,
-// the ticket pool, the host thread pool and the enqueue helpers shared by
-// cordahip.cpp (C-ABI, tx / stream / device paths) and host_batch.cpp (the
-// generic CSR signature batch).
+// libcordahip's internal runtime types (not ABI): per-device state and what it
+// owns (buffers, fences, events, streams), the ticket pool, the host thread pool
+// and the enqueue helpers (runtime.cpp) shared by cordahip.cpp (C-ABI, tx /
+// stream / device paths) and host_batch.cpp (the generic CSR signature batch).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cstdlib>
 #include <condition_variable>
@@ -123,10 +124,11 @@ hipError_t launch_ecdsa_sign(const uint8_t* scheme, const uint8_t* seeds, const 
 
 namespace rt {
 
-// The library's device memory per HIP device (every DevBuf, the fixed tables):
-// bytes in use and their peak, for cordahip_device_mem and the budget
-// (CORDAHIP_DEVICE_MEM_BUDGET) that sizes the workspaces.
-constexpr int kMaxHipDevices = 64;
+// The library's device memory per HIP device (every DevBuf, the fixed tables
+// included): bytes in use and their peak, for cordahip_device_mem and the budget
+// (CORDAHIP_DEVICE_MEM_BUDGET) that sizes the workspaces. Process-wide: every
+// context (and test replica) on one GPU charges the same account.
+constexpr int kMaxHipDevices = 32;  // cordahip_init takes a 32-bit device mask
 struct MemAcct {
   std::atomic<uint64_t> in_use{0}, peak{0};
   void add(uint64_t b) {
@@ -137,9 +139,13 @@ struct MemAcct {
   }
   void sub(uint64_t b) { in_use.fetch_sub(b); }
 };
-MemAcct& mem_acct(int dev);
+inline MemAcct& mem_acct(int dev) {
+  static MemAcct acct[kMaxHipDevices];
+  assert(dev >= 0 && dev < kMaxHipDevices);
+  return acct[dev];
+}
 
-// grow-only device buffer (accounted on the device it was allocated on)
+// grow-only device buffer, accounted on its owner's HIP device (Device::bind)
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
@@ -147,12 +153,9 @@ struct DevBuf {
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     release();
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess) d = 0;
     hipError_t e = hipMalloc(&p, bytes);
     if (e == hipSuccess) {
       cap = bytes;
-      dev = d;
       mem_acct(dev).add(bytes);
     } else {
       p = nullptr;
@@ -175,13 +178,12 @@ struct DevBuf {
 struct PinBuf {
   void* p = nullptr;
   size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
+  hipError_t ensure(size_t bytes, unsigned flags = hipHostMallocDefault) {
     if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    release();
+    hipError_t e = hipHostMalloc(&p, bytes, flags);
     if (e == hipSuccess) cap = bytes;
+    else p = nullptr;
     return e;
   }
   void release() {
@@ -193,6 +195,39 @@ struct PinBuf {
   T* as() const { return static_cast<T*>(p); }
 };
 
+// The event that fences buffers shared between streams: every user makes its
+// stream wait for the previous user's work, then records its own. Created on
+// first use; a fence never recorded holds nobody back.
+struct Fence {
+  hipEvent_t ev = nullptr;
+  hipError_t create() { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+  hipError_t sync() const { return ev ? hipEventSynchronize(ev) : hipSuccess; }  // the host waits
+  hipError_t wait(hipStream_t s) { return create() ? hipErrorUnknown : hipStreamWaitEvent(s, ev, 0); }
+  hipError_t record(hipStream_t s) { return create() ? hipErrorUnknown : hipEventRecord(ev, s); }
+  // Growing a buffer frees the smaller one, which the previous user's kernels (on
+  // whatever stream) may still be using: the host waits for them first. `ensure`
+  // ensures every buffer behind this fence; it runs only when `needed`.
+  template <class G>
+  hipError_t grow(bool needed, G&& ensure) const {
+    if (!needed) return hipSuccess;
+    const hipError_t e = sync();
+    return e ? e : ensure();
+  }
+};
+
+// What a struct below owns, it names once: its visit(v) passes every such member to
+// one of these. A visitor derives from Visitor and redefines what it acts on; events,
+// fences and streams may be null (created on first use).
+enum : bool { kFreed = false, kKept = true };
+struct Visitor {
+  void dev(DevBuf&, bool /*keep: derived data the idle release leaves in place*/) {}
+  void pin(PinBuf&, bool /*keep*/) {}
+  void fence(Fence&) {}
+  // staged: marks a pipeline stage's buffers free (the idle release waits for it, as for a fence)
+  void event(hipEvent_t&, bool /*staged*/) {}
+  void stream(hipStream_t&) {}
+};
+
 // one stage (buffer set) of the C5 streaming pipeline (cordahip_stream_verify);
 // its events order the reuse of the buffers, so the host never waits per chunk
 struct StreamStage {
@@ -200,6 +235,13 @@ struct StreamStage {
   hipEvent_t ed_done = nullptr, ec_done = nullptr;      // its kernels and status D2H done: buffers free
   DevBuf ed_keys, ed_sigs, ed_msgs, ed_status;
   DevBuf ec_scheme, ec_keys, ec_key_len, ec_sigs, ec_sig_len, ec_msgs, ec_status;
+  template <class V>
+  void visit(V& v) {
+    for (hipEvent_t* e : {&ed_copied, &ec_copied, &ed_done, &ec_done}) v.event(*e, false);
+    for (DevBuf* b : {&ed_keys, &ed_sigs, &ed_msgs, &ed_status, &ec_scheme, &ec_keys, &ec_key_len, &ec_sigs,
+                      &ec_sig_len, &ec_msgs, &ec_status})
+      v.dev(*b, kFreed);
+  }
 };
 constexpr int kStreamStages = 3;
 // lanes per chunk, both sections together (C5 A/B on one box, profiles/r02_c5_stream_ab.json:
@@ -216,6 +258,12 @@ struct PackStage {
   DevBuf d[9];
   bool pending = false;
   uint64_t tag0 = 0, tag1 = 0, tag2 = 0;  // which chunk is in flight (pipeline-defined)
+  template <class V>
+  void visit(V& v) {
+    for (hipEvent_t* e : {&copied, &done}) v.event(*e, false);
+    for (PinBuf& b : h) v.pin(b, kFreed);
+    for (DevBuf& b : d) v.dev(b, kFreed);
+  }
 };
 constexpr int kPackStages = 3;
 // Signed-tx batches keep more of their small (2^17-signature) chunks in flight:
@@ -246,12 +294,27 @@ struct BatchStage {
   bool direct = false;    // rows == lanes: statuses / verdict words went straight to the caller's pinned arrays
   DevBuf dverdict;        // the direct chunks' verdict words (wave ballots of the Ed25519 kernel)
   bool pending = false;
+  template <class V>
+  void visit(V& v) {
+    for (hipEvent_t* e : {&copied, &ed_done, &ec_done}) v.event(*e, true);
+    for (PinBuf& b : h) v.pin(b, kFreed);
+    for (DevBuf& b : d) v.dev(b, kFreed);
+    for (PinBuf& b : hidx) v.pin(b, kFreed);
+    for (DevBuf& b : didx) v.dev(b, kFreed);
+    v.dev(dverdict, kFreed);
+  }
 };
 
 struct TxWork {  // device buffers of the transaction paths (grow-only)
   DevBuf leaf_bytes, leaf_off, tx_leaf_off, hashes, txid, tx_status, tx_sig_off, msgs;
   DevBuf comp_items, payload, comp_status;  // component-level batches: items, their payload, encoder statuses
   DevBuf tok, tok_hash, tx_tok_off, root, stack;  // filtered-tx (partial Merkle tree) path
+  template <class V>
+  void visit(V& v) {
+    for (DevBuf* b : {&leaf_bytes, &leaf_off, &tx_leaf_off, &hashes, &txid, &tx_status, &tx_sig_off, &msgs,
+                      &comp_items, &payload, &comp_status, &tok, &tok_hash, &tx_tok_off, &root, &stack})
+      v.dev(*b, kFreed);
+  }
 };
 
 // One set of a device's transaction and signature-pipeline buffers. A call
@@ -259,11 +322,11 @@ struct TxWork {  // device buffers of the transaction paths (grow-only)
 // work enqueued on the set's device buffers (the next holder's first wait).
 struct TxSet {
   TxWork tx;
-  hipEvent_t tx_ev = nullptr;
+  Fence tx_ev;
   BatchStage pb[kTxStages];  // generic CSR batches (the first kPackStages) and the signed-tx signature chunks
   // component calls: the encoder's usage counters after this set's last call,
   // host-mapped: [templates in the arena, table slots in use, misses of set 0, of set 1]
-  uint32_t* kryo_usage = nullptr;
+  PinBuf kryo_usage;
   uint32_t* kryo_usage_dev = nullptr;
   // the device signed-tx calls' fork / join: the id chain runs on the id stream beside
   // the key half of the Ed25519 prep on the caller's stream
@@ -271,13 +334,28 @@ struct TxSet {
   // their chunked Ed25519 section (ed_verify_device_chunks): s_ed2 forks off the
   // caller's stream and joins it again
   hipEvent_t ed_fork = nullptr, ed_join = nullptr;
+  template <class V>
+  void visit(V& v) {
+    tx.visit(v);
+    v.fence(tx_ev);
+    for (BatchStage& st : pb) st.visit(v);
+    v.pin(kryo_usage, kKept);
+    for (hipEvent_t* e : {&fork, &ids, &ed_fork, &ed_join}) v.event(*e, false);
+  }
 };
 constexpr int kTxSets = 2;
 
 struct EcWork {  // device buffers of the ECDSA paths (grow-only)
   DevBuf counters, perm;
-  DevBuf ws;                 // split-kernel workspace (kEcWsSlots records)
-  hipEvent_t ev = nullptr;   // last enqueued user of counters/perm/ws (cross-stream reuse)
+  DevBuf ws;  // split-kernel workspace (kEcWsSlots records)
+  Fence ev;   // last enqueued user of counters/perm/ws (cross-stream reuse)
+  template <class V>
+  void visit(V& v) {
+    v.dev(counters, kKept);
+    v.dev(perm, kFreed);
+    v.dev(ws, kFreed);
+    v.fence(ev);
+  }
 };
 
 // RSA (rsa.hip): the verify launches' workspace and the single stage of the
@@ -286,9 +364,44 @@ struct EcWork {  // device buffers of the ECDSA paths (grow-only)
 // allocated before a device's first RSA lane.
 struct RsaWork {
   DevBuf ws;
-  hipEvent_t ev = nullptr;  // last enqueued user of ws (cross-stream reuse)
+  Fence ev;  // last enqueued user of ws (cross-stream reuse)
   PinBuf h[7];
   DevBuf d[7];
+  template <class V>
+  void visit(V& v) {
+    v.dev(ws, kFreed);
+    v.fence(ev);
+    for (PinBuf& b : h) v.pin(b, kFreed);
+    for (DevBuf& b : d) v.dev(b, kFreed);
+  }
+};
+
+// Fork-join pool for host-side packing and scattering. parallel_for splits
+// [0, n) into pieces of at least `grain` lanes; the caller runs pieces too,
+// so concurrent callers (one pipeline per device and section) all progress.
+class HostPool {
+ public:
+  // cpus non-empty: every worker thread is bound to them (a device's NUMA node)
+  explicit HostPool(int nthreads, const std::vector<int>& cpus = {});
+  ~HostPool();
+  int threads() const { return (int)threads_.size() + 1; }
+  void parallel_for(uint64_t n, uint64_t grain, const std::function<void(uint64_t, uint64_t)>& fn);
+
+ private:
+  struct Job {
+    const std::function<void(uint64_t, uint64_t)>* fn = nullptr;
+    uint64_t n = 0, piece = 0, npieces = 0;
+    std::atomic<uint64_t> next{0}, done{0};
+    std::mutex m;
+    std::condition_variable cv;
+  };
+  static void run_pieces(Job& j);
+  void worker();
+  std::mutex m_;
+  std::condition_variable cv_;
+  std::deque<std::shared_ptr<Job>> q_;
+  std::vector<std::thread> threads_;
+  bool stop_ = false;
 };
 
 // Per-call timing of the *_device entry points: a ring of event pairs per
@@ -299,8 +412,6 @@ struct TimedCall {
   hipEvent_t a = nullptr, b = nullptr;
   uint64_t gen = 0;
 };
-
-class HostPool;
 
 struct Device {
   int id = 0;
@@ -319,9 +430,8 @@ struct Device {
   uint64_t ec_ws_slots = 0;
   std::atomic<int> active{0};
   std::atomic<int64_t> last_use_ms{0};
-  uint32_t* btab = nullptr;
-  uint32_t* gtab_k1 = nullptr;  // [k]G tables, k = 0..128, secp256k1 / P-256
-  uint32_t* gtab_r1 = nullptr;
+  DevBuf btab;              // the fixed-base tables, built once by cordahip_init
+  DevBuf gtab_k1, gtab_r1;  // [k]G tables, k = 0..128, secp256k1 / P-256
   // ECDSA workspaces: slot 0 for the device path and the stream drain, slot 1 for the
   // host pipelines' alternate chunks (capped at half of slot 0), each with its lock;
   // ec_turn alternates the host chunks between them (s_ec / s_ec2)
@@ -360,7 +470,7 @@ struct Device {
   // k's end-of-grid tail leaves idle (slot 0 alone serves the device paths).
   std::mutex ed_mu[2];
   DevBuf ed_ws[2];
-  hipEvent_t ed_ev[2] = {nullptr, nullptr};
+  Fence ed_ev[2];
   // The pipelines' three streams, created together and shared by the C5 drain
   // and the packed host pipelines: every H2D on s_copy (PCIe in chunk order),
   // each section's kernels + status D2H on its own stream. Three active
@@ -390,44 +500,84 @@ struct Device {
   // a host-mapped copy of its usage counters, stored after each call)
   bool kryo_fresh = false;
   bool kryo_templates_ok = false;  // the last component batch had no encoder misses (cordahip.cpp)
-  uint32_t* kryo_usage = nullptr;      // cordahip_kryo_encode_device's own report
+  PinBuf kryo_usage;               // cordahip_kryo_encode_device's own report
   uint32_t* kryo_usage_dev = nullptr;
   uint64_t kryo_gen = 0;           // table clears so far (kryo_mu): a call's end updates kryo_templates_ok
                                    // only if no clear came after its start
-  hipEvent_t kryo_ev = nullptr;
+  Fence kryo_ev;
   // cordahip_tx_cover_device: the trees' evaluation stacks (8 B per token);
   // cover_mu orders the enqueues, cover_ev fences the scratch across streams
   std::mutex cover_mu;
   DevBuf cover_stack;
-  hipEvent_t cover_ev = nullptr;
-};
+  Fence cover_ev;
 
-// Fork-join pool for host-side packing and scattering. parallel_for splits
-// [0, n) into pieces of at least `grain` lanes; the caller runs pieces too,
-// so concurrent callers (one pipeline per device and section) all progress.
-class HostPool {
- public:
-  // cpus non-empty: every worker thread is bound to them (a device's NUMA node)
-  explicit HostPool(int nthreads, const std::vector<int>& cpus = {});
-  ~HostPool();
-  int threads() const { return (int)threads_.size() + 1; }
-  void parallel_for(uint64_t n, uint64_t grain, const std::function<void(uint64_t, uint64_t)>& fn);
-
- private:
-  struct Job {
-    const std::function<void(uint64_t, uint64_t)>* fn = nullptr;
-    uint64_t n = 0, piece = 0, npieces = 0;
-    std::atomic<uint64_t> next{0}, done{0};
-    std::mutex m;
-    std::condition_variable cv;
+  template <class V>
+  void visit(V& v) {
+    for (DevBuf* b : {&btab, &gtab_k1, &gtab_r1}) v.dev(*b, kKept);
+    for (EcWork& w : ec) w.visit(v);
+    rsa.visit(v);
+    for (hipStream_t* s : {&s_rsa, &stream, &s_copy, &s_ed, &s_ec, &s_ed2, &s_idcopy}) v.stream(*s);  // s_ec2 is s_idcopy
+    for (TimedCall& tc : ring)
+      for (hipEvent_t* e : {&tc.a, &tc.b}) v.event(*e, false);
+    for (TxSet& S : set) S.visit(v);
+    for (DevBuf& b : ed_ws) v.dev(b, kFreed);
+    for (Fence& f : ed_ev) v.fence(f);
+    for (StreamStage& st : sstage) st.visit(v);
+    for (PackStage& st : ped) st.visit(v);
+    for (DevBuf* b : {&kryo_sizes, &kryo_temp, &kryo_ws, &kryo_items}) v.dev(*b, kFreed);
+    v.dev(kryo_fixed, kKept);
+    v.pin(kryo_usage, kKept);
+    v.fence(kryo_ev);
+    v.dev(cover_stack, kFreed);
+    v.fence(cover_ev);
+  }
+  // before any allocation: the HIP device whose account the buffers charge
+  void bind(int hip_id) {
+    struct Bind : Visitor {
+      int id;
+      void dev(DevBuf& b, bool) { b.dev = id; }
+    } v;
+    id = v.id = hip_id;
+    visit(v);
+  }
+  struct Release : Visitor {  // the buffers; all: the kept ones too
+    bool all = false;
+    void dev(DevBuf& b, bool keep) {
+      if (all || !keep) b.release();
+    }
+    void pin(PinBuf& b, bool keep) {
+      if (all || !keep) b.release();
+    }
   };
-  static void run_pieces(Job& j);
-  void worker();
-  std::mutex m_;
-  std::condition_variable cv_;
-  std::deque<std::shared_ptr<Job>> q_;
-  std::vector<std::thread> threads_;
-  bool stop_ = false;
+  // the idle release's part once the caller holds every lock that guards a buffer
+  // (trim_device): waits for the fences and the stages' events, then frees what is not kept
+  void release_idle() {
+    struct Quiesce : Visitor {
+      void fence(Fence& f) { (void)f.sync(); }
+      void event(hipEvent_t& e, bool staged) {
+        if (staged && e) (void)hipEventSynchronize(e);
+      }
+    } q;
+    visit(q);
+    Release r;
+    visit(r);
+  }
+  ~Device() {  // everything visited
+    (void)hipSetDevice(id);
+    struct Destroy : Release {
+      void fence(Fence& f) { event(f.ev, false); }
+      void event(hipEvent_t& e, bool) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+      }
+      void stream(hipStream_t& s) {
+        if (s) (void)hipStreamDestroy(s);
+        s = nullptr;
+      }
+    } v;
+    v.all = true;
+    visit(v);
+  }
 };
 
 // The calling thread bound to a device's CPUs for a scope (its previous affinity
@@ -523,7 +673,23 @@ hipError_t blocked(const char* what, F&& f) {
 }
 
 int hip_err(hipError_t e);
+// Entry points run host code that allocates (staging vectors, worker threads): no
+// C++ exception may cross the C ABI into the JVM.
+template <class F>
+int guarded(F&& f) noexcept {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return CORDAHIP_ERR_OUT_OF_MEMORY;
+  } catch (...) {
+    return CORDAHIP_ERR_HIP;
+  }
+}
 hipError_t ensure_streams(Device& d);
+void trim_device(Device& d);  // the idle release of one device (cordahip_trim, the reaper)
+// the Ed25519 section of a device signed-tx call, in chunks on two streams
+hipError_t ed_verify_device_chunks(Device& d, TxSet& S, const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs,
+                                   uint64_t n, uint8_t* status, hipStream_t s);
 // before_msgs != nullptr: the messages are produced on stream s by that callback,
 // which runs after the keys' half of the prep is enqueued (launch_ed25519_verify)
 hipError_t ed_verify_enqueue(Device& d, const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs,
@@ -619,7 +785,7 @@ struct cordahip_ctx {
   std::mutex txof_mu;
   std::vector<std::pair<std::unique_ptr<uint64_t[]>, uint64_t>> txof_free;
   // the idle release (CORDAHIP_IDLE_RELEASE_MS): a thread that frees an idle
-  // device's grow-only buffers (cordahip.cpp trim_device)
+  // device's grow-only buffers (runtime.cpp trim_device)
   std::thread reaper;
   std::mutex reaper_mu;
   std::condition_variable reaper_cv;

@@ -90,8 +90,9 @@ int cordahip_device_count(const cordahip_ctx* ctx);
 
 /* Device memory (ABI 4). cordahip_device_mem: the bytes the library holds on
  * `device`'s GPU now and at most so far (workspaces, stages, fixed tables), and
- * its budget. The budget (CORDAHIP_DEVICE_MEM_BUDGET at cordahip_init, bytes
- * with an optional K/M/G suffix; default 128 GiB, at most 90% of the device)
+ * its budget. The two byte counts are per GPU and process-wide: every context
+ * on that GPU adds to them. The budget (CORDAHIP_DEVICE_MEM_BUDGET at
+ * cordahip_init, bytes with an optional K/M/G suffix; default 128 GiB, at most 90% of the device)
  * sizes the verification workspaces -- Ed25519 45% (+20% for the pipelines'
  * second slot), ECDSA 15%; a smaller budget only costs extra launches. The
  * batch-proportional buffers (stages, id buffers) follow the batches. Buffers

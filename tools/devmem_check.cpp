@@ -1,0 +1,240 @@
+// What a Device owns (corda_amd/csrc/runtime.hpp: the visit of its buffers, fences,
+// events and streams; Device::bind, release_idle and the destructor) against
+// counting fakes of the HIP calls that code links to -- host only, no GPU:
+// tests/test_devmem.py builds this with g++ -fsanitize=address,undefined and runs it.
+//  a  the visit reaches every DevBuf / PinBuf / event / stream the structs hold
+//     (sizeof of each struct = the bytes visited + its plain members)
+//  b  the idle release leaves exactly the kept buffers, and the account equals them
+//  c  after ~Device nothing is live and the account is zero (ASan: no leak either)
+//  d  the same for a half-initialised Device (hipMalloc failing midway, null events)
+//  e  two Devices charge the accounts of their own ids, whatever hipGetDevice says
+// prints one JSON line; exit status 1 and a message on the first failed check
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+#include <set>
+
+#include "../corda_amd/csrc/runtime.hpp"
+
+using namespace cordahip::rt;
+
+namespace {
+struct Fakes {
+  std::map<void*, size_t> dev, pin;
+  std::set<void*> events, streams;
+  long mallocs = 0, fail_malloc_at = -1;  // the fail_malloc_at-th hipMalloc from now fails
+  int set_device = -1;
+  void* handle() { return ::operator new(1); }
+  bool clean() const { return dev.empty() && pin.empty() && events.empty() && streams.empty(); }
+} g;
+
+void fail(const char* what) {
+  fprintf(stderr, "devmem_check: %s\n", what);
+  exit(1);
+}
+#define CHECK(x) \
+  if (!(x)) fail(#x)
+}  // namespace
+
+extern "C" {
+hipError_t hipMalloc(void** p, size_t bytes) {
+  if (g.mallocs++ == g.fail_malloc_at) return hipErrorOutOfMemory;
+  *p = g.handle();
+  g.dev[*p] = bytes;
+  return hipSuccess;
+}
+hipError_t hipFree(void* p) {
+  CHECK(g.dev.erase(p) == 1);
+  ::operator delete(p);
+  return hipSuccess;
+}
+hipError_t hipHostMalloc(void** p, size_t bytes, unsigned int) {
+  *p = g.handle();
+  g.pin[*p] = bytes;
+  return hipSuccess;
+}
+hipError_t hipHostFree(void* p) {
+  CHECK(g.pin.erase(p) == 1);
+  ::operator delete(p);
+  return hipSuccess;
+}
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
+  *e = static_cast<hipEvent_t>(g.handle());
+  g.events.insert(*e);
+  return hipSuccess;
+}
+hipError_t hipEventDestroy(hipEvent_t e) {
+  CHECK(g.events.erase(e) == 1);
+  ::operator delete(e);
+  return hipSuccess;
+}
+hipError_t hipEventSynchronize(hipEvent_t e) {
+  CHECK(g.events.count(e) == 1);
+  return hipSuccess;
+}
+hipError_t hipStreamDestroy(hipStream_t s) {
+  CHECK(g.streams.erase(s) == 1);  // an alias destroyed twice fails here
+  ::operator delete(s);
+  return hipSuccess;
+}
+hipError_t hipSetDevice(int id) {
+  g.set_device = id;
+  return hipSuccess;
+}
+hipError_t hipGetDevice(int* id) {  // nothing may ask: the answer is another device's
+  *id = 0;
+  return hipSuccess;
+}
+}
+// a Device's pool is never created here
+cordahip::rt::HostPool::~HostPool() {}
+
+namespace {
+struct Count : Visitor {
+  size_t ndev = 0, npin = 0, nfence = 0, nevent = 0, nstream = 0;
+  void dev(DevBuf&, bool) { ndev++; }
+  void pin(PinBuf&, bool) { npin++; }
+  void fence(Fence&) { nfence++; }
+  void event(hipEvent_t&, bool) { nevent++; }
+  void stream(hipStream_t&) { nstream++; }
+  size_t bytes() const {
+    return ndev * sizeof(DevBuf) + npin * sizeof(PinBuf) + nfence * sizeof(Fence) + nevent * sizeof(hipEvent_t) +
+           nstream * sizeof(hipStream_t);
+  }
+};
+// a: sizeof(T) is what the visit reached plus `plain` bytes of other members, so a
+// buffer or event added to T and not visited fails here (a plain member added: raise
+// `plain` by its size)
+template <class T>
+Count visited(T& t, size_t plain, const char* name) {
+  Count c;
+  t.visit(c);
+  if (sizeof(T) != c.bytes() + plain) {
+    fprintf(stderr, "devmem_check: %s: sizeof %zu, visited %zu + plain %zu -- a member is not visited?\n", name,
+            sizeof(T), c.bytes(), plain);
+    exit(1);
+  }
+  return c;
+}
+
+// the plain members of the structs that have some (bool: with its padding)
+constexpr size_t kPackPlain = 8 /* pending */ + 3 * sizeof(uint64_t);
+constexpr size_t kBatchPlain = 2 * sizeof(std::vector<uint64_t>) + 2 * sizeof(uint64_t) + 8 /* direct */ + 8 /* pending */;
+constexpr size_t kTxSetPlain = sizeof(uint32_t*) /* kryo_usage_dev */ + kTxStages * kBatchPlain;
+
+struct Grow : Visitor {  // every buffer a few bytes, every event and stream created
+  size_t k = 0;
+  bool events = true;
+  void dev(DevBuf& b, bool) { (void)b.ensure(8 + k++ % 5); }
+  void pin(PinBuf& b, bool) { (void)b.ensure(8 + k++ % 5); }
+  void fence(Fence& f) {
+    if (events) (void)f.create();
+  }
+  void event(hipEvent_t& e, bool) {
+    if (events && !e) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
+  }
+  void stream(hipStream_t& s) {
+    if (!events || s) return;
+    s = static_cast<hipStream_t>(g.handle());
+    g.streams.insert(s);
+  }
+};
+struct Kept : Visitor {
+  std::set<void*> devs, pins;
+  uint64_t bytes = 0;
+  void dev(DevBuf& b, bool keep) {
+    CHECK(keep ? b.p && b.cap : !b.p && !b.cap);
+    if (keep) devs.insert(b.p), bytes += b.cap;
+  }
+  void pin(PinBuf& b, bool keep) {
+    CHECK(keep ? b.p && b.cap : !b.p && !b.cap);
+    if (keep) pins.insert(b.p);
+  }
+};
+template <class M>
+std::set<void*> keys(const M& m) {
+  std::set<void*> s;
+  for (const auto& kv : m) s.insert(kv.first);
+  return s;
+}
+}  // namespace
+
+int main() {
+  // a: each struct on its own, then the whole Device
+  size_t ndev, npin, nev;
+  {
+    TxWork tw;
+    StreamStage ss;
+    PackStage ps;
+    BatchStage bs;
+    TxSet ts;
+    EcWork ew;
+    RsaWork rw;
+    visited(tw, 0, "TxWork");
+    visited(ss, 0, "StreamStage");
+    visited(ps, kPackPlain, "PackStage");
+    visited(bs, kBatchPlain, "BatchStage");
+    visited(ts, kTxSetPlain, "TxSet");
+    visited(ew, 0, "EcWork");
+    visited(rw, 0, "RsaWork");
+  }
+  auto* d = new Device;
+  d->bind(3);
+  {
+    // Device's plain members: ids, placement, pool, budget and workspace sizes, activity,
+    // the mutexes and condition variable, turn counters, ring generations, set_busy,
+    // s_ec2 (an alias), the encoder's flags and counters
+    constexpr size_t kDeviceOwnPlain = 1288;
+    const Count c = visited(*d, kDeviceOwnPlain + kTxSets * kTxSetPlain + kPackStages * kPackPlain, "Device");
+    ndev = c.ndev, npin = c.npin, nev = c.nfence + c.nevent;
+    CHECK(c.nstream == 7);
+  }
+  Grow grow;
+  d->visit(grow);
+  d->s_ec2 = d->s_idcopy;  // as ensure_streams leaves them
+  CHECK(g.dev.size() == ndev && g.pin.size() == npin && g.events.size() == nev && g.streams.size() == 7);
+  uint64_t all = 0;
+  for (const auto& kv : g.dev) all += kv.second;
+  CHECK(mem_acct(3).in_use.load() == all && mem_acct(3).peak.load() == all);
+  // b: the idle release
+  d->release_idle();
+  Kept kept;
+  d->visit(kept);
+  CHECK(kept.devs.size() == 3 + 2 + 1);  // the fixed tables, the ECDSA counters, the encoder's table
+  CHECK(keys(g.dev) == kept.devs && keys(g.pin) == kept.pins);
+  CHECK(mem_acct(3).in_use.load() == kept.bytes);
+  CHECK(g.events.size() == nev && g.streams.size() == 7);  // events and streams stay
+  d->visit(grow);  // and the device works again
+  CHECK(g.dev.size() == ndev && g.pin.size() == npin);
+  // c: destruction
+  g.set_device = -1;
+  delete d;
+  CHECK(g.set_device == 3 && g.clean() && mem_acct(3).in_use.load() == 0);
+  // d: half-initialised -- no events or streams, the 40th hipMalloc fails
+  d = new Device;
+  d->bind(4);
+  grow.events = false;
+  g.mallocs = 0;
+  g.fail_malloc_at = 40;
+  d->visit(grow);
+  g.fail_malloc_at = -1;
+  CHECK(g.dev.size() == ndev - 1 && g.events.empty() && g.streams.empty());
+  delete d;
+  CHECK(g.clean() && mem_acct(4).in_use.load() == 0);
+  delete new Device;  // never bound, nothing allocated
+  CHECK(g.clean());
+  // e: two devices, two accounts; hipGetDevice's answer (0) gets nothing
+  {
+    Device a, b;
+    a.bind(3);
+    b.bind(5);
+    (void)a.btab.ensure(1000);
+    (void)b.btab.ensure(10);
+    (void)b.cover_stack.ensure(7);
+    CHECK(mem_acct(3).in_use.load() == 1000 && mem_acct(5).in_use.load() == 17 && mem_acct(0).in_use.load() == 0);
+  }
+  CHECK(g.clean() && mem_acct(3).in_use.load() == 0 && mem_acct(5).in_use.load() == 0);
+  printf("{\"dev_bufs\": %zu, \"pin_bufs\": %zu, \"events\": %zu, \"streams\": 7, \"kept_dev_bufs\": %zu}\n", ndev, npin,
+         nev, kept.devs.size());
+  return 0;
+}
