@@ -39,6 +39,7 @@ EXPORTS = [
     "cordahip_rsa_public_op_device", "cordahip_rsa_pss_verify_device",
     "cordahip_cover_eval_host", "cordahip_signed_tx_verify_covered", "cordahip_tx_submit_covered",
     "cordahip_signed_txcomp_verify_covered", "cordahip_txcomp_submit_covered", "cordahip_tx_cover_device",
+    "cordahip_filtered_tx_build", "cordahip_filtered_tx_build_submit", "cordahip_filtered_tx_build_device",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
@@ -52,6 +53,9 @@ RSA_GROUP_LANES = 8  # lanes that share one signature in rsa_modexp_kernel (cord
 TX_NO_LEAVES, TX_NO_SIGNATURES, TX_BAD_TREE, TX_BAD_COMPONENT = 6, 7, 8, 9
 # required-signer coverage (cordahip_cover): tx statuses and req_status values
 TX_SIGNATURES_MISSING, TX_BAD_COVER = 10, 11
+# FilteredTransaction build (cordahip_filtered_tx_build): the count rule of PartialMerkleTree.build;
+# a token slot below the bound (device-resident call only)
+TX_HASHES_NOT_IN_TREE, TX_TOK_SLOT_TOO_SMALL = 12, 13
 REQ_FULFILLED, REQ_MISSING, REQ_MISSING_ALLOWED, REQ_NOT_EVALUATED, REQ_MALFORMED = 0, 1, 2, 3, 4
 
 
@@ -137,6 +141,28 @@ class FilteredTxBatch(ctypes.Structure):
         ("root", ctypes.c_void_p), ("tx_status", ctypes.c_void_p),
         ("nleaves", ctypes.c_uint64), ("leaf_bytes_len", ctypes.c_uint64), ("ntok", ctypes.c_uint64),  # ABI 4
     ]
+
+
+class FilteredBuildBatch(ctypes.Structure):
+    _fields_ = [
+        ("ntx", ctypes.c_uint64),
+        ("leaf_bytes", ctypes.c_void_p), ("leaf_off", ctypes.c_void_p), ("tx_leaf_off", ctypes.c_void_p),
+        ("include", ctypes.c_void_p), ("tx_tok_off", ctypes.c_void_p),
+        ("txid", ctypes.c_void_p), ("tok", ctypes.c_void_p), ("tok_hash", ctypes.c_void_p),
+        ("tx_ntok", ctypes.c_void_p), ("tx_status", ctypes.c_void_p),
+        ("nleaves", ctypes.c_uint64), ("leaf_bytes_len", ctypes.c_uint64), ("ntok", ctypes.c_uint64),
+    ]
+
+
+def pmt_slot_bound(m: int) -> int:
+    """Tokens the slot of an m-leaf transaction must hold in cordahip_filtered_tx_build:
+    2 * pad(m) - 1, pad(m) the next power of two >= m; 0 for m == 0."""
+    if m == 0:
+        return 0
+    p = 1
+    while p < m:
+        p *= 2
+    return 2 * p - 1
 
 
 class CoverTok(ctypes.Structure):
@@ -240,6 +266,10 @@ def lib() -> ctypes.CDLL:
         "cordahip_txcomp_submit_covered": (i32, [vp, ctypes.POINTER(SignedTxcompBatch), ctypes.POINTER(Cover),
                                                  ctypes.POINTER(u64)]),
         "cordahip_tx_cover_device": (i32, [vp, i32, u64, vp, vp, vp, vp, vp, ctypes.POINTER(Cover), vp]),
+        "cordahip_filtered_tx_build": (i32, [vp, ctypes.POINTER(FilteredBuildBatch)]),
+        "cordahip_filtered_tx_build_submit": (i32, [vp, ctypes.POINTER(FilteredBuildBatch), ctypes.POINTER(u64)]),
+        "cordahip_filtered_tx_build_device": (i32, [vp, i32, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp,
+                                                    vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(l, name)

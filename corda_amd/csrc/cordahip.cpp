@@ -1202,6 +1202,75 @@ int filtered_tx_impl(cordahip_ctx* ctx, const cordahip_filtered_tx_batch* b) {
   return for_shards(ctx->devs, n, 1, [&](Device& d, uint64_t t0, uint64_t t1) { return filtered_tx_shard(d, b, t0, t1); });
 }
 
+// FilteredTransaction build for txs [t0, t1) on one device: K3 hashes the
+// leaves, K10 builds each tree and writes its tokens into the caller's slot.
+// The shard's slots are the contiguous token range [tx_tok_off[t0], tx_tok_off[t1]),
+// which comes back whole (entries past a transaction's tx_ntok are unspecified).
+int filtered_build_shard(Device& d, const cordahip_filtered_build_batch* b, uint64_t t0, uint64_t t1) {
+  SetLease lease(d);
+  TxSet& S = lease.get();
+  const NodeBind nb(d);
+  const Activity act(d);
+  if (int rc = tx_acquire_host(d, S)) return rc;
+  const uint64_t ntx = t1 - t0;
+  const uint64_t l0 = b->tx_leaf_off[t0], l1 = b->tx_leaf_off[t1], nleaves = l1 - l0;
+  const uint64_t b0 = nleaves ? b->leaf_off[l0] : 0, b1 = nleaves ? b->leaf_off[l1] : 0;
+  const uint64_t k0 = b->tx_tok_off[t0], k1 = b->tx_tok_off[t1], ntok = k1 - k0;
+  std::vector<uint64_t> loff(nleaves + 1), toff(ntx + 1), koff(ntx + 1);
+  for (uint64_t i = 0; i <= nleaves; i++) loff[i] = nleaves ? b->leaf_off[l0 + i] - b0 : 0;
+  for (uint64_t i = 0; i <= ntx; i++) {
+    toff[i] = b->tx_leaf_off[t0 + i] - l0;
+    koff[i] = b->tx_tok_off[t0 + i] - k0;
+  }
+  TxWork& w = S.tx;
+  const uint64_t nl1 = std::max<uint64_t>(nleaves, 1);
+  if (w.leaf_bytes.ensure(std::max<uint64_t>(b1 - b0, 16)) || w.leaf_off.ensure((nleaves + 1) * 8) ||
+      w.tx_leaf_off.ensure((ntx + 1) * 8) || w.hashes.ensure(nl1 * 32) || w.incl.ensure(nl1) ||
+      w.pmt_up.ensure(nl1 * 64) || w.pmt_has.ensure(nl1 * 3) || w.tx_tok_off.ensure((ntx + 1) * 8) ||
+      w.tok.ensure(std::max<uint64_t>(ntok, 1)) || w.tok_hash.ensure(std::max<uint64_t>(ntok, 1) * 32) ||
+      w.txid.ensure(ntx * 32) || w.tx_ntok.ensure(ntx * 8) || w.tx_status.ensure(ntx))
+    return CORDAHIP_ERR_OUT_OF_MEMORY;
+  hipStream_t s = d.stream;
+  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
+  hipError_t e = hipSuccess;
+  if (b1 > b0) e = hipMemcpyAsync(w.leaf_bytes.p, b->leaf_bytes + b0, b1 - b0, h2d, s);
+  e = e ? e : hipMemcpyAsync(w.leaf_off.p, loff.data(), (nleaves + 1) * 8, h2d, s);
+  e = e ? e : hipMemcpyAsync(w.tx_leaf_off.p, toff.data(), (ntx + 1) * 8, h2d, s);
+  if (nleaves) e = e ? e : hipMemcpyAsync(w.incl.p, b->include + l0, nleaves, h2d, s);
+  e = e ? e : hipMemcpyAsync(w.tx_tok_off.p, koff.data(), (ntx + 1) * 8, h2d, s);
+  e = e ? e : launch_sha256_leaves(w.leaf_bytes.as<uint8_t>(), w.leaf_off.as<uint64_t>(), nleaves,
+                                   w.hashes.as<uint32_t>(), s);
+  e = e ? e : launch_pmt_build(w.hashes.as<uint32_t>(), w.tx_leaf_off.as<uint64_t>(), ntx, w.incl.as<uint8_t>(),
+                               w.tx_tok_off.as<uint64_t>(), ntok, w.pmt_up.as<uint32_t>(), w.pmt_has.as<uint8_t>(),
+                               w.txid.as<uint8_t>(), w.tok.as<uint8_t>(), w.tok_hash.as<uint8_t>(),
+                               w.tx_ntok.as<uint64_t>(), w.tx_status.as<uint8_t>(), s);
+  e = e ? e : hipMemcpyAsync(b->txid + t0 * 32, w.txid.p, ntx * 32, d2h, s);
+  e = e ? e : hipMemcpyAsync(b->tx_ntok + t0, w.tx_ntok.p, ntx * 8, d2h, s);
+  e = e ? e : hipMemcpyAsync(b->tx_status + t0, w.tx_status.p, ntx, d2h, s);
+  if (ntok) {
+    e = e ? e : hipMemcpyAsync(b->tok + k0, w.tok.p, ntok, d2h, s);
+    e = e ? e : hipMemcpyAsync(b->tok_hash + k0 * 32, w.tok_hash.p, ntok * 32, d2h, s);
+  }
+  e = e ? e : S.tx_ev.record(s);
+  e = e ? e : S.tx_ev.sync();
+  if (e != hipSuccess) (void)hipStreamSynchronize(s);
+  return hip_err(e);
+}
+
+int filtered_build_impl(cordahip_ctx* ctx, const cordahip_filtered_build_batch* b) {
+  const uint64_t n = b->ntx;
+  if (n == 0) return CORDAHIP_SUCCESS;
+  if (!b->leaf_off || !b->tx_leaf_off || !b->tx_tok_off || !b->txid || !b->tx_ntok || !b->tx_status)
+    return CORDAHIP_ERR_INVALID_ARG;
+  if (!check_filtered_build_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
+  // the offsets are sound: what they span must exist
+  const uint64_t l0 = b->tx_leaf_off[0], l1 = b->tx_leaf_off[n];
+  if (l0 != l1 && (!b->include || (b->leaf_off[l0] != b->leaf_off[l1] && !b->leaf_bytes))) return CORDAHIP_ERR_INVALID_ARG;
+  if (b->tx_tok_off[0] != b->tx_tok_off[n] && (!b->tok || !b->tok_hash)) return CORDAHIP_ERR_INVALID_ARG;
+  return for_shards(ctx->devs, n, 1,
+                    [&](Device& d, uint64_t t0, uint64_t t1) { return filtered_build_shard(d, b, t0, t1); });
+}
+
 Device* dev_at(cordahip_ctx* ctx, int device) {
   if (!ctx || device < 0 || device >= (int)ctx->devs.size()) return nullptr;
   return ctx->devs[device].get();
@@ -1486,6 +1555,55 @@ int cordahip_ed25519_verify_host(cordahip_ctx* ctx, const uint8_t* keys, const u
 int cordahip_filtered_tx_verify(cordahip_ctx* ctx, const cordahip_filtered_tx_batch* batch) {
   if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
   return guarded([&] { return filtered_tx_impl(ctx, batch); });
+}
+
+int cordahip_filtered_tx_build(cordahip_ctx* ctx, const cordahip_filtered_build_batch* batch) {
+  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return filtered_build_impl(ctx, batch); });
+}
+
+int cordahip_filtered_tx_build_submit(cordahip_ctx* ctx, const cordahip_filtered_build_batch* batch,
+                                      uint64_t* ticket) {
+  return submit(ctx, ticket, filtered_build_impl, batch);
+}
+
+int cordahip_filtered_tx_build_device(cordahip_ctx* ctx, int device, const void* d_leaf_bytes,
+                                      const void* d_leaf_off, uint64_t nleaves, const void* d_tx_leaf_off,
+                                      uint64_t ntx, const void* d_include, const void* d_tx_tok_off, uint64_t ntok,
+                                      void* d_txid, void* d_tok, void* d_tok_hash, void* d_tx_ntok,
+                                      void* d_tx_status, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || (ntx && (!d_leaf_off || !d_tx_leaf_off || !d_tx_tok_off || !d_txid || !d_tx_ntok || !d_tx_status)) ||
+      (ntx && nleaves && !d_include) || (ntx && ntok && (!d_tok || !d_tok_hash)))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if (nleaves > (1ull << 56)) return CORDAHIP_ERR_INVALID_ARG;  // the workspace sizes below stay in 64 bits
+  // a buffer set for the enqueue: its leaf hashes and tree levels, fenced by its
+  // event until these kernels finish (the next holder waits on it)
+  SetLease lease(*d);
+  TxSet& S = lease.get();
+  TxWork& w = S.tx;
+  const uint64_t nl1 = std::max<uint64_t>(nleaves, 1);
+  return device_call(
+      *d, hip_stream,
+      [&] {
+        return S.tx_ev.grow(w.hashes.cap < nl1 * 32 || w.pmt_up.cap < nl1 * 64 || w.pmt_has.cap < nl1 * 3, [&] {
+          return w.hashes.ensure(nl1 * 32) || w.pmt_up.ensure(nl1 * 64) || w.pmt_has.ensure(nl1 * 3)
+                     ? hipErrorOutOfMemory
+                     : hipSuccess;
+        });
+      },
+      [&](hipStream_t s) {
+        hipError_t e = S.tx_ev.wait(s);  // the set's previous user is done
+        e = e ? e : launch_sha256_leaves(static_cast<const uint8_t*>(d_leaf_bytes),
+                                         static_cast<const uint64_t*>(d_leaf_off), nleaves, w.hashes.as<uint32_t>(), s);
+        e = e ? e : launch_pmt_build(w.hashes.as<uint32_t>(), static_cast<const uint64_t*>(d_tx_leaf_off), ntx,
+                                     static_cast<const uint8_t*>(d_include), static_cast<const uint64_t*>(d_tx_tok_off),
+                                     ntok, w.pmt_up.as<uint32_t>(), w.pmt_has.as<uint8_t>(),
+                                     static_cast<uint8_t*>(d_txid), static_cast<uint8_t*>(d_tok),
+                                     static_cast<uint8_t*>(d_tok_hash), static_cast<uint64_t*>(d_tx_ntok),
+                                     static_cast<uint8_t*>(d_tx_status), s);
+        return e ? e : S.tx_ev.record(s);
+      });
 }
 
 int cordahip_stream_verify(cordahip_ctx* ctx, const cordahip_stream_batch* batch) {

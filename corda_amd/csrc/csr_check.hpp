@@ -17,6 +17,7 @@
 #include <atomic>
 
 #include "../../include/cordahip.h"
+#include "pmt_core.hpp"
 
 namespace cordahip {
 namespace rt {
@@ -79,6 +80,31 @@ bool check_filtered_batch(Par&& par, const cordahip_filtered_tx_batch* b) {
   if (!csr_ok(par, b->tx_leaf_off, 0, b->ntx, b->nleaves)) return false;
   if (!csr_ok(par, b->leaf_off, b->tx_leaf_off[0], b->tx_leaf_off[b->ntx], b->leaf_bytes_len)) return false;
   return csr_ok(par, b->tx_tok_off, 0, b->ntx, b->ntok);
+}
+
+// a filtered-tx build batch: the leaf level as in check_txid_batch; the token
+// slots tx_tok_off[0..ntx] non-decreasing and within ntok; every transaction's
+// slot at least 2 pad(m_t) - 1 tokens (pmt_core.hpp slot_bound: 0 for no
+// leaves; an m_t whose bound does not fit in 64 bits is rejected)
+template <class Par>
+bool check_filtered_build_batch(Par&& par, const cordahip_filtered_build_batch* b) {
+  if (b->ntx == 0) return true;
+  if (!b->tx_leaf_off || !b->leaf_off || !b->tx_tok_off) return false;
+  if (!csr_ok(par, b->tx_leaf_off, 0, b->ntx, b->nleaves)) return false;
+  if (!csr_ok(par, b->leaf_off, b->tx_leaf_off[0], b->tx_leaf_off[b->ntx], b->leaf_bytes_len)) return false;
+  if (!csr_ok(par, b->tx_tok_off, 0, b->ntx, b->ntok)) return false;
+  std::atomic<bool> ok{true};
+  par(b->ntx, 1u << 16, [&](uint64_t x, uint64_t y) {
+    for (uint64_t t = x; t < y; t++) {
+      uint64_t need;
+      if (!pmt::slot_bound(b->tx_leaf_off[t + 1] - b->tx_leaf_off[t], &need) ||
+          b->tx_tok_off[t + 1] - b->tx_tok_off[t] < need) {
+        ok.store(false, std::memory_order_relaxed);
+        return;
+      }
+    }
+  });
+  return ok.load();
 }
 
 // a cover (required-signer coverage): tx_req_off[0..ntx] non-decreasing and

@@ -97,6 +97,10 @@ hipError_t launch_tx_cover(const cordahip_cover& c, uint64_t ntx, uint8_t* tx_st
 hipError_t launch_pmt_verify(const uint32_t* leaf_hashes, const uint64_t* tx_leaf_off, const uint8_t* tok,
                              const uint8_t* tok_hash, const uint64_t* tx_tok_off, const uint8_t* root, uint64_t ntx,
                              uint32_t* stack, uint8_t* tx_status, hipStream_t s);
+// K10 (tx.hip): up = 2 * nleaves hashes, has = 3 * nleaves bytes of workspace (pmt_core.hpp)
+hipError_t launch_pmt_build(const uint32_t* hashes, const uint64_t* tx_leaf_off, uint64_t ntx, const uint8_t* include,
+                            const uint64_t* tx_tok_off, uint64_t ntok, uint32_t* up, uint8_t* has, uint8_t* txid,
+                            uint8_t* tok, uint8_t* tok_hash, uint64_t* tx_ntok, uint8_t* tx_status, hipStream_t s);
 size_t ecdsa_gtable_bytes();
 hipError_t launch_ecdsa_gtables(uint32_t* k1, uint32_t* r1, hipStream_t s);
 hipError_t launch_ecdsa_verify(const uint8_t* scheme, const uint8_t* keys, const uint8_t* key_len,
@@ -309,10 +313,12 @@ struct TxWork {  // device buffers of the transaction paths (grow-only)
   DevBuf leaf_bytes, leaf_off, tx_leaf_off, hashes, txid, tx_status, tx_sig_off, msgs;
   DevBuf comp_items, payload, comp_status;  // component-level batches: items, their payload, encoder statuses
   DevBuf tok, tok_hash, tx_tok_off, root, stack;  // filtered-tx (partial Merkle tree) path
+  DevBuf incl, tx_ntok, pmt_up, pmt_has;          // filtered-tx build: filter bytes, token counts, tree levels
   template <class V>
   void visit(V& v) {
     for (DevBuf* b : {&leaf_bytes, &leaf_off, &tx_leaf_off, &hashes, &txid, &tx_status, &tx_sig_off, &msgs,
-                      &comp_items, &payload, &comp_status, &tok, &tok_hash, &tx_tok_off, &root, &stack})
+                      &comp_items, &payload, &comp_status, &tok, &tok_hash, &tx_tok_off, &root, &stack, &incl,
+                      &tx_ntok, &pmt_up, &pmt_has})
       v.dev(*b, kFreed);
   }
 };

@@ -1,7 +1,8 @@
 // Transaction ids and per-transaction signature verdicts for gfx950 —
 // kernels K3 (leaf hashes), K4 (Merkle roots) and K5 (per-tx reduction).
 //
-// K6 (FilteredTransaction.verify) and K9 (required-signer coverage) follow them.
+// K6 (FilteredTransaction.verify), K9 (required-signer coverage) and K10
+// (FilteredTransaction build: the partial Merkle tree of a tear-off) follow them.
 //
 // Reference path:
 //   WireTransaction.id = MerkleTree.getMerkleTree(availableComponentHashes).hash
@@ -19,6 +20,7 @@
 #include <stdint.h>
 
 #include "cover_core.hpp"
+#include "pmt_core.hpp"
 #include "sha2_device.hpp"
 #include "status.hpp"
 
@@ -465,6 +467,52 @@ hipError_t launch_pmt_verify(const uint32_t* leaf_hashes, const uint64_t* tx_lea
   if (!ntx) return hipSuccess;
   hipLaunchKernelGGL(pmt_verify_kernel, dim3((uint32_t)((ntx + 255) / 256)), dim3(256), 0, s, leaf_hashes,
                      tx_leaf_off, tok, tok_hash, tx_tok_off, root, ntx, stack, tx_status);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// K10: FilteredTransaction.buildMerkleTransaction after the leaf hashes
+// (MerkleTransaction.kt:121-128 -> PartialMerkleTree.build, PartialMerkleTree.kt:68-125),
+// launched after K3 on the same stream: one lane per transaction, like K4 and
+// K6 (the batch is the parallelism). The lane runs pmt_core.hpp build_tx, the
+// code the host fuzzer runs: the included set and count rule, K4's reduction
+// with every level kept in the transaction's own workspace slice (each node
+// hashed once; padding from kZeroHash), the id, and the post-order token walk
+// into the caller's slot [tx_tok_off[t], tx_tok_off[t + 1]). The offsets of the
+// device-resident call lie in HBM, so the lane judges its own slot: one that
+// is reversed or reaches past ntok counts as empty (no token is written).
+struct PmtNodeHash {
+  __device__ void operator()(uint32_t out[8], const uint32_t a[8], const uint32_t b[8]) const {
+    sha256_node(out, a, b);
+  }
+};
+struct PmtZeroHash {
+  __device__ void operator()(int level, uint32_t out[8]) const {
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[k] = kZeroHash[level][k];
+  }
+};
+
+__global__ void __launch_bounds__(256) pmt_build_kernel(const uint32_t* __restrict__ hashes,
+                                                       const uint64_t* __restrict__ tx_leaf_off, uint64_t ntx,
+                                                       const uint8_t* __restrict__ include,
+                                                       const uint64_t* __restrict__ tx_tok_off, uint64_t ntok,
+                                                       uint32_t* __restrict__ up, uint8_t* __restrict__ has,
+                                                       uint8_t* __restrict__ txid, uint8_t* __restrict__ tok,
+                                                       uint8_t* __restrict__ tok_hash, uint64_t* __restrict__ tx_ntok,
+                                                       uint8_t* __restrict__ tx_status) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ntx) return;
+  pmt::build_lane(t, hashes, tx_leaf_off, include, tx_tok_off, ntok, up, has, txid, tok, tok_hash, tx_ntok,
+                  tx_status, PmtNodeHash{}, PmtZeroHash{});
+}
+
+hipError_t launch_pmt_build(const uint32_t* hashes, const uint64_t* tx_leaf_off, uint64_t ntx, const uint8_t* include,
+                            const uint64_t* tx_tok_off, uint64_t ntok, uint32_t* up, uint8_t* has, uint8_t* txid,
+                            uint8_t* tok, uint8_t* tok_hash, uint64_t* tx_ntok, uint8_t* tx_status, hipStream_t s) {
+  if (!ntx) return hipSuccess;
+  hipLaunchKernelGGL(pmt_build_kernel, dim3((uint32_t)((ntx + 255) / 256)), dim3(256), 0, s, hashes, tx_leaf_off, ntx,
+                     include, tx_tok_off, ntok, up, has, txid, tok, tok_hash, tx_ntok, tx_status);
   return hipGetLastError();
 }
 

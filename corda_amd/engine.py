@@ -13,8 +13,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (EngineError, FilteredTxBatch, SigBatch, SignedTxBatch, SignedTxcompBatch, StreamBatch, TxcompBatch,
-                   TxidBatch, check, lib)
+from ._lib import (EngineError, FilteredBuildBatch, FilteredTxBatch, SigBatch, SignedTxBatch, SignedTxcompBatch,
+                   StreamBatch, TxcompBatch, TxidBatch, check, lib)
 
 
 def _ptr(a: np.ndarray) -> int:
@@ -400,6 +400,60 @@ class Engine:
             return Ticket(self, t.value, lambda: st[:len(ftxs)], (lb, lo, to, tok, th, ko, root, st, b))
         check(lib().cordahip_filtered_tx_verify(self._ctx, ctypes.byref(b)), "cordahip_filtered_tx_verify")
         return st[:len(ftxs)]
+
+    # ---- FilteredTransaction build / PartialMerkleTree.build -------------------
+    def filtered_tx_build(self, txs, async_: bool = False):
+        """txs[t] = (leaves: [bytes], include: [bool]), one include flag per leaf (the filter predicate's
+        verdict on that component). The token slots are sized by the bound (_lib.pmt_slot_bound). Returns
+        (ids[ntx,32], status[ntx], tokens) with tokens[t] = [(tok, hash32 or None), ...], the form
+        filtered_tx_verify takes (empty for a non-OK transaction); or, async_, a Ticket whose wait()
+        returns them."""
+        n = len(txs)
+        leaves = [leaf for tx in txs for leaf in tx[0]]
+        lb, lo = self._csr(leaves)
+        inc = np.ascontiguousarray(np.array([1 if f else 0 for tx in txs for f in tx[1]] or [0], dtype=np.uint8))
+        assert all(len(tx[0]) == len(tx[1]) for tx in txs)
+        to = np.zeros(n + 1, dtype=np.uint64)
+        ko = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            to[1:] = np.cumsum([len(tx[0]) for tx in txs], dtype=np.uint64)
+            ko[1:] = np.cumsum([_lib.pmt_slot_bound(len(tx[0])) for tx in txs], dtype=np.uint64)
+        ntok = int(ko[n])
+        tok = np.zeros(max(ntok, 1), dtype=np.uint8)
+        th = np.zeros((max(ntok, 1), 32), dtype=np.uint8)
+        txid = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        cnt = np.zeros(max(n, 1), dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        b = FilteredBuildBatch(n, _ptr(lb), _ptr(lo), _ptr(to), _ptr(inc), _ptr(ko), _ptr(txid), _ptr(tok), _ptr(th),
+                               _ptr(cnt), _ptr(st), len(leaves), lb.size, ntok)
+
+        def res():
+            out = []
+            for t in range(n):
+                k0 = int(ko[t])
+                out.append([(int(tok[k]), None if tok[k] == 2 else th[k].tobytes())
+                            for k in range(k0, k0 + int(cnt[t]))])
+            return txid[:n], st[:n], out
+
+        if async_:
+            t = ctypes.c_uint64()
+            check(lib().cordahip_filtered_tx_build_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)),
+                  "cordahip_filtered_tx_build_submit")
+            return Ticket(self, t.value, res, (lb, lo, to, inc, ko, txid, tok, th, cnt, st, b))
+        check(lib().cordahip_filtered_tx_build(self._ctx, ctypes.byref(b)), "cordahip_filtered_tx_build")
+        return res()
+
+    def filtered_tx_build_device(self, leaf_bytes, leaf_off, tx_leaf_off, include, tx_tok_off, txid, tok, tok_hash,
+                                 tx_ntok, tx_status, device: int = 0, stream=None):
+        """cordahip_filtered_tx_build_device over device tensors: leaf_bytes uint8, leaf_off int64
+        [nleaves + 1], tx_leaf_off / tx_tok_off int64 [ntx + 1], include uint8 [nleaves]; outputs
+        txid [ntx, 32], tok [ntok], tok_hash [ntok, 32] uint8, tx_ntok int64 [ntx], tx_status uint8 [ntx]."""
+        s = stream.cuda_stream if stream is not None else 0
+        check(lib().cordahip_filtered_tx_build_device(
+            self._ctx, device, leaf_bytes.data_ptr(), leaf_off.data_ptr(), leaf_off.shape[0] - 1,
+            tx_leaf_off.data_ptr(), tx_leaf_off.shape[0] - 1, include.data_ptr(), tx_tok_off.data_ptr(),
+            tok.shape[0], txid.data_ptr(), tok.data_ptr(), tok_hash.data_ptr(), tx_ntok.data_ptr(),
+            tx_status.data_ptr(), s), "cordahip_filtered_tx_build_device")
 
     # ---- C5: streaming mixed-scheme drain (host, ideally pinned, memory) -------
     def stream_verify(self, ed, ec):

@@ -32,6 +32,7 @@ OK, BAD_SIG, MALFORMED_SIG, BAD_KEY, UNSUPPORTED, EMPTY = 0, 1, 2, 3, 4, 5
 TX_NO_LEAVES, TX_NO_SIGNATURES = 6, 7
 TX_SIGNATURES_MISSING, TX_BAD_COVER = 10, 11  # required-signer coverage (cordahip_cover)
 REQ_MISSING = 1
+TX_HASHES_NOT_IN_TREE = 12  # FilteredTransaction build: the count rule (PartialMerkleTree.kt:75-76)
 
 
 class SignatureException(Exception):
@@ -195,6 +196,37 @@ def verify_signatures_batch_covered(engine, stxs: Sequence[SignedTx], allowed_to
             out.append(Outcome(tid, _lane_exception(st), int(first_bad[t])))
         else:
             out.append(Outcome(tid, None))
+    return out
+
+
+def build_filtered_transactions(engine, wtxs, filtering: Callable[[bytes], bool]):
+    """WireTransaction.buildFilteredTransaction(filtering) (WireTransaction.kt, via
+    FilteredTransaction.buildMerkleTransaction, MerkleTransaction.kt:121-128) for every
+    transaction, one engine call (Engine.filtered_tx_build: K3 leaf hashes, K10 trees).
+
+    wtxs[t]: a SignedTx or the transaction's serialised components (the Merkle leaves) in
+    availableComponents order; filtering(component) is the predicate filterWithFun applies to
+    each of them. Returns per transaction (filtered leaves, tokens, root): the FilteredLeaves'
+    components in order, the PartialMerkleTree's post-order tokens and rootHash -- the tuple
+    Engine.filtered_tx_verify takes. Like a loop over the Kotlin call, the first transaction
+    (input order) whose build throws raises: MerkleTreeException for a transaction with no
+    components (MerkleTree.kt:49-50) and for included hashes the tree does not hold one to one
+    (PartialMerkleTree.kt:75-76: an unselected component equal to a selected one)."""
+    comps = [list(w.components) if isinstance(w, SignedTx) else list(w) for w in wtxs]
+    if not comps:
+        return []
+    masks = [[bool(filtering(c)) for c in cs] for cs in comps]
+    ids, status, toks = engine.filtered_tx_build(list(zip(comps, masks)))
+    out = []
+    for t, cs in enumerate(comps):
+        st = int(status[t])
+        if st == TX_NO_LEAVES:
+            raise MerkleTreeException("Cannot calculate Merkle root on empty hash list.")
+        if st == TX_HASHES_NOT_IN_TREE:
+            raise MerkleTreeException("Some of the provided hashes are not in the tree.")
+        if st != OK:
+            raise RuntimeError("filtered_tx_build: transaction %d has status %d" % (t, st))
+        out.append(([c for c, f in zip(cs, masks[t]) if f], toks[t], bytes(ids[t])))
     return out
 
 

@@ -358,6 +358,79 @@ typedef struct {
 int cordahip_filtered_tx_verify(cordahip_ctx* ctx, const cordahip_filtered_tx_batch* batch);
 int cordahip_filtered_tx_submit(cordahip_ctx* ctx, const cordahip_filtered_tx_batch* batch, uint64_t* ticket);
 
+/* FilteredTransaction build, the sender's side of a tear-off (what NotaryFlow.Client
+ * and RatesFixFlow run before they send to a non-validating notary or an oracle):
+ *   WireTransaction.buildFilteredTransaction -> FilteredTransaction.buildMerkleTransaction
+ *                                core/.../transactions/MerkleTransaction.kt:121-128
+ *   MerkleTree.getMerkleTree     core/.../crypto/MerkleTree.kt:27-66
+ *   PartialMerkleTree.build      core/.../crypto/PartialMerkleTree.kt:68-125
+ * Per transaction t: its m leaves (leaf CSR exactly as in cordahip_txid_batch)
+ * and one include byte per leaf (nonzero: the JVM's filter predicate selected
+ * that component; evaluating the predicate stays with the JVM). With h_i the
+ * SHA-256 of leaf i and pad(m) the next power of two >= m:
+ *   - membership is by hash, as the reference tests `root.hash in includeHashes`:
+ *     leaf i becomes an IncludedLeaf iff some flagged leaf j has h_j == h_i,
+ *     whether or not i itself is flagged;
+ *   - if the number of IncludedLeafs differs from the number of flagged leaves
+ *     (includeHashes.size != usedHashes.size, :75-76) the transaction fails with
+ *     CORDAHIP_TX_HASHES_NOT_IN_TREE (leaves a,a,a with only the first flagged;
+ *     all three flagged is OK);
+ *   - a subtree with no included leaf below it is one Leaf(its hash); padding
+ *     positions are Leaf(zeroHash) unless cut higher;
+ *   - no flagged leaf: the single token Leaf(rootHash), status OK (the later
+ *     verify() is what throws); m == 1: one token, IncludedLeaf or Leaf;
+ *   - m == 0: CORDAHIP_TX_NO_LEAVES, no token, the id as cordahip_tx_ids writes it.
+ * The reference's require(zeroHash !in includeHashes) (:71) cannot be reached
+ * from leaf bytes -- it needs a SHA-256 preimage of 32 zero bytes -- so it has
+ * no status here. Listing a hash more often than the tree holds it
+ * (PartialMerkleTreeTest.kt:161-165) cannot be expressed by a mask over the
+ * transaction's own leaves, and buildMerkleTransaction cannot produce it either.
+ *
+ * Output: txid[t] = rootHash (for every m > 0, whatever the status); the
+ * post-order token stream in exactly the encoding cordahip_filtered_tx_verify
+ * reads (0 IncludedLeaf, 1 Leaf, 2 Node; tok_hash of a Node is unspecified);
+ * tx_ntok[t] tokens (0 for a non-OK transaction); tx_status[t].
+ * Token slots are sized by the CALLER: tx_tok_off is an input, transaction t
+ * owns entries [tx_tok_off[t], tx_tok_off[t+1]) of tok and tok_hash and its
+ * tokens are written from the slot's start. A slot must hold 2*pad(m) - 1
+ * tokens (0 for m == 0), the exact worst case. Slot entries at or past
+ * tx_ntok[t] are unspecified; nothing outside [tx_tok_off[0], tx_tok_off[ntx])
+ * is written. The host forms check every slot (and the CSR levels) before any
+ * enqueue: a violation is CORDAHIP_ERR_INVALID_ARG with the outputs untouched. */
+#define CORDAHIP_TX_HASHES_NOT_IN_TREE 12 /* MerkleTreeException, PartialMerkleTree.kt:75-76 */
+#define CORDAHIP_TX_TOK_SLOT_TOO_SMALL 13 /* device-resident call only: slot < 2*pad(m)-1 */
+typedef struct {
+  uint64_t ntx;
+  const uint8_t* leaf_bytes;
+  const uint64_t* leaf_off;    /* [nleaves+1] into leaf_bytes */
+  const uint64_t* tx_leaf_off; /* [ntx+1] */
+  const uint8_t* include;      /* [nleaves] nonzero: the filter selected this component */
+  const uint64_t* tx_tok_off;  /* [ntx+1] in: token slots */
+  uint8_t* txid;               /* [ntx*32] out: rootHash */
+  uint8_t* tok;                /* [ntok] out */
+  uint8_t* tok_hash;           /* [ntok*32] out */
+  uint64_t* tx_ntok;           /* [ntx] out */
+  uint8_t* tx_status;          /* [ntx] out */
+  uint64_t nleaves;            /* leaves (leaf_off has nleaves+1 entries, include nleaves) */
+  uint64_t leaf_bytes_len;     /* bytes at leaf_bytes */
+  uint64_t ntok;               /* token entries at tok (and 32-byte hashes at tok_hash) */
+} cordahip_filtered_build_batch;
+int cordahip_filtered_tx_build(cordahip_ctx* ctx, const cordahip_filtered_build_batch* batch);
+int cordahip_filtered_tx_build_submit(cordahip_ctx* ctx, const cordahip_filtered_build_batch* batch,
+                                      uint64_t* ticket);
+/* Device-resident form: every array in HBM on `device`, K3 and K10 on
+ * hip_stream. Its offsets are read on the device only, so the kernel guards
+ * the slots itself: a transaction whose slot is smaller than 2*pad(m) - 1 (or
+ * reversed, or reaching past ntok) gets CORDAHIP_TX_TOK_SLOT_TOO_SMALL, its
+ * id, tx_ntok[t] = 0 and no token; a failed count rule is reported first. The
+ * leaf-level offsets are the caller's contract, as in
+ * cordahip_signed_tx_verify_ed25519_device. */
+int cordahip_filtered_tx_build_device(cordahip_ctx* ctx, int device, const void* d_leaf_bytes,
+                                      const void* d_leaf_off, uint64_t nleaves, const void* d_tx_leaf_off,
+                                      uint64_t ntx, const void* d_include, const void* d_tx_tok_off, uint64_t ntok,
+                                      void* d_txid, void* d_tok, void* d_tok_hash, void* d_tx_ntok,
+                                      void* d_tx_status, void* hip_stream);
+
 /* ---- native Kryo leaf encoder ------------------------- *
  * The Merkle leaf of a transaction component is SHA-256 of its p2p Kryo bytes:
  *   serializedHash(x) = p2PKryo().withoutReferences { x.serialize(kryo).hash }
