@@ -447,21 +447,63 @@ CDEV void load_point(ge_p3& p, const uint32_t* __restrict__ o) {
   fe_set(p.Z, 1);
 }
 
-// entries [1..8]base of a per-lane table (entry 0, the identity, is shared:
-// table_entry in ed25519_ws.hpp)
-CDEV void store_table8(uint32_t* __restrict__ rec, const ge_p3& base) {
-  ge_cached c, c1;
-  ge_to_cached(c1, base);
-  store_cached(rec, c1);
-  ge_p3 Q;
-  ge_dbl<true>(Q, base);
-  ge_to_cached(c, Q);
-  store_cached(rec + kWhEntryWords, c);
-  for (int k = 3; k <= 8; k++) {
-    ge_add<true>(Q, Q, c1);
-    ge_to_cached(c, Q);
-    store_cached(rec + kWhEntryWords * (k - 1), c);
-  }
+// The joint table i P + j Q (P = -A, Q = -R affine; ed25519_joint.hpp) is built
+// from doublings and mixed additions only, in two loops of two passes each (one
+// copy of each body in the I-cache), which meet through the record:
+//   single pass (base = P, then Q): [1]base, whose cached form with Z = 1 is
+//     also its niels form, and [2]base;
+//   sign pass (s = -1, then +1): D = P + sQ, 2D = 2P + 2sQ, D + sQ = P + 2sQ,
+//     D + P = 2P + sQ.
+// 4 doublings, 6 mixed additions, 2 + 10 products by 2d: 16 S + 70 M per lane.
+// P and Q are parked (X, Y, T) in the slots of 2P + 2Q and 2P - 2Q: Q's slot
+// is free once the single passes are done, P's is written last.
+static constexpr int kParkP = joint_index(2, 2), kParkQ = joint_index(2, -2);
+
+CDEV uint32_t* joint_slot(uint32_t* rec, int idx) { return rec + kWhTab + idx * kWhEntryWords; }
+
+// an entry with Z = 1 read back as the niels form of its point
+CDEV void load_cached_niels(ge_niels& n, const uint32_t* __restrict__ p) {
+  ge_cached c;
+  load_cached(c, p);
+  n.ypx = c.YpX;
+  n.ymx = c.YmX;
+  n.xy2d = c.T2d;
+}
+
+// pass 0: [1]P, [2]P; pass 1: [1]Q, [2]Q
+CDEV void joint_single_pass(uint32_t* __restrict__ rec, int pass) {
+  ge_p3 B, D;
+  load_point(B, joint_slot(rec, pass ? kParkQ : kParkP));
+  ge_cached c;
+  ge_to_cached(c, B);
+  store_cached(joint_slot(rec, pass ? joint_index(0, 1) : joint_index(1, 0)), c);
+  ge_dbl<true>(D, B);
+  ge_to_cached(c, D);
+  store_cached(joint_slot(rec, pass ? joint_index(0, 2) : joint_index(2, 0)), c);
+}
+
+// the four entries that mix P and Q with relative sign s (s = -1 first: the
+// s = +1 pass overwrites P's parking slot with its last store)
+CDEV void joint_sign_pass(uint32_t* __restrict__ rec, int s) {
+  ge_p3 D, E;
+  ge_niels nq, np;
+  ge_cached c;
+  load_point(D, joint_slot(rec, kParkP));
+  load_cached_niels(nq, joint_slot(rec, joint_index(0, 1)));
+  niels_cneg(nq, s < 0);
+  ge_madd<true>(D, D, nq);  // P + sQ
+  ge_to_cached(c, D);
+  store_cached(joint_slot(rec, joint_index(1, s)), c);
+  ge_madd<true>(E, D, nq);  // P + 2sQ
+  ge_to_cached(c, E);
+  store_cached(joint_slot(rec, joint_index(1, 2 * s)), c);
+  load_cached_niels(np, joint_slot(rec, joint_index(1, 0)));
+  ge_madd<true>(E, D, np);  // 2P + sQ
+  ge_to_cached(c, E);
+  store_cached(joint_slot(rec, joint_index(2, s)), c);
+  ge_dbl<true>(E, D);       // 2P + 2sQ
+  ge_to_cached(c, E);
+  store_cached(joint_slot(rec, joint_index(2, 2 * s)), c);
 }
 
 // ---------------------------------------------------------------------------
@@ -471,18 +513,20 @@ CDEV void store_table8(uint32_t* __restrict__ rec, const ge_p3& base) {
 // Record layout: ed25519_ws.hpp (kWh*).
 
 // Phases, each finished (and its table written to the workspace) before the
-// next starts: decode A -> table [k](-A) | strict decode R -> table [k](-R) |
+// next starts: decode A, strict decode R | joint table i(-A) + j(-R) |
 // SHA-512, h, S_eff, lattice reduction, e = c1 S_eff mod L. Lanes whose
 // status is already decided run the phases on the identity / zero scalars.
 #ifndef ED_PREP_WAVES
 #define ED_PREP_WAVES 2
 #endif
-// Phase 1 of the prep (no message): decode A and R, the pre-engine statuses, the
-// tables [k](-A), [k](-R). Returns the lane's status (kStatusPending: verify);
-// abyte = EdDSAPublicKey.Abyte, Rw = R's bytes, both for the SHA-512 of phase 2.
-CDEV uint8_t prep_keys_phase(const uint8_t* __restrict__ keys, const uint8_t* __restrict__ sigs, uint64_t i,
-                             uint32_t msg_len, const uint8_t* __restrict__ pre_status, uint32_t empty_is_error,
-                             uint32_t* __restrict__ rec, uint32_t abyte[8], uint32_t Rw[8]) {
+// Phase 1 of the prep (no message) is prep_decode_phase, then prep_table_phase:
+// decode A and R, the pre-engine statuses | the joint table i(-A) + j(-R).
+// Returns the lane's status (kStatusPending: verify); abyte =
+// EdDSAPublicKey.Abyte, Rw = R's bytes, both for the SHA-512 of phase 2. It
+// leaves P = -A and Q = -R parked in the record for the table phase.
+CDEV uint8_t prep_decode_phase(const uint8_t* __restrict__ keys, const uint8_t* __restrict__ sigs, uint64_t i,
+                               uint32_t msg_len, const uint8_t* __restrict__ pre_status, uint32_t empty_is_error,
+                               uint32_t* __restrict__ rec, uint32_t abyte[8], uint32_t Rw[8]) {
   uint8_t st = kStatusPending;
   load8(Rw, reinterpret_cast<const uint32_t*>(sigs + i * 64));
   {
@@ -504,26 +548,39 @@ CDEV uint8_t prep_keys_phase(const uint8_t* __restrict__ keys, const uint8_t* __
       ge_identity(A);
       ge_identity(R);
     }
-    // -A, -R parked in the last entry of their table (Z = 1: X, Y, T), so the
-    // table loop below holds one point at a time
+    // P = -A, Q = -R parked in the record (Z = 1: X, Y, T), so the table loops
+    // below hold one point at a time
     fe_neg(A.X, A.X);
     fe_neg(A.T, A.T);
     fe_neg(R.X, R.X);
     fe_neg(R.T, R.T);
-    store_point(rec + kWhTabA + kWhEntryWords * 7, A);
-    store_point(rec + kWhTabR + kWhEntryWords * 7, R);
+    store_point(joint_slot(rec, kParkP), A);
+    store_point(joint_slot(rec, kParkQ), R);
   }
-  PHASE_BARRIER();
-  // tables [k](-A), [k](-R): one loop body keeps a single copy of the table
-  // code in the I-cache
+  return st;
+}
+
+CDEV void prep_table_phase(uint32_t* __restrict__ rec) {
+  // the joint table i P + j Q: one loop body per kind of pass keeps a single
+  // copy of its code in the I-cache
 #pragma unroll 1
   for (int pass = 0; pass < 2; pass++) {
-    uint32_t* tab = rec + (pass ? kWhTabR : kWhTabA);
-    ge_p3 P;
-    load_point(P, tab + kWhEntryWords * 7);  // read before store_table8 overwrites slot 8
-    store_table8(tab, P);
+    joint_single_pass(rec, pass);
     PHASE_BARRIER();
   }
+#pragma unroll 1
+  for (int s = -1; s <= 1; s += 2) {
+    joint_sign_pass(rec, s);
+    PHASE_BARRIER();
+  }
+}
+
+CDEV uint8_t prep_keys_phase(const uint8_t* __restrict__ keys, const uint8_t* __restrict__ sigs, uint64_t i,
+                             uint32_t msg_len, const uint8_t* __restrict__ pre_status, uint32_t empty_is_error,
+                             uint32_t* __restrict__ rec, uint32_t abyte[8], uint32_t Rw[8]) {
+  const uint8_t st = prep_decode_phase(keys, sigs, i, msg_len, pre_status, empty_is_error, rec, abyte, Rw);
+  PHASE_BARRIER();
+  prep_table_phase(rec);
   return st;
 }
 

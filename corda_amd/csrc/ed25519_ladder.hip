@@ -5,9 +5,10 @@
 // with |c0|, c1 ~ 2^128 (c0 == c1 h mod 8L, c1 odd) and e = c1 S_eff mod L: the
 // i2p 0.2.0 cofactorless check encode([S]B - [h]A) == R rewritten over
 // half-size scalars (T. Pornin, ePrint 2020/454; the equivalence argument is in
-// ed25519.hip above half_scalars). 4-bit Booth windows over the per-lane
-// [0..8](-A), [0..8](-R) tables (gathered from the workspace one window ahead,
-// so the four doublings hide the load), 16-bit Booth windows over B and
+// ed25519.hip above half_scalars). 2-bit Booth windows over both scalars at
+// once: one addition per window of an entry i(-A) + j(-R) of the per-lane joint
+// table (ed25519_joint.hpp; gathered from the workspace one window ahead, so
+// the two doublings hide the load), 16-bit Booth windows over B and
 // B' = [2^128]B from L2/MALL-resident tables (ed25519_ws.hpp). Digit positions are the same in every lane, so the
 // ladder never diverges; P == O is X == 0 and Y == Z (no inversion).
 // Verdict word per wave by ballot.
@@ -82,43 +83,38 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_LAD
   }
   const bool c0neg = rec[kWhFlags] & 1u;  // [c0](-A) with c0 < 0 is [|c0|]A: flip the digit signs
   // at least the windows the fixed-base digits need (e's low half: kBDigits
-  // digits of kBBits bits); |c0|, c1 ~ 2^128 give 33
-  const int W = max(wave_max((bits + 1 + 3) / 4), (kBDigits - 1) * (kBBits / 4) + 1);
+  // digits of kBBits bits); |c0|, c1 ~ 2^128 give 65
+  const int W = max(wave_max((bits + 2) / 2), (kBDigits - 1) * (kBBits / 2) + 1);
   const uint32_t* btab2 = btab + kBTableEntries * kBEntryWords;
   ge_p3 P;
   ge_identity(P);
   for (int j = W - 1; j >= 0; j--) {
-    const int da = booth_digit_col<4>(ska, j), dr = booth_digit_col<4>(skr, j);
-    ge_cached ca, cr;  // issued before the doublings, consumed after them
-    load_cached(ca, table_entry(rec + kWhTabA, da < 0 ? -da : da));
-    load_cached(cr, table_entry(rec + kWhTabR, dr < 0 ? -dr : dr));
+    const joint_sel sel = joint_select(joint_booth2(ska, 256, 8, j), joint_booth2(skr, 256, 8, j), c0neg);
+    ge_cached c;  // issued before the doublings, consumed after them
+    load_cached(c, table_entry(rec, sel.idx));
     if (j != W - 1) {
-      ge_dbl<false>(P, P);
-      ge_dbl<false>(P, P);
       ge_dbl<false>(P, P);
       ge_dbl<true>(P, P);
     }
-    cached_cneg(ca, (da < 0) != c0neg);
-    ge_add<true>(P, P, ca);
+    cached_cneg(c, sel.neg);
     // fixed-base window: the L2 gather of each niels entry is issued one
     // addition ahead of its use (registers allow no more)
-    // (W is the wave's maximum and may exceed 33: the low half's windows end at
+    // (W is the wave's maximum and may exceed 65: the low half's windows end at
     // digit kBDigits - 1, the high half's digits ride on B')
-    const bool bwin = j % (kBBits / 4) == 0 && j < kBDigits * (kBBits / 4);
-    cached_cneg(cr, dr < 0);
+    const bool bwin = j % (kBBits / 2) == 0 && j < kBDigits * (kBBits / 2);
     if (bwin) {
-      const int d0 = booth_digit_col<kBBits>(ske, j / (kBBits / 4));
-      const int d1 = booth_digit_col<kBBits>(ske, j / (kBBits / 4) + kBDigits);
+      const int d0 = booth_digit_col<kBBits>(ske, j / (kBBits / 2));
+      const int d1 = booth_digit_col<kBBits>(ske, j / (kBBits / 2) + kBDigits);
       ge_niels nb0, nb1;
       load_niels(nb0, btab, d0 < 0 ? -d0 : d0);
-      ge_add<true>(P, P, cr);
+      ge_add<true>(P, P, c);
       load_niels(nb1, btab2, d1 < 0 ? -d1 : d1);
       niels_cneg(nb0, d0 < 0);
       ge_madd<true>(P, P, nb0);
       niels_cneg(nb1, d1 < 0);
       ge_madd<false>(P, P, nb1);
     } else {
-      ge_add<false>(P, P, cr);
+      ge_add<false>(P, P, c);
     }
   }
   fe d;

@@ -11,6 +11,7 @@
 // one paired chain), the ladder by the group formulas' independent products;
 // both issue those products as generated asm pairs (fe25519_asm.hpp).
 #pragma once
+#include "ed25519_joint.hpp"
 #include "fe25519.hpp"
 #include "ge25519.hpp"
 #include "sc25519.hpp"
@@ -30,29 +31,29 @@ static constexpr int kBTableEntries = (1 << (kBBits - 1)) + 1;
 static constexpr int kBEntryWords = 32;
 static constexpr uint8_t kStatusPending = 0xff;
 
-// Per-lane workspace record (3,200 B = 50 x 64 B, so every record and every
-// entry starts on a 64-B sector): entries [1..8](-A), [1..8](-R) in cached form
-// (40 words) padded to 48 words, so a gather of one entry reads exactly three
-// 64-B sectors (at 40-word stride an entry straddled 3-4 sectors and 2-3
-// 128-B lines). Digit 0 gathers the shared identity entry kIdentityCached
-// (L2-resident) instead of a per-lane copy.
+// Per-lane workspace record (2,432 B = 38 x 64 B, so every record and every
+// entry starts on a 64-B sector): the 12 entries i(-A) + j(-R) of the joint
+// table (ed25519_joint.hpp: i, j in [-2, 2], i > 0 or i == 0 and j > 0) in
+// cached form (40 words) padded to 48 words, so a gather of one entry reads
+// exactly three 64-B sectors (at 40-word stride an entry straddled 3-4 sectors
+// and 2-3 128-B lines). The digit pair (0, 0) gathers the shared identity entry
+// kIdentityCached (L2-resident) instead of a per-lane copy.
 static constexpr int kWhEntryWords = 48;
-static constexpr int kWhTabA = 0;                       // [k](-A) at (k - 1) * kWhEntryWords, k = 1..8
-static constexpr int kWhTabR = 8 * kWhEntryWords;       // [k](-R)
-static constexpr int kWhKa = 16 * kWhEntryWords;        // |c0|, c1, e (8 words each)
+static constexpr int kWhTab = 0;                               // entry idx at idx * kWhEntryWords
+static constexpr int kWhKa = kJointEntries * kWhEntryWords;    // |c0|, c1, e (8 words each)
 static constexpr int kWhKr = kWhKa + 8;
 static constexpr int kWhE = kWhKa + 16;
 static constexpr int kWhFlags = kWhKa + 24;             // bit 0: c0 < 0
-static constexpr int kWhLaneWords = kWhKa + 32;         // 800 words
+static constexpr int kWhLaneWords = kWhKa + 32;         // 608 words
 static_assert(kWhLaneWords % 16 == 0, "records must start on 64-B sectors");
 
-// the identity in cached form (Y+X, Y-X, Z, 2dT) = (1, 1, 1, 0), entry 0 of
-// every per-lane table (defined in ed25519_ladder.hip)
+// the identity in cached form (Y+X, Y-X, Z, 2dT) = (1, 1, 1, 0), the entry of
+// the digit pair (0, 0) in every lane (defined in ed25519_ladder.hip)
 extern __device__ const uint32_t kIdentityCached[kWhEntryWords];
 
-// entry |d| of a per-lane table (tab = rec + kWhTabA or kWhTabR)
-CDEV const uint32_t* table_entry(const uint32_t* tab, int absd) {
-  return absd == 0 ? kIdentityCached : tab + (absd - 1) * kWhEntryWords;
+// entry idx (joint_select) of a lane's joint table
+CDEV const uint32_t* table_entry(const uint32_t* rec, int idx) {
+  return idx == kJointIdentity ? kIdentityCached : rec + kWhTab + idx * kWhEntryWords;
 }
 
 CDEV void load_niels(ge_niels& n, const uint32_t* __restrict__ tab, int idx) {

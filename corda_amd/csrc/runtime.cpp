@@ -216,9 +216,9 @@ hipError_t ensure_streams(Device& d) {
 // Launch-pair sizes of the split kernels = the largest workspace per device.
 // Bigger launches pay fewer end-of-grid tails (C2, measured: 2^18 91.5, 2^20
 // 93.2, 2^22 96.4, 2^24 97.2 M verifs/s): a 2^24-lane batch runs as ONE
-// prep/ladder pair over 54 GB of HBM (19% of the MI355X's 288 GB). Smaller
+// prep/ladder pair over 41 GB of HBM (14% of the MI355X's 288 GB). Smaller
 // batches allocate only what they use (grow-only, from 2^18 lanes up).
-constexpr uint64_t kEdWsLanes = 1ull << 24;  // x 3,200 B = 54 GB of Ed25519 workspace at most
+constexpr uint64_t kEdWsLanes = 1ull << 24;  // x 2,432 B = 41 GB of Ed25519 workspace at most
 constexpr uint64_t kEcWsSlots = 1ull << 24;  // x 1,120 B = 18.8 GB of ECDSA workspace at most
 constexpr uint64_t kWsMinLanes = 1ull << 18;
 
@@ -351,8 +351,8 @@ hipError_t ed_verify_device_chunks(Device& d, TxSet& S, const uint8_t* keys, con
 // of the device): the workspaces it sizes -- Ed25519 slot 0 45% of it, slot 1 20%
 // (and half of slot 0 at most), ECDSA 15% -- each also capped by its r05 maximum
 // (2^24 lanes / slots, CORDAHIP_ED25519_WS_LANES / CORDAHIP_ECDSA_WS_SLOTS). The
-// default therefore keeps C2's single 2^24-lane launch pair (53.7 GB) and the
-// r05 peak: 53.7 + 26.8 + 18.8 GB of workspaces. The other buffers follow the
+// default therefore keeps C2's single 2^24-lane launch pair (40.8 GB) and the
+// r05 lane counts: 40.8 + 20.4 + 18.8 GB of workspaces. The other buffers follow the
 // batches (the id and signature stages, component slices, C5's stages) and are
 // not split. A smaller budget costs extra launch pairs, never a failed batch.
 uint64_t parse_bytes(const char* v, uint64_t dflt) {

@@ -8,14 +8,17 @@
 // counter: the model's L2-miss bytes must reproduce the measured FETCH before
 // its MALL-miss (= HBM) bytes are believed.
 //
-// Access stream (ed25519_ladder.hip, ed25519_ws.hpp): lane l's 3,200-B record
-// at l * 3200; per window (33 of 4 bits over |c0|, c1 ~ 2^128), one 160-B
-// entry of the lane's [1..8](-A) table and one of its [1..8](-R) table
-// (192-B stride, sector-aligned), entry |d| - 1 for Booth digit d, digit 0 the
-// shared identity entry; every 4th window one 128-B niels entry of each 4.2 MB
-// fixed-base table ([k]B, [k]B', 16-bit Booth digits); the record's scalars
-// once. Blocks of 256 lanes, dealt round-robin to the 8 XCDs; 512 blocks
-// resident (2 waves per SIMD, 247 VGPRs); each XCD's L2 is 4 MB, the MALL
+// Access stream (ed25519_ladder.hip, ed25519_ws.hpp): lane l's 2,432-B record
+// at l * 2432; per window (65 of 2 bits over |c0|, c1 ~ 2^128), one 160-B
+// entry of the lane's 12-entry joint table i(-A) + j(-R) (192-B stride,
+// sector-aligned; ed25519_joint.hpp joint_index for the Booth digit pair, up to
+// sign), the pair (0, 0) the shared identity entry; every 8th window one 128-B
+// niels entry of each 4.2 MB fixed-base table ([k]B, [k]B', 16-bit Booth
+// digits); the record's scalars once. The measured FETCH the header quotes is
+// the r06 kernels' (two 8-entry tables, 3,200-B records): recalibrate on
+// profiles/r10_pmc_c2.json before quoting a split for the joint table.
+// Blocks of 256 lanes, dealt round-robin to the 8 XCDs; 512 blocks
+// resident (2 waves per SIMD, 234 VGPRs); each XCD's L2 is 4 MB, the MALL
 // 256 MB shared; 128-B lines, LRU, the MALL allocating on every L2 miss.
 // Two schedules bracket reality: lockstep rounds (every resident block at the
 // same window) and staggered (resident blocks at uniformly spread windows).
@@ -55,13 +58,18 @@ struct Stats {
   uint64_t lanes = 0, l2_miss = 0, mall_miss = 0, accesses = 0;
 };
 
-constexpr uint64_t kLine = 128, kRec = 3200, kEntry = 192, kEntryRead = 160;
-constexpr int kWindows = 33, kLanesPerBlock = 256, kXcd = 8, kResident = 512;
+constexpr uint64_t kLine = 128, kRec = 2432, kEntry = 192, kEntryRead = 160;
+constexpr int kJointEntries = 12, kWindows = 65, kLanesPerBlock = 256, kXcd = 8, kResident = 512;
 constexpr uint64_t kBTab = 1ull << 40, kBEntries = 32769, kIdentity = 1ull << 41;
 
-int booth4(std::mt19937_64& g) {  // |d| of a 4-bit Booth digit: 0 and 8 at 1/16, 1..7 at 1/8
-  const int r = (int)(g() & 15);
-  return r == 0 ? 0 : r == 15 ? 8 : (r + 1) / 2;
+int booth2(std::mt19937_64& g) {  // a 2-bit Booth digit: 0 and +-1 at 1/4 each, +-2 at 1/8 each
+  const int v = (int)(g() & 7);
+  return ((v + 1) >> 1) - ((v >> 2) << 2);
+}
+// joint table entry of the digit pair (ed25519_joint.hpp joint_select), -1 = identity
+int joint_entry(int da, int dr) {
+  const bool neg = da < 0 || (da == 0 && dr < 0);
+  return 5 * (neg ? -da : da) + (neg ? -dr : dr) - 1;
 }
 
 int main(int argc, char** argv) {
@@ -103,11 +111,10 @@ int main(int argc, char** argv) {
         for (int t = 0; t < kLanesPerBlock; t++) {
           const uint64_t lane = sl.block * kLanesPerBlock + t;
           const uint64_t rec = lane * kRec;
-          if (sl.window == 0) access(sl.acc, xcd, rec + 16 * kEntry, 128);  // scalars
-          const int da = booth4(g), dr = booth4(g);
-          access(sl.acc, xcd, da ? rec + (da - 1) * kEntry : kIdentity, kEntryRead);
-          access(sl.acc, xcd, dr ? rec + 8 * kEntry + (dr - 1) * kEntry : kIdentity, kEntryRead);
-          if (sl.window % 4 == 3) {
+          if (sl.window == 0) access(sl.acc, xcd, rec + kJointEntries * kEntry, 128);  // scalars
+          const int e = joint_entry(booth2(g), booth2(g));
+          access(sl.acc, xcd, e >= 0 ? rec + e * kEntry : kIdentity, kEntryRead);
+          if (sl.window % 8 == 7) {
             access(sl.acc, xcd, kBTab + (g() % kBEntries) * kLine, kLine);
             access(sl.acc, xcd, kBTab + (kBEntries + g() % kBEntries) * kLine, kLine);
           }
