@@ -40,6 +40,8 @@ EXPORTS = [
     "cordahip_cover_eval_host", "cordahip_signed_tx_verify_covered", "cordahip_tx_submit_covered",
     "cordahip_signed_txcomp_verify_covered", "cordahip_txcomp_submit_covered", "cordahip_tx_cover_device",
     "cordahip_filtered_tx_build", "cordahip_filtered_tx_build_submit", "cordahip_filtered_tx_build_device",
+    "cordahip_signer_add_ed25519", "cordahip_signer_remove", "cordahip_sign", "cordahip_sign_submit",
+    "cordahip_ed25519_sign_keyed_device",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
@@ -57,6 +59,10 @@ TX_SIGNATURES_MISSING, TX_BAD_COVER = 10, 11
 # a token slot below the bound (device-resident call only)
 TX_HASHES_NOT_IN_TREE, TX_TOK_SLOT_TOO_SMALL = 12, 13
 REQ_FULFILLED, REQ_MISSING, REQ_MISSING_ALLOWED, REQ_NOT_EVALUATED, REQ_MALFORMED = 0, 1, 2, 3, 4
+# signing lanes (cordahip_sign): besides OK and EMPTY; precedence SKIPPED, UNKNOWN_KEY, EMPTY
+SIGN_UNKNOWN_KEY, SIGN_SKIPPED = 14, 15
+SIGNER_MAX_KEYS = 4096  # live keys per context (a full table: CORDAHIP_ERR_OUT_OF_MEMORY)
+ERR_INVALID_ARG, ERR_OUT_OF_MEMORY = -1, -4
 
 
 class EngineUnavailable(RuntimeError):
@@ -151,6 +157,17 @@ class FilteredBuildBatch(ctypes.Structure):
         ("txid", ctypes.c_void_p), ("tok", ctypes.c_void_p), ("tok_hash", ctypes.c_void_p),
         ("tx_ntok", ctypes.c_void_p), ("tx_status", ctypes.c_void_p),
         ("nleaves", ctypes.c_uint64), ("leaf_bytes_len", ctypes.c_uint64), ("ntok", ctypes.c_uint64),
+    ]
+
+
+class SignBatch(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("key_id", ctypes.c_void_p),
+        ("msg", ctypes.c_void_p), ("msg_off", ctypes.c_void_p),
+        ("gate", ctypes.c_void_p),
+        ("sig", ctypes.c_void_p), ("status", ctypes.c_void_p),
+        ("msg_bytes", ctypes.c_uint64),
     ]
 
 
@@ -270,6 +287,11 @@ def lib() -> ctypes.CDLL:
         "cordahip_filtered_tx_build_submit": (i32, [vp, ctypes.POINTER(FilteredBuildBatch), ctypes.POINTER(u64)]),
         "cordahip_filtered_tx_build_device": (i32, [vp, i32, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp,
                                                     vp]),
+        "cordahip_signer_add_ed25519": (i32, [vp, vp, ctypes.POINTER(u32), vp]),
+        "cordahip_signer_remove": (i32, [vp, u32]),
+        "cordahip_sign": (i32, [vp, ctypes.POINTER(SignBatch)]),
+        "cordahip_sign_submit": (i32, [vp, ctypes.POINTER(SignBatch), ctypes.POINTER(u64)]),
+        "cordahip_ed25519_sign_keyed_device": (i32, [vp, i32, vp, vp, u32, u64, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(l, name)

@@ -26,7 +26,9 @@
 #include "cover_core.hpp"
 #include "csr_check.hpp"
 #include "der.hpp"
+#include "ed25519_comb.hpp"
 #include "kryo_core.hpp"
+#include "pack_rows.hpp"
 #include "runtime.hpp"
 #include "status.hpp"
 
@@ -1271,6 +1273,188 @@ int filtered_build_impl(cordahip_ctx* ctx, const cordahip_filtered_build_batch* 
                     [&](Device& d, uint64_t t0, uint64_t t1) { return filtered_build_shard(d, b, t0, t1); });
 }
 
+// ---- Ed25519 signing with registered keys (K11, ed25519_sign.hip) -------------
+// A key's record zeroed on one device (sign_mu held, device current): after every
+// signing kernel that may still read it; the stream is drained before return.
+hipError_t signer_zero_record(Device& d, uint32_t slot) {
+  if (!d.keys.tab.p) return hipSuccess;
+  hipError_t e = d.keys.ev.sync();
+  e = e ? e : hipMemsetAsync(d.keys.tab.as<uint32_t>() + (size_t)slot * kSignRecWords, 0, kSignRecWords * 4, d.stream);
+  const hipError_t f = hipStreamSynchronize(d.stream);
+  return e ? e : f;
+}
+
+// The seed expanded into the record of key_id's slot on one device (sign_mu held);
+// pub: the device's A. The seed crosses in the device's page-locked stage, wiped
+// here whatever happens; the kernel zeroes its device scratch.
+int signer_expand_on(Device& d, const uint8_t seed[32], uint32_t key_id, uint8_t pub[32]) {
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  if (!d.keys.tab.p) {  // the first key of this device: the table, zeroed
+    if (d.keys.tab.ensure(ed25519_keytab_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+    if (hipMemsetAsync(d.keys.tab.p, 0, d.keys.tab.cap, d.stream) != hipSuccess) return CORDAHIP_ERR_HIP;
+  }
+  if (d.keys.stage.ensure(64) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  uint8_t* stage = d.keys.stage.as<uint8_t>();
+  uint32_t* tab = d.keys.tab.as<uint32_t>();
+  std::memcpy(stage, seed, 32);
+  hipError_t e = hipMemcpyAsync(tab + kSignSeedWord, stage, 32, hipMemcpyHostToDevice, d.stream);
+  e = e ? e : launch_ed25519_key_expand(tab, key_id, d.comb(), d.stream);
+  e = e ? e : hipMemcpyAsync(stage + 32, tab + kSignPubWord, 32, hipMemcpyDeviceToHost, d.stream);
+  const hipError_t f = hipStreamSynchronize(d.stream);
+  secure_wipe(stage, 32);
+  if (e == hipSuccess && f == hipSuccess) std::memcpy(pub, stage + 32, 32);
+  return hip_err(e ? e : f);
+}
+
+int signer_add_impl(cordahip_ctx* ctx, const uint8_t seed[32], uint32_t* key_id, uint8_t pub[32]) {
+  std::lock_guard<std::mutex> g(ctx->signer_mu);
+  if (ctx->signer_gen.empty()) {
+    ctx->signer_gen.assign(kSignKeySlots, 0);
+    ctx->signer_live.assign(kSignKeySlots, 0);
+  }
+  if (ctx->signer_count >= kSignKeySlots) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  uint32_t slot = 0;
+  while (ctx->signer_live[slot]) slot++;
+  // the slot's reuse counter: ids differ across a slot's keys until it wraps (2^20 adds into one slot)
+  const uint32_t gen = (ctx->signer_gen[slot] + 1) & ((1u << (32 - kSignSlotBits)) - 1);
+  const uint32_t id = slot | (gen << kSignSlotBits);
+  ctx->signer_gen[slot] = gen;  // consumed even if the add fails
+  int rc = CORDAHIP_SUCCESS;
+  size_t done = 0;
+  uint8_t first[32], cur[32];
+  for (; done < ctx->devs.size() && rc == CORDAHIP_SUCCESS; done++) {
+    Device& d = *ctx->devs[done];
+    std::lock_guard<std::mutex> gd(d.sign_mu);
+    const Activity act(d);
+    rc = signer_expand_on(d, seed, id, done ? cur : first);
+    if (rc == CORDAHIP_SUCCESS && done && std::memcmp(first, cur, 32) != 0) rc = CORDAHIP_ERR_HIP;
+  }
+  if (rc != CORDAHIP_SUCCESS) {  // no device keeps a record of a key the caller never got
+    for (size_t k = 0; k < done; k++) {
+      Device& d = *ctx->devs[k];
+      std::lock_guard<std::mutex> gd(d.sign_mu);
+      if (hipSetDevice(d.id) == hipSuccess && d.keys.tab.p) {
+        (void)signer_zero_record(d, slot);
+        (void)hipMemsetAsync(d.keys.tab.as<uint32_t>() + kSignSeedWord, 0, 32, d.stream);
+        (void)hipStreamSynchronize(d.stream);
+      }
+    }
+    return rc;
+  }
+  ctx->signer_live[slot] = 1;
+  ctx->signer_count++;
+  *key_id = id;
+  std::memcpy(pub, first, 32);
+  if (tracing()) fprintf(stderr, "[cordahip] signer: key id %u added (%u live)\n", id, ctx->signer_count);
+  return CORDAHIP_SUCCESS;
+}
+
+int signer_remove_impl(cordahip_ctx* ctx, uint32_t key_id) {
+  std::lock_guard<std::mutex> g(ctx->signer_mu);
+  const uint32_t slot = key_id & (kSignKeySlots - 1);
+  if (ctx->signer_gen.empty() || !ctx->signer_live[slot] || (slot | (ctx->signer_gen[slot] << kSignSlotBits)) != key_id)
+    return CORDAHIP_ERR_INVALID_ARG;
+  ctx->signer_live[slot] = 0;  // the id is dead from here on, whatever a device answers below
+  ctx->signer_count--;
+  hipError_t e = hipSuccess;
+  for (auto& dp : ctx->devs) {
+    Device& d = *dp;
+    std::lock_guard<std::mutex> gd(d.sign_mu);
+    const Activity act(d);
+    const hipError_t s = hipSetDevice(d.id);
+    const hipError_t z = s ? s : signer_zero_record(d, slot);
+    e = e ? e : z;
+  }
+  if (tracing()) fprintf(stderr, "[cordahip] signer: key id %u removed (%u live)\n", key_id, ctx->signer_count);
+  return hip_err(e);
+}
+
+// The keyed signer on stream s (sign_mu held, device current): behind the table's
+// previous user, followed by the table's fence. A device without a key table yet
+// passes none: every ungated lane is then UNKNOWN_KEY.
+hipError_t sign_enqueue(Device& d, const uint32_t* key_id, const uint8_t* msgs, const uint64_t* moff,
+                        const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* gate, uint8_t* sigs,
+                        uint8_t* status, hipStream_t s) {
+  hipError_t e = d.keys.ev.wait(s);
+  e = e ? e
+        : launch_ed25519_sign_keyed(key_id, msgs, moff, mlen, msg_len, n, gate, d.keys.tab.as<uint32_t>(),
+                                    d.comb(), sigs, status, s);
+  return e ? e : d.keys.ev.record(s);
+}
+
+// cordahip_sign for lanes [lo, hi) on one device, a chunk of CORDAHIP_HOST_CHUNK
+// lanes at a time: the lanes packed into the device's page-locked stage (dense
+// 32-byte rows when every message of the chunk is 32 bytes -- the ids; else each
+// message at a 16-byte-aligned offset with its length), across PCIe, K11, and the
+// signature rows and statuses back into the caller's arrays in lane order.
+int sign_shard(cordahip_ctx* ctx, Device& d, const cordahip_sign_batch* b, uint64_t lo, uint64_t hi) {
+  std::lock_guard<std::mutex> g(d.sign_host_mu);
+  const NodeBind nb(d);
+  const Activity act(d);
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  const uint64_t chunk = env_lanes("CORDAHIP_HOST_CHUNK", 1ull << 22);
+  HostPool& pool = pool_of(ctx, d);
+  hipStream_t s = d.stream;
+  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
+  std::vector<uint64_t> poff;
+  for (uint64_t a = lo; a < hi; a += chunk) {
+    const uint64_t m = std::min(chunk, hi - a);
+    const double t0 = now_ms();
+    poff.resize(m);
+    const SignLayout lay = sign_chunk_layout(b, a, m, poff.data());
+    const bool dense = lay.dense;
+    const uint64_t bytes = lay.bytes;
+    const size_t need[7] = {(size_t)m * 4, (size_t)std::max<uint64_t>(bytes, 16), (size_t)m * 8, (size_t)m * 4,
+                            (size_t)m,     (size_t)m * 64,                        (size_t)m};
+    for (int k = 0; k < 7; k++)  // the previous chunk has drained: growing frees nothing in use
+      if (d.sign_h[k].ensure(need[k]) != hipSuccess || d.sign_d[k].ensure(need[k]) != hipSuccess)
+        return CORDAHIP_ERR_OUT_OF_MEMORY;
+    uint8_t* hm = d.sign_h[1].as<uint8_t>();
+    uint64_t* ho = d.sign_h[2].as<uint64_t>();
+    uint32_t* hl = d.sign_h[3].as<uint32_t>();
+    pool.parallel_for(m, 1u << 14, [&](uint64_t x, uint64_t y) {
+      sign_pack_rows(b, a, x, y, lay, poff.data(), d.sign_h[0].as<uint32_t>(), d.sign_h[4].as<uint8_t>(), hm, ho, hl);
+    });
+    hipError_t e = hipMemcpyAsync(d.sign_d[0].p, d.sign_h[0].p, m * 4, h2d, s);
+    if (bytes) e = e ? e : hipMemcpyAsync(d.sign_d[1].p, hm, bytes, h2d, s);
+    if (!dense) {
+      e = e ? e : hipMemcpyAsync(d.sign_d[2].p, ho, m * 8, h2d, s);
+      e = e ? e : hipMemcpyAsync(d.sign_d[3].p, hl, m * 4, h2d, s);
+    }
+    if (b->gate) e = e ? e : hipMemcpyAsync(d.sign_d[4].p, d.sign_h[4].p, m, h2d, s);
+    if (e == hipSuccess) {
+      std::lock_guard<std::mutex> gs(d.sign_mu);
+      e = sign_enqueue(d, d.sign_d[0].as<uint32_t>(), d.sign_d[1].as<uint8_t>(),
+                       dense ? nullptr : d.sign_d[2].as<uint64_t>(), dense ? nullptr : d.sign_d[3].as<uint32_t>(), 32, m,
+                       b->gate ? d.sign_d[4].as<uint8_t>() : nullptr, d.sign_d[5].as<uint8_t>(),
+                       d.sign_d[6].as<uint8_t>(), s);
+    }
+    e = e ? e : hipMemcpyAsync(d.sign_h[5].p, d.sign_d[5].p, m * 64, d2h, s);
+    e = e ? e : hipMemcpyAsync(d.sign_h[6].p, d.sign_d[6].p, m, d2h, s);
+    e = e ? e : d.sign_host_ev.record(s);
+    e = e ? e : d.sign_host_ev.sync();
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(s);  // no queued work outlives the call
+      return CORDAHIP_ERR_HIP;
+    }
+    std::memcpy(b->sig + a * 64, d.sign_h[5].p, m * 64);
+    std::memcpy(b->status + a, d.sign_h[6].p, m);
+    if (tracing())
+      fprintf(stderr, "[cordahip] dev %d sign chunk: %llu lanes (%s messages) in %.2f ms\n", d.id,
+              (unsigned long long)m, dense ? "32-byte" : "CSR", now_ms() - t0);
+  }
+  return CORDAHIP_SUCCESS;
+}
+
+int sign_impl(cordahip_ctx* ctx, const cordahip_sign_batch* b) {
+  const uint64_t n = b->n;
+  if (n == 0) return CORDAHIP_SUCCESS;
+  if (!b->key_id || !b->msg_off || !b->sig || !b->status) return CORDAHIP_ERR_INVALID_ARG;
+  if (!check_sign_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
+  if (b->msg_off[0] != b->msg_off[n] && !b->msg) return CORDAHIP_ERR_INVALID_ARG;
+  return for_shards(ctx->devs, n, 64, [&](Device& d, uint64_t lo, uint64_t hi) { return sign_shard(ctx, d, b, lo, hi); });
+}
+
 Device* dev_at(cordahip_ctx* ctx, int device) {
   if (!ctx || device < 0 || device >= (int)ctx->devs.size()) return nullptr;
   return ctx->devs[device].get();
@@ -1620,6 +1804,43 @@ int cordahip_ed25519_sign_device(cordahip_ctx* ctx, int device, const void* d_se
   return hip_err(launch_ed25519_sign(static_cast<const uint8_t*>(d_seeds), static_cast<const uint8_t*>(d_msgs),
                                      msg_len, n, d->btab.as<uint32_t>(), static_cast<uint8_t*>(d_pubs),
                                      static_cast<uint8_t*>(d_sigs), s));
+}
+
+int cordahip_signer_add_ed25519(cordahip_ctx* ctx, const uint8_t seed[32], uint32_t* key_id, uint8_t pub[32]) {
+  if (!ctx || !seed || !key_id || !pub) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return signer_add_impl(ctx, seed, key_id, pub); });
+}
+
+int cordahip_signer_remove(cordahip_ctx* ctx, uint32_t key_id) {
+  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return signer_remove_impl(ctx, key_id); });
+}
+
+int cordahip_sign(cordahip_ctx* ctx, const cordahip_sign_batch* batch) {
+  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return sign_impl(ctx, batch); });
+}
+
+int cordahip_sign_submit(cordahip_ctx* ctx, const cordahip_sign_batch* batch, uint64_t* ticket) {
+  return submit(ctx, ticket, sign_impl, batch);
+}
+
+int cordahip_ed25519_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
+                                       uint32_t msg_len, uint64_t n, const void* d_gate, void* d_sigs,
+                                       void* d_status, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || (n && (!d_key_id || !d_sigs || !d_status || (msg_len && !d_msgs)))) return CORDAHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_sigs) & 15) || (reinterpret_cast<uintptr_t>(d_key_id) & 3) ||
+      (msg_len == 32 && (reinterpret_cast<uintptr_t>(d_msgs) & 15)))
+    return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    std::lock_guard<std::mutex> g(d->sign_mu);
+    return device_call(*d, hip_stream, [&](hipStream_t s) {
+      return sign_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_msgs), nullptr,
+                          nullptr, msg_len, n, static_cast<const uint8_t*>(d_gate), static_cast<uint8_t*>(d_sigs),
+                          static_cast<uint8_t*>(d_status), s);
+    });
+  });
 }
 
 int cordahip_ecdsa_sign_device(cordahip_ctx* ctx, int device, const void* d_scheme, const void* d_seeds,

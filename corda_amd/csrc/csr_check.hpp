@@ -107,6 +107,23 @@ bool check_filtered_build_batch(Par&& par, const cordahip_filtered_build_batch* 
   return ok.load();
 }
 
+// a signing batch: msg_off[0..n] non-decreasing and within msg_bytes, and no
+// single message of 2^32 bytes or more (the kernel's message lengths are 32-bit)
+template <class Par>
+bool check_sign_batch(Par&& par, const cordahip_sign_batch* b) {
+  if (b->n == 0) return true;
+  if (!b->msg_off || !csr_ok(par, b->msg_off, 0, b->n, b->msg_bytes)) return false;
+  std::atomic<bool> ok{true};
+  par(b->n, 1u << 16, [&](uint64_t x, uint64_t y) {
+    for (uint64_t i = x; i < y; i++)
+      if (b->msg_off[i + 1] - b->msg_off[i] > 0xffffffffull) {
+        ok.store(false, std::memory_order_relaxed);
+        return;
+      }
+  });
+  return ok.load();
+}
+
 // a cover (required-signer coverage): tx_req_off[0..ntx] non-decreasing and
 // within nreq, req_tok_off over the required keys it spans within ntok, the
 // whole key table's ckey_off[0..nckey] within ckey_bytes (any leaf may name any

@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "ed25519_ops.hpp"
 #include "ed25519_ws.hpp"
 #include "sha2_device.hpp"
 #include "status.hpp"
@@ -34,23 +35,8 @@
 namespace cordahip {
 
 // ---------------------------------------------------------------------------
-// B table (layout: ed25519_ws.hpp), built once per context by a kernel.
-CDEV void ge_base(ge_p3& b) {
-  const uint32_t bx[10] = {0x325d51a, 0x18b5823, 0xf6592a, 0x104a92d, 0x1a4b31d,
-                           0x1d6dc5c, 0x27118fe, 0x7fd814, 0x13cd6e5, 0x85a4db};
-  const uint32_t by[10] = {0x2666658, 0x1999999, 0xcccccc, 0x1333333, 0x1999999,
-                           0x666666, 0x3333333, 0xcccccc, 0x2666666, 0x1999999};
-  const uint32_t bt[10] = {0x1b7dda3, 0x1a2ace9, 0x25eadbb, 0x3ba8a, 0x83c27e,
-                           0xabe37d, 0x1274732, 0xccacdd, 0xfd78b7, 0x19e1d7c};
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    b.X.v[i] = bx[i];
-    b.Y.v[i] = by[i];
-    b.T.v[i] = bt[i];
-  }
-  fe_set(b.Z, 1);
-}
-
+// B table (layout: ed25519_ws.hpp), built once per context by a kernel
+// (ge_base, store_niels_entry: ed25519_ops.hpp).
 // tab: entries [0, kBTableEntries) = [k]B, then [k]B' with B' = [2^128]B
 __global__ void __launch_bounds__(64) ed25519_btable_kernel(uint32_t* __restrict__ tab) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,86 +53,7 @@ __global__ void __launch_bounds__(64) ed25519_btable_kernel(uint32_t* __restrict
     ge_dbl<true>(P, P);
     if ((k >> bit) & 1) ge_add<true>(P, P, bc);
   }
-  fe zi, x, y, t, d2;
-  fe_invert(zi, P.Z);
-  fe_mul(x, P.X, zi);
-  fe_mul(y, P.Y, zi);
-  fe_const_d2(d2);
-  ge_niels n;
-  fe_add(n.ypx, y, x);
-  fe_carry(n.ypx);
-  fe_sub(n.ymx, y, x);
-  fe_mul(t, x, y);
-  fe_mul(n.xy2d, t, d2);
-  uint32_t* o = tab + g * kBEntryWords;
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    o[i] = n.ypx.v[i];
-    o[10 + i] = n.ymx.v[i];
-    o[20 + i] = n.xy2d.v[i];
-  }
-  o[30] = 0;
-  o[31] = 0;
-}
-
-
-// ---------------------------------------------------------------------------
-// SHA-512 over  seg0(32 B, registers) || seg1(32 B, registers, optional) || msg
-// (global, msg_len bytes). Fast path: everything fits one block with msg_len
-// a multiple of 8 bytes' worth of whole words read as registers.
-CDEV uint32_t byte_of(const uint32_t w[8], int idx) { return (word_sel(w, idx >> 2) >> (8 * (idx & 3))) & 0xffu; }
-
-CDEV void sha512_segments(uint32_t out_le[16], const uint32_t s0[8], const uint32_t s1[8], bool has_s1,
-                          const uint8_t* __restrict__ msg, uint32_t msg_len) {
-  uint64_t h[8];
-  sha512_init(h);
-  const uint32_t pre = has_s1 ? 64u : 32u;
-  const uint64_t total = (uint64_t)pre + msg_len;
-  uint64_t w[16];
-  if (has_s1 && msg_len == 32) {
-    // hot shape: R || A || txId = 96 bytes, one block
-    const uint4* m4 = reinterpret_cast<const uint4*>(msg);
-    const uint4 ma = m4[0], mb = m4[1];
-    const uint32_t m[8] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      w[q] = ((uint64_t)bswap32(s0[2 * q]) << 32) | bswap32(s0[2 * q + 1]);
-      w[4 + q] = ((uint64_t)bswap32(s1[2 * q]) << 32) | bswap32(s1[2 * q + 1]);
-      w[8 + q] = ((uint64_t)bswap32(m[2 * q]) << 32) | bswap32(m[2 * q + 1]);
-    }
-    w[12] = 0x8000000000000000ULL;
-    w[13] = 0;
-    w[14] = 0;
-    w[15] = total * 8;
-    sha512_block(h, w);
-  } else {
-#ifndef ED_NO_GENERIC_SHA
-    const uint64_t nblocks = (total + 17 + 127) / 128;
-    for (uint64_t b = 0; b < nblocks; b++) {
-      for (int q = 0; q < 16; q++) {
-        uint64_t word = 0;
-        for (int k = 0; k < 8; k++) {
-          const uint64_t pos = b * 128 + (uint64_t)q * 8 + k;
-          uint32_t byte;
-          if (pos < 32) byte = byte_of(s0, (int)pos);
-          else if (pos < pre) byte = byte_of(s1, (int)(pos - 32));
-          else if (pos < total) byte = msg[pos - pre];
-          else if (pos == total) byte = 0x80;
-          else if (b == nblocks - 1 && q == 15) byte = (uint32_t)(((total * 8) >> (8 * (7 - k))) & 0xff);
-          else byte = 0;
-          word = (word << 8) | byte;
-        }
-        w[q] = word;
-      }
-      sha512_block(h, w);
-    }
-#endif
-  }
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    out_le[2 * i] = bswap32((uint32_t)(h[i] >> 32));
-    out_le[2 * i + 1] = bswap32((uint32_t)h[i]);
-  }
+  store_niels_entry(tab + g * kBEntryWords, P);
 }
 
 // ---------------------------------------------------------------------------
@@ -411,8 +318,6 @@ CDEV bool ge_strict_ok(const ge_p3& R, const uint32_t w[8]) {
   return !((w[7] >> 31) && fe_iszero(R.X));
 }
 
-CDEV void sc_muladd(uint32_t out[8], const uint32_t a[8], const uint32_t b[8], const uint32_t c[8]);
-
 // an affine point (Z = 1) as X, Y, T (30 words, 16-B aligned slot of 40)
 CDEV void store_point(uint32_t* __restrict__ o, const ge_p3& p) {
   uint4* o4 = reinterpret_cast<uint4*>(o);
@@ -675,31 +580,6 @@ CDEV void fixed_base_mult(ge_p3& P, const uint32_t k[8], const uint32_t* __restr
     niels_cneg(nb, d < 0);
     ge_madd<true>(P, P, nb);
   }
-}
-
-CDEV void sc_muladd(uint32_t out[8], const uint32_t a[8], const uint32_t b[8], const uint32_t c[8]) {
-  uint32_t x[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) x[i] = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    uint64_t carry = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const uint64_t t = (uint64_t)a[i] * b[j] + x[i + j] + carry;
-      x[i + j] = (uint32_t)t;
-      carry = t >> 32;
-    }
-    x[i + 8] = (uint32_t)carry;
-  }
-  uint64_t carry = 0;
-#pragma unroll
-  for (int i = 0; i < 16; i++) {
-    const uint64_t t = (uint64_t)x[i] + (i < 8 ? c[i] : 0u) + carry;
-    x[i] = (uint32_t)t;
-    carry = t >> 32;
-  }
-  sc_reduce512(out, x);
 }
 
 __global__ void __launch_bounds__(256) ed25519_sign_kernel(const uint8_t* __restrict__ seeds,

@@ -157,5 +157,42 @@ inline void pack_ec_row(const cordahip_sig_batch* b, const MV& mv, bool do_verif
   mo += ml;
 }
 
+// ---- cordahip_sign chunks (a batch that passed check_sign_batch) ----------------
+// Lanes [a, a + m) go to the device as dense 32-byte rows when every message of
+// the chunk has 32 bytes (transaction ids: the signer's one-block shape), else
+// each message at a 16-byte-aligned offset of the stage with its length beside it.
+struct SignLayout {
+  bool dense;
+  uint64_t bytes;  // message bytes of the stage
+};
+// poff[m]: the lanes' offsets in the stage (written only for a chunk that is not dense)
+inline SignLayout sign_chunk_layout(const cordahip_sign_batch* b, uint64_t a, uint64_t m, uint64_t* poff) {
+  SignLayout l{true, m * 32};
+  for (uint64_t i = 0; i < m && l.dense; i++) l.dense = b->msg_off[a + i + 1] - b->msg_off[a + i] == 32;
+  if (l.dense) return l;
+  l.bytes = 0;
+  for (uint64_t i = 0; i < m; i++) {
+    poff[i] = l.bytes;
+    l.bytes += (b->msg_off[a + i + 1] - b->msg_off[a + i] + 15) / 16 * 16;
+  }
+  return l;
+}
+// rows [x, y) of the chunk at lane a: key ids, gate bytes (b->gate != NULL), messages, and
+// -- not dense -- offsets and lengths
+inline void sign_pack_rows(const cordahip_sign_batch* b, uint64_t a, uint64_t x, uint64_t y, const SignLayout& l,
+                           const uint64_t* poff, uint32_t* hid, uint8_t* hgate, uint8_t* hm, uint64_t* ho,
+                           uint32_t* hl) {
+  for (uint64_t i = x; i < y; i++) {
+    const uint64_t o = b->msg_off[a + i], len = b->msg_off[a + i + 1] - o, p = l.dense ? i * 32 : poff[i];
+    hid[i] = b->key_id[a + i];
+    if (b->gate) hgate[i] = b->gate[a + i];
+    if (len) std::memcpy(hm + p, b->msg + o, len);
+    if (!l.dense) {
+      ho[i] = p;
+      hl[i] = (uint32_t)len;
+    }
+  }
+}
+
 }  // namespace rt
 }  // namespace cordahip

@@ -385,10 +385,28 @@ void device_budget(Device& d) {  // device current
 void trim_device(Device& d) {
   SetLease l0(d, 0, true), l1(d, 1, true);
   std::lock_guard<std::mutex> gk(d.kryo_mu), gs(d.stream_mu), gp(d.ped_mu), ge0(d.ed_mu[0]), ge1(d.ed_mu[1]),
-      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu), gv(d.cover_mu);
+      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu), gv(d.cover_mu), gh(d.sign_host_mu);
   if (hipSetDevice(d.id) != hipSuccess) return;
   d.release_idle();
   if (tracing()) fprintf(stderr, "[cordahip] dev %d: idle buffers released\n", d.id);
+}
+
+void secure_wipe(void* p, size_t n) {
+  volatile unsigned char* v = static_cast<volatile unsigned char*>(p);
+  while (n--) *v++ = 0;
+}
+
+// The signer's key records zeroed on every device: after every signing kernel
+// that may read them (keys.ev), before ~Device frees the tables.
+void signer_wipe(cordahip_ctx* ctx) {
+  for (auto& dp : ctx->devs) {
+    Device& d = *dp;
+    std::lock_guard<std::mutex> g(d.sign_mu);
+    if (!d.keys.tab.p || hipSetDevice(d.id) != hipSuccess) continue;
+    (void)d.keys.ev.sync();
+    (void)hipMemsetAsync(d.keys.tab.p, 0, d.keys.tab.cap, d.stream);
+    (void)hipStreamSynchronize(d.stream);
+  }
 }
 
 // the in-process partition rule (cordahip_shard_range)
@@ -442,7 +460,7 @@ static int init_impl(uint32_t device_mask, cordahip_ctx** out) {
     for (auto& tc : dev.ring)
       if (hipEventCreate(&tc.a) != hipSuccess || hipEventCreate(&tc.b) != hipSuccess) rc = CORDAHIP_ERR_HIP;
     if (rc != CORDAHIP_SUCCESS) break;
-    if (dev.btab.ensure(ed25519_btable_bytes()) || dev.gtab_k1.ensure(ecdsa_gtable_bytes()) ||
+    if (dev.btab.ensure(ed25519_btable_bytes() + ed25519_comb_bytes()) || dev.gtab_k1.ensure(ecdsa_gtable_bytes()) ||
         dev.gtab_r1.ensure(ecdsa_gtable_bytes())) {
       rc = CORDAHIP_ERR_OUT_OF_MEMORY;
       break;
@@ -454,6 +472,7 @@ static int init_impl(uint32_t device_mask, cordahip_ctx** out) {
       break;
     }
     if (launch_ed25519_btable(dev.btab.as<uint32_t>(), dev.stream) != hipSuccess ||
+        launch_ed25519_comb(dev.comb(), dev.stream) != hipSuccess ||
         launch_ecdsa_gtables(dev.gtab_k1.as<uint32_t>(), dev.gtab_r1.as<uint32_t>(), dev.stream) != hipSuccess ||
         hipStreamSynchronize(dev.stream) != hipSuccess)
       rc = CORDAHIP_ERR_HIP;
@@ -550,6 +569,7 @@ void cordahip_shutdown(cordahip_ctx* ctx) {
     std::lock_guard<std::mutex> g(ctx->mu);
     ctx->jobs.clear();
   }
+  signer_wipe(ctx);  // no key record outlives the context in device memory
   delete ctx;  // ~Device frees each device's buffers, events and streams
 }
 

@@ -35,6 +35,18 @@ hipError_t launch_ed25519_verify(const uint8_t* keys, const uint8_t* sigs, const
 size_t ed25519_ws_lane_bytes();
 hipError_t launch_ed25519_sign(const uint8_t* seeds, const uint8_t* msgs, uint32_t msg_len, uint64_t n,
                                const uint32_t* btab, uint8_t* pubs, uint8_t* sigs, hipStream_t s);
+// ed25519_sign.hip (K11): the comb table [d 16^j]B, the key table's expansion
+// kernel (the seed is in the table's scratch words; the public key comes back
+// there: ed25519_comb.hpp kSignSeedWord / kSignPubWord) and the keyed signer
+// (moff / mlen non-null: per-lane message offsets and lengths, else dense rows)
+size_t ed25519_comb_bytes();
+size_t ed25519_keytab_bytes();
+hipError_t launch_ed25519_comb(uint32_t* tab, hipStream_t s);
+hipError_t launch_ed25519_key_expand(uint32_t* keytab, uint32_t key_id, const uint32_t* comb, hipStream_t s);
+hipError_t launch_ed25519_sign_keyed(const uint32_t* key_id, const uint8_t* msgs, const uint64_t* moff,
+                                     const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* gate,
+                                     const uint32_t* keytab, const uint32_t* comb, uint8_t* sigs, uint8_t* status,
+                                     hipStream_t s);
 hipError_t launch_sha256_leaves(const uint8_t* bytes, const uint64_t* off, uint64_t nleaves, uint32_t* hashes,
                                 hipStream_t s);
 hipError_t launch_merkle_root(uint32_t* hashes, const uint64_t* tx_leaf_off, uint64_t ntx, uint8_t* txid,
@@ -382,6 +394,27 @@ struct RsaWork {
   }
 };
 
+// The Ed25519 signer's key table of one device (ed25519_comb.hpp: 4,096 records of
+// 128 bytes and the expansion kernel's scratch): private keys, so it is handled apart
+// from the buffers above. It is allocated (zeroed) by the context's first
+// cordahip_signer_add_ed25519, counted in the device's account like every DevBuf, and
+// then lives until cordahip_shutdown, which zeroes it before ~Device frees it: the
+// idle release and cordahip_trim never see it (Device::visit leaves it out;
+// Device::visit_keys is for bind and ~Device), so a signer cannot lose its keys to an
+// idle timer. ev: the fence of the kernels that read the table. stage: 64 page-locked
+// bytes the seed goes out and the public key comes back in (wiped before add returns).
+struct SignKeys {
+  DevBuf tab;
+  PinBuf stage;
+  Fence ev;
+  template <class V>
+  void visit(V& v) {
+    v.dev(tab, kKept);
+    v.pin(stage, kKept);
+    v.fence(ev);
+  }
+};
+
 // Fork-join pool for host-side packing and scattering. parallel_for splits
 // [0, n) into pieces of at least `grain` lanes; the caller runs pieces too,
 // so concurrent callers (one pipeline per device and section) all progress.
@@ -516,10 +549,30 @@ struct Device {
   std::mutex cover_mu;
   DevBuf cover_stack;
   Fence cover_ev;
+  // Ed25519 signing (K11). The comb table [d 16^j]B sits in btab's allocation, after
+  // the B tables (comb()), built with them by cordahip_init. keys: the key records
+  // (SignKeys). sign_mu orders every user of the key table: a signing call holds it
+  // while it enqueues -- its stream waits for keys.ev, its kernel is followed by
+  // keys.ev -- and add / remove hold it for their whole run; remove waits for keys.ev
+  // first, so no kernel still reads the record it zeroes.
+  SignKeys keys;
+  std::mutex sign_mu;
+  uint32_t* comb() const { return reinterpret_cast<uint32_t*>(static_cast<char*>(btab.p) + ed25519_btable_bytes()); }
+  // cordahip_sign's chunk stage: h/d[0] key ids, [1] messages, [2] their offsets, [3]
+  // their lengths, [4] gate bytes, [5] signature rows, [6] statuses. sign_host_mu is
+  // held for a shard's run; sign_host_ev follows a chunk's last copy.
+  std::mutex sign_host_mu;
+  PinBuf sign_h[7];
+  DevBuf sign_d[7];
+  Fence sign_host_ev;
 
+  // everything but `keys`, which the idle release is never offered (visit_keys)
   template <class V>
   void visit(V& v) {
     for (DevBuf* b : {&btab, &gtab_k1, &gtab_r1}) v.dev(*b, kKept);
+    for (PinBuf& b : sign_h) v.pin(b, kFreed);
+    for (DevBuf& b : sign_d) v.dev(b, kFreed);
+    v.fence(sign_host_ev);
     for (EcWork& w : ec) w.visit(v);
     rsa.visit(v);
     for (hipStream_t* s : {&s_rsa, &stream, &s_copy, &s_ed, &s_ec, &s_ed2, &s_idcopy}) v.stream(*s);  // s_ec2 is s_idcopy
@@ -545,6 +598,13 @@ struct Device {
     } v;
     id = v.id = hip_id;
     visit(v);
+    visit_keys(v);
+  }
+  // the signer's key table: bound and destroyed with the rest, never released while
+  // the context lives
+  template <class V>
+  void visit_keys(V& v) {
+    keys.visit(v);
   }
   struct Release : Visitor {  // the buffers; all: the kept ones too
     bool all = false;
@@ -583,6 +643,7 @@ struct Device {
     } v;
     v.all = true;
     visit(v);
+    visit_keys(v);
   }
 };
 
@@ -792,6 +853,13 @@ struct cordahip_ctx {
   std::vector<std::pair<std::unique_ptr<uint64_t[]>, uint64_t>> txof_free;
   // the idle release (CORDAHIP_IDLE_RELEASE_MS): a thread that frees an idle
   // device's grow-only buffers (runtime.cpp trim_device)
+  // the signer's key registry (cordahip_signer_add_ed25519 / _remove): which of the
+  // key table's slots are live and each slot's reuse counter (empty until the first
+  // add); no key material. signer_mu is held for an add's or a remove's whole run.
+  std::mutex signer_mu;
+  std::vector<uint32_t> signer_gen;
+  std::vector<uint8_t> signer_live;
+  uint32_t signer_count = 0;
   std::thread reaper;
   std::mutex reaper_mu;
   std::condition_variable reaper_cv;
@@ -855,5 +923,9 @@ int sig_verify_range(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_si
 int ed25519_dense_host(cordahip_ctx* ctx, const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs,
                        uint32_t msg_len, uint64_t n, uint8_t* status, uint64_t* verdict);
 void verdict_from_status(cordahip_ctx* ctx, const uint8_t* status, uint64_t n, uint64_t* verdict);
+// every key record of every device zeroed (cordahip_shutdown, before the tables are freed)
+void signer_wipe(cordahip_ctx* ctx);
+// zero n bytes with a write the compiler cannot drop
+void secure_wipe(void* p, size_t n);
 }  // namespace rt
 }  // namespace cordahip

@@ -53,7 +53,20 @@ CDEV void sc_sub_L9(uint32_t r[9]) {
   }
 }
 
+// r -= L where sub (a select per word: no branch on r)
+CDEV void sc_csub_L9(uint32_t r[9], bool sub) {
+  uint32_t t[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) t[i] = r[i];
+  sc_sub_L9(t);
+#pragma unroll
+  for (int i = 0; i < 9; i++) r[i] = sub ? t[i] : r[i];
+}
+
 // Barrett reduction (HAC 14.42, b = 2^32, k = 8) of a 512-bit x mod L.
+// SELECT: the two final conditional subtractions are selects instead of
+// branches (the signer's scalars are secret; verification's are public).
+template <bool SELECT = false>
 CDEV void sc_reduce512(uint32_t out[8], const uint32_t x[16]) {
   // q2 = (x >> 224) * mu ; only words >= 9 are used (q3 = q2 >> 288)
   uint32_t p[18];
@@ -95,8 +108,13 @@ CDEV void sc_reduce512(uint32_t out[8], const uint32_t x[16]) {
     r[i] = (uint32_t)d;
     borrow = (d >> 63) & 1;
   }
-  if (sc_geq_L9(r)) sc_sub_L9(r);
-  if (sc_geq_L9(r)) sc_sub_L9(r);
+  if (SELECT) {
+    sc_csub_L9(r, sc_geq_L9(r));
+    sc_csub_L9(r, sc_geq_L9(r));
+  } else {
+    if (sc_geq_L9(r)) sc_sub_L9(r);
+    if (sc_geq_L9(r)) sc_sub_L9(r);
+  }
 #pragma unroll
   for (int i = 0; i < 8; i++) out[i] = r[i];
 }

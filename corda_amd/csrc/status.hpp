@@ -11,4 +11,7 @@ static constexpr uint8_t kStatusMalformedSig = 2; // engine SignatureException
 static constexpr uint8_t kStatusBadKey = 3;       // key decode IllegalArgumentException
 static constexpr uint8_t kStatusUnsupported = 4;  // IllegalArgumentException (scheme)
 static constexpr uint8_t kStatusEmpty = 5;        // IllegalArgumentException (empty input)
+// signing lanes (CORDAHIP_SIGN_*)
+static constexpr uint8_t kSignUnknownKey = 14;    // no such key in the registry (KMS lookup fails)
+static constexpr uint8_t kSignSkipped = 15;       // the lane's gate byte was nonzero
 }  // namespace cordahip

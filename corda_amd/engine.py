@@ -108,6 +108,55 @@ class Engine:
                                                  msgs.shape[1], n, pubs.data_ptr(), sigs.data_ptr(), s),
               "cordahip_ed25519_sign_device")
 
+    # ---- Ed25519 signing with registered keys (Crypto.doSign per lane) -----------
+    def signer_add_ed25519(self, seed: bytes):
+        """cordahip_signer_add_ed25519: the 32-byte seed expanded on every device of the context.
+        Returns (key_id, pub); the library keeps no host copy of the seed."""
+        assert len(seed) == 32
+        kid = ctypes.c_uint32()
+        pub = ctypes.create_string_buffer(32)
+        check(lib().cordahip_signer_add_ed25519(self._ctx, bytes(seed), ctypes.byref(kid), pub),
+              "cordahip_signer_add_ed25519")
+        return kid.value, pub.raw
+
+    def signer_remove(self, key_id: int):
+        """cordahip_signer_remove: waits for the signing calls in flight, zeroes the key's record on
+        every device; the id answers SIGN_UNKNOWN_KEY from then on."""
+        check(lib().cordahip_signer_remove(self._ctx, key_id), "cordahip_signer_remove")
+
+    def sign_batch(self, key_ids: Sequence[int], msgs: Sequence[bytes], gate=None, async_: bool = False):
+        """cordahip_sign / cordahip_sign_submit: lane i signs msgs[i] with key key_ids[i] unless gate[i]
+        is nonzero. Returns (sigs[n, 64], status[n]) -- zero rows where status is not OK -- or,
+        async_, a Ticket whose wait() returns them."""
+        n = len(msgs)
+        assert len(key_ids) == n and (gate is None or len(gate) == n)
+        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
+        mb, mo = self._csr(list(msgs))
+        g = None if gate is None else np.ascontiguousarray(np.asarray(list(gate) or [0], dtype=np.uint8))
+        sig = np.zeros((max(n, 1), 64), dtype=np.uint8)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        b = _lib.SignBatch(n, _ptr(ids), _ptr(mb), _ptr(mo), _ptr(g) if g is not None else None, _ptr(sig), _ptr(st),
+                           mb.size if n and mo[n] else 0)
+        keep = (ids, mb, mo, g, sig, st, b)
+        res = lambda: (sig[:n], st[:n])  # noqa: E731
+        if async_:
+            t = ctypes.c_uint64()
+            check(lib().cordahip_sign_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)), "cordahip_sign_submit")
+            return Ticket(self, t.value, res, keep)
+        check(lib().cordahip_sign(self._ctx, ctypes.byref(b)), "cordahip_sign")
+        return res()
+
+    def ed25519_sign_keyed_device(self, key_ids, msgs, sigs, status, gate=None, device: int = 0, stream=None):
+        """cordahip_ed25519_sign_keyed_device over device tensors: key_ids int32 [n], msgs uint8
+        [n, L], gate uint8 [n] or None (typically the tx_status an earlier call on `stream` wrote);
+        outputs sigs uint8 [n, 64] and status uint8 [n]."""
+        n = key_ids.shape[0]
+        s = stream.cuda_stream if stream is not None else 0
+        check(lib().cordahip_ed25519_sign_keyed_device(
+            self._ctx, device, key_ids.data_ptr(), msgs.data_ptr() if msgs.shape[1] else None, msgs.shape[1], n,
+            gate.data_ptr() if gate is not None else None, sigs.data_ptr(), status.data_ptr(), s),
+            "cordahip_ed25519_sign_keyed_device")
+
     def ecdsa_sign_device(self, scheme, seeds, msgs, keys, key_len, sigs, sig_len, device: int = 0, stream=None):
         """Device tensors: scheme[n] u8 (2/3), seeds[n,32], msgs[n,L] -> keys[n,65], key_len[n], sigs[n,72], sig_len[n]."""
         n = seeds.shape[0]

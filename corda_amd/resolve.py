@@ -33,6 +33,7 @@ TX_NO_LEAVES, TX_NO_SIGNATURES = 6, 7
 TX_SIGNATURES_MISSING, TX_BAD_COVER = 10, 11  # required-signer coverage (cordahip_cover)
 REQ_MISSING = 1
 TX_HASHES_NOT_IN_TREE = 12  # FilteredTransaction build: the count rule (PartialMerkleTree.kt:75-76)
+_SIGN_UNKNOWN_KEY = 14  # cordahip_sign: the lane's key id names no live key
 
 
 class SignatureException(Exception):
@@ -49,6 +50,11 @@ class SignaturesMissingException(SignatureException):
 
 class IllegalArgumentException(Exception):
     """java.lang.IllegalArgumentException (require failures, unsupported schemes, bad keys)."""
+
+
+class NoSuchElementException(Exception):
+    """java.util.NoSuchElementException (the KMS holds no key pair for the key asked for:
+    `publicKey.keys.first { keys.containsKey(it) }`, PersistentKeyManagementService.kt:80-85)."""
 
 
 class MerkleTreeException(Exception):
@@ -228,6 +234,30 @@ def build_filtered_transactions(engine, wtxs, filtering: Callable[[bytes], bool]
             raise RuntimeError("filtered_tx_build: transaction %d has status %d" % (t, st))
         out.append(([c for c, f in zip(cs, masks[t]) if f], toks[t], bytes(ids[t])))
     return out
+
+
+def verify_and_sign_filtered_transactions(engine, ftxs, key_id: int):
+    """What an oracle or a non-validating notary does with a batch of tear-offs
+    (NodeInterestRates.sign, NodeInterestRates.kt:149-180: ftx.verify(), then
+    keyManagementService.sign(ftx.rootHash.bytes, signingKey); NotaryFlow.Service,
+    NotaryFlow.kt:114-116): Engine.filtered_tx_verify over ftxs (the tuples it takes),
+    then one Engine.sign_batch over the root hashes with the registered key `key_id`,
+    gated on the verification statuses -- a tear-off that did not verify is not signed.
+
+    Returns (tx_status, sigs): tx_status[t] as filtered_tx_verify gives it, sigs[t] the
+    64-byte signature over ftxs[t]'s root, or None where tx_status[t] != OK. An id that
+    names no live key raises NoSuchElementException, as the KMS's key lookup does
+    (PersistentKeyManagementService.kt:80-89)."""
+    if not ftxs:
+        return [], []
+    status = engine.filtered_tx_verify(ftxs)
+    sigs, sst = engine.sign_batch([key_id] * len(ftxs), [bytes(f[2]) for f in ftxs], gate=status)
+    out = []
+    for t in range(len(ftxs)):
+        if int(sst[t]) == _SIGN_UNKNOWN_KEY:
+            raise NoSuchElementException("no registered key %d" % key_id)
+        out.append(bytes(sigs[t]) if int(sst[t]) == OK else None)
+    return [int(x) for x in status], out
 
 
 def topological_sort(stxs: Sequence[SignedTx], ids: Sequence[bytes]) -> List[int]:

@@ -265,6 +265,82 @@ int cordahip_stream_verify(cordahip_ctx* ctx, const cordahip_stream_batch* batch
 int cordahip_ed25519_sign_device(cordahip_ctx* ctx, int device, const void* d_seeds, const void* d_msgs,
                                  uint32_t msg_len, uint64_t n, void* d_pubs, void* d_sigs, void* hip_stream);
 
+/* ---- Ed25519 batch signing with registered keys -------------------------------- *
+ * Replaces, per lane, Crypto.doSign(EDDSA_ED25519_SHA512, key, clearData)
+ * (Crypto.kt:394-401) as the notary (NotaryFlow.Service.signAndSendResponse ->
+ * service.sign(txId.bytes), NotaryFlow.kt:114-116), an oracle
+ * (keyManagementService.sign(ftx.rootHash.bytes, key), NodeInterestRates.kt:149-180)
+ * and ServiceHub.kt:138,179 reach it: a handful of long-lived keys, many 32-byte
+ * ids. Ed25519 signing is deterministic (RFC 8032; i2p EdDSAEngine), so every
+ * signature is bit-identical to the JVM's. ECDSA and RSA signing and
+ * CompositeSignature assembly are not offered.
+ *
+ * Key registry. cordahip_signer_add_ed25519 expands the 32-byte seed on every
+ * device of the context (h = SHA-512(seed), a = clamp(h[0:32]) mod L, prefix =
+ * h[32:64], A = [a]B) into a 128-byte record of a per-device table, returns the
+ * key's id and writes A (EdDSAPublicKey.Abyte, what the oracle's keypair gives)
+ * to pub. A context holds up to 4096 live keys; a full table is
+ * CORDAHIP_ERR_OUT_OF_MEMORY. The table (512 KB per device) is allocated by the
+ * first add -- a context that never signs allocates nothing -- is counted in
+ * cordahip_device_mem, and is kept by cordahip_trim and the idle release.
+ * Custody: the seed crosses to each device through page-locked staging the
+ * library wipes before add returns, and a device scratch the expansion kernel
+ * zeroes; after add returns the host side holds no seed, a or prefix.
+ * cordahip_signer_remove and cordahip_shutdown zero the record on every device
+ * before they return (shutdown: before the table is freed). CORDAHIP_TRACE
+ * never prints key material. INTEGRATION.md (key custody) says what this does
+ * and does not protect against.
+ * Ordering: remove waits for every signing call already enqueued on the
+ * context's devices (caller streams included) before it zeroes the record, so
+ * such a call signs with the key or not at all; a signing call enqueued after
+ * remove returns answers CORDAHIP_SIGN_UNKNOWN_KEY for that id -- also after
+ * the slot has been given to a new key: an id is never reused (slot | reuse
+ * counter << 12, compared with the id stored in the record). remove of an id
+ * that is not live is CORDAHIP_ERR_INVALID_ARG.
+ *
+ * Per-lane statuses, by precedence:
+ *   CORDAHIP_SIGN_SKIPPED      gate[i] != 0 (the lane was not to be signed)
+ *   CORDAHIP_SIGN_UNKNOWN_KEY  key_id[i] names no live key (the KMS looks the key
+ *                              pair up before doSign, PersistentKeyManagementService.kt:87-89)
+ *   CORDAHIP_STATUS_EMPTY      an empty message ("Signing of an empty array is
+ *                              not permitted!", Crypto.kt:397)
+ *   CORDAHIP_STATUS_OK         sig[i*64 .. i*64+64) = R || S
+ * Every lane that is not OK gets 64 zero bytes; no secret is read for it.
+ *
+ * cordahip_sign / cordahip_sign_submit: host memory, messages CSR (checked as
+ * every CSR array of this header is: msg_off non-decreasing within msg_bytes,
+ * whole, before any enqueue; a single message of 2^32 bytes or more is refused
+ * the same way: CORDAHIP_ERR_INVALID_ARG, outputs untouched, context usable).
+ * Lanes are sharded over the context's devices (cordahip_shard_range, align 64)
+ * and stream in chunks of CORDAHIP_HOST_CHUNK lanes through page-locked staging;
+ * signature rows come back in lane order. */
+#define CORDAHIP_SIGN_UNKNOWN_KEY 14
+#define CORDAHIP_SIGN_SKIPPED 15
+int cordahip_signer_add_ed25519(cordahip_ctx* ctx, const uint8_t seed[32], uint32_t* key_id, uint8_t pub[32]);
+int cordahip_signer_remove(cordahip_ctx* ctx, uint32_t key_id);
+typedef struct {
+  uint64_t n;
+  const uint32_t* key_id;  /* [n] ids from cordahip_signer_add_ed25519 */
+  const uint8_t* msg;
+  const uint64_t* msg_off; /* [n+1] into msg */
+  const uint8_t* gate;     /* [n] nonzero: skip the lane; may be NULL */
+  uint8_t* sig;            /* [n*64] out: R || S, zero rows for lanes that are not OK */
+  uint8_t* status;         /* [n] out */
+  uint64_t msg_bytes;      /* bytes at msg; msg_off[n] <= msg_bytes */
+} cordahip_sign_batch;
+int cordahip_sign(cordahip_ctx* ctx, const cordahip_sign_batch* batch);
+int cordahip_sign_submit(cordahip_ctx* ctx, const cordahip_sign_batch* batch, uint64_t* ticket);
+/* Device-resident form: d_key_id uint32[n], d_msgs dense rows of msg_len bytes
+ * (16-byte aligned when msg_len == 32, the one-block shape), d_gate uint8[n] or
+ * NULL, d_sigs [n*64] (16-byte aligned), d_status [n], all in HBM on `device`,
+ * on hip_stream. d_gate is typically the tx_status an earlier call on the same
+ * stream wrote (cordahip_filtered_tx_verify's kernels, a *_device signed-tx
+ * call): "verify, then sign only what verified" without a host round trip.
+ * msg_len == 0 makes every ungated lane with a live key EMPTY. */
+int cordahip_ed25519_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
+                                       uint32_t msg_len, uint64_t n, const void* d_gate, void* d_sigs,
+                                       void* d_status, void* hip_stream);
+
 /* ECDSA keygen + sign (device memory), corpus generation: per lane scheme 2/3,
  * d = SHA-256(seed) mod n, k = SHA-256(seed || msg[:64]) mod n; writes the
  * uncompressed SEC1 key (65-byte slot, key_len = 65) and the DER signature

@@ -8,6 +8,9 @@
 //  c  after ~Device nothing is live and the account is zero (ASan: no leak either)
 //  d  the same for a half-initialised Device (hipMalloc failing midway, null events)
 //  e  two Devices charge the accounts of their own ids, whatever hipGetDevice says
+//  f  the signer's key table (SignKeys: not part of Device::visit, so the idle release
+//     is never offered it) is bound with the device, survives the idle release with its
+//     bytes still in the account, and is freed by ~Device
 // prints one JSON line; exit status 1 and a message on the first failed check
 #include <cstdio>
 #include <cstdlib>
@@ -170,6 +173,8 @@ int main() {
     TxSet ts;
     EcWork ew;
     RsaWork rw;
+    SignKeys sk;
+    visited(sk, 0, "SignKeys");
     visited(tw, 0, "TxWork");
     visited(ss, 0, "StreamStage");
     visited(ps, kPackPlain, "PackStage");
@@ -183,8 +188,9 @@ int main() {
   {
     // Device's plain members: ids, placement, pool, budget and workspace sizes, activity,
     // the mutexes and condition variable, turn counters, ring generations, set_busy,
-    // s_ec2 (an alias), the encoder's flags and counters
-    constexpr size_t kDeviceOwnPlain = 1288;
+    // s_ec2 (an alias), the encoder's flags and counters; the signer's two mutexes and its
+    // key table, which has a visit of its own (f)
+    constexpr size_t kDeviceOwnPlain = 1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys);
     const Count c = visited(*d, kDeviceOwnPlain + kTxSets * kTxSetPlain + kPackStages * kPackPlain, "Device");
     ndev = c.ndev, npin = c.npin, nev = c.nfence + c.nevent;
     CHECK(c.nstream == 7);
@@ -234,6 +240,26 @@ int main() {
     CHECK(mem_acct(3).in_use.load() == 1000 && mem_acct(5).in_use.load() == 17 && mem_acct(0).in_use.load() == 0);
   }
   CHECK(g.clean() && mem_acct(3).in_use.load() == 0 && mem_acct(5).in_use.load() == 0);
+  // f: the key table
+  {
+    auto* k = new Device;
+    k->bind(6);
+    CHECK(k->keys.tab.dev == 6);
+    Grow gk;
+    k->visit(gk);
+    const size_t before = g.dev.size();
+    k->visit_keys(gk);
+    CHECK(g.dev.size() == before + 1 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
+    void *tab = k->keys.tab.p, *stage = k->keys.stage.p;
+    k->release_idle();
+    CHECK(k->keys.tab.p == tab && k->keys.stage.p == stage && g.dev.count(tab) && g.pin.count(stage));
+    Kept kk;
+    k->visit(kk);  // what the release walks: the same kept buffers as in b
+    CHECK(kk.devs.size() == kept.devs.size());
+    CHECK(mem_acct(6).in_use.load() == kk.bytes + k->keys.tab.cap);
+    delete k;
+    CHECK(g.clean() && mem_acct(6).in_use.load() == 0);
+  }
   printf("{\"dev_bufs\": %zu, \"pin_bufs\": %zu, \"events\": %zu, \"streams\": 7, \"kept_dev_bufs\": %zu}\n", ndev, npin,
          nev, kept.devs.size());
   return 0;
