@@ -42,6 +42,8 @@ EXPORTS = [
     "cordahip_filtered_tx_build", "cordahip_filtered_tx_build_submit", "cordahip_filtered_tx_build_device",
     "cordahip_signer_add_ed25519", "cordahip_signer_remove", "cordahip_sign", "cordahip_sign_submit",
     "cordahip_ed25519_sign_keyed_device",
+    "cordahip_vkey_add_ed25519", "cordahip_vkey_remove", "cordahip_verify_keyed", "cordahip_verify_keyed_submit",
+    "cordahip_ed25519_verify_keyed_device",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
@@ -63,6 +65,10 @@ REQ_FULFILLED, REQ_MISSING, REQ_MISSING_ALLOWED, REQ_NOT_EVALUATED, REQ_MALFORME
 SIGN_UNKNOWN_KEY, SIGN_SKIPPED = 14, 15
 SIGNER_MAX_KEYS = 4096  # live keys per context (a full table: CORDAHIP_ERR_OUT_OF_MEMORY)
 ERR_INVALID_ARG, ERR_OUT_OF_MEMORY = -1, -4
+# keyed verification lanes (cordahip_verify_keyed): the lane's id names no live key; first in precedence
+VERIFY_UNKNOWN_KEY = 16
+VKEY_MAX_KEYS = 64  # live verification keys per context (a full registry: CORDAHIP_ERR_OUT_OF_MEMORY)
+VKEY_NO_ID = 0xFFFFFFFF  # the id cordahip_vkey_add_ed25519 reports for bytes that are not a key
 
 
 class EngineUnavailable(RuntimeError):
@@ -168,6 +174,18 @@ class SignBatch(ctypes.Structure):
         ("gate", ctypes.c_void_p),
         ("sig", ctypes.c_void_p), ("status", ctypes.c_void_p),
         ("msg_bytes", ctypes.c_uint64),
+    ]
+
+
+class KeyedSigBatch(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("key_id", ctypes.c_void_p),
+        ("sig", ctypes.c_void_p), ("sig_off", ctypes.c_void_p),
+        ("msg", ctypes.c_void_p), ("msg_off", ctypes.c_void_p),
+        ("status", ctypes.c_void_p), ("verdict", ctypes.c_void_p),
+        ("flags", ctypes.c_uint32),
+        ("sig_bytes", ctypes.c_uint64), ("msg_bytes", ctypes.c_uint64),
     ]
 
 
@@ -292,6 +310,11 @@ def lib() -> ctypes.CDLL:
         "cordahip_sign": (i32, [vp, ctypes.POINTER(SignBatch)]),
         "cordahip_sign_submit": (i32, [vp, ctypes.POINTER(SignBatch), ctypes.POINTER(u64)]),
         "cordahip_ed25519_sign_keyed_device": (i32, [vp, i32, vp, vp, u32, u64, vp, vp, vp, vp]),
+        "cordahip_vkey_add_ed25519": (i32, [vp, vp, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint8)]),
+        "cordahip_vkey_remove": (i32, [vp, u32]),
+        "cordahip_verify_keyed": (i32, [vp, ctypes.POINTER(KeyedSigBatch)]),
+        "cordahip_verify_keyed_submit": (i32, [vp, ctypes.POINTER(KeyedSigBatch), ctypes.POINTER(u64)]),
+        "cordahip_ed25519_verify_keyed_device": (i32, [vp, i32, vp, vp, vp, u32, u64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(l, name)

@@ -27,6 +27,7 @@
 #include "csr_check.hpp"
 #include "der.hpp"
 #include "ed25519_comb.hpp"
+#include "ed25519_vkey.hpp"
 #include "kryo_core.hpp"
 #include "pack_rows.hpp"
 #include "runtime.hpp"
@@ -1455,6 +1456,204 @@ int sign_impl(cordahip_ctx* ctx, const cordahip_sign_batch* b) {
   return for_shards(ctx->devs, n, 64, [&](Device& d, uint64_t lo, uint64_t hi) { return sign_shard(ctx, d, b, lo, hi); });
 }
 
+// ---- Ed25519 verification against registered keys (K12, ed25519_vkey.hip) --------
+// A key's record cleared on one device (vkey_mu held, device current): after every
+// keyed kernel that may still read it; the stream is drained before return. The
+// table's entries stay: without a record whose id matches, no lane reads them.
+hipError_t vkey_clear_record(Device& d, uint32_t slot) {
+  if (!d.vkeys.tab.p) return hipSuccess;
+  hipError_t e = d.vkeys.ev.sync();
+  e = e ? e
+        : hipMemsetAsync(d.vkeys.tab.as<uint32_t>() + kVkeyRecBase + (size_t)slot * kVkeyRecWords, 0,
+                         kVkeyRecWords * 4, d.stream);
+  const hipError_t f = hipStreamSynchronize(d.stream);
+  return e ? e : f;
+}
+
+// The key's record and table built in key_id's slot on one device (vkey_mu held);
+// *decoded: whether the device took the bytes for a point.
+int vkey_build_on(Device& d, const uint8_t key[32], uint32_t key_id, bool* decoded) {
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  if (!d.vkeys.tab.p) {  // the first key of this device: the tables; the records zeroed, the table of B built
+    if (d.vkeys.tab.ensure(ed25519_vkey_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+    if (hipMemsetAsync(d.vkeys.tab.as<uint32_t>() + kVkeyRecBase, 0, (kVkeyAllWords - kVkeyRecBase) * 4, d.stream) !=
+            hipSuccess ||
+        launch_ed25519_vkey_base(d.vkeys.tab.as<uint32_t>(), d.stream) != hipSuccess)
+      return CORDAHIP_ERR_HIP;
+  }
+  if (d.vkeys.stage.ensure(64) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  uint8_t* stage = d.vkeys.stage.as<uint8_t>();
+  uint32_t* tab = d.vkeys.tab.as<uint32_t>();
+  std::memcpy(stage, key, 32);
+  std::memset(stage + 32, 0, 32);
+  hipError_t e = d.vkeys.ev.sync();  // a removed key's slot: no kernel still reads its table
+  e = e ? e : hipMemcpyAsync(tab + kVkeyKeyWord, stage, 32, hipMemcpyHostToDevice, d.stream);
+  e = e ? e : launch_ed25519_vkey_build(tab, key_id, d.stream);
+  e = e ? e : hipMemcpyAsync(stage + 32, tab + kVkeyOkWord, 32, hipMemcpyDeviceToHost, d.stream);
+  const hipError_t f = hipStreamSynchronize(d.stream);
+  if (e == hipSuccess && f == hipSuccess) {
+    uint32_t flag;
+    std::memcpy(&flag, stage + 32, 4);
+    *decoded = flag == 1u;
+  }
+  return hip_err(e ? e : f);
+}
+
+int vkey_add_impl(cordahip_ctx* ctx, const uint8_t key[32], uint32_t* key_id, uint8_t* key_status) {
+  std::lock_guard<std::mutex> g(ctx->vkey_mu);
+  if (ctx->vkey_gen.empty()) {
+    ctx->vkey_gen.assign(kVkeySlots, 0);
+    ctx->vkey_live.assign(kVkeySlots, 0);
+  }
+  if (ctx->vkey_count >= kVkeySlots) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  uint32_t slot = 0;
+  while (ctx->vkey_live[slot]) slot++;
+  const uint32_t gen = vkey_next_gen(ctx->vkey_gen[slot]);
+  const uint32_t id = vkey_make_id(slot, gen);
+  ctx->vkey_gen[slot] = gen;  // consumed even if the add fails
+  int rc = CORDAHIP_SUCCESS;
+  size_t done = 0;
+  bool first = false, cur = false;
+  for (; done < ctx->devs.size() && rc == CORDAHIP_SUCCESS; done++) {
+    Device& d = *ctx->devs[done];
+    std::lock_guard<std::mutex> gd(d.vkey_mu);
+    const Activity act(d);
+    rc = vkey_build_on(d, key, id, done ? &cur : &first);
+    if (rc == CORDAHIP_SUCCESS && done && cur != first) rc = CORDAHIP_ERR_HIP;
+    if (rc == CORDAHIP_SUCCESS && !first) break;  // not a point: no device wrote anything
+  }
+  if (rc != CORDAHIP_SUCCESS) {  // no device keeps a record of a key the caller never got
+    for (size_t k = 0; k < done; k++) {
+      Device& d = *ctx->devs[k];
+      std::lock_guard<std::mutex> gd(d.vkey_mu);
+      if (hipSetDevice(d.id) == hipSuccess) (void)vkey_clear_record(d, slot);
+    }
+    return rc;
+  }
+  if (!first) {
+    *key_id = kVkeyNoId;
+    *key_status = CORDAHIP_STATUS_BAD_KEY;
+    return CORDAHIP_SUCCESS;
+  }
+  ctx->vkey_live[slot] = 1;
+  ctx->vkey_count++;
+  *key_id = id;
+  *key_status = CORDAHIP_STATUS_OK;
+  if (tracing()) fprintf(stderr, "[cordahip] vkey: key id %u added (%u live)\n", id, ctx->vkey_count);
+  return CORDAHIP_SUCCESS;
+}
+
+int vkey_remove_impl(cordahip_ctx* ctx, uint32_t key_id) {
+  std::lock_guard<std::mutex> g(ctx->vkey_mu);
+  const uint32_t slot = vkey_slot(key_id);
+  if (ctx->vkey_gen.empty() || !ctx->vkey_live[slot] || vkey_make_id(slot, ctx->vkey_gen[slot]) != key_id)
+    return CORDAHIP_ERR_INVALID_ARG;
+  ctx->vkey_live[slot] = 0;  // the id is dead from here on, whatever a device answers below
+  ctx->vkey_count--;
+  hipError_t e = hipSuccess;
+  for (auto& dp : ctx->devs) {
+    Device& d = *dp;
+    std::lock_guard<std::mutex> gd(d.vkey_mu);
+    const Activity act(d);
+    const hipError_t s = hipSetDevice(d.id);
+    const hipError_t z = s ? s : vkey_clear_record(d, slot);
+    e = e ? e : z;
+  }
+  if (tracing()) fprintf(stderr, "[cordahip] vkey: key id %u removed (%u live)\n", key_id, ctx->vkey_count);
+  return hip_err(e);
+}
+
+// The keyed verifier on stream s (vkey_mu held, device current): behind the tables'
+// previous user, followed by the tables' fence. A device without key tables yet
+// passes none: every lane is then UNKNOWN_KEY.
+hipError_t vkey_enqueue(Device& d, const uint32_t* key_id, const uint8_t* sigs, const uint8_t* msgs,
+                        const uint64_t* moff, const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* pre,
+                        uint32_t flags, uint8_t* status, unsigned long long* verdict, hipStream_t s) {
+  hipError_t e = d.vkeys.ev.wait(s);
+  e = e ? e
+        : launch_ed25519_verify_keyed(key_id, sigs, msgs, moff, mlen, msg_len, n, pre, flags,
+                                      d.vkeys.tab.as<uint32_t>(), status, verdict, s);
+  return e ? e : d.vkeys.ev.record(s);
+}
+
+// cordahip_verify_keyed for lanes [lo, hi) on one device (lo a multiple of 64), a chunk
+// of CORDAHIP_HOST_CHUNK lanes at a time: the lanes packed into the device's page-locked
+// stage (pack_rows.hpp keyed_pack_rows), across PCIe, K12, and the statuses and verdict
+// words back into the caller's arrays.
+int verify_keyed_shard(cordahip_ctx* ctx, Device& d, const cordahip_keyed_sig_batch* b, uint64_t lo, uint64_t hi) {
+  std::lock_guard<std::mutex> g(d.vkey_host_mu);
+  const NodeBind nb(d);
+  const Activity act(d);
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  const uint64_t chunk = (env_lanes("CORDAHIP_HOST_CHUNK", 1ull << 22) + 63) / 64 * 64;  // whole verdict words
+  HostPool& pool = pool_of(ctx, d);
+  hipStream_t s = d.stream;
+  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
+  std::vector<uint64_t> poff;
+  for (uint64_t a = lo; a < hi; a += chunk) {
+    const uint64_t m = std::min(chunk, hi - a);
+    const uint64_t words = (m + 63) / 64;
+    const double t0 = now_ms();
+    poff.resize(m);
+    const SignLayout lay = msg_chunk_layout(b->msg_off, a, m, poff.data());
+    const bool dense = lay.dense;
+    const uint64_t bytes = lay.bytes;
+    const size_t need[8] = {(size_t)m * 4, (size_t)m * 64, (size_t)m, (size_t)std::max<uint64_t>(bytes, 16),
+                            (size_t)m * 8, (size_t)m * 4,  (size_t)m, (size_t)words * 8};
+    for (int k = 0; k < 8; k++)  // the previous chunk has drained: growing frees nothing in use
+      if (d.vkey_h[k].ensure(need[k]) != hipSuccess || d.vkey_d[k].ensure(need[k]) != hipSuccess)
+        return CORDAHIP_ERR_OUT_OF_MEMORY;
+    uint8_t* hm = d.vkey_h[3].as<uint8_t>();
+    uint64_t* ho = d.vkey_h[4].as<uint64_t>();
+    uint32_t* hl = d.vkey_h[5].as<uint32_t>();
+    pool.parallel_for(m, 1u << 14, [&](uint64_t x, uint64_t y) {
+      keyed_pack_rows(b, a, x, y, lay, poff.data(), d.vkey_h[0].as<uint32_t>(), d.vkey_h[1].as<uint8_t>(),
+                      d.vkey_h[2].as<uint8_t>(), hm, ho, hl);
+    });
+    hipError_t e = hipMemcpyAsync(d.vkey_d[0].p, d.vkey_h[0].p, m * 4, h2d, s);
+    e = e ? e : hipMemcpyAsync(d.vkey_d[1].p, d.vkey_h[1].p, m * 64, h2d, s);
+    e = e ? e : hipMemcpyAsync(d.vkey_d[2].p, d.vkey_h[2].p, m, h2d, s);
+    if (bytes) e = e ? e : hipMemcpyAsync(d.vkey_d[3].p, hm, bytes, h2d, s);
+    if (!dense) {
+      e = e ? e : hipMemcpyAsync(d.vkey_d[4].p, ho, m * 8, h2d, s);
+      e = e ? e : hipMemcpyAsync(d.vkey_d[5].p, hl, m * 4, h2d, s);
+    }
+    if (e == hipSuccess) {
+      std::lock_guard<std::mutex> gs(d.vkey_mu);
+      e = vkey_enqueue(d, d.vkey_d[0].as<uint32_t>(), d.vkey_d[1].as<uint8_t>(), d.vkey_d[3].as<uint8_t>(),
+                       dense ? nullptr : d.vkey_d[4].as<uint64_t>(), dense ? nullptr : d.vkey_d[5].as<uint32_t>(), 32, m,
+                       d.vkey_d[2].as<uint8_t>(), b->flags, d.vkey_d[6].as<uint8_t>(),
+                       d.vkey_d[7].as<unsigned long long>(), s);
+    }
+    e = e ? e : hipMemcpyAsync(d.vkey_h[6].p, d.vkey_d[6].p, m, d2h, s);
+    e = e ? e : hipMemcpyAsync(d.vkey_h[7].p, d.vkey_d[7].p, words * 8, d2h, s);
+    e = e ? e : d.vkey_host_ev.record(s);
+    e = e ? e : d.vkey_host_ev.sync();
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(s);  // no queued work outlives the call
+      return CORDAHIP_ERR_HIP;
+    }
+    std::memcpy(b->status + a, d.vkey_h[6].p, m);
+    if (b->verdict) std::memcpy(b->verdict + a / 64, d.vkey_h[7].p, words * 8);
+    if (tracing())
+      fprintf(stderr, "[cordahip] dev %d keyed verify chunk: %llu lanes (%s messages) in %.2f ms\n", d.id,
+              (unsigned long long)m, dense ? "32-byte" : "CSR", now_ms() - t0);
+  }
+  return CORDAHIP_SUCCESS;
+}
+
+int verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) {
+  const uint64_t n = b->n;
+  if (n == 0) return CORDAHIP_SUCCESS;
+  if (!b->key_id || !b->sig_off || !b->msg_off || !b->status) return CORDAHIP_ERR_INVALID_ARG;
+  if (b->flags & ~CORDAHIP_FLAG_IS_VALID) return CORDAHIP_ERR_INVALID_ARG;
+  if (!check_keyed_sig_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
+  if ((b->msg_off[0] != b->msg_off[n] && !b->msg) || (b->sig_off[0] != b->sig_off[n] && !b->sig))
+    return CORDAHIP_ERR_INVALID_ARG;
+  return for_shards(ctx->devs, n, 64,
+                    [&](Device& d, uint64_t lo, uint64_t hi) { return verify_keyed_shard(ctx, d, b, lo, hi); });
+}
+
 Device* dev_at(cordahip_ctx* ctx, int device) {
   if (!ctx || device < 0 || device >= (int)ctx->devs.size()) return nullptr;
   return ctx->devs[device].get();
@@ -1839,6 +2038,43 @@ int cordahip_ed25519_sign_keyed_device(cordahip_ctx* ctx, int device, const void
       return sign_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_msgs), nullptr,
                           nullptr, msg_len, n, static_cast<const uint8_t*>(d_gate), static_cast<uint8_t*>(d_sigs),
                           static_cast<uint8_t*>(d_status), s);
+    });
+  });
+}
+
+int cordahip_vkey_add_ed25519(cordahip_ctx* ctx, const uint8_t key[32], uint32_t* key_id, uint8_t* key_status) {
+  if (!ctx || !key || !key_id || !key_status) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return vkey_add_impl(ctx, key, key_id, key_status); });
+}
+
+int cordahip_vkey_remove(cordahip_ctx* ctx, uint32_t key_id) {
+  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return vkey_remove_impl(ctx, key_id); });
+}
+
+int cordahip_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch) {
+  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return verify_keyed_impl(ctx, batch); });
+}
+
+int cordahip_verify_keyed_submit(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch, uint64_t* ticket) {
+  return submit(ctx, ticket, verify_keyed_impl, batch);
+}
+
+int cordahip_ed25519_verify_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_sigs,
+                                         const void* d_msgs, uint32_t msg_len, uint64_t n, void* d_status,
+                                         void* d_verdict, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || (n && (!d_key_id || !d_sigs || !d_status || (msg_len && !d_msgs)))) return CORDAHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_sigs) & 15) || (reinterpret_cast<uintptr_t>(d_key_id) & 3) ||
+      (reinterpret_cast<uintptr_t>(d_verdict) & 7) || (msg_len == 32 && (reinterpret_cast<uintptr_t>(d_msgs) & 15)))
+    return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    std::lock_guard<std::mutex> g(d->vkey_mu);
+    return device_call(*d, hip_stream, [&](hipStream_t s) {
+      return vkey_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_sigs),
+                          static_cast<const uint8_t*>(d_msgs), nullptr, nullptr, msg_len, n, nullptr, 0u,
+                          static_cast<uint8_t*>(d_status), static_cast<unsigned long long*>(d_verdict), s);
     });
   });
 }

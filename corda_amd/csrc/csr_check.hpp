@@ -124,6 +124,25 @@ bool check_sign_batch(Par&& par, const cordahip_sign_batch* b) {
   return ok.load();
 }
 
+// a keyed verification batch: sig_off[0..n] and msg_off[0..n] non-decreasing and
+// within sig_bytes / msg_bytes, and no single message of 2^32 bytes or more (the
+// kernel's message lengths are 32-bit; a signature of any length is a status)
+template <class Par>
+bool check_keyed_sig_batch(Par&& par, const cordahip_keyed_sig_batch* b) {
+  if (b->n == 0) return true;
+  if (!b->sig_off || !csr_ok(par, b->sig_off, 0, b->n, b->sig_bytes)) return false;
+  if (!b->msg_off || !csr_ok(par, b->msg_off, 0, b->n, b->msg_bytes)) return false;
+  std::atomic<bool> ok{true};
+  par(b->n, 1u << 16, [&](uint64_t x, uint64_t y) {
+    for (uint64_t i = x; i < y; i++)
+      if (b->msg_off[i + 1] - b->msg_off[i] > 0xffffffffull) {
+        ok.store(false, std::memory_order_relaxed);
+        return;
+      }
+  });
+  return ok.load();
+}
+
 // a cover (required-signer coverage): tx_req_off[0..ntx] non-decreasing and
 // within nreq, req_tok_off over the required keys it spans within ntok, the
 // whole key table's ckey_off[0..nckey] within ckey_bytes (any leaf may name any

@@ -29,22 +29,6 @@ __device__ __attribute__((aligned(64))) const uint32_t kIdentityCached[kWhEntryW
                                                             1, 0, 0, 0, 0, 0, 0, 0, 0, 0,   // Z
                                                             0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // 2dT
 
-// booth_digit (sc25519.hpp) over a scalar stored word-major in LDS: word w of
-// this thread's scalar at col[w * 256]
-template <int W>
-CDEV int booth_digit_col(const uint32_t* col, int j) {
-  const int lo = W * j - 1;  // may be -1
-  uint32_t v;
-  if (lo < 0) {
-    v = (col[0] << 1) & ((1u << (W + 1)) - 1);
-  } else {
-    const int w = lo >> 5, sh = lo & 31;
-    const uint64_t hi = w + 1 <= 7 ? col[(w + 1) * 256] : 0u;
-    v = (uint32_t)(((hi << 32) | col[w * 256]) >> sh) & ((1u << (W + 1)) - 1);
-  }
-  return (int)((v + 1) >> 1) - (int)((v >> W) << W);
-}
-
 // waves per SIMD the register allocation targets (2: up to 256 VGPRs)
 #ifndef ED_LADDER_WAVES
 #define ED_LADDER_WAVES 2

@@ -166,16 +166,20 @@ struct SignLayout {
   uint64_t bytes;  // message bytes of the stage
 };
 // poff[m]: the lanes' offsets in the stage (written only for a chunk that is not dense)
-inline SignLayout sign_chunk_layout(const cordahip_sign_batch* b, uint64_t a, uint64_t m, uint64_t* poff) {
+// msg_off: the batch's message offsets (cordahip_verify_keyed chunks share the layout)
+inline SignLayout msg_chunk_layout(const uint64_t* msg_off, uint64_t a, uint64_t m, uint64_t* poff) {
   SignLayout l{true, m * 32};
-  for (uint64_t i = 0; i < m && l.dense; i++) l.dense = b->msg_off[a + i + 1] - b->msg_off[a + i] == 32;
+  for (uint64_t i = 0; i < m && l.dense; i++) l.dense = msg_off[a + i + 1] - msg_off[a + i] == 32;
   if (l.dense) return l;
   l.bytes = 0;
   for (uint64_t i = 0; i < m; i++) {
     poff[i] = l.bytes;
-    l.bytes += (b->msg_off[a + i + 1] - b->msg_off[a + i] + 15) / 16 * 16;
+    l.bytes += (msg_off[a + i + 1] - msg_off[a + i] + 15) / 16 * 16;
   }
   return l;
+}
+inline SignLayout sign_chunk_layout(const cordahip_sign_batch* b, uint64_t a, uint64_t m, uint64_t* poff) {
+  return msg_chunk_layout(b->msg_off, a, m, poff);
 }
 // rows [x, y) of the chunk at lane a: key ids, gate bytes (b->gate != NULL), messages, and
 // -- not dense -- offsets and lengths
@@ -186,6 +190,33 @@ inline void sign_pack_rows(const cordahip_sign_batch* b, uint64_t a, uint64_t x,
     const uint64_t o = b->msg_off[a + i], len = b->msg_off[a + i + 1] - o, p = l.dense ? i * 32 : poff[i];
     hid[i] = b->key_id[a + i];
     if (b->gate) hgate[i] = b->gate[a + i];
+    if (len) std::memcpy(hm + p, b->msg + o, len);
+    if (!l.dense) {
+      ho[i] = p;
+      hl[i] = (uint32_t)len;
+    }
+  }
+}
+
+// ---- cordahip_verify_keyed chunks (a batch that passed check_keyed_sig_batch) ----
+// Messages as in a signing chunk (msg_chunk_layout). Rows [x, y) of the chunk at lane
+// a: key ids, the 64-byte signature rows with the statuses the host decides as in
+// pack_ed_row -- the Crypto.doVerify require()s, then the engine's length check; such
+// a lane gets a zero row -- messages, and -- not dense -- offsets and lengths
+inline void keyed_pack_rows(const cordahip_keyed_sig_batch* b, uint64_t a, uint64_t x, uint64_t y, const SignLayout& l,
+                            const uint64_t* poff, uint32_t* hid, uint8_t* hsig, uint8_t* hpre, uint8_t* hm,
+                            uint64_t* ho, uint32_t* hl) {
+  const bool do_verify = !(b->flags & CORDAHIP_FLAG_IS_VALID);
+  for (uint64_t i = x; i < y; i++) {
+    const uint64_t o = b->msg_off[a + i], len = b->msg_off[a + i + 1] - o, p = l.dense ? i * 32 : poff[i];
+    const uint64_t so = b->sig_off[a + i], sl = b->sig_off[a + i + 1] - so;
+    hid[i] = b->key_id[a + i];
+    uint8_t st = CORDAHIP_STATUS_OK;
+    if (do_verify && (sl == 0 || len == 0)) st = CORDAHIP_STATUS_EMPTY;  // Crypto.kt:475-476
+    else if (sl != 64) st = CORDAHIP_STATUS_MALFORMED_SIG;               // EdDSAEngine: signature length
+    if (st == CORDAHIP_STATUS_OK) std::memcpy(hsig + i * 64, b->sig + so, 64);
+    else std::memset(hsig + i * 64, 0, 64);
+    hpre[i] = st;
     if (len) std::memcpy(hm + p, b->msg + o, len);
     if (!l.dense) {
       ho[i] = p;

@@ -385,7 +385,7 @@ void device_budget(Device& d) {  // device current
 void trim_device(Device& d) {
   SetLease l0(d, 0, true), l1(d, 1, true);
   std::lock_guard<std::mutex> gk(d.kryo_mu), gs(d.stream_mu), gp(d.ped_mu), ge0(d.ed_mu[0]), ge1(d.ed_mu[1]),
-      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu), gv(d.cover_mu), gh(d.sign_host_mu);
+      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu), gv(d.cover_mu), gh(d.sign_host_mu), gvh(d.vkey_host_mu);
   if (hipSetDevice(d.id) != hipSuccess) return;
   d.release_idle();
   if (tracing()) fprintf(stderr, "[cordahip] dev %d: idle buffers released\n", d.id);

@@ -47,6 +47,18 @@ hipError_t launch_ed25519_sign_keyed(const uint32_t* key_id, const uint8_t* msgs
                                      const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* gate,
                                      const uint32_t* keytab, const uint32_t* comb, uint8_t* sigs, uint8_t* status,
                                      hipStream_t s);
+// ed25519_vkey.hip (K12): a verification key's record and window table built in the
+// device's key table (the 32 key bytes are in the table's scratch words, the decode
+// verdict comes back there: ed25519_vkey.hpp kVkeyKeyWord / kVkeyOkWord) and the keyed
+// verifier (moff / mlen non-null: per-lane message offsets and lengths, else dense
+// rows; pre: optional per-lane statuses decided by the host; flags: CORDAHIP_FLAG_IS_VALID)
+size_t ed25519_vkey_bytes();
+hipError_t launch_ed25519_vkey_build(uint32_t* vtab, uint32_t key_id, hipStream_t s);
+hipError_t launch_ed25519_vkey_base(uint32_t* vtab, hipStream_t s);  // the table of B, once per device
+hipError_t launch_ed25519_verify_keyed(const uint32_t* key_id, const uint8_t* sigs, const uint8_t* msgs,
+                                       const uint64_t* moff, const uint32_t* mlen, uint32_t msg_len, uint64_t n,
+                                       const uint8_t* pre, uint32_t flags, const uint32_t* vtab, uint8_t* status,
+                                       unsigned long long* verdict, hipStream_t s);
 hipError_t launch_sha256_leaves(const uint8_t* bytes, const uint64_t* off, uint64_t nleaves, uint32_t* hashes,
                                 hipStream_t s);
 hipError_t launch_merkle_root(uint32_t* hashes, const uint64_t* tx_leaf_off, uint64_t ntx, uint8_t* txid,
@@ -415,6 +427,26 @@ struct SignKeys {
   }
 };
 
+// The Ed25519 verification-key table of one device (ed25519_vkey.hpp: 64 window tables
+// of 512 KiB and the base point's, their records and the build kernel's scratch). Public keys, but handled
+// like the signer's table: allocated (zeroed) by the context's first
+// cordahip_vkey_add_ed25519, counted in the device's account, and then kept until
+// ~Device -- the idle release and cordahip_trim never see it (Device::visit_keys), so a
+// verifier cannot lose its registered keys to an idle timer. ev: the fence of the
+// kernels that read the table. stage: 64 page-locked bytes the key bytes go out and the
+// decode verdict comes back in.
+struct VerifyKeys {
+  DevBuf tab;
+  PinBuf stage;
+  Fence ev;
+  template <class V>
+  void visit(V& v) {
+    v.dev(tab, kKept);
+    v.pin(stage, kKept);
+    v.fence(ev);
+  }
+};
+
 // Fork-join pool for host-side packing and scattering. parallel_for splits
 // [0, n) into pieces of at least `grain` lanes; the caller runs pieces too,
 // so concurrent callers (one pipeline per device and section) all progress.
@@ -566,10 +598,29 @@ struct Device {
   DevBuf sign_d[7];
   Fence sign_host_ev;
 
-  // everything but `keys`, which the idle release is never offered (visit_keys)
+  // Ed25519 verification against registered keys (K12). vkeys: the key tables
+  // (VerifyKeys). vkey_mu orders every user of them exactly as sign_mu orders the
+  // signer's: a keyed verification holds it while it enqueues -- its stream waits for
+  // vkeys.ev, its kernel is followed by vkeys.ev -- and add / remove hold it for their
+  // whole run; remove waits for vkeys.ev first.
+  VerifyKeys vkeys;
+  std::mutex vkey_mu;
+  // cordahip_verify_keyed's chunk stage: h/d[0] key ids, [1] signature rows, [2] host
+  // pre-statuses, [3] messages, [4] their offsets, [5] their lengths, [6] statuses, [7]
+  // verdict words. vkey_host_mu is held for a shard's run; vkey_host_ev follows a
+  // chunk's last copy.
+  std::mutex vkey_host_mu;
+  PinBuf vkey_h[8];
+  DevBuf vkey_d[8];
+  Fence vkey_host_ev;
+
+  // everything but `keys` and `vkeys`, which the idle release is never offered (visit_keys)
   template <class V>
   void visit(V& v) {
     for (DevBuf* b : {&btab, &gtab_k1, &gtab_r1}) v.dev(*b, kKept);
+    for (PinBuf& b : vkey_h) v.pin(b, kFreed);
+    for (DevBuf& b : vkey_d) v.dev(b, kFreed);
+    v.fence(vkey_host_ev);
     for (PinBuf& b : sign_h) v.pin(b, kFreed);
     for (DevBuf& b : sign_d) v.dev(b, kFreed);
     v.fence(sign_host_ev);
@@ -600,11 +651,12 @@ struct Device {
     visit(v);
     visit_keys(v);
   }
-  // the signer's key table: bound and destroyed with the rest, never released while
-  // the context lives
+  // the signer's key table and the verification keys' tables: bound and destroyed with
+  // the rest, never released while the context lives
   template <class V>
   void visit_keys(V& v) {
     keys.visit(v);
+    vkeys.visit(v);
   }
   struct Release : Visitor {  // the buffers; all: the kept ones too
     bool all = false;
@@ -860,6 +912,13 @@ struct cordahip_ctx {
   std::vector<uint32_t> signer_gen;
   std::vector<uint8_t> signer_live;
   uint32_t signer_count = 0;
+  // the verification-key registry (cordahip_vkey_add_ed25519 / _remove): which slots
+  // are live and each slot's reuse counter (empty until the first add). vkey_mu is held
+  // for an add's or a remove's whole run. Ids are a namespace of their own.
+  std::mutex vkey_mu;
+  std::vector<uint32_t> vkey_gen;
+  std::vector<uint8_t> vkey_live;
+  uint32_t vkey_count = 0;
   std::thread reaper;
   std::mutex reaper_mu;
   std::condition_variable reaper_cv;

@@ -10,11 +10,17 @@
 //     so the kernel is free to use a different (fixed-window, SIMD-uniform)
 //     recoding of S_eff mod L for the actual multiplication.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// device code under hipcc; plain inline functions for a host compiler
+// (tools/ed_vkey_check.cpp reduces its scalars with sc_reduce512)
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #ifndef CDEV
 #define CDEV __device__ __forceinline__
+#endif
+#elif !defined(CDEV)
+#define CDEV inline
 #endif
 
 namespace cordahip {

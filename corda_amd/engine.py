@@ -157,6 +157,56 @@ class Engine:
             gate.data_ptr() if gate is not None else None, sigs.data_ptr(), status.data_ptr(), s),
             "cordahip_ed25519_sign_keyed_device")
 
+    # ---- Ed25519 verification against registered keys (Crypto.doVerify / isValid per lane) ----
+    def vkey_add_ed25519(self, key: bytes):
+        """cordahip_vkey_add_ed25519: the 32 key bytes decoded and their window table built on every
+        device of the context. Returns (key_id, key_status): (id, OK), or (VKEY_NO_ID, BAD_KEY) for bytes
+        that are not a key (no slot taken). Ids are not the signer's ids."""
+        assert len(key) == 32
+        kid, st = ctypes.c_uint32(), ctypes.c_uint8()
+        check(lib().cordahip_vkey_add_ed25519(self._ctx, bytes(key), ctypes.byref(kid), ctypes.byref(st)),
+              "cordahip_vkey_add_ed25519")
+        return kid.value, st.value
+
+    def vkey_remove(self, key_id: int):
+        """cordahip_vkey_remove: waits for the keyed calls in flight, clears the key's record on every
+        device; the id answers VERIFY_UNKNOWN_KEY from then on."""
+        check(lib().cordahip_vkey_remove(self._ctx, key_id), "cordahip_vkey_remove")
+
+    def verify_keyed_batch(self, key_ids: Sequence[int], sigs: Sequence[bytes], msgs: Sequence[bytes],
+                           is_valid: bool = False, async_: bool = False):
+        """cordahip_verify_keyed / cordahip_verify_keyed_submit: lane i checks sigs[i] over msgs[i] against
+        the registered key key_ids[i]. Returns (status[n], verdict) -- or, async_, a Ticket whose wait()
+        returns them. is_valid as in verify_batch."""
+        n = len(sigs)
+        assert len(key_ids) == n and len(msgs) == n
+        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
+        sb, so = self._csr(list(sigs))
+        mb, mo = self._csr(list(msgs))
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        verdict = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
+        b = _lib.KeyedSigBatch(n, _ptr(ids), _ptr(sb), _ptr(so), _ptr(mb), _ptr(mo), _ptr(status), _ptr(verdict),
+                               _lib.FLAG_IS_VALID if is_valid else 0, sb.size if n and so[n] else 0,
+                               mb.size if n and mo[n] else 0)
+        keep = (ids, sb, so, mb, mo, status, verdict, b)
+        if async_:
+            t = ctypes.c_uint64()
+            check(lib().cordahip_verify_keyed_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)),
+                  "cordahip_verify_keyed_submit")
+            return Ticket(self, t.value, lambda: (status[:n], verdict), keep)
+        check(lib().cordahip_verify_keyed(self._ctx, ctypes.byref(b)), "cordahip_verify_keyed")
+        return status[:n], verdict
+
+    def ed25519_verify_keyed_device(self, key_ids, sigs, msgs, status, verdict=None, device: int = 0, stream=None):
+        """cordahip_ed25519_verify_keyed_device over device tensors: key_ids int32 [n], sigs uint8 [n, 64],
+        msgs uint8 [n, L]; outputs status uint8 [n] and verdict int64 [(n + 63) // 64] or None."""
+        n = key_ids.shape[0]
+        s = stream.cuda_stream if stream is not None else 0
+        check(lib().cordahip_ed25519_verify_keyed_device(
+            self._ctx, device, key_ids.data_ptr(), sigs.data_ptr(), msgs.data_ptr() if msgs.shape[1] else None,
+            msgs.shape[1], n, status.data_ptr(), verdict.data_ptr() if verdict is not None else None, s),
+            "cordahip_ed25519_verify_keyed_device")
+
     def ecdsa_sign_device(self, scheme, seeds, msgs, keys, key_len, sigs, sig_len, device: int = 0, stream=None):
         """Device tensors: scheme[n] u8 (2/3), seeds[n,32], msgs[n,L] -> keys[n,65], key_len[n], sigs[n,72], sig_len[n]."""
         n = seeds.shape[0]

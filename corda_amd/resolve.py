@@ -34,6 +34,7 @@ TX_SIGNATURES_MISSING, TX_BAD_COVER = 10, 11  # required-signer coverage (cordah
 REQ_MISSING = 1
 TX_HASHES_NOT_IN_TREE = 12  # FilteredTransaction build: the count rule (PartialMerkleTree.kt:75-76)
 _SIGN_UNKNOWN_KEY = 14  # cordahip_sign: the lane's key id names no live key
+_VERIFY_UNKNOWN_KEY = 16  # cordahip_verify_keyed: the lane's key id names no live verification key
 
 
 class SignatureException(Exception):
@@ -258,6 +259,33 @@ def verify_and_sign_filtered_transactions(engine, ftxs, key_id: int):
             raise NoSuchElementException("no registered key %d" % key_id)
         out.append(bytes(sigs[t]) if int(sst[t]) == OK else None)
     return [int(x) for x in status], out
+
+
+def validate_notary_signatures(engine, key_id: int, ids: Sequence[bytes], sigs: Sequence[bytes]):
+    """What a notary client does with the notary's answers (NotaryFlow.Client.call,
+    NotaryFlow.kt:75-83: `check(sig.by in notaryParty.owningKey.keys); sig.verify(stx.id.bytes)`)
+    for a batch of transactions notarised by one key: one Engine.verify_keyed_batch of sigs[t]
+    over ids[t] against the verification key registered as `key_id` (the caller registered the
+    notary identity's key, engine.vkey_add_ed25519, and sends here the signatures whose `by` is
+    that key -- the membership check is a comparison of key bytes it has already made).
+
+    Returns one outcome per lane: None where the signature verifies, else the exception
+    sig.verify throws (_lane_exception's mapping); an id that names no live key is a
+    NoSuchElementException, as for the signer's registry."""
+    if not ids:
+        return []
+    assert len(ids) == len(sigs)
+    status, _ = engine.verify_keyed_batch([key_id] * len(ids), [bytes(s) for s in sigs], [bytes(i) for i in ids])
+    out = []
+    for st in status:
+        st = int(st)
+        if st == OK:
+            out.append(None)
+        elif st == _VERIFY_UNKNOWN_KEY:
+            out.append(NoSuchElementException("no registered verification key %d" % key_id))
+        else:
+            out.append(_lane_exception(st))
+    return out
 
 
 def topological_sort(stxs: Sequence[SignedTx], ids: Sequence[bytes]) -> List[int]:

@@ -341,6 +341,90 @@ int cordahip_ed25519_sign_keyed_device(cordahip_ctx* ctx, int device, const void
                                        uint32_t msg_len, uint64_t n, const void* d_gate, void* d_sigs,
                                        void* d_status, void* hip_stream);
 
+/* ---- Ed25519 batch verification against registered public keys ----------------- *
+ * Replaces, per lane, Crypto.doVerify / Crypto.isValid(EDDSA_ED25519_SHA512, key,
+ * sig, clear) (Crypto.kt:472-541) for the keys a node sees all day: the notary
+ * identities of the network map (every transaction ResolveTransactionsFlow walks
+ * carries a notary signature; the client's check of the notary's answer,
+ * NotaryFlow.kt:75-83), its oracles' keys, fixed issuers. A key is registered
+ * once; a lane then names it by id and is verified as i2p's engine states the
+ * rule, encode([S_eff]B + [h](-A)) == R bytewise, from tables alone (64 mixed
+ * additions: signed 8-bit windows over the key's table and over one of B) -- no
+ * key decompression, no doubling, no decode of R. Apart from UNKNOWN_KEY a lane
+ * answers exactly what cordahip_sig_verify answers for the same signature and
+ * message with that key's bytes, under both flags values.
+ *
+ * Key registry. cordahip_vkey_add_ed25519 decodes the 32 bytes by the rules the
+ * generic path uses (i2p 0.2.0 GroupElement(curve, bytes): y not range checked,
+ * x = 0 with the sign bit set accepted, no small-order check). Bytes that do
+ * not decode are data, not an ABI error: the call returns CORDAHIP_SUCCESS with
+ * *key_status = CORDAHIP_STATUS_BAD_KEY and *key_id = 0xFFFFFFFF and takes no
+ * slot (the JVM raises at key construction, as today). Otherwise *key_status =
+ * CORDAHIP_STATUS_OK and a kernel on every device of the context builds the
+ * key's record: the canonical Abyte (what SHA-512 hashes) and the window table
+ * [d 256^j](-A), d = 1..128, j = 0..31 (512 KiB). Two adds of the same bytes
+ * give two ids. A context holds up to 64 live keys (CORDAHIP_VKEY_MAX_KEYS); a
+ * full registry is CORDAHIP_ERR_OUT_OF_MEMORY. The tables (32.5 MiB per device:
+ * 64 keys' and the base point's) are allocated by the first add -- a context that never registers a key
+ * allocates nothing -- are counted in cordahip_device_mem, and are kept by
+ * cordahip_trim and the idle release.
+ * Ordering, as for the signer: cordahip_vkey_remove waits for every keyed call
+ * already enqueued on the context's devices (caller streams included) before it
+ * clears the record; a call enqueued after remove returns answers
+ * CORDAHIP_VERIFY_UNKNOWN_KEY for that id -- also after the slot has been given
+ * to a new key: an id is never reused (slot | reuse counter << 6, compared with
+ * the id stored in the record). remove of an id that is not live is
+ * CORDAHIP_ERR_INVALID_ARG.
+ * Verification-key ids and signer ids (cordahip_signer_add_ed25519) are separate
+ * namespaces: neither call accepts the other's ids.
+ * A public key is public. No custody rule applies to these tables and nothing
+ * about them is constant-time: the kernel gathers table entries indexed by a
+ * lane's own digits (the signer's read-everything-and-select scan protects a
+ * secret scalar; here it would only cost time).
+ *
+ * Per-lane statuses, by precedence:
+ *   CORDAHIP_VERIFY_UNKNOWN_KEY   key_id[i] names no live key (no table is read)
+ *   CORDAHIP_STATUS_EMPTY         flags == 0 (doVerify) only: empty signature or
+ *                                 empty message (Crypto.kt:475-476)
+ *   CORDAHIP_STATUS_MALFORMED_SIG signature length != 64
+ *   CORDAHIP_STATUS_BAD_SIG
+ *   CORDAHIP_STATUS_OK
+ * verdict bit i = (status[i] == OK).
+ *
+ * cordahip_verify_keyed / cordahip_verify_keyed_submit: host memory, signatures
+ * and messages CSR, checked whole before any enqueue (sig_off, msg_off
+ * non-decreasing within sig_bytes, msg_bytes; a single message of 2^32 bytes or
+ * more is refused the same way): CORDAHIP_ERR_INVALID_ARG, outputs untouched,
+ * context usable. Lanes are sharded over the context's devices
+ * (cordahip_shard_range, align 64: a device owns whole verdict words) and stream
+ * in chunks of CORDAHIP_HOST_CHUNK lanes through page-locked staging. */
+#define CORDAHIP_VERIFY_UNKNOWN_KEY 16
+#define CORDAHIP_VKEY_MAX_KEYS 64 /* live keys per context */
+int cordahip_vkey_add_ed25519(cordahip_ctx* ctx, const uint8_t key[32], uint32_t* key_id, uint8_t* key_status);
+int cordahip_vkey_remove(cordahip_ctx* ctx, uint32_t key_id);
+typedef struct {
+  uint64_t n;
+  const uint32_t* key_id;  /* [n] ids from cordahip_vkey_add_ed25519 */
+  const uint8_t* sig;
+  const uint64_t* sig_off; /* [n+1] into sig */
+  const uint8_t* msg;
+  const uint64_t* msg_off; /* [n+1] into msg */
+  uint8_t* status;         /* [n] out */
+  uint64_t* verdict;       /* [(n+63)/64] out, may be NULL */
+  uint32_t flags;          /* 0 or CORDAHIP_FLAG_IS_VALID */
+  uint64_t sig_bytes, msg_bytes; /* bytes at sig / msg; sig_off[n] <= sig_bytes, msg_off[n] <= msg_bytes */
+} cordahip_keyed_sig_batch;
+int cordahip_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch);
+int cordahip_verify_keyed_submit(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch, uint64_t* ticket);
+/* Device-resident form, doVerify rules: d_key_id uint32[n], d_sigs dense 64-byte
+ * rows, d_msgs dense rows of msg_len bytes (both 16-byte aligned, as for
+ * cordahip_ed25519_verify_device), d_status [n], d_verdict [(n+63)/64] or NULL,
+ * all in HBM on `device`, on hip_stream. msg_len == 0 makes every lane with a
+ * live key EMPTY, as in cordahip_ed25519_verify_device. */
+int cordahip_ed25519_verify_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_sigs,
+                                         const void* d_msgs, uint32_t msg_len, uint64_t n, void* d_status,
+                                         void* d_verdict, void* hip_stream);
+
 /* ECDSA keygen + sign (device memory), corpus generation: per lane scheme 2/3,
  * d = SHA-256(seed) mod n, k = SHA-256(seed || msg[:64]) mod n; writes the
  * uncompressed SEC1 key (65-byte slot, key_len = 65) and the DER signature

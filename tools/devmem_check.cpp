@@ -8,9 +8,10 @@
 //  c  after ~Device nothing is live and the account is zero (ASan: no leak either)
 //  d  the same for a half-initialised Device (hipMalloc failing midway, null events)
 //  e  two Devices charge the accounts of their own ids, whatever hipGetDevice says
-//  f  the signer's key table (SignKeys: not part of Device::visit, so the idle release
-//     is never offered it) is bound with the device, survives the idle release with its
-//     bytes still in the account, and is freed by ~Device
+//  f  the signer's key table and the verification keys' tables (SignKeys, VerifyKeys:
+//     not part of Device::visit, so the idle release is never offered them) are bound
+//     with the device, survive the idle release with their bytes still in the account,
+//     and are freed by ~Device
 // prints one JSON line; exit status 1 and a message on the first failed check
 #include <cstdio>
 #include <cstdlib>
@@ -175,6 +176,8 @@ int main() {
     RsaWork rw;
     SignKeys sk;
     visited(sk, 0, "SignKeys");
+    VerifyKeys vk;
+    visited(vk, 0, "VerifyKeys");
     visited(tw, 0, "TxWork");
     visited(ss, 0, "StreamStage");
     visited(ps, kPackPlain, "PackStage");
@@ -190,7 +193,9 @@ int main() {
     // the mutexes and condition variable, turn counters, ring generations, set_busy,
     // s_ec2 (an alias), the encoder's flags and counters; the signer's two mutexes and its
     // key table, which has a visit of its own (f)
-    constexpr size_t kDeviceOwnPlain = 1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys);
+    // and the verification keys' two mutexes and tables, visited with the signer's (f)
+    constexpr size_t kDeviceOwnPlain =
+        1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys) + 2 * sizeof(std::mutex) + sizeof(VerifyKeys);
     const Count c = visited(*d, kDeviceOwnPlain + kTxSets * kTxSetPlain + kPackStages * kPackPlain, "Device");
     ndev = c.ndev, npin = c.npin, nev = c.nfence + c.nevent;
     CHECK(c.nstream == 7);
@@ -249,14 +254,16 @@ int main() {
     k->visit(gk);
     const size_t before = g.dev.size();
     k->visit_keys(gk);
-    CHECK(g.dev.size() == before + 1 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
-    void *tab = k->keys.tab.p, *stage = k->keys.stage.p;
+    CHECK(g.dev.size() == before + 2 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
+    CHECK(k->vkeys.tab.dev == 6 && k->vkeys.tab.p && k->vkeys.stage.p && k->vkeys.ev.ev);
+    void *tab = k->keys.tab.p, *stage = k->keys.stage.p, *vtab = k->vkeys.tab.p, *vstage = k->vkeys.stage.p;
     k->release_idle();
     CHECK(k->keys.tab.p == tab && k->keys.stage.p == stage && g.dev.count(tab) && g.pin.count(stage));
+    CHECK(k->vkeys.tab.p == vtab && k->vkeys.stage.p == vstage && g.dev.count(vtab) && g.pin.count(vstage));
     Kept kk;
     k->visit(kk);  // what the release walks: the same kept buffers as in b
     CHECK(kk.devs.size() == kept.devs.size());
-    CHECK(mem_acct(6).in_use.load() == kk.bytes + k->keys.tab.cap);
+    CHECK(mem_acct(6).in_use.load() == kk.bytes + k->keys.tab.cap + k->vkeys.tab.cap);
     delete k;
     CHECK(g.clean() && mem_acct(6).in_use.load() == 0);
   }
