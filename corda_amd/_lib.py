@@ -44,6 +44,8 @@ EXPORTS = [
     "cordahip_ed25519_sign_keyed_device",
     "cordahip_vkey_add_ed25519", "cordahip_vkey_remove", "cordahip_verify_keyed", "cordahip_verify_keyed_submit",
     "cordahip_ed25519_verify_keyed_device",
+    "cordahip_vkey_add_ecdsa", "cordahip_ecdsa_verify_keyed", "cordahip_ecdsa_verify_keyed_submit",
+    "cordahip_ecdsa_verify_keyed_device",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
@@ -315,6 +317,10 @@ def lib() -> ctypes.CDLL:
         "cordahip_verify_keyed": (i32, [vp, ctypes.POINTER(KeyedSigBatch)]),
         "cordahip_verify_keyed_submit": (i32, [vp, ctypes.POINTER(KeyedSigBatch), ctypes.POINTER(u64)]),
         "cordahip_ed25519_verify_keyed_device": (i32, [vp, i32, vp, vp, vp, u32, u64, vp, vp, vp]),
+        "cordahip_vkey_add_ecdsa": (i32, [vp, u32, vp, u32, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint8)]),
+        "cordahip_ecdsa_verify_keyed": (i32, [vp, ctypes.POINTER(KeyedSigBatch)]),
+        "cordahip_ecdsa_verify_keyed_submit": (i32, [vp, ctypes.POINTER(KeyedSigBatch), ctypes.POINTER(u64)]),
+        "cordahip_ecdsa_verify_keyed_device": (i32, [vp, i32, vp, vp, vp, vp, u32, u64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(l, name)

@@ -27,6 +27,7 @@
 #include "csr_check.hpp"
 #include "der.hpp"
 #include "ed25519_comb.hpp"
+#include "ecdsa_vkey.hpp"
 #include "ed25519_vkey.hpp"
 #include "kryo_core.hpp"
 #include "pack_rows.hpp"
@@ -1461,11 +1462,24 @@ int sign_impl(cordahip_ctx* ctx, const cordahip_sign_batch* b) {
 // keyed kernel that may still read it; the stream is drained before return. The
 // table's entries stay: without a record whose id matches, no lane reads them.
 hipError_t vkey_clear_record(Device& d, uint32_t slot) {
-  if (!d.vkeys.tab.p) return hipSuccess;
-  hipError_t e = d.vkeys.ev.sync();
-  e = e ? e
-        : hipMemsetAsync(d.vkeys.tab.as<uint32_t>() + kVkeyRecBase + (size_t)slot * kVkeyRecWords, 0,
-                         kVkeyRecWords * 4, d.stream);
+  if (!d.vkeys.tab.p && !d.ec_vkeys.tab.p) return hipSuccess;
+  hipError_t e = hipSuccess;
+  if (d.vkeys.tab.p) {
+    e = d.vkeys.ev.sync();
+    e = e ? e
+          : hipMemsetAsync(d.vkeys.tab.as<uint32_t>() + kVkeyRecBase + (size_t)slot * kVkeyRecWords, 0,
+                           kVkeyRecWords * 4, d.stream);
+  }
+  if (d.ec_vkeys.tab.p) {  // the slot's record of the other family (K13): one pool, one remove
+    hipError_t x = d.ec_vkeys.ev.sync();
+    x = x ? x
+          : hipMemsetAsync(d.ec_vkeys.tab.as<uint32_t>() + kEcVkeyRecBase + (size_t)slot * kEcVkeyRecWords, 0,
+                           kEcVkeyRecWords * 4, d.stream);
+    e = e ? e : x;
+    EcVkeyState& st = d.ec_vkey_state;
+    if (st.scheme[slot]) st.live[st.scheme[slot] - 2]--;
+    st.scheme[slot] = 0;
+  }
   const hipError_t f = hipStreamSynchronize(d.stream);
   return e ? e : f;
 }
@@ -1499,7 +1513,55 @@ int vkey_build_on(Device& d, const uint8_t key[32], uint32_t key_id, bool* decod
   return hip_err(e ? e : f);
 }
 
-int vkey_add_impl(cordahip_ctx* ctx, const uint8_t key[32], uint32_t* key_id, uint8_t* key_status) {
+// The ECDSA key's record and table built in key_id's slot on one device (vkey_mu held):
+// the device's first ECDSA key allocates the tables (records zeroed), its first key of a
+// curve builds that curve's base-point table. *decoded: whether the device took the
+// SEC1 bytes for a point of the curve (BC ECCurve.decodePoint).
+int ec_vkey_build_on(Device& d, uint32_t scheme, const uint8_t* key, uint32_t key_len, uint32_t key_id, bool* decoded) {
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  EcVkeyState& st = d.ec_vkey_state;
+  if (!d.ec_vkeys.tab.p) {
+    if (d.ec_vkeys.tab.ensure(ecdsa_vkey_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+    st = EcVkeyState{};
+    if (hipMemsetAsync(d.ec_vkeys.tab.as<uint32_t>() + kEcVkeyRecBase, 0, (kEcVkeyAllWords - kEcVkeyRecBase) * 4,
+                       d.stream) != hipSuccess)
+      return CORDAHIP_ERR_HIP;
+  }
+  uint32_t* tab = d.ec_vkeys.tab.as<uint32_t>();
+  const bool build_base = !st.base[scheme - 2];  // marked built only once the stream has drained below
+  if (build_base && launch_ecdsa_vkey_build(tab, scheme, ec_vkey_base_slot(scheme), 0u, 0u, d.stream) != hipSuccess)
+    return CORDAHIP_ERR_HIP;
+  if (d.ec_vkeys.stage.ensure(128) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  uint8_t* stage = d.ec_vkeys.stage.as<uint8_t>();
+  std::memset(stage, 0, 128);
+  std::memcpy(stage, key, key_len);
+  hipError_t e = d.ec_vkeys.ev.sync();  // a removed key's slot: no kernel still reads its table
+  e = e ? e : hipMemcpyAsync(tab + kEcVkeyKeyWord, stage, 80, hipMemcpyHostToDevice, d.stream);
+  e = e ? e : launch_ecdsa_vkey_build(tab, scheme, vkey_slot(key_id), key_id, key_len, d.stream);
+  e = e ? e : hipMemcpyAsync(stage + 80, tab + kEcVkeyOkWord, 16, hipMemcpyDeviceToHost, d.stream);
+  const hipError_t f = hipStreamSynchronize(d.stream);
+  if (e == hipSuccess && f == hipSuccess) {
+    uint32_t flag;
+    std::memcpy(&flag, stage + 80, 4);
+    *decoded = flag == 1u;
+    if (build_base) st.base[scheme - 2] = 1;
+    if (*decoded) {
+      st.scheme[vkey_slot(key_id)] = (uint8_t)scheme;
+      st.live[scheme - 2]++;
+    }
+  }
+  return hip_err(e ? e : f);
+}
+
+// scheme 0: an Ed25519 key of 32 bytes (K12); 2 / 3: an ECDSA key in SEC1 form (K13).
+// One pool of slots and one id space for both.
+int vkey_add_impl(cordahip_ctx* ctx, uint32_t scheme, const uint8_t* key, uint32_t key_len, uint32_t* key_id,
+                  uint8_t* key_status) {
+  if (scheme && key_len != 33 && key_len != 65) {  // ECCurve.decodePoint: invalid point encoding
+    *key_id = kVkeyNoId;
+    *key_status = CORDAHIP_STATUS_BAD_KEY;
+    return CORDAHIP_SUCCESS;
+  }
   std::lock_guard<std::mutex> g(ctx->vkey_mu);
   if (ctx->vkey_gen.empty()) {
     ctx->vkey_gen.assign(kVkeySlots, 0);
@@ -1518,7 +1580,8 @@ int vkey_add_impl(cordahip_ctx* ctx, const uint8_t key[32], uint32_t* key_id, ui
     Device& d = *ctx->devs[done];
     std::lock_guard<std::mutex> gd(d.vkey_mu);
     const Activity act(d);
-    rc = vkey_build_on(d, key, id, done ? &cur : &first);
+    rc = scheme ? ec_vkey_build_on(d, scheme, key, key_len, id, done ? &cur : &first)
+                : vkey_build_on(d, key, id, done ? &cur : &first);
     if (rc == CORDAHIP_SUCCESS && done && cur != first) rc = CORDAHIP_ERR_HIP;
     if (rc == CORDAHIP_SUCCESS && !first) break;  // not a point: no device wrote anything
   }
@@ -1652,6 +1715,101 @@ int verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) {
     return CORDAHIP_ERR_INVALID_ARG;
   return for_shards(ctx->devs, n, 64,
                     [&](Device& d, uint64_t lo, uint64_t hi) { return verify_keyed_shard(ctx, d, b, lo, hi); });
+}
+
+// The ECDSA keyed verifier on stream s (vkey_mu held, device current): as vkey_enqueue,
+// behind the ECDSA tables' fence. A device without ECDSA tables passes none: every lane
+// is then UNKNOWN_KEY.
+hipError_t ec_vkey_enqueue(Device& d, const uint32_t* key_id, const uint8_t* sigs, const uint8_t* sig_len,
+                           const uint8_t* msgs, const uint64_t* moff, const uint32_t* mlen, uint32_t msg_len,
+                           uint64_t n, const uint8_t* pre, uint32_t flags, uint8_t* status,
+                           unsigned long long* verdict, hipStream_t s) {
+  const EcVkeyState& st = d.ec_vkey_state;
+  const bool have = d.ec_vkeys.tab.p != nullptr;
+  hipError_t e = d.ec_vkeys.ev.wait(s);
+  e = e ? e
+        : launch_ecdsa_verify_keyed(key_id, sigs, sig_len, msgs, moff, mlen, msg_len, n, pre, flags,
+                                    d.ec_vkeys.tab.as<uint32_t>(), have && st.live[0] > 0, have && st.live[1] > 0,
+                                    status, verdict, s);
+  return e ? e : d.ec_vkeys.ev.record(s);
+}
+
+// cordahip_ecdsa_verify_keyed for lanes [lo, hi) on one device: verify_keyed_shard with
+// 72-byte DER slots and their lengths (pack_rows.hpp keyed_ec_pack_rows) and K13.
+int ec_verify_keyed_shard(cordahip_ctx* ctx, Device& d, const cordahip_keyed_sig_batch* b, uint64_t lo, uint64_t hi) {
+  std::lock_guard<std::mutex> g(d.vkey_host_mu);
+  const NodeBind nb(d);
+  const Activity act(d);
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  const uint64_t chunk = (env_lanes("CORDAHIP_HOST_CHUNK", 1ull << 22) + 63) / 64 * 64;  // whole verdict words
+  HostPool& pool = pool_of(ctx, d);
+  hipStream_t s = d.stream;
+  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
+  std::vector<uint64_t> poff;
+  for (uint64_t a = lo; a < hi; a += chunk) {
+    const uint64_t m = std::min(chunk, hi - a);
+    const uint64_t words = (m + 63) / 64;
+    const double t0 = now_ms();
+    poff.resize(m);
+    const SignLayout lay = msg_chunk_layout(b->msg_off, a, m, poff.data());
+    const bool dense = lay.dense;
+    const uint64_t bytes = lay.bytes;
+    const size_t need[9] = {(size_t)m * 4, (size_t)m * 72, (size_t)m, (size_t)std::max<uint64_t>(bytes, 16),
+                            (size_t)m * 8, (size_t)m * 4,  (size_t)m, (size_t)words * 8,
+                            (size_t)m};
+    for (int k = 0; k < 9; k++)  // the previous chunk has drained: growing frees nothing in use
+      if (d.vkey_h[k].ensure(need[k]) != hipSuccess || d.vkey_d[k].ensure(need[k]) != hipSuccess)
+        return CORDAHIP_ERR_OUT_OF_MEMORY;
+    uint8_t* hm = d.vkey_h[3].as<uint8_t>();
+    uint64_t* ho = d.vkey_h[4].as<uint64_t>();
+    uint32_t* hl = d.vkey_h[5].as<uint32_t>();
+    pool.parallel_for(m, 1u << 14, [&](uint64_t x, uint64_t y) {
+      keyed_ec_pack_rows(b, a, x, y, lay, poff.data(), d.vkey_h[0].as<uint32_t>(), d.vkey_h[1].as<uint8_t>(),
+                         d.vkey_h[8].as<uint8_t>(), d.vkey_h[2].as<uint8_t>(), hm, ho, hl);
+    });
+    hipError_t e = hipMemcpyAsync(d.vkey_d[0].p, d.vkey_h[0].p, m * 4, h2d, s);
+    e = e ? e : hipMemcpyAsync(d.vkey_d[1].p, d.vkey_h[1].p, m * 72, h2d, s);
+    e = e ? e : hipMemcpyAsync(d.vkey_d[2].p, d.vkey_h[2].p, m, h2d, s);
+    e = e ? e : hipMemcpyAsync(d.vkey_d[8].p, d.vkey_h[8].p, m, h2d, s);
+    if (bytes) e = e ? e : hipMemcpyAsync(d.vkey_d[3].p, hm, bytes, h2d, s);
+    if (!dense) {
+      e = e ? e : hipMemcpyAsync(d.vkey_d[4].p, ho, m * 8, h2d, s);
+      e = e ? e : hipMemcpyAsync(d.vkey_d[5].p, hl, m * 4, h2d, s);
+    }
+    if (e == hipSuccess) {
+      std::lock_guard<std::mutex> gs(d.vkey_mu);
+      e = ec_vkey_enqueue(d, d.vkey_d[0].as<uint32_t>(), d.vkey_d[1].as<uint8_t>(), d.vkey_d[8].as<uint8_t>(),
+                          d.vkey_d[3].as<uint8_t>(), dense ? nullptr : d.vkey_d[4].as<uint64_t>(),
+                          dense ? nullptr : d.vkey_d[5].as<uint32_t>(), 32, m, d.vkey_d[2].as<uint8_t>(), b->flags,
+                          d.vkey_d[6].as<uint8_t>(), d.vkey_d[7].as<unsigned long long>(), s);
+    }
+    e = e ? e : hipMemcpyAsync(d.vkey_h[6].p, d.vkey_d[6].p, m, d2h, s);
+    e = e ? e : hipMemcpyAsync(d.vkey_h[7].p, d.vkey_d[7].p, words * 8, d2h, s);
+    e = e ? e : d.vkey_host_ev.record(s);
+    e = e ? e : d.vkey_host_ev.sync();
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(s);  // no queued work outlives the call
+      return CORDAHIP_ERR_HIP;
+    }
+    std::memcpy(b->status + a, d.vkey_h[6].p, m);
+    if (b->verdict) std::memcpy(b->verdict + a / 64, d.vkey_h[7].p, words * 8);
+    if (tracing())
+      fprintf(stderr, "[cordahip] dev %d keyed ECDSA verify chunk: %llu lanes (%s messages) in %.2f ms\n", d.id,
+              (unsigned long long)m, dense ? "32-byte" : "CSR", now_ms() - t0);
+  }
+  return CORDAHIP_SUCCESS;
+}
+
+int ec_verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) {
+  const uint64_t n = b->n;
+  if (n == 0) return CORDAHIP_SUCCESS;
+  if (!b->key_id || !b->sig_off || !b->msg_off || !b->status) return CORDAHIP_ERR_INVALID_ARG;
+  if (b->flags & ~CORDAHIP_FLAG_IS_VALID) return CORDAHIP_ERR_INVALID_ARG;
+  if (!check_keyed_sig_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
+  if ((b->msg_off[0] != b->msg_off[n] && !b->msg) || (b->sig_off[0] != b->sig_off[n] && !b->sig))
+    return CORDAHIP_ERR_INVALID_ARG;
+  return for_shards(ctx->devs, n, 64,
+                    [&](Device& d, uint64_t lo, uint64_t hi) { return ec_verify_keyed_shard(ctx, d, b, lo, hi); });
 }
 
 Device* dev_at(cordahip_ctx* ctx, int device) {
@@ -2044,7 +2202,15 @@ int cordahip_ed25519_sign_keyed_device(cordahip_ctx* ctx, int device, const void
 
 int cordahip_vkey_add_ed25519(cordahip_ctx* ctx, const uint8_t key[32], uint32_t* key_id, uint8_t* key_status) {
   if (!ctx || !key || !key_id || !key_status) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return vkey_add_impl(ctx, key, key_id, key_status); });
+  return guarded([&] { return vkey_add_impl(ctx, 0u, key, 32u, key_id, key_status); });
+}
+
+int cordahip_vkey_add_ecdsa(cordahip_ctx* ctx, uint32_t scheme, const uint8_t* key, uint32_t key_len, uint32_t* key_id,
+                            uint8_t* key_status) {
+  if (!ctx || !key_id || !key_status || (key_len && !key)) return CORDAHIP_ERR_INVALID_ARG;
+  if (scheme != CORDAHIP_SCHEME_ECDSA_SECP256K1_SHA256 && scheme != CORDAHIP_SCHEME_ECDSA_SECP256R1_SHA256)
+    return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return vkey_add_impl(ctx, scheme, key, key_len, key_id, key_status); });
 }
 
 int cordahip_vkey_remove(cordahip_ctx* ctx, uint32_t key_id) {
@@ -2075,6 +2241,34 @@ int cordahip_ed25519_verify_keyed_device(cordahip_ctx* ctx, int device, const vo
       return vkey_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_sigs),
                           static_cast<const uint8_t*>(d_msgs), nullptr, nullptr, msg_len, n, nullptr, 0u,
                           static_cast<uint8_t*>(d_status), static_cast<unsigned long long*>(d_verdict), s);
+    });
+  });
+}
+
+int cordahip_ecdsa_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch) {
+  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return ec_verify_keyed_impl(ctx, batch); });
+}
+
+int cordahip_ecdsa_verify_keyed_submit(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch, uint64_t* ticket) {
+  return submit(ctx, ticket, ec_verify_keyed_impl, batch);
+}
+
+int cordahip_ecdsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_sigs,
+                                       const void* d_sig_len, const void* d_msgs, uint32_t msg_len, uint64_t n,
+                                       void* d_status, void* d_verdict, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || (n && (!d_key_id || !d_sigs || !d_sig_len || !d_status || (msg_len && !d_msgs))))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_key_id) & 3) || (reinterpret_cast<uintptr_t>(d_verdict) & 7))
+    return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    std::lock_guard<std::mutex> g(d->vkey_mu);
+    return device_call(*d, hip_stream, [&](hipStream_t s) {
+      return ec_vkey_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_sigs),
+                             static_cast<const uint8_t*>(d_sig_len), static_cast<const uint8_t*>(d_msgs), nullptr,
+                             nullptr, msg_len, n, nullptr, 0u, static_cast<uint8_t*>(d_status),
+                             static_cast<unsigned long long*>(d_verdict), s);
     });
   });
 }

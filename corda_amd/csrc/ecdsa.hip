@@ -25,6 +25,7 @@
 #include <string>
 
 #include "der.hpp"
+#include "ecdsa_vkey.hpp"
 #include "fp29.hpp"
 #include "fp29_asm.hpp"
 #include "fp29_consts.hpp"
@@ -1406,5 +1407,14 @@ hipError_t launch_ecdsa_verify(const uint8_t* scheme, const uint8_t* keys, const
   if (verdict) hipLaunchKernelGGL(verdict_kernel, grid, dim3(256), 0, s, status, n, verdict);
   return hipGetLastError();
 }
+
+// K13, verification against registered keys: the kernels share this unit's device
+// functions (none of them changes; the generic kernels compile as before)
+#include "ecdsa_vkey.hip"
+#define CH_SAME_N(i) (kEcVkeyNK1[i] == K1N::limb(i) && kEcVkeyNR1[i] == R1N::limb(i))
+static_assert(CH_SAME_N(0) && CH_SAME_N(1) && CH_SAME_N(2) && CH_SAME_N(3) && CH_SAME_N(4) && CH_SAME_N(5) &&
+                  CH_SAME_N(6) && CH_SAME_N(7),
+              "ecdsa_vkey.hpp's group orders are this unit's");
+#undef CH_SAME_N
 
 }  // namespace cordahip

@@ -225,5 +225,42 @@ inline void keyed_pack_rows(const cordahip_keyed_sig_batch* b, uint64_t a, uint6
   }
 }
 
+// ---- cordahip_ecdsa_verify_keyed chunks (a batch that passed check_keyed_sig_batch) ----
+// As keyed_pack_rows, with the DER signatures in 72-byte slots and their lengths
+// beside them. A signature longer than its slot holds no r, s < n, so the DER rules
+// alone decide it here, as in pack_ec_row: EMPTY first for an empty message under
+// doVerify, else well-formed -> BAD_SIG, else MALFORMED_SIG; such a lane gets a zero
+// slot of length 72. Every other decision is the kernel's (hpre stays OK).
+inline void keyed_ec_pack_rows(const cordahip_keyed_sig_batch* b, uint64_t a, uint64_t x, uint64_t y,
+                               const SignLayout& l, const uint64_t* poff, uint32_t* hid, uint8_t* hsig, uint8_t* hsl,
+                               uint8_t* hpre, uint8_t* hm, uint64_t* ho, uint32_t* hl) {
+  const bool do_verify = !(b->flags & CORDAHIP_FLAG_IS_VALID);
+  for (uint64_t i = x; i < y; i++) {
+    const uint64_t o = b->msg_off[a + i], len = b->msg_off[a + i + 1] - o, p = l.dense ? i * 32 : poff[i];
+    const uint64_t so = b->sig_off[a + i], sl = b->sig_off[a + i + 1] - so;
+    hid[i] = b->key_id[a + i];
+    uint8_t st = CORDAHIP_STATUS_OK;
+    if (sl <= 72) {
+      if (sl) std::memcpy(hsig + i * 72, b->sig + so, sl);
+      std::memset(hsig + i * 72 + sl, 0, 72 - sl);
+      hsl[i] = (uint8_t)sl;
+    } else {
+      DerInt dr, ds;
+      st = (len == 0 && do_verify) ? CORDAHIP_STATUS_EMPTY
+           : der_decode_sig(b->sig + so, (uint32_t)std::min<uint64_t>(sl, 0xffffffffu), dr, ds)
+               ? CORDAHIP_STATUS_BAD_SIG
+               : CORDAHIP_STATUS_MALFORMED_SIG;
+      std::memset(hsig + i * 72, 0, 72);
+      hsl[i] = 72;
+    }
+    hpre[i] = st;
+    if (len) std::memcpy(hm + p, b->msg + o, len);
+    if (!l.dense) {
+      ho[i] = p;
+      hl[i] = (uint32_t)len;
+    }
+  }
+}
+
 }  // namespace rt
 }  // namespace cordahip

@@ -134,6 +134,20 @@ hipError_t launch_ecdsa_verify(const uint8_t* scheme, const uint8_t* keys, const
                                unsigned long long* verdict, unsigned int* counters6, unsigned int* perm,
                                uint32_t* ws, uint64_t ws_slots, uint32_t flags, hipStream_t s);
 size_t ecdsa_ws_slot_bytes();
+// ecdsa_vkey.hip (K13): a registered ECDSA key's record and window table built in the
+// device's table (the SEC1 bytes are in the table's scratch words, the decode verdict
+// comes back there: ecdsa_vkey.hpp kEcVkeyKeyWord / kEcVkeyOkWord; slot >= 64: the
+// curve's base-point table) and the keyed verifier (72-byte DER slots with lengths;
+// messages, pre and flags as for launch_ed25519_verify_keyed; live_k1 / live_r1: the
+// curves that have a live key on the device)
+size_t ecdsa_vkey_bytes();
+hipError_t launch_ecdsa_vkey_build(uint32_t* vtab, uint32_t scheme, uint32_t slot, uint32_t key_id, uint32_t key_len,
+                                   hipStream_t s);
+hipError_t launch_ecdsa_verify_keyed(const uint32_t* key_id, const uint8_t* sigs, const uint8_t* sig_len,
+                                     const uint8_t* msgs, const uint64_t* moff, const uint32_t* mlen, uint32_t msg_len,
+                                     uint64_t n, const uint8_t* pre, uint32_t flags, const uint32_t* vtab,
+                                     bool live_k1, bool live_r1, uint8_t* status, unsigned long long* verdict,
+                                     hipStream_t s);
 // rsa.hip: rows of W = 64 / 96 / 128 little-endian words, one width per launch
 uint32_t rsa_group_lanes();  // lanes that share one signature in rsa_modexp_kernel
 hipError_t launch_rsa_public_op(const uint32_t* mod, const uint32_t* exp, const uint32_t* in, uint32_t W, uint64_t n,
@@ -447,6 +461,31 @@ struct VerifyKeys {
   }
 };
 
+// The ECDSA verification-key table of one device (ecdsa_vkey.hpp: 64 window tables of
+// 320 KiB, the two curves' base-point tables, the records and the build kernel's
+// scratch), allocated (records zeroed) by the context's first
+// cordahip_vkey_add_ecdsa and then handled exactly like VerifyKeys. stage: 128
+// page-locked bytes, the SEC1 bytes out and the decode verdict back.
+struct EcVerifyKeys {
+  DevBuf tab;
+  PinBuf stage;
+  Fence ev;
+  template <class V>
+  void visit(V& v) {
+    v.dev(tab, kKept);
+    v.pin(stage, kKept);
+    v.fence(ev);
+  }
+};
+// What the host knows of that table (Device::vkey_mu): base[c]: the base-point table of
+// curve c (0: secp256k1, 1: P-256) has been built; live[c]: that curve's live keys on
+// this device; scheme[slot]: the curve of the slot's live record (0: none).
+struct EcVkeyState {
+  uint32_t base[2] = {0, 0};
+  uint32_t live[2] = {0, 0};
+  uint8_t scheme[64] = {};
+};
+
 // Fork-join pool for host-side packing and scattering. parallel_for splits
 // [0, n) into pieces of at least `grain` lanes; the caller runs pieces too,
 // so concurrent callers (one pipeline per device and section) all progress.
@@ -605,16 +644,21 @@ struct Device {
   // whole run; remove waits for vkeys.ev first.
   VerifyKeys vkeys;
   std::mutex vkey_mu;
+  // ECDSA verification against registered keys (K13): the tables of the same registry's
+  // ECDSA keys, under the same vkey_mu, with a fence of their own.
+  EcVerifyKeys ec_vkeys;
+  EcVkeyState ec_vkey_state;
   // cordahip_verify_keyed's chunk stage: h/d[0] key ids, [1] signature rows, [2] host
   // pre-statuses, [3] messages, [4] their offsets, [5] their lengths, [6] statuses, [7]
-  // verdict words. vkey_host_mu is held for a shard's run; vkey_host_ev follows a
-  // chunk's last copy.
+  // verdict words, [8] signature lengths (cordahip_ecdsa_verify_keyed only, whose rows
+  // are 72-byte DER slots). vkey_host_mu is held for a shard's run; vkey_host_ev
+  // follows a chunk's last copy.
   std::mutex vkey_host_mu;
-  PinBuf vkey_h[8];
-  DevBuf vkey_d[8];
+  PinBuf vkey_h[9];
+  DevBuf vkey_d[9];
   Fence vkey_host_ev;
 
-  // everything but `keys` and `vkeys`, which the idle release is never offered (visit_keys)
+  // everything but `keys`, `vkeys` and `ec_vkeys`, which the idle release is never offered (visit_keys)
   template <class V>
   void visit(V& v) {
     for (DevBuf* b : {&btab, &gtab_k1, &gtab_r1}) v.dev(*b, kKept);
@@ -657,6 +701,7 @@ struct Device {
   void visit_keys(V& v) {
     keys.visit(v);
     vkeys.visit(v);
+    ec_vkeys.visit(v);
   }
   struct Release : Visitor {  // the buffers; all: the kept ones too
     bool all = false;
@@ -912,9 +957,10 @@ struct cordahip_ctx {
   std::vector<uint32_t> signer_gen;
   std::vector<uint8_t> signer_live;
   uint32_t signer_count = 0;
-  // the verification-key registry (cordahip_vkey_add_ed25519 / _remove): which slots
-  // are live and each slot's reuse counter (empty until the first add). vkey_mu is held
-  // for an add's or a remove's whole run. Ids are a namespace of their own.
+  // the verification-key registry (cordahip_vkey_add_ed25519 / _add_ecdsa / _remove):
+  // which slots are live and each slot's reuse counter (empty until the first add), one
+  // pool for both families. vkey_mu is held for an add's or a remove's whole run. Ids
+  // are a namespace of their own.
   std::mutex vkey_mu;
   std::vector<uint32_t> vkey_gen;
   std::vector<uint8_t> vkey_live;

@@ -261,13 +261,16 @@ def verify_and_sign_filtered_transactions(engine, ftxs, key_id: int):
     return [int(x) for x in status], out
 
 
-def validate_notary_signatures(engine, key_id: int, ids: Sequence[bytes], sigs: Sequence[bytes]):
+def validate_notary_signatures(engine, key_id: int, ids: Sequence[bytes], sigs: Sequence[bytes],
+                               ecdsa: bool = False):
     """What a notary client does with the notary's answers (NotaryFlow.Client.call,
     NotaryFlow.kt:75-83: `check(sig.by in notaryParty.owningKey.keys); sig.verify(stx.id.bytes)`)
     for a batch of transactions notarised by one key: one Engine.verify_keyed_batch of sigs[t]
     over ids[t] against the verification key registered as `key_id` (the caller registered the
     notary identity's key, engine.vkey_add_ed25519, and sends here the signatures whose `by` is
     that key -- the membership check is a comparison of key bytes it has already made).
+    ecdsa: the notary's key is an ECDSA key (engine.vkey_add_ecdsa, e.g. held in an HSM) and the
+    signatures are DER: Engine.ecdsa_verify_keyed_batch instead.
 
     Returns one outcome per lane: None where the signature verifies, else the exception
     sig.verify throws (_lane_exception's mapping); an id that names no live key is a
@@ -275,7 +278,8 @@ def validate_notary_signatures(engine, key_id: int, ids: Sequence[bytes], sigs: 
     if not ids:
         return []
     assert len(ids) == len(sigs)
-    status, _ = engine.verify_keyed_batch([key_id] * len(ids), [bytes(s) for s in sigs], [bytes(i) for i in ids])
+    verify = engine.ecdsa_verify_keyed_batch if ecdsa else engine.verify_keyed_batch
+    status, _ = verify([key_id] * len(ids), [bytes(s) for s in sigs], [bytes(i) for i in ids])
     out = []
     for st in status:
         st = int(st)

@@ -425,6 +425,69 @@ int cordahip_ed25519_verify_keyed_device(cordahip_ctx* ctx, int device, const vo
                                          const void* d_msgs, uint32_t msg_len, uint64_t n, void* d_status,
                                          void* d_verdict, void* hip_stream);
 
+/* ---- ECDSA verification against registered public keys (kernel K13) --------
+ * Replaces, per lane, Crypto.doVerify / Crypto.isValid for ECDSA_SECP256K1_SHA256
+ * (2) and ECDSA_SECP256R1_SHA256 (3) (Crypto.kt:472-541 -> BouncyCastle
+ * ECDSASigner.verifySignature) for long-lived keys: notaries and oracles whose
+ * keys sit in an HSM, the doorman's and the node CAs' certificate keys. A key is
+ * registered once; a lane names it by id and computes P = [e/s]G + [r/s]Q from
+ * window tables alone -- 64 mixed additions over signed 8-bit digits of the two
+ * scalars, the key's table and one of the curve's base point -- then decides
+ * x(P) mod n == r projectively: no doubling, no key decode (no square root for a
+ * compressed key), no per-lane table, no workspace. Apart from UNKNOWN_KEY a lane
+ * answers exactly what cordahip_sig_verify answers for the same signature and
+ * message with that key's bytes, under both flags values.
+ *
+ * Key registry. cordahip_vkey_add_ecdsa decodes the SEC1 bytes by the rules the
+ * generic path uses (BC ECCurve.decodePoint: uncompressed 04 || x || y or
+ * compressed 02 / 03 || x; a wrong length, a hybrid or infinity encoding, x or
+ * y >= p, a point off the curve, an x without a square root are not keys). Such
+ * bytes are data, not an ABI error: CORDAHIP_SUCCESS with *key_status =
+ * CORDAHIP_STATUS_BAD_KEY and *key_id = 0xFFFFFFFF, and no slot is taken. A
+ * scheme other than 2 or 3 is CORDAHIP_ERR_INVALID_ARG. Otherwise a kernel on
+ * every device of the context builds the key's record and its window table
+ * [d 256^j]Q, d = 1..128, j = 0..31 (320 KiB).
+ * The registry is the Ed25519 one: ONE pool of CORDAHIP_VKEY_MAX_KEYS live keys
+ * per context and one id space for both families; the 65th live key of either
+ * family is CORDAHIP_ERR_OUT_OF_MEMORY, and cordahip_vkey_remove removes a key
+ * of either family, with the ordering documented above. An ECDSA id given to
+ * cordahip_verify_keyed, or an Ed25519 id given to the calls below, names no key
+ * of that family: the lane is CORDAHIP_VERIFY_UNKNOWN_KEY.
+ * The ECDSA tables (20.6 MiB per device: 64 keys' and the two curves' base
+ * points') are allocated by the first ECDSA add of 33 or 65 bytes, whether or
+ * not the device then takes the bytes for a point (the decode runs there) -- a
+ * context that calls only the Ed25519 add, or none, does not allocate them -- are counted in
+ * cordahip_device_mem, and are kept by cordahip_trim and the idle release.
+ * Nothing about them is constant-time: a public key is public.
+ *
+ * Per-lane statuses, by precedence:
+ *   CORDAHIP_VERIFY_UNKNOWN_KEY   key_id[i] names no live ECDSA key (no table is read)
+ *   CORDAHIP_STATUS_EMPTY         flags == 0 (doVerify) only: empty signature or
+ *                                 empty message (Crypto.kt:475-476)
+ *   CORDAHIP_STATUS_MALFORMED_SIG not strict DER (der.hpp rules)
+ *   CORDAHIP_STATUS_BAD_SIG       r or s outside [1, n-1], or the equation fails
+ *   CORDAHIP_STATUS_OK
+ * verdict bit i = (status[i] == OK).
+ *
+ * cordahip_ecdsa_verify_keyed / _submit: cordahip_keyed_sig_batch with DER
+ * signatures of any length in the CSR; checks, sharding, chunking and staging as
+ * for cordahip_verify_keyed. A signature longer than 72 bytes holds no r, s < n:
+ * the DER rules decide it on the host (BAD_SIG when well-formed, else
+ * MALFORMED_SIG), exactly as for generic batches. */
+int cordahip_vkey_add_ecdsa(cordahip_ctx* ctx, uint32_t scheme, const uint8_t* key, uint32_t key_len,
+                            uint32_t* key_id, uint8_t* key_status);
+int cordahip_ecdsa_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch);
+int cordahip_ecdsa_verify_keyed_submit(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch, uint64_t* ticket);
+/* Device-resident form, doVerify rules: d_key_id uint32[n], d_sigs DER signatures in
+ * dense 72-byte slots, d_sig_len uint8[n], d_msgs dense rows of msg_len bytes,
+ * d_status [n], d_verdict [(n+63)/64] or NULL, all in HBM on `device`, on
+ * hip_stream. As in cordahip_ecdsa_verify_device, a sig_len above 72 is
+ * MALFORMED_SIG (EMPTY first when msg_len == 0), and msg_len == 0 makes every
+ * lane with a live key EMPTY. */
+int cordahip_ecdsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_sigs,
+                                       const void* d_sig_len, const void* d_msgs, uint32_t msg_len, uint64_t n,
+                                       void* d_status, void* d_verdict, void* hip_stream);
+
 /* ECDSA keygen + sign (device memory), corpus generation: per lane scheme 2/3,
  * d = SHA-256(seed) mod n, k = SHA-256(seed || msg[:64]) mod n; writes the
  * uncompressed SEC1 key (65-byte slot, key_len = 65) and the DER signature

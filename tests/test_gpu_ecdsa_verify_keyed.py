@@ -1,0 +1,625 @@
+"""ECDSA verification against registered public keys on the GPU (K13: cordahip_vkey_add_ecdsa,
+cordahip_ecdsa_verify_keyed, cordahip_ecdsa_verify_keyed_submit,
+cordahip_ecdsa_verify_keyed_device; cordahip_vkey_remove and the pool of slots shared with the
+Ed25519 registry) against tests/golden/ecdsa_vectors.json, tests/golden/cert_vectors.json, the
+oracles and the generic ECDSA path, lane for lane. Outputs are prefilled with 0xA5 and sit
+between guard bytes, so a lane the library does not write, or a write outside the arrays, shows."""
+import collections
+import ctypes
+import hashlib
+
+import numpy as np
+import pytest
+
+import bc_ecdsa as bc
+import ec_vkey_model as model
+from corda_amd import _lib
+from corda_amd._lib import lib
+
+pytestmark = pytest.mark.gpu
+OK, BAD_SIG, MALFORMED_SIG, BAD_KEY, EMPTY = _lib.OK, 1, 2, 3, _lib.EMPTY
+UNKNOWN = _lib.VERIFY_UNKNOWN_KEY
+NO_ID = _lib.VKEY_NO_ID
+GUARD = 64
+# ecdsa_vkey.hpp: 64 tables of 320 KiB and the two base points', 64 records of 64 bytes, 96 bytes of scratch
+EC_VKEY_BYTES = 66 * 320 * 1024 + 64 * 64 + 96
+
+
+def verdict_bits(verdict, n):
+    return np.array([(int(verdict[i >> 6]) >> (i & 63)) & 1 for i in range(n)], np.uint8)
+
+
+class HostBatch:
+    """cordahip_keyed_sig_batch arrays with guard bytes around status and verdict, everything 0xA5."""
+
+    def __init__(self, ids, sigs, msgs, flags=0):
+        self.n = n = len(sigs)
+        self.flags = flags
+        self.ids = np.asarray(ids, np.uint32)
+        self.soff = np.zeros(n + 1, np.uint64)
+        self.soff[1:] = np.cumsum([len(s) for s in sigs])
+        self.sig = np.frombuffer(b"".join(sigs) or b"\0", np.uint8).copy()
+        self.moff = np.zeros(n + 1, np.uint64)
+        self.moff[1:] = np.cumsum([len(m) for m in msgs])
+        self.msg = np.frombuffer(b"".join(msgs) or b"\0", np.uint8).copy()
+        self.words = (n + 63) // 64
+        self.st_buf = np.full(GUARD + n + GUARD, 0xA5, np.uint8)
+        self.vd_buf = np.full(GUARD + self.words * 8 + GUARD, 0xA5, np.uint8)
+
+    def batch(self, soff=None, moff=None):
+        p = lambda a: a.ctypes.data  # noqa: E731
+        return _lib.KeyedSigBatch(self.n, p(self.ids), p(self.sig), p(self.soff if soff is None else soff),
+                                  p(self.msg), p(self.moff if moff is None else moff), p(self.st_buf) + GUARD,
+                                  p(self.vd_buf) + GUARD, self.flags, int(self.soff[self.n]), int(self.moff[self.n]))
+
+    @property
+    def st(self):
+        return self.st_buf[GUARD:GUARD + self.n]
+
+    @property
+    def verdict(self):
+        return self.vd_buf[GUARD:GUARD + self.words * 8].view(np.uint64)
+
+    def untouched(self):
+        return (self.st_buf == 0xA5).all() and (self.vd_buf == 0xA5).all()
+
+    def guards_intact(self):
+        return all((b[:GUARD] == 0xA5).all() and (b[-GUARD:] == 0xA5).all() for b in (self.st_buf, self.vd_buf))
+
+    def run(self, engine, fn="cordahip_ecdsa_verify_keyed"):
+        rc = getattr(lib(), fn)(engine.ctx, ctypes.byref(self.batch()))
+        assert rc == 0, rc
+        assert self.guards_intact()
+        bits = verdict_bits(self.verdict, self.words * 64)  # the verdict bit is status == OK, zero past n
+        assert np.array_equal(bits[:self.n], (self.st == OK).astype(np.uint8)) and not bits[self.n:].any()
+        return self.st.copy()
+
+
+def gpu_sign(engine, schemes, seeds, msgs):
+    """cordahip_ecdsa_sign_device: (keys [n, 65], DER sigs as a list of bytes); d = SHA-256(seed) mod n,
+    so lanes that share a seed and a scheme share a key. msgs: [n, L] uint8, L > 0."""
+    import torch
+    dev = torch.device("cuda:0")
+    n = len(schemes)
+    up = lambda a, dt=np.uint8: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
+    keys = torch.zeros((n, 65), dtype=torch.uint8, device=dev)
+    sigs = torch.zeros((n, 72), dtype=torch.uint8, device=dev)
+    kl, sl = (torch.zeros(n, dtype=torch.uint8, device=dev) for _ in range(2))
+    engine.ecdsa_sign_device(up(schemes), up(np.frombuffer(b"".join(seeds), np.uint8).reshape(n, 32)), up(msgs), keys, kl,
+                             sigs, sl, stream=torch.cuda.current_stream())
+    torch.cuda.synchronize()
+    s, l = sigs.cpu().numpy(), sl.cpu().numpy()
+    assert (kl.cpu().numpy() == 65).all()
+    return keys.cpu().numpy(), [s[i, :l[i]].tobytes() for i in range(n)]
+
+
+def oracle_batch(oracle, schemes, pubs, sigs, msgs):
+    """oracle_ecdsa_verify_batch (doVerify rules) over lists of bytes."""
+    n = len(pubs)
+    off = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.uint64)  # noqa: E731
+    buf = lambda xs: np.frombuffer(b"".join(xs) or b"\0", np.uint8).copy()  # noqa: E731
+    sc = np.asarray(schemes, np.uint8)
+    kb, ko, sb, so, mb, mo = buf(pubs), off(pubs), buf(sigs), off(sigs), buf(msgs), off(msgs)
+    want = np.zeros(n, np.uint8)
+    oracle.oracle_ecdsa_verify_batch(n, sc.ctypes.data, kb.ctypes.data, ko.ctypes.data, sb.ctypes.data, so.ctypes.data,
+                                     mb.ctypes.data, mo.ctypes.data, want.ctypes.data, 8)
+    return want
+
+
+SCHEMES5 = [3, 3, 3, 2, 2]
+
+
+@pytest.fixture(scope="module")
+def ec5(engine):
+    """Five ECDSA keys registered on the session engine, 3 P-256 and 2 secp256k1, one of each curve in
+    compressed form: ([ids], [seeds], [key bytes as registered])."""
+    seeds = [hashlib.sha256(b"ec-vkey-seed-%d" % i).digest() for i in range(5)]
+    keys, _ = gpu_sign(engine, SCHEMES5, seeds, np.zeros((5, 32), np.uint8))
+    pubs = [keys[i].tobytes() for i in range(5)]
+    pubs[1], pubs[4] = bc.compress(pubs[1]), bc.compress(pubs[4])
+    ids = []
+    for sch, p in zip(SCHEMES5, pubs):
+        kid, st = engine.vkey_add_ecdsa(sch, p)
+        assert st == OK and kid != NO_ID
+        ids.append(kid)
+    assert len(set(ids)) == 5
+    yield ids, seeds, pubs
+    for kid in ids:
+        engine.vkey_remove(kid)
+
+
+# ---- 1. golden vectors through the host call -------------------------------------------------
+def test_golden_vectors_host_call(ec_vectors, cert_vectors, oracle):
+    from corda_amd.engine import Engine
+    assert len(ec_vectors) == 832
+    by_key = collections.defaultdict(list)
+    for v in ec_vectors:
+        by_key[(v["scheme"], v["pub"])].append(v)
+    keys = list(by_key)
+    assert len(keys) == 280
+    all_ids, left_out = set(), 0
+    ran = collections.Counter()
+    with Engine(1) as eng:
+        for g in range(0, len(keys), _lib.VKEY_MAX_KEYS):
+            group = keys[g:g + _lib.VKEY_MAX_KEYS]
+            ids = {}
+            for k in group:
+                kid, st = eng.vkey_add_ecdsa(k[0], k[1])
+                if st == BAD_KEY:  # left out only if every vector of the key says so
+                    assert kid == NO_ID and all(v["status"] == BAD_KEY for v in by_key[k]), k[1].hex()
+                    left_out += len(by_key[k])
+                    continue
+                assert st == OK and kid not in all_ids
+                all_ids.add(kid)
+                ids[k] = kid
+            lanes = [v for k in group if k in ids for v in by_key[k]]
+            lane_ids = [ids[(v["scheme"], v["pub"])] for v in lanes]
+            sigs, msgs = [v["sig"] for v in lanes], [v["msg"] for v in lanes]
+            got = HostBatch(lane_ids, sigs, msgs).run(eng)
+            wrong = [(v["cat"], v["note"], int(s), v["status"]) for v, s in zip(lanes, got) if s != v["status"]]
+            assert not wrong, wrong[:10]
+            got_iv = HostBatch(lane_ids, sigs, msgs, flags=_lib.FLAG_IS_VALID).run(eng)
+            want_iv = [oracle.oracle_ecdsa_is_valid(v["scheme"], v["pub"], len(v["pub"]), v["sig"], len(v["sig"]),
+                                                    v["msg"], len(v["msg"])) for v in lanes]
+            wrong = [(v["cat"], v["note"], int(s), w) for v, s, w in zip(lanes, got_iv, want_iv) if s != w]
+            assert not wrong, wrong[:10]
+            for v in lanes:
+                ran[v["cat"]] += 1
+            for kid in ids.values():  # the next group takes these slots under new ids
+                eng.vkey_remove(kid)
+        assert left_out == 94 and sum(ran.values()) == 738
+        total = collections.Counter(v["cat"] for v in ec_vectors)
+        for cat in total:
+            if cat.startswith(("der_", "r_", "s_")) or cat in ("high_s", "x_ge_n", "valid_compressed", "empty"):
+                assert ran[cat] == total[cat] > 0, cat
+        assert max(len(v["sig"]) for v in ec_vectors) > 72  # the host's DER decision on long signatures ran
+
+        # the reference's own certificates: every issuer key registered, all 66 lanes in one call
+        assert len(cert_vectors) == 66
+        ids = {}
+        for v in cert_vectors:
+            k = (v["scheme"], v["pub"])
+            if k not in ids:
+                kid, st = eng.vkey_add_ecdsa(*k)
+                assert (st == BAD_KEY) == (v["status"] == BAD_KEY) and (kid == NO_ID) == (st == BAD_KEY)
+                ids[k] = kid
+        got = HostBatch([ids[(v["scheme"], v["pub"])] for v in cert_vectors], [v["sig"] for v in cert_vectors],
+                        [v["msg"] for v in cert_vectors]).run(eng)
+        # a certificate whose key is not a point has no id: its recorded BAD_KEY was the add's answer
+        want = [UNKNOWN if v["status"] == BAD_KEY else v["status"] for v in cert_vectors]
+        wrong = [(v["cat"], int(s), w) for v, s, w in zip(cert_vectors, got, want) if s != w]
+        assert not wrong, wrong
+        assert (got == OK).sum() == 12 and (got == UNKNOWN).sum() == 6
+
+
+# ---- 2. seeded corruption against the oracle and the generic path -----------------------------
+KINDS = ["bit_flip", "other_key_id", "n_minus_s", "s_random"]
+
+
+def test_seeded_corruption_matches_oracle_and_generic_path(engine, oracle, ec5):
+    import torch
+    ids, seeds, pubs = ec5
+    n = 4096
+    rng = np.random.default_rng(20261020)
+    msgs_np = np.frombuffer(b"".join(hashlib.sha256(b"ec-vkey-lane-%d" % i).digest() for i in range(n)),
+                            np.uint8).reshape(n, 32)
+    _, sigs = gpu_sign(engine, [SCHEMES5[i % 5] for i in range(n)], [seeds[i % 5] for i in range(n)], msgs_np)
+    lane_key, kind = [], []
+    for i in range(n):
+        k, use, kd = i % 5, i % 5, None
+        if i % 4 == 3:
+            kd = KINDS[(i // 4) % 4]
+            nn = bc.CURVES[SCHEMES5[k]].n
+            if kd == "bit_flip":
+                s = bytearray(sigs[i])
+                bit = int(rng.integers(0, 8 * len(s)))
+                s[bit >> 3] ^= 1 << (bit & 7)
+                sigs[i] = bytes(s)
+            elif kd == "other_key_id":
+                use = (k + 1 + int(rng.integers(0, 4))) % 5
+            elif kd == "n_minus_s":
+                r, s = bc.der_decode(sigs[i])
+                sigs[i] = bc.der_encode(r, nn - s)
+            else:
+                r, _ = bc.der_decode(sigs[i])
+                sigs[i] = bc.der_encode(r, 1 + int.from_bytes(rng.bytes(32), "big") % (nn - 1))
+        lane_key.append(use)
+        kind.append(kd)
+    msgs = [msgs_np[i].tobytes() for i in range(n)]
+    lane_sch = [SCHEMES5[k] for k in lane_key]
+    lane_pub = [pubs[k] for k in lane_key]
+    want = oracle_batch(oracle, lane_sch, lane_pub, sigs, msgs)
+    got = HostBatch([ids[k] for k in lane_key], sigs, msgs).run(engine)
+    bad = np.nonzero(got != want)[0]
+    assert not len(bad), [(int(i), kind[i], int(got[i]), int(want[i])) for i in bad[:10]]
+    # the generic dense call on the same lanes, with the keys' bytes
+    dev = torch.device("cuda:0")
+    K, S = np.zeros((n, 65), np.uint8), np.zeros((n, 72), np.uint8)
+    for i in range(n):
+        assert len(sigs[i]) <= 72
+        K[i, :len(lane_pub[i])] = np.frombuffer(lane_pub[i], np.uint8)
+        S[i, :len(sigs[i])] = np.frombuffer(sigs[i], np.uint8)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)  # noqa: E731
+    t_st = torch.full((n,), 0xA5, dtype=torch.uint8, device=dev)
+    engine.ecdsa_verify_device(up(lane_sch), up(K), up([len(p) for p in lane_pub]), up(S), up([len(s) for s in sigs]),
+                               up(msgs_np), t_st, None, stream=torch.cuda.current_stream())
+    torch.cuda.synchronize()
+    assert np.array_equal(t_st.cpu().numpy(), got)
+    assert all(got[i] == OK for i in range(n) if kind[i] in (None, "n_minus_s"))  # BC has no low-s rule
+    for kd in ("bit_flip", "other_key_id", "s_random"):
+        st = {int(want[i]) for i in range(n) if kind[i] == kd}
+        assert BAD_SIG in st, kd
+    assert MALFORMED_SIG in {int(want[i]) for i in range(n) if kind[i] == "bit_flip"}
+
+
+# ---- 3. the branches a table sum has and a ladder hardly ever reaches ----------------------------
+FIXED_SCALARS = ["1", "n-1", "2^255-1", "2^255", "2^255+1", "0x80..", "0x81..", "0xff.."]
+
+
+def mul_g(scheme, d):
+    """[d]G as a sum over the model's table of G (tests/test_ec_vkey_model.py checks that table), SEC1."""
+    x, y = model.trace(scheme, None, d, 0)[0]
+    return b"\x04" + x.to_bytes(32, "big") + y.to_bytes(32, "big")
+
+
+def fixed_scalars(n):
+    return [1, n - 1, (1 << 255) - 1, 1 << 255, (1 << 255) + 1, int.from_bytes(b"\x80" * 32, "big") % n,
+            int.from_bytes(b"\x81" * 32, "big") % n, int.from_bytes(b"\xff" * 32, "big") % n]
+
+
+def test_exceptional_branches_and_chosen_scalars(oracle):
+    from corda_amd.engine import Engine
+    lanes = []  # (scheme, key bytes, sig, msg, what)
+    need = {"dbl": 8, "inf": 8, "zero": 8}
+    found = {}
+    for scheme, c in bc.CURVES.items():
+        n = c.n
+        # u1 + d u2 = k for every valid lane, so the sum's partial results follow the top digits of k:
+        # it can pass through infinity only where those are zero. A nonce with a zero top byte makes
+        # the lanes meet the inverse of an entry at position 31 and, rarely, an equal entry below it.
+        k = (int.from_bytes(hashlib.sha256(b"ec-vkey-nonce-%d" % scheme).digest(), "big") >> 8) % n
+        r = bc._mul(c, k, c.G)[0] % n
+        kinv = pow(k, -1, n)
+        pub = {d: mul_g(scheme, d) for d in (1, n - 1)}
+        assert pub[1] == bc.keypair(scheme, 1) and pub[n - 1][1:33] == pub[1][1:33] and pub[n - 1] != pub[1]
+        qtab = {d: model.point_table(c, bc.decode_point(c, pub[d])) for d in (1, n - 1)}
+        have = collections.Counter()
+        i = 0
+        while any(have[e] < need[e] for e in need):
+            assert i < 60000, have  # about 0.4 % of the messages take each branch
+            d = (1, n - 1)[i & 1]
+            msg = hashlib.sha256(b"ec-vkey-branch-%d-%d" % (scheme, i)).digest()
+            i += 1
+            e = int.from_bytes(hashlib.sha256(msg).digest(), "big") % n
+            s = kinv * (e + r * d) % n
+            if s == 0:
+                continue
+            w = pow(s, -1, n)
+            _, ev = model.scalar_trace(n, d, e * w % n, r * w % n)  # the search: modular arithmetic alone
+            hit = [x for x in ("dbl", "inf", "zero") if ev[x] and have[x] < need[x]]
+            if not hit:
+                continue
+            assert bc.sign(scheme, d, msg, k) == (r, s)
+            sig = bc.der_encode(r, s)
+            pt, pev = model.trace(scheme, qtab[d], e * w % n, r * w % n)  # the condition, through the point model
+            assert pev == ev and pt is not None and pt[0] % n == r
+            for x in ("dbl", "inf", "zero"):
+                have[x] += bool(pev[x])
+            lanes.append((scheme, pub[d], sig, msg, "search " + "+".join(hit)))
+        found[scheme] = dict(have)
+        assert all(have[x] >= 8 for x in need), have
+        # chosen u1, and by the mirrored recipe chosen u2: P = [u1]G + [u2][d]G = [k]G
+        for name, u in zip(FIXED_SCALARS, fixed_scalars(n)):
+            for which in (1, 2):
+                msg = hashlib.sha256(b"ec-vkey-chosen-%d-%s-%d" % (scheme, name.encode(), which)).digest()
+                e = int.from_bytes(hashlib.sha256(msg).digest(), "big") % n
+                if which == 1:
+                    u1 = u
+                    s = e * pow(u1, -1, n) % n
+                    u2 = r * pow(s, -1, n) % n
+                else:
+                    u2 = u
+                    s = r * pow(u2, -1, n) % n
+                    u1 = e * pow(s, -1, n) % n
+                d = (k - u1) * pow(u2, -1, n) % n
+                assert d and s and (u1, u2)[which - 1] == u
+                lanes.append((scheme, mul_g(scheme, d), bc.der_encode(r, s), msg, "u%d = %s" % (which, name)))
+    want = oracle_batch(oracle, [x[0] for x in lanes], [x[1] for x in lanes], [x[2] for x in lanes], [x[3] for x in lanes])
+    assert (want == OK).all(), [lanes[i][4] for i in np.nonzero(want != OK)[0]]
+    keys = list(dict.fromkeys((x[0], x[1]) for x in lanes))
+    assert len(keys) == 2 * (2 + 16) <= _lib.VKEY_MAX_KEYS
+    with Engine(1) as eng:
+        ids = {}
+        for k in keys:
+            ids[k], st = eng.vkey_add_ecdsa(*k)
+            assert st == OK
+        got = HostBatch([ids[(x[0], x[1])] for x in lanes], [x[2] for x in lanes], [x[3] for x in lanes]).run(eng)
+        wrong = [(x[0], x[4], int(g)) for x, g in zip(lanes, got) if g != OK]
+        assert not wrong, (wrong[:10], found)
+        # and a lane that passes through infinity and ends there is BAD_SIG, not OK: Q = -G, u1 = u2
+        # cannot be signed (P = O); a flipped message on every lane above must reject
+        got = HostBatch([ids[(x[0], x[1])] for x in lanes], [x[2] for x in lanes],
+                        [bytes([x[3][0] ^ 1]) + x[3][1:] for x in lanes]).run(eng)
+        assert (got == BAD_SIG).all()
+
+
+# ---- 4. the device call ----------------------------------------------------------------------
+@pytest.mark.parametrize("msg_len", [32, 200, 0])
+def test_device_call_partial_wave_and_unknown_ids(engine, oracle, ec5, msg_len):
+    import torch
+    ids, seeds, pubs = ec5
+    n = 2085  # not a multiple of 64 or 256: a partial last wave and a partial verdict word
+    words = (n + 63) // 64
+    removed, st = engine.vkey_add_ecdsa(SCHEMES5[0], pubs[0])
+    assert st == OK
+    engine.vkey_remove(removed)
+    ed_pub = ctypes.create_string_buffer(32)
+    oracle.oracle_ed25519_keypair(hashlib.sha256(b"ec-vkey-ed").digest(), ed_pub)
+    ed_id, st = engine.vkey_add_ed25519(ed_pub.raw)
+    assert st == OK
+    never = (removed & 63) | (0x155555 << 6)
+    unknown_ids = {7: never, 64: NO_ID, 1000: removed, 1500: ed_id, n - 1: never}
+    lane_k = [(i * 7 + i // 64) % 5 for i in range(n)]  # both curves inside every wave
+    if msg_len:
+        msgs_np = np.frombuffer(b"".join((hashlib.sha512(b"ec-vkey-dev-%d" % i).digest() * 4)[:msg_len] for i in range(n)),
+                                np.uint8).reshape(n, msg_len)
+        _, sigs = gpu_sign(engine, [SCHEMES5[k] for k in lane_k], [seeds[k] for k in lane_k], msgs_np)
+    else:
+        msgs_np = np.zeros((n, 0), np.uint8)
+        sigs = [bc.der_encode(5 + i, 7 + i) for i in range(n)]
+    for i in range(3, n, 7):
+        s = bytearray(sigs[i])
+        s[i % len(s)] ^= 1 << (i % 8)
+        sigs[i] = bytes(s)
+    sig_len = [len(s) for s in sigs]
+    sigs[20], sig_len[20] = b"", 0
+    sig_len[33] = 73  # longer than the slot: MALFORMED_SIG (EMPTY first when the message is empty)
+    msgs = [msgs_np[i].tobytes() for i in range(n)]
+    try:
+        want = oracle_batch(oracle, [SCHEMES5[k] for k in lane_k], [pubs[k] for k in lane_k], sigs, msgs)
+        want[33] = MALFORMED_SIG if msg_len else EMPTY
+        for i in unknown_ids:
+            want[i] = UNKNOWN
+        if msg_len == 0:
+            assert all(want[i] == EMPTY for i in range(n) if i not in unknown_ids)
+        else:
+            assert want[20] == EMPTY and (want == OK).sum() > n // 2 and (want == BAD_SIG).sum() > n // 20
+        dev = torch.device("cuda:0")
+        stream = torch.cuda.Stream(device=dev)
+        pad = 100
+        S = np.zeros((n, 72), np.uint8)
+        for i in range(n):
+            S[i, :len(sigs[i])] = np.frombuffer(sigs[i], np.uint8)
+        lane_id = [unknown_ids.get(i, ids[lane_k[i]]) for i in range(n)]
+        with torch.cuda.stream(stream):
+            t_ids = torch.from_numpy(np.asarray(lane_id, np.uint32).view(np.int32).copy()).to(dev)
+            t_sig = torch.from_numpy(S).to(dev)
+            t_sl = torch.from_numpy(np.asarray(sig_len, np.uint8)).to(dev)
+            t_msg = torch.from_numpy(msgs_np.copy()).to(dev) if msg_len else \
+                torch.empty((n, 0), dtype=torch.uint8, device=dev)
+            t_st = torch.full((pad + n + pad,), 0xA5, dtype=torch.uint8, device=dev)
+            t_vd = torch.full((2 + words + 2,), -0x5A5A5A5A5A5A5A5B, dtype=torch.int64, device=dev)
+            engine.ecdsa_verify_keyed_device(t_ids, t_sig, t_sl, t_msg, t_st[pad:pad + n], t_vd[2:2 + words],
+                                             stream=stream)
+        stream.synchronize()
+    finally:
+        engine.vkey_remove(ed_id)
+    st_all, vd_all = t_st.cpu().numpy(), t_vd.cpu().numpy().view(np.uint64)
+    assert (st_all[:pad] == 0xA5).all() and (st_all[pad + n:] == 0xA5).all()  # guards, and the rows after n
+    assert (vd_all[:2] == 0xA5A5A5A5A5A5A5A5).all() and (vd_all[2 + words:] == 0xA5A5A5A5A5A5A5A5).all()
+    got = st_all[pad:pad + n]
+    bad = np.nonzero(got != want)[0]
+    assert not len(bad), [(int(i), int(got[i]), int(want[i])) for i in bad[:10]]
+    bits = verdict_bits(vd_all[2:2 + words], words * 64)
+    assert np.array_equal(bits[:n], (want == OK).astype(np.uint8)) and not bits[n:].any()
+
+
+# ---- 5. registry lifecycle across the two families ----------------------------------------------
+def test_registry_lifecycle_across_families(oracle):
+    from corda_amd.engine import Engine
+    msg = hashlib.sha256(b"ec-vkey-life-msg").digest()
+    ed_seed = hashlib.sha256(b"ec-vkey-life-ed").digest()
+    ed_pub, ed_sig = ctypes.create_string_buffer(32), ctypes.create_string_buffer(64)
+    oracle.oracle_ed25519_sign(ed_seed, msg, 32, ed_pub, ed_sig)
+    ed_pub, ed_sig = ed_pub.raw, ed_sig.raw
+
+    def mem(e):
+        u = ctypes.c_uint64()
+        assert lib().cordahip_device_mem(e.ctx, 0, ctypes.byref(u), None, None) == 0
+        return u.value
+
+    with Engine(1) as e:
+        seeds = [hashlib.sha256(b"ec-vkey-life-%d" % i).digest() for i in range(2)]
+        keys, sigs = gpu_sign(e, [3, 2], seeds, np.frombuffer(msg * 2, np.uint8).reshape(2, 32))
+        pubs = [keys[i].tobytes() for i in range(2)]
+        # no ECDSA key yet: every id is unknown, and nothing is allocated for them
+        assert HostBatch([0, 64], [sigs[0]] * 2, [msg] * 2).run(e).tolist() == [UNKNOWN] * 2
+        ed_a, st = e.vkey_add_ed25519(ed_pub)
+        assert st == OK
+        assert lib().cordahip_trim(e.ctx) == 0
+        before = mem(e)
+        a, st = e.vkey_add_ecdsa(3, pubs[0])
+        assert st == OK and (a & 63) != (ed_a & 63)
+        assert mem(e) - before == EC_VKEY_BYTES  # the tables appear with the first ECDSA add ...
+        assert HostBatch([a], [sigs[0]], [msg]).run(e).tolist() == [OK]
+        assert lib().cordahip_trim(e.ctx) == 0
+        assert mem(e) - before == EC_VKEY_BYTES  # ... and survive trim
+        assert HostBatch([a], [sigs[0]], [msg]).run(e).tolist() == [OK]
+        # an id of the other family names no key of this one, in both directions
+        assert HostBatch([ed_a, a], [sigs[0]] * 2, [msg] * 2).run(e).tolist() == [UNKNOWN, OK]
+        assert HostBatch([a, ed_a], [ed_sig] * 2, [msg] * 2).run(e, "cordahip_verify_keyed").tolist() == [UNKNOWN, OK]
+        # a scheme that is not ECDSA is an argument error; bytes that are no key are data
+        kid_c, kst = ctypes.c_uint32(), ctypes.c_uint8()
+        assert lib().cordahip_vkey_add_ecdsa(e.ctx, 4, pubs[0], 65, ctypes.byref(kid_c), ctypes.byref(kst)) == \
+            _lib.ERR_INVALID_ARG
+        assert e.vkey_add_ecdsa(2, pubs[0]) == (NO_ID, BAD_KEY)  # a P-256 point is not on secp256k1
+        assert e.vkey_add_ecdsa(3, pubs[0][:64]) == (NO_ID, BAD_KEY)
+        assert e.vkey_add_ecdsa(3, b"\x06" + pubs[0][1:]) == (NO_ID, BAD_KEY)  # hybrid
+        assert e.vkey_add_ecdsa(3, b"\x00") == (NO_ID, BAD_KEY)  # infinity
+        # remove, then the slot under a new id and the other curve: the old id stays unknown
+        e.vkey_remove(a)
+        assert lib().cordahip_vkey_remove(e.ctx, a) == _lib.ERR_INVALID_ARG
+        b, st = e.vkey_add_ecdsa(2, bc.compress(pubs[1]))
+        assert st == OK and b != a and (b & 63) == (a & 63)
+        assert HostBatch([a, b, b], [sigs[0], sigs[1], sigs[0]], [msg] * 3).run(e).tolist() == [UNKNOWN, OK, BAD_SIG]
+        # an Ed25519 key into a slot an ECDSA key held, and back
+        e.vkey_remove(b)
+        ed_b, st = e.vkey_add_ed25519(ed_pub)
+        assert st == OK and (ed_b & 63) == (b & 63)
+        assert HostBatch([b, ed_b], [sigs[1]] * 2, [msg] * 2).run(e).tolist() == [UNKNOWN] * 2
+        assert HostBatch([ed_b, b], [ed_sig] * 2, [msg] * 2).run(e, "cordahip_verify_keyed").tolist() == [OK, UNKNOWN]
+        # fill the pool with both families: the 65th key of either is refused
+        live, ec_live = [ed_a, ed_b], []
+        while len(live) < _lib.VKEY_MAX_KEYS:
+            i = len(live)
+            if i % 2:
+                sch = 3 if i % 4 == 1 else 2
+                kid, st = e.vkey_add_ecdsa(sch, pubs[0] if sch == 3 else pubs[1])
+                ec_live.append((kid, sch))
+            else:
+                kid, st = e.vkey_add_ed25519(ed_pub)
+            assert st == OK
+            live.append(kid)
+        assert len(set(live)) == _lib.VKEY_MAX_KEYS and len(ec_live) == 31
+        assert lib().cordahip_vkey_add_ecdsa(e.ctx, 3, pubs[0], 65, ctypes.byref(kid_c), ctypes.byref(kst)) == \
+            _lib.ERR_OUT_OF_MEMORY
+        assert lib().cordahip_vkey_add_ed25519(e.ctx, ed_pub, ctypes.byref(kid_c), ctypes.byref(kst)) == \
+            _lib.ERR_OUT_OF_MEMORY
+        # every ECDSA key of the full pool answers: the P-256 signature verifies under the P-256 keys alone
+        want = [OK if sch == 3 else BAD_SIG for _, sch in ec_live]
+        got = HostBatch([k for k, _ in ec_live], [sigs[0]] * len(ec_live), [msg] * len(ec_live)).run(e)
+        assert got.tolist() == want and OK in want and BAD_SIG in want
+        e.vkey_remove(live.pop())
+        kid, st = e.vkey_add_ecdsa(2, pubs[1])  # the freed slot is there again, for either family
+        assert st == OK
+
+
+# ---- 6. host-call plumbing ---------------------------------------------------------------------
+def test_bad_csr_is_invalid_arg_and_leaves_outputs(engine, ec5):
+    ids, seeds, _ = ec5
+    n = 70
+    msgs_np = np.frombuffer(b"".join(hashlib.sha256(b"ec-vkey-csr-%d" % i).digest() for i in range(n)),
+                            np.uint8).reshape(n, 32)
+    _, sigs = gpu_sign(engine, [SCHEMES5[i % 5] for i in range(n)], [seeds[i % 5] for i in range(n)], msgs_np)
+    msgs = [msgs_np[i].tobytes() for i in range(n)]
+    lane_id = [ids[i % 5] for i in range(n)]
+
+    def decreasing(off):
+        o = off.copy()
+        o[30] = o[31] + 1
+        return o
+
+    def past_end(off):
+        o = off.copy()
+        o[n] += 1
+        return o
+
+    for which, mutate in [("soff", decreasing), ("soff", past_end), ("moff", decreasing), ("moff", past_end)]:
+        hb = HostBatch(lane_id, sigs, msgs)
+        bad = mutate(getattr(hb, which))
+        rc = lib().cordahip_ecdsa_verify_keyed(engine.ctx, ctypes.byref(hb.batch(**{which: bad})))
+        assert rc == _lib.ERR_INVALID_ARG, (which, mutate.__name__)
+        assert hb.untouched(), (which, mutate.__name__)
+        t = ctypes.c_uint64()
+        assert lib().cordahip_ecdsa_verify_keyed_submit(engine.ctx, ctypes.byref(hb.batch(**{which: bad})),
+                                                        ctypes.byref(t)) == 0
+        assert lib().cordahip_wait(engine.ctx, t.value, -1) == _lib.ERR_INVALID_ARG and hb.untouched()
+        assert not HostBatch(lane_id, sigs, msgs).run(engine).any()  # the context is still usable
+    hb = HostBatch(lane_id, sigs, msgs, flags=4)  # an unknown flag
+    assert lib().cordahip_ecdsa_verify_keyed(engine.ctx, ctypes.byref(hb.batch())) == _lib.ERR_INVALID_ARG
+    assert hb.untouched()
+
+
+def test_two_tickets_waited_in_reverse(engine, oracle, ec5):
+    ids, seeds, pubs = ec5
+    batches = []
+    for b, n in enumerate((300, 131)):
+        L = 32 - 5 * b
+        msgs_np = np.frombuffer(b"".join(hashlib.sha256(b"ec-vkey-ticket-%d-%d" % (b, i)).digest()[:L] for i in range(n)),
+                                np.uint8).reshape(n, L)
+        lane_k = [(i + b) % 5 for i in range(n)]
+        _, sigs = gpu_sign(engine, [SCHEMES5[k] for k in lane_k], [seeds[k] for k in lane_k], msgs_np)
+        msgs = [msgs_np[i].tobytes() for i in range(n)]
+        for i in range(b, n, 3):
+            msgs[i] = bytes([msgs[i][0] ^ 4]) + msgs[i][1:]
+        want = oracle_batch(oracle, [SCHEMES5[k] for k in lane_k], [pubs[k] for k in lane_k], sigs, msgs)
+        assert (want == OK).any() and (want == BAD_SIG).any()
+        batches.append(([ids[k] for k in lane_k], sigs, msgs, want))
+    tickets = [engine.ecdsa_verify_keyed_batch(x[0], x[1], x[2], submit=True) for x in batches]
+    for t, x in reversed(list(zip(tickets, batches))):
+        st, vd = t.wait()
+        assert np.array_equal(st, x[3])
+        assert np.array_equal(verdict_bits(vd, len(st)), (x[3] == OK).astype(np.uint8))
+
+
+def test_validate_notary_signatures_ecdsa(engine, ec5):
+    from corda_amd import resolve
+    ids, seeds, _ = ec5
+    n = 64
+    tx_np = np.frombuffer(b"".join(hashlib.sha256(b"ec-vkey-notary-%d" % i).digest() for i in range(n)),
+                          np.uint8).reshape(n, 32)
+    txids = [tx_np[i].tobytes() for i in range(n)]
+    _, sigs = gpu_sign(engine, [SCHEMES5[0]] * n, [seeds[0]] * n, tx_np)
+    _, other = gpu_sign(engine, [SCHEMES5[1]] * n, [seeds[1]] * n, tx_np)
+    sigs[17] = other[17]    # signed by another key
+    sigs[40] = sigs[40][:-1]  # truncated
+    out = resolve.validate_notary_signatures(engine, ids[0], txids, sigs, ecdsa=True)
+    assert len(out) == n
+    assert all(o is None for i, o in enumerate(out) if i not in (17, 40))
+    assert isinstance(out[17], resolve.SignatureException) and "Verification failed" in str(out[17])
+    assert isinstance(out[40], resolve.SignatureException) and "decoding" in str(out[40])
+    # without the keyword the id is looked up among the Ed25519 keys: it names none
+    out = resolve.validate_notary_signatures(engine, ids[0], txids[:3], sigs[:3])
+    assert all(isinstance(o, resolve.NoSuchElementException) for o in out)
+    assert resolve.validate_notary_signatures(engine, ids[0], [], [], ecdsa=True) == []
+
+
+def test_three_device_replicas_and_chunks(oracle, monkeypatch):
+    """The shard split (whole verdict words per device), the chunk loop and the per-device key tables
+    on a context of three Device objects (CORDAHIP_TEST_DEVICE_REPLICAS, read by cordahip_init): every
+    replica holds the same tables; add and remove reach all of them."""
+    import torch
+    from corda_amd.engine import Engine
+    monkeypatch.setenv("CORDAHIP_TEST_DEVICE_REPLICAS", "3")
+    monkeypatch.setenv("CORDAHIP_HOST_CHUNK", "64")
+    seeds = [hashlib.sha256(b"ec-vkey-replica-%d" % i).digest() for i in range(3)]
+    sch3 = [3, 2, 3]
+    with Engine(1) as eng:
+        assert eng.device_count() == 3
+        n = 300  # shards of 128, 128 and 44 lanes, chunks of 64
+        msgs_np = np.frombuffer(b"".join(hashlib.sha256(b"ec-vkey-replica-msg-%d" % i).digest() for i in range(n)),
+                                np.uint8).reshape(n, 32)
+        keys, sigs = gpu_sign(eng, [sch3[i % 3] for i in range(n)], [seeds[i % 3] for i in range(n)], msgs_np)
+        pubs = [keys[i].tobytes() for i in range(3)]
+        ids = []
+        for sch, p in zip(sch3, pubs):
+            kid, st = eng.vkey_add_ecdsa(sch, p)
+            assert st == OK
+            ids.append(kid)
+        # dense chunks, then CSR chunks (a message cut short no longer verifies: BAD_SIG either way)
+        msgs = [msgs_np[i].tobytes() if i < 150 else msgs_np[i].tobytes()[:1 + i % 31] for i in range(n)]
+        for i in range(0, n, 5):
+            s = bytearray(sigs[i])
+            s[-1 - i % 20] ^= 0x10
+            sigs[i] = bytes(s)
+        want = oracle_batch(oracle, [sch3[i % 3] for i in range(n)], [pubs[i % 3] for i in range(n)], sigs, msgs)
+        assert (want[:150] == OK).sum() == 120 and (want != OK).sum() >= 150 + 30 - 5
+        lane_ids = [ids[i % 3] for i in range(n)]
+        assert np.array_equal(HostBatch(lane_ids, sigs, msgs).run(eng), want)
+        eng.vkey_remove(ids[1])
+        got = HostBatch(lane_ids, sigs, msgs).run(eng)
+        assert np.array_equal(got, np.where(np.arange(n) % 3 == 1, UNKNOWN, want))
+        dev = torch.device("cuda:0")
+        S = np.zeros((6, 72), np.uint8)
+        for i in range(6):
+            S[i, :len(sigs[i])] = np.frombuffer(sigs[i], np.uint8)
+        for d in range(3):  # every replica's own tables through the device call
+            t_ids = torch.from_numpy(np.asarray(lane_ids[:6], np.uint32).view(np.int32).copy()).to(dev)
+            t_sig = torch.from_numpy(S).to(dev)
+            t_sl = torch.from_numpy(np.asarray([len(s) for s in sigs[:6]], np.uint8)).to(dev)
+            t_msg = torch.from_numpy(msgs_np[:6].copy()).to(dev)
+            t_st = torch.full((6,), 0xA5, dtype=torch.uint8, device=dev)
+            eng.ecdsa_verify_keyed_device(t_ids, t_sig, t_sl, t_msg, t_st, None, device=d,
+                                          stream=torch.cuda.current_stream())
+            torch.cuda.synchronize()
+            assert np.array_equal(t_st.cpu().numpy(), got[:6]), d

@@ -178,6 +178,8 @@ int main() {
     visited(sk, 0, "SignKeys");
     VerifyKeys vk;
     visited(vk, 0, "VerifyKeys");
+    EcVerifyKeys ek;
+    visited(ek, 0, "EcVerifyKeys");
     visited(tw, 0, "TxWork");
     visited(ss, 0, "StreamStage");
     visited(ps, kPackPlain, "PackStage");
@@ -194,8 +196,9 @@ int main() {
     // s_ec2 (an alias), the encoder's flags and counters; the signer's two mutexes and its
     // key table, which has a visit of its own (f)
     // and the verification keys' two mutexes and tables, visited with the signer's (f)
-    constexpr size_t kDeviceOwnPlain =
-        1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys) + 2 * sizeof(std::mutex) + sizeof(VerifyKeys);
+    // and the registered ECDSA keys' tables and what the host knows of them (f)
+    constexpr size_t kDeviceOwnPlain = 1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys) + 2 * sizeof(std::mutex) +
+                                       sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + sizeof(EcVkeyState);
     const Count c = visited(*d, kDeviceOwnPlain + kTxSets * kTxSetPlain + kPackStages * kPackPlain, "Device");
     ndev = c.ndev, npin = c.npin, nev = c.nfence + c.nevent;
     CHECK(c.nstream == 7);
@@ -254,16 +257,19 @@ int main() {
     k->visit(gk);
     const size_t before = g.dev.size();
     k->visit_keys(gk);
-    CHECK(g.dev.size() == before + 2 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
+    CHECK(g.dev.size() == before + 3 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
     CHECK(k->vkeys.tab.dev == 6 && k->vkeys.tab.p && k->vkeys.stage.p && k->vkeys.ev.ev);
+    CHECK(k->ec_vkeys.tab.dev == 6 && k->ec_vkeys.tab.p && k->ec_vkeys.stage.p && k->ec_vkeys.ev.ev);
     void *tab = k->keys.tab.p, *stage = k->keys.stage.p, *vtab = k->vkeys.tab.p, *vstage = k->vkeys.stage.p;
+    void *etab = k->ec_vkeys.tab.p, *estage = k->ec_vkeys.stage.p;
     k->release_idle();
     CHECK(k->keys.tab.p == tab && k->keys.stage.p == stage && g.dev.count(tab) && g.pin.count(stage));
     CHECK(k->vkeys.tab.p == vtab && k->vkeys.stage.p == vstage && g.dev.count(vtab) && g.pin.count(vstage));
+    CHECK(k->ec_vkeys.tab.p == etab && k->ec_vkeys.stage.p == estage && g.dev.count(etab) && g.pin.count(estage));
     Kept kk;
     k->visit(kk);  // what the release walks: the same kept buffers as in b
     CHECK(kk.devs.size() == kept.devs.size());
-    CHECK(mem_acct(6).in_use.load() == kk.bytes + k->keys.tab.cap + k->vkeys.tab.cap);
+    CHECK(mem_acct(6).in_use.load() == kk.bytes + k->keys.tab.cap + k->vkeys.tab.cap + k->ec_vkeys.tab.cap);
     delete k;
     CHECK(g.clean() && mem_acct(6).in_use.load() == 0);
   }
