@@ -54,6 +54,16 @@ __global__ void __launch_bounds__(64) ed25519_btable_kernel(uint32_t* __restrict
     if ((k >> bit) & 1) ge_add<true>(P, P, bc);
   }
   store_niels_entry(tab + g * kBEntryWords, P);
+  if (g == 0) {
+    // the joint table's shared identity entry, behind the two tables
+    // (Y + X, Y - X, Z, 2dT) = (1, 1, 1, 0)
+    ge_cached id;
+    fe_set(id.YpX, 1);
+    fe_set(id.YmX, 1);
+    fe_set(id.Z, 1);
+    fe_set(id.T2d, 0);
+    store_cached(tab + kBIdentityWord, id);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -354,17 +364,40 @@ CDEV void load_point(ge_p3& p, const uint32_t* __restrict__ o) {
 
 // The joint table i P + j Q (P = -A, Q = -R affine; ed25519_joint.hpp) is built
 // from doublings and mixed additions only, in two loops of two passes each (one
-// copy of each body in the I-cache), which meet through the record:
+// copy of each body in the I-cache), which meet through the parked points:
 //   single pass (base = P, then Q): [1]base, whose cached form with Z = 1 is
 //     also its niels form, and [2]base;
 //   sign pass (s = -1, then +1): D = P + sQ, 2D = 2P + 2sQ, D + sQ = P + 2sQ,
 //     D + P = 2P + sQ.
 // 4 doublings, 6 mixed additions, 2 + 10 products by 2d: 16 S + 70 M per lane.
-// P and Q are parked (X, Y, T) in the slots of 2P + 2Q and 2P - 2Q: Q's slot
-// is free once the single passes are done, P's is written last.
+// Between the passes P and Q are parked. ED_PREP_LDS: in LDS, word-major, one
+// column of kPqWords per thread (256 threads: 70 KB, two blocks per CU), so no
+// pass waits for a store of its own wave to come back from memory:
+//   P as X, Y, T and, once its single pass has the product, 2dT: (1, 0) as
+//     niels is (Y + X, Y - X, 2dT), two additions away;
+//   Q as X, Y, T until its single pass has read it, then as the niels form of
+//     (0, 1) in the same words (nothing later needs Q itself).
+// Without it: as (X, Y, T) in the record's slots of 2P + 2Q and 2P - 2Q (Q's
+// slot is free once the single passes are done, P's is written last), the
+// niels forms read back from the entries (1, 0) and (0, 1).
+#ifndef ED_PREP_LDS
+#define ED_PREP_LDS 1
+#endif
+#if !ED_PREP_LDS
 static constexpr int kParkP = joint_index(2, 2), kParkQ = joint_index(2, -2);
+#endif
+static constexpr int kPqT2d = 30, kPqQ = 40, kPqWords = 70;  // P: X Y T 2dT at 0 10 20 30; Q: three fe at 40 50 60
 
 CDEV uint32_t* joint_slot(uint32_t* rec, int idx) { return rec + kWhTab + idx * kWhEntryWords; }
+
+CDEV void pq_store(uint32_t* col, int at, const fe& f) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) col[(at + i) * 256] = f.v[i];
+}
+CDEV void pq_load(fe& f, const uint32_t* col, int at) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) f.v[i] = col[(at + i) * 256];
+}
 
 // an entry with Z = 1 read back as the niels form of its point
 CDEV void load_cached_niels(ge_niels& n, const uint32_t* __restrict__ p) {
@@ -375,26 +408,80 @@ CDEV void load_cached_niels(ge_niels& n, const uint32_t* __restrict__ p) {
   n.xy2d = c.T2d;
 }
 
+// the affine point parked by the decode phase: which = 0 is P, 1 is Q
+CDEV void park_point(uint32_t* __restrict__ rec, uint32_t* col, int which, const ge_p3& p) {
+#if ED_PREP_LDS
+  pq_store(col, which * kPqQ, p.X);
+  pq_store(col, which * kPqQ + 10, p.Y);
+  pq_store(col, which * kPqQ + 20, p.T);
+#else
+  store_point(joint_slot(rec, which ? kParkQ : kParkP), p);
+#endif
+}
+CDEV void load_parked(ge_p3& p, uint32_t* __restrict__ rec, const uint32_t* col, int which) {
+#if ED_PREP_LDS
+  pq_load(p.X, col, which * kPqQ);
+  pq_load(p.Y, col, which * kPqQ + 10);
+  pq_load(p.T, col, which * kPqQ + 20);
+  fe_set(p.Z, 1);
+#else
+  load_point(p, joint_slot(rec, which ? kParkQ : kParkP));
+#endif
+}
+// a single pass has the cached form c (Z = 1) of its point: keep what the sign
+// passes need of it
+CDEV void park_niels(uint32_t* col, int pass, const ge_cached& c) {
+#if ED_PREP_LDS
+  if (pass) {
+    pq_store(col, kPqQ, c.YpX);
+    pq_store(col, kPqQ + 10, c.YmX);
+    pq_store(col, kPqQ + 20, c.T2d);
+  } else {
+    pq_store(col, kPqT2d, c.T2d);
+  }
+#endif
+}
+// the niels form of P (which = 0) or Q
+CDEV void load_parked_niels(ge_niels& n, uint32_t* __restrict__ rec, const uint32_t* col, int which) {
+#if ED_PREP_LDS
+  if (which) {
+    pq_load(n.ypx, col, kPqQ);
+    pq_load(n.ymx, col, kPqQ + 10);
+    pq_load(n.xy2d, col, kPqQ + 20);
+  } else {
+    fe x, y;
+    pq_load(x, col, 0);
+    pq_load(y, col, 10);
+    fe_add(n.ypx, y, x);  // as ge_to_cached
+    fe_sub(n.ymx, y, x);
+    pq_load(n.xy2d, col, kPqT2d);
+  }
+#else
+  load_cached_niels(n, joint_slot(rec, which ? joint_index(0, 1) : joint_index(1, 0)));
+#endif
+}
+
 // pass 0: [1]P, [2]P; pass 1: [1]Q, [2]Q
-CDEV void joint_single_pass(uint32_t* __restrict__ rec, int pass) {
+CDEV void joint_single_pass(uint32_t* __restrict__ rec, uint32_t* col, int pass) {
   ge_p3 B, D;
-  load_point(B, joint_slot(rec, pass ? kParkQ : kParkP));
+  load_parked(B, rec, col, pass);
   ge_cached c;
   ge_to_cached(c, B);
+  park_niels(col, pass, c);
   store_cached(joint_slot(rec, pass ? joint_index(0, 1) : joint_index(1, 0)), c);
   ge_dbl<true>(D, B);
   ge_to_cached(c, D);
   store_cached(joint_slot(rec, pass ? joint_index(0, 2) : joint_index(2, 0)), c);
 }
 
-// the four entries that mix P and Q with relative sign s (s = -1 first: the
-// s = +1 pass overwrites P's parking slot with its last store)
-CDEV void joint_sign_pass(uint32_t* __restrict__ rec, int s) {
+// the four entries that mix P and Q with relative sign s (s = -1 first: without
+// ED_PREP_LDS the s = +1 pass overwrites P's parking slot with its last store)
+CDEV void joint_sign_pass(uint32_t* __restrict__ rec, uint32_t* col, int s) {
   ge_p3 D, E;
   ge_niels nq, np;
   ge_cached c;
-  load_point(D, joint_slot(rec, kParkP));
-  load_cached_niels(nq, joint_slot(rec, joint_index(0, 1)));
+  load_parked(D, rec, col, 0);
+  load_parked_niels(nq, rec, col, 1);
   niels_cneg(nq, s < 0);
   ge_madd<true>(D, D, nq);  // P + sQ
   ge_to_cached(c, D);
@@ -402,7 +489,10 @@ CDEV void joint_sign_pass(uint32_t* __restrict__ rec, int s) {
   ge_madd<true>(E, D, nq);  // P + 2sQ
   ge_to_cached(c, E);
   store_cached(joint_slot(rec, joint_index(1, 2 * s)), c);
-  load_cached_niels(np, joint_slot(rec, joint_index(1, 0)));
+#if ED_PREP_LDS
+  PHASE_BARRIER();  // nothing orders the LDS reads of np behind the stores above: keep them here
+#endif
+  load_parked_niels(np, rec, col, 0);
   ge_madd<true>(E, D, np);  // 2P + sQ
   ge_to_cached(c, E);
   store_cached(joint_slot(rec, joint_index(2, s)), c);
@@ -428,10 +518,10 @@ CDEV void joint_sign_pass(uint32_t* __restrict__ rec, int s) {
 // decode A and R, the pre-engine statuses | the joint table i(-A) + j(-R).
 // Returns the lane's status (kStatusPending: verify); abyte =
 // EdDSAPublicKey.Abyte, Rw = R's bytes, both for the SHA-512 of phase 2. It
-// leaves P = -A and Q = -R parked in the record for the table phase.
+// leaves P = -A and Q = -R parked (ED_PREP_LDS) for the table phase.
 CDEV uint8_t prep_decode_phase(const uint8_t* __restrict__ keys, const uint8_t* __restrict__ sigs, uint64_t i,
                                uint32_t msg_len, const uint8_t* __restrict__ pre_status, uint32_t empty_is_error,
-                               uint32_t* __restrict__ rec, uint32_t abyte[8], uint32_t Rw[8]) {
+                               uint32_t* __restrict__ rec, uint32_t* col, uint32_t abyte[8], uint32_t Rw[8]) {
   uint8_t st = kStatusPending;
   load8(Rw, reinterpret_cast<const uint32_t*>(sigs + i * 64));
   {
@@ -453,39 +543,39 @@ CDEV uint8_t prep_decode_phase(const uint8_t* __restrict__ keys, const uint8_t* 
       ge_identity(A);
       ge_identity(R);
     }
-    // P = -A, Q = -R parked in the record (Z = 1: X, Y, T), so the table loops
-    // below hold one point at a time
+    // P = -A, Q = -R parked (Z = 1: X, Y, T), so the table loops below hold
+    // one point at a time
     fe_neg(A.X, A.X);
     fe_neg(A.T, A.T);
     fe_neg(R.X, R.X);
     fe_neg(R.T, R.T);
-    store_point(joint_slot(rec, kParkP), A);
-    store_point(joint_slot(rec, kParkQ), R);
+    park_point(rec, col, 0, A);
+    park_point(rec, col, 1, R);
   }
   return st;
 }
 
-CDEV void prep_table_phase(uint32_t* __restrict__ rec) {
+CDEV void prep_table_phase(uint32_t* __restrict__ rec, uint32_t* col) {
   // the joint table i P + j Q: one loop body per kind of pass keeps a single
   // copy of its code in the I-cache
 #pragma unroll 1
   for (int pass = 0; pass < 2; pass++) {
-    joint_single_pass(rec, pass);
+    joint_single_pass(rec, col, pass);
     PHASE_BARRIER();
   }
 #pragma unroll 1
   for (int s = -1; s <= 1; s += 2) {
-    joint_sign_pass(rec, s);
+    joint_sign_pass(rec, col, s);
     PHASE_BARRIER();
   }
 }
 
 CDEV uint8_t prep_keys_phase(const uint8_t* __restrict__ keys, const uint8_t* __restrict__ sigs, uint64_t i,
                              uint32_t msg_len, const uint8_t* __restrict__ pre_status, uint32_t empty_is_error,
-                             uint32_t* __restrict__ rec, uint32_t abyte[8], uint32_t Rw[8]) {
-  const uint8_t st = prep_decode_phase(keys, sigs, i, msg_len, pre_status, empty_is_error, rec, abyte, Rw);
+                             uint32_t* __restrict__ rec, uint32_t* col, uint32_t abyte[8], uint32_t Rw[8]) {
+  const uint8_t st = prep_decode_phase(keys, sigs, i, msg_len, pre_status, empty_is_error, rec, col, abyte, Rw);
   PHASE_BARRIER();
-  prep_table_phase(rec);
+  prep_table_phase(rec, col);
   return st;
 }
 
@@ -510,11 +600,30 @@ CDEV void prep_msg_phase(const uint8_t* __restrict__ sigs, const uint8_t* __rest
 #pragma unroll
     for (int q = 0; q < 8; q++) ka[q] = kr[q] = e[q] = 0;
   }
+#if ED_SEL_STREAM
+  // what the ladder consumes (ed25519_sel.hpp): window selectors, B digits, window count
+  uint32_t sel[32];
+  sel_recode(sel, ka, kr, e, c0neg);
+  sel[kSelWords] = 0;
+  uint4* o4 = reinterpret_cast<uint4*>(rec + kWhSel);
+#pragma unroll
+  for (int q = 0; q < 8; q++) o4[q] = make_uint4(sel[4 * q], sel[4 * q + 1], sel[4 * q + 2], sel[4 * q + 3]);
+#else
   store8(rec + kWhKa, ka);
   store8(rec + kWhKr, kr);
   store8(rec + kWhE, e);
   reinterpret_cast<uint4*>(rec + kWhFlags)[0] = make_uint4(c0neg ? 1u : 0u, 0u, 0u, 0u);
+#endif
 }
+
+// this thread's column of the parking area (ED_PREP_LDS)
+#if ED_PREP_LDS
+#define PREP_PARK_COLUMN(col)                  \
+  __shared__ uint32_t pq_lds[kPqWords][256]; \
+  uint32_t* col = &pq_lds[0][threadIdx.x]
+#else
+#define PREP_PARK_COLUMN(col) uint32_t* col = nullptr
+#endif
 
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_PREP_WAVES))) ed25519_prep_half_kernel(
     const uint8_t* __restrict__ keys, const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ msgs,
@@ -525,7 +634,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_PRE
   const uint64_t i = base + li;
   uint32_t* rec = ws + li * kWhLaneWords;
   uint32_t abyte[8], Rw[8];
-  const uint8_t st = prep_keys_phase(keys, sigs, i, msg_len, pre_status, empty_is_error, rec, abyte, Rw);
+  PREP_PARK_COLUMN(col);
+  const uint8_t st = prep_keys_phase(keys, sigs, i, msg_len, pre_status, empty_is_error, rec, col, abyte, Rw);
   prep_msg_phase(sigs, msgs, msg_len, i, st, abyte, Rw, rec);
   status[i] = st;
 }
@@ -544,7 +654,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_PRE
   const uint64_t i = base + li;
   uint32_t* rec = ws + li * kWhLaneWords;
   uint32_t abyte[8], Rw[8];
-  status[i] = prep_keys_phase(keys, sigs, i, msg_len, pre_status, empty_is_error, rec, abyte, Rw);
+  PREP_PARK_COLUMN(col);
+  status[i] = prep_keys_phase(keys, sigs, i, msg_len, pre_status, empty_is_error, rec, col, abyte, Rw);
   store8(rec + kWhKa, abyte);
 }
 
@@ -650,7 +761,8 @@ hipError_t launch_ed25519_btable(uint32_t* tab, hipStream_t s) {
   hipLaunchKernelGGL(ed25519_btable_kernel, dim3((2 * kBTableEntries + 63) / 64), dim3(64), 0, s, tab);
   return hipGetLastError();
 }
-size_t ed25519_btable_bytes() { return 2 * (size_t)kBTableEntries * kBEntryWords * sizeof(uint32_t); }
+// the two tables and the identity entry behind them, padded to 256 B
+size_t ed25519_btable_bytes() { return ((size_t)kBIdentityWord + 64) * sizeof(uint32_t); }
 
 size_t ed25519_ws_lane_bytes() { return kWhLaneWords * sizeof(uint32_t); }
 

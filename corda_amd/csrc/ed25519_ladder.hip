@@ -8,7 +8,8 @@
 // ed25519.hip above half_scalars). 2-bit Booth windows over both scalars at
 // once: one addition per window of an entry i(-A) + j(-R) of the per-lane joint
 // table (ed25519_joint.hpp; gathered from the workspace one window ahead, so
-// the two doublings hide the load), 16-bit Booth windows over B and
+// the two doublings hide the load; which entry, and the fixed-base digits, come
+// recoded from the prep: ed25519_sel.hpp), 16-bit Booth windows over B and
 // B' = [2^128]B from L2/MALL-resident tables (ed25519_ws.hpp). Digit positions are the same in every lane, so the
 // ladder never diverges; P == O is X == 0 and Y == Z (no inversion).
 // Verdict word per wave by ballot.
@@ -24,6 +25,8 @@
 
 namespace cordahip {
 
+// the identity entry: behind the B tables (ED_IDENT_GLOBAL, ed25519_ws.hpp) or
+// this constant, whose generic address turns the entry gather into flat loads
 __device__ __attribute__((aligned(64))) const uint32_t kIdentityCached[kWhEntryWords] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0,   // Y + X
                                                             1, 0, 0, 0, 0, 0, 0, 0, 0, 0,   // Y - X
                                                             1, 0, 0, 0, 0, 0, 0, 0, 0, 0,   // Z
@@ -44,6 +47,83 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_LAD
   const bool active = li < m;
   const uint64_t lc = active ? li : m - 1;  // inactive lanes replay the last record, discard it
   const uint32_t* rec = ws + lc * kWhLaneWords;
+#if ED_IDENT_GLOBAL
+  const uint32_t* ident = btab + kBIdentityWord;  // a global pointer like rec: the gather stays global_load
+#else
+  const uint32_t* ident = kIdentityCached;
+#endif
+  const uint32_t* btab2 = btab + kBTableEntries * kBEntryWords;
+  ge_p3 P;
+  ge_identity(P);
+#if ED_SEL_STREAM
+  // the selector stream (ed25519_sel.hpp) lives in LDS, word-major, one column
+  // per thread: a window reads one word of it, a fixed-base window three more,
+  // and no VGPR is pinned across the loop
+  __shared__ uint32_t sk[kSelWords][256];
+  {
+    const uint4* r4 = reinterpret_cast<const uint4*>(rec + kWhSel);
+#pragma unroll
+    for (int q = 0; q < (kSelWords + 3) / 4; q++) {
+      const uint4 v = r4[q];
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int t = 0; t < 4; t++)
+        if (4 * q + t < kSelWords) sk[4 * q + t][threadIdx.x] = w[t];
+    }
+  }
+  const uint32_t* col = &sk[0][threadIdx.x];
+  // at least the windows the fixed-base digits need (e's low half: kBDigits
+  // digits of kBBits bits); |c0|, c1 ~ 2^128 give 65. Lanes with fewer windows
+  // of their own select the identity above them. (A count is at most 129.)
+  const int W = min(max(wave_max((int)(col[kSelMeta * 256] >> 16)), (kBDigits - 1) * (kBBits / 2) + 1), kSelWindows);
+  // window j's selector is read while window j + 1 computes; its word and
+  // field are the same in every lane
+  uint32_t selw = col[((W - 1) / kSelPerWord) * 256];
+  for (int j = W - 1; j >= 0; j--) {
+    const int jn = max(j - 1, 0);
+    const uint32_t selw_next = col[(jn / kSelPerWord) * 256];
+    const uint32_t sel = selw >> (kSelBits * (j % kSelPerWord));
+    const uint32_t idx = sel & 15u;
+    const bool neg = sel & kSelNeg;
+    ge_cached c;  // issued before the doublings, consumed after them
+    load_cached(c, idx == kSelIdentity ? ident : rec + kWhTab + idx * kWhEntryWords);
+    // fixed-base window (W is the wave's maximum and may exceed 65: the low
+    // half's windows end at digit kBDigits - 1, the high half's digits ride on
+    // B'): its digits are read here, ahead of the doublings
+    const bool bwin = j % (kBBits / 2) == 0 && j < kBDigits * (kBBits / 2);
+    uint32_t m0 = 0, m1 = 0, sg = 0;
+    const int t = j / (kBBits / 2);
+    if (bwin) {
+      m0 = col[(kSelMag + (t >> 1)) * 256];
+      m1 = col[(kSelMag + ((t + kBDigits) >> 1)) * 256];
+      sg = col[kSelMeta * 256];
+    }
+    if (j != W - 1) {
+      ge_dbl<false>(P, P);
+      ge_dbl<true>(P, P);
+    }
+    cached_cneg(c, neg);
+    if (bwin) {
+      // the L2 gather of each niels entry is issued one addition ahead of its
+      // use (registers allow no more)
+      const int sh = 16 * (t & 1);
+      ge_niels nb0, nb1;
+      uint32_t pad0[2], pad1[2];
+      load_niels(nb0, btab, (int)((m0 >> sh) & 0xffffu), pad0);
+      ge_add<true>(P, P, c);
+      load_niels(nb1, btab2, (int)((m1 >> sh) & 0xffffu), pad1);
+      niels_pad_use(pad0);
+      niels_cneg(nb0, (sg >> t) & 1u);
+      ge_madd<true>(P, P, nb0);
+      niels_pad_use(pad1);
+      niels_cneg(nb1, (sg >> (t + kBDigits)) & 1u);
+      ge_madd<false>(P, P, nb1);
+    } else {
+      ge_add<false>(P, P, c);
+    }
+    selw = selw_next;
+  }
+#else
   // |c0|, c1 and e live in LDS (word-major, one column per thread): each window
   // reads two words of each, and the 24 VGPRs they would pin across the loop
   // go to the group formulas' wider product blocks instead
@@ -69,13 +149,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_LAD
   // at least the windows the fixed-base digits need (e's low half: kBDigits
   // digits of kBBits bits); |c0|, c1 ~ 2^128 give 65
   const int W = max(wave_max((bits + 2) / 2), (kBDigits - 1) * (kBBits / 2) + 1);
-  const uint32_t* btab2 = btab + kBTableEntries * kBEntryWords;
-  ge_p3 P;
-  ge_identity(P);
   for (int j = W - 1; j >= 0; j--) {
     const joint_sel sel = joint_select(joint_booth2(ska, 256, 8, j), joint_booth2(skr, 256, 8, j), c0neg);
     ge_cached c;  // issued before the doublings, consumed after them
-    load_cached(c, table_entry(rec, sel.idx));
+    load_cached(c, table_entry(rec, sel.idx, ident));
     if (j != W - 1) {
       ge_dbl<false>(P, P);
       ge_dbl<true>(P, P);
@@ -101,6 +178,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_LAD
       ge_add<false>(P, P, c);
     }
   }
+#endif
   fe d;
   fe_sub(d, P.Y, P.Z);
   const bool zero = fe_iszero(P.X) && fe_iszero(d);

@@ -12,6 +12,7 @@
 // both issue those products as generated asm pairs (fe25519_asm.hpp).
 #pragma once
 #include "ed25519_joint.hpp"
+#include "ed25519_sel.hpp"
 #include "fe25519.hpp"
 #include "ge25519.hpp"
 #include "sc25519.hpp"
@@ -29,6 +30,10 @@ static constexpr int kBBits = 16;
 static constexpr int kBDigits = 8;  // per half: 8 x 16 = 128 bits
 static constexpr int kBTableEntries = (1 << (kBBits - 1)) + 1;
 static constexpr int kBEntryWords = 32;
+// the identity in cached form follows the two tables in their allocation (one
+// padded entry of the joint table's format, written by ed25519_btable_kernel)
+static constexpr int kBIdentityWord = 2 * kBTableEntries * kBEntryWords;
+static_assert(kSelBDigits == 2 * kBDigits, "ed25519_sel.hpp recodes both halves of e");
 static constexpr uint8_t kStatusPending = 0xff;
 
 // Per-lane workspace record (2,432 B = 38 x 64 B, so every record and every
@@ -37,26 +42,40 @@ static constexpr uint8_t kStatusPending = 0xff;
 // cached form (40 words) padded to 48 words, so a gather of one entry reads
 // exactly three 64-B sectors (at 40-word stride an entry straddled 3-4 sectors
 // and 2-3 128-B lines). The digit pair (0, 0) gathers the shared identity entry
-// kIdentityCached (L2-resident) instead of a per-lane copy.
+// (L2-resident) instead of a per-lane copy.
+//
+// The 32 words behind the table hold the ladder's selector stream
+// (ED_SEL_STREAM, ed25519_sel.hpp: 31 words) or, without it, |c0|, c1, e and
+// the sign of c0. Between the two launches of the split prep the first 8 hold
+// Abyte.
+#ifndef ED_SEL_STREAM
+#define ED_SEL_STREAM 1  // 0: the ladder recodes the scalars itself, window by window
+#endif
+#ifndef ED_IDENT_GLOBAL
+#define ED_IDENT_GLOBAL 1  // 0: the identity entry is a __device__ constant (flat gathers)
+#endif
 static constexpr int kWhEntryWords = 48;
 static constexpr int kWhTab = 0;                               // entry idx at idx * kWhEntryWords
-static constexpr int kWhKa = kJointEntries * kWhEntryWords;    // |c0|, c1, e (8 words each)
+static constexpr int kWhKa = kJointEntries * kWhEntryWords;    // the scalar words: |c0|, c1, e (8 words each)
 static constexpr int kWhKr = kWhKa + 8;
 static constexpr int kWhE = kWhKa + 16;
 static constexpr int kWhFlags = kWhKa + 24;             // bit 0: c0 < 0
 static constexpr int kWhLaneWords = kWhKa + 32;         // 608 words
 static_assert(kWhLaneWords % 16 == 0, "records must start on 64-B sectors");
 
+static constexpr int kWhSel = kWhKa;                     // the selector stream (kSelWords, padded to 32)
+
 // the identity in cached form (Y+X, Y-X, Z, 2dT) = (1, 1, 1, 0), the entry of
 // the digit pair (0, 0) in every lane (defined in ed25519_ladder.hip)
 extern __device__ const uint32_t kIdentityCached[kWhEntryWords];
 
-// entry idx (joint_select) of a lane's joint table
-CDEV const uint32_t* table_entry(const uint32_t* rec, int idx) {
-  return idx == kJointIdentity ? kIdentityCached : rec + kWhTab + idx * kWhEntryWords;
+// entry idx (joint_select) of a lane's joint table; ident: the shared identity entry
+CDEV const uint32_t* table_entry(const uint32_t* rec, int idx, const uint32_t* ident) {
+  return idx == kJointIdentity ? ident : rec + kWhTab + idx * kWhEntryWords;
 }
 
-CDEV void load_niels(ge_niels& n, const uint32_t* __restrict__ tab, int idx) {
+// pad: the entry's last two words (padding), for niels_pad_use below
+CDEV void load_niels(ge_niels& n, const uint32_t* __restrict__ tab, int idx, uint32_t pad[2]) {
   const uint4* e = reinterpret_cast<const uint4*>(tab + idx * kBEntryWords);
   uint32_t w[32];
 #pragma unroll
@@ -73,6 +92,26 @@ CDEV void load_niels(ge_niels& n, const uint32_t* __restrict__ tab, int idx) {
     n.ymx.v[i] = w[10 + i];
     n.xy2d.v[i] = w[20 + i];
   }
+  pad[0] = w[30];
+  pad[1] = w[31];
+}
+CDEV void load_niels(ge_niels& n, const uint32_t* __restrict__ tab, int idx) {
+  uint32_t pad[2];
+  load_niels(n, tab, idx, pad);
+}
+// The gather's last quad carries the two padding words. Left unused they are
+// dead destination registers, which the allocator hands to the product block
+// that follows the gather as temporaries, and that block then waits for the
+// loads it was meant to cover (s_waitcnt vmcnt(1) in front of it). Naming them
+// as inputs of an empty asm statement where the entry is first used keeps the
+// two registers allocated until there, so the first wait is at the use.
+#ifndef ED_NIELS_PAD_LIVE
+#define ED_NIELS_PAD_LIVE 1
+#endif
+CDEV void niels_pad_use(const uint32_t pad[2]) {
+#if ED_NIELS_PAD_LIVE
+  asm volatile("" ::"v"(pad[0]), "v"(pad[1]));
+#endif
 }
 
 // conditional negation of a niels / cached point: swap (y+x, y-x), negate t
