@@ -1465,6 +1465,7 @@ hipError_t vkey_clear_record(Device& d, uint32_t slot) {
   if (!d.vkeys.tab.p && !d.ec_vkeys.tab.p) return hipSuccess;
   hipError_t e = hipSuccess;
   if (d.vkeys.tab.p) {
+    d.vkeys.live &= ~(1ull << slot);  // routed enqueues (K14) count the device's live Ed25519 keys
     e = d.vkeys.ev.sync();
     e = e ? e
           : hipMemsetAsync(d.vkeys.tab.as<uint32_t>() + kVkeyRecBase + (size_t)slot * kVkeyRecWords, 0,
@@ -1509,6 +1510,7 @@ int vkey_build_on(Device& d, const uint8_t key[32], uint32_t key_id, bool* decod
     uint32_t flag;
     std::memcpy(&flag, stage + 32, 4);
     *decoded = flag == 1u;
+    if (*decoded) d.vkeys.live |= 1ull << vkey_slot(key_id);
   }
   return hip_err(e ? e : f);
 }
@@ -2216,6 +2218,30 @@ int cordahip_vkey_add_ecdsa(cordahip_ctx* ctx, uint32_t scheme, const uint8_t* k
 int cordahip_vkey_remove(cordahip_ctx* ctx, uint32_t key_id) {
   if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
   return guarded([&] { return vkey_remove_impl(ctx, key_id); });
+}
+
+int cordahip_vkey_set_routing(cordahip_ctx* ctx, uint32_t on) {
+  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
+  for (auto& dp : ctx->devs) dp->route_on.store(on ? 1u : 0u);
+  return CORDAHIP_SUCCESS;
+}
+
+int cordahip_vkey_route_stats(cordahip_ctx* ctx, int device, uint64_t* keyed_lanes, uint64_t* generic_lanes) {
+  Device* d = dev_at(ctx, device);
+  if (!d || !keyed_lanes || !generic_lanes) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    std::lock_guard<std::mutex> g(d->vkey_mu);
+    uint64_t tot[2] = {0, 0};
+    if (d->vkeys.route_tot.p) {  // else: no routed enqueue on this device yet
+      // every routed enqueue's partition pass is followed by vkeys.ev
+      if (hipSetDevice(d->id) != hipSuccess || d->vkeys.ev.sync() != hipSuccess ||
+          hipMemcpy(tot, d->vkeys.route_tot.p, sizeof tot, hipMemcpyDeviceToHost) != hipSuccess)
+        return CORDAHIP_ERR_HIP;
+    }
+    *keyed_lanes = tot[0];
+    *generic_lanes = tot[1];
+    return CORDAHIP_SUCCESS;
+  });
 }
 
 int cordahip_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch) {

@@ -28,6 +28,7 @@
 #include <stdlib.h>
 
 #include "ed25519_ops.hpp"
+#include "ed25519_route.hpp"
 #include "ed25519_ws.hpp"
 #include "sha2_device.hpp"
 #include "status.hpp"
@@ -640,6 +641,26 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_PRE
   status[i] = st;
 }
 
+// The fused prep of a routed batch (K14, ed25519_route.hpp): workspace record li
+// belongs to lane generic[base + li]; the chunk holds route_chunk_lanes(generic
+// count, base, m) records, the count read from the scratch header.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_PREP_WAVES)))
+ed25519_prep_half_idx_kernel(const uint8_t* __restrict__ keys, const uint8_t* __restrict__ sigs,
+                             const uint8_t* __restrict__ msgs, uint32_t msg_len, uint64_t base, uint64_t m,
+                             const uint8_t* __restrict__ pre_status, uint8_t* __restrict__ status,
+                             uint32_t* __restrict__ ws, uint32_t empty_is_error, const uint32_t* __restrict__ scratch,
+                             uint64_t lanes) {
+  const uint64_t li = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (li >= route_chunk_lanes(scratch[kRouteCntGeneric], base, m)) return;
+  const uint64_t i = scratch[route_off_generic(lanes) + base + li];
+  uint32_t* rec = ws + li * kWhLaneWords;
+  uint32_t abyte[8], Rw[8];
+  PREP_PARK_COLUMN(col);
+  const uint8_t st = prep_keys_phase(keys, sigs, i, msg_len, pre_status, empty_is_error, rec, col, abyte, Rw);
+  prep_msg_phase(sigs, msgs, msg_len, i, st, abyte, Rw, rec);
+  status[i] = st;
+}
+
 // The same prep in two launches, for batches whose messages arrive after their
 // keys and signatures (the signed-tx chunks: each message is its transaction's
 // id, gathered on the device once the id slice is done): phase 1 needs no
@@ -799,6 +820,29 @@ hipError_t launch_ed25519_verify(const uint8_t* keys, const uint8_t* sigs, const
       e = e ? e : hipGetLastError();
     }
     if (e == hipSuccess) e = launch_ed25519_ladder(base, m, btab, ws, status, verdict, s);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// The generic engine over the generic list of a routed batch of n lanes (scratch:
+// ed25519_route.hpp): one fused-prep / ladder pair per ws_lanes list positions. The
+// host does not know the list's length, so the pairs cover all n positions; the
+// kernels read the count, and a pair wholly past it does nothing. No verdict words:
+// the caller gathers them from the statuses.
+hipError_t launch_ed25519_verify_idx(const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
+                                     uint64_t n, const uint32_t* btab, const uint8_t* pre_status, uint8_t* status,
+                                     uint32_t* ws, uint64_t ws_lanes, uint32_t flags, const uint32_t* scratch,
+                                     hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (!ws || ws_lanes < 64 || ws_lanes % 64 || !scratch) return hipErrorInvalidValue;
+  for (uint64_t base = 0; base < n; base += ws_lanes) {
+    const uint64_t m = n - base < ws_lanes ? n - base : ws_lanes;
+    const uint32_t blocks = (uint32_t)((m + 255) / 256);
+    hipLaunchKernelGGL(ed25519_prep_half_idx_kernel, dim3(blocks), dim3(256), 0, s, keys, sigs, msgs, msg_len, base, m,
+                       pre_status, status, ws, (flags & 1u) ? 0u : 1u, scratch, n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = launch_ed25519_ladder_idx(base, m, btab, ws, status, scratch, n, s);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

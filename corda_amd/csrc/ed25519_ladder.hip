@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ed25519_route.hpp"
 #include "ed25519_ws.hpp"
 #include "status.hpp"
 
@@ -40,9 +41,13 @@ __device__ __attribute__((aligned(64))) const uint32_t kIdentityCached[kWhEntryW
 // VGPRs v160..v167, so the kernel needs a budget of >= 168 VGPRs: 512 / waves
 static_assert(512 / ED_LADDER_WAVES >= 168, "fe25519_asm.hpp's v160..v167 accumulators need >= 168 VGPRs per lane");
 
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_LADDER_WAVES))) ed25519_ladder_half_kernel(
-    uint64_t base, uint64_t m, const uint32_t* __restrict__ btab, const uint32_t* __restrict__ ws,
-    uint8_t* __restrict__ status, unsigned long long* __restrict__ verdict) {
+// The body serves two kernels. kIdx false: the ladder itself, record li is lane
+// base + li. kIdx true: the routed instance (K14, ed25519_route.hpp): record li is
+// lane list[base + li], no verdict words.
+template <bool kIdx>
+CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict__ btab,
+                           const uint32_t* __restrict__ ws, uint8_t* __restrict__ status,
+                           unsigned long long* __restrict__ verdict, const uint32_t* __restrict__ list) {
   const uint64_t li = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = li < m;
   const uint64_t lc = active ? li : m - 1;  // inactive lanes replay the last record, discard it
@@ -182,7 +187,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_LAD
   fe d;
   fe_sub(d, P.Y, P.Z);
   const bool zero = fe_iszero(P.X) && fe_iszero(d);
-  const uint64_t i = base + li;
+  const uint64_t i = kIdx ? (active ? list[base + li] : 0) : base + li;
   uint8_t st = kStatusBadSig;
   if (active) {
     st = status[i];
@@ -191,15 +196,43 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_LAD
       status[i] = st;
     }
   }
-  const unsigned long long ok = __ballot(active && st == kStatusOk);
-  // base is a multiple of 64 (workspace chunks are), so lane 0 of a wave owns a whole verdict word
-  if ((threadIdx.x & 63) == 0 && active && verdict) verdict[i >> 6] = ok;
+  if (!kIdx) {
+    const unsigned long long ok = __ballot(active && st == kStatusOk);
+    // base is a multiple of 64 (workspace chunks are), so lane 0 of a wave owns a whole verdict word
+    if ((threadIdx.x & 63) == 0 && active && verdict) verdict[i >> 6] = ok;
+  }
+}
+
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_LADDER_WAVES))) ed25519_ladder_half_kernel(
+    uint64_t base, uint64_t m, const uint32_t* __restrict__ btab, const uint32_t* __restrict__ ws,
+    uint8_t* __restrict__ status, unsigned long long* __restrict__ verdict) {
+  ladder_half_lane<false>(base, m, btab, ws, status, verdict, nullptr);
+}
+
+// The routed instance: the workspace chunk at list position base holds
+// route_chunk_lanes(generic count, base, m) records; a chunk or a block wholly past
+// the count does nothing.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_LADDER_WAVES)))
+ed25519_ladder_half_idx_kernel(uint64_t base, uint64_t m, const uint32_t* __restrict__ btab,
+                               const uint32_t* __restrict__ ws, uint8_t* __restrict__ status,
+                               const uint32_t* __restrict__ scratch, uint64_t lanes) {
+  const uint64_t mm = route_chunk_lanes(scratch[kRouteCntGeneric], base, m);
+  if ((uint64_t)blockIdx.x * blockDim.x >= mm) return;
+  ladder_half_lane<true>(base, mm, btab, ws, status, nullptr, scratch + route_off_generic(lanes));
 }
 
 hipError_t launch_ed25519_ladder(uint64_t base, uint64_t m, const uint32_t* btab, const uint32_t* ws, uint8_t* status,
                                  unsigned long long* verdict, hipStream_t s) {
   const uint32_t blocks = (uint32_t)((m + 255) / 256);
   hipLaunchKernelGGL(ed25519_ladder_half_kernel, dim3(blocks), dim3(256), 0, s, base, m, btab, ws, status, verdict);
+  return hipGetLastError();
+}
+
+hipError_t launch_ed25519_ladder_idx(uint64_t base, uint64_t m, const uint32_t* btab, const uint32_t* ws,
+                                     uint8_t* status, const uint32_t* scratch, uint64_t lanes, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((m + 255) / 256);
+  hipLaunchKernelGGL(ed25519_ladder_half_idx_kernel, dim3(blocks), dim3(256), 0, s, base, m, btab, ws, status, scratch,
+                     lanes);
   return hipGetLastError();
 }
 

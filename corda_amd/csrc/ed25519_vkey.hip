@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "ed25519_ops.hpp"
+#include "ed25519_route.hpp"
 #include "ed25519_vkey.hpp"
 #include "status.hpp"
 
@@ -121,13 +122,20 @@ static_assert(512 / ED_VKEY_WAVES >= 168, "fe25519_asm.hpp's v160..v167 accumula
 // words), pre[i] when non-zero (the host form's EMPTY / MALFORMED_SIG), EMPTY
 // (no message byte, doVerify rules), BAD_SIG, OK. verdict word per wave by
 // ballot: bit = status OK; lanes past n write nothing.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_VKEY_WAVES))) ed25519_verify_keyed_kernel(
-    const uint32_t* __restrict__ key_id, const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ msgs,
-    const uint64_t* __restrict__ moff, const uint32_t* __restrict__ mlen, uint32_t msg_len, uint64_t n,
-    const uint8_t* __restrict__ pre, uint32_t empty_is_error, const uint32_t* __restrict__ vtab,
-    uint8_t* __restrict__ status, unsigned long long* __restrict__ verdict) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = i < n;
+//
+// The body serves two kernels. kIdx false: K12 itself, lane i is thread i. kIdx true:
+// the routed instance (K14, ed25519_route.hpp): thread j below n takes lane
+// i = list[j], key_id is the route array (indexed by lane), no verdict words.
+template <bool kIdx>
+CDEV void verify_keyed_lane(const uint32_t* __restrict__ key_id, const uint32_t* __restrict__ list,
+                            const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ msgs,
+                            const uint64_t* __restrict__ moff, const uint32_t* __restrict__ mlen, uint32_t msg_len,
+                            uint64_t n, const uint8_t* __restrict__ pre, uint32_t empty_is_error,
+                            const uint32_t* __restrict__ vtab, uint8_t* __restrict__ status,
+                            unsigned long long* __restrict__ verdict) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = j < n;
+  const uint64_t i = kIdx ? (active ? list[j] : 0) : j;
   __shared__ uint32_t sk[16][256];  // h and S_eff, biased: only the thread's own column is read
   uint8_t st = kStatusBadSig;
   uint32_t slot = 0;
@@ -192,9 +200,33 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_VKE
     st = diff == 0 ? kStatusOk : kStatusBadSig;
   }
   if (active) status[i] = st;
-  const unsigned long long ok = __ballot(active && st == kStatusOk);
-  // 256-lane blocks from lane 0: lane 0 of a wave owns a whole verdict word
-  if ((threadIdx.x & 63) == 0 && active && verdict) verdict[i >> 6] = ok;
+  if (!kIdx) {
+    const unsigned long long ok = __ballot(active && st == kStatusOk);
+    // 256-lane blocks from lane 0: lane 0 of a wave owns a whole verdict word
+    if ((threadIdx.x & 63) == 0 && active && verdict) verdict[i >> 6] = ok;
+  }
+}
+
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_VKEY_WAVES))) ed25519_verify_keyed_kernel(
+    const uint32_t* __restrict__ key_id, const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ msgs,
+    const uint64_t* __restrict__ moff, const uint32_t* __restrict__ mlen, uint32_t msg_len, uint64_t n,
+    const uint8_t* __restrict__ pre, uint32_t empty_is_error, const uint32_t* __restrict__ vtab,
+    uint8_t* __restrict__ status, unsigned long long* __restrict__ verdict) {
+  verify_keyed_lane<false>(key_id, nullptr, sigs, msgs, moff, mlen, msg_len, n, pre, empty_is_error, vtab, status,
+                           verdict);
+}
+
+// The routed instance: dense message rows, the lane count read from the scratch
+// header; blocks past it exit at once.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ED_VKEY_WAVES)))
+ed25519_verify_keyed_idx_kernel(const uint32_t* __restrict__ scratch, uint64_t lanes,
+                                const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ msgs, uint32_t msg_len,
+                                const uint8_t* __restrict__ pre, uint32_t empty_is_error,
+                                const uint32_t* __restrict__ vtab, uint8_t* __restrict__ status) {
+  const uint64_t n = scratch[kRouteCntKeyed];
+  if ((uint64_t)blockIdx.x * blockDim.x >= n) return;
+  verify_keyed_lane<true>(scratch + route_off_route(lanes), scratch + route_off_keyed(lanes), sigs, msgs, nullptr,
+                          nullptr, msg_len, n, pre, empty_is_error, vtab, status, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -222,6 +254,19 @@ hipError_t launch_ed25519_verify_keyed(const uint32_t* key_id, const uint8_t* si
   if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ed25519_verify_keyed_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, key_id, sigs, msgs, moff,
                      mlen, msg_len, n, pre, (flags & 1u) ? 0u : 1u, vtab, status, verdict);
+  return hipGetLastError();
+}
+
+// K12 over the keyed list of a routed batch of `lanes` lanes (scratch:
+// ed25519_route.hpp): the grid covers every lane, the kernel reads the count
+hipError_t launch_ed25519_verify_keyed_idx(const uint32_t* scratch, uint64_t lanes, const uint8_t* sigs,
+                                           const uint8_t* msgs, uint32_t msg_len, const uint8_t* pre, uint32_t flags,
+                                           const uint32_t* vtab, uint8_t* status, hipStream_t s) {
+  if (lanes == 0) return hipSuccess;
+  const uint64_t blocks = (lanes + 255) / 256;
+  if (blocks > 0x7fffffffull || !vtab) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ed25519_verify_keyed_idx_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, scratch, lanes, sigs,
+                     msgs, msg_len, pre, (flags & 1u) ? 0u : 1u, vtab, status);
   return hipGetLastError();
 }
 

@@ -221,5 +221,9 @@ CDEV int wave_max(int v) {
 // host-side launcher of the ladder (ed25519_ladder.hip)
 hipError_t launch_ed25519_ladder(uint64_t base, uint64_t m, const uint32_t* btab, const uint32_t* ws, uint8_t* status,
                                  unsigned long long* verdict, hipStream_t s);
+// the routed instance (K14): records of the generic list's positions base .. base + m
+// of a batch of `lanes` lanes, the count read from scratch (ed25519_route.hpp)
+hipError_t launch_ed25519_ladder_idx(uint64_t base, uint64_t m, const uint32_t* btab, const uint32_t* ws,
+                                     uint8_t* status, const uint32_t* scratch, uint64_t lanes, hipStream_t s);
 
 }  // namespace cordahip

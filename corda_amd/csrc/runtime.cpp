@@ -278,14 +278,11 @@ hipError_t rsa_verify_enqueue(Device& d, const uint32_t* mod, const uint32_t* ex
   return e ? e : w.ev.record(s);
 }
 
-// Enqueue Ed25519 verification of n dense lanes on stream s (device already current).
-hipError_t ed_verify_enqueue(Device& d, const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs,
-                             uint32_t msg_len, uint64_t n, const uint8_t* pre, uint8_t* status,
-                             unsigned long long* verdict, uint32_t flags, hipStream_t s, int slot,
-                             const std::function<hipError_t()>* before_msgs) {
-  std::lock_guard<std::mutex> g(d.ed_mu[slot]);
+// The Ed25519 workspace of a slot grown for n lanes (d.ed_mu[slot] held); `more`
+// ensures what else the caller keeps behind the slot's fence.
+template <class G>
+static hipError_t ed_ws_grow(Device& d, int slot, uint64_t n, bool more_needed, G&& more) {
   DevBuf& ws = d.ed_ws[slot];
-  Fence& ev = d.ed_ev[slot];
   // the budget's Ed25519 shares (cordahip_init, device_budget): slot 1 only serves the
   // alternating chunks of the pipelines (host batches, streams, signed-tx chunks) and
   // holds at most half of slot 0. The launch loops over whatever the workspace holds,
@@ -293,7 +290,9 @@ hipError_t ed_verify_enqueue(Device& d, const uint8_t* keys, const uint8_t* sigs
   const uint64_t cap_lanes = d.ed_ws_lanes[slot ? 1 : 0];
   const uint64_t lanes = std::min<uint64_t>(cap_lanes, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
   const uint64_t lane_bytes = ed25519_ws_lane_bytes();
-  hipError_t e = ev.grow(ws.cap < lanes * lane_bytes, [&] {
+  const bool ws_needed = ws.cap < lanes * lane_bytes;
+  return d.ed_ev[slot].grow(ws_needed || more_needed, [&] {
+    if (!ws_needed) return more();
     uint64_t want = std::max<uint64_t>(lanes, std::min<uint64_t>(cap_lanes, kWsMinLanes));
     const uint64_t had = ws.cap / lane_bytes / 64 * 64;  // ensure() frees it before allocating
     hipError_t g = ws.ensure(want * lane_bytes);
@@ -304,12 +303,86 @@ hipError_t ed_verify_enqueue(Device& d, const uint8_t* keys, const uint8_t* sigs
       want = std::max<uint64_t>(std::max<uint64_t>(64, had), want / 2 / 64 * 64);
       g = ws.ensure(want * lane_bytes);
     }
-    return g;
+    return g ? g : more();
+  });
+}
+
+// The keyed half of a routed enqueue (K14; d.ed_mu[slot] held, the slot's scratch sc
+// large enough, s behind the slot's fence): under d.vkey_mu, as every keyed call --
+// behind vkeys.ev, followed by vkeys.ev -- the route and partition pass and K12 over
+// the keyed list. *routed stays false, and nothing is launched, when no Ed25519 key
+// is live any more or the counters cannot be allocated: the caller then takes the
+// unrouted path, which is always right.
+static hipError_t ed_route_and_keyed(Device& d, DevBuf& sc, const uint8_t* keys, const uint8_t* sigs,
+                                     const uint8_t* msgs, uint32_t msg_len, uint64_t n, const uint8_t* pre,
+                                     uint8_t* status, uint32_t flags, hipStream_t s,
+                                     const std::function<hipError_t()>* before_msgs, bool* routed) {
+  std::lock_guard<std::mutex> vk(d.vkey_mu);
+  if (!d.vkeys.live || !d.vkeys.tab.p) return hipSuccess;
+  if (!d.vkeys.route_tot.p) {  // the device's first routed enqueue
+    if (d.vkeys.route_tot.ensure(16) != hipSuccess) {
+      (void)hipGetLastError();
+      return hipSuccess;
+    }
+    const hipError_t z = hipMemsetAsync(d.vkeys.route_tot.p, 0, 16, s);
+    if (z != hipSuccess) return z;
+  }
+  *routed = true;
+  const uint32_t* vtab = d.vkeys.tab.as<uint32_t>();
+  hipError_t e = d.vkeys.ev.wait(s);
+  e = e ? e : launch_ed25519_route(keys, n, vtab, sc.as<uint32_t>(), d.vkeys.route_tot.as<unsigned long long>(), s);
+  // the split-prep callers' messages: route and partition needed only the keys
+  if (e == hipSuccess && before_msgs) e = (*before_msgs)();
+  e = e ? e : launch_ed25519_verify_keyed_idx(sc.as<uint32_t>(), n, sigs, msgs, msg_len, pre, flags, vtab, status, s);
+  const hipError_t r = d.vkeys.ev.record(s);  // whatever was launched is fenced, also after a failure
+  return e ? e : r;
+}
+
+// Enqueue Ed25519 verification of n dense lanes on stream s (device already current).
+// With routing on and a live Ed25519 key (K14): route and partition, K12 over the
+// keyed list, K1 over the generic list, the verdict words from the statuses -- all on
+// s, no count read back. Lock order: ed_mu[slot], then vkey_mu (Device, runtime.hpp);
+// vkey_mu is never held while this function waits for a lock, a fence or an allocation.
+hipError_t ed_verify_enqueue(Device& d, const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs,
+                             uint32_t msg_len, uint64_t n, const uint8_t* pre, uint8_t* status,
+                             unsigned long long* verdict, uint32_t flags, hipStream_t s, int slot,
+                             const std::function<hipError_t()>* before_msgs) {
+  std::lock_guard<std::mutex> g(d.ed_mu[slot]);
+  DevBuf& ws = d.ed_ws[slot];
+  DevBuf& sc = d.ed_route[slot];
+  Fence& ev = d.ed_ev[slot];
+  const uint64_t lane_bytes = ed25519_ws_lane_bytes();
+  bool want_route = d.route_on.load(std::memory_order_relaxed) && n && n <= ed25519_route_max_lanes();
+  if (want_route) {  // a look at the registry; decided for good in ed_route_and_keyed
+    std::lock_guard<std::mutex> vk(d.vkey_mu);
+    want_route = d.vkeys.live && d.vkeys.tab.p;
+  }
+  // the scratch grows in powers of two from a floor, like the workspace behind the same
+  // fence; no room for it: the batch is verified unrouted
+  const size_t sc_bytes = want_route ? ed25519_route_scratch_bytes(n) : 0;
+  hipError_t e = ed_ws_grow(d, slot, n, sc.cap < sc_bytes, [&] {
+    if (sc.cap < sc_bytes && sc.ensure(sc_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      want_route = false;
+    }
+    return hipSuccess;
   });
   e = e ? e : ev.wait(s);
-  e = e ? e
-        : launch_ed25519_verify(keys, sigs, msgs, msg_len, n, d.btab.as<uint32_t>(), pre, status, verdict,
-                                ws.as<uint32_t>(), ws.cap / lane_bytes / 64 * 64, flags, s, before_msgs);
+  bool routed = false;
+  if (e == hipSuccess && want_route)
+    e = ed_route_and_keyed(d, sc, keys, sigs, msgs, msg_len, n, pre, status, flags, s, before_msgs, &routed);
+  if (e == hipSuccess && routed) {
+    e = launch_ed25519_verify_idx(keys, sigs, msgs, msg_len, n, d.btab.as<uint32_t>(), pre, status, ws.as<uint32_t>(),
+                                  ws.cap / lane_bytes / 64 * 64, flags, sc.as<uint32_t>(), s);
+    if (e == hipSuccess && verdict) e = launch_ed25519_status_verdict(status, n, verdict, s);
+  } else if (e == hipSuccess) {
+    e = launch_ed25519_verify(keys, sigs, msgs, msg_len, n, d.btab.as<uint32_t>(), pre, status, verdict,
+                              ws.as<uint32_t>(), ws.cap / lane_bytes / 64 * 64, flags, s, before_msgs);
+  }
+  if (routed) {  // whatever was launched is fenced, also after a failure
+    const hipError_t r = ev.record(s);
+    return e ? e : r;
+  }
   return e ? e : ev.record(s);
 }
 

@@ -59,6 +59,24 @@ hipError_t launch_ed25519_verify_keyed(const uint32_t* key_id, const uint8_t* si
                                        const uint64_t* moff, const uint32_t* mlen, uint32_t msg_len, uint64_t n,
                                        const uint8_t* pre, uint32_t flags, const uint32_t* vtab, uint8_t* status,
                                        unsigned long long* verdict, hipStream_t s);
+// K14 (ed25519_route.hip, ed25519_route.hpp): routed Ed25519 batches. The partition
+// pass fills `scratch` (ed25519_route_scratch_bytes(n): route ids, the keyed and the
+// generic list, their counts; at least that large) and adds to the device's cumulative counters; the
+// indexed instances of K12 and K1 run over the lists, their lane counts read on the
+// device; the verdict words are gathered from the statuses afterwards.
+size_t ed25519_route_scratch_bytes(uint64_t n);  // a capacity: powers of two from a floor
+uint64_t ed25519_route_max_lanes();              // larger batches are not routed (32-bit lane indices)
+hipError_t launch_ed25519_route(const uint8_t* keys, uint64_t n, const uint32_t* vtab, uint32_t* scratch,
+                                unsigned long long* totals, hipStream_t s);
+hipError_t launch_ed25519_verify_keyed_idx(const uint32_t* scratch, uint64_t lanes, const uint8_t* sigs,
+                                           const uint8_t* msgs, uint32_t msg_len, const uint8_t* pre, uint32_t flags,
+                                           const uint32_t* vtab, uint8_t* status, hipStream_t s);
+hipError_t launch_ed25519_verify_idx(const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
+                                     uint64_t n, const uint32_t* btab, const uint8_t* pre_status, uint8_t* status,
+                                     uint32_t* ws, uint64_t ws_lanes, uint32_t flags, const uint32_t* scratch,
+                                     hipStream_t s);
+hipError_t launch_ed25519_status_verdict(const uint8_t* status, uint64_t n, unsigned long long* verdict,
+                                         hipStream_t s);
 hipError_t launch_sha256_leaves(const uint8_t* bytes, const uint64_t* off, uint64_t nleaves, uint32_t* hashes,
                                 hipStream_t s);
 hipError_t launch_merkle_root(uint32_t* hashes, const uint64_t* tx_leaf_off, uint64_t ntx, uint8_t* txid,
@@ -448,16 +466,22 @@ struct SignKeys {
 // ~Device -- the idle release and cordahip_trim never see it (Device::visit_keys), so a
 // verifier cannot lose its registered keys to an idle timer. ev: the fence of the
 // kernels that read the table. stage: 64 page-locked bytes the key bytes go out and the
-// decode verdict comes back in.
+// decode verdict comes back in. live: the slots whose record is live on this device
+// (bit per slot, Device::vkey_mu). route_tot: the device's cumulative counters of
+// routed lanes (K14: keyed, generic; two 64-bit words, zeroed when allocated by the
+// first routed enqueue), written by kernels ordered by ev.
 struct VerifyKeys {
   DevBuf tab;
   PinBuf stage;
   Fence ev;
+  uint64_t live = 0;
+  DevBuf route_tot;
   template <class V>
   void visit(V& v) {
     v.dev(tab, kKept);
     v.pin(stage, kKept);
     v.fence(ev);
+    v.dev(route_tot, kKept);
   }
 };
 
@@ -578,8 +602,12 @@ struct Device {
   // Two workspace slots: the host pipelines alternate consecutive chunks between
   // them and between s_ed / s_ed2, so chunk k + 1's kernels fill the CUs chunk
   // k's end-of-grid tail leaves idle (slot 0 alone serves the device paths).
+  // ed_route: the slot's routing scratch (K14, ed25519_route.hpp: 12 bytes per lane
+  // and a header, grown in powers of two), behind the same lock and fence, released
+  // with the workspace.
   std::mutex ed_mu[2];
   DevBuf ed_ws[2];
+  DevBuf ed_route[2];
   Fence ed_ev[2];
   // The pipelines' three streams, created together and shared by the C5 drain
   // and the packed host pipelines: every H2D on s_copy (PCIe in chunk order),
@@ -642,8 +670,23 @@ struct Device {
   // signer's: a keyed verification holds it while it enqueues -- its stream waits for
   // vkeys.ev, its kernel is followed by vkeys.ev -- and add / remove hold it for their
   // whole run; remove waits for vkeys.ev first.
+  // Routing (K14, cordahip_vkey_set_routing): with route_on set and a live Ed25519
+  // key (vkeys.live), ed_verify_enqueue is a keyed call too: under ed_mu[slot] it takes
+  // vkey_mu for the route pass and the K12 launch -- behind vkeys.ev, followed by
+  // vkeys.ev -- and drops it before the generic engine. With route_on clear it takes no
+  // lock it did not take before.
+  // Lock order of the locks met on these paths, outermost first:
+  //   ped_mu / stream_mu / a SetLease (the pipelines) -> ed_mu[0] -> ed_mu[1] ->
+  //   ... -> vkey_host_mu -> vkey_mu.
+  // trim_device takes them in that order up to vkey_host_mu; a keyed host call holds
+  // vkey_host_mu and takes vkey_mu inside it; a routed enqueue holds ed_mu[slot] and
+  // takes vkey_mu inside it. vkey_mu is innermost: whoever holds it (add, remove, the
+  // stats call, a keyed or routed enqueue) takes no other lock of the device but tmu
+  // (the timing ring's, a leaf held for a few assignments), and a routed enqueue never
+  // holds it while it waits for another lock, the slot's fence or the scratch's growth.
   VerifyKeys vkeys;
   std::mutex vkey_mu;
+  std::atomic<uint32_t> route_on{0};
   // ECDSA verification against registered keys (K13): the tables of the same registry's
   // ECDSA keys, under the same vkey_mu, with a fence of their own.
   EcVerifyKeys ec_vkeys;
@@ -675,6 +718,7 @@ struct Device {
       for (hipEvent_t* e : {&tc.a, &tc.b}) v.event(*e, false);
     for (TxSet& S : set) S.visit(v);
     for (DevBuf& b : ed_ws) v.dev(b, kFreed);
+    for (DevBuf& b : ed_route) v.dev(b, kFreed);
     for (Fence& f : ed_ev) v.fence(f);
     for (StreamStage& st : sstage) st.visit(v);
     for (PackStage& st : ped) st.visit(v);

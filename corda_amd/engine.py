@@ -173,6 +173,20 @@ class Engine:
         device; the id answers VERIFY_UNKNOWN_KEY from then on."""
         check(lib().cordahip_vkey_remove(self._ctx, key_id), "cordahip_vkey_remove")
 
+    def vkey_set_routing(self, on: bool):
+        """cordahip_vkey_set_routing: on, every Ed25519 batch (generic, signed-tx, dense, stream) sends
+        the lanes whose 32 key bytes equal a registered key's canonical encoding to the keyed verifier,
+        on the GPU; statuses are those of the unrouted call. Off (the default): nothing changes."""
+        check(lib().cordahip_vkey_set_routing(self._ctx, 1 if on else 0), "cordahip_vkey_set_routing")
+
+    def vkey_route_stats(self, device: int = 0):
+        """cordahip_vkey_route_stats: (keyed_lanes, generic_lanes) that routed enqueues on `device` have
+        sent each way since init; waits for the routed work already enqueued there."""
+        k, g = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().cordahip_vkey_route_stats(self._ctx, device, ctypes.byref(k), ctypes.byref(g)),
+              "cordahip_vkey_route_stats")
+        return k.value, g.value
+
     def verify_keyed_batch(self, key_ids: Sequence[int], sigs: Sequence[bytes], msgs: Sequence[bytes],
                            is_valid: bool = False, async_: bool = False):
         """cordahip_verify_keyed / cordahip_verify_keyed_submit: lane i checks sigs[i] over msgs[i] against

@@ -425,6 +425,45 @@ int cordahip_ed25519_verify_keyed_device(cordahip_ctx* ctx, int device, const vo
                                          const void* d_msgs, uint32_t msg_len, uint64_t n, void* d_status,
                                          void* d_verdict, void* hip_stream);
 
+/* ---- Routing registered-key lanes to the keyed verifier (kernel K14) ----------
+ * The calls the JVM makes with mixed batches -- cordahip_sig_verify / _submit,
+ * the signed-tx calls (host and device), cordahip_ed25519_verify_device / _host,
+ * cordahip_stream_verify -- carry key bytes, not key ids. With routing on, the
+ * library recognises the lanes of registered Ed25519 keys itself, on the GPU, and
+ * verifies them with the keyed verifier above; the caller changes nothing else.
+ *
+ * cordahip_vkey_set_routing(ctx, on): on != 0 turns routing on for every device of
+ * the context, 0 (the default) off. It takes effect with the next Ed25519 batch
+ * enqueued. Off, every call does exactly what it did before this switch existed:
+ * nothing more is launched, allocated or locked.
+ *
+ * The rule, while routing is on and the device holds at least one live Ed25519
+ * verification key: a lane is verified by the keyed verifier exactly when its 32
+ * key bytes equal the canonical encoding (EdDSAPublicKey.Abyte) stored in a live
+ * record; every other lane by the generic verifier as before. Nothing but the key
+ * bytes enters the decision. A non-canonical encoding of a registered point
+ * misses and stays generic (which decodes it to the same point); of two live
+ * records with equal bytes either may serve; ECDSA records are never matched.
+ * Every lane's status and verdict bit equal the unrouted call's under both flags
+ * values; no lane of these calls ever answers CORDAHIP_VERIFY_UNKNOWN_KEY.
+ * The partition runs on the caller's stream and the host reads no count back.
+ * It needs 12 bytes per lane of scratch per Ed25519 workspace slot (grown in
+ * powers of two from 2^16 lanes), counted in cordahip_device_mem and released by
+ * cordahip_trim and the idle release with the workspace; a batch whose scratch
+ * does not fit in device memory is verified unrouted, not failed. Batches of 2^32 lanes or more in one enqueue are not routed.
+ *
+ * Ordering: a routed batch is a keyed call. cordahip_vkey_remove waits for the
+ * routed batches already enqueued before it clears a record, so no record dies
+ * between a lane's match and its verification; an add or a remove that races a
+ * batch decides only which verifier a lane takes, never its status.
+ *
+ * cordahip_vkey_route_stats: the lanes that routed enqueues on `device` have sent
+ * to the keyed and to the generic verifier since cordahip_init. Lanes verified
+ * while routing was off, or while the device held no live Ed25519 key, count in
+ * neither. The call waits for the routed work already enqueued on the device. */
+int cordahip_vkey_set_routing(cordahip_ctx* ctx, uint32_t on);
+int cordahip_vkey_route_stats(cordahip_ctx* ctx, int device, uint64_t* keyed_lanes, uint64_t* generic_lanes);
+
 /* ---- ECDSA verification against registered public keys (kernel K13) --------
  * Replaces, per lane, Crypto.doVerify / Crypto.isValid for ECDSA_SECP256K1_SHA256
  * (2) and ECDSA_SECP256R1_SHA256 (3) (Crypto.kt:472-541 -> BouncyCastle
