@@ -47,6 +47,7 @@ EXPORTS = [
     "cordahip_vkey_add_ecdsa", "cordahip_ecdsa_verify_keyed", "cordahip_ecdsa_verify_keyed_submit",
     "cordahip_ecdsa_verify_keyed_device",
     "cordahip_vkey_set_routing", "cordahip_vkey_route_stats",
+    "cordahip_vkey_set_routing_ecdsa", "cordahip_vkey_route_stats_ecdsa",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
@@ -317,6 +318,8 @@ def lib() -> ctypes.CDLL:
         "cordahip_vkey_remove": (i32, [vp, u32]),
         "cordahip_vkey_set_routing": (i32, [vp, u32]),
         "cordahip_vkey_route_stats": (i32, [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "cordahip_vkey_set_routing_ecdsa": (i32, [vp, u32]),
+        "cordahip_vkey_route_stats_ecdsa": (i32, [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "cordahip_verify_keyed": (i32, [vp, ctypes.POINTER(KeyedSigBatch)]),
         "cordahip_verify_keyed_submit": (i32, [vp, ctypes.POINTER(KeyedSigBatch), ctypes.POINTER(u64)]),
         "cordahip_ed25519_verify_keyed_device": (i32, [vp, i32, vp, vp, vp, u32, u64, vp, vp, vp]),

@@ -2244,6 +2244,30 @@ int cordahip_vkey_route_stats(cordahip_ctx* ctx, int device, uint64_t* keyed_lan
   });
 }
 
+int cordahip_vkey_set_routing_ecdsa(cordahip_ctx* ctx, uint32_t on) {
+  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
+  for (auto& dp : ctx->devs) dp->ec_route_on.store(on ? 1u : 0u);
+  return CORDAHIP_SUCCESS;
+}
+
+int cordahip_vkey_route_stats_ecdsa(cordahip_ctx* ctx, int device, uint64_t* keyed_lanes, uint64_t* generic_lanes) {
+  Device* d = dev_at(ctx, device);
+  if (!d || !keyed_lanes || !generic_lanes) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    std::lock_guard<std::mutex> g(d->vkey_mu);
+    uint64_t tot[2] = {0, 0};
+    if (d->ec_vkeys.route_tot.p) {  // else: no routed ECDSA enqueue on this device yet
+      // every routed enqueue's partition pass is followed by ec_vkeys.ev
+      if (hipSetDevice(d->id) != hipSuccess || d->ec_vkeys.ev.sync() != hipSuccess ||
+          hipMemcpy(tot, d->ec_vkeys.route_tot.p, sizeof tot, hipMemcpyDeviceToHost) != hipSuccess)
+        return CORDAHIP_ERR_HIP;
+    }
+    *keyed_lanes = tot[0];
+    *generic_lanes = tot[1];
+    return CORDAHIP_SUCCESS;
+  });
+}
+
 int cordahip_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch) {
   if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
   return guarded([&] { return verify_keyed_impl(ctx, batch); });

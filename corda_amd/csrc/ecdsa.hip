@@ -25,6 +25,7 @@
 #include <string>
 
 #include "der.hpp"
+#include "ecdsa_route.hpp"
 #include "ecdsa_vkey.hpp"
 #include "fp29.hpp"
 #include "fp29_asm.hpp"
@@ -1169,16 +1170,20 @@ __global__ void __launch_bounds__(256) verdict_kernel(const uint8_t* __restrict_
 }
 
 // ---- split verification (default): prep -> batch inversion -> ladder --------
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) ecdsa_prep_kernel(
-    const unsigned int* __restrict__ perm, const uint8_t* __restrict__ scheme, const uint8_t* __restrict__ keys,
-    const uint8_t* __restrict__ key_len, const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ sig_len,
-    const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ msg_off, uint32_t msg_len, uint64_t base,
-    uint64_t m, const uint8_t* __restrict__ pre_status, uint8_t* __restrict__ status, uint32_t* __restrict__ ws,
-    uint32_t empty_is_error) {
+// The body serves two kernels. kRouted false: the prep itself. kRouted true: the routed
+// instance (K15, ecdsa_route.hip): perm is the routed partition's, never null, and m
+// the chunk's share of the generic list, read on the device.
+template <bool kRouted>
+CDEV void ecdsa_prep_body(const unsigned int* __restrict__ perm, const uint8_t* __restrict__ scheme,
+                          const uint8_t* __restrict__ keys, const uint8_t* __restrict__ key_len,
+                          const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ sig_len,
+                          const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ msg_off, uint32_t msg_len,
+                          uint64_t base, uint64_t m, const uint8_t* __restrict__ pre_status,
+                          uint8_t* __restrict__ status, uint32_t* __restrict__ ws, uint32_t empty_is_error) {
   const uint64_t li = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (li >= m) return;
   const uint64_t slot = base + li;
-  const uint64_t i = perm ? perm[slot] : slot;
+  const uint64_t i = kRouted ? perm[slot] : perm ? perm[slot] : slot;
   const uint8_t sch = scheme[i];
   const uint8_t* key = keys + i * 65;
   const uint8_t* sig = sigs + i * 72;
@@ -1200,6 +1205,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) e
   else
     st = kStatusUnsupported;
   status[i] = st;
+}
+
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) ecdsa_prep_kernel(
+    const unsigned int* __restrict__ perm, const uint8_t* __restrict__ scheme, const uint8_t* __restrict__ keys,
+    const uint8_t* __restrict__ key_len, const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ sig_len,
+    const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ msg_off, uint32_t msg_len, uint64_t base,
+    uint64_t m, const uint8_t* __restrict__ pre_status, uint8_t* __restrict__ status, uint32_t* __restrict__ ws,
+    uint32_t empty_is_error) {
+  ecdsa_prep_body<false>(perm, scheme, keys, key_len, sigs, sig_len, msgs, msg_off, msg_len, base, m, pre_status,
+                         status, ws, empty_is_error);
 }
 
 // Montgomery's trick over chunk-relative slots [a, b) of one curve: prefix
@@ -1335,14 +1350,15 @@ CDEV void ecdsa_affine_lane(uint32_t* __restrict__ rec) {
 // amdgpu_waves_per_eu(2) is a lower bound on occupancy, i.e. a VGPR CAP of 256
 // for both (the allocation itself sets 3 waves for P-256); every budget >= 164
 // leaves room for fp29_asm.hpp's fixed accumulators v160..v163.
-template <int S>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) ecdsa_ladder_kernel(
-    const unsigned int* __restrict__ perm, const uint8_t* __restrict__ scheme, uint64_t base, uint64_t m,
-    const uint32_t* __restrict__ gtab, uint32_t* __restrict__ ws, uint8_t* __restrict__ status) {
+// The body serves two kernels, as ecdsa_prep_body does (kRouted: K15's instance).
+template <int S, bool kRouted>
+CDEV void ecdsa_ladder_body(const unsigned int* __restrict__ perm, const uint8_t* __restrict__ scheme, uint64_t base,
+                            uint64_t m, const uint32_t* __restrict__ gtab, uint32_t* __restrict__ ws,
+                            uint8_t* __restrict__ status) {
   const uint64_t li = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (li >= m) return;
   const uint64_t slot = base + li;
-  const uint64_t i = perm ? perm[slot] : slot;
+  const uint64_t i = kRouted ? perm[slot] : perm ? perm[slot] : slot;
   if (scheme[i] != S || status[i] != kEcPending) return;
   uint32_t* rec = ws + li * kEcWords;
   // table-to-affine pass fused into the ladder: as a kernel of its own its
@@ -1350,6 +1366,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) e
   // VALU-bound ladder of the SIMD's other waves (same thread writes, then reads)
   ecdsa_affine_lane<Curve<S>>(rec);
   status[i] = ecdsa_ladder_lane<Curve<S>>(rec, gtab);
+}
+
+template <int S>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) ecdsa_ladder_kernel(
+    const unsigned int* __restrict__ perm, const uint8_t* __restrict__ scheme, uint64_t base, uint64_t m,
+    const uint32_t* __restrict__ gtab, uint32_t* __restrict__ ws, uint8_t* __restrict__ status) {
+  ecdsa_ladder_body<S, false>(perm, scheme, base, m, gtab, ws, status);
 }
 
 // ---------------------------------------------------------------------------
@@ -1411,6 +1434,9 @@ hipError_t launch_ecdsa_verify(const uint8_t* scheme, const uint8_t* keys, const
 // K13, verification against registered keys: the kernels share this unit's device
 // functions (none of them changes; the generic kernels compile as before)
 #include "ecdsa_vkey.hip"
+// K15, routing to K13: the partition by key bytes and the indexed instances of K13 and
+// of this unit's prep and ladder
+#include "ecdsa_route.hip"
 #define CH_SAME_N(i) (kEcVkeyNK1[i] == K1N::limb(i) && kEcVkeyNR1[i] == R1N::limb(i))
 static_assert(CH_SAME_N(0) && CH_SAME_N(1) && CH_SAME_N(2) && CH_SAME_N(3) && CH_SAME_N(4) && CH_SAME_N(5) &&
                   CH_SAME_N(6) && CH_SAME_N(7),

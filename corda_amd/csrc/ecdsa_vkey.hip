@@ -131,17 +131,24 @@ CDEV int ec_vkey_fetch(f29& x, f29& y, const uint32_t* __restrict__ tab, const u
 // BAD_SIG, OK. A lane whose key is of the other curve is left to that curve's
 // instance. jmadd keeps its exceptional branches (accumulator equal to the
 // entry, its inverse, at infinity): a sum without doublings reaches them.
-template <int S>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) ecdsa_verify_keyed_kernel(
-    const uint32_t* __restrict__ key_id, const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ sig_len,
-    const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ moff, const uint32_t* __restrict__ mlen,
-    uint32_t msg_len, uint64_t n, const uint8_t* __restrict__ pre, uint32_t empty_is_error,
-    const uint32_t* __restrict__ vtab, uint8_t* __restrict__ status) {
+//
+// The body serves two kernels. kIdx false: K13 itself, lane i is thread i. kIdx true:
+// the routed instance (K15, ecdsa_route.hpp): thread j below n takes lane
+// i = list[j], key_id is the route array (indexed by lane), and moff is the generic
+// engine's CSR offsets (the message's length is moff[i + 1] - moff[i]; mlen unused).
+template <int S, bool kIdx>
+CDEV void ec_verify_keyed_lane(const uint32_t* __restrict__ key_id, const unsigned int* __restrict__ list,
+                               const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ sig_len,
+                               const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ moff,
+                               const uint32_t* __restrict__ mlen, uint32_t msg_len, uint64_t n,
+                               const uint8_t* __restrict__ pre, uint32_t empty_is_error,
+                               const uint32_t* __restrict__ vtab, uint8_t* __restrict__ status) {
   using C = Curve<S>;
   using N = typename C::N;
   using F = typename C::F;
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint64_t i = kIdx ? list[j] : j;
   __shared__ uint32_t sk[24][256];  // u1 and u2, biased, and r: only the thread's own column is read
   const uint32_t id = key_id[i];
   const uint32_t slot = vkey_slot(id);
@@ -157,7 +164,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) e
     }
     if (rec[kEcVkeyRecScheme] != (uint32_t)S) return;  // the other curve's instance decides
   }
-  const uint64_t ml = moff ? mlen[i] : msg_len;
+  const uint64_t ml = moff ? (kIdx ? moff[i + 1] - moff[i] : (uint64_t)mlen[i]) : msg_len;
   const uint8_t* msg = moff ? msgs + moff[i] : msgs + i * (uint64_t)msg_len;
   const uint8_t* sig = sigs + i * 72;
   uint32_t sl = sig_len[i];
@@ -245,6 +252,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) e
     st = x_check<C>(acc, r);
   }
   status[i] = st;
+}
+
+template <int S>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) ecdsa_verify_keyed_kernel(
+    const uint32_t* __restrict__ key_id, const uint8_t* __restrict__ sigs, const uint8_t* __restrict__ sig_len,
+    const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ moff, const uint32_t* __restrict__ mlen,
+    uint32_t msg_len, uint64_t n, const uint8_t* __restrict__ pre, uint32_t empty_is_error,
+    const uint32_t* __restrict__ vtab, uint8_t* __restrict__ status) {
+  ec_verify_keyed_lane<S, false>(key_id, nullptr, sigs, sig_len, msgs, moff, mlen, msg_len, n, pre, empty_is_error,
+                                 vtab, status);
 }
 
 // ---------------------------------------------------------------------------

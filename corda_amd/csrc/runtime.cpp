@@ -230,31 +230,102 @@ uint64_t env_lanes(const char* name, uint64_t dflt) {
   return x >= 64 ? x / 64 * 64 : dflt;
 }
 
+// The keyed half of a routed ECDSA enqueue (K15; d.ec_mu[slot] held, the slot's scratch
+// and perm large enough, s behind the slot's fence): under d.vkey_mu, as every keyed
+// call -- behind ec_vkeys.ev, followed by ec_vkeys.ev -- the gather, route and scatter
+// passes and K13 over each live curve's run. *routed stays false, and nothing is
+// launched, when no ECDSA key is live any more or the counters cannot be allocated:
+// the caller then takes the unrouted path, which is always right.
+static hipError_t ec_route_and_keyed(Device& d, EcWork& w, const uint8_t* scheme, const uint8_t* keys,
+                                     const uint8_t* key_len, const uint8_t* sigs, const uint8_t* sig_len,
+                                     const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len, uint64_t n,
+                                     const uint8_t* pre, uint8_t* status, uint32_t flags, hipStream_t s,
+                                     bool* routed) {
+  std::lock_guard<std::mutex> vk(d.vkey_mu);
+  const EcVkeyState& st = d.ec_vkey_state;
+  if (!d.ec_vkeys.tab.p || !(st.live[0] || st.live[1])) return hipSuccess;
+  if (!d.ec_vkeys.route_tot.p) {  // the device's first routed ECDSA enqueue
+    if (d.ec_vkeys.route_tot.ensure(16) != hipSuccess) {
+      (void)hipGetLastError();
+      return hipSuccess;
+    }
+    const hipError_t z = hipMemsetAsync(d.ec_vkeys.route_tot.p, 0, 16, s);
+    if (z != hipSuccess) return z;
+  }
+  *routed = true;
+  const uint32_t* vtab = d.ec_vkeys.tab.as<uint32_t>();
+  hipError_t e = d.ec_vkeys.ev.wait(s);
+  e = e ? e
+        : launch_ecdsa_route(scheme, keys, key_len, n, vtab, w.route.as<uint32_t>(), w.counters.as<unsigned int>(),
+                             w.perm.as<unsigned int>(), d.ec_vkeys.route_tot.as<unsigned long long>(), s);
+  e = e ? e
+        : launch_ecdsa_verify_keyed_idx(w.route.as<uint32_t>(), w.perm.as<unsigned int>(),
+                                        w.counters.as<unsigned int>(), n, sigs, sig_len, msgs, msg_off, msg_len, pre,
+                                        flags, vtab, st.live[0] > 0, st.live[1] > 0, status, s);
+  const hipError_t r = d.ec_vkeys.ev.record(s);  // whatever was launched is fenced, also after a failure
+  return e ? e : r;
+}
+
 // Enqueue ECDSA verification of n slot-layout lanes on stream s (device current,
 // d.ec_mu[slot] held): the slot's work buffers are reused only after their previous
 // user's kernels (on whatever stream) have finished.
+// With ECDSA routing on and a live ECDSA key (K15): gather, route and scatter, K13 over
+// each curve's keyed run, K2 over the generic list, the verdict words from the statuses
+// -- all on s, no count read back. Lock order: ec_mu[slot], then vkey_mu (Device,
+// runtime.hpp); vkey_mu is never held while this function waits for a lock, a fence or
+// an allocation.
 hipError_t ec_verify_enqueue(Device& d, const uint8_t* scheme, const uint8_t* keys, const uint8_t* key_len,
                              const uint8_t* sigs, const uint8_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off,
                              uint32_t msg_len, uint64_t n, const uint8_t* pre, uint8_t* status,
                              unsigned long long* verdict, uint32_t flags, hipStream_t s, int slot) {
   EcWork& w = d.ec[slot];
+  bool want_route = d.ec_route_on.load(std::memory_order_relaxed) && n && n <= ecdsa_route_max_lanes();
+  if (want_route) {  // a look at the registry; decided for good in ec_route_and_keyed
+    std::lock_guard<std::mutex> vk(d.vkey_mu);
+    want_route = d.ec_vkeys.tab.p && (d.ec_vkey_state.live[0] || d.ec_vkey_state.live[1]);
+  }
+  // the scratch grows in powers of two from a floor, behind the workspace's fence; no
+  // room for it: the batch is verified unrouted
+  const size_t sc_bytes = want_route ? ecdsa_route_scratch_bytes(n) : 0;
   // the budget's ECDSA share (cordahip_init); slot 1 serves the host pipelines'
   // alternate chunks and holds at most half of slot 0
   const uint64_t ws_slots = slot ? std::max<uint64_t>(64, d.ec_ws_slots / 2 / 64 * 64) : d.ec_ws_slots;
   const uint64_t slots = std::min<uint64_t>(ws_slots, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
   const uint64_t perm_bytes = std::max<uint64_t>(n, 1) * 4;
-  hipError_t e = w.ev.grow(w.ws.cap < slots * ecdsa_ws_slot_bytes() || w.perm.cap < perm_bytes, [&] {
-    const uint64_t want = std::max<uint64_t>(slots, std::min<uint64_t>(ws_slots, kWsMinLanes));
-    return w.ws.ensure(want * ecdsa_ws_slot_bytes()) || w.perm.ensure(perm_bytes) ? hipErrorOutOfMemory : hipSuccess;
+  const bool ws_needed = w.ws.cap < slots * ecdsa_ws_slot_bytes() || w.perm.cap < perm_bytes;
+  hipError_t e = w.ev.grow(ws_needed || w.route.cap < sc_bytes, [&] {
+    if (ws_needed) {
+      const uint64_t want = std::max<uint64_t>(slots, std::min<uint64_t>(ws_slots, kWsMinLanes));
+      if (w.ws.ensure(want * ecdsa_ws_slot_bytes()) || w.perm.ensure(perm_bytes)) return hipErrorOutOfMemory;
+    }
+    if (w.route.cap < sc_bytes && w.route.ensure(sc_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      want_route = false;
+    }
+    return hipSuccess;
   });
   if (e != hipSuccess) return e;
   if (w.counters.ensure(64)) return hipErrorOutOfMemory;
   e = w.ev.wait(s);
-  e = e ? e
-        : launch_ecdsa_verify(scheme, keys, key_len, sigs, sig_len, msgs, msg_off, msg_len, n,
-                              d.gtab_k1.as<uint32_t>(), d.gtab_r1.as<uint32_t>(), pre, status, verdict,
-                              w.counters.as<unsigned int>(), w.perm.as<unsigned int>(), w.ws.as<uint32_t>(),
-                              w.ws.cap / ecdsa_ws_slot_bytes() / 64 * 64, flags, s);
+  bool routed = false;
+  if (e == hipSuccess && want_route)
+    e = ec_route_and_keyed(d, w, scheme, keys, key_len, sigs, sig_len, msgs, msg_off, msg_len, n, pre, status, flags,
+                           s, &routed);
+  if (e == hipSuccess && routed) {
+    e = launch_ecdsa_verify_routed(scheme, keys, key_len, sigs, sig_len, msgs, msg_off, msg_len, n,
+                                   d.gtab_k1.as<uint32_t>(), d.gtab_r1.as<uint32_t>(), pre, status, verdict,
+                                   w.counters.as<unsigned int>(), w.perm.as<unsigned int>(), w.ws.as<uint32_t>(),
+                                   w.ws.cap / ecdsa_ws_slot_bytes() / 64 * 64, flags, s);
+  } else if (e == hipSuccess) {
+    e = launch_ecdsa_verify(scheme, keys, key_len, sigs, sig_len, msgs, msg_off, msg_len, n,
+                            d.gtab_k1.as<uint32_t>(), d.gtab_r1.as<uint32_t>(), pre, status, verdict,
+                            w.counters.as<unsigned int>(), w.perm.as<unsigned int>(), w.ws.as<uint32_t>(),
+                            w.ws.cap / ecdsa_ws_slot_bytes() / 64 * 64, flags, s);
+  }
+  if (routed) {  // whatever was launched is fenced, also after a failure
+    const hipError_t r = w.ev.record(s);
+    return e ? e : r;
+  }
   return e ? e : w.ev.record(s);
 }
 

@@ -166,6 +166,29 @@ hipError_t launch_ecdsa_verify_keyed(const uint32_t* key_id, const uint8_t* sigs
                                      uint64_t n, const uint8_t* pre, uint32_t flags, const uint32_t* vtab,
                                      bool live_k1, bool live_r1, uint8_t* status, unsigned long long* verdict,
                                      hipStream_t s);
+// K15 (ecdsa_route.hip, ecdsa_route.hpp): routed ECDSA batches. The route pass fills
+// `scratch` (ecdsa_route_scratch_bytes(n): the gathered records and route ids; at
+// least that large), the seven class counts and cursors in `counters` (64 bytes) and
+// perm[n] -- the generic list first, then each curve's keyed run -- and adds to the
+// device's cumulative counters; the indexed instances of K13 and K2 run over the
+// lists, their lane counts read on the device.
+size_t ecdsa_route_scratch_bytes(uint64_t n);  // a capacity: powers of two from a floor
+uint64_t ecdsa_route_max_lanes();              // larger batches are not routed (32-bit lane indices)
+hipError_t launch_ecdsa_route(const uint8_t* scheme, const uint8_t* keys, const uint8_t* key_len, uint64_t n,
+                              const uint32_t* vtab, uint32_t* scratch, unsigned int* counters, unsigned int* perm,
+                              unsigned long long* totals, hipStream_t s);
+hipError_t launch_ecdsa_verify_keyed_idx(const uint32_t* scratch, const unsigned int* perm,
+                                         const unsigned int* counters, uint64_t n, const uint8_t* sigs,
+                                         const uint8_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off,
+                                         uint32_t msg_len, const uint8_t* pre, uint32_t flags, const uint32_t* vtab,
+                                         bool live_k1, bool live_r1, uint8_t* status, hipStream_t s);
+hipError_t launch_ecdsa_verify_routed(const uint8_t* scheme, const uint8_t* keys, const uint8_t* key_len,
+                                      const uint8_t* sigs, const uint8_t* sig_len, const uint8_t* msgs,
+                                      const uint64_t* msg_off, uint32_t msg_len, uint64_t n, const uint32_t* gk1,
+                                      const uint32_t* gr1, const uint8_t* pre_status, uint8_t* status,
+                                      unsigned long long* verdict, const unsigned int* counters,
+                                      const unsigned int* perm, uint32_t* ws, uint64_t ws_slots, uint32_t flags,
+                                      hipStream_t s);
 // rsa.hip: rows of W = 64 / 96 / 128 little-endian words, one width per launch
 uint32_t rsa_group_lanes();  // lanes that share one signature in rsa_modexp_kernel
 hipError_t launch_rsa_public_op(const uint32_t* mod, const uint32_t* exp, const uint32_t* in, uint32_t W, uint64_t n,
@@ -410,12 +433,17 @@ constexpr int kTxSets = 2;
 struct EcWork {  // device buffers of the ECDSA paths (grow-only)
   DevBuf counters, perm;
   DevBuf ws;  // split-kernel workspace (kEcWsSlots records)
-  Fence ev;   // last enqueued user of counters/perm/ws (cross-stream reuse)
+  // the slot's routing scratch (K15, ecdsa_route.hpp: the gathered records and 4 bytes
+  // per lane, grown in powers of two), behind the same lock and fence, released with
+  // the workspace
+  DevBuf route;
+  Fence ev;  // last enqueued user of counters/perm/ws/route (cross-stream reuse)
   template <class V>
   void visit(V& v) {
     v.dev(counters, kKept);
     v.dev(perm, kFreed);
     v.dev(ws, kFreed);
+    v.dev(route, kFreed);
     v.fence(ev);
   }
 };
@@ -489,16 +517,21 @@ struct VerifyKeys {
 // 320 KiB, the two curves' base-point tables, the records and the build kernel's
 // scratch), allocated (records zeroed) by the context's first
 // cordahip_vkey_add_ecdsa and then handled exactly like VerifyKeys. stage: 128
-// page-locked bytes, the SEC1 bytes out and the decode verdict back.
+// page-locked bytes, the SEC1 bytes out and the decode verdict back. route_tot: the
+// device's cumulative counters of routed ECDSA lanes (K15: keyed, generic; two 64-bit
+// words, zeroed when allocated by the first routed enqueue), written by kernels
+// ordered by ev.
 struct EcVerifyKeys {
   DevBuf tab;
   PinBuf stage;
   Fence ev;
+  DevBuf route_tot;
   template <class V>
   void visit(V& v) {
     v.dev(tab, kKept);
     v.pin(stage, kKept);
     v.fence(ev);
+    v.dev(route_tot, kKept);
   }
 };
 // What the host knows of that table (Device::vkey_mu): base[c]: the base-point table of
@@ -677,10 +710,11 @@ struct Device {
   // lock it did not take before.
   // Lock order of the locks met on these paths, outermost first:
   //   ped_mu / stream_mu / a SetLease (the pipelines) -> ed_mu[0] -> ed_mu[1] ->
-  //   ... -> vkey_host_mu -> vkey_mu.
+  //   ec_mu[0] -> ec_mu[1] -> ... -> vkey_host_mu -> vkey_mu.
   // trim_device takes them in that order up to vkey_host_mu; a keyed host call holds
-  // vkey_host_mu and takes vkey_mu inside it; a routed enqueue holds ed_mu[slot] and
-  // takes vkey_mu inside it. vkey_mu is innermost: whoever holds it (add, remove, the
+  // vkey_host_mu and takes vkey_mu inside it; a routed enqueue holds ed_mu[slot]
+  // (Ed25519, K14) or ec_mu[slot] (ECDSA, K15) and takes vkey_mu inside it. vkey_mu is
+  // innermost: whoever holds it (add, remove, the
   // stats call, a keyed or routed enqueue) takes no other lock of the device but tmu
   // (the timing ring's, a leaf held for a few assignments), and a routed enqueue never
   // holds it while it waits for another lock, the slot's fence or the scratch's growth.
@@ -689,8 +723,14 @@ struct Device {
   std::atomic<uint32_t> route_on{0};
   // ECDSA verification against registered keys (K13): the tables of the same registry's
   // ECDSA keys, under the same vkey_mu, with a fence of their own.
+  // Routing (K15, cordahip_vkey_set_routing_ecdsa): with ec_route_on set and a live
+  // ECDSA key (ec_vkey_state.live), ec_verify_enqueue is a keyed call too: under the
+  // caller's ec_mu[slot] it takes vkey_mu for the route pass and the K13 launches --
+  // behind ec_vkeys.ev, followed by ec_vkeys.ev -- and drops it before the generic
+  // engine. With ec_route_on clear it takes no lock it did not take before.
   EcVerifyKeys ec_vkeys;
   EcVkeyState ec_vkey_state;
+  std::atomic<uint32_t> ec_route_on{0};
   // cordahip_verify_keyed's chunk stage: h/d[0] key ids, [1] signature rows, [2] host
   // pre-statuses, [3] messages, [4] their offsets, [5] their lengths, [6] statuses, [7]
   // verdict words, [8] signature lengths (cordahip_ecdsa_verify_keyed only, whose rows

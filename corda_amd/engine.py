@@ -187,6 +187,21 @@ class Engine:
               "cordahip_vkey_route_stats")
         return k.value, g.value
 
+    def vkey_set_routing_ecdsa(self, on: bool):
+        """cordahip_vkey_set_routing_ecdsa: on, every ECDSA batch (generic, signed-tx, dense, stream) sends
+        the lanes whose scheme and key bytes are a SEC1 encoding (04 || X || Y or (02 | Y & 1) || X) of a
+        registered ECDSA key's point to the keyed verifier, on the GPU; statuses are those of the unrouted
+        call. Off (the default): nothing changes. Ed25519 routing is a switch of its own."""
+        check(lib().cordahip_vkey_set_routing_ecdsa(self._ctx, 1 if on else 0), "cordahip_vkey_set_routing_ecdsa")
+
+    def vkey_route_stats_ecdsa(self, device: int = 0):
+        """cordahip_vkey_route_stats_ecdsa: (keyed_lanes, generic_lanes) that routed ECDSA enqueues on
+        `device` have sent each way since init; waits for the routed work already enqueued there."""
+        k, g = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().cordahip_vkey_route_stats_ecdsa(self._ctx, device, ctypes.byref(k), ctypes.byref(g)),
+              "cordahip_vkey_route_stats_ecdsa")
+        return k.value, g.value
+
     def verify_keyed_batch(self, key_ids: Sequence[int], sigs: Sequence[bytes], msgs: Sequence[bytes],
                            is_valid: bool = False, async_: bool = False):
         """cordahip_verify_keyed / cordahip_verify_keyed_submit: lane i checks sigs[i] over msgs[i] against

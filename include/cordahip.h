@@ -443,7 +443,9 @@ int cordahip_ed25519_verify_keyed_device(cordahip_ctx* ctx, int device, const vo
  * record; every other lane by the generic verifier as before. Nothing but the key
  * bytes enters the decision. A non-canonical encoding of a registered point
  * misses and stays generic (which decodes it to the same point); of two live
- * records with equal bytes either may serve; ECDSA records are never matched.
+ * records with equal bytes either may serve; ECDSA records are never matched
+ * by this switch (ECDSA lanes have one of their own: cordahip_vkey_set_routing_ecdsa
+ * below, kernel K15).
  * Every lane's status and verdict bit equal the unrouted call's under both flags
  * values; no lane of these calls ever answers CORDAHIP_VERIFY_UNKNOWN_KEY.
  * The partition runs on the caller's stream and the host reads no count back.
@@ -526,6 +528,61 @@ int cordahip_ecdsa_verify_keyed_submit(cordahip_ctx* ctx, const cordahip_keyed_s
 int cordahip_ecdsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_sigs,
                                        const void* d_sig_len, const void* d_msgs, uint32_t msg_len, uint64_t n,
                                        void* d_status, void* d_verdict, void* hip_stream);
+
+/* ---- Routing registered-key ECDSA lanes to the keyed verifier (kernel K15) ----
+ * What kernel K14 does for Ed25519 lanes, for ECDSA lanes and K13: the calls that
+ * carry key bytes -- cordahip_sig_verify / _submit, the host signed-tx calls,
+ * cordahip_ecdsa_verify_device, cordahip_stream_verify -- recognise the lanes of
+ * registered ECDSA keys themselves, on the GPU, and verify them with the keyed
+ * verifier above. A switch and counters of their own: cordahip_vkey_set_routing
+ * and cordahip_vkey_route_stats keep their meaning and stay Ed25519-only.
+ *
+ * cordahip_vkey_set_routing_ecdsa(ctx, on): on != 0 turns ECDSA routing on for
+ * every device of the context, 0 (the default) off. It takes effect with the next
+ * ECDSA batch enqueued. Off, every call does exactly what it did before this
+ * switch existed: nothing more is launched, allocated or locked (one relaxed
+ * atomic load decides).
+ *
+ * The rule, while ECDSA routing is on and the device holds at least one live ECDSA
+ * verification key: a lane is verified by the keyed verifier exactly when its
+ * scheme is 2 or 3 and equals the scheme of a live ECDSA record, and its key bytes
+ * are one of the two SEC1 encodings of that record's point: 65 bytes 04 || X || Y,
+ * or 33 bytes (02 | Y's low bit) || X, X and Y canonical (below p), big-endian.
+ * Nothing but the lane's scheme, key length and key bytes enters the decision.
+ * Both accepted encodings of a registered point match; hybrid encodings are not
+ * keys, so there is no third. Each of these misses and stays generic, which
+ * answers exactly what it answers today: a lane of the other scheme with the same
+ * bytes, 04 || X || p - Y (another point), 04 || X || Y + p (not a key), a
+ * compressed encoding with the wrong parity (another point), any other length.
+ * Of two live records of one scheme that hold the same point either may serve;
+ * Ed25519 records are never seen. Every lane's status and verdict bit equal the
+ * unrouted call's under both flags values (K13's own contract: it applies the
+ * host's pre-status, the doVerify EMPTY rule and the sig_len > 72 rule as the
+ * generic verifier does); no lane of these calls ever answers
+ * CORDAHIP_VERIFY_UNKNOWN_KEY.
+ * The partition runs on the caller's stream and the host reads no count back; the
+ * keyed lanes run as one launch per curve over that curve's lanes only, so a batch
+ * that mixes curves pays each curve's instance for its own lanes. It needs 4,672
+ * bytes and 4 bytes per lane of scratch per ECDSA workspace slot (the lanes grown
+ * in powers of two from 2^16), counted in cordahip_device_mem and released by
+ * cordahip_trim and the idle release with the workspace, and 16 bytes of counters
+ * per device, which are kept; the ECDSA key tables keep their size. A batch whose
+ * scratch does not fit in device memory is verified unrouted, not failed, as is
+ * one enqueued after the device's last ECDSA key was removed. Batches of 2^32
+ * lanes or more in one enqueue are not routed.
+ *
+ * Ordering: a routed batch is a keyed call. cordahip_vkey_remove waits for the
+ * routed batches already enqueued before it clears a record, so no record dies
+ * between a lane's match and its verification; an add or a remove that races a
+ * batch decides only which verifier a lane takes, never its status.
+ *
+ * cordahip_vkey_route_stats_ecdsa: the lanes that routed ECDSA enqueues on `device`
+ * have sent to the keyed and to the generic verifier since cordahip_init. Lanes
+ * verified while ECDSA routing was off, or while the device held no live ECDSA
+ * key, count in neither. The call waits for the routed work already enqueued on
+ * the device. A device the context does not have is CORDAHIP_ERR_INVALID_ARG. */
+int cordahip_vkey_set_routing_ecdsa(cordahip_ctx* ctx, uint32_t on);
+int cordahip_vkey_route_stats_ecdsa(cordahip_ctx* ctx, int device, uint64_t* keyed_lanes, uint64_t* generic_lanes);
 
 /* ECDSA keygen + sign (device memory), corpus generation: per lane scheme 2/3,
  * d = SHA-256(seed) mod n, k = SHA-256(seed || msg[:64]) mod n; writes the

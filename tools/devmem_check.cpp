@@ -197,9 +197,9 @@ int main() {
     // key table, which has a visit of its own (f)
     // and the verification keys' two mutexes and tables, visited with the signer's (f)
     // and the registered ECDSA keys' tables and what the host knows of them (f)
-    // and the routing switch (route_on, padded to 8 bytes)
+    // and the two routing switches (route_on, ec_route_on: each padded to 8 bytes)
     constexpr size_t kDeviceOwnPlain = 1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys) + 2 * sizeof(std::mutex) +
-                                       sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + sizeof(EcVkeyState) + 8;
+                                       sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + sizeof(EcVkeyState) + 16;
     const Count c = visited(*d, kDeviceOwnPlain + kTxSets * kTxSetPlain + kPackStages * kPackPlain, "Device");
     ndev = c.ndev, npin = c.npin, nev = c.nfence + c.nevent;
     CHECK(c.nstream == 7);
@@ -258,9 +258,10 @@ int main() {
     k->visit(gk);
     const size_t before = g.dev.size();
     k->visit_keys(gk);
-    // the three tables and the routed lanes' counters (VerifyKeys::route_tot)
-    CHECK(g.dev.size() == before + 4 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
+    // the three tables and the routed lanes' counters (VerifyKeys::route_tot, EcVerifyKeys::route_tot)
+    CHECK(g.dev.size() == before + 5 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
     CHECK(k->vkeys.route_tot.dev == 6 && k->vkeys.route_tot.p);
+    CHECK(k->ec_vkeys.route_tot.dev == 6 && k->ec_vkeys.route_tot.p);
     CHECK(k->vkeys.tab.dev == 6 && k->vkeys.tab.p && k->vkeys.stage.p && k->vkeys.ev.ev);
     CHECK(k->ec_vkeys.tab.dev == 6 && k->ec_vkeys.tab.p && k->ec_vkeys.stage.p && k->ec_vkeys.ev.ev);
     void *tab = k->keys.tab.p, *stage = k->keys.stage.p, *vtab = k->vkeys.tab.p, *vstage = k->vkeys.stage.p;
@@ -273,7 +274,8 @@ int main() {
     k->visit(kk);  // what the release walks: the same kept buffers as in b
     CHECK(kk.devs.size() == kept.devs.size());
     CHECK(mem_acct(6).in_use.load() ==
-          kk.bytes + k->keys.tab.cap + k->vkeys.tab.cap + k->vkeys.route_tot.cap + k->ec_vkeys.tab.cap);
+          kk.bytes + k->keys.tab.cap + k->vkeys.tab.cap + k->vkeys.route_tot.cap + k->ec_vkeys.tab.cap +
+              k->ec_vkeys.route_tot.cap);
     delete k;
     CHECK(g.clean() && mem_acct(6).in_use.load() == 0);
   }
