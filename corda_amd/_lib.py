@@ -48,6 +48,9 @@ EXPORTS = [
     "cordahip_ecdsa_verify_keyed_device",
     "cordahip_vkey_set_routing", "cordahip_vkey_route_stats",
     "cordahip_vkey_set_routing_ecdsa", "cordahip_vkey_route_stats_ecdsa",
+    "cordahip_commit_log_create", "cordahip_commit_log_destroy", "cordahip_commit_log_reserve",
+    "cordahip_commit_log_stats", "cordahip_commit_log_load", "cordahip_commit_log_lookup",
+    "cordahip_commit_inputs", "cordahip_commit_inputs_submit", "cordahip_commit_inputs_device",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
@@ -73,6 +76,12 @@ ERR_INVALID_ARG, ERR_OUT_OF_MEMORY = -1, -4
 VERIFY_UNKNOWN_KEY = 16
 VKEY_MAX_KEYS = 64  # live verification keys per context (a full registry: CORDAHIP_ERR_OUT_OF_MEMORY)
 VKEY_NO_ID = 0xFFFFFFFF  # the id cordahip_vkey_add_ed25519 reports for bytes that are not a key
+# notary commit log (cordahip_commit_inputs): tx_status besides OK; ref_state values; an absent window side
+COMMIT_CONFLICT, COMMIT_TIME_WINDOW_INVALID, COMMIT_SKIPPED = 16, 17, 18
+REF_ABSENT, REF_SELF, REF_OTHER = 0, 1, 2
+TW_SIDE_ABSENT = -(1 << 63)
+TW_SATURATE = 1 << 62  # window sides beyond +-2^62 ns are saturated there by the caller
+ERR_LOG_FULL = -9
 
 
 class EngineUnavailable(RuntimeError):
@@ -191,6 +200,37 @@ class KeyedSigBatch(ctypes.Structure):
         ("flags", ctypes.c_uint32),
         ("sig_bytes", ctypes.c_uint64), ("msg_bytes", ctypes.c_uint64),
     ]
+
+
+class StateRef(ctypes.Structure):
+    _fields_ = [("txhash", ctypes.c_uint8 * 32), ("index", ctypes.c_uint32)]
+
+
+class ConsumingTx(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_uint8 * 32), ("input_index", ctypes.c_uint32), ("caller", ctypes.c_uint32)]
+
+
+class CommitRow(ctypes.Structure):
+    _fields_ = [("ref", StateRef), ("by", ConsumingTx)]
+
+
+class CommitBatch(ctypes.Structure):
+    _fields_ = [
+        ("ntx", ctypes.c_uint64),
+        ("txid", ctypes.c_void_p), ("caller", ctypes.c_void_p),
+        ("refs", ctypes.c_void_p), ("tx_ref_off", ctypes.c_void_p), ("n_refs", ctypes.c_uint64),
+        ("tw_from", ctypes.c_void_p), ("tw_until", ctypes.c_void_p),
+        ("now_ns", ctypes.c_int64), ("tolerance_ns", ctypes.c_int64),
+        ("gate", ctypes.c_void_p),
+        ("tx_status", ctypes.c_void_p), ("committed", ctypes.c_void_p),
+        ("ref_state", ctypes.c_void_p), ("ref_by", ctypes.c_void_p),
+    ]
+
+
+# numpy images of cordahip_state_ref (36 bytes), cordahip_consuming_tx (40) and cordahip_commit_row (76)
+STATE_REF_DTYPE = np.dtype([("txhash", "u1", 32), ("index", "<u4")])
+CONSUMING_TX_DTYPE = np.dtype([("id", "u1", 32), ("input_index", "<u4"), ("caller", "<u4")])
+COMMIT_ROW_DTYPE = np.dtype([("ref", STATE_REF_DTYPE), ("by", CONSUMING_TX_DTYPE)])
 
 
 def pmt_slot_bound(m: int) -> int:
@@ -327,6 +367,15 @@ def lib() -> ctypes.CDLL:
         "cordahip_ecdsa_verify_keyed": (i32, [vp, ctypes.POINTER(KeyedSigBatch)]),
         "cordahip_ecdsa_verify_keyed_submit": (i32, [vp, ctypes.POINTER(KeyedSigBatch), ctypes.POINTER(u64)]),
         "cordahip_ecdsa_verify_keyed_device": (i32, [vp, i32, vp, vp, vp, vp, u32, u64, vp, vp, vp]),
+        "cordahip_commit_log_create": (i32, [vp, i32, u32, vp, ctypes.POINTER(u32)]),
+        "cordahip_commit_log_destroy": (i32, [vp, u32]),
+        "cordahip_commit_log_reserve": (i32, [vp, u32, u32]),
+        "cordahip_commit_log_stats": (i32, [vp, u32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "cordahip_commit_log_load": (i32, [vp, u32, vp, u64, ctypes.POINTER(u64)]),
+        "cordahip_commit_log_lookup": (i32, [vp, u32, vp, u64, vp, vp]),
+        "cordahip_commit_inputs": (i32, [vp, u32, ctypes.POINTER(CommitBatch)]),
+        "cordahip_commit_inputs_submit": (i32, [vp, u32, ctypes.POINTER(CommitBatch), ctypes.POINTER(u64)]),
+        "cordahip_commit_inputs_device": (i32, [vp, u32, ctypes.POINTER(CommitBatch), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(l, name)

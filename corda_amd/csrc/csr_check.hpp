@@ -143,6 +143,18 @@ bool check_keyed_sig_batch(Par&& par, const cordahip_keyed_sig_batch* b) {
   return ok.load();
 }
 
+// a commit batch (notary commit log): |now_ns| < 2^61 and 0 <= tolerance_ns < 2^61
+// (the time-window differences then cannot overflow), tw_from and tw_until both
+// given or both null, tx_ref_off[0..ntx] non-decreasing and within n_refs
+template <class Par>
+bool check_commit(Par&& par, const cordahip_commit_batch* b) {
+  const int64_t lim = (int64_t)1 << 61;
+  if (b->now_ns <= -lim || b->now_ns >= lim || b->tolerance_ns < 0 || b->tolerance_ns >= lim) return false;
+  if ((b->tw_from == nullptr) != (b->tw_until == nullptr)) return false;
+  if (b->ntx == 0) return true;
+  return b->tx_ref_off && csr_ok(par, b->tx_ref_off, 0, b->ntx, b->n_refs);
+}
+
 // a cover (required-signer coverage): tx_req_off[0..ntx] non-decreasing and
 // within nreq, req_tok_off over the required keys it spans within ntok, the
 // whole key table's ckey_off[0..nckey] within ckey_bytes (any leaf may name any

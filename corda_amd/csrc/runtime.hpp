@@ -22,9 +22,24 @@
 #include <vector>
 
 #include "../../include/cordahip.h"
+#include "commit_core.hpp"
 #include "numa_place.hpp"
 
 namespace cordahip {
+// commit_log.hip (K16): a commit call's launches (clamp, pre-pass, the claim / win /
+// lose rounds, in-order sweep, report; scratch: commit_scratch_bytes(ntx, n_refs);
+// entries: the log's entry counter), the
+// unfiltered lookup, the load (claim + insert; counters: entries, rows already present) and
+// the rehash of every entry into a new, zeroed table
+size_t commit_scratch_bytes(uint64_t ntx, uint64_t n_refs);
+hipError_t launch_commit_inputs(const commit::Table& T, commit::Batch B, uint64_t n_refs, uint64_t base, void* scratch,
+                                unsigned long long* entries, hipStream_t s);
+hipError_t launch_commit_lookup(const commit::Table& T, const uint32_t* refs, uint64_t n, uint8_t* present,
+                                uint32_t* by, hipStream_t s);
+size_t commit_load_scratch_bytes(uint64_t n);
+hipError_t launch_commit_load(const commit::Table& T, const uint32_t* rows, uint64_t n, void* scratch,
+                              unsigned long long* counters, hipStream_t s);
+hipError_t launch_commit_rehash(const commit::Table& from, const commit::Table& to, hipStream_t s);
 hipError_t launch_ed25519_btable(uint32_t* tab, hipStream_t s);
 size_t ed25519_btable_bytes();
 hipError_t launch_ed25519_verify(const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
@@ -828,6 +843,43 @@ struct Device {
   }
 };
 
+// One notary commit log (K16, cordahip_commit_log_*): the table of consumed StateRefs
+// on one device. Owned by the context's registry, not by the Device: cordahip_trim and
+// the idle release never see it; destroy and cordahip_shutdown free it. Its buffers are
+// counted in the device's account like every DevBuf. mu is held by every call on the
+// log while it enqueues (and by destroy / reserve / stats / load for their whole run);
+// ev follows each call's last kernel, and the next call's stream waits for it. bound:
+// the host's upper bound of the live entries; next_seq: the sequence number of the
+// next call's first transaction (loaded rows carry 0). counters: two 64-bit words on
+// the device (live entries; the last load's rows already present). scratch and the
+// stages grow only; stage_ev follows a host call's last copy. Ticketed commits take a
+// turn number at submit and run in that order (turn_mu / turn_cv).
+struct CommitLog {
+  uint32_t id = 0;
+  Device* dev = nullptr;
+  std::mutex mu;
+  DevBuf tab, counters, scratch, stage_d;
+  PinBuf stage_h;
+  Fence ev, stage_ev;
+  uint32_t capacity_log2 = 0;
+  uint64_t k0 = 0, k1 = 0;
+  uint64_t bound = 0;
+  uint64_t next_seq = 1;
+  std::mutex turn_mu;
+  std::condition_variable turn_cv;
+  uint64_t turn_next = 0, turn_now = 0;
+  commit::Table table() const { return commit::Table{tab.as<uint32_t>(), (1ull << capacity_log2) - 1, k0, k1}; }
+  ~CommitLog() {
+    if (dev) (void)hipSetDevice(dev->id);
+    (void)ev.sync();
+    (void)stage_ev.sync();
+    for (DevBuf* b : {&tab, &counters, &scratch, &stage_d}) b->release();
+    stage_h.release();
+    for (Fence* f : {&ev, &stage_ev})
+      if (f->ev) (void)hipEventDestroy(f->ev);
+  }
+};
+
 // The calling thread bound to a device's CPUs for a scope (its previous affinity
 // restored after): pipelines pack rows and first-touch pinned stages on the GPU's
 // NUMA node. No-op when the device has no placement.
@@ -1049,6 +1101,11 @@ struct cordahip_ctx {
   std::vector<uint32_t> vkey_gen;
   std::vector<uint8_t> vkey_live;
   uint32_t vkey_count = 0;
+  // the notary commit logs (cordahip_commit_log_create / _destroy): id -> log; ids
+  // count up and are never reused. logs_mu guards the map and the counter only.
+  std::mutex logs_mu;
+  std::unordered_map<uint32_t, std::shared_ptr<cordahip::rt::CommitLog>> logs;
+  uint32_t next_log_id = 1;
   std::thread reaper;
   std::mutex reaper_mu;
   std::condition_variable reaper_cv;

@@ -157,6 +157,140 @@ class Engine:
             gate.data_ptr() if gate is not None else None, sigs.data_ptr(), status.data_ptr(), s),
             "cordahip_ed25519_sign_keyed_device")
 
+    # ---- notary commit log (validateTimeWindow + commitInputStates per transaction) ----
+    def commit_log_create(self, capacity_log2: int, device: int = 0, salt: Optional[bytes] = None) -> int:
+        """cordahip_commit_log_create: an empty log of 2^capacity_log2 slots on `device`; salt: the
+        16 bytes that key the slot index (None: drawn by the library). Returns the log id."""
+        assert salt is None or len(salt) == 16
+        lid = ctypes.c_uint32()
+        check(lib().cordahip_commit_log_create(self._ctx, device, capacity_log2, salt, ctypes.byref(lid)),
+              "cordahip_commit_log_create")
+        return lid.value
+
+    def commit_log_destroy(self, log_id: int):
+        check(lib().cordahip_commit_log_destroy(self._ctx, log_id), "cordahip_commit_log_destroy")
+
+    def commit_log_reserve(self, log_id: int, capacity_log2: int):
+        """cordahip_commit_log_reserve: grow to 2^capacity_log2 slots and rehash on the device."""
+        check(lib().cordahip_commit_log_reserve(self._ctx, log_id, capacity_log2), "cordahip_commit_log_reserve")
+
+    def commit_log_stats(self, log_id: int):
+        """(entries, capacity, next_seq) once every call enqueued on the log has finished."""
+        e, c, s = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().cordahip_commit_log_stats(self._ctx, log_id, ctypes.byref(e), ctypes.byref(c), ctypes.byref(s)),
+              "cordahip_commit_log_stats")
+        return e.value, c.value, s.value
+
+    @staticmethod
+    def _state_refs(refs):
+        a = np.zeros(max(len(refs), 1), dtype=_lib.STATE_REF_DTYPE)
+        for i, (h, idx) in enumerate(refs):
+            a[i]["txhash"] = np.frombuffer(bytes(h), np.uint8)
+            a[i]["index"] = idx
+        return a
+
+    def commit_log_load(self, log_id: int, rows) -> int:
+        """cordahip_commit_log_load: rows = [((txhash, index), (txid, input_index, caller))], the
+        database's committed states at start-up. Returns how many were present already."""
+        n = len(rows)
+        a = np.zeros(max(n, 1), dtype=_lib.COMMIT_ROW_DTYPE)
+        for i, ((h, idx), (tid, pos, caller)) in enumerate(rows):
+            a[i]["ref"]["txhash"] = np.frombuffer(bytes(h), np.uint8)
+            a[i]["ref"]["index"] = idx
+            a[i]["by"]["id"] = np.frombuffer(bytes(tid), np.uint8)
+            a[i]["by"]["input_index"] = pos
+            a[i]["by"]["caller"] = caller
+        dup = ctypes.c_uint64()
+        check(lib().cordahip_commit_log_load(self._ctx, log_id, a.ctypes.data if n else None, n, ctypes.byref(dup)),
+              "cordahip_commit_log_load")
+        return dup.value
+
+    def commit_log_lookup(self, log_id: int, refs):
+        """cordahip_commit_log_lookup over refs = [(txhash, index)]: one entry per ref, None where
+        absent, else the stored (txid, input_index, caller)."""
+        n = len(refs)
+        a = self._state_refs(refs)
+        present = np.zeros(max(n, 1), dtype=np.uint8)
+        by = np.zeros(max(n, 1), dtype=_lib.CONSUMING_TX_DTYPE)
+        check(lib().cordahip_commit_log_lookup(self._ctx, log_id, a.ctypes.data if n else None, n,
+                                               present.ctypes.data, by.ctypes.data), "cordahip_commit_log_lookup")
+        return [(by[i]["id"].tobytes(), int(by[i]["input_index"]), int(by[i]["caller"])) if present[i] else None
+                for i in range(n)]
+
+    def commit_inputs(self, log_id: int, txs, now_ns: int = 0, tolerance_ns: int = 0, gate=None,
+                      async_: bool = False):
+        """cordahip_commit_inputs / _submit. txs[t] = (txid, caller, refs, window): txid 32 bytes,
+        caller the requesting party's id, refs = [(txhash, index)] in input order, window None or
+        (from_ns or None, until_ns or None) (sides beyond +-2^62 ns are saturated there). gate: a
+        status per transaction (nonzero: skip), e.g. filtered_tx_verify's.
+        Returns (tx_status[ntx], committed[ntx], ref_state, ref_by) with ref_state[t] / ref_by[t] one
+        entry per input of transaction t (ref_by: None where absent, else (txid, input_index, caller));
+        or, async_, a Ticket whose wait() returns them."""
+        n = len(txs)
+        assert gate is None or len(gate) == n
+        flat = [r for tx in txs for r in tx[2]]
+        nr = len(flat)
+        txid = np.frombuffer(b"".join(bytes(tx[0]) for tx in txs) or bytes(32), dtype=np.uint8).copy()
+        assert txid.size == max(n, 1) * 32
+        caller = np.ascontiguousarray(np.asarray([tx[1] for tx in txs] or [0], dtype=np.uint32))
+        refs = self._state_refs(flat)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            off[1:] = np.cumsum([len(tx[2]) for tx in txs], dtype=np.uint64)
+        fr = un = None
+        if any(tx[3] is not None for tx in txs):
+            def side(v):
+                return _lib.TW_SIDE_ABSENT if v is None else max(-_lib.TW_SATURATE, min(_lib.TW_SATURATE, int(v)))
+            fr = np.asarray([side(tx[3][0]) if tx[3] else _lib.TW_SIDE_ABSENT for tx in txs], dtype=np.int64)
+            un = np.asarray([side(tx[3][1]) if tx[3] else _lib.TW_SIDE_ABSENT for tx in txs], dtype=np.int64)
+        g = None if gate is None else np.ascontiguousarray(np.asarray(list(gate) or [0], dtype=np.uint8))
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        cm = np.zeros(max(n, 1), dtype=np.uint8)
+        rs = np.zeros(max(nr, 1), dtype=np.uint8)
+        rb = np.zeros(max(nr, 1), dtype=_lib.CONSUMING_TX_DTYPE)
+        b = _lib.CommitBatch(n, _ptr(txid), _ptr(caller), refs.ctypes.data if nr else None, _ptr(off), nr,
+                             _ptr(fr) if fr is not None else None, _ptr(un) if un is not None else None,
+                             now_ns, tolerance_ns, _ptr(g) if g is not None else None, _ptr(st), _ptr(cm),
+                             _ptr(rs), rb.ctypes.data)
+        keep = (txid, caller, refs, off, fr, un, g, st, cm, rs, rb, b)
+
+        def res():
+            states, bys = [], []
+            for t in range(n):
+                a, z = int(off[t]), int(off[t + 1])
+                states.append([int(x) for x in rs[a:z]])
+                bys.append([(rb[i]["id"].tobytes(), int(rb[i]["input_index"]), int(rb[i]["caller"])) if rs[i] else None
+                            for i in range(a, z)])
+            return st[:n], cm[:n], states, bys
+
+        if async_:
+            t = ctypes.c_uint64()
+            check(lib().cordahip_commit_inputs_submit(self._ctx, log_id, ctypes.byref(b), ctypes.byref(t)),
+                  "cordahip_commit_inputs_submit")
+            return Ticket(self, t.value, res, keep)
+        check(lib().cordahip_commit_inputs(self._ctx, log_id, ctypes.byref(b)), "cordahip_commit_inputs")
+        return res()
+
+    def commit_inputs_submit(self, log_id: int, txs, now_ns: int = 0, tolerance_ns: int = 0, gate=None):
+        """commit_inputs as a Ticket; tickets of one log commit in submit order."""
+        return self.commit_inputs(log_id, txs, now_ns, tolerance_ns, gate, async_=True)
+
+    def commit_inputs_device(self, log_id: int, txid, caller, refs, tx_ref_off, tx_status, committed, ref_state,
+                             ref_by, tw_from=None, tw_until=None, now_ns: int = 0, tolerance_ns: int = 0, gate=None,
+                             stream=None):
+        """cordahip_commit_inputs_device over device tensors on the log's device: txid uint8 [ntx, 32],
+        caller int32 [ntx], refs uint8 [n_refs, 36], tx_ref_off int64 [ntx + 1], tw_from / tw_until int64
+        [ntx] or None, gate uint8 [ntx] or None (typically the tx_status an earlier call on `stream`
+        wrote); outputs tx_status / committed uint8 [ntx], ref_state uint8 [n_refs], ref_by uint8
+        [n_refs, 40]. tx_status can go straight in as ed25519_sign_keyed_device's gate."""
+        s = stream.cuda_stream if stream is not None else 0
+        p = lambda x: x.data_ptr() if x is not None and x.numel() else None  # noqa: E731
+        b = _lib.CommitBatch(txid.shape[0], p(txid), p(caller), p(refs), p(tx_ref_off), refs.shape[0], p(tw_from),
+                             p(tw_until), now_ns, tolerance_ns, p(gate), p(tx_status), p(committed), p(ref_state),
+                             p(ref_by))
+        check(lib().cordahip_commit_inputs_device(self._ctx, log_id, ctypes.byref(b), s),
+              "cordahip_commit_inputs_device")
+
     # ---- Ed25519 verification against registered keys (Crypto.doVerify / isValid per lane) ----
     def vkey_add_ed25519(self, key: bytes):
         """cordahip_vkey_add_ed25519: the 32 key bytes decoded and their window table built on every

@@ -261,6 +261,115 @@ def verify_and_sign_filtered_transactions(engine, ftxs, key_id: int):
     return [int(x) for x in status], out
 
 
+_COMMIT_CONFLICT, _COMMIT_TIME_WINDOW_INVALID = 16, 17  # cordahip_commit_inputs tx statuses
+
+
+@dataclass
+class NotaryError:
+    """NotaryError (NotaryFlow.kt): kind is "TransactionInvalid", "TimeWindowInvalid" or "Conflict";
+    a Conflict carries tx_id and state_history = {(txhash, index): (txid, input_index, caller)},
+    the consumed inputs in input order (first occurrence of a ref), as the reference's signed
+    UniquenessProvider.Conflict lists them."""
+    kind: str
+    tx_id: Optional[bytes] = None
+    state_history: dict = field(default_factory=dict)
+
+
+def time_window_valid(window, now_ns: int, tolerance_ns: int) -> bool:
+    """TimeWindowChecker.isValid (TimeWindowChecker.kt:14-25) in exact nanoseconds: window None or
+    (from_ns or None, until_ns or None); invalid iff now - until > tolerance or from - now > tolerance."""
+    if window is None:
+        return True
+    lo, hi = window
+    return not ((hi is not None and now_ns - hi > tolerance_ns) or (lo is not None and lo - now_ns > tolerance_ns))
+
+
+def commit_input_states(log: dict, txs, now_ns: int = 0, tolerance_ns: int = 0, gate=None):
+    """The pure-Python mirror of Engine.commit_inputs: TrustedAuthorityNotaryService.validateTimeWindow
+    and commitInputStates (NotaryService.kt:44-47, :53-67) over PersistentUniquenessProvider.commit
+    (PersistentUniquenessProvider.kt:62-82), one transaction at a time in batch order against `log`
+    = {(txhash, index): (txid, input_index, caller)}, which it updates. txs and the result are
+    Engine.commit_inputs's: (tx_status, committed, ref_state, ref_by)."""
+    status, committed, states, bys = [], [], [], []
+    for t, (txid, caller, refs, window) in enumerate(txs):
+        txid, caller = bytes(txid), int(caller)
+        keys = [(bytes(h), int(i)) for h, i in refs]
+        st, cm = OK, 0
+        rs, rb = [0] * len(keys), [None] * len(keys)
+        if gate is not None and gate[t]:
+            st = 18
+        elif not time_window_valid(window, now_ns, tolerance_ns):
+            st = _COMMIT_TIME_WINDOW_INVALID
+        else:
+            history = {k: log[k] for k in keys if k in log}  # UniquenessProvider.Conflict.stateHistory
+            if not history:
+                for i, k in enumerate(keys):
+                    log[k] = (txid, i, caller)
+                cm = 1
+            else:
+                for i, k in enumerate(keys):
+                    if k in history:
+                        rb[i] = history[k]
+                        rs[i] = 1 if history[k] == (txid, i, caller) else 2
+                if 2 in rs:
+                    st = _COMMIT_CONFLICT
+        status.append(st)
+        committed.append(cm)
+        states.append(rs)
+        bys.append(rb)
+    return status, committed, states, bys
+
+
+def notarise_filtered_transactions(engine, log_id: int, ftxs, inputs, time_windows, callers, key_id: int,
+                                   now: int, tolerance: int):
+    """The batch form of NotaryFlow.Service.call (NotaryFlow.kt:98-104) for a non-validating notary:
+    Engine.filtered_tx_verify over the tear-offs (ftx.verify()), Engine.commit_inputs gated on its
+    statuses (validateTimeWindow, commitInputStates, in batch order against the commit log `log_id`),
+    Engine.sign_batch over the root hashes gated on the commit statuses (service.sign(txId.bytes)).
+
+    ftxs[t]: the tuple filtered_tx_verify takes, its root the transaction id; inputs[t]: the
+    tear-off's input StateRefs [(txhash, index)]; time_windows[t]: None or (from_ns or None, until_ns
+    or None); callers[t]: the requesting party's id; now / tolerance in ns.
+
+    Returns (answers, committed_rows). answers[t] is the 64-byte signature, or the NotaryError the
+    reference sends: TransactionInvalid for a tear-off that does not verify, TimeWindowInvalid,
+    Conflict with its state history. committed_rows lists ((txhash, index), (txid, input_index,
+    caller)) for every input state this call consumed -- what the caller persists BEFORE it releases
+    the signatures (a ref listed twice once, with the position the log stores: its last)."""
+    n = len(ftxs)
+    assert len(inputs) == len(time_windows) == len(callers) == n
+    if n == 0:
+        return [], []
+    ids = [bytes(f[2]) for f in ftxs]
+    verified = engine.filtered_tx_verify(ftxs)
+    txs = [(ids[t], callers[t], list(inputs[t]), time_windows[t]) for t in range(n)]
+    status, committed, ref_state, ref_by = engine.commit_inputs(log_id, txs, now, tolerance, gate=verified)
+    sigs, sst = engine.sign_batch([key_id] * n, ids, gate=status)
+    answers, rows = [], []
+    for t in range(n):
+        st = int(status[t])
+        if int(verified[t]) != OK:
+            answers.append(NotaryError("TransactionInvalid", ids[t]))
+        elif st == _COMMIT_TIME_WINDOW_INVALID:
+            answers.append(NotaryError("TimeWindowInvalid", ids[t]))
+        elif st == _COMMIT_CONFLICT:
+            hist = {}
+            for r, by in zip(inputs[t], ref_by[t]):
+                if by is not None:
+                    hist.setdefault((bytes(r[0]), int(r[1])), by)
+            answers.append(NotaryError("Conflict", ids[t], hist))
+        elif int(sst[t]) == _SIGN_UNKNOWN_KEY:
+            raise NoSuchElementException("no registered key %d" % key_id)
+        else:
+            answers.append(bytes(sigs[t]))
+        if committed[t]:
+            last = {}
+            for i, r in enumerate(inputs[t]):
+                last[(bytes(r[0]), int(r[1]))] = (ids[t], i, int(callers[t]))
+            rows.extend(last.items())
+    return answers, rows
+
+
 def validate_notary_signatures(engine, key_id: int, ids: Sequence[bytes], sigs: Sequence[bytes],
                                ecdsa: bool = False):
     """What a notary client does with the notary's answers (NotaryFlow.Client.call,

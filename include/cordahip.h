@@ -1075,6 +1075,118 @@ int cordahip_tx_cover_device(cordahip_ctx* ctx, int device, uint64_t ntx, void* 
                              const void* d_tx_sig_off, const void* d_sig_scheme, const void* d_sig_key,
                              const void* d_sig_key_off, const cordahip_cover* cover, void* hip_stream);
 
+/* ---- notary commit log: batched uniqueness check (K16) ------------------------ *
+ * The middle of NotaryFlow.Service.call (NotaryFlow.kt:98-104) for a batch:
+ * service.validateTimeWindow (NotaryService.kt:44-47, TimeWindowChecker.kt:14-25)
+ * and service.commitInputStates (NotaryService.kt:53-67 ->
+ * PersistentUniquenessProvider.commit, PersistentUniquenessProvider.kt:62-82) over
+ * a device-resident index of the consumed StateRefs and their ConsumingTx. A
+ * batch gets exactly the answers the serial provider gives when it takes the
+ * transactions one at a time in batch order, whatever the log held before. The
+ * log is the in-memory index the provider's map is: the database stays the
+ * durable record (the caller persists the rows of the transactions marked
+ * `committed`), and consensus is not touched.
+ *
+ * Per transaction t, in batch order:
+ *   gate[t] != 0                       CORDAHIP_COMMIT_SKIPPED, nothing looked up
+ *   time window invalid                CORDAHIP_COMMIT_TIME_WINDOW_INVALID, nothing
+ *     (until present and now - until > tolerance, or from present and
+ *      from - now > tolerance; exact in ns, exactly `tolerance` is valid)
+ *   no input in the log                every refs[i] -> (txid, i, caller) put in list
+ *                                      order (a ref listed twice keeps its LAST
+ *                                      position); OK, committed = 1; also with no inputs
+ *   every present input i stores exactly (txid, i, caller)
+ *                                      OK, committed = 0 (already committed: the
+ *                                      notary signs again), NOTHING inserted -- not
+ *                                      even inputs that were absent
+ *   otherwise                          CORDAHIP_COMMIT_CONFLICT, committed = 0,
+ *                                      nothing inserted
+ * ref_state[i] / ref_by[i] for the three last outcomes: 0 absent (zero row), 1
+ * consumed by exactly this (txid, i, caller), 2 consumed by another -- ref_by the
+ * stored record; the conflict's stateHistory is every input with ref_state != 0.
+ * Skipped and out-of-window transactions get zero rows.
+ *
+ * Chaining. OK is 0 for "committed" and "already committed" alike, so tx_status
+ * goes straight in as the signer's gate (cordahip_sign's gate,
+ * cordahip_ed25519_sign_keyed_device's d_gate), and `gate` takes
+ * cordahip_filtered_tx_verify's tx_status. With the device form nothing is read
+ * back to the host between the calls.
+ * Time bounds. tw_from / tw_until that do not fit are saturated by the caller at
+ * +-2^62 ns; INT64_MIN marks an absent side. |now_ns| < 2^61 and
+ * 0 <= tolerance_ns < 2^61, else CORDAHIP_ERR_INVALID_ARG: no difference overflows.
+ * Capacity. 2^capacity_log2 slots of 96 bytes (6 <= capacity_log2 <= 32), fixed
+ * between cordahip_commit_log_reserve calls. The host keeps an upper bound of the
+ * live entries: every commit call adds its n_refs and every load its n, whatever
+ * the outcomes; cordahip_commit_log_stats reads the exact count back and tightens
+ * the bound. A call whose bound would pass 7/8 of the capacity returns
+ * CORDAHIP_ERR_LOG_FULL before any enqueue, the log and the outputs untouched.
+ * Below that load linear probing always finds a slot: there is no per-transaction
+ * "full" status, and the device form never reads a counter back.
+ * Ordering. Calls on one log are serialised in enqueue order (a lock per log, and
+ * an event fence when the caller's stream differs from the previous call's); two
+ * tickets submitted one after the other from one thread commit in submit order
+ * (the ticket queue of a log is drained in order). destroy and reserve wait for
+ * every call already enqueued.
+ * Memory and ids. The table is counted in cordahip_device_mem; cordahip_trim and
+ * the idle release keep it (like the signer's table); destroy and
+ * cordahip_shutdown free it. A log id is never reused.
+ * Load. cordahip_commit_log_load inserts rows with sequence number 0, older than
+ * every batch; a row whose ref is present already (in the log, or earlier in the
+ * same call) is counted in *n_already_present and left alone.
+ * Devices. A log lives on the one device named at creation.
+ * The slot index is a keyed hash (SipHash-1-3) of the 36 ref bytes under the
+ * log's 128-bit salt (NULL: drawn by the library): ref bytes are client-chosen.
+ * CSR: tx_ref_off[0..ntx] non-decreasing and tx_ref_off[ntx] <= n_refs, checked
+ * whole before any enqueue (host forms). In the device form an offset beyond
+ * n_refs is cut to n_refs on the device, so no kernel indexes outside the arrays;
+ * device pointers are 8-byte aligned (uint64 / int64 arrays) or 4-byte aligned. */
+#define CORDAHIP_COMMIT_CONFLICT 16            /* NotaryError.Conflict (UniquenessException) */
+#define CORDAHIP_COMMIT_TIME_WINDOW_INVALID 17 /* NotaryError.TimeWindowInvalid */
+#define CORDAHIP_COMMIT_SKIPPED 18             /* gate[t] != 0 */
+#define CORDAHIP_ERR_LOG_FULL (-9)
+typedef struct { uint8_t txhash[32]; uint32_t index; } cordahip_state_ref;                       /* 36 B rows */
+typedef struct { uint8_t id[32]; uint32_t input_index; uint32_t caller; } cordahip_consuming_tx; /* 40 B rows */
+typedef struct { cordahip_state_ref ref; cordahip_consuming_tx by; } cordahip_commit_row;        /* 76 B rows */
+
+int cordahip_commit_log_create(cordahip_ctx* ctx, int device, uint32_t capacity_log2, const uint8_t salt[16],
+                               uint32_t* log_id);
+int cordahip_commit_log_destroy(cordahip_ctx* ctx, uint32_t log_id);
+/* grow + rehash on the device; a capacity_log2 at or below the current one changes nothing */
+int cordahip_commit_log_reserve(cordahip_ctx* ctx, uint32_t log_id, uint32_t capacity_log2);
+/* entries: live entries (exact); capacity: slots; next_seq: the sequence number of the next call's first transaction */
+int cordahip_commit_log_stats(cordahip_ctx* ctx, uint32_t log_id, uint64_t* entries, uint64_t* capacity,
+                              uint64_t* next_seq);
+int cordahip_commit_log_load(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_row* rows, uint64_t n,
+                             uint64_t* n_already_present);
+/* present[n] (0 / 1), by[n] (zero rows where absent): the log as it stands after every call enqueued before */
+int cordahip_commit_log_lookup(cordahip_ctx* ctx, uint32_t log_id, const cordahip_state_ref* refs, uint64_t n,
+                               uint8_t* present, cordahip_consuming_tx* by);
+
+typedef struct {
+  uint64_t ntx;
+  const uint8_t* txid;            /* [ntx*32] */
+  const uint32_t* caller;         /* [ntx] the JVM's id for the requesting Party; equal ids stand for equal Parties */
+  const cordahip_state_ref* refs; /* [n_refs] */
+  const uint64_t* tx_ref_off;     /* [ntx+1] into refs */
+  uint64_t n_refs;
+  const int64_t* tw_from;         /* [ntx] ns since the epoch, INT64_MIN = side absent; NULL with tw_until NULL: no windows */
+  const int64_t* tw_until;
+  int64_t now_ns, tolerance_ns;
+  const uint8_t* gate;            /* [ntx] nonzero: skip; may be NULL */
+  uint8_t* tx_status;             /* [ntx] out: OK / COMMIT_CONFLICT / COMMIT_TIME_WINDOW_INVALID / COMMIT_SKIPPED */
+  uint8_t* committed;             /* [ntx] out: 1 = this call inserted the transaction's refs (the rows to persist) */
+  uint8_t* ref_state;             /* [n_refs] out */
+  cordahip_consuming_tx* ref_by;  /* [n_refs] out */
+} cordahip_commit_batch;
+int cordahip_commit_inputs(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* batch);
+int cordahip_commit_inputs_submit(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* batch,
+                                  uint64_t* ticket);
+/* The device-resident form: `d_batch` is a HOST struct whose pointers are DEVICE
+ * memory on the log's device (as cordahip_tx_cover_device takes its cover).
+ * Stream-ordered on hip_stream; returns once enqueued. */
+int cordahip_commit_inputs_device(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* d_batch,
+                                  void* hip_stream);
+
 /* Device time (ms) of the calling thread's most recent *_device call on
  * `device`, from HIP events recorded around its launches on the stream it ran
  * on (waits for them); -1 if the thread made no such call. Each call gets its
