@@ -51,6 +51,7 @@ EXPORTS = [
     "cordahip_commit_log_create", "cordahip_commit_log_destroy", "cordahip_commit_log_reserve",
     "cordahip_commit_log_stats", "cordahip_commit_log_load", "cordahip_commit_log_lookup",
     "cordahip_commit_inputs", "cordahip_commit_inputs_submit", "cordahip_commit_inputs_device",
+    "cordahip_commit_log_revoke", "cordahip_commit_log_export",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
@@ -376,6 +377,8 @@ def lib() -> ctypes.CDLL:
         "cordahip_commit_inputs": (i32, [vp, u32, ctypes.POINTER(CommitBatch)]),
         "cordahip_commit_inputs_submit": (i32, [vp, u32, ctypes.POINTER(CommitBatch), ctypes.POINTER(u64)]),
         "cordahip_commit_inputs_device": (i32, [vp, u32, ctypes.POINTER(CommitBatch), vp]),
+        "cordahip_commit_log_revoke": (i32, [vp, u32, vp, u64, vp, ctypes.POINTER(u64)]),
+        "cordahip_commit_log_export": (i32, [vp, u32, u64, vp, vp, u64, ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(l, name)

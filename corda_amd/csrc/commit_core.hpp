@@ -14,9 +14,15 @@
 //   words 0-1   state = the entry's sequence number + 1 (little-endian pair), 0 = empty
 //   words 2-10  the StateRef (txhash[32], index)
 //   words 11-20 the ConsumingTx (id[32], input_index, caller)
-//   words 21-23 padding
-// An entry is never removed, and its key never changes, so a probe ends at the key
-// or at the first empty slot. The sequence number of transaction t of a batch is
+//   words 21-23 padding (word 21: the revoke mark, nonzero only between the two
+//               launches of one cordahip_commit_log_revoke)
+// An entry's key never changes, and an entry is removed only by
+// cordahip_commit_log_revoke (erase_at / erase_row below): backward-shift deletion, which
+// leaves the table as if the entry had never been put -- no tombstones, so every slot
+// between an entry's home and its slot stays occupied and a probe still ends at the key
+// or at the first empty slot. That is why find, put, insert_absent, the commit / load /
+// lookup / rehash kernels, the host's bound and the visibility rule below are the same
+// with removal as without it. The sequence number of transaction t of a batch is
 // base + t (base: the log's running transaction counter, >= 1; loaded rows carry 0):
 // a reader that belongs to transaction t sees an entry iff its sequence number is
 // below t's, i.e. state <= base + t -- the log as it stood when the serial provider
@@ -37,7 +43,7 @@ namespace cordahip {
 namespace commit {
 
 constexpr uint32_t kSlotWords = 24, kRefWords = 9, kByWords = 10;
-constexpr uint32_t kSlotRef = 2, kSlotBy = 11;
+constexpr uint32_t kSlotRef = 2, kSlotBy = 11, kSlotMark = 21;
 constexpr uint8_t kRefAbsent = 0, kRefSelf = 1, kRefOther = 2;
 // tx_status values (include/cordahip.h CORDAHIP_COMMIT_*)
 constexpr uint8_t kCommitOk = 0, kCommitConflict = 16, kCommitTimeWindowInvalid = 17, kCommitSkipped = 18;
@@ -157,6 +163,68 @@ COMMIT_HD int put(const Table& T, const uint32_t* ref, uint64_t state, const uin
 COMMIT_HD int load_row(const Table& T, const uint32_t* row) {
   if (find(T, row, kNoFilter) >= 0) return 0;
   return put(T, row, 1, row + kRefWords);
+}
+
+// The entry in slot i removed by backward shift: j walks forward from i to the first
+// empty slot; an entry at j whose home slot lies cyclically in (i, j] stays, any other
+// moves to i whole (state and padding included) and i becomes j; the last i is cleared
+// whole. Entries move only backwards, inside the run of occupied slots that held i.
+COMMIT_HD void erase_at(const Table& T, uint64_t i) {
+  uint64_t j = i;
+  for (uint64_t n = 0; n <= T.mask; n++) {
+    j = (j + 1) & T.mask;
+    if (slot_state(T, j) == 0) break;
+    const uint32_t* src = T.slots + j * kSlotWords;
+    const uint64_t home = hash_ref(src + kSlotRef, T.k0, T.k1) & T.mask;
+    if (((j - home) & T.mask) < ((j - i) & T.mask)) continue;  // home in (i, j]
+    uint32_t* dst = T.slots + i * kSlotWords;
+    for (uint32_t q = 0; q < kSlotWords; q++) dst[q] = src[q];
+    i = j;
+  }
+  uint32_t* w = T.slots + i * kSlotWords;
+  for (uint32_t q = 0; q < kSlotWords; q++) w[q] = 0;
+}
+
+// the 40 bytes stored in slot s equal `by`
+COMMIT_HD bool by_equal(const Table& T, uint64_t s, const uint32_t* by) {
+  const uint32_t* w = T.slots + s * kSlotWords + kSlotBy;
+  uint32_t d = 0;
+  for (uint32_t q = 0; q < kByWords; q++) d |= w[q] ^ by[q];
+  return d == 0;
+}
+
+// One row of cordahip_commit_log_revoke, rows taken in order: the entry of the row's
+// ref removed iff its stored ConsumingTx equals the row's in all 40 bytes (returns 1),
+// else nothing touched (returns 0). The kernels' mark + repair gives the same table;
+// this is its in-order statement.
+COMMIT_HD int erase_row(const Table& T, const uint32_t* row) {
+  const int64_t s = find(T, row, kNoFilter);
+  if (s < 0 || !by_equal(T, (uint64_t)s, row + kRefWords)) return 0;
+  erase_at(T, (uint64_t)s);
+  return 1;
+}
+
+// The repair of one cluster (a maximal cyclic run of occupied slots) that begins at
+// `start` (its predecessor is empty): every entry whose mark word is set is removed.
+// The cluster is measured first, then its original extent walked: erase_at at a marked
+// slot and the same position looked at again (a marked entry may have moved in), else
+// one step on, over the holes earlier shifts opened. Shifts stay inside the extent and
+// never write a slot that was empty when the walk began, so clusters are independent.
+// Returns the entries removed.
+COMMIT_HD uint64_t repair_cluster(const Table& T, uint64_t start) {
+  uint64_t len = 0;
+  while (len <= T.mask && slot_state(T, (start + len) & T.mask) != 0) len++;
+  uint64_t removed = 0;
+  for (uint64_t p = 0; p < len;) {
+    const uint64_t s = (start + p) & T.mask;
+    if (slot_state(T, s) != 0 && T.slots[s * kSlotWords + kSlotMark] != 0) {
+      erase_at(T, s);  // one entry fewer each time: at most len times in all
+      removed++;
+    } else {
+      p++;
+    }
+  }
+  return removed;
 }
 
 // TimeWindowChecker.isValid (:22-23), exact in nanoseconds. The caller saturates

@@ -41,14 +41,18 @@
 //            chains t_k ^ t_{k+1} != {} included, which defeat any round count
 //   report   one lane per transaction: statuses, committed bytes, ref_state / ref_by
 // cordahip_commit_log_load is claim + insert over its rows (each distinct new ref's first
-// row inserts it), cordahip_commit_log_reserve a rehash with the same insert.
+// row inserts it), cordahip_commit_log_reserve a rehash with the same insert,
+// cordahip_commit_log_revoke mark + repair (backward-shift deletion, one lane per
+// cluster), cordahip_commit_log_export one pass over the slots.
 // Visibility: within a launch lanes communicate only through 64-bit agent-scope
 // atomics -- the claim table's ordinals, the state word of a log slot, the counters.
 // Slot payloads are written with plain stores and read only by later launches. The
 // pre-pass, lose and the report only read the table; the sweep is one lane reading
 // its own stores; the rehash, like win, claims empty slots by compare-and-swap on
-// the state word and looks at no payload (every key of the old table is distinct).
-// Oracle: tests/commit_log_model.py.
+// the state word and looks at no payload (every key of the old table is distinct);
+// the revoke's mark launch changes only mark words (atomicOr), and its repair launch
+// is one lane per cluster reading its own stores.
+// Oracle: tests/commit_log_model.py (tests/commit_revoke_model.py for revoke / export).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -274,6 +278,79 @@ __global__ void __launch_bounds__(256) commit_rehash_kernel(Table from, Table to
   }
 }
 
+// cordahip_commit_log_revoke, two launches, one lane per row (commit_core.hpp's erase_row
+// is the in-order statement). mark: the row's ref is looked up and the stored
+// ConsumingTx compared; a match sets the slot's mark word (atomicOr: equal rows agree)
+// and walks back to the first slot of its cluster, which it claims by compare-and-swap
+// in a per-call scratch table keyed by that slot -- one matched row per cluster ends up
+// with the start in owned[i], every other row with kNoCluster. No state word changes in
+// this launch, so every lane measures the same clusters (the host keeps the load at or
+// below 7/8, so every cluster has an empty slot before it and the walk ends there). repair: the owner of a cluster
+// removes its marked entries (repair_cluster); clusters never share a slot that is
+// written, so the owners are independent. counters[0] is the log's entry count,
+// counters[1] the entries this call removed.
+constexpr unsigned long long kNoCluster = ~0ull;
+
+__global__ void __launch_bounds__(256) commit_revoke_mark_kernel(Table T, const uint32_t* __restrict__ rows,
+                                                                 uint64_t n, unsigned long long* __restrict__ claim,
+                                                                 uint64_t cmask, uint8_t* __restrict__ revoked,
+                                                                 unsigned long long* __restrict__ owned,
+                                                                 unsigned long long* __restrict__ counters) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) counters[1] = 0;
+  if (i >= n) return;
+  const uint32_t* row = rows + i * (kRefWords + kByWords);
+  const int64_t s = find(T, row, kNoFilter);
+  const bool hit = s >= 0 && by_equal(T, (uint64_t)s, row + kRefWords);
+  revoked[i] = hit;
+  unsigned long long mine = kNoCluster;
+  if (hit) {
+    atomicOr(T.slots + (uint64_t)s * kSlotWords + kSlotMark, 1u);
+    uint64_t start = (uint64_t)s;
+    for (uint64_t k = 0; k <= T.mask && slot_state(T, (start - 1) & T.mask) != 0; k++) start = (start - 1) & T.mask;
+    uint64_t c = (start * 0x9e3779b97f4a7c15ull >> 20) & cmask;
+    for (uint64_t k = 0; k <= cmask; k++, c = (c + 1) & cmask) {
+      const unsigned long long cur = atomicCAS(claim + c, kClaimEmpty, (unsigned long long)start);
+      if (cur == kClaimEmpty) mine = start;
+      if (cur == kClaimEmpty || cur == start) break;
+    }
+  }
+  owned[i] = mine;
+}
+
+__global__ void __launch_bounds__(256) commit_revoke_repair_kernel(Table T, uint64_t n,
+                                                                   const unsigned long long* __restrict__ owned,
+                                                                   unsigned long long* __restrict__ counters) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  long long removed = 0;
+  if (i < n && owned[i] != kNoCluster) removed = (long long)repair_cluster(T, owned[i]);
+  wave_add(counters, -removed);
+  wave_add(counters + 1, removed);
+}
+
+// cordahip_commit_log_export, one lane per slot: a live slot whose sequence number
+// (state - 1) is at least since_seq takes the next output index from *total -- one
+// atomic per wave, the lanes ranked by their position among the wave's takers -- and
+// writes its row and its sequence number when the index is below cap. *total ends as
+// the number of matching entries.
+__global__ void __launch_bounds__(256) commit_export_kernel(Table T, uint64_t since_seq, uint32_t* __restrict__ rows,
+                                                            uint64_t* __restrict__ seq, uint64_t cap,
+                                                            unsigned long long* __restrict__ total) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t st = i <= T.mask ? slot_state(T, i) : 0;
+  const bool take = st != 0 && st - 1 >= since_seq;
+  const unsigned long long takers = __ballot(take);
+  const uint32_t lane = threadIdx.x & 63;
+  unsigned long long first = 0;
+  if (lane == 0 && takers) first = atomicAdd(total, (unsigned long long)__popcll(takers));
+  first = __shfl(first, 0, 64);
+  const uint64_t at = first + (uint64_t)__popcll(takers & ((1ull << lane) - 1));
+  if (!take || at >= cap) return;
+  const uint32_t* w = T.slots + i * kSlotWords + kSlotRef;
+  for (uint32_t q = 0; q < kRefWords + kByWords; q++) rows[at * (kRefWords + kByWords) + q] = w[q];
+  seq[at] = st - 1;
+}
+
 // ---------------------------------------------------------------------------
 // host-side launchers (called by cordahip.cpp)
 static bool grid_of(uint64_t n, uint32_t* blocks) {
@@ -353,6 +430,32 @@ hipError_t launch_commit_load(const Table& T, const uint32_t* rows, uint64_t n, 
   hipLaunchKernelGGL(commit_load_claim_kernel, dim3(g), dim3(256), 0, s, T, rows, n, claim, cslots - 1, fresh, counters);
   hipLaunchKernelGGL(commit_load_insert_kernel, dim3(g), dim3(256), 0, s, T, rows, n, claim, cslots - 1, fresh,
                      counters);
+  return hipGetLastError();
+}
+
+// scratch a revoke of n rows needs: a cluster start per row, then the claim table
+size_t commit_revoke_scratch_bytes(uint64_t n) { return (size_t)(n * 8 + claim_slots(n) * 8); }
+
+hipError_t launch_commit_revoke(const Table& T, const uint32_t* rows, uint64_t n, uint8_t* revoked, void* scratch,
+                                unsigned long long* counters, hipStream_t s) {
+  uint32_t g;
+  if (n == 0 || !grid_of(n, &g)) return n ? hipErrorInvalidValue : hipSuccess;
+  unsigned long long* owned = static_cast<unsigned long long*>(scratch);
+  unsigned long long* claim = owned + n;
+  const uint64_t cslots = claim_slots(n);
+  if (const hipError_t e = hipMemsetAsync(claim, 0xff, cslots * 8, s)) return e;
+  hipLaunchKernelGGL(commit_revoke_mark_kernel, dim3(g), dim3(256), 0, s, T, rows, n, claim, cslots - 1, revoked, owned,
+                     counters);
+  hipLaunchKernelGGL(commit_revoke_repair_kernel, dim3(g), dim3(256), 0, s, T, n, owned, counters);
+  return hipGetLastError();
+}
+
+hipError_t launch_commit_export(const Table& T, uint64_t since_seq, uint32_t* rows, uint64_t* seq, uint64_t cap,
+                                unsigned long long* total, hipStream_t s) {
+  uint32_t g;
+  if (!grid_of(T.mask + 1, &g)) return hipErrorInvalidValue;
+  if (const hipError_t e = hipMemsetAsync(total, 0, 8, s)) return e;
+  hipLaunchKernelGGL(commit_export_kernel, dim3(g), dim3(256), 0, s, T, since_seq, rows, seq, cap, total);
   return hipGetLastError();
 }
 

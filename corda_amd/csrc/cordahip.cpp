@@ -1998,6 +1998,101 @@ int commit_log_lookup_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_st
   return CORDAHIP_SUCCESS;
 }
 
+// A synchronous call's turn among the log's tickets: taken at construction behind every
+// ticket submitted so far, given up at destruction (commit_submit_impl's jobs wait the
+// same way, so a later ticket runs after the call).
+class CommitTurn {
+ public:
+  explicit CommitTurn(CommitLog& L) : L_(L) {
+    std::unique_lock<std::mutex> w(L_.turn_mu);
+    const uint64_t turn = L_.turn_next++;
+    L_.turn_cv.wait(w, [&] { return L_.turn_now == turn; });
+  }
+  ~CommitTurn() {
+    {
+      std::lock_guard<std::mutex> w(L_.turn_mu);
+      L_.turn_now++;
+    }
+    L_.turn_cv.notify_all();
+  }
+  CommitTurn(const CommitTurn&) = delete;
+  CommitTurn& operator=(const CommitTurn&) = delete;
+
+ private:
+  CommitLog& L_;
+};
+
+int commit_log_revoke_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_row* rows, uint64_t n,
+                           uint8_t* revoked, uint64_t* n_removed) {
+  const auto L = log_at(ctx, log_id);
+  if (!L || (n && (!rows || !revoked))) return CORDAHIP_ERR_INVALID_ARG;
+  if (n_removed) *n_removed = 0;
+  if (n == 0) return CORDAHIP_SUCCESS;
+  const CommitTurn turn(*L);
+  std::lock_guard<std::mutex> g(L->mu);
+  Device& d = *L->dev;
+  const Activity act(d);
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  const size_t o_rev = (n * kCommitRowBytes + 15) & ~(size_t)15, o_cnt = (o_rev + n + 15) & ~(size_t)15;
+  if (const int rc = commit_stage(*L, o_cnt + 8)) return rc;
+  const size_t need = commit_revoke_scratch_bytes(n);
+  if (L->ev.grow(need > L->scratch.cap, [&] { return L->scratch.ensure(need); }) != hipSuccess)
+    return CORDAHIP_ERR_OUT_OF_MEMORY;
+  uint8_t *h = L->stage_h.as<uint8_t>(), *dv = L->stage_d.as<uint8_t>();
+  std::memcpy(h, rows, n * kCommitRowBytes);
+  hipStream_t s = d.stream;
+  unsigned long long* ctr = L->counters.as<unsigned long long>();
+  hipError_t e = hipMemcpyAsync(dv, h, n * kCommitRowBytes, hipMemcpyHostToDevice, s);
+  e = e ? e : L->ev.wait(s);
+  e = e ? e : launch_commit_revoke(L->table(), reinterpret_cast<const uint32_t*>(dv), n, dv + o_rev, L->scratch.p, ctr, s);
+  e = e ? e : L->ev.record(s);
+  e = e ? e : hipMemcpyAsync(h + o_rev, dv + o_rev, n, hipMemcpyDeviceToHost, s);
+  e = e ? e : hipMemcpyAsync(h + o_cnt, ctr + 1, 8, hipMemcpyDeviceToHost, s);
+  const hipError_t f = hipStreamSynchronize(s);
+  if (e != hipSuccess || f != hipSuccess) return CORDAHIP_ERR_HIP;
+  std::memcpy(revoked, h + o_rev, n);
+  if (n_removed) std::memcpy(n_removed, h + o_cnt, 8);
+  return CORDAHIP_SUCCESS;  // the bound stays: it remains an upper bound of the live entries
+}
+
+int commit_log_export_impl(cordahip_ctx* ctx, uint32_t log_id, uint64_t since_seq, cordahip_commit_row* rows,
+                           uint64_t* seq, uint64_t cap, uint64_t* n_total) {
+  const auto L = log_at(ctx, log_id);
+  if (!L || !n_total || (cap && !rows)) return CORDAHIP_ERR_INVALID_ARG;
+  const CommitTurn turn(*L);
+  std::lock_guard<std::mutex> g(L->mu);
+  Device& d = *L->dev;
+  const Activity act(d);
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  cap = std::min(cap, L->bound);  // no more entries than the bound are live: slots past it are never written
+  const size_t o_seq = (cap * kCommitRowBytes + 15) & ~(size_t)15, o_cnt = o_seq + cap * 8;
+  if (const int rc = commit_stage(*L, o_cnt + 8)) return rc;
+  uint8_t *h = L->stage_h.as<uint8_t>(), *dv = L->stage_d.as<uint8_t>();
+  hipStream_t s = d.stream;
+  unsigned long long* total = reinterpret_cast<unsigned long long*>(dv + o_cnt);
+  hipError_t e = L->ev.wait(s);
+  e = e ? e
+        : launch_commit_export(L->table(), since_seq, reinterpret_cast<uint32_t*>(dv),
+                               reinterpret_cast<uint64_t*>(dv + o_seq), cap, total, s);
+  e = e ? e : L->ev.record(s);
+  e = e ? e : hipMemcpyAsync(h + o_cnt, total, 8, hipMemcpyDeviceToHost, s);
+  hipError_t f = hipStreamSynchronize(s);
+  if (e != hipSuccess || f != hipSuccess) return CORDAHIP_ERR_HIP;
+  uint64_t total_h = 0;
+  std::memcpy(&total_h, h + o_cnt, 8);
+  const uint64_t m = std::min(total_h, cap);
+  if (m) {  // only what was written comes back
+    e = hipMemcpyAsync(h, dv, m * kCommitRowBytes, hipMemcpyDeviceToHost, s);
+    e = e ? e : hipMemcpyAsync(h + o_seq, dv + o_seq, m * 8, hipMemcpyDeviceToHost, s);
+    f = hipStreamSynchronize(s);
+    if (e != hipSuccess || f != hipSuccess) return CORDAHIP_ERR_HIP;
+    std::memcpy(rows, h, m * kCommitRowBytes);
+    if (seq) std::memcpy(seq, h + o_seq, m * 8);
+  }
+  *n_total = total_h;
+  return CORDAHIP_SUCCESS;
+}
+
 // The commit kernels on stream s behind the log's previous call, followed by the
 // log's fence; the log's counters advance (mu held, device current, the scratch
 // grown, the load bound checked).
@@ -2579,6 +2674,18 @@ int cordahip_commit_log_lookup(cordahip_ctx* ctx, uint32_t log_id, const cordahi
                                uint8_t* present, cordahip_consuming_tx* by) {
   if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
   return guarded([&] { return commit_log_lookup_impl(ctx, log_id, refs, n, present, by); });
+}
+
+int cordahip_commit_log_revoke(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_row* rows, uint64_t n,
+                               uint8_t* revoked, uint64_t* n_removed) {
+  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return commit_log_revoke_impl(ctx, log_id, rows, n, revoked, n_removed); });
+}
+
+int cordahip_commit_log_export(cordahip_ctx* ctx, uint32_t log_id, uint64_t since_seq, cordahip_commit_row* rows,
+                               uint64_t* seq, uint64_t cap, uint64_t* n_total) {
+  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return commit_log_export_impl(ctx, log_id, since_seq, rows, seq, cap, n_total); });
 }
 
 int cordahip_commit_inputs(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* batch) {

@@ -40,6 +40,13 @@ size_t commit_load_scratch_bytes(uint64_t n);
 hipError_t launch_commit_load(const commit::Table& T, const uint32_t* rows, uint64_t n, void* scratch,
                               unsigned long long* counters, hipStream_t s);
 hipError_t launch_commit_rehash(const commit::Table& from, const commit::Table& to, hipStream_t s);
+// the revoke (mark + per-cluster repair; counters: entries, entries removed by this call)
+// and the export of the live entries with a sequence number >= since_seq (*total: how many)
+size_t commit_revoke_scratch_bytes(uint64_t n);
+hipError_t launch_commit_revoke(const commit::Table& T, const uint32_t* rows, uint64_t n, uint8_t* revoked,
+                                void* scratch, unsigned long long* counters, hipStream_t s);
+hipError_t launch_commit_export(const commit::Table& T, uint64_t since_seq, uint32_t* rows, uint64_t* seq,
+                                uint64_t cap, unsigned long long* total, hipStream_t s);
 hipError_t launch_ed25519_btable(uint32_t* tab, hipStream_t s);
 size_t ed25519_btable_bytes();
 hipError_t launch_ed25519_verify(const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,

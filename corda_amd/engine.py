@@ -189,21 +189,59 @@ class Engine:
             a[i]["index"] = idx
         return a
 
-    def commit_log_load(self, log_id: int, rows) -> int:
-        """cordahip_commit_log_load: rows = [((txhash, index), (txid, input_index, caller))], the
-        database's committed states at start-up. Returns how many were present already."""
-        n = len(rows)
-        a = np.zeros(max(n, 1), dtype=_lib.COMMIT_ROW_DTYPE)
+    @staticmethod
+    def _commit_rows(rows):
+        a = np.zeros(max(len(rows), 1), dtype=_lib.COMMIT_ROW_DTYPE)
         for i, ((h, idx), (tid, pos, caller)) in enumerate(rows):
             a[i]["ref"]["txhash"] = np.frombuffer(bytes(h), np.uint8)
             a[i]["ref"]["index"] = idx
             a[i]["by"]["id"] = np.frombuffer(bytes(tid), np.uint8)
             a[i]["by"]["input_index"] = pos
             a[i]["by"]["caller"] = caller
+        return a
+
+    def commit_log_load(self, log_id: int, rows) -> int:
+        """cordahip_commit_log_load: rows = [((txhash, index), (txid, input_index, caller))], the
+        database's committed states at start-up. Returns how many were present already."""
+        n = len(rows)
+        a = self._commit_rows(rows)
         dup = ctypes.c_uint64()
         check(lib().cordahip_commit_log_load(self._ctx, log_id, a.ctypes.data if n else None, n, ctypes.byref(dup)),
               "cordahip_commit_log_load")
         return dup.value
+
+    def commit_log_revoke(self, log_id: int, rows):
+        """cordahip_commit_log_revoke: rows as commit_log_load takes them -- the rows of `committed`
+        transactions whose database write failed. A row removes its ref's entry iff the stored
+        (txid, input_index, caller) is exactly the row's. Returns (revoked, n_removed): a 0 / 1 per
+        row, and the entries removed (equal rows count once)."""
+        n = len(rows)
+        a = self._commit_rows(rows)
+        revoked = np.zeros(max(n, 1), dtype=np.uint8)
+        removed = ctypes.c_uint64()
+        check(lib().cordahip_commit_log_revoke(self._ctx, log_id, a.ctypes.data if n else None, n,
+                                               revoked.ctypes.data if n else None, ctypes.byref(removed)),
+              "cordahip_commit_log_revoke")
+        return [int(x) for x in revoked[:n]], removed.value
+
+    def commit_log_export(self, log_id: int, since_seq: int = 0):
+        """cordahip_commit_log_export: [((txhash, index), (txid, input_index, caller), seq)] for every
+        live entry whose sequence number is >= since_seq, in no particular order (a counting call
+        first, then the call that fetches; both see the same log unless another thread changes it
+        in between, in which case the rows that fitted are returned)."""
+        total = ctypes.c_uint64()
+        check(lib().cordahip_commit_log_export(self._ctx, log_id, since_seq, None, None, 0, ctypes.byref(total)),
+              "cordahip_commit_log_export")
+        cap = total.value
+        if cap == 0:
+            return []
+        a = np.zeros(cap, dtype=_lib.COMMIT_ROW_DTYPE)
+        seq = np.zeros(cap, dtype=np.uint64)
+        check(lib().cordahip_commit_log_export(self._ctx, log_id, since_seq, a.ctypes.data, seq.ctypes.data, cap,
+                                               ctypes.byref(total)), "cordahip_commit_log_export")
+        return [((a[i]["ref"]["txhash"].tobytes(), int(a[i]["ref"]["index"])),
+                 (a[i]["by"]["id"].tobytes(), int(a[i]["by"]["input_index"]), int(a[i]["by"]["caller"])), int(seq[i]))
+                for i in range(min(cap, total.value))]
 
     def commit_log_lookup(self, log_id: int, refs):
         """cordahip_commit_log_lookup over refs = [(txhash, index)]: one entry per ref, None where

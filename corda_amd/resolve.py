@@ -370,6 +370,28 @@ def notarise_filtered_transactions(engine, log_id: int, ftxs, inputs, time_windo
     return answers, rows
 
 
+def notarise_filtered_transactions_persisted(engine, log_id: int, ftxs, inputs, time_windows, callers, key_id: int,
+                                             now: int, tolerance: int, persist):
+    """notarise_filtered_transactions with the database write inside the call, as the reference's
+    commit runs inside the flow's database transaction (PersistentUniquenessProvider.kt:62-82 over
+    AbstractJDBCHashMap): persist(committed_rows) is called before anything is returned. If it
+    raises, exactly those rows are revoked (Engine.commit_log_revoke: the log is again the log the
+    database describes, every row must have been revoked) and the exception is re-raised -- no
+    answer, and so no signature, leaves the call. Answers of a later batch on the same log must not
+    be released while this one's rows are neither persisted nor revoked.
+
+    Returns (answers, committed_rows) as notarise_filtered_transactions does."""
+    answers, rows = notarise_filtered_transactions(engine, log_id, ftxs, inputs, time_windows, callers, key_id,
+                                                   now, tolerance)
+    try:
+        persist(rows)
+    except BaseException:
+        revoked, removed = engine.commit_log_revoke(log_id, rows)
+        assert all(revoked) and removed == len(rows), "rows of a failed write that the log no longer holds"
+        raise
+    return answers, rows
+
+
 def validate_notary_signatures(engine, key_id: int, ids: Sequence[bytes], sigs: Sequence[bytes],
                                ecdsa: bool = False):
     """What a notary client does with the notary's answers (NotaryFlow.Client.call,

@@ -1161,6 +1161,42 @@ int cordahip_commit_log_load(cordahip_ctx* ctx, uint32_t log_id, const cordahip_
 /* present[n] (0 / 1), by[n] (zero rows where absent): the log as it stands after every call enqueued before */
 int cordahip_commit_log_lookup(cordahip_ctx* ctx, uint32_t log_id, const cordahip_state_ref* refs, uint64_t n,
                                uint8_t* present, cordahip_consuming_tx* by);
+/* Revoke: take back rows the caller could not persist (the database write failed while
+ * the process lives -- what a rollback of the reference's JDBC-backed map does,
+ * PersistentUniquenessProvider.kt:62-82). rows[i] = (ref, by) is a row as the caller was
+ * about to persist it (cordahip_commit_log_load's shape; a ref listed twice carries its
+ * LAST position). Row i removes the entry of `ref` iff the log holds `ref` and the stored
+ * ConsumingTx equals `by` in all 40 bytes (id, input_index, caller): revoked[i] = 1.
+ * Otherwise (absent ref, another id, position or caller) revoked[i] = 0 and the entry,
+ * if any, is untouched. Equal rows repeated in one call all get 1 and remove the entry
+ * once: *n_removed (may be NULL) counts entries, not rows. Loaded rows (sequence number
+ * 0) are revocable on the same terms. Afterwards the log is, through every entry point,
+ * the log into which the removed entries were never put: lookups say absent, the same
+ * transaction commits again with committed = 1, another transaction spending the ref
+ * commits, cordahip_commit_log_stats reports `entries` lower by *n_removed. next_seq does
+ * not move, and the host's upper bound stays where it is until the next _stats call.
+ * A host form (host pointers) that returns when done; it runs behind every call already
+ * enqueued on the log, on any stream, and behind every ticket of
+ * cordahip_commit_inputs_submit submitted before it. n == 0 is a successful no-op.
+ * CORDAHIP_ERR_INVALID_ARG before any enqueue: NULL ctx, unknown or destroyed log id,
+ * NULL rows / revoked with n > 0. */
+int cordahip_commit_log_revoke(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_row* rows, uint64_t n,
+                               uint8_t* revoked /* [n] out */, uint64_t* n_removed /* may be NULL */);
+/* Export: the `snapshot` half of the replicated notaries' snapshot / install
+ * (DistributedImmutableMap.kt:80-98, BFTSMaRt.kt:240-249; cordahip_commit_log_load is
+ * install). Every live entry whose sequence number is >= since_seq (0: everything):
+ * a loaded row carries 0, and transaction t of a commit call carries N + t, N being the
+ * next_seq cordahip_commit_log_stats reported before that call -- so since_seq = a
+ * next_seq read earlier exports exactly what the calls since then inserted (and nobody
+ * revoked). *n_total is the number of matching entries; the first min(*n_total, cap)
+ * slots of rows (and of seq, which may be NULL) are written and nothing beyond them.
+ * *n_total > cap is not an error: size cap from _stats and call again; cap == 0 with
+ * NULL rows only counts. THE ORDER OF THE ROWS IS UNSPECIFIED (it is neither insertion
+ * nor sequence order, and differs between calls). Ordered on the log like revoke.
+ * CORDAHIP_ERR_INVALID_ARG: NULL ctx or n_total, unknown log id, NULL rows with cap > 0. */
+int cordahip_commit_log_export(cordahip_ctx* ctx, uint32_t log_id, uint64_t since_seq,
+                               cordahip_commit_row* rows /* [cap] out */, uint64_t* seq /* [cap] out, may be NULL */,
+                               uint64_t cap, uint64_t* n_total /* out */);
 
 typedef struct {
   uint64_t ntx;
