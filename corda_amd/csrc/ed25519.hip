@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "ed25519_half.hpp"
 #include "ed25519_ops.hpp"
 #include "ed25519_route.hpp"
 #include "ed25519_ws.hpp"
@@ -78,102 +79,11 @@ __global__ void __launch_bounds__(64) ed25519_btable_kernel(uint32_t* __restrict
 // stopped below sqrt(8L), gives |c0|, |c1| ~ 2^128: the ladder needs ~128
 // doublings instead of ~252 (idea: T. Pornin, ePrint 2020/454). The
 // equivalence is checked on the golden catalogue in tools/proto/half_scalar.py.
-// a >= b as the absence of a borrow out of a - b (branch-free: a
-// short-circuit word compare becomes divergent control flow on the GPU)
-CDEV bool mp8_ge(const uint32_t a[8], const uint32_t b[8]) {
-  uint32_t br = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) br = (uint32_t)(((uint64_t)a[i] - b[i] - br) >> 63);
-  return br == 0;
-}
-CDEV void mp8_add(uint32_t r[8], const uint32_t a[8], const uint32_t b[8]) {
-  uint64_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    c += (uint64_t)a[i] + b[i];
-    r[i] = (uint32_t)c;
-    c >>= 32;
-  }
-}
-CDEV void mp8_neg(uint32_t a[8]) {
-  uint64_t c = 1;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    c += (uint64_t)(~a[i]);
-    a[i] = (uint32_t)c;
-    c >>= 32;
-  }
-}
-CDEV void mp8_copy(uint32_t d[8], const uint32_t s[8]) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) d[i] = s[i];
-}
-// |a| of a two's-complement value and its sign
-CDEV int mp8_absbits(const uint32_t a[8]) {
-  uint32_t t[8];
-  mp8_copy(t, a);
-  if (a[7] >> 31) mp8_neg(t);
-  return mp8_bitlen(t);
-}
-
-// value of an 8-word integer as a double (relative error < 2^-49)
-CDEV double mp8_f64(const uint32_t a[8]) {
-  double d = (double)a[7];
-#pragma unroll
-  for (int i = 6; i >= 0; i--) d = fma(d, 4294967296.0, (double)a[i]);
-  return d;
-}
-// a -= q * b  (mod 2^256), q < 2^32
-CDEV void mp8_submul(uint32_t a[8], const uint32_t b[8], uint32_t q) {
-  uint64_t pc = 0;
-  uint32_t br = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const uint64_t p = (uint64_t)q * b[i] + pc;
-    pc = p >> 32;
-    const uint64_t d = (uint64_t)a[i] - (uint32_t)p - br;
-    a[i] = (uint32_t)d;
-    br = (uint32_t)(d >> 63);
-  }
-}
-// o = b << k  (mod 2^256), 0 <= k < 256
-CDEV void mp8_shl_dyn(uint32_t o[8], const uint32_t b[8], int k) {
-  const int ws = k >> 5, bs = k & 31;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const uint32_t lo = (i - ws >= 0) ? word_sel(b, i - ws) : 0u;
-    const uint32_t lo2 = (i - ws - 1 >= 0) ? word_sel(b, i - ws - 1) : 0u;
-    o[i] = bs ? ((lo << bs) | (lo2 >> (32 - bs))) : lo;
-  }
-}
-
-// rp <- rp mod rc,  tp <- tp - (rp div rc) * tc   (mod 2^256), rc > 0.
-// The quotient comes from a double-precision estimate scaled down by
-// (1 - 2^-40): it never exceeds the true quotient (relative error of the
-// estimate < 2^-48), so rp stays non-negative, and the loop repeats until
-// rp < rc. Euclid's partial quotients are small (~1.7 bits per step), so one
-// pass is the rule; a quotient >= 2^32 is taken 31 bits at a time.
-CDEV void euclid_divstep(uint32_t rp[8], const uint32_t rc[8], uint32_t tp[8], const uint32_t tc[8]) {
-  const double inv = 1.0 / mp8_f64(rc);
-  while (mp8_ge(rp, rc)) {
-    const double qd = mp8_f64(rp) * inv * (1.0 - 0x1p-40);
-    if (qd < 4294967296.0) {
-      uint32_t q = (uint32_t)qd;
-      q = q ? q : 1u;
-      mp8_submul(rp, rc, q);
-      mp8_submul(tp, tc, q);
-    } else {
-      const int e = (int)((__double_as_longlong(qd) >> 52) & 0x7ff) - 1023;  // qd in [2^e, 2^(e+1))
-      const int k = e - 31;
-      const uint32_t q = (uint32_t)(qd * __longlong_as_double((long long)(1023 - k) << 52));  // qd / 2^k
-      uint32_t bs[8], ts[8];
-      mp8_shl_dyn(bs, rc, k);
-      mp8_shl_dyn(ts, tc, k);
-      mp8_submul(rp, bs, q);
-      mp8_submul(tp, ts, q);
-    }
-  }
-}
+// Which lattice vector is taken (ed25519_half.hpp half_choose: the first short
+// remainder when its cofactor is odd, else the shortest of six neighbours with
+// an odd c1, the previous Euclid vector among them) does not enter the
+// argument: it holds for every (c0, c1) with c0 == c1*h (mod 8L) and c1 odd.
+// The multiprecision helpers and the exact division step are in that header.
 
 // floor(a / 2^s) as a double, exact for a < 2^(s+53)
 CDEV double mp8_top(const uint32_t a[8], int s) {
@@ -274,47 +184,7 @@ CDEV void half_scalars(uint32_t c0abs[8], bool& c0neg, uint32_t c1[8], const uin
       tc[i] = b;
     }
   }
-  uint32_t a0[8], a1[8];  // chosen (c0, c1), two's complement
-  mp8_copy(a0, rc);
-  mp8_copy(a1, tc);
-  if (!(tc[0] & 1)) {
-    // v1 = (rc, tc) has even c1; v3 = next Euclid vector has odd c1, and so do v1 +- v3
-    uint32_t r3[8], t3[8];
-    mp8_copy(r3, rp);
-    mp8_copy(t3, tp);
-    euclid_divstep(r3, rc, t3, tc);
-    uint32_t p0[8], p1[8], m0[8], m1[8], nr3[8], nt3[8];
-    mp8_add(p0, rc, r3);
-    mp8_add(p1, tc, t3);
-    mp8_copy(nr3, r3);
-    mp8_neg(nr3);
-    mp8_copy(nt3, t3);
-    mp8_neg(nt3);
-    mp8_add(m0, rc, nr3);
-    mp8_add(m1, tc, nt3);
-    int best = max(mp8_absbits(r3), mp8_absbits(t3));
-    mp8_copy(a0, r3);
-    mp8_copy(a1, t3);
-    const int bp = max(mp8_absbits(p0), mp8_absbits(p1));
-    if (bp < best) {
-      best = bp;
-      mp8_copy(a0, p0);
-      mp8_copy(a1, p1);
-    }
-    const int bm = max(mp8_absbits(m0), mp8_absbits(m1));
-    if (bm < best) {
-      mp8_copy(a0, m0);
-      mp8_copy(a1, m1);
-    }
-  }
-  if (a1[7] >> 31) {  // make c1 positive: (c0, c1) -> (-c0, -c1)
-    mp8_neg(a0);
-    mp8_neg(a1);
-  }
-  c0neg = (a0[7] >> 31) != 0;
-  if (c0neg) mp8_neg(a0);
-  mp8_copy(c0abs, a0);
-  mp8_copy(c1, a1);
+  half_choose(c0abs, c0neg, c1, rp, rc, tp, tc);  // ed25519_half.hpp
 }
 
 // Strict R decode: the reference never decodes R, it compares encode(R')

@@ -12,7 +12,9 @@
 // recoded from the prep: ed25519_sel.hpp), 16-bit Booth windows over B and
 // B' = [2^128]B from L2/MALL-resident tables (ed25519_ws.hpp). Digit positions are the same in every lane, so the
 // ladder never diverges; P == O is X == 0 and Y == Z (no inversion).
-// Verdict word per wave by ballot.
+// A wave runs the windows of its longest lane, so a block hands its lanes to its
+// four waves in window-count order (ED_LADDER_ORDER); verdict words by ballot,
+// by the block's last wave.
 // field products in hand-scheduled pairs (ge25519.hpp fe_mul_pair, fe25519_asm.hpp)
 #ifndef FE_USE_ASM2
 #define FE_USE_ASM2 1
@@ -41,6 +43,18 @@ __device__ __attribute__((aligned(64))) const uint32_t kIdentityCached[kWhEntryW
 // VGPRs v160..v167, so the kernel needs a budget of >= 168 VGPRs: 512 / waves
 static_assert(512 / ED_LADDER_WAVES >= 168, "fe25519_asm.hpp's v160..v167 accumulators need >= 168 VGPRs per lane");
 
+// ED_LADDER_ORDER: a block's lanes go to its four waves in window-count order
+// (ladder_half_lane). Keys of the counting rank: counts kOrderLo .. kOrderHi,
+// then the lanes past the batch.
+#ifndef ED_LADDER_ORDER
+#define ED_LADDER_ORDER 1
+#endif
+#if ED_LADDER_ORDER && !ED_SEL_STREAM
+#error "ED_LADDER_ORDER ranks the lanes by the selector stream's window count"
+#endif
+static constexpr int kOrderLo = 60, kOrderHi = 74, kOrderKeys = kOrderHi - kOrderLo + 2;
+static_assert(kOrderKeys <= 64, "one lane of a wave per key");
+
 // The body serves two kernels. kIdx false: the ladder itself, record li is lane
 // base + li. kIdx true: the routed instance (K14, ed25519_route.hpp): record li is
 // lane list[base + li], no verdict words.
@@ -48,7 +62,63 @@ template <bool kIdx>
 CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict__ btab,
                            const uint32_t* __restrict__ ws, uint8_t* __restrict__ status,
                            unsigned long long* __restrict__ verdict, const uint32_t* __restrict__ list) {
-  const uint64_t li = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t blk = (uint64_t)blockIdx.x * blockDim.x;
+#if ED_LADDER_ORDER
+  // This thread loads the selector words of record blk + threadIdx.x, the block
+  // ranks its 256 records by window count, and thread t then runs the record of
+  // rank t: each wave's W = its longest lane, so the block's waves get its
+  // lanes in count order and only the last one pays for the block's longest.
+  __shared__ uint32_t sk[kSelWords][256];
+  __shared__ uint8_t order_src[256];               // rank -> thread that loaded the record
+  __shared__ uint32_t order_cnt[4][kOrderKeys];    // per wave: lanes of each key
+  __shared__ uint32_t order_done;                  // waves that have left their ok bits (verdict words below)
+  uint64_t li;
+  {
+    const uint64_t l0 = blk + threadIdx.x;
+    const uint32_t* r0 = ws + (l0 < m ? l0 : m - 1) * kWhLaneWords;
+    const uint4* r4 = reinterpret_cast<const uint4*>(r0 + kWhSel);
+    uint4 v[(kSelWords + 3) / 4];
+#pragma unroll
+    for (int q = 0; q < (kSelWords + 3) / 4; q++) v[q] = r4[q];
+    static_assert(kSelMeta == 30 && (kSelWords + 3) / 4 == 8, "the count is in the last quad's third word");
+    // a stable counting rank over the keys: the window count clamped to
+    // [kOrderLo, kOrderHi] (fewer or more are rare and only order less well),
+    // lanes past the batch last: they lengthen no wave (W below skips them)
+    const int cnt = (int)(v[7].z >> 16);
+    const int key = l0 < m ? min(max(cnt, kOrderLo), kOrderHi) - kOrderLo : kOrderKeys - 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t before = 0, mine = 0;
+#pragma unroll
+    for (int k = 0; k < kOrderKeys; k++) {
+      const unsigned long long mk = __ballot(key == k);
+      if (key == k) before = (uint32_t)__popcll(mk & ((1ull << lane) - 1));
+      if (lane == k) mine = (uint32_t)__popcll(mk);
+    }
+    if (lane < kOrderKeys) order_cnt[wave][lane] = mine;
+    if (threadIdx.x == 0) order_done = 0;
+    __syncthreads();
+    uint32_t rank = before;
+#pragma unroll
+    for (int k = 0; k < kOrderKeys; k++)
+#pragma unroll
+      for (int w = 0; w < 4; w++) {
+        const uint32_t c = order_cnt[w][k];
+        rank += (k < key || (k == key && w < wave)) ? c : 0u;
+      }
+    order_src[rank] = (uint8_t)threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < (kSelWords + 3) / 4; q++) {
+      const uint32_t w[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+#pragma unroll
+      for (int t = 0; t < 4; t++)
+        if (4 * q + t < kSelWords) sk[4 * q + t][rank] = w[t];
+    }
+    __syncthreads();
+    li = blk + order_src[threadIdx.x];
+  }
+#else
+  const uint64_t li = blk + threadIdx.x;
+#endif
   const bool active = li < m;
   const uint64_t lc = active ? li : m - 1;  // inactive lanes replay the last record, discard it
   const uint32_t* rec = ws + lc * kWhLaneWords;
@@ -64,6 +134,7 @@ CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict
   // the selector stream (ed25519_sel.hpp) lives in LDS, word-major, one column
   // per thread: a window reads one word of it, a fixed-base window three more,
   // and no VGPR is pinned across the loop
+#if !ED_LADDER_ORDER
   __shared__ uint32_t sk[kSelWords][256];
   {
     const uint4* r4 = reinterpret_cast<const uint4*>(rec + kWhSel);
@@ -76,11 +147,17 @@ CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict
         if (4 * q + t < kSelWords) sk[4 * q + t][threadIdx.x] = w[t];
     }
   }
+#endif
   const uint32_t* col = &sk[0][threadIdx.x];
   // at least the windows the fixed-base digits need (e's low half: kBDigits
   // digits of kBBits bits); |c0|, c1 ~ 2^128 give 65. Lanes with fewer windows
   // of their own select the identity above them. (A count is at most 129.)
-  const int W = min(max(wave_max((int)(col[kSelMeta * 256] >> 16)), (kBDigits - 1) * (kBBits / 2) + 1), kSelWindows);
+#if ED_LADDER_ORDER
+  const int own = active ? (int)(col[kSelMeta * 256] >> 16) : 0;  // a lane past the batch follows its wave
+#else
+  const int own = (int)(col[kSelMeta * 256] >> 16);
+#endif
+  const int W = min(max(wave_max(own), (kBDigits - 1) * (kBBits / 2) + 1), kSelWindows);
   // window j's selector is read while window j + 1 computes; its word and
   // field are the same in every lane
   uint32_t selw = col[((W - 1) / kSelPerWord) * 256];
@@ -197,9 +274,33 @@ CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict
     }
   }
   if (!kIdx) {
+#if ED_LADDER_ORDER
+    // Verdict words are in lane order and a wave's lanes are not: every wave
+    // leaves its ok bits in LDS under the threads that loaded the records, and
+    // the wave that finishes last turns them into the block's four words. No
+    // barrier: a finished wave gives its registers back at once.
+    __shared__ uint8_t order_ok[256];
+    order_ok[li - blk] = active && st == kStatusOk;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    uint32_t arrived = 0;
+    if ((threadIdx.x & 63) == 0)
+      arrived = __hip_atomic_fetch_add(&order_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    arrived = (uint32_t)__shfl((int)arrived, 0);
+    if (arrived == blockDim.x / 64 - 1) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      const int lane = threadIdx.x & 63;
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const unsigned long long ok = __ballot(order_ok[64 * q + lane] != 0);
+        // base is a multiple of 64 (workspace chunks are), and so is blk: word q is the block's own
+        if (lane == q && blk + 64 * q < m && verdict) verdict[(base + blk + 64 * q) >> 6] = ok;
+      }
+    }
+#else
     const unsigned long long ok = __ballot(active && st == kStatusOk);
     // base is a multiple of 64 (workspace chunks are), so lane 0 of a wave owns a whole verdict word
     if ((threadIdx.x & 63) == 0 && active && verdict) verdict[i >> 6] = ok;
+#endif
   }
 }
 

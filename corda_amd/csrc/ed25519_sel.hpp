@@ -18,9 +18,13 @@
 //
 // 132 windows, because the scalars are not always half-size: |c0|, c1 < 8L <
 // 2^256 need up to 129. Where Euclid's short vector has an even c1 the prep
-// takes the next one (half_scalars, ed25519.hip), whose length is 8L over the
-// short one's: about one lane in 300 has more than 134 bits, and nothing bounds
-// it below 256. Windows 80 and up are recoded only for a lane that has a bit
+// takes the shortest of six neighbours with an odd c1 (half_choose,
+// ed25519_half.hpp): the next Euclid vector, whose length is 8L over the short
+// one's remainder, or the previous one, which is short when that one is long.
+// By the CPU model (tools/proto/half_scalar_windows.py; not a GPU measurement)
+// about one lane in 5,000 needs 68 windows or more (one in 120 while only the
+// next vector's three were tried) and the longest of 200,000 needs 69 (73), but
+// nothing bounds it below 129: h = L - 1 gives 252 bits. Windows 80 and up are recoded only for a lane that has a bit
 // at or above 159 (one branch); every other position is a compile-time
 // constant once the loops are unrolled: no dynamic shift. Usable from host and
 // device (tests/test_ed_sel_recode.py builds tools/ed_sel_check.cpp from it).
