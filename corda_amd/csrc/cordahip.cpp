@@ -11,7 +11,8 @@
 // worker pool. The fixed-base tables are built once per device at init by a
 // kernel. There is no CPU verification fallback: a HIP failure is returned to
 // the caller as CORDAHIP_ERR_HIP. The generic CSR signature batch lives in
-// host_batch.cpp; the shared runtime types in runtime.hpp; the per-device runtime
+// host_batch.cpp; the registered-key calls in keyed.cpp; the notary commit log in
+// commit_api.cpp; the shared runtime types in runtime.hpp; the per-device runtime
 // (pools, streams, budget, enqueue helpers, idle release, init / shutdown) in
 // runtime.cpp.
 #include <hip/hip_runtime.h>
@@ -21,22 +22,45 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <random>
-#include <tuple>
 
+#include "api_support.hpp"
 #include "cover_core.hpp"
 #include "csr_check.hpp"
-#include "der.hpp"
-#include "ed25519_comb.hpp"
-#include "ecdsa_vkey.hpp"
-#include "ed25519_vkey.hpp"
 #include "kryo_core.hpp"
-#include "pack_rows.hpp"
 #include "runtime.hpp"
 #include "status.hpp"
 
 using namespace cordahip;
 using namespace cordahip::rt;
+
+// device uid -> (ring slot, generation) of this thread's most recent timed call
+static thread_local std::unordered_map<uint64_t, std::pair<int, uint64_t>> tl_last_call;
+
+uint64_t cordahip::rt::submit_job(cordahip_ctx* ctx, std::function<int()> fn) {
+  auto st = std::make_shared<JobState>();
+  uint64_t t;
+  {
+    std::lock_guard<std::mutex> g(ctx->mu);
+    t = ctx->next_ticket++;
+    ctx->jobs.emplace(t, st);
+  }
+  ctx->pool->push(st, std::move(fn));
+  return t;
+}
+
+// timing slot for one *_device call (records `a` now on stream s); the slot's
+// generation is the call's sequence number, so a reader whose slot was reused
+// by a later call (more than kTimingRing calls in between) can tell
+TimedCall* cordahip::rt::timed_begin(Device& d, hipStream_t s) {
+  std::lock_guard<std::mutex> g(d.tmu);
+  const uint64_t seq = ++d.ring_next;
+  const int idx = (int)(seq % kTimingRing);
+  TimedCall* tc = &d.ring[idx];
+  tc->gen = seq;
+  if (hipEventRecord(tc->a, s) != hipSuccess) return nullptr;
+  tl_last_call[d.uid] = {idx, seq};
+  return tc;
+}
 
 namespace {
 
@@ -103,78 +127,6 @@ hipError_t kryo_scratch_ensure(Device& d, uint64_t n, size_t temp_bytes) {
                ? hipErrorOutOfMemory
                : hipSuccess;
   });
-}
-
-// the context's host pool as csr_check.hpp's parallel runner
-struct PoolPar {
-  HostPool& pool;
-  template <class F>
-  void operator()(uint64_t n, uint64_t grain, F&& fn) const {
-    pool.parallel_for(n, grain, std::function<void(uint64_t, uint64_t)>(fn));
-  }
-};
-
-// device uid -> (ring slot, generation) of this thread's most recent timed call
-thread_local std::unordered_map<uint64_t, std::pair<int, uint64_t>> tl_last_call;
-
-uint64_t submit_job(cordahip_ctx* ctx, std::function<int()> fn) {
-  auto st = std::make_shared<JobState>();
-  uint64_t t;
-  {
-    std::lock_guard<std::mutex> g(ctx->mu);
-    t = ctx->next_ticket++;
-    ctx->jobs.emplace(t, st);
-  }
-  ctx->pool->push(st, std::move(fn));
-  return t;
-}
-
-// A *_submit call: its descriptors by value (their arrays stay caller-owned) into a
-// queued job that runs impl(ctx, &copy...); the ticket.
-template <class F, class... D>
-int submit(cordahip_ctx* ctx, uint64_t* ticket, F impl, const D*... desc) {
-  if (!ctx || !ticket || (... || !desc)) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] {
-    *ticket = submit_job(ctx, [ctx, impl, copies = std::make_tuple(*desc...)] {
-      return std::apply([&](const D&... c) { return impl(ctx, &c...); }, copies);
-    });
-    return (int)CORDAHIP_SUCCESS;
-  });
-}
-
-// timing slot for one *_device call (records `a` now on stream s); the slot's
-// generation is the call's sequence number, so a reader whose slot was reused
-// by a later call (more than kTimingRing calls in between) can tell
-TimedCall* timed_begin(Device& d, hipStream_t s) {
-  std::lock_guard<std::mutex> g(d.tmu);
-  const uint64_t seq = ++d.ring_next;
-  const int idx = (int)(seq % kTimingRing);
-  TimedCall* tc = &d.ring[idx];
-  tc->gen = seq;
-  if (hipEventRecord(tc->a, s) != hipSuccess) return nullptr;
-  tl_last_call[d.uid] = {idx, seq};
-  return tc;
-}
-
-// A *_device entry point once its arguments are checked: the call counts as activity
-// on the device, the device is current, `prepare` grows what the call needs (device
-// memory it could not get is CORDAHIP_ERR_OUT_OF_MEMORY), and the call's timing pair
-// brackets what `enqueue` puts on the caller's stream (NULL: the device's null stream).
-template <class P, class F>
-int device_call(Device& d, void* hip_stream, P&& prepare, F&& enqueue) {
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  if (const hipError_t e = prepare()) return e == hipErrorOutOfMemory ? CORDAHIP_ERR_OUT_OF_MEMORY : CORDAHIP_ERR_HIP;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  TimedCall* tc = timed_begin(d, s);
-  if (!tc) return CORDAHIP_ERR_HIP;
-  hipError_t e = enqueue(s);
-  e = e ? e : hipEventRecord(tc->b, s);
-  return hip_err(e);
-}
-template <class F>
-int device_call(Device& d, void* hip_stream, F&& enqueue) {
-  return device_call(d, hip_stream, [] { return hipSuccess; }, enqueue);
 }
 
 // What the two device signed-tx entry points share (leaves or components in HBM,
@@ -1276,988 +1228,6 @@ int filtered_build_impl(cordahip_ctx* ctx, const cordahip_filtered_build_batch* 
                     [&](Device& d, uint64_t t0, uint64_t t1) { return filtered_build_shard(d, b, t0, t1); });
 }
 
-// ---- Ed25519 signing with registered keys (K11, ed25519_sign.hip) -------------
-// A key's record zeroed on one device (sign_mu held, device current): after every
-// signing kernel that may still read it; the stream is drained before return.
-hipError_t signer_zero_record(Device& d, uint32_t slot) {
-  if (!d.keys.tab.p) return hipSuccess;
-  hipError_t e = d.keys.ev.sync();
-  e = e ? e : hipMemsetAsync(d.keys.tab.as<uint32_t>() + (size_t)slot * kSignRecWords, 0, kSignRecWords * 4, d.stream);
-  const hipError_t f = hipStreamSynchronize(d.stream);
-  return e ? e : f;
-}
-
-// The seed expanded into the record of key_id's slot on one device (sign_mu held);
-// pub: the device's A. The seed crosses in the device's page-locked stage, wiped
-// here whatever happens; the kernel zeroes its device scratch.
-int signer_expand_on(Device& d, const uint8_t seed[32], uint32_t key_id, uint8_t pub[32]) {
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  if (!d.keys.tab.p) {  // the first key of this device: the table, zeroed
-    if (d.keys.tab.ensure(ed25519_keytab_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-    if (hipMemsetAsync(d.keys.tab.p, 0, d.keys.tab.cap, d.stream) != hipSuccess) return CORDAHIP_ERR_HIP;
-  }
-  if (d.keys.stage.ensure(64) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-  uint8_t* stage = d.keys.stage.as<uint8_t>();
-  uint32_t* tab = d.keys.tab.as<uint32_t>();
-  std::memcpy(stage, seed, 32);
-  hipError_t e = hipMemcpyAsync(tab + kSignSeedWord, stage, 32, hipMemcpyHostToDevice, d.stream);
-  e = e ? e : launch_ed25519_key_expand(tab, key_id, d.comb(), d.stream);
-  e = e ? e : hipMemcpyAsync(stage + 32, tab + kSignPubWord, 32, hipMemcpyDeviceToHost, d.stream);
-  const hipError_t f = hipStreamSynchronize(d.stream);
-  secure_wipe(stage, 32);
-  if (e == hipSuccess && f == hipSuccess) std::memcpy(pub, stage + 32, 32);
-  return hip_err(e ? e : f);
-}
-
-int signer_add_impl(cordahip_ctx* ctx, const uint8_t seed[32], uint32_t* key_id, uint8_t pub[32]) {
-  std::lock_guard<std::mutex> g(ctx->signer_mu);
-  if (ctx->signer_gen.empty()) {
-    ctx->signer_gen.assign(kSignKeySlots, 0);
-    ctx->signer_live.assign(kSignKeySlots, 0);
-  }
-  if (ctx->signer_count >= kSignKeySlots) return CORDAHIP_ERR_OUT_OF_MEMORY;
-  uint32_t slot = 0;
-  while (ctx->signer_live[slot]) slot++;
-  // the slot's reuse counter: ids differ across a slot's keys until it wraps (2^20 adds into one slot)
-  const uint32_t gen = (ctx->signer_gen[slot] + 1) & ((1u << (32 - kSignSlotBits)) - 1);
-  const uint32_t id = slot | (gen << kSignSlotBits);
-  ctx->signer_gen[slot] = gen;  // consumed even if the add fails
-  int rc = CORDAHIP_SUCCESS;
-  size_t done = 0;
-  uint8_t first[32], cur[32];
-  for (; done < ctx->devs.size() && rc == CORDAHIP_SUCCESS; done++) {
-    Device& d = *ctx->devs[done];
-    std::lock_guard<std::mutex> gd(d.sign_mu);
-    const Activity act(d);
-    rc = signer_expand_on(d, seed, id, done ? cur : first);
-    if (rc == CORDAHIP_SUCCESS && done && std::memcmp(first, cur, 32) != 0) rc = CORDAHIP_ERR_HIP;
-  }
-  if (rc != CORDAHIP_SUCCESS) {  // no device keeps a record of a key the caller never got
-    for (size_t k = 0; k < done; k++) {
-      Device& d = *ctx->devs[k];
-      std::lock_guard<std::mutex> gd(d.sign_mu);
-      if (hipSetDevice(d.id) == hipSuccess && d.keys.tab.p) {
-        (void)signer_zero_record(d, slot);
-        (void)hipMemsetAsync(d.keys.tab.as<uint32_t>() + kSignSeedWord, 0, 32, d.stream);
-        (void)hipStreamSynchronize(d.stream);
-      }
-    }
-    return rc;
-  }
-  ctx->signer_live[slot] = 1;
-  ctx->signer_count++;
-  *key_id = id;
-  std::memcpy(pub, first, 32);
-  if (tracing()) fprintf(stderr, "[cordahip] signer: key id %u added (%u live)\n", id, ctx->signer_count);
-  return CORDAHIP_SUCCESS;
-}
-
-int signer_remove_impl(cordahip_ctx* ctx, uint32_t key_id) {
-  std::lock_guard<std::mutex> g(ctx->signer_mu);
-  const uint32_t slot = key_id & (kSignKeySlots - 1);
-  if (ctx->signer_gen.empty() || !ctx->signer_live[slot] || (slot | (ctx->signer_gen[slot] << kSignSlotBits)) != key_id)
-    return CORDAHIP_ERR_INVALID_ARG;
-  ctx->signer_live[slot] = 0;  // the id is dead from here on, whatever a device answers below
-  ctx->signer_count--;
-  hipError_t e = hipSuccess;
-  for (auto& dp : ctx->devs) {
-    Device& d = *dp;
-    std::lock_guard<std::mutex> gd(d.sign_mu);
-    const Activity act(d);
-    const hipError_t s = hipSetDevice(d.id);
-    const hipError_t z = s ? s : signer_zero_record(d, slot);
-    e = e ? e : z;
-  }
-  if (tracing()) fprintf(stderr, "[cordahip] signer: key id %u removed (%u live)\n", key_id, ctx->signer_count);
-  return hip_err(e);
-}
-
-// The keyed signer on stream s (sign_mu held, device current): behind the table's
-// previous user, followed by the table's fence. A device without a key table yet
-// passes none: every ungated lane is then UNKNOWN_KEY.
-hipError_t sign_enqueue(Device& d, const uint32_t* key_id, const uint8_t* msgs, const uint64_t* moff,
-                        const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* gate, uint8_t* sigs,
-                        uint8_t* status, hipStream_t s) {
-  hipError_t e = d.keys.ev.wait(s);
-  e = e ? e
-        : launch_ed25519_sign_keyed(key_id, msgs, moff, mlen, msg_len, n, gate, d.keys.tab.as<uint32_t>(),
-                                    d.comb(), sigs, status, s);
-  return e ? e : d.keys.ev.record(s);
-}
-
-// cordahip_sign for lanes [lo, hi) on one device, a chunk of CORDAHIP_HOST_CHUNK
-// lanes at a time: the lanes packed into the device's page-locked stage (dense
-// 32-byte rows when every message of the chunk is 32 bytes -- the ids; else each
-// message at a 16-byte-aligned offset with its length), across PCIe, K11, and the
-// signature rows and statuses back into the caller's arrays in lane order.
-int sign_shard(cordahip_ctx* ctx, Device& d, const cordahip_sign_batch* b, uint64_t lo, uint64_t hi) {
-  std::lock_guard<std::mutex> g(d.sign_host_mu);
-  const NodeBind nb(d);
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  const uint64_t chunk = env_lanes("CORDAHIP_HOST_CHUNK", 1ull << 22);
-  HostPool& pool = pool_of(ctx, d);
-  hipStream_t s = d.stream;
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
-  std::vector<uint64_t> poff;
-  for (uint64_t a = lo; a < hi; a += chunk) {
-    const uint64_t m = std::min(chunk, hi - a);
-    const double t0 = now_ms();
-    poff.resize(m);
-    const SignLayout lay = sign_chunk_layout(b, a, m, poff.data());
-    const bool dense = lay.dense;
-    const uint64_t bytes = lay.bytes;
-    const size_t need[7] = {(size_t)m * 4, (size_t)std::max<uint64_t>(bytes, 16), (size_t)m * 8, (size_t)m * 4,
-                            (size_t)m,     (size_t)m * 64,                        (size_t)m};
-    for (int k = 0; k < 7; k++)  // the previous chunk has drained: growing frees nothing in use
-      if (d.sign_h[k].ensure(need[k]) != hipSuccess || d.sign_d[k].ensure(need[k]) != hipSuccess)
-        return CORDAHIP_ERR_OUT_OF_MEMORY;
-    uint8_t* hm = d.sign_h[1].as<uint8_t>();
-    uint64_t* ho = d.sign_h[2].as<uint64_t>();
-    uint32_t* hl = d.sign_h[3].as<uint32_t>();
-    pool.parallel_for(m, 1u << 14, [&](uint64_t x, uint64_t y) {
-      sign_pack_rows(b, a, x, y, lay, poff.data(), d.sign_h[0].as<uint32_t>(), d.sign_h[4].as<uint8_t>(), hm, ho, hl);
-    });
-    hipError_t e = hipMemcpyAsync(d.sign_d[0].p, d.sign_h[0].p, m * 4, h2d, s);
-    if (bytes) e = e ? e : hipMemcpyAsync(d.sign_d[1].p, hm, bytes, h2d, s);
-    if (!dense) {
-      e = e ? e : hipMemcpyAsync(d.sign_d[2].p, ho, m * 8, h2d, s);
-      e = e ? e : hipMemcpyAsync(d.sign_d[3].p, hl, m * 4, h2d, s);
-    }
-    if (b->gate) e = e ? e : hipMemcpyAsync(d.sign_d[4].p, d.sign_h[4].p, m, h2d, s);
-    if (e == hipSuccess) {
-      std::lock_guard<std::mutex> gs(d.sign_mu);
-      e = sign_enqueue(d, d.sign_d[0].as<uint32_t>(), d.sign_d[1].as<uint8_t>(),
-                       dense ? nullptr : d.sign_d[2].as<uint64_t>(), dense ? nullptr : d.sign_d[3].as<uint32_t>(), 32, m,
-                       b->gate ? d.sign_d[4].as<uint8_t>() : nullptr, d.sign_d[5].as<uint8_t>(),
-                       d.sign_d[6].as<uint8_t>(), s);
-    }
-    e = e ? e : hipMemcpyAsync(d.sign_h[5].p, d.sign_d[5].p, m * 64, d2h, s);
-    e = e ? e : hipMemcpyAsync(d.sign_h[6].p, d.sign_d[6].p, m, d2h, s);
-    e = e ? e : d.sign_host_ev.record(s);
-    e = e ? e : d.sign_host_ev.sync();
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(s);  // no queued work outlives the call
-      return CORDAHIP_ERR_HIP;
-    }
-    std::memcpy(b->sig + a * 64, d.sign_h[5].p, m * 64);
-    std::memcpy(b->status + a, d.sign_h[6].p, m);
-    if (tracing())
-      fprintf(stderr, "[cordahip] dev %d sign chunk: %llu lanes (%s messages) in %.2f ms\n", d.id,
-              (unsigned long long)m, dense ? "32-byte" : "CSR", now_ms() - t0);
-  }
-  return CORDAHIP_SUCCESS;
-}
-
-int sign_impl(cordahip_ctx* ctx, const cordahip_sign_batch* b) {
-  const uint64_t n = b->n;
-  if (n == 0) return CORDAHIP_SUCCESS;
-  if (!b->key_id || !b->msg_off || !b->sig || !b->status) return CORDAHIP_ERR_INVALID_ARG;
-  if (!check_sign_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
-  if (b->msg_off[0] != b->msg_off[n] && !b->msg) return CORDAHIP_ERR_INVALID_ARG;
-  return for_shards(ctx->devs, n, 64, [&](Device& d, uint64_t lo, uint64_t hi) { return sign_shard(ctx, d, b, lo, hi); });
-}
-
-// ---- Ed25519 verification against registered keys (K12, ed25519_vkey.hip) --------
-// A key's record cleared on one device (vkey_mu held, device current): after every
-// keyed kernel that may still read it; the stream is drained before return. The
-// table's entries stay: without a record whose id matches, no lane reads them.
-hipError_t vkey_clear_record(Device& d, uint32_t slot) {
-  if (!d.vkeys.tab.p && !d.ec_vkeys.tab.p) return hipSuccess;
-  hipError_t e = hipSuccess;
-  if (d.vkeys.tab.p) {
-    d.vkeys.live &= ~(1ull << slot);  // routed enqueues (K14) count the device's live Ed25519 keys
-    e = d.vkeys.ev.sync();
-    e = e ? e
-          : hipMemsetAsync(d.vkeys.tab.as<uint32_t>() + kVkeyRecBase + (size_t)slot * kVkeyRecWords, 0,
-                           kVkeyRecWords * 4, d.stream);
-  }
-  if (d.ec_vkeys.tab.p) {  // the slot's record of the other family (K13): one pool, one remove
-    hipError_t x = d.ec_vkeys.ev.sync();
-    x = x ? x
-          : hipMemsetAsync(d.ec_vkeys.tab.as<uint32_t>() + kEcVkeyRecBase + (size_t)slot * kEcVkeyRecWords, 0,
-                           kEcVkeyRecWords * 4, d.stream);
-    e = e ? e : x;
-    EcVkeyState& st = d.ec_vkey_state;
-    if (st.scheme[slot]) st.live[st.scheme[slot] - 2]--;
-    st.scheme[slot] = 0;
-  }
-  const hipError_t f = hipStreamSynchronize(d.stream);
-  return e ? e : f;
-}
-
-// The key's record and table built in key_id's slot on one device (vkey_mu held);
-// *decoded: whether the device took the bytes for a point.
-int vkey_build_on(Device& d, const uint8_t key[32], uint32_t key_id, bool* decoded) {
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  if (!d.vkeys.tab.p) {  // the first key of this device: the tables; the records zeroed, the table of B built
-    if (d.vkeys.tab.ensure(ed25519_vkey_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-    if (hipMemsetAsync(d.vkeys.tab.as<uint32_t>() + kVkeyRecBase, 0, (kVkeyAllWords - kVkeyRecBase) * 4, d.stream) !=
-            hipSuccess ||
-        launch_ed25519_vkey_base(d.vkeys.tab.as<uint32_t>(), d.stream) != hipSuccess)
-      return CORDAHIP_ERR_HIP;
-  }
-  if (d.vkeys.stage.ensure(64) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-  uint8_t* stage = d.vkeys.stage.as<uint8_t>();
-  uint32_t* tab = d.vkeys.tab.as<uint32_t>();
-  std::memcpy(stage, key, 32);
-  std::memset(stage + 32, 0, 32);
-  hipError_t e = d.vkeys.ev.sync();  // a removed key's slot: no kernel still reads its table
-  e = e ? e : hipMemcpyAsync(tab + kVkeyKeyWord, stage, 32, hipMemcpyHostToDevice, d.stream);
-  e = e ? e : launch_ed25519_vkey_build(tab, key_id, d.stream);
-  e = e ? e : hipMemcpyAsync(stage + 32, tab + kVkeyOkWord, 32, hipMemcpyDeviceToHost, d.stream);
-  const hipError_t f = hipStreamSynchronize(d.stream);
-  if (e == hipSuccess && f == hipSuccess) {
-    uint32_t flag;
-    std::memcpy(&flag, stage + 32, 4);
-    *decoded = flag == 1u;
-    if (*decoded) d.vkeys.live |= 1ull << vkey_slot(key_id);
-  }
-  return hip_err(e ? e : f);
-}
-
-// The ECDSA key's record and table built in key_id's slot on one device (vkey_mu held):
-// the device's first ECDSA key allocates the tables (records zeroed), its first key of a
-// curve builds that curve's base-point table. *decoded: whether the device took the
-// SEC1 bytes for a point of the curve (BC ECCurve.decodePoint).
-int ec_vkey_build_on(Device& d, uint32_t scheme, const uint8_t* key, uint32_t key_len, uint32_t key_id, bool* decoded) {
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  EcVkeyState& st = d.ec_vkey_state;
-  if (!d.ec_vkeys.tab.p) {
-    if (d.ec_vkeys.tab.ensure(ecdsa_vkey_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-    st = EcVkeyState{};
-    if (hipMemsetAsync(d.ec_vkeys.tab.as<uint32_t>() + kEcVkeyRecBase, 0, (kEcVkeyAllWords - kEcVkeyRecBase) * 4,
-                       d.stream) != hipSuccess)
-      return CORDAHIP_ERR_HIP;
-  }
-  uint32_t* tab = d.ec_vkeys.tab.as<uint32_t>();
-  const bool build_base = !st.base[scheme - 2];  // marked built only once the stream has drained below
-  if (build_base && launch_ecdsa_vkey_build(tab, scheme, ec_vkey_base_slot(scheme), 0u, 0u, d.stream) != hipSuccess)
-    return CORDAHIP_ERR_HIP;
-  if (d.ec_vkeys.stage.ensure(128) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-  uint8_t* stage = d.ec_vkeys.stage.as<uint8_t>();
-  std::memset(stage, 0, 128);
-  std::memcpy(stage, key, key_len);
-  hipError_t e = d.ec_vkeys.ev.sync();  // a removed key's slot: no kernel still reads its table
-  e = e ? e : hipMemcpyAsync(tab + kEcVkeyKeyWord, stage, 80, hipMemcpyHostToDevice, d.stream);
-  e = e ? e : launch_ecdsa_vkey_build(tab, scheme, vkey_slot(key_id), key_id, key_len, d.stream);
-  e = e ? e : hipMemcpyAsync(stage + 80, tab + kEcVkeyOkWord, 16, hipMemcpyDeviceToHost, d.stream);
-  const hipError_t f = hipStreamSynchronize(d.stream);
-  if (e == hipSuccess && f == hipSuccess) {
-    uint32_t flag;
-    std::memcpy(&flag, stage + 80, 4);
-    *decoded = flag == 1u;
-    if (build_base) st.base[scheme - 2] = 1;
-    if (*decoded) {
-      st.scheme[vkey_slot(key_id)] = (uint8_t)scheme;
-      st.live[scheme - 2]++;
-    }
-  }
-  return hip_err(e ? e : f);
-}
-
-// scheme 0: an Ed25519 key of 32 bytes (K12); 2 / 3: an ECDSA key in SEC1 form (K13).
-// One pool of slots and one id space for both.
-int vkey_add_impl(cordahip_ctx* ctx, uint32_t scheme, const uint8_t* key, uint32_t key_len, uint32_t* key_id,
-                  uint8_t* key_status) {
-  if (scheme && key_len != 33 && key_len != 65) {  // ECCurve.decodePoint: invalid point encoding
-    *key_id = kVkeyNoId;
-    *key_status = CORDAHIP_STATUS_BAD_KEY;
-    return CORDAHIP_SUCCESS;
-  }
-  std::lock_guard<std::mutex> g(ctx->vkey_mu);
-  if (ctx->vkey_gen.empty()) {
-    ctx->vkey_gen.assign(kVkeySlots, 0);
-    ctx->vkey_live.assign(kVkeySlots, 0);
-  }
-  if (ctx->vkey_count >= kVkeySlots) return CORDAHIP_ERR_OUT_OF_MEMORY;
-  uint32_t slot = 0;
-  while (ctx->vkey_live[slot]) slot++;
-  const uint32_t gen = vkey_next_gen(ctx->vkey_gen[slot]);
-  const uint32_t id = vkey_make_id(slot, gen);
-  ctx->vkey_gen[slot] = gen;  // consumed even if the add fails
-  int rc = CORDAHIP_SUCCESS;
-  size_t done = 0;
-  bool first = false, cur = false;
-  for (; done < ctx->devs.size() && rc == CORDAHIP_SUCCESS; done++) {
-    Device& d = *ctx->devs[done];
-    std::lock_guard<std::mutex> gd(d.vkey_mu);
-    const Activity act(d);
-    rc = scheme ? ec_vkey_build_on(d, scheme, key, key_len, id, done ? &cur : &first)
-                : vkey_build_on(d, key, id, done ? &cur : &first);
-    if (rc == CORDAHIP_SUCCESS && done && cur != first) rc = CORDAHIP_ERR_HIP;
-    if (rc == CORDAHIP_SUCCESS && !first) break;  // not a point: no device wrote anything
-  }
-  if (rc != CORDAHIP_SUCCESS) {  // no device keeps a record of a key the caller never got
-    for (size_t k = 0; k < done; k++) {
-      Device& d = *ctx->devs[k];
-      std::lock_guard<std::mutex> gd(d.vkey_mu);
-      if (hipSetDevice(d.id) == hipSuccess) (void)vkey_clear_record(d, slot);
-    }
-    return rc;
-  }
-  if (!first) {
-    *key_id = kVkeyNoId;
-    *key_status = CORDAHIP_STATUS_BAD_KEY;
-    return CORDAHIP_SUCCESS;
-  }
-  ctx->vkey_live[slot] = 1;
-  ctx->vkey_count++;
-  *key_id = id;
-  *key_status = CORDAHIP_STATUS_OK;
-  if (tracing()) fprintf(stderr, "[cordahip] vkey: key id %u added (%u live)\n", id, ctx->vkey_count);
-  return CORDAHIP_SUCCESS;
-}
-
-int vkey_remove_impl(cordahip_ctx* ctx, uint32_t key_id) {
-  std::lock_guard<std::mutex> g(ctx->vkey_mu);
-  const uint32_t slot = vkey_slot(key_id);
-  if (ctx->vkey_gen.empty() || !ctx->vkey_live[slot] || vkey_make_id(slot, ctx->vkey_gen[slot]) != key_id)
-    return CORDAHIP_ERR_INVALID_ARG;
-  ctx->vkey_live[slot] = 0;  // the id is dead from here on, whatever a device answers below
-  ctx->vkey_count--;
-  hipError_t e = hipSuccess;
-  for (auto& dp : ctx->devs) {
-    Device& d = *dp;
-    std::lock_guard<std::mutex> gd(d.vkey_mu);
-    const Activity act(d);
-    const hipError_t s = hipSetDevice(d.id);
-    const hipError_t z = s ? s : vkey_clear_record(d, slot);
-    e = e ? e : z;
-  }
-  if (tracing()) fprintf(stderr, "[cordahip] vkey: key id %u removed (%u live)\n", key_id, ctx->vkey_count);
-  return hip_err(e);
-}
-
-// The keyed verifier on stream s (vkey_mu held, device current): behind the tables'
-// previous user, followed by the tables' fence. A device without key tables yet
-// passes none: every lane is then UNKNOWN_KEY.
-hipError_t vkey_enqueue(Device& d, const uint32_t* key_id, const uint8_t* sigs, const uint8_t* msgs,
-                        const uint64_t* moff, const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* pre,
-                        uint32_t flags, uint8_t* status, unsigned long long* verdict, hipStream_t s) {
-  hipError_t e = d.vkeys.ev.wait(s);
-  e = e ? e
-        : launch_ed25519_verify_keyed(key_id, sigs, msgs, moff, mlen, msg_len, n, pre, flags,
-                                      d.vkeys.tab.as<uint32_t>(), status, verdict, s);
-  return e ? e : d.vkeys.ev.record(s);
-}
-
-// cordahip_verify_keyed for lanes [lo, hi) on one device (lo a multiple of 64), a chunk
-// of CORDAHIP_HOST_CHUNK lanes at a time: the lanes packed into the device's page-locked
-// stage (pack_rows.hpp keyed_pack_rows), across PCIe, K12, and the statuses and verdict
-// words back into the caller's arrays.
-int verify_keyed_shard(cordahip_ctx* ctx, Device& d, const cordahip_keyed_sig_batch* b, uint64_t lo, uint64_t hi) {
-  std::lock_guard<std::mutex> g(d.vkey_host_mu);
-  const NodeBind nb(d);
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  const uint64_t chunk = (env_lanes("CORDAHIP_HOST_CHUNK", 1ull << 22) + 63) / 64 * 64;  // whole verdict words
-  HostPool& pool = pool_of(ctx, d);
-  hipStream_t s = d.stream;
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
-  std::vector<uint64_t> poff;
-  for (uint64_t a = lo; a < hi; a += chunk) {
-    const uint64_t m = std::min(chunk, hi - a);
-    const uint64_t words = (m + 63) / 64;
-    const double t0 = now_ms();
-    poff.resize(m);
-    const SignLayout lay = msg_chunk_layout(b->msg_off, a, m, poff.data());
-    const bool dense = lay.dense;
-    const uint64_t bytes = lay.bytes;
-    const size_t need[8] = {(size_t)m * 4, (size_t)m * 64, (size_t)m, (size_t)std::max<uint64_t>(bytes, 16),
-                            (size_t)m * 8, (size_t)m * 4,  (size_t)m, (size_t)words * 8};
-    for (int k = 0; k < 8; k++)  // the previous chunk has drained: growing frees nothing in use
-      if (d.vkey_h[k].ensure(need[k]) != hipSuccess || d.vkey_d[k].ensure(need[k]) != hipSuccess)
-        return CORDAHIP_ERR_OUT_OF_MEMORY;
-    uint8_t* hm = d.vkey_h[3].as<uint8_t>();
-    uint64_t* ho = d.vkey_h[4].as<uint64_t>();
-    uint32_t* hl = d.vkey_h[5].as<uint32_t>();
-    pool.parallel_for(m, 1u << 14, [&](uint64_t x, uint64_t y) {
-      keyed_pack_rows(b, a, x, y, lay, poff.data(), d.vkey_h[0].as<uint32_t>(), d.vkey_h[1].as<uint8_t>(),
-                      d.vkey_h[2].as<uint8_t>(), hm, ho, hl);
-    });
-    hipError_t e = hipMemcpyAsync(d.vkey_d[0].p, d.vkey_h[0].p, m * 4, h2d, s);
-    e = e ? e : hipMemcpyAsync(d.vkey_d[1].p, d.vkey_h[1].p, m * 64, h2d, s);
-    e = e ? e : hipMemcpyAsync(d.vkey_d[2].p, d.vkey_h[2].p, m, h2d, s);
-    if (bytes) e = e ? e : hipMemcpyAsync(d.vkey_d[3].p, hm, bytes, h2d, s);
-    if (!dense) {
-      e = e ? e : hipMemcpyAsync(d.vkey_d[4].p, ho, m * 8, h2d, s);
-      e = e ? e : hipMemcpyAsync(d.vkey_d[5].p, hl, m * 4, h2d, s);
-    }
-    if (e == hipSuccess) {
-      std::lock_guard<std::mutex> gs(d.vkey_mu);
-      e = vkey_enqueue(d, d.vkey_d[0].as<uint32_t>(), d.vkey_d[1].as<uint8_t>(), d.vkey_d[3].as<uint8_t>(),
-                       dense ? nullptr : d.vkey_d[4].as<uint64_t>(), dense ? nullptr : d.vkey_d[5].as<uint32_t>(), 32, m,
-                       d.vkey_d[2].as<uint8_t>(), b->flags, d.vkey_d[6].as<uint8_t>(),
-                       d.vkey_d[7].as<unsigned long long>(), s);
-    }
-    e = e ? e : hipMemcpyAsync(d.vkey_h[6].p, d.vkey_d[6].p, m, d2h, s);
-    e = e ? e : hipMemcpyAsync(d.vkey_h[7].p, d.vkey_d[7].p, words * 8, d2h, s);
-    e = e ? e : d.vkey_host_ev.record(s);
-    e = e ? e : d.vkey_host_ev.sync();
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(s);  // no queued work outlives the call
-      return CORDAHIP_ERR_HIP;
-    }
-    std::memcpy(b->status + a, d.vkey_h[6].p, m);
-    if (b->verdict) std::memcpy(b->verdict + a / 64, d.vkey_h[7].p, words * 8);
-    if (tracing())
-      fprintf(stderr, "[cordahip] dev %d keyed verify chunk: %llu lanes (%s messages) in %.2f ms\n", d.id,
-              (unsigned long long)m, dense ? "32-byte" : "CSR", now_ms() - t0);
-  }
-  return CORDAHIP_SUCCESS;
-}
-
-int verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) {
-  const uint64_t n = b->n;
-  if (n == 0) return CORDAHIP_SUCCESS;
-  if (!b->key_id || !b->sig_off || !b->msg_off || !b->status) return CORDAHIP_ERR_INVALID_ARG;
-  if (b->flags & ~CORDAHIP_FLAG_IS_VALID) return CORDAHIP_ERR_INVALID_ARG;
-  if (!check_keyed_sig_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
-  if ((b->msg_off[0] != b->msg_off[n] && !b->msg) || (b->sig_off[0] != b->sig_off[n] && !b->sig))
-    return CORDAHIP_ERR_INVALID_ARG;
-  return for_shards(ctx->devs, n, 64,
-                    [&](Device& d, uint64_t lo, uint64_t hi) { return verify_keyed_shard(ctx, d, b, lo, hi); });
-}
-
-// The ECDSA keyed verifier on stream s (vkey_mu held, device current): as vkey_enqueue,
-// behind the ECDSA tables' fence. A device without ECDSA tables passes none: every lane
-// is then UNKNOWN_KEY.
-hipError_t ec_vkey_enqueue(Device& d, const uint32_t* key_id, const uint8_t* sigs, const uint8_t* sig_len,
-                           const uint8_t* msgs, const uint64_t* moff, const uint32_t* mlen, uint32_t msg_len,
-                           uint64_t n, const uint8_t* pre, uint32_t flags, uint8_t* status,
-                           unsigned long long* verdict, hipStream_t s) {
-  const EcVkeyState& st = d.ec_vkey_state;
-  const bool have = d.ec_vkeys.tab.p != nullptr;
-  hipError_t e = d.ec_vkeys.ev.wait(s);
-  e = e ? e
-        : launch_ecdsa_verify_keyed(key_id, sigs, sig_len, msgs, moff, mlen, msg_len, n, pre, flags,
-                                    d.ec_vkeys.tab.as<uint32_t>(), have && st.live[0] > 0, have && st.live[1] > 0,
-                                    status, verdict, s);
-  return e ? e : d.ec_vkeys.ev.record(s);
-}
-
-// cordahip_ecdsa_verify_keyed for lanes [lo, hi) on one device: verify_keyed_shard with
-// 72-byte DER slots and their lengths (pack_rows.hpp keyed_ec_pack_rows) and K13.
-int ec_verify_keyed_shard(cordahip_ctx* ctx, Device& d, const cordahip_keyed_sig_batch* b, uint64_t lo, uint64_t hi) {
-  std::lock_guard<std::mutex> g(d.vkey_host_mu);
-  const NodeBind nb(d);
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  const uint64_t chunk = (env_lanes("CORDAHIP_HOST_CHUNK", 1ull << 22) + 63) / 64 * 64;  // whole verdict words
-  HostPool& pool = pool_of(ctx, d);
-  hipStream_t s = d.stream;
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
-  std::vector<uint64_t> poff;
-  for (uint64_t a = lo; a < hi; a += chunk) {
-    const uint64_t m = std::min(chunk, hi - a);
-    const uint64_t words = (m + 63) / 64;
-    const double t0 = now_ms();
-    poff.resize(m);
-    const SignLayout lay = msg_chunk_layout(b->msg_off, a, m, poff.data());
-    const bool dense = lay.dense;
-    const uint64_t bytes = lay.bytes;
-    const size_t need[9] = {(size_t)m * 4, (size_t)m * 72, (size_t)m, (size_t)std::max<uint64_t>(bytes, 16),
-                            (size_t)m * 8, (size_t)m * 4,  (size_t)m, (size_t)words * 8,
-                            (size_t)m};
-    for (int k = 0; k < 9; k++)  // the previous chunk has drained: growing frees nothing in use
-      if (d.vkey_h[k].ensure(need[k]) != hipSuccess || d.vkey_d[k].ensure(need[k]) != hipSuccess)
-        return CORDAHIP_ERR_OUT_OF_MEMORY;
-    uint8_t* hm = d.vkey_h[3].as<uint8_t>();
-    uint64_t* ho = d.vkey_h[4].as<uint64_t>();
-    uint32_t* hl = d.vkey_h[5].as<uint32_t>();
-    pool.parallel_for(m, 1u << 14, [&](uint64_t x, uint64_t y) {
-      keyed_ec_pack_rows(b, a, x, y, lay, poff.data(), d.vkey_h[0].as<uint32_t>(), d.vkey_h[1].as<uint8_t>(),
-                         d.vkey_h[8].as<uint8_t>(), d.vkey_h[2].as<uint8_t>(), hm, ho, hl);
-    });
-    hipError_t e = hipMemcpyAsync(d.vkey_d[0].p, d.vkey_h[0].p, m * 4, h2d, s);
-    e = e ? e : hipMemcpyAsync(d.vkey_d[1].p, d.vkey_h[1].p, m * 72, h2d, s);
-    e = e ? e : hipMemcpyAsync(d.vkey_d[2].p, d.vkey_h[2].p, m, h2d, s);
-    e = e ? e : hipMemcpyAsync(d.vkey_d[8].p, d.vkey_h[8].p, m, h2d, s);
-    if (bytes) e = e ? e : hipMemcpyAsync(d.vkey_d[3].p, hm, bytes, h2d, s);
-    if (!dense) {
-      e = e ? e : hipMemcpyAsync(d.vkey_d[4].p, ho, m * 8, h2d, s);
-      e = e ? e : hipMemcpyAsync(d.vkey_d[5].p, hl, m * 4, h2d, s);
-    }
-    if (e == hipSuccess) {
-      std::lock_guard<std::mutex> gs(d.vkey_mu);
-      e = ec_vkey_enqueue(d, d.vkey_d[0].as<uint32_t>(), d.vkey_d[1].as<uint8_t>(), d.vkey_d[8].as<uint8_t>(),
-                          d.vkey_d[3].as<uint8_t>(), dense ? nullptr : d.vkey_d[4].as<uint64_t>(),
-                          dense ? nullptr : d.vkey_d[5].as<uint32_t>(), 32, m, d.vkey_d[2].as<uint8_t>(), b->flags,
-                          d.vkey_d[6].as<uint8_t>(), d.vkey_d[7].as<unsigned long long>(), s);
-    }
-    e = e ? e : hipMemcpyAsync(d.vkey_h[6].p, d.vkey_d[6].p, m, d2h, s);
-    e = e ? e : hipMemcpyAsync(d.vkey_h[7].p, d.vkey_d[7].p, words * 8, d2h, s);
-    e = e ? e : d.vkey_host_ev.record(s);
-    e = e ? e : d.vkey_host_ev.sync();
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(s);  // no queued work outlives the call
-      return CORDAHIP_ERR_HIP;
-    }
-    std::memcpy(b->status + a, d.vkey_h[6].p, m);
-    if (b->verdict) std::memcpy(b->verdict + a / 64, d.vkey_h[7].p, words * 8);
-    if (tracing())
-      fprintf(stderr, "[cordahip] dev %d keyed ECDSA verify chunk: %llu lanes (%s messages) in %.2f ms\n", d.id,
-              (unsigned long long)m, dense ? "32-byte" : "CSR", now_ms() - t0);
-  }
-  return CORDAHIP_SUCCESS;
-}
-
-int ec_verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) {
-  const uint64_t n = b->n;
-  if (n == 0) return CORDAHIP_SUCCESS;
-  if (!b->key_id || !b->sig_off || !b->msg_off || !b->status) return CORDAHIP_ERR_INVALID_ARG;
-  if (b->flags & ~CORDAHIP_FLAG_IS_VALID) return CORDAHIP_ERR_INVALID_ARG;
-  if (!check_keyed_sig_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
-  if ((b->msg_off[0] != b->msg_off[n] && !b->msg) || (b->sig_off[0] != b->sig_off[n] && !b->sig))
-    return CORDAHIP_ERR_INVALID_ARG;
-  return for_shards(ctx->devs, n, 64,
-                    [&](Device& d, uint64_t lo, uint64_t hi) { return ec_verify_keyed_shard(ctx, d, b, lo, hi); });
-}
-
-Device* dev_at(cordahip_ctx* ctx, int device) {
-  if (!ctx || device < 0 || device >= (int)ctx->devs.size()) return nullptr;
-  return ctx->devs[device].get();
-}
-
-// ---- notary commit log (K16, commit_log.hip) -------------------------------------
-std::shared_ptr<CommitLog> log_at(cordahip_ctx* ctx, uint32_t id) {
-  std::lock_guard<std::mutex> g(ctx->logs_mu);
-  const auto it = ctx->logs.find(id);
-  return it == ctx->logs.end() ? nullptr : it->second;
-}
-
-constexpr uint32_t kCommitMinLog2 = 6, kCommitMaxLog2 = 32;
-constexpr size_t kCommitRowBytes = sizeof(cordahip_commit_row), kCommitRefBytes = sizeof(cordahip_state_ref),
-                 kCommitByBytes = sizeof(cordahip_consuming_tx);
-static_assert(kCommitRefBytes == commit::kRefWords * 4 && kCommitByBytes == commit::kByWords * 4 &&
-                  kCommitRowBytes == kCommitRefBytes + kCommitByBytes,
-              "commit_core.hpp's rows are the header's");
-
-// would `more` further entries pass 7/8 of the capacity? (mu held)
-bool commit_log_full(const CommitLog& L, uint64_t more) {
-  const uint64_t room = ((1ull << L.capacity_log2) / 8) * 7;
-  return L.bound > room || more > room - L.bound;
-}
-
-// the log's host stage of at least `bytes` on both sides (mu held; the previous host
-// call has drained, so growing frees nothing in use)
-int commit_stage(CommitLog& L, size_t bytes) {
-  bytes = std::max<size_t>(bytes, 64);
-  if (L.stage_h.ensure(bytes) != hipSuccess || L.stage_d.ensure(bytes) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-  return CORDAHIP_SUCCESS;
-}
-
-int commit_log_create_impl(cordahip_ctx* ctx, int device, uint32_t capacity_log2, const uint8_t* salt,
-                           uint32_t* log_id) {
-  Device* d = dev_at(ctx, device);
-  if (!d || capacity_log2 < kCommitMinLog2 || capacity_log2 > kCommitMaxLog2) return CORDAHIP_ERR_INVALID_ARG;
-  const Activity act(*d);
-  if (hipSetDevice(d->id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  auto L = std::make_shared<CommitLog>();
-  L->dev = d;
-  for (DevBuf* b : {&L->tab, &L->counters, &L->scratch, &L->stage_d}) b->dev = d->id;
-  L->capacity_log2 = capacity_log2;
-  uint8_t k[16];
-  if (salt) {
-    std::memcpy(k, salt, 16);
-  } else {
-    std::random_device rd;
-    for (int i = 0; i < 16; i += 4) {
-      const uint32_t r = rd();
-      std::memcpy(k + i, &r, 4);
-    }
-  }
-  std::memcpy(&L->k0, k, 8);
-  std::memcpy(&L->k1, k + 8, 8);
-  if (L->tab.ensure((size_t)commit::kSlotWords * 4 << capacity_log2) != hipSuccess || L->counters.ensure(16) != hipSuccess)
-    return CORDAHIP_ERR_OUT_OF_MEMORY;
-  hipError_t e = hipMemsetAsync(L->tab.p, 0, L->tab.cap, d->stream);
-  e = e ? e : hipMemsetAsync(L->counters.p, 0, 16, d->stream);
-  const hipError_t f = hipStreamSynchronize(d->stream);
-  if (e != hipSuccess || f != hipSuccess) return CORDAHIP_ERR_HIP;
-  std::lock_guard<std::mutex> g(ctx->logs_mu);
-  L->id = ctx->next_log_id++;
-  if (L->id == 0) return CORDAHIP_ERR_OUT_OF_MEMORY;  // 2^32 logs created: ids are never reused
-  ctx->logs.emplace(L->id, L);
-  *log_id = L->id;
-  return CORDAHIP_SUCCESS;
-}
-
-int commit_log_destroy_impl(cordahip_ctx* ctx, uint32_t log_id) {
-  std::shared_ptr<CommitLog> L;
-  {
-    std::lock_guard<std::mutex> g(ctx->logs_mu);
-    const auto it = ctx->logs.find(log_id);
-    if (it == ctx->logs.end()) return CORDAHIP_ERR_INVALID_ARG;
-    L = it->second;
-    ctx->logs.erase(it);  // no new call finds it; a ticket already queued keeps it alive until it has run
-  }
-  std::lock_guard<std::mutex> g(L->mu);
-  if (hipSetDevice(L->dev->id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  return hip_err(L->ev.sync());  // the table goes with the last reference (~CommitLog)
-}
-
-int commit_log_reserve_impl(cordahip_ctx* ctx, uint32_t log_id, uint32_t capacity_log2) {
-  const auto L = log_at(ctx, log_id);
-  if (!L || capacity_log2 > kCommitMaxLog2) return CORDAHIP_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> g(L->mu);
-  if (capacity_log2 <= L->capacity_log2) return CORDAHIP_SUCCESS;  // never shrinks
-  Device& d = *L->dev;
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess || L->ev.sync() != hipSuccess) return CORDAHIP_ERR_HIP;
-  DevBuf nt;
-  nt.dev = d.id;
-  if (nt.ensure((size_t)commit::kSlotWords * 4 << capacity_log2) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-  const commit::Table from = L->table();
-  const commit::Table to{nt.as<uint32_t>(), (1ull << capacity_log2) - 1, L->k0, L->k1};
-  hipError_t e = hipMemsetAsync(nt.p, 0, nt.cap, d.stream);
-  e = e ? e : launch_commit_rehash(from, to, d.stream);
-  const hipError_t f = hipStreamSynchronize(d.stream);
-  if (e != hipSuccess || f != hipSuccess) {
-    nt.release();
-    return CORDAHIP_ERR_HIP;
-  }
-  std::swap(L->tab, nt);
-  nt.release();
-  L->capacity_log2 = capacity_log2;
-  return CORDAHIP_SUCCESS;
-}
-
-int commit_log_stats_impl(cordahip_ctx* ctx, uint32_t log_id, uint64_t* entries, uint64_t* capacity,
-                          uint64_t* next_seq) {
-  const auto L = log_at(ctx, log_id);
-  if (!L) return CORDAHIP_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> g(L->mu);
-  if (hipSetDevice(L->dev->id) != hipSuccess || L->ev.sync() != hipSuccess) return CORDAHIP_ERR_HIP;
-  uint64_t n = 0;
-  if (hipMemcpy(&n, L->counters.p, 8, hipMemcpyDeviceToHost) != hipSuccess) return CORDAHIP_ERR_HIP;
-  L->bound = n;  // every call enqueued so far has finished: the count is exact
-  if (entries) *entries = n;
-  if (capacity) *capacity = 1ull << L->capacity_log2;
-  if (next_seq) *next_seq = L->next_seq;
-  return CORDAHIP_SUCCESS;
-}
-
-int commit_log_load_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_row* rows, uint64_t n,
-                         uint64_t* n_already_present) {
-  const auto L = log_at(ctx, log_id);
-  if (!L || (n && !rows)) return CORDAHIP_ERR_INVALID_ARG;
-  if (n_already_present) *n_already_present = 0;
-  if (n == 0) return CORDAHIP_SUCCESS;
-  std::lock_guard<std::mutex> g(L->mu);
-  if (commit_log_full(*L, n)) return CORDAHIP_ERR_LOG_FULL;
-  Device& d = *L->dev;
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  if (const int rc = commit_stage(*L, n * kCommitRowBytes)) return rc;
-  const size_t need = commit_load_scratch_bytes(n);
-  if (L->ev.grow(need > L->scratch.cap, [&] { return L->scratch.ensure(need); }) != hipSuccess)
-    return CORDAHIP_ERR_OUT_OF_MEMORY;
-  std::memcpy(L->stage_h.p, rows, n * kCommitRowBytes);
-  hipStream_t s = d.stream;
-  unsigned long long* ctr = L->counters.as<unsigned long long>();
-  hipError_t e = hipMemcpyAsync(L->stage_d.p, L->stage_h.p, n * kCommitRowBytes, hipMemcpyHostToDevice, s);
-  e = e ? e : L->ev.wait(s);
-  e = e ? e : launch_commit_load(L->table(), L->stage_d.as<uint32_t>(), n, L->scratch.p, ctr, s);
-  e = e ? e : L->ev.record(s);
-  e = e ? e : hipMemcpyAsync(L->stage_h.p, ctr + 1, 8, hipMemcpyDeviceToHost, s);
-  const hipError_t f = hipStreamSynchronize(s);
-  if (e != hipSuccess || f != hipSuccess) return CORDAHIP_ERR_HIP;
-  const uint64_t already = *L->stage_h.as<uint64_t>();
-  L->bound += n - std::min(already, n);
-  if (n_already_present) *n_already_present = already;
-  return CORDAHIP_SUCCESS;
-}
-
-int commit_log_lookup_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_state_ref* refs, uint64_t n,
-                           uint8_t* present, cordahip_consuming_tx* by) {
-  const auto L = log_at(ctx, log_id);
-  if (!L || (n && (!refs || !present || !by))) return CORDAHIP_ERR_INVALID_ARG;
-  if (n == 0) return CORDAHIP_SUCCESS;
-  std::lock_guard<std::mutex> g(L->mu);
-  Device& d = *L->dev;
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  const size_t o_by = (n * kCommitRefBytes + 15) & ~(size_t)15, o_pr = o_by + n * kCommitByBytes;
-  if (const int rc = commit_stage(*L, o_pr + n)) return rc;
-  uint8_t *h = L->stage_h.as<uint8_t>(), *dv = L->stage_d.as<uint8_t>();
-  std::memcpy(h, refs, n * kCommitRefBytes);
-  hipStream_t s = d.stream;
-  hipError_t e = hipMemcpyAsync(dv, h, n * kCommitRefBytes, hipMemcpyHostToDevice, s);
-  e = e ? e : L->ev.wait(s);
-  e = e ? e
-        : launch_commit_lookup(L->table(), reinterpret_cast<const uint32_t*>(dv), n, dv + o_pr,
-                               reinterpret_cast<uint32_t*>(dv + o_by), s);
-  e = e ? e : L->ev.record(s);
-  e = e ? e : hipMemcpyAsync(h + o_by, dv + o_by, n * kCommitByBytes + n, hipMemcpyDeviceToHost, s);
-  const hipError_t f = hipStreamSynchronize(s);
-  if (e != hipSuccess || f != hipSuccess) return CORDAHIP_ERR_HIP;
-  std::memcpy(by, h + o_by, n * kCommitByBytes);
-  std::memcpy(present, h + o_pr, n);
-  return CORDAHIP_SUCCESS;
-}
-
-// A synchronous call's turn among the log's tickets: taken at construction behind every
-// ticket submitted so far, given up at destruction (commit_submit_impl's jobs wait the
-// same way, so a later ticket runs after the call).
-class CommitTurn {
- public:
-  explicit CommitTurn(CommitLog& L) : L_(L) {
-    std::unique_lock<std::mutex> w(L_.turn_mu);
-    const uint64_t turn = L_.turn_next++;
-    L_.turn_cv.wait(w, [&] { return L_.turn_now == turn; });
-  }
-  ~CommitTurn() {
-    {
-      std::lock_guard<std::mutex> w(L_.turn_mu);
-      L_.turn_now++;
-    }
-    L_.turn_cv.notify_all();
-  }
-  CommitTurn(const CommitTurn&) = delete;
-  CommitTurn& operator=(const CommitTurn&) = delete;
-
- private:
-  CommitLog& L_;
-};
-
-int commit_log_revoke_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_row* rows, uint64_t n,
-                           uint8_t* revoked, uint64_t* n_removed) {
-  const auto L = log_at(ctx, log_id);
-  if (!L || (n && (!rows || !revoked))) return CORDAHIP_ERR_INVALID_ARG;
-  if (n_removed) *n_removed = 0;
-  if (n == 0) return CORDAHIP_SUCCESS;
-  const CommitTurn turn(*L);
-  std::lock_guard<std::mutex> g(L->mu);
-  Device& d = *L->dev;
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  const size_t o_rev = (n * kCommitRowBytes + 15) & ~(size_t)15, o_cnt = (o_rev + n + 15) & ~(size_t)15;
-  if (const int rc = commit_stage(*L, o_cnt + 8)) return rc;
-  const size_t need = commit_revoke_scratch_bytes(n);
-  if (L->ev.grow(need > L->scratch.cap, [&] { return L->scratch.ensure(need); }) != hipSuccess)
-    return CORDAHIP_ERR_OUT_OF_MEMORY;
-  uint8_t *h = L->stage_h.as<uint8_t>(), *dv = L->stage_d.as<uint8_t>();
-  std::memcpy(h, rows, n * kCommitRowBytes);
-  hipStream_t s = d.stream;
-  unsigned long long* ctr = L->counters.as<unsigned long long>();
-  hipError_t e = hipMemcpyAsync(dv, h, n * kCommitRowBytes, hipMemcpyHostToDevice, s);
-  e = e ? e : L->ev.wait(s);
-  e = e ? e : launch_commit_revoke(L->table(), reinterpret_cast<const uint32_t*>(dv), n, dv + o_rev, L->scratch.p, ctr, s);
-  e = e ? e : L->ev.record(s);
-  e = e ? e : hipMemcpyAsync(h + o_rev, dv + o_rev, n, hipMemcpyDeviceToHost, s);
-  e = e ? e : hipMemcpyAsync(h + o_cnt, ctr + 1, 8, hipMemcpyDeviceToHost, s);
-  const hipError_t f = hipStreamSynchronize(s);
-  if (e != hipSuccess || f != hipSuccess) return CORDAHIP_ERR_HIP;
-  std::memcpy(revoked, h + o_rev, n);
-  if (n_removed) std::memcpy(n_removed, h + o_cnt, 8);
-  return CORDAHIP_SUCCESS;  // the bound stays: it remains an upper bound of the live entries
-}
-
-int commit_log_export_impl(cordahip_ctx* ctx, uint32_t log_id, uint64_t since_seq, cordahip_commit_row* rows,
-                           uint64_t* seq, uint64_t cap, uint64_t* n_total) {
-  const auto L = log_at(ctx, log_id);
-  if (!L || !n_total || (cap && !rows)) return CORDAHIP_ERR_INVALID_ARG;
-  const CommitTurn turn(*L);
-  std::lock_guard<std::mutex> g(L->mu);
-  Device& d = *L->dev;
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  cap = std::min(cap, L->bound);  // no more entries than the bound are live: slots past it are never written
-  const size_t o_seq = (cap * kCommitRowBytes + 15) & ~(size_t)15, o_cnt = o_seq + cap * 8;
-  if (const int rc = commit_stage(*L, o_cnt + 8)) return rc;
-  uint8_t *h = L->stage_h.as<uint8_t>(), *dv = L->stage_d.as<uint8_t>();
-  hipStream_t s = d.stream;
-  unsigned long long* total = reinterpret_cast<unsigned long long*>(dv + o_cnt);
-  hipError_t e = L->ev.wait(s);
-  e = e ? e
-        : launch_commit_export(L->table(), since_seq, reinterpret_cast<uint32_t*>(dv),
-                               reinterpret_cast<uint64_t*>(dv + o_seq), cap, total, s);
-  e = e ? e : L->ev.record(s);
-  e = e ? e : hipMemcpyAsync(h + o_cnt, total, 8, hipMemcpyDeviceToHost, s);
-  hipError_t f = hipStreamSynchronize(s);
-  if (e != hipSuccess || f != hipSuccess) return CORDAHIP_ERR_HIP;
-  uint64_t total_h = 0;
-  std::memcpy(&total_h, h + o_cnt, 8);
-  const uint64_t m = std::min(total_h, cap);
-  if (m) {  // only what was written comes back
-    e = hipMemcpyAsync(h, dv, m * kCommitRowBytes, hipMemcpyDeviceToHost, s);
-    e = e ? e : hipMemcpyAsync(h + o_seq, dv + o_seq, m * 8, hipMemcpyDeviceToHost, s);
-    f = hipStreamSynchronize(s);
-    if (e != hipSuccess || f != hipSuccess) return CORDAHIP_ERR_HIP;
-    std::memcpy(rows, h, m * kCommitRowBytes);
-    if (seq) std::memcpy(seq, h + o_seq, m * 8);
-  }
-  *n_total = total_h;
-  return CORDAHIP_SUCCESS;
-}
-
-// The commit kernels on stream s behind the log's previous call, followed by the
-// log's fence; the log's counters advance (mu held, device current, the scratch
-// grown, the load bound checked).
-hipError_t commit_enqueue(CommitLog& L, const commit::Batch& B, uint64_t n_refs, hipStream_t s) {
-  hipError_t e = L.ev.wait(s);
-  e = e ? e
-        : launch_commit_inputs(L.table(), B, n_refs, L.next_seq, L.scratch.p, L.counters.as<unsigned long long>(), s);
-  e = e ? e : L.ev.record(s);
-  L.next_seq += B.ntx;  // consumed even if an enqueue failed: sequence numbers only ever grow
-  L.bound += n_refs;
-  return e;
-}
-hipError_t commit_scratch(CommitLog& L, uint64_t ntx, uint64_t n_refs) {
-  const size_t need = commit_scratch_bytes(ntx, n_refs);
-  return L.ev.grow(need > L.scratch.cap, [&] { return L.scratch.ensure(need); });
-}
-
-// what the host and the device form ask of the scalars and the pointer pairing
-bool commit_scalars_ok(const cordahip_commit_batch* b) {
-  const cordahip_commit_batch z{0, nullptr, nullptr, nullptr, nullptr, 0, b->tw_from, b->tw_until, b->now_ns,
-                                b->tolerance_ns, nullptr, nullptr, nullptr, nullptr, nullptr};
-  return check_commit([](uint64_t, uint64_t, auto&&) {}, &z);
-}
-
-int commit_on(cordahip_ctx* ctx, CommitLog& L, const cordahip_commit_batch* b) {
-  const uint64_t ntx = b->ntx;
-  if (!check_commit(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
-  if (ntx == 0) return CORDAHIP_SUCCESS;
-  if (!b->txid || !b->caller || !b->tx_status || !b->committed) return CORDAHIP_ERR_INVALID_ARG;
-  const uint64_t r0 = b->tx_ref_off[0], nr = b->tx_ref_off[ntx] - r0;
-  if (nr && (!b->refs || !b->ref_state || !b->ref_by)) return CORDAHIP_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> g(L.mu);
-  if (commit_log_full(L, b->n_refs)) return CORDAHIP_ERR_LOG_FULL;
-  Device& d = *L.dev;
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  // the stage: inputs, then outputs, every array at a 16-byte boundary
-  size_t pos = 0;
-  const auto take = [&](size_t bytes) {
-    const size_t at = pos;
-    pos = (pos + bytes + 15) & ~(size_t)15;
-    return at;
-  };
-  const size_t o_txid = take(ntx * 32), o_caller = take(ntx * 4), o_refs = take(nr * kCommitRefBytes),
-               o_off = take((ntx + 1) * 8), o_from = take(b->tw_from ? ntx * 8 : 0),
-               o_until = take(b->tw_from ? ntx * 8 : 0), o_gate = take(b->gate ? ntx : 0), in_bytes = pos,
-               o_status = take(ntx), o_comm = take(ntx), o_state = take(nr), o_by = take(nr * kCommitByBytes);
-  if (const int rc = commit_stage(L, pos)) return rc;
-  if (commit_scratch(L, ntx, nr) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-  uint8_t *h = L.stage_h.as<uint8_t>(), *dv = L.stage_d.as<uint8_t>();
-  std::memcpy(h + o_txid, b->txid, ntx * 32);
-  std::memcpy(h + o_caller, b->caller, ntx * 4);
-  if (nr) std::memcpy(h + o_refs, b->refs + r0, nr * kCommitRefBytes);
-  uint64_t* off = reinterpret_cast<uint64_t*>(h + o_off);
-  for (uint64_t t = 0; t <= ntx; t++) off[t] = b->tx_ref_off[t] - r0;
-  if (b->tw_from) {
-    std::memcpy(h + o_from, b->tw_from, ntx * 8);
-    std::memcpy(h + o_until, b->tw_until, ntx * 8);
-  }
-  if (b->gate) std::memcpy(h + o_gate, b->gate, ntx);
-  commit::Batch B{};
-  B.ntx = ntx;
-  B.txid = reinterpret_cast<const uint32_t*>(dv + o_txid);
-  B.caller = reinterpret_cast<const uint32_t*>(dv + o_caller);
-  B.refs = reinterpret_cast<const uint32_t*>(dv + o_refs);
-  B.off = reinterpret_cast<const uint64_t*>(dv + o_off);
-  B.tw_from = b->tw_from ? reinterpret_cast<const int64_t*>(dv + o_from) : nullptr;
-  B.tw_until = b->tw_from ? reinterpret_cast<const int64_t*>(dv + o_until) : nullptr;
-  B.now_ns = b->now_ns;
-  B.tolerance_ns = b->tolerance_ns;
-  B.gate = b->gate ? dv + o_gate : nullptr;
-  B.tx_status = dv + o_status;
-  B.committed = dv + o_comm;
-  B.ref_state = dv + o_state;
-  B.ref_by = reinterpret_cast<uint32_t*>(dv + o_by);
-  hipStream_t s = d.stream;
-  const double t0 = now_ms();
-  hipError_t e = hipMemcpyAsync(dv, h, in_bytes, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    e = commit_enqueue(L, B, nr, s);
-    L.bound += b->n_refs - nr;  // the bound counts the call's n_refs, as the device form's must
-  }
-  e = e ? e : hipMemcpyAsync(h + o_status, dv + o_status, pos - o_status, hipMemcpyDeviceToHost, s);
-  e = e ? e : L.stage_ev.record(s);
-  e = e ? e : L.stage_ev.sync();
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s);  // no queued work outlives the call
-    return CORDAHIP_ERR_HIP;
-  }
-  std::memcpy(b->tx_status, h + o_status, ntx);
-  std::memcpy(b->committed, h + o_comm, ntx);
-  if (nr) {
-    std::memcpy(b->ref_state + r0, h + o_state, nr);
-    std::memcpy(b->ref_by + r0, h + o_by, nr * kCommitByBytes);
-  }
-  if (tracing())
-    fprintf(stderr, "[cordahip] dev %d commit log %u: %llu txs, %llu refs in %.2f ms\n", d.id, L.id,
-            (unsigned long long)ntx, (unsigned long long)nr, now_ms() - t0);
-  return CORDAHIP_SUCCESS;
-}
-
-int commit_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* b) {
-  const auto L = log_at(ctx, log_id);
-  return L ? commit_on(ctx, *L, b) : CORDAHIP_ERR_INVALID_ARG;
-}
-
-// The ticketed form: the call takes the log's next turn at submit, and the queued
-// jobs of one log run in turn order whichever worker picks them up (the pool's queue
-// is first in, first out, so the job whose turn it is has always been picked up).
-int commit_submit_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* b, uint64_t* ticket) {
-  const auto L = log_at(ctx, log_id);
-  if (!L) return CORDAHIP_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> g(L->turn_mu);
-  const uint64_t turn = L->turn_next;
-  *ticket = submit_job(ctx, [ctx, L, turn, copy = *b] {
-    {
-      std::unique_lock<std::mutex> w(L->turn_mu);
-      L->turn_cv.wait(w, [&] { return L->turn_now == turn; });
-    }
-    const int rc = guarded([&] { return commit_on(ctx, *L, &copy); });
-    {
-      std::lock_guard<std::mutex> w(L->turn_mu);
-      L->turn_now++;
-    }
-    L->turn_cv.notify_all();
-    return rc;
-  });
-  L->turn_next++;  // only once the job is queued: a failed submit leaves no gap in the turns
-  return CORDAHIP_SUCCESS;
-}
-
-int commit_device_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* b, void* hip_stream) {
-  const auto L = log_at(ctx, log_id);
-  if (!L || !commit_scalars_ok(b)) return CORDAHIP_ERR_INVALID_ARG;
-  const uint64_t ntx = b->ntx;
-  if (ntx == 0) return CORDAHIP_SUCCESS;
-  if (!b->txid || !b->caller || !b->tx_ref_off || !b->tx_status || !b->committed ||
-      (b->n_refs && (!b->refs || !b->ref_state || !b->ref_by)))
-    return CORDAHIP_ERR_INVALID_ARG;
-  const auto mis = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
-  if (mis(b->txid, 4) || mis(b->caller, 4) || mis(b->refs, 4) || mis(b->ref_by, 4) || mis(b->tx_ref_off, 8) ||
-      mis(b->tw_from, 8) || mis(b->tw_until, 8))
-    return CORDAHIP_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> g(L->mu);
-  if (commit_log_full(*L, b->n_refs)) return CORDAHIP_ERR_LOG_FULL;
-  commit::Batch B{};
-  B.ntx = ntx;
-  B.txid = reinterpret_cast<const uint32_t*>(b->txid);
-  B.caller = b->caller;
-  B.refs = reinterpret_cast<const uint32_t*>(b->refs);
-  B.off = b->tx_ref_off;
-  B.tw_from = b->tw_from;
-  B.tw_until = b->tw_until;
-  B.now_ns = b->now_ns;
-  B.tolerance_ns = b->tolerance_ns;
-  B.gate = b->gate;
-  B.tx_status = b->tx_status;
-  B.committed = b->committed;
-  B.ref_state = b->ref_state;
-  B.ref_by = reinterpret_cast<uint32_t*>(b->ref_by);
-  return device_call(
-      *L->dev, hip_stream, [&] { return commit_scratch(*L, ntx, b->n_refs); },
-      [&](hipStream_t s) { return commit_enqueue(*L, B, b->n_refs, s); });
-}
-
 }  // namespace
 
 extern "C" {
@@ -2603,227 +1573,6 @@ int cordahip_ed25519_sign_device(cordahip_ctx* ctx, int device, const void* d_se
   return hip_err(launch_ed25519_sign(static_cast<const uint8_t*>(d_seeds), static_cast<const uint8_t*>(d_msgs),
                                      msg_len, n, d->btab.as<uint32_t>(), static_cast<uint8_t*>(d_pubs),
                                      static_cast<uint8_t*>(d_sigs), s));
-}
-
-int cordahip_signer_add_ed25519(cordahip_ctx* ctx, const uint8_t seed[32], uint32_t* key_id, uint8_t pub[32]) {
-  if (!ctx || !seed || !key_id || !pub) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return signer_add_impl(ctx, seed, key_id, pub); });
-}
-
-int cordahip_signer_remove(cordahip_ctx* ctx, uint32_t key_id) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return signer_remove_impl(ctx, key_id); });
-}
-
-int cordahip_sign(cordahip_ctx* ctx, const cordahip_sign_batch* batch) {
-  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return sign_impl(ctx, batch); });
-}
-
-int cordahip_sign_submit(cordahip_ctx* ctx, const cordahip_sign_batch* batch, uint64_t* ticket) {
-  return submit(ctx, ticket, sign_impl, batch);
-}
-
-int cordahip_ed25519_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
-                                       uint32_t msg_len, uint64_t n, const void* d_gate, void* d_sigs,
-                                       void* d_status, void* hip_stream) {
-  Device* d = dev_at(ctx, device);
-  if (!d || (n && (!d_key_id || !d_sigs || !d_status || (msg_len && !d_msgs)))) return CORDAHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_sigs) & 15) || (reinterpret_cast<uintptr_t>(d_key_id) & 3) ||
-      (msg_len == 32 && (reinterpret_cast<uintptr_t>(d_msgs) & 15)))
-    return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&]() -> int {
-    std::lock_guard<std::mutex> g(d->sign_mu);
-    return device_call(*d, hip_stream, [&](hipStream_t s) {
-      return sign_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_msgs), nullptr,
-                          nullptr, msg_len, n, static_cast<const uint8_t*>(d_gate), static_cast<uint8_t*>(d_sigs),
-                          static_cast<uint8_t*>(d_status), s);
-    });
-  });
-}
-
-int cordahip_commit_log_create(cordahip_ctx* ctx, int device, uint32_t capacity_log2, const uint8_t salt[16],
-                               uint32_t* log_id) {
-  if (!ctx || !log_id) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_log_create_impl(ctx, device, capacity_log2, salt, log_id); });
-}
-
-int cordahip_commit_log_destroy(cordahip_ctx* ctx, uint32_t log_id) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_log_destroy_impl(ctx, log_id); });
-}
-
-int cordahip_commit_log_reserve(cordahip_ctx* ctx, uint32_t log_id, uint32_t capacity_log2) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_log_reserve_impl(ctx, log_id, capacity_log2); });
-}
-
-int cordahip_commit_log_stats(cordahip_ctx* ctx, uint32_t log_id, uint64_t* entries, uint64_t* capacity,
-                              uint64_t* next_seq) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_log_stats_impl(ctx, log_id, entries, capacity, next_seq); });
-}
-
-int cordahip_commit_log_load(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_row* rows, uint64_t n,
-                             uint64_t* n_already_present) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_log_load_impl(ctx, log_id, rows, n, n_already_present); });
-}
-
-int cordahip_commit_log_lookup(cordahip_ctx* ctx, uint32_t log_id, const cordahip_state_ref* refs, uint64_t n,
-                               uint8_t* present, cordahip_consuming_tx* by) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_log_lookup_impl(ctx, log_id, refs, n, present, by); });
-}
-
-int cordahip_commit_log_revoke(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_row* rows, uint64_t n,
-                               uint8_t* revoked, uint64_t* n_removed) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_log_revoke_impl(ctx, log_id, rows, n, revoked, n_removed); });
-}
-
-int cordahip_commit_log_export(cordahip_ctx* ctx, uint32_t log_id, uint64_t since_seq, cordahip_commit_row* rows,
-                               uint64_t* seq, uint64_t cap, uint64_t* n_total) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_log_export_impl(ctx, log_id, since_seq, rows, seq, cap, n_total); });
-}
-
-int cordahip_commit_inputs(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* batch) {
-  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_impl(ctx, log_id, batch); });
-}
-
-int cordahip_commit_inputs_submit(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* batch,
-                                  uint64_t* ticket) {
-  if (!ctx || !batch || !ticket) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_submit_impl(ctx, log_id, batch, ticket); });
-}
-
-int cordahip_commit_inputs_device(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* d_batch,
-                                  void* hip_stream) {
-  if (!ctx || !d_batch) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return commit_device_impl(ctx, log_id, d_batch, hip_stream); });
-}
-
-int cordahip_vkey_add_ed25519(cordahip_ctx* ctx, const uint8_t key[32], uint32_t* key_id, uint8_t* key_status) {
-  if (!ctx || !key || !key_id || !key_status) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return vkey_add_impl(ctx, 0u, key, 32u, key_id, key_status); });
-}
-
-int cordahip_vkey_add_ecdsa(cordahip_ctx* ctx, uint32_t scheme, const uint8_t* key, uint32_t key_len, uint32_t* key_id,
-                            uint8_t* key_status) {
-  if (!ctx || !key_id || !key_status || (key_len && !key)) return CORDAHIP_ERR_INVALID_ARG;
-  if (scheme != CORDAHIP_SCHEME_ECDSA_SECP256K1_SHA256 && scheme != CORDAHIP_SCHEME_ECDSA_SECP256R1_SHA256)
-    return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return vkey_add_impl(ctx, scheme, key, key_len, key_id, key_status); });
-}
-
-int cordahip_vkey_remove(cordahip_ctx* ctx, uint32_t key_id) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return vkey_remove_impl(ctx, key_id); });
-}
-
-int cordahip_vkey_set_routing(cordahip_ctx* ctx, uint32_t on) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  for (auto& dp : ctx->devs) dp->route_on.store(on ? 1u : 0u);
-  return CORDAHIP_SUCCESS;
-}
-
-int cordahip_vkey_route_stats(cordahip_ctx* ctx, int device, uint64_t* keyed_lanes, uint64_t* generic_lanes) {
-  Device* d = dev_at(ctx, device);
-  if (!d || !keyed_lanes || !generic_lanes) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&]() -> int {
-    std::lock_guard<std::mutex> g(d->vkey_mu);
-    uint64_t tot[2] = {0, 0};
-    if (d->vkeys.route_tot.p) {  // else: no routed enqueue on this device yet
-      // every routed enqueue's partition pass is followed by vkeys.ev
-      if (hipSetDevice(d->id) != hipSuccess || d->vkeys.ev.sync() != hipSuccess ||
-          hipMemcpy(tot, d->vkeys.route_tot.p, sizeof tot, hipMemcpyDeviceToHost) != hipSuccess)
-        return CORDAHIP_ERR_HIP;
-    }
-    *keyed_lanes = tot[0];
-    *generic_lanes = tot[1];
-    return CORDAHIP_SUCCESS;
-  });
-}
-
-int cordahip_vkey_set_routing_ecdsa(cordahip_ctx* ctx, uint32_t on) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  for (auto& dp : ctx->devs) dp->ec_route_on.store(on ? 1u : 0u);
-  return CORDAHIP_SUCCESS;
-}
-
-int cordahip_vkey_route_stats_ecdsa(cordahip_ctx* ctx, int device, uint64_t* keyed_lanes, uint64_t* generic_lanes) {
-  Device* d = dev_at(ctx, device);
-  if (!d || !keyed_lanes || !generic_lanes) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&]() -> int {
-    std::lock_guard<std::mutex> g(d->vkey_mu);
-    uint64_t tot[2] = {0, 0};
-    if (d->ec_vkeys.route_tot.p) {  // else: no routed ECDSA enqueue on this device yet
-      // every routed enqueue's partition pass is followed by ec_vkeys.ev
-      if (hipSetDevice(d->id) != hipSuccess || d->ec_vkeys.ev.sync() != hipSuccess ||
-          hipMemcpy(tot, d->ec_vkeys.route_tot.p, sizeof tot, hipMemcpyDeviceToHost) != hipSuccess)
-        return CORDAHIP_ERR_HIP;
-    }
-    *keyed_lanes = tot[0];
-    *generic_lanes = tot[1];
-    return CORDAHIP_SUCCESS;
-  });
-}
-
-int cordahip_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch) {
-  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return verify_keyed_impl(ctx, batch); });
-}
-
-int cordahip_verify_keyed_submit(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch, uint64_t* ticket) {
-  return submit(ctx, ticket, verify_keyed_impl, batch);
-}
-
-int cordahip_ed25519_verify_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_sigs,
-                                         const void* d_msgs, uint32_t msg_len, uint64_t n, void* d_status,
-                                         void* d_verdict, void* hip_stream) {
-  Device* d = dev_at(ctx, device);
-  if (!d || (n && (!d_key_id || !d_sigs || !d_status || (msg_len && !d_msgs)))) return CORDAHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_sigs) & 15) || (reinterpret_cast<uintptr_t>(d_key_id) & 3) ||
-      (reinterpret_cast<uintptr_t>(d_verdict) & 7) || (msg_len == 32 && (reinterpret_cast<uintptr_t>(d_msgs) & 15)))
-    return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&]() -> int {
-    std::lock_guard<std::mutex> g(d->vkey_mu);
-    return device_call(*d, hip_stream, [&](hipStream_t s) {
-      return vkey_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_sigs),
-                          static_cast<const uint8_t*>(d_msgs), nullptr, nullptr, msg_len, n, nullptr, 0u,
-                          static_cast<uint8_t*>(d_status), static_cast<unsigned long long*>(d_verdict), s);
-    });
-  });
-}
-
-int cordahip_ecdsa_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch) {
-  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return ec_verify_keyed_impl(ctx, batch); });
-}
-
-int cordahip_ecdsa_verify_keyed_submit(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch, uint64_t* ticket) {
-  return submit(ctx, ticket, ec_verify_keyed_impl, batch);
-}
-
-int cordahip_ecdsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_sigs,
-                                       const void* d_sig_len, const void* d_msgs, uint32_t msg_len, uint64_t n,
-                                       void* d_status, void* d_verdict, void* hip_stream) {
-  Device* d = dev_at(ctx, device);
-  if (!d || (n && (!d_key_id || !d_sigs || !d_sig_len || !d_status || (msg_len && !d_msgs))))
-    return CORDAHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_key_id) & 3) || (reinterpret_cast<uintptr_t>(d_verdict) & 7))
-    return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&]() -> int {
-    std::lock_guard<std::mutex> g(d->vkey_mu);
-    return device_call(*d, hip_stream, [&](hipStream_t s) {
-      return ec_vkey_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_sigs),
-                             static_cast<const uint8_t*>(d_sig_len), static_cast<const uint8_t*>(d_msgs), nullptr,
-                             nullptr, msg_len, n, nullptr, 0u, static_cast<uint8_t*>(d_status),
-                             static_cast<unsigned long long*>(d_verdict), s);
-    });
-  });
 }
 
 int cordahip_ecdsa_sign_device(cordahip_ctx* ctx, int device, const void* d_scheme, const void* d_seeds,

@@ -181,20 +181,27 @@ inline SignLayout msg_chunk_layout(const uint64_t* msg_off, uint64_t a, uint64_t
 inline SignLayout sign_chunk_layout(const cordahip_sign_batch* b, uint64_t a, uint64_t m, uint64_t* poff) {
   return msg_chunk_layout(b->msg_off, a, m, poff);
 }
+// the message half of row i: the len bytes at msg + o to the row's place in the stage and
+// -- not dense -- that place and the length beside them
+inline void pack_msg(const uint8_t* msg, uint64_t o, uint64_t len, uint64_t i, const SignLayout& l, const uint64_t* poff,
+                     uint8_t* hm, uint64_t* ho, uint32_t* hl) {
+  const uint64_t p = l.dense ? i * 32 : poff[i];
+  if (len) std::memcpy(hm + p, msg + o, len);
+  if (!l.dense) {
+    ho[i] = p;
+    hl[i] = (uint32_t)len;
+  }
+}
 // rows [x, y) of the chunk at lane a: key ids, gate bytes (b->gate != NULL), messages, and
 // -- not dense -- offsets and lengths
 inline void sign_pack_rows(const cordahip_sign_batch* b, uint64_t a, uint64_t x, uint64_t y, const SignLayout& l,
                            const uint64_t* poff, uint32_t* hid, uint8_t* hgate, uint8_t* hm, uint64_t* ho,
                            uint32_t* hl) {
   for (uint64_t i = x; i < y; i++) {
-    const uint64_t o = b->msg_off[a + i], len = b->msg_off[a + i + 1] - o, p = l.dense ? i * 32 : poff[i];
+    const uint64_t o = b->msg_off[a + i], len = b->msg_off[a + i + 1] - o;
     hid[i] = b->key_id[a + i];
     if (b->gate) hgate[i] = b->gate[a + i];
-    if (len) std::memcpy(hm + p, b->msg + o, len);
-    if (!l.dense) {
-      ho[i] = p;
-      hl[i] = (uint32_t)len;
-    }
+    pack_msg(b->msg, o, len, i, l, poff, hm, ho, hl);
   }
 }
 
@@ -208,7 +215,7 @@ inline void keyed_pack_rows(const cordahip_keyed_sig_batch* b, uint64_t a, uint6
                             uint64_t* ho, uint32_t* hl) {
   const bool do_verify = !(b->flags & CORDAHIP_FLAG_IS_VALID);
   for (uint64_t i = x; i < y; i++) {
-    const uint64_t o = b->msg_off[a + i], len = b->msg_off[a + i + 1] - o, p = l.dense ? i * 32 : poff[i];
+    const uint64_t o = b->msg_off[a + i], len = b->msg_off[a + i + 1] - o;
     const uint64_t so = b->sig_off[a + i], sl = b->sig_off[a + i + 1] - so;
     hid[i] = b->key_id[a + i];
     uint8_t st = CORDAHIP_STATUS_OK;
@@ -217,11 +224,7 @@ inline void keyed_pack_rows(const cordahip_keyed_sig_batch* b, uint64_t a, uint6
     if (st == CORDAHIP_STATUS_OK) std::memcpy(hsig + i * 64, b->sig + so, 64);
     else std::memset(hsig + i * 64, 0, 64);
     hpre[i] = st;
-    if (len) std::memcpy(hm + p, b->msg + o, len);
-    if (!l.dense) {
-      ho[i] = p;
-      hl[i] = (uint32_t)len;
-    }
+    pack_msg(b->msg, o, len, i, l, poff, hm, ho, hl);
   }
 }
 
@@ -236,7 +239,7 @@ inline void keyed_ec_pack_rows(const cordahip_keyed_sig_batch* b, uint64_t a, ui
                                uint8_t* hpre, uint8_t* hm, uint64_t* ho, uint32_t* hl) {
   const bool do_verify = !(b->flags & CORDAHIP_FLAG_IS_VALID);
   for (uint64_t i = x; i < y; i++) {
-    const uint64_t o = b->msg_off[a + i], len = b->msg_off[a + i + 1] - o, p = l.dense ? i * 32 : poff[i];
+    const uint64_t o = b->msg_off[a + i], len = b->msg_off[a + i + 1] - o;
     const uint64_t so = b->sig_off[a + i], sl = b->sig_off[a + i + 1] - so;
     hid[i] = b->key_id[a + i];
     uint8_t st = CORDAHIP_STATUS_OK;
@@ -254,11 +257,7 @@ inline void keyed_ec_pack_rows(const cordahip_keyed_sig_batch* b, uint64_t a, ui
       hsl[i] = 72;
     }
     hpre[i] = st;
-    if (len) std::memcpy(hm + p, b->msg + o, len);
-    if (!l.dense) {
-      ho[i] = p;
-      hl[i] = (uint32_t)len;
-    }
+    pack_msg(b->msg, o, len, i, l, poff, hm, ho, hl);
   }
 }
 

@@ -242,7 +242,7 @@ static hipError_t ec_route_and_keyed(Device& d, EcWork& w, const uint8_t* scheme
                                      const uint8_t* pre, uint8_t* status, uint32_t flags, hipStream_t s,
                                      bool* routed) {
   std::lock_guard<std::mutex> vk(d.vkey_mu);
-  const EcVkeyState& st = d.ec_vkey_state;
+  const EcVkeyState& st = d.ec_vkeys.state;
   if (!d.ec_vkeys.tab.p || !(st.live[0] || st.live[1])) return hipSuccess;
   if (!d.ec_vkeys.route_tot.p) {  // the device's first routed ECDSA enqueue
     if (d.ec_vkeys.route_tot.ensure(16) != hipSuccess) {
@@ -282,7 +282,7 @@ hipError_t ec_verify_enqueue(Device& d, const uint8_t* scheme, const uint8_t* ke
   bool want_route = d.ec_route_on.load(std::memory_order_relaxed) && n && n <= ecdsa_route_max_lanes();
   if (want_route) {  // a look at the registry; decided for good in ec_route_and_keyed
     std::lock_guard<std::mutex> vk(d.vkey_mu);
-    want_route = d.ec_vkeys.tab.p && (d.ec_vkey_state.live[0] || d.ec_vkey_state.live[1]);
+    want_route = d.ec_vkeys.tab.p && (d.ec_vkeys.state.live[0] || d.ec_vkeys.state.live[1]);
   }
   // the scratch grows in powers of two from a floor, behind the workspace's fence; no
   // room for it: the batch is verified unrouted
@@ -529,7 +529,7 @@ void device_budget(Device& d) {  // device current
 void trim_device(Device& d) {
   SetLease l0(d, 0, true), l1(d, 1, true);
   std::lock_guard<std::mutex> gk(d.kryo_mu), gs(d.stream_mu), gp(d.ped_mu), ge0(d.ed_mu[0]), ge1(d.ed_mu[1]),
-      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu), gv(d.cover_mu), gh(d.sign_host_mu), gvh(d.vkey_host_mu);
+      gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu), gv(d.cover_mu), gh(d.sign_stage.mu), gvh(d.vkey_stage.mu);
   if (hipSetDevice(d.id) != hipSuccess) return;
   d.release_idle();
   if (tracing()) fprintf(stderr, "[cordahip] dev %d: idle buffers released\n", d.id);

@@ -1,7 +1,8 @@
 // libcordahip's internal runtime types (not ABI): per-device state and what it
 // owns (buffers, fences, events, streams), the ticket pool, the host thread pool
 // and the enqueue helpers (runtime.cpp) shared by cordahip.cpp (C-ABI, tx /
-// stream / device paths) and host_batch.cpp (the generic CSR signature batch).
+// stream / device paths), keyed.cpp (registered keys), commit_api.cpp (the commit
+// log) and host_batch.cpp (the generic CSR signature batch).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +24,7 @@
 
 #include "../../include/cordahip.h"
 #include "commit_core.hpp"
+#include "key_slots.hpp"
 #include "numa_place.hpp"
 
 namespace cordahip {
@@ -488,16 +490,13 @@ struct RsaWork {
   }
 };
 
-// The Ed25519 signer's key table of one device (ed25519_comb.hpp: 4,096 records of
-// 128 bytes and the expansion kernel's scratch): private keys, so it is handled apart
-// from the buffers above. It is allocated (zeroed) by the context's first
-// cordahip_signer_add_ed25519, counted in the device's account like every DevBuf, and
-// then lives until cordahip_shutdown, which zeroes it before ~Device frees it: the
-// idle release and cordahip_trim never see it (Device::visit leaves it out;
-// Device::visit_keys is for bind and ~Device), so a signer cannot lose its keys to an
-// idle timer. ev: the fence of the kernels that read the table. stage: 64 page-locked
-// bytes the seed goes out and the public key comes back in (wiped before add returns).
-struct SignKeys {
+// The key table of one registered-key family on one device. It is allocated (zeroed) by
+// the context's first add of the family, counted in the device's account like every
+// DevBuf, and then kept until ~Device: the idle release and cordahip_trim never see it
+// (Device::visit leaves it out; Device::visit_keys is for bind and ~Device), so nobody
+// loses registered keys to an idle timer. ev: the fence of the kernels that read the
+// table. stage: page-locked bytes a key goes out and its answer comes back in.
+struct KeyTable {
   DevBuf tab;
   PinBuf stage;
   Fence ev;
@@ -509,60 +508,76 @@ struct SignKeys {
   }
 };
 
-// The Ed25519 verification-key table of one device (ed25519_vkey.hpp: 64 window tables
-// of 512 KiB and the base point's, their records and the build kernel's scratch). Public keys, but handled
-// like the signer's table: allocated (zeroed) by the context's first
-// cordahip_vkey_add_ed25519, counted in the device's account, and then kept until
-// ~Device -- the idle release and cordahip_trim never see it (Device::visit_keys), so a
-// verifier cannot lose its registered keys to an idle timer. ev: the fence of the
-// kernels that read the table. stage: 64 page-locked bytes the key bytes go out and the
-// decode verdict comes back in. live: the slots whose record is live on this device
-// (bit per slot, Device::vkey_mu). route_tot: the device's cumulative counters of
+// The Ed25519 signer's (ed25519_comb.hpp: 4,096 records of 128 bytes and the expansion
+// kernel's scratch): private keys, so cordahip_shutdown zeroes it before ~Device frees
+// it. stage: 64 bytes, the seed out and the public key back (wiped before add returns).
+struct SignKeys : KeyTable {};
+
+// The Ed25519 verification keys' (ed25519_vkey.hpp: 64 window tables of 512 KiB and the
+// base point's, their records and the build kernel's scratch). stage: 64 bytes, the key
+// bytes out and the decode verdict back. live: the slots whose record is live on this
+// device (bit per slot, Device::vkey_mu). route_tot: the device's cumulative counters of
 // routed lanes (K14: keyed, generic; two 64-bit words, zeroed when allocated by the
 // first routed enqueue), written by kernels ordered by ev.
-struct VerifyKeys {
-  DevBuf tab;
-  PinBuf stage;
-  Fence ev;
+struct VerifyKeys : KeyTable {
   uint64_t live = 0;
   DevBuf route_tot;
   template <class V>
   void visit(V& v) {
-    v.dev(tab, kKept);
-    v.pin(stage, kKept);
-    v.fence(ev);
+    KeyTable::visit(v);
     v.dev(route_tot, kKept);
   }
 };
 
-// The ECDSA verification-key table of one device (ecdsa_vkey.hpp: 64 window tables of
-// 320 KiB, the two curves' base-point tables, the records and the build kernel's
-// scratch), allocated (records zeroed) by the context's first
-// cordahip_vkey_add_ecdsa and then handled exactly like VerifyKeys. stage: 128
-// page-locked bytes, the SEC1 bytes out and the decode verdict back. route_tot: the
-// device's cumulative counters of routed ECDSA lanes (K15: keyed, generic; two 64-bit
-// words, zeroed when allocated by the first routed enqueue), written by kernels
-// ordered by ev.
-struct EcVerifyKeys {
-  DevBuf tab;
-  PinBuf stage;
-  Fence ev;
-  DevBuf route_tot;
-  template <class V>
-  void visit(V& v) {
-    v.dev(tab, kKept);
-    v.pin(stage, kKept);
-    v.fence(ev);
-    v.dev(route_tot, kKept);
-  }
-};
-// What the host knows of that table (Device::vkey_mu): base[c]: the base-point table of
-// curve c (0: secp256k1, 1: P-256) has been built; live[c]: that curve's live keys on
-// this device; scheme[slot]: the curve of the slot's live record (0: none).
+// The ECDSA verification keys' (ecdsa_vkey.hpp: 64 window tables of 320 KiB, the two
+// curves' base-point tables, the records and the build kernel's scratch). stage: 128
+// bytes, the SEC1 bytes out and the decode verdict back. route_tot: as VerifyKeys' (K15).
+// state: what the host knows of the table (Device::vkey_mu): base[c]: the base-point
+// table of curve c (0: secp256k1, 1: P-256) has been built; live[c]: that curve's live
+// keys on this device; scheme[slot]: the curve of the slot's live record (0: none).
 struct EcVkeyState {
   uint32_t base[2] = {0, 0};
   uint32_t live[2] = {0, 0};
   uint8_t scheme[64] = {};
+};
+struct EcVerifyKeys : KeyTable {
+  DevBuf route_tot;
+  EcVkeyState state;
+  template <class V>
+  void visit(V& v) {
+    KeyTable::visit(v);
+    v.dev(route_tot, kKept);
+  }
+};
+
+// a page-locked buffer and its twin on the device (ensure: true when it failed)
+struct StageBuf {
+  PinBuf h;
+  DevBuf d;
+  bool ensure(size_t bytes) { return h.ensure(bytes) != hipSuccess || d.ensure(bytes) != hipSuccess; }
+  hipError_t to_device(size_t bytes, hipStream_t s) { return hipMemcpyAsync(d.p, h.p, bytes, hipMemcpyHostToDevice, s); }
+  hipError_t to_host(size_t bytes, hipStream_t s) { return hipMemcpyAsync(h.p, d.p, bytes, hipMemcpyDeviceToHost, s); }
+};
+// The chunk stage of a registered-key host call (keyed.cpp keyed_chunks): page-locked
+// buffers the host packs a chunk's lanes into and their twins on the device. Every call
+// uses ids (key ids), msgs, msg_off and msg_len (the messages, with offsets and lengths
+// when the chunk is not dense 32-byte rows) and status. cordahip_sign adds gate (gate
+// bytes in) and sig_rows (64-byte signatures out); the verifiers add sig_rows (in: 64
+// bytes a row, 72-byte DER slots for ECDSA), sig_len (ECDSA only), pre (the host's
+// pre-statuses) and verdict (words out). What a call does not use stays empty. mu is
+// held for a shard's run; ev follows a chunk's last copy.
+struct KeyedStage {
+  std::mutex mu;
+  StageBuf ids, msgs, msg_off, msg_len, status, gate, sig_rows, sig_len, pre, verdict;
+  Fence ev;
+  template <class V>
+  void visit(V& v) {
+    for (StageBuf* b : {&ids, &msgs, &msg_off, &msg_len, &status, &gate, &sig_rows, &sig_len, &pre, &verdict}) {
+      v.pin(b->h, kFreed);
+      v.dev(b->d, kFreed);
+    }
+    v.fence(ev);
+  }
 };
 
 // Fork-join pool for host-side packing and scattering. parallel_for splits
@@ -712,13 +727,8 @@ struct Device {
   SignKeys keys;
   std::mutex sign_mu;
   uint32_t* comb() const { return reinterpret_cast<uint32_t*>(static_cast<char*>(btab.p) + ed25519_btable_bytes()); }
-  // cordahip_sign's chunk stage: h/d[0] key ids, [1] messages, [2] their offsets, [3]
-  // their lengths, [4] gate bytes, [5] signature rows, [6] statuses. sign_host_mu is
-  // held for a shard's run; sign_host_ev follows a chunk's last copy.
-  std::mutex sign_host_mu;
-  PinBuf sign_h[7];
-  DevBuf sign_d[7];
-  Fence sign_host_ev;
+  // cordahip_sign's chunk stage (KeyedStage)
+  KeyedStage sign_stage;
 
   // Ed25519 verification against registered keys (K12). vkeys: the key tables
   // (VerifyKeys). vkey_mu orders every user of them exactly as sign_mu orders the
@@ -732,9 +742,9 @@ struct Device {
   // lock it did not take before.
   // Lock order of the locks met on these paths, outermost first:
   //   ped_mu / stream_mu / a SetLease (the pipelines) -> ed_mu[0] -> ed_mu[1] ->
-  //   ec_mu[0] -> ec_mu[1] -> ... -> vkey_host_mu -> vkey_mu.
-  // trim_device takes them in that order up to vkey_host_mu; a keyed host call holds
-  // vkey_host_mu and takes vkey_mu inside it; a routed enqueue holds ed_mu[slot]
+  //   ec_mu[0] -> ec_mu[1] -> ... -> sign_stage.mu -> vkey_stage.mu -> vkey_mu.
+  // trim_device takes them in that order up to vkey_stage.mu; a keyed host call holds
+  // vkey_stage.mu and takes vkey_mu inside it; a routed enqueue holds ed_mu[slot]
   // (Ed25519, K14) or ec_mu[slot] (ECDSA, K15) and takes vkey_mu inside it. vkey_mu is
   // innermost: whoever holds it (add, remove, the
   // stats call, a keyed or routed enqueue) takes no other lock of the device but tmu
@@ -746,33 +756,21 @@ struct Device {
   // ECDSA verification against registered keys (K13): the tables of the same registry's
   // ECDSA keys, under the same vkey_mu, with a fence of their own.
   // Routing (K15, cordahip_vkey_set_routing_ecdsa): with ec_route_on set and a live
-  // ECDSA key (ec_vkey_state.live), ec_verify_enqueue is a keyed call too: under the
+  // ECDSA key (ec_vkeys.state.live), ec_verify_enqueue is a keyed call too: under the
   // caller's ec_mu[slot] it takes vkey_mu for the route pass and the K13 launches --
   // behind ec_vkeys.ev, followed by ec_vkeys.ev -- and drops it before the generic
   // engine. With ec_route_on clear it takes no lock it did not take before.
   EcVerifyKeys ec_vkeys;
-  EcVkeyState ec_vkey_state;
   std::atomic<uint32_t> ec_route_on{0};
-  // cordahip_verify_keyed's chunk stage: h/d[0] key ids, [1] signature rows, [2] host
-  // pre-statuses, [3] messages, [4] their offsets, [5] their lengths, [6] statuses, [7]
-  // verdict words, [8] signature lengths (cordahip_ecdsa_verify_keyed only, whose rows
-  // are 72-byte DER slots). vkey_host_mu is held for a shard's run; vkey_host_ev
-  // follows a chunk's last copy.
-  std::mutex vkey_host_mu;
-  PinBuf vkey_h[9];
-  DevBuf vkey_d[9];
-  Fence vkey_host_ev;
+  // the chunk stage of cordahip_verify_keyed and cordahip_ecdsa_verify_keyed (KeyedStage)
+  KeyedStage vkey_stage;
 
   // everything but `keys`, `vkeys` and `ec_vkeys`, which the idle release is never offered (visit_keys)
   template <class V>
   void visit(V& v) {
     for (DevBuf* b : {&btab, &gtab_k1, &gtab_r1}) v.dev(*b, kKept);
-    for (PinBuf& b : vkey_h) v.pin(b, kFreed);
-    for (DevBuf& b : vkey_d) v.dev(b, kFreed);
-    v.fence(vkey_host_ev);
-    for (PinBuf& b : sign_h) v.pin(b, kFreed);
-    for (DevBuf& b : sign_d) v.dev(b, kFreed);
-    v.fence(sign_host_ev);
+    vkey_stage.visit(v);
+    sign_stage.visit(v);
     for (EcWork& w : ec) w.visit(v);
     rsa.visit(v);
     for (hipStream_t* s : {&s_rsa, &stream, &s_copy, &s_ed, &s_ec, &s_ed2, &s_idcopy}) v.stream(*s);  // s_ec2 is s_idcopy
@@ -1093,21 +1091,10 @@ struct cordahip_ctx {
   std::vector<std::pair<std::unique_ptr<uint64_t[]>, uint64_t>> txof_free;
   // the idle release (CORDAHIP_IDLE_RELEASE_MS): a thread that frees an idle
   // device's grow-only buffers (runtime.cpp trim_device)
-  // the signer's key registry (cordahip_signer_add_ed25519 / _remove): which of the
-  // key table's slots are live and each slot's reuse counter (empty until the first
-  // add); no key material. signer_mu is held for an add's or a remove's whole run.
-  std::mutex signer_mu;
-  std::vector<uint32_t> signer_gen;
-  std::vector<uint8_t> signer_live;
-  uint32_t signer_count = 0;
-  // the verification-key registry (cordahip_vkey_add_ed25519 / _add_ecdsa / _remove):
-  // which slots are live and each slot's reuse counter (empty until the first add), one
-  // pool for both families. vkey_mu is held for an add's or a remove's whole run. Ids
-  // are a namespace of their own.
-  std::mutex vkey_mu;
-  std::vector<uint32_t> vkey_gen;
-  std::vector<uint8_t> vkey_live;
-  uint32_t vkey_count = 0;
+  // the two key registries (key_slots.hpp): which slots are live and each slot's reuse
+  // counter; no key material. Their ids are namespaces of their own.
+  cordahip::rt::SignerSlots signers;  // cordahip_signer_add_ed25519 / _remove
+  cordahip::rt::VkeySlots vkeys;      // cordahip_vkey_add_ed25519 / _add_ecdsa / _remove
   // the notary commit logs (cordahip_commit_log_create / _destroy): id -> log; ids
   // count up and are never reused. logs_mu guards the map and the counter only.
   std::mutex logs_mu;

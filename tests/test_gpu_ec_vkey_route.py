@@ -713,7 +713,7 @@ def test_registry_changes_under_routing(oracle):
 
 # ---- 8. the lock order ---------------------------------------------------------------------------
 def test_trim_keyed_and_routed_calls_together(oracle):
-    """cordahip_trim (every buffer lock, vkey_host_mu last), cordahip_ecdsa_verify_keyed (vkey_host_mu
+    """cordahip_trim (every buffer lock, vkey_stage.mu last), cordahip_ecdsa_verify_keyed (vkey_stage.mu
     around vkey_mu), a routed ECDSA dense call (ec_mu around vkey_mu) and a routed Ed25519 dense call
     (ed_mu around vkey_mu) from four threads: one lock order, so all four finish, with the right
     statuses throughout and the exact final counts."""

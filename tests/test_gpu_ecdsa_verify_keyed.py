@@ -46,11 +46,11 @@ class HostBatch:
         self.st_buf = np.full(GUARD + n + GUARD, 0xA5, np.uint8)
         self.vd_buf = np.full(GUARD + self.words * 8 + GUARD, 0xA5, np.uint8)
 
-    def batch(self, soff=None, moff=None):
+    def batch(self, soff=None, moff=None, verdict=True):
         p = lambda a: a.ctypes.data  # noqa: E731
         return _lib.KeyedSigBatch(self.n, p(self.ids), p(self.sig), p(self.soff if soff is None else soff),
                                   p(self.msg), p(self.moff if moff is None else moff), p(self.st_buf) + GUARD,
-                                  p(self.vd_buf) + GUARD, self.flags, int(self.soff[self.n]), int(self.moff[self.n]))
+                                  p(self.vd_buf) + GUARD if verdict else None, self.flags, int(self.soff[self.n]), int(self.moff[self.n]))
 
     @property
     def st(self):
@@ -66,10 +66,13 @@ class HostBatch:
     def guards_intact(self):
         return all((b[:GUARD] == 0xA5).all() and (b[-GUARD:] == 0xA5).all() for b in (self.st_buf, self.vd_buf))
 
-    def run(self, engine, fn="cordahip_ecdsa_verify_keyed"):
-        rc = getattr(lib(), fn)(engine.ctx, ctypes.byref(self.batch()))
+    def run(self, engine, fn="cordahip_ecdsa_verify_keyed", verdict=True):
+        rc = getattr(lib(), fn)(engine.ctx, ctypes.byref(self.batch(verdict=verdict)))
         assert rc == 0, rc
         assert self.guards_intact()
+        if not verdict:  # a NULL verdict pointer: statuses only
+            assert (self.vd_buf == 0xA5).all()
+            return self.st.copy()
         bits = verdict_bits(self.verdict, self.words * 64)  # the verdict bit is status == OK, zero past n
         assert np.array_equal(bits[:self.n], (self.st == OK).astype(np.uint8)) and not bits[self.n:].any()
         return self.st.copy()
@@ -623,3 +626,40 @@ def test_three_device_replicas_and_chunks(oracle, monkeypatch):
                                           stream=torch.cuda.current_stream())
             torch.cuda.synchronize()
             assert np.array_equal(t_st.cpu().numpy(), got[:6]), d
+
+
+@pytest.fixture(scope="module")
+def three_chunks(engine, oracle, ec5):
+    """130 lanes for CORDAHIP_HOST_CHUNK=64, signed on the GPU and judged by the oracle once: chunk 0
+    all 32-byte messages (dense rows), chunk 1 mixed lengths with 0- and 33-byte messages (CSR: the
+    offset and length buffers are first needed in the middle of the call), chunk 2 a 2-lane tail."""
+    ids, seeds, pubs = ec5
+    lens = [32] * 64 + [(0, 33, 32, 1, 31, 64, 100)[i % 7] for i in range(64)] + [32, 32]
+    n = len(lens)
+    msgs = [hashlib.shake_256(b"ec-vkey-3chunk-%d" % i).digest(lens[i]) for i in range(n)]
+    sigs = [None] * n
+    for L in sorted(set(lens)):  # the signer takes dense rows: one call per length (an empty message: any DER)
+        sel = [i for i in range(n) if lens[i] == L]
+        rows = np.frombuffer(b"".join(msgs[i] for i in sel) if L else bytes(len(sel)), np.uint8).reshape(len(sel), L or 1)
+        _, out = gpu_sign(engine, [SCHEMES5[i % 5] for i in sel], [seeds[i % 5] for i in sel], rows)
+        for i, sg in zip(sel, out):
+            sigs[i] = sg
+    for i in range(0, n, 6):
+        sg = bytearray(sigs[i])
+        sg[-1 - i % 20] ^= 0x10
+        sigs[i] = bytes(sg)
+    sigs[129] = sigs[129] + bytes(80)  # longer than the 72-byte slot: the host's DER decision
+    want = oracle_batch(oracle, [SCHEMES5[i % 5] for i in range(n)], [pubs[i % 5] for i in range(n)], sigs, msgs)
+    assert {OK, BAD_SIG, EMPTY} <= set(want.tolist()) and (want[64:128] == OK).sum() > 32 and want[129] != OK
+    return [ids[i % 5] for i in range(n)], sigs, msgs, want
+
+
+@pytest.mark.parametrize("with_verdict", [True, False])
+def test_three_chunks_dense_csr_tail(engine, three_chunks, monkeypatch, with_verdict):
+    """The chunk loop's three shapes in one call, with and without verdict words; with them, run()
+    checks that the tail's word has no bit set past lane 129."""
+    monkeypatch.setenv("CORDAHIP_HOST_CHUNK", "64")
+    lane_ids, sigs, msgs, want = three_chunks
+    got = HostBatch(lane_ids, sigs, msgs).run(engine, verdict=with_verdict)
+    bad = np.nonzero(got != want)[0]
+    assert not len(bad), [(int(i), len(msgs[i]), int(got[i]), int(want[i])) for i in bad[:10]]

@@ -244,6 +244,39 @@ def test_small_chunks_two_tickets(engine, oracle, keys, monkeypatch):
             assert sig[i].tobytes() == want, (b, i, lens[i])
 
 
+@pytest.fixture(scope="module")
+def three_chunks(oracle, keys):
+    """130 lanes for CORDAHIP_HOST_CHUNK=64, signed by the C oracle once: chunk 0 all 32-byte
+    messages (dense rows), chunk 1 mixed lengths with 0- and 33-byte messages (CSR: the offset and
+    length buffers are first needed in the middle of the call), chunk 2 a 2-lane tail."""
+    lens = [32] * 64 + [(0, 33, 32, 1, 31, 64, 100)[i % 7] for i in range(64)] + [32, 32]
+    n = len(lens)
+    msgs = [hashlib.shake_256(b"sign-3chunk-%d" % i).digest(lens[i]) for i in range(n)]
+    ids = [keys[i % len(keys)][0] for i in range(n)]
+    want = [csign(oracle, keys[i % len(keys)][1], msgs[i])[1] if lens[i] else bytes(64) for i in range(n)]
+    return ids, msgs, lens, want
+
+
+@pytest.mark.parametrize("gated", [False, True])
+def test_three_chunks_dense_csr_tail(engine, three_chunks, monkeypatch, gated):
+    """The chunk loop's three shapes in one call, with a NULL gate and with gate bytes (a gated
+    lane in each chunk, the tail's last lane among them)."""
+    monkeypatch.setenv("CORDAHIP_HOST_CHUNK", "64")
+    ids, msgs, lens, want = three_chunks
+    n = len(lens)
+    gate = [int(i % 9 == 3) * (1 + i % 255) for i in range(n)] if gated else None
+    if gated:
+        gate[129] = 1
+        assert any(gate[:64]) and any(gate[64:128]) and gate[64] == 0  # lane 64 is empty and ungated
+    hb = HostBatch(ids, msgs, gate)
+    assert lib().cordahip_sign(engine.ctx, ctypes.byref(hb.batch())) == 0
+    assert hb.guards_intact()
+    skipped = [bool(gated and gate[i]) for i in range(n)]
+    assert [int(s) for s in hb.st] == [SKIPPED if skipped[i] else OK if lens[i] else EMPTY for i in range(n)]
+    bad = [i for i in range(n) if hb.sig[i].tobytes() != (bytes(64) if skipped[i] else want[i])]
+    assert not bad, bad[:10]
+
+
 def test_three_device_replicas(oracle, vectors, monkeypatch):
     """The shard split and the per-device key tables on a context of three Device objects
     (CORDAHIP_TEST_DEVICE_REPLICAS, read by cordahip_init): every replica holds the same

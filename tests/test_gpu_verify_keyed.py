@@ -61,11 +61,11 @@ class HostBatch:
         self.st_buf = np.full(GUARD + n + GUARD, 0xA5, np.uint8)
         self.vd_buf = np.full(GUARD + self.words * 8 + GUARD, 0xA5, np.uint8)
 
-    def batch(self, soff=None, moff=None, sig_bytes=None, msg_bytes=None):
+    def batch(self, soff=None, moff=None, sig_bytes=None, msg_bytes=None, verdict=True):
         p = lambda a: a.ctypes.data  # noqa: E731
         return _lib.KeyedSigBatch(self.n, p(self.ids), p(self.sig), p(self.soff if soff is None else soff),
                                   p(self.msg), p(self.moff if moff is None else moff), p(self.st_buf) + GUARD,
-                                  p(self.vd_buf) + GUARD, self.flags,
+                                  p(self.vd_buf) + GUARD if verdict else None, self.flags,
                                   int(self.soff[self.n]) if sig_bytes is None else sig_bytes,
                                   int(self.moff[self.n]) if msg_bytes is None else msg_bytes)
 
@@ -83,10 +83,13 @@ class HostBatch:
     def guards_intact(self):
         return all((b[:GUARD] == 0xA5).all() and (b[-GUARD:] == 0xA5).all() for b in (self.st_buf, self.vd_buf))
 
-    def run(self, engine):
-        rc = lib().cordahip_verify_keyed(engine.ctx, ctypes.byref(self.batch()))
+    def run(self, engine, verdict=True):
+        rc = lib().cordahip_verify_keyed(engine.ctx, ctypes.byref(self.batch(verdict=verdict)))
         assert rc == 0, rc
         assert self.guards_intact()
+        if not verdict:  # a NULL verdict pointer: statuses only
+            assert (self.vd_buf == 0xA5).all()
+            return self.st.copy()
         # the verdict bit is status == OK, the bits past n are zero
         bits = verdict_bits(self.verdict, self.words * 64)
         assert np.array_equal(bits[:self.n], (self.st == OK).astype(np.uint8)) and not bits[self.n:].any()
@@ -441,3 +444,38 @@ def test_three_device_replicas_and_chunks(oracle, monkeypatch):
                                             stream=torch.cuda.current_stream())
             torch.cuda.synchronize()
             assert np.array_equal(t_st.cpu().numpy(), got[:6]), d
+
+
+# ---- 9. three chunks of one call: dense, CSR, a two-lane tail ---------------------------------
+@pytest.fixture(scope="module")
+def three_chunks(oracle, five):
+    """130 lanes for CORDAHIP_HOST_CHUNK=64, signed and judged by the oracle once: chunk 0 all
+    32-byte messages (dense rows), chunk 1 mixed lengths with 0- and 33-byte messages (CSR: the
+    offset and length buffers are first needed in the middle of the call), chunk 2 a 2-lane tail."""
+    ids, seeds, pubs = five
+    lens = [32] * 64 + [(0, 33, 32, 1, 31, 64, 100)[i % 7] for i in range(64)] + [32, 32]
+    n = len(lens)
+    msgs = [hashlib.shake_256(b"vkey-3chunk-%d" % i).digest(lens[i]) for i in range(n)]
+    sigs = [bytearray(csign(oracle, seeds[i % 5], msgs[i])[1]) for i in range(n)]
+    for i in range(0, n, 6):
+        sigs[i][i % 64] ^= 0x04
+    sigs[70], sigs[129] = sigs[70][:63], sigs[129] + b"\0"  # not 64 bytes: the host's pre-status
+    sigs = [bytes(s) for s in sigs]
+    want = np.zeros(n, np.uint8)
+    for L in sorted(set(lens)):  # the oracle's batch takes dense rows: one call per length
+        sel = [i for i in range(n) if lens[i] == L and len(sigs[i]) == 64]
+        want[sel] = oracle_statuses(oracle, [pubs[i % 5] for i in sel], [sigs[i] for i in sel], [msgs[i] for i in sel])
+    want[[70, 129]] = MALFORMED_SIG  # EdDSAEngine: signature length (both messages are non-empty)
+    assert lens[70] and {OK, BAD_SIG, EMPTY} <= set(want.tolist()) and (want[64:128] == OK).sum() > 32
+    return [ids[i % 5] for i in range(n)], sigs, msgs, want
+
+
+@pytest.mark.parametrize("with_verdict", [True, False])
+def test_three_chunks_dense_csr_tail(engine, three_chunks, monkeypatch, with_verdict):
+    """The chunk loop's three shapes in one call, with and without verdict words; with them, run()
+    checks that the tail's word has no bit set past lane 129."""
+    monkeypatch.setenv("CORDAHIP_HOST_CHUNK", "64")
+    lane_ids, sigs, msgs, want = three_chunks
+    got = HostBatch(lane_ids, sigs, msgs).run(engine, verdict=with_verdict)
+    bad = np.nonzero(got != want)[0]
+    assert not len(bad), [(int(i), len(msgs[i]), int(got[i]), int(want[i])) for i in bad[:10]]

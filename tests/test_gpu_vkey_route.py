@@ -583,7 +583,7 @@ def test_stream_call_is_routed(oracle):
 
 # ---- 8. the lock order ---------------------------------------------------------------------------
 def test_trim_keyed_and_routed_calls_together(oracle):
-    """cordahip_trim (every buffer lock, vkey_host_mu last), cordahip_verify_keyed (vkey_host_mu
+    """cordahip_trim (every buffer lock, vkey_stage.mu last), cordahip_verify_keyed (vkey_stage.mu
     around vkey_mu) and a routed dense device call (ed_mu around vkey_mu) from three threads: one
     lock order, so all three finish, with the right statuses throughout."""
     import threading

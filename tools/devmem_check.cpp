@@ -179,7 +179,9 @@ int main() {
     VerifyKeys vk;
     visited(vk, sizeof(uint64_t) /* live */, "VerifyKeys");
     EcVerifyKeys ek;
-    visited(ek, 0, "EcVerifyKeys");
+    visited(ek, sizeof(EcVkeyState) /* state */, "EcVerifyKeys");
+    KeyedStage ks;
+    visited(ks, sizeof(std::mutex) /* mu */, "KeyedStage");
     visited(tw, 0, "TxWork");
     visited(ss, 0, "StreamStage");
     visited(ps, kPackPlain, "PackStage");
@@ -193,13 +195,13 @@ int main() {
   {
     // Device's plain members: ids, placement, pool, budget and workspace sizes, activity,
     // the mutexes and condition variable, turn counters, ring generations, set_busy,
-    // s_ec2 (an alias), the encoder's flags and counters; the signer's two mutexes and its
-    // key table, which has a visit of its own (f)
-    // and the verification keys' two mutexes and tables, visited with the signer's (f)
-    // and the registered ECDSA keys' tables and what the host knows of them (f)
+    // s_ec2 (an alias), the encoder's flags and counters; the signer's mutex, its chunk
+    // stage's and its key table, which has a visit of its own (f)
+    // and the verification keys' mutex, their chunk stage's and their tables, visited with the signer's (f)
+    // and the registered ECDSA keys' tables with what the host knows of them (f)
     // and the two routing switches (route_on, ec_route_on: each padded to 8 bytes)
     constexpr size_t kDeviceOwnPlain = 1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys) + 2 * sizeof(std::mutex) +
-                                       sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + sizeof(EcVkeyState) + 16;
+                                       sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + 16;
     const Count c = visited(*d, kDeviceOwnPlain + kTxSets * kTxSetPlain + kPackStages * kPackPlain, "Device");
     ndev = c.ndev, npin = c.npin, nev = c.nfence + c.nevent;
     CHECK(c.nstream == 7);
