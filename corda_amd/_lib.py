@@ -42,6 +42,8 @@ EXPORTS = [
     "cordahip_filtered_tx_build", "cordahip_filtered_tx_build_submit", "cordahip_filtered_tx_build_device",
     "cordahip_signer_add_ed25519", "cordahip_signer_remove", "cordahip_sign", "cordahip_sign_submit",
     "cordahip_ed25519_sign_keyed_device",
+    "cordahip_signer_add_ecdsa", "cordahip_ecdsa_sign", "cordahip_ecdsa_sign_submit",
+    "cordahip_ecdsa_sign_keyed_device",
     "cordahip_vkey_add_ed25519", "cordahip_vkey_remove", "cordahip_verify_keyed", "cordahip_verify_keyed_submit",
     "cordahip_ed25519_verify_keyed_device",
     "cordahip_vkey_add_ecdsa", "cordahip_ecdsa_verify_keyed", "cordahip_ecdsa_verify_keyed_submit",
@@ -71,6 +73,11 @@ TX_HASHES_NOT_IN_TREE, TX_TOK_SLOT_TOO_SMALL = 12, 13
 REQ_FULFILLED, REQ_MISSING, REQ_MISSING_ALLOWED, REQ_NOT_EVALUATED, REQ_MALFORMED = 0, 1, 2, 3, 4
 # signing lanes (cordahip_sign): besides OK and EMPTY; precedence SKIPPED, UNKNOWN_KEY, EMPTY
 SIGN_UNKNOWN_KEY, SIGN_SKIPPED = 14, 15
+# ECDSA signing lanes (cordahip_ecdsa_sign): every nonce candidate of the bounded loop was rejected;
+# after EMPTY in precedence. The 72-byte DER slot of a signature row.
+SIGN_FAILED = 16
+ECDSA_SIG_SLOT = 72
+SIGNER_NO_ID = 0xFFFFFFFF  # the id cordahip_signer_add_ecdsa reports for a d that is not a key
 SIGNER_MAX_KEYS = 4096  # live keys per context (a full table: CORDAHIP_ERR_OUT_OF_MEMORY)
 ERR_INVALID_ARG, ERR_OUT_OF_MEMORY = -1, -4
 # keyed verification lanes (cordahip_verify_keyed): the lane's id names no live key; first in precedence
@@ -187,6 +194,17 @@ class SignBatch(ctypes.Structure):
         ("msg", ctypes.c_void_p), ("msg_off", ctypes.c_void_p),
         ("gate", ctypes.c_void_p),
         ("sig", ctypes.c_void_p), ("status", ctypes.c_void_p),
+        ("msg_bytes", ctypes.c_uint64),
+    ]
+
+
+class EcdsaSignBatch(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("key_id", ctypes.c_void_p),
+        ("msg", ctypes.c_void_p), ("msg_off", ctypes.c_void_p),
+        ("gate", ctypes.c_void_p),
+        ("sig", ctypes.c_void_p), ("sig_len", ctypes.c_void_p), ("status", ctypes.c_void_p),
         ("msg_bytes", ctypes.c_uint64),
     ]
 
@@ -355,6 +373,10 @@ def lib() -> ctypes.CDLL:
         "cordahip_sign": (i32, [vp, ctypes.POINTER(SignBatch)]),
         "cordahip_sign_submit": (i32, [vp, ctypes.POINTER(SignBatch), ctypes.POINTER(u64)]),
         "cordahip_ed25519_sign_keyed_device": (i32, [vp, i32, vp, vp, u32, u64, vp, vp, vp, vp]),
+        "cordahip_signer_add_ecdsa": (i32, [vp, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint8), vp]),
+        "cordahip_ecdsa_sign": (i32, [vp, ctypes.POINTER(EcdsaSignBatch)]),
+        "cordahip_ecdsa_sign_submit": (i32, [vp, ctypes.POINTER(EcdsaSignBatch), ctypes.POINTER(u64)]),
+        "cordahip_ecdsa_sign_keyed_device": (i32, [vp, i32, vp, vp, u32, u64, vp, vp, vp, vp, vp]),
         "cordahip_vkey_add_ed25519": (i32, [vp, vp, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint8)]),
         "cordahip_vkey_remove": (i32, [vp, u32]),
         "cordahip_vkey_set_routing": (i32, [vp, u32]),

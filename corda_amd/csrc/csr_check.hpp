@@ -108,9 +108,10 @@ bool check_filtered_build_batch(Par&& par, const cordahip_filtered_build_batch* 
 }
 
 // a signing batch: msg_off[0..n] non-decreasing and within msg_bytes, and no
-// single message of 2^32 bytes or more (the kernel's message lengths are 32-bit)
-template <class Par>
-bool check_sign_batch(Par&& par, const cordahip_sign_batch* b) {
+// single message of 2^32 bytes or more (the kernel's message lengths are 32-bit).
+// B: cordahip_sign_batch or cordahip_ecdsa_sign_batch (the same message fields).
+template <class Par, class B>
+bool check_sign_batch(Par&& par, const B* b) {
   if (b->n == 0) return true;
   if (!b->msg_off || !csr_ok(par, b->msg_off, 0, b->n, b->msg_bytes)) return false;
   std::atomic<bool> ok{true};

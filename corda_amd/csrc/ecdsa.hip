@@ -26,6 +26,7 @@
 
 #include "der.hpp"
 #include "ecdsa_route.hpp"
+#include "ecdsa_sign_core.hpp"
 #include "ecdsa_vkey.hpp"
 #include "fp29.hpp"
 #include "fp29_asm.hpp"
@@ -1437,6 +1438,9 @@ hipError_t launch_ecdsa_verify(const uint8_t* scheme, const uint8_t* keys, const
 // K15, routing to K13: the partition by key bytes and the indexed instances of K13 and
 // of this unit's prep and ladder
 #include "ecdsa_route.hip"
+// K17, signing with registered keys: the kernels share this unit's device functions in the
+// same way
+#include "ecdsa_sign_keyed.hip"
 #define CH_SAME_N(i) (kEcVkeyNK1[i] == K1N::limb(i) && kEcVkeyNR1[i] == R1N::limb(i))
 static_assert(CH_SAME_N(0) && CH_SAME_N(1) && CH_SAME_N(2) && CH_SAME_N(3) && CH_SAME_N(4) && CH_SAME_N(5) &&
                   CH_SAME_N(6) && CH_SAME_N(7),

@@ -1,6 +1,6 @@
 // libcordahip.so's registered-key calls: the signer's and the verification keys'
 // registries (cordahip_signer_*, cordahip_vkey_*), the host calls that sign and verify
-// with them a chunk at a time (cordahip_sign, cordahip_verify_keyed,
+// with them a chunk at a time (cordahip_sign, cordahip_ecdsa_sign, cordahip_verify_keyed,
 // cordahip_ecdsa_verify_keyed) and their *_device forms. The shared runtime types are in
 // runtime.hpp; the routed enqueues of the generic paths (K14, K15) in runtime.cpp.
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 
 #include "api_support.hpp"
 #include "csr_check.hpp"
+#include "ecdsa_sign_core.hpp"
 #include "ecdsa_vkey.hpp"
 #include "ed25519_comb.hpp"
 #include "ed25519_vkey.hpp"
@@ -68,9 +69,23 @@ int clear_on_each_device(cordahip_ctx* ctx, std::mutex Device::*mu, Clear clear)
 // A key's record zeroed on one device (sign_mu held, device current): after every
 // signing kernel that may still read it; the stream is drained before return.
 hipError_t signer_zero_record(Device& d, uint32_t slot) {
-  if (!d.keys.tab.p) return hipSuccess;
-  hipError_t e = d.keys.ev.sync();
-  e = e ? e : hipMemsetAsync(d.keys.tab.as<uint32_t>() + (size_t)slot * kSignRecWords, 0, kSignRecWords * 4, d.stream);
+  if (!d.keys.tab.p && !d.ec_keys.tab.p) return hipSuccess;
+  hipError_t e = hipSuccess;
+  if (d.keys.tab.p) {
+    e = d.keys.ev.sync();
+    e = e ? e
+          : hipMemsetAsync(d.keys.tab.as<uint32_t>() + (size_t)slot * kSignRecWords, 0, kSignRecWords * 4, d.stream);
+  }
+  if (d.ec_keys.tab.p) {  // the slot's record of the other family (K17): one pool, one remove
+    EcSignKeys& k = d.ec_keys;
+    hipError_t x = k.ev.sync();
+    x = x ? x
+          : hipMemsetAsync(k.tab.as<uint32_t>() + kEcSignRecBase + (size_t)slot * kEcSignRecWords, 0,
+                           kEcSignRecWords * 4, d.stream);
+    e = e ? e : x;
+    if (k.scheme[slot]) k.live[k.scheme[slot] - 2]--;
+    k.scheme[slot] = 0;
+  }
   const hipError_t f = hipStreamSynchronize(d.stream);
   return e ? e : f;
 }
@@ -130,6 +145,89 @@ int signer_remove_impl(cordahip_ctx* ctx, uint32_t key_id) {
   const int rc = clear_on_each_device(ctx, &Device::sign_mu, [&](Device& d) { return signer_zero_record(d, slot); });
   if (tracing()) fprintf(stderr, "[cordahip] signer: key id %u removed (%u live)\n", key_id, reg.count);
   return rc;
+}
+
+// ---- ECDSA signing with registered keys (K17, ecdsa_sign_keyed.hip) -------------
+// The key's record written in key_id's slot on one device (sign_mu held): the device's
+// first ECDSA signer key allocates the table (records and scratch zeroed), its first
+// key of a curve builds that curve's comb table. *taken: whether the device took d for
+// a key (0 < d < n); pub: its Q = [d]G as X || Y. d crosses in the device's page-locked
+// stage, wiped here whatever happens; the kernel zeroes its device scratch.
+int ec_signer_add_on(Device& d, uint32_t scheme, const uint8_t key[32], uint32_t key_id, bool* taken,
+                     uint8_t pub[64]) {
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  EcSignKeys& k = d.ec_keys;
+  if (!k.tab.p) {
+    if (k.tab.ensure(ecdsa_signtab_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+    k.comb[0] = k.comb[1] = k.live[0] = k.live[1] = 0;
+    std::memset(k.scheme, 0, sizeof k.scheme);
+    if (hipMemsetAsync(k.tab.as<uint32_t>() + kEcSignRecBase, 0, (size_t)(kEcSignAllWords - kEcSignRecBase) * 4,
+                       d.stream) != hipSuccess)
+      return CORDAHIP_ERR_HIP;
+  }
+  uint32_t* tab = k.tab.as<uint32_t>();
+  const bool build_comb = !k.comb[scheme - 2];  // marked built only once the stream has drained below
+  if (build_comb && launch_ecdsa_sign_comb(tab, scheme, d.stream) != hipSuccess) return CORDAHIP_ERR_HIP;
+  if (k.stage.ensure(128) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  uint8_t* stage = k.stage.as<uint8_t>();
+  std::memcpy(stage, key, 32);
+  std::memset(stage + 32, 0, 96);
+  hipError_t e = k.ev.sync();  // a removed key's slot: no kernel still reads its record
+  e = e ? e : hipMemcpyAsync(tab + kEcSignKeyWord, stage, 32, hipMemcpyHostToDevice, d.stream);
+  e = e ? e : launch_ecdsa_signer_add(tab, scheme, key_id, d.stream);
+  e = e ? e : hipMemcpyAsync(stage + 32, tab + kEcSignOutWord, 80, hipMemcpyDeviceToHost, d.stream);
+  const hipError_t f = hipStreamSynchronize(d.stream);
+  secure_wipe(stage, 32);
+  if (e == hipSuccess && f == hipSuccess) {
+    uint32_t flag;
+    std::memcpy(&flag, stage + 32, 4);
+    *taken = flag == 1u;
+    std::memcpy(pub, stage + 32 + 16, 64);
+    if (build_comb) k.comb[scheme - 2] = 1;
+    if (*taken) {
+      const uint32_t slot = key_id & (kSignKeySlots - 1);
+      k.scheme[slot] = (uint8_t)scheme;
+      k.live[scheme - 2]++;
+    }
+  }
+  return hip_err(e ? e : f);
+}
+
+int ec_signer_add_impl(cordahip_ctx* ctx, uint32_t scheme, const uint8_t key[32], uint32_t* key_id,
+                       uint8_t* key_status, uint8_t pub[65]) {
+  auto& reg = ctx->signers;
+  std::lock_guard<std::mutex> g(reg.mu);
+  uint32_t slot, id;
+  if (!reg.acquire(slot, id)) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  bool first = false, cur = false;
+  uint8_t pfirst[64], pcur[64];
+  const int rc = on_each_device(
+      ctx, &Device::sign_mu,
+      [&](Device& d, size_t i, bool& more) {
+        const int r = ec_signer_add_on(d, scheme, key, id, i ? &cur : &first, i ? pcur : pfirst);
+        if (r == CORDAHIP_SUCCESS && !first) more = false;  // not a key: no device wrote a record
+        return r;
+      },
+      [&] { return cur == first && std::memcmp(pfirst, pcur, 64) == 0; },
+      [&](Device& d) {  // no device keeps a record of a key the caller never got
+        if (!d.ec_keys.tab.p) return;
+        (void)signer_zero_record(d, slot);
+        (void)hipMemsetAsync(d.ec_keys.tab.as<uint32_t>() + kEcSignKeyWord, 0, 32, d.stream);
+        (void)hipStreamSynchronize(d.stream);
+      });
+  if (rc != CORDAHIP_SUCCESS) return rc;
+  if (!first) {
+    *key_id = 0xFFFFFFFFu;
+    *key_status = CORDAHIP_STATUS_BAD_KEY;
+    return CORDAHIP_SUCCESS;
+  }
+  reg.commit(slot);
+  *key_id = id;
+  *key_status = CORDAHIP_STATUS_OK;
+  pub[0] = 4;
+  std::memcpy(pub + 1, pfirst, 64);
+  if (tracing()) fprintf(stderr, "[cordahip] signer: ECDSA key id %u (scheme %u) added (%u live)\n", id, scheme, reg.count);
+  return CORDAHIP_SUCCESS;
 }
 
 // One chunk of a registered-key host call: lanes [a, a + m) of the batch, their messages
@@ -240,6 +338,66 @@ int sign_impl(cordahip_ctx* ctx, const cordahip_sign_batch* b) {
   if (b->msg_off[0] != b->msg_off[n] && !b->msg) return CORDAHIP_ERR_INVALID_ARG;
   return for_shards(ctx->devs, n, 64, [&](Device& d, uint64_t lo, uint64_t hi) {
     return keyed_chunks(ctx, d, d.sign_stage, b->msg_off, b->status, lo, hi, 1, "sign", SignCall{d, b, d.sign_stage});
+  });
+}
+
+// The ECDSA keyed signer on stream s (sign_mu held, device current): behind the ECDSA
+// table's previous user, followed by its fence. A device without that table passes
+// none: every ungated lane is then UNKNOWN_KEY.
+hipError_t ec_sign_enqueue(Device& d, const uint32_t* key_id, const uint8_t* msgs, const uint64_t* moff,
+                           const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* gate, uint8_t* sigs,
+                           uint8_t* sig_len, uint8_t* status, hipStream_t s) {
+  const EcSignKeys& k = d.ec_keys;
+  const bool have = k.tab.p != nullptr;
+  hipError_t e = d.ec_keys.ev.wait(s);
+  e = e ? e
+        : launch_ecdsa_sign_keyed(key_id, msgs, moff, mlen, msg_len, n, gate, k.tab.as<uint32_t>(),
+                                  have && k.live[0] > 0, have && k.live[1] > 0, sigs, sig_len, status, s);
+  return e ? e : d.ec_keys.ev.record(s);
+}
+
+// cordahip_ecdsa_sign's part of a chunk (keyed_chunks): the gate bytes in, K17, the
+// 72-byte DER slots and their lengths out.
+struct EcSignCall {
+  Device& d;
+  const cordahip_ecdsa_sign_batch* b;
+  KeyedStage& st;
+  bool ensure(const KeyedChunk& c) {
+    return st.gate.ensure(c.m) || st.sig_rows.ensure(c.m * kEcSignSigBytes) || st.sig_len.ensure(c.m);
+  }
+  void pack(const KeyedChunk& c, uint64_t x, uint64_t y) {
+    sign_pack_rows(b, c.a, x, y, c.lay, c.poff, st.ids.h.as<uint32_t>(), st.gate.h.as<uint8_t>(),
+                   st.msgs.h.as<uint8_t>(), st.msg_off.h.as<uint64_t>(), st.msg_len.h.as<uint32_t>());
+  }
+  hipError_t enqueue(const KeyedChunk& c) {
+    if (b->gate)
+      if (const hipError_t e = st.gate.to_device(c.m, c.s)) return e;
+    const bool dense = c.lay.dense;
+    std::lock_guard<std::mutex> gs(d.sign_mu);
+    return ec_sign_enqueue(d, st.ids.d.as<uint32_t>(), st.msgs.d.as<uint8_t>(),
+                           dense ? nullptr : st.msg_off.d.as<uint64_t>(), dense ? nullptr : st.msg_len.d.as<uint32_t>(),
+                           32, c.m, b->gate ? st.gate.d.as<uint8_t>() : nullptr, st.sig_rows.d.as<uint8_t>(),
+                           st.sig_len.d.as<uint8_t>(), st.status.d.as<uint8_t>(), c.s);
+  }
+  hipError_t fetch(const KeyedChunk& c) {
+    const hipError_t e = st.sig_rows.to_host(c.m * kEcSignSigBytes, c.s);
+    return e ? e : st.sig_len.to_host(c.m, c.s);
+  }
+  void deliver(const KeyedChunk& c) {
+    std::memcpy(b->sig + c.a * kEcSignSigBytes, st.sig_rows.h.p, c.m * kEcSignSigBytes);
+    std::memcpy(b->sig_len + c.a, st.sig_len.h.p, c.m);
+  }
+};
+
+int ec_sign_impl(cordahip_ctx* ctx, const cordahip_ecdsa_sign_batch* b) {
+  const uint64_t n = b->n;
+  if (n == 0) return CORDAHIP_SUCCESS;
+  if (!b->key_id || !b->msg_off || !b->sig || !b->sig_len || !b->status) return CORDAHIP_ERR_INVALID_ARG;
+  if (!check_sign_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
+  if (b->msg_off[0] != b->msg_off[n] && !b->msg) return CORDAHIP_ERR_INVALID_ARG;
+  return for_shards(ctx->devs, n, 64, [&](Device& d, uint64_t lo, uint64_t hi) {
+    return keyed_chunks(ctx, d, d.sign_stage, b->msg_off, b->status, lo, hi, 1, "ECDSA sign",
+                        EcSignCall{d, b, d.sign_stage});
   });
 }
 
@@ -537,6 +695,41 @@ int cordahip_ed25519_sign_keyed_device(cordahip_ctx* ctx, int device, const void
       return sign_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_msgs), nullptr,
                           nullptr, msg_len, n, static_cast<const uint8_t*>(d_gate), static_cast<uint8_t*>(d_sigs),
                           static_cast<uint8_t*>(d_status), s);
+    });
+  });
+}
+
+int cordahip_signer_add_ecdsa(cordahip_ctx* ctx, uint32_t scheme, const uint8_t d[32], uint32_t* key_id,
+                              uint8_t* key_status, uint8_t pub[65]) {
+  if (!ctx || !d || !key_id || !key_status || !pub) return CORDAHIP_ERR_INVALID_ARG;
+  if (scheme != CORDAHIP_SCHEME_ECDSA_SECP256K1_SHA256 && scheme != CORDAHIP_SCHEME_ECDSA_SECP256R1_SHA256)
+    return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return ec_signer_add_impl(ctx, scheme, d, key_id, key_status, pub); });
+}
+
+int cordahip_ecdsa_sign(cordahip_ctx* ctx, const cordahip_ecdsa_sign_batch* batch) {
+  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return ec_sign_impl(ctx, batch); });
+}
+
+int cordahip_ecdsa_sign_submit(cordahip_ctx* ctx, const cordahip_ecdsa_sign_batch* batch, uint64_t* ticket) {
+  return submit(ctx, ticket, ec_sign_impl, batch);
+}
+
+int cordahip_ecdsa_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
+                                     uint32_t msg_len, uint64_t n, const void* d_gate, void* d_sigs,
+                                     void* d_sig_len, void* d_status, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || (n && (!d_key_id || !d_sigs || !d_sig_len || !d_status || (msg_len && !d_msgs))))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_sigs) & 3) || (reinterpret_cast<uintptr_t>(d_key_id) & 3))
+    return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    std::lock_guard<std::mutex> g(d->sign_mu);
+    return device_call(*d, hip_stream, [&](hipStream_t s) {
+      return ec_sign_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_msgs), nullptr,
+                             nullptr, msg_len, n, static_cast<const uint8_t*>(d_gate), static_cast<uint8_t*>(d_sigs),
+                             static_cast<uint8_t*>(d_sig_len), static_cast<uint8_t*>(d_status), s);
     });
   });
 }

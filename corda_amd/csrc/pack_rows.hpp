@@ -193,8 +193,9 @@ inline void pack_msg(const uint8_t* msg, uint64_t o, uint64_t len, uint64_t i, c
   }
 }
 // rows [x, y) of the chunk at lane a: key ids, gate bytes (b->gate != NULL), messages, and
-// -- not dense -- offsets and lengths
-inline void sign_pack_rows(const cordahip_sign_batch* b, uint64_t a, uint64_t x, uint64_t y, const SignLayout& l,
+// -- not dense -- offsets and lengths. B: cordahip_sign_batch or cordahip_ecdsa_sign_batch.
+template <class B>
+inline void sign_pack_rows(const B* b, uint64_t a, uint64_t x, uint64_t y, const SignLayout& l,
                            const uint64_t* poff, uint32_t* hid, uint8_t* hgate, uint8_t* hm, uint64_t* ho,
                            uint32_t* hl) {
   for (uint64_t i = x; i < y; i++) {

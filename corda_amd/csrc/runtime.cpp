@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "ecdsa_sign_core.hpp"
 #include "runtime.hpp"
 
 using namespace cordahip;
@@ -546,9 +547,18 @@ void signer_wipe(cordahip_ctx* ctx) {
   for (auto& dp : ctx->devs) {
     Device& d = *dp;
     std::lock_guard<std::mutex> g(d.sign_mu);
-    if (!d.keys.tab.p || hipSetDevice(d.id) != hipSuccess) continue;
-    (void)d.keys.ev.sync();
-    (void)hipMemsetAsync(d.keys.tab.p, 0, d.keys.tab.cap, d.stream);
+    if ((!d.keys.tab.p && !d.ec_keys.tab.p) || hipSetDevice(d.id) != hipSuccess) continue;
+    if (d.keys.tab.p) {
+      (void)d.keys.ev.sync();
+      (void)hipMemsetAsync(d.keys.tab.p, 0, d.keys.tab.cap, d.stream);
+    }
+    if (d.ec_keys.tab.p) {  // the ECDSA records (K17); the comb tables behind them are public
+      (void)d.ec_keys.ev.sync();
+      (void)hipMemsetAsync(d.ec_keys.tab.as<uint32_t>() + kEcSignRecBase, 0,
+                           (size_t)(kEcSignAllWords - kEcSignRecBase) * 4, d.stream);
+      std::memset(d.ec_keys.live, 0, sizeof d.ec_keys.live);
+      std::memset(d.ec_keys.scheme, 0, sizeof d.ec_keys.scheme);
+    }
     (void)hipStreamSynchronize(d.stream);
   }
 }

@@ -71,6 +71,19 @@ hipError_t launch_ed25519_sign_keyed(const uint32_t* key_id, const uint8_t* msgs
                                      const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* gate,
                                      const uint32_t* keytab, const uint32_t* comb, uint8_t* sigs, uint8_t* status,
                                      hipStream_t s);
+// ecdsa_sign_keyed.hip (K17, in ecdsa.hip's unit): a curve's comb table [d 16^j]G built
+// in the ECDSA signer's table, a key added (d is in the table's scratch words, the
+// answer and Q = [d]G come back there: ecdsa_sign_core.hpp kEcSignKeyWord /
+// kEcSignOutWord) and the keyed signer (messages and gate as for
+// launch_ed25519_sign_keyed; 72-byte DER slots with lengths out; live_k1 / live_r1: the
+// curves that have a live signer key on the device)
+size_t ecdsa_signtab_bytes();
+hipError_t launch_ecdsa_sign_comb(uint32_t* tab, uint32_t scheme, hipStream_t s);
+hipError_t launch_ecdsa_signer_add(uint32_t* tab, uint32_t scheme, uint32_t key_id, hipStream_t s);
+hipError_t launch_ecdsa_sign_keyed(const uint32_t* key_id, const uint8_t* msgs, const uint64_t* moff,
+                                   const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* gate,
+                                   const uint32_t* tab, bool live_k1, bool live_r1, uint8_t* sigs, uint8_t* sig_len,
+                                   uint8_t* status, hipStream_t s);
 // ed25519_vkey.hip (K12): a verification key's record and window table built in the
 // device's key table (the 32 key bytes are in the table's scratch words, the decode
 // verdict comes back there: ed25519_vkey.hpp kVkeyKeyWord / kVkeyOkWord) and the keyed
@@ -513,6 +526,18 @@ struct KeyTable {
 // it. stage: 64 bytes, the seed out and the public key back (wiped before add returns).
 struct SignKeys : KeyTable {};
 
+// The ECDSA signer's (ecdsa_sign_core.hpp: the two curves' comb tables, 4,096 records of
+// 128 bytes and the add kernel's scratch): private keys, zeroed by cordahip_shutdown like
+// SignKeys. stage: 128 bytes, d out and the answer with Q back (d wiped before add
+// returns). comb[c]: the comb table of curve c (0: secp256k1, 1: P-256) has been built;
+// live[c]: that curve's live keys on this device; scheme[slot]: the curve of the slot's
+// live record (0: none) -- all under Device::sign_mu.
+struct EcSignKeys : KeyTable {
+  uint32_t comb[2] = {0, 0};
+  uint32_t live[2] = {0, 0};
+  uint8_t scheme[kSignKeySlots] = {};
+};
+
 // The Ed25519 verification keys' (ed25519_vkey.hpp: 64 window tables of 512 KiB and the
 // base point's, their records and the build kernel's scratch). stage: 64 bytes, the key
 // bytes out and the decode verdict back. live: the slots whose record is live on this
@@ -725,9 +750,13 @@ struct Device {
   // keys.ev -- and add / remove hold it for their whole run; remove waits for keys.ev
   // first, so no kernel still reads the record it zeroes.
   SignKeys keys;
+  // ECDSA signing (K17): the records of the same registry's ECDSA keys and the curves'
+  // comb tables, an allocation of their own under the same sign_mu, with a fence of
+  // their own (ec_keys.ev) that add, remove and every signing call use as keys.ev is used.
+  EcSignKeys ec_keys;
   std::mutex sign_mu;
   uint32_t* comb() const { return reinterpret_cast<uint32_t*>(static_cast<char*>(btab.p) + ed25519_btable_bytes()); }
-  // cordahip_sign's chunk stage (KeyedStage)
+  // the chunk stage of cordahip_sign and cordahip_ecdsa_sign (KeyedStage)
   KeyedStage sign_stage;
 
   // Ed25519 verification against registered keys (K12). vkeys: the key tables
@@ -765,7 +794,7 @@ struct Device {
   // the chunk stage of cordahip_verify_keyed and cordahip_ecdsa_verify_keyed (KeyedStage)
   KeyedStage vkey_stage;
 
-  // everything but `keys`, `vkeys` and `ec_vkeys`, which the idle release is never offered (visit_keys)
+  // everything but `keys`, `ec_keys`, `vkeys` and `ec_vkeys`, which the idle release is never offered (visit_keys)
   template <class V>
   void visit(V& v) {
     for (DevBuf* b : {&btab, &gtab_k1, &gtab_r1}) v.dev(*b, kKept);
@@ -804,6 +833,7 @@ struct Device {
   template <class V>
   void visit_keys(V& v) {
     keys.visit(v);
+    ec_keys.visit(v);
     vkeys.visit(v);
     ec_vkeys.visit(v);
   }

@@ -26,6 +26,7 @@ class Engine:
         l = lib()
         self._ctx = ctypes.c_void_p()
         check(l.cordahip_init(device_mask, ctypes.byref(self._ctx)), "cordahip_init")
+        self._signer_family = {}  # signer ids this engine registered: "ed25519", 2 or 3 (signer_family)
 
     def close(self):
         if self._ctx:
@@ -117,12 +118,14 @@ class Engine:
         pub = ctypes.create_string_buffer(32)
         check(lib().cordahip_signer_add_ed25519(self._ctx, bytes(seed), ctypes.byref(kid), pub),
               "cordahip_signer_add_ed25519")
+        self._signer_family[kid.value] = "ed25519"
         return kid.value, pub.raw
 
     def signer_remove(self, key_id: int):
         """cordahip_signer_remove: waits for the signing calls in flight, zeroes the key's record on
         every device; the id answers SIGN_UNKNOWN_KEY from then on."""
         check(lib().cordahip_signer_remove(self._ctx, key_id), "cordahip_signer_remove")
+        self._signer_family.pop(int(key_id), None)
 
     def sign_batch(self, key_ids: Sequence[int], msgs: Sequence[bytes], gate=None, async_: bool = False):
         """cordahip_sign / cordahip_sign_submit: lane i signs msgs[i] with key key_ids[i] unless gate[i]
@@ -156,6 +159,64 @@ class Engine:
             self._ctx, device, key_ids.data_ptr(), msgs.data_ptr() if msgs.shape[1] else None, msgs.shape[1], n,
             gate.data_ptr() if gate is not None else None, sigs.data_ptr(), status.data_ptr(), s),
             "cordahip_ed25519_sign_keyed_device")
+
+    # ---- ECDSA signing with registered keys (RFC 6979 nonces) ------------------------
+    def signer_add_ecdsa(self, scheme: int, d: bytes):
+        """cordahip_signer_add_ecdsa: the private scalar d (32 big-endian bytes) of scheme 2
+        (secp256k1) or 3 (P-256) registered on every device of the context. Returns (key_id,
+        key_status, pub): pub is Q = [d]G as 65 SEC1 bytes; (SIGNER_NO_ID, BAD_KEY, None) for d = 0 or
+        d >= n (no slot taken). Ids share the Ed25519 signer's pool; signer_remove serves both."""
+        assert len(d) == 32
+        kid, st = ctypes.c_uint32(), ctypes.c_uint8()
+        pub = ctypes.create_string_buffer(65)
+        check(lib().cordahip_signer_add_ecdsa(self._ctx, scheme, bytes(d), ctypes.byref(kid), ctypes.byref(st), pub),
+              "cordahip_signer_add_ecdsa")
+        if st.value != 0:
+            return kid.value, st.value, None
+        self._signer_family[kid.value] = int(scheme)
+        return kid.value, st.value, pub.raw
+
+    def signer_family(self, key_id: int):
+        """The family of a signer id this engine registered and has not removed: "ed25519", 2
+        (ECDSA secp256k1) or 3 (ECDSA P-256); None for any other id."""
+        return self._signer_family.get(int(key_id))
+
+    def ecdsa_sign_batch(self, key_ids: Sequence[int], msgs: Sequence[bytes], gate=None, async_: bool = False):
+        """cordahip_ecdsa_sign / cordahip_ecdsa_sign_submit: lane i signs msgs[i] with the ECDSA key
+        key_ids[i] unless gate[i] is nonzero. Returns (sigs[n, 72], sig_len[n], status[n]) -- DER in
+        zero-padded 72-byte slots, zero rows and length 0 where status is not OK -- or, async_, a
+        Ticket whose wait() returns them."""
+        n = len(msgs)
+        assert len(key_ids) == n and (gate is None or len(gate) == n)
+        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
+        mb, mo = self._csr(list(msgs))
+        g = None if gate is None else np.ascontiguousarray(np.asarray(list(gate) or [0], dtype=np.uint8))
+        sig = np.zeros((max(n, 1), _lib.ECDSA_SIG_SLOT), dtype=np.uint8)
+        sl = np.zeros(max(n, 1), dtype=np.uint8)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        b = _lib.EcdsaSignBatch(n, _ptr(ids), _ptr(mb), _ptr(mo), _ptr(g) if g is not None else None, _ptr(sig),
+                                _ptr(sl), _ptr(st), mb.size if n and mo[n] else 0)
+        keep = (ids, mb, mo, g, sig, sl, st, b)
+        res = lambda: (sig[:n], sl[:n], st[:n])  # noqa: E731
+        if async_:
+            t = ctypes.c_uint64()
+            check(lib().cordahip_ecdsa_sign_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)),
+                  "cordahip_ecdsa_sign_submit")
+            return Ticket(self, t.value, res, keep)
+        check(lib().cordahip_ecdsa_sign(self._ctx, ctypes.byref(b)), "cordahip_ecdsa_sign")
+        return res()
+
+    def ecdsa_sign_keyed_device(self, key_ids, msgs, sigs, sig_len, status, gate=None, device: int = 0,
+                                stream=None):
+        """cordahip_ecdsa_sign_keyed_device over device tensors: key_ids int32 [n], msgs uint8 [n, L],
+        gate uint8 [n] or None (typically the tx_status an earlier call on `stream` wrote); outputs
+        sigs uint8 [n, 72], sig_len uint8 [n] and status uint8 [n]."""
+        n = key_ids.shape[0]
+        s = stream.cuda_stream if stream is not None else 0
+        check(lib().cordahip_ecdsa_sign_keyed_device(
+            self._ctx, device, key_ids.data_ptr(), msgs.data_ptr() if msgs.shape[1] else None, msgs.shape[1], n,
+            gate.data_ptr() if gate is not None else None, sigs.data_ptr(), sig_len.data_ptr(), status.data_ptr(), s),
+            "cordahip_ecdsa_sign_keyed_device")
 
     # ---- notary commit log (validateTimeWindow + commitInputStates per transaction) ----
     def commit_log_create(self, capacity_log2: int, device: int = 0, salt: Optional[bytes] = None) -> int:

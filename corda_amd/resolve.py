@@ -237,22 +237,37 @@ def build_filtered_transactions(engine, wtxs, filtering: Callable[[bytes], bool]
     return out
 
 
+def _sign_with(engine, key_id: int, msgs, gate):
+    """One signing call over msgs with the registered key `key_id`, gated: Engine.sign_batch for an
+    Ed25519 signer id, Engine.ecdsa_sign_batch for an ECDSA one (Engine.signer_family). Returns
+    (sigs, status): sigs[t] the signature bytes -- 64 bytes R || S, or the DER bytes of an ECDSA
+    signature -- for a lane whose status is OK."""
+    family = getattr(engine, "signer_family", lambda k: None)(key_id)
+    if family in (2, 3):
+        rows, lens, sst = engine.ecdsa_sign_batch([key_id] * len(msgs), msgs, gate=gate)
+        return [bytes(rows[t][:int(lens[t])]) for t in range(len(msgs))], sst
+    rows, sst = engine.sign_batch([key_id] * len(msgs), msgs, gate=gate)
+    return [bytes(r) for r in rows], sst
+
+
 def verify_and_sign_filtered_transactions(engine, ftxs, key_id: int):
     """What an oracle or a non-validating notary does with a batch of tear-offs
     (NodeInterestRates.sign, NodeInterestRates.kt:149-180: ftx.verify(), then
     keyManagementService.sign(ftx.rootHash.bytes, signingKey); NotaryFlow.Service,
     NotaryFlow.kt:114-116): Engine.filtered_tx_verify over ftxs (the tuples it takes),
-    then one Engine.sign_batch over the root hashes with the registered key `key_id`,
-    gated on the verification statuses -- a tear-off that did not verify is not signed.
+    then one signing call over the root hashes with the registered key `key_id` (Ed25519:
+    Engine.sign_batch; an ECDSA signer id: Engine.ecdsa_sign_batch), gated on the
+    verification statuses -- a tear-off that did not verify is not signed.
 
     Returns (tx_status, sigs): tx_status[t] as filtered_tx_verify gives it, sigs[t] the
-    64-byte signature over ftxs[t]'s root, or None where tx_status[t] != OK. An id that
+    signature over ftxs[t]'s root (64 bytes for an Ed25519 key, DER for an ECDSA key), or
+    None where tx_status[t] != OK. An id that
     names no live key raises NoSuchElementException, as the KMS's key lookup does
     (PersistentKeyManagementService.kt:80-89)."""
     if not ftxs:
         return [], []
     status = engine.filtered_tx_verify(ftxs)
-    sigs, sst = engine.sign_batch([key_id] * len(ftxs), [bytes(f[2]) for f in ftxs], gate=status)
+    sigs, sst = _sign_with(engine, key_id, [bytes(f[2]) for f in ftxs], status)
     out = []
     for t in range(len(ftxs)):
         if int(sst[t]) == _SIGN_UNKNOWN_KEY:
@@ -325,13 +340,14 @@ def notarise_filtered_transactions(engine, log_id: int, ftxs, inputs, time_windo
     """The batch form of NotaryFlow.Service.call (NotaryFlow.kt:98-104) for a non-validating notary:
     Engine.filtered_tx_verify over the tear-offs (ftx.verify()), Engine.commit_inputs gated on its
     statuses (validateTimeWindow, commitInputStates, in batch order against the commit log `log_id`),
-    Engine.sign_batch over the root hashes gated on the commit statuses (service.sign(txId.bytes)).
+    Engine.sign_batch (Engine.ecdsa_sign_batch for an ECDSA signer id) over the root hashes gated on
+    the commit statuses (service.sign(txId.bytes)).
 
     ftxs[t]: the tuple filtered_tx_verify takes, its root the transaction id; inputs[t]: the
     tear-off's input StateRefs [(txhash, index)]; time_windows[t]: None or (from_ns or None, until_ns
     or None); callers[t]: the requesting party's id; now / tolerance in ns.
 
-    Returns (answers, committed_rows). answers[t] is the 64-byte signature, or the NotaryError the
+    Returns (answers, committed_rows). answers[t] is the signature (64 bytes; DER for an ECDSA key), or the NotaryError the
     reference sends: TransactionInvalid for a tear-off that does not verify, TimeWindowInvalid,
     Conflict with its state history. committed_rows lists ((txhash, index), (txid, input_index,
     caller)) for every input state this call consumed -- what the caller persists BEFORE it releases
@@ -344,7 +360,7 @@ def notarise_filtered_transactions(engine, log_id: int, ftxs, inputs, time_windo
     verified = engine.filtered_tx_verify(ftxs)
     txs = [(ids[t], callers[t], list(inputs[t]), time_windows[t]) for t in range(n)]
     status, committed, ref_state, ref_by = engine.commit_inputs(log_id, txs, now, tolerance, gate=verified)
-    sigs, sst = engine.sign_batch([key_id] * n, ids, gate=status)
+    sigs, sst = _sign_with(engine, key_id, ids, status)
     answers, rows = [], []
     for t in range(n):
         st = int(status[t])

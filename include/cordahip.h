@@ -272,8 +272,9 @@ int cordahip_ed25519_sign_device(cordahip_ctx* ctx, int device, const void* d_se
  * (keyManagementService.sign(ftx.rootHash.bytes, key), NodeInterestRates.kt:149-180)
  * and ServiceHub.kt:138,179 reach it: a handful of long-lived keys, many 32-byte
  * ids. Ed25519 signing is deterministic (RFC 8032; i2p EdDSAEngine), so every
- * signature is bit-identical to the JVM's. ECDSA and RSA signing and
- * CompositeSignature assembly are not offered.
+ * signature is bit-identical to the JVM's. ECDSA signing with registered keys is
+ * the section after this one; RSA signing and CompositeSignature assembly are not
+ * offered.
  *
  * Key registry. cordahip_signer_add_ed25519 expands the 32-byte seed on every
  * device of the context (h = SHA-512(seed), a = clamp(h[0:32]) mod L, prefix =
@@ -340,6 +341,85 @@ int cordahip_sign_submit(cordahip_ctx* ctx, const cordahip_sign_batch* batch, ui
 int cordahip_ed25519_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
                                        uint32_t msg_len, uint64_t n, const void* d_gate, void* d_sigs,
                                        void* d_status, void* hip_stream);
+
+/* ---- ECDSA batch signing with registered keys (RFC 6979 nonces) ----------------- *
+ * Replaces, per lane, Crypto.doSign(ECDSA_SECP256K1_SHA256 / ECDSA_SECP256R1_SHA256,
+ * key, clearData) (Crypto.kt:394-401 -> JCA "SHA256withECDSA") for a notary, oracle or
+ * issuer whose identity key is an ECDSA key. BouncyCastle's default signer draws a
+ * random nonce, so no implementation can reproduce the JVM's bytes; an ECDSA
+ * signature is judged by its verifier, and this signer derives the nonce as RFC 6979
+ * 3.2 does (HMAC-SHA256; BouncyCastle ships the same rule as HMacDSAKCalculator):
+ * reproducible, no random number generator on the GPU, and accepted by every
+ * verifier, Crypto.doVerify included. Per lane:
+ *   h1 = SHA-256(m), e = int(h1) mod n, k = the RFC 6979 nonce of (d, h1),
+ *   r = x([k]G) mod n, s = k^-1 (e + d r) mod n,
+ *   sig = the minimal DER SEQUENCE { INTEGER r, INTEGER s } in a 72-byte slot.
+ * s is not normalised to the low half (BC 1.57 does not normalise it either, nor do
+ * the RFC's vectors). A candidate with k = 0, k >= n, r = 0 or s = 0 is passed over
+ * by the RFC's 3.2 h.3 update; the loop is bounded at 8 candidates, and a lane that
+ * exhausts it answers CORDAHIP_SIGN_FAILED with a zero row -- for a correct
+ * implementation an event of probability below 2^-250 on either curve (a candidate is
+ * rejected with probability below 2^-31: n > 2^256 - 2^225 on P-256 and
+ * n > 2^256 - 2^129 on secp256k1, and r = 0 or s = 0 needs a 2^-256 coincidence;
+ * eight in a row: below 2^-250).
+ *
+ * Key registry. cordahip_signer_add_ecdsa takes the private scalar d as 32 big-endian
+ * bytes. d = 0 or d >= n is data, not an ABI error: CORDAHIP_SUCCESS with
+ * *key_status = CORDAHIP_STATUS_BAD_KEY, *key_id = 0xFFFFFFFF and no slot taken; a
+ * scheme other than 2 or 3 is CORDAHIP_ERR_INVALID_ARG. Otherwise a kernel on every
+ * device writes the key's record and pub receives Q = [d]G as 65 SEC1 uncompressed
+ * bytes. Ids come from the signer's one pool (4096 slots with the Ed25519 keys, the
+ * same id form), and cordahip_signer_remove serves both families with the ordering
+ * stated above. An ECDSA id handed to cordahip_sign* answers
+ * CORDAHIP_SIGN_UNKNOWN_KEY, and an Ed25519 id handed to cordahip_ecdsa_sign* does.
+ * The ECDSA records and the two curves' comb tables [d 16^j]G (40 KiB each, built on
+ * a device's first key of the curve) are an allocation of their own (592 KB per
+ * device), made by the first ECDSA add, counted in cordahip_device_mem and kept by
+ * cordahip_trim and the idle release. Custody is the Ed25519 signer's: d crosses
+ * through page-locked staging wiped before add returns and a device scratch the add
+ * kernel zeroes; remove and shutdown zero the record on every device;
+ * CORDAHIP_TRACE never prints key material. The kernel reads no address and takes no
+ * branch that depends on d, the nonce or their digits.
+ *
+ * Per-lane statuses, by precedence: CORDAHIP_SIGN_SKIPPED, CORDAHIP_SIGN_UNKNOWN_KEY,
+ * CORDAHIP_STATUS_EMPTY (as for cordahip_sign), CORDAHIP_SIGN_FAILED, then
+ * CORDAHIP_STATUS_OK: sig[i*72 .. i*72+sig_len[i]) is the signature, the rest of the
+ * slot zero. Every lane that is not OK gets 72 zero bytes and length 0; no secret is
+ * read for it. A batch may mix both curves and many keys.
+ *
+ * cordahip_ecdsa_sign / _submit: host memory, CSR checked whole before any enqueue,
+ * sharding, CORDAHIP_HOST_CHUNK chunking and tickets as for cordahip_sign.
+ *
+ * CORDAHIP_SIGN_FAILED is an enumerator, not one of the CORDAHIP_SIGN_* macros: those
+ * two are the statuses every signing call shares, and no other lane status has their
+ * values. This one is the ECDSA signing calls' alone, and its value, 16, is also
+ * CORDAHIP_VERIFY_UNKNOWN_KEY's (keyed verification) and CORDAHIP_COMMIT_CONFLICT's
+ * (the commit log); no call writes two of them, so a status array is read by the call
+ * that filled it. */
+enum { CORDAHIP_SIGN_FAILED = 16 };
+int cordahip_signer_add_ecdsa(cordahip_ctx* ctx, uint32_t scheme, const uint8_t d[32] /* big-endian */,
+                              uint32_t* key_id, uint8_t* key_status, uint8_t pub[65]);
+typedef struct {
+  uint64_t n;
+  const uint32_t* key_id;  /* [n] ids from cordahip_signer_add_ecdsa */
+  const uint8_t* msg;
+  const uint64_t* msg_off; /* [n+1] into msg */
+  const uint8_t* gate;     /* [n] nonzero: skip the lane; may be NULL */
+  uint8_t* sig;            /* [n*72] out: DER, zero-padded; zero rows for lanes that are not OK */
+  uint8_t* sig_len;        /* [n] out */
+  uint8_t* status;         /* [n] out */
+  uint64_t msg_bytes;      /* bytes at msg; msg_off[n] <= msg_bytes */
+} cordahip_ecdsa_sign_batch;
+int cordahip_ecdsa_sign(cordahip_ctx* ctx, const cordahip_ecdsa_sign_batch* batch);
+int cordahip_ecdsa_sign_submit(cordahip_ctx* ctx, const cordahip_ecdsa_sign_batch* batch, uint64_t* ticket);
+/* Device-resident form: d_key_id uint32[n], d_msgs dense rows of msg_len bytes,
+ * d_gate uint8[n] or NULL, d_sigs [n*72] (4-byte aligned), d_sig_len [n], d_status [n],
+ * all in HBM on `device`, on hip_stream. d_gate is typically the tx_status an earlier
+ * call on the same stream wrote. msg_len == 0 makes every ungated lane with a live
+ * key EMPTY. */
+int cordahip_ecdsa_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
+                                     uint32_t msg_len, uint64_t n, const void* d_gate, void* d_sigs,
+                                     void* d_sig_len, void* d_status, void* hip_stream);
 
 /* ---- Ed25519 batch verification against registered public keys ----------------- *
  * Replaces, per lane, Crypto.doVerify / Crypto.isValid(EDDSA_ED25519_SHA512, key,
