@@ -48,6 +48,8 @@ EXPORTS = [
     "cordahip_ed25519_verify_keyed_device",
     "cordahip_vkey_add_ecdsa", "cordahip_ecdsa_verify_keyed", "cordahip_ecdsa_verify_keyed_submit",
     "cordahip_ecdsa_verify_keyed_device",
+    "cordahip_vkey_add_rsa", "cordahip_rsa_verify_keyed", "cordahip_rsa_verify_keyed_submit",
+    "cordahip_rsa_verify_keyed_device", "cordahip_rsa_public_op_keyed_device",
     "cordahip_vkey_set_routing", "cordahip_vkey_route_stats",
     "cordahip_vkey_set_routing_ecdsa", "cordahip_vkey_route_stats_ecdsa",
     "cordahip_commit_log_create", "cordahip_commit_log_destroy", "cordahip_commit_log_reserve",
@@ -84,6 +86,7 @@ ERR_INVALID_ARG, ERR_OUT_OF_MEMORY = -1, -4
 VERIFY_UNKNOWN_KEY = 16
 VKEY_MAX_KEYS = 64  # live verification keys per context (a full registry: CORDAHIP_ERR_OUT_OF_MEMORY)
 VKEY_NO_ID = 0xFFFFFFFF  # the id cordahip_vkey_add_ed25519 reports for bytes that are not a key
+RSA_VKEY_TABLE_BYTES = 67584  # a device's RSA verification-key table: 64 records of 1,056 bytes (rsa_vkey.hpp)
 # notary commit log (cordahip_commit_inputs): tx_status besides OK; ref_state values; an absent window side
 COMMIT_CONFLICT, COMMIT_TIME_WINDOW_INVALID, COMMIT_SKIPPED = 16, 17, 18
 REF_ABSENT, REF_SELF, REF_OTHER = 0, 1, 2
@@ -390,6 +393,11 @@ def lib() -> ctypes.CDLL:
         "cordahip_ecdsa_verify_keyed": (i32, [vp, ctypes.POINTER(KeyedSigBatch)]),
         "cordahip_ecdsa_verify_keyed_submit": (i32, [vp, ctypes.POINTER(KeyedSigBatch), ctypes.POINTER(u64)]),
         "cordahip_ecdsa_verify_keyed_device": (i32, [vp, i32, vp, vp, vp, vp, u32, u64, vp, vp, vp]),
+        "cordahip_vkey_add_rsa": (i32, [vp, vp, u32, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint8)]),
+        "cordahip_rsa_verify_keyed": (i32, [vp, ctypes.POINTER(KeyedSigBatch)]),
+        "cordahip_rsa_verify_keyed_submit": (i32, [vp, ctypes.POINTER(KeyedSigBatch), ctypes.POINTER(u64)]),
+        "cordahip_rsa_verify_keyed_device": (i32, [vp, i32, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp]),
+        "cordahip_rsa_public_op_keyed_device": (i32, [vp, i32, vp, vp, u32, u64, vp, vp]),
         "cordahip_commit_log_create": (i32, [vp, i32, u32, vp, ctypes.POINTER(u32)]),
         "cordahip_commit_log_destroy": (i32, [vp, u32]),
         "cordahip_commit_log_reserve": (i32, [vp, u32, u32]),

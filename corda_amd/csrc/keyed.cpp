@@ -1,7 +1,7 @@
 // libcordahip.so's registered-key calls: the signer's and the verification keys'
 // registries (cordahip_signer_*, cordahip_vkey_*), the host calls that sign and verify
 // with them a chunk at a time (cordahip_sign, cordahip_ecdsa_sign, cordahip_verify_keyed,
-// cordahip_ecdsa_verify_keyed) and their *_device forms. The shared runtime types are in
+// cordahip_ecdsa_verify_keyed, cordahip_rsa_verify_keyed) and their *_device forms. The shared runtime types are in
 // runtime.hpp; the routed enqueues of the generic paths (K14, K15) in runtime.cpp.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +16,7 @@
 #include "ed25519_comb.hpp"
 #include "ed25519_vkey.hpp"
 #include "pack_rows.hpp"
+#include "rsa_vkey.hpp"
 
 using namespace cordahip;
 using namespace cordahip::rt;
@@ -406,7 +407,7 @@ int ec_sign_impl(cordahip_ctx* ctx, const cordahip_ecdsa_sign_batch* b) {
 // keyed kernel that may still read it; the stream is drained before return. The
 // table's entries stay: without a record whose id matches, no lane reads them.
 hipError_t vkey_clear_record(Device& d, uint32_t slot) {
-  if (!d.vkeys.tab.p && !d.ec_vkeys.tab.p) return hipSuccess;
+  if (!d.vkeys.tab.p && !d.ec_vkeys.tab.p && !d.rsa_vkeys.tab.p) return hipSuccess;
   hipError_t e = hipSuccess;
   if (d.vkeys.tab.p) {
     d.vkeys.live &= ~(1ull << slot);  // routed enqueues (K14) count the device's live Ed25519 keys
@@ -424,6 +425,13 @@ hipError_t vkey_clear_record(Device& d, uint32_t slot) {
     EcVkeyState& st = d.ec_vkeys.state;
     if (st.scheme[slot]) st.live[st.scheme[slot] - 2]--;
     st.scheme[slot] = 0;
+  }
+  if (d.rsa_vkeys.tab.p) {  // and of the RSA family (K18)
+    hipError_t x = d.rsa_vkeys.ev.sync();
+    x = x ? x
+          : hipMemsetAsync(d.rsa_vkeys.tab.as<uint8_t>() + (size_t)slot * sizeof(rsa::VkeyRecord), 0,
+                           sizeof(rsa::VkeyRecord), d.stream);
+    e = e ? e : x;
   }
   const hipError_t f = hipStreamSynchronize(d.stream);
   return e ? e : f;
@@ -536,11 +544,70 @@ int vkey_add_impl(cordahip_ctx* ctx, uint32_t scheme, const uint8_t* key, uint32
   return CORDAHIP_SUCCESS;
 }
 
+// The RSA key's record, built by the host (rsa_vkey.hpp build_vkey_record), put in its
+// id's slot on one device (vkey_mu held): the device's first RSA key allocates the table,
+// zeroed. The record crosses in the table's page-locked stage, behind the table's fence.
+int rsa_vkey_put_on(Device& d, const rsa::VkeyRecord& rec) {
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  RsaVerifyKeys& k = d.rsa_vkeys;
+  if (!k.tab.p) {
+    if (k.tab.ensure(rsa_vkey_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+    if (hipMemsetAsync(k.tab.p, 0, k.tab.cap, d.stream) != hipSuccess) {
+      k.tab.release();  // never a table that was not zeroed
+      return CORDAHIP_ERR_HIP;
+    }
+  }
+  if (k.stage.ensure(sizeof rec) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  std::memcpy(k.stage.p, &rec, sizeof rec);
+  hipError_t e = k.ev.sync();  // a removed key's slot: no kernel still reads its record
+  e = e ? e
+        : hipMemcpyAsync(k.tab.as<uint8_t>() + (size_t)vkey_slot(rec.id) * sizeof rec, k.stage.p, sizeof rec,
+                         hipMemcpyHostToDevice, d.stream);
+  const hipError_t f = hipStreamSynchronize(d.stream);
+  return hip_err(e ? e : f);
+}
+
+// An RSA key (K18): the SPKI BIT STRING payload decoded as a generic lane's key is; the
+// same pool of slots and the same id space as the other two families.
+int rsa_vkey_add_impl(cordahip_ctx* ctx, const uint8_t* key, uint32_t key_len, uint32_t* key_id,
+                      uint8_t* key_status) {
+  rsa::VkeyRecord rec;
+  const uint8_t ks = rsa::vkey_record_from_der(key, key_len, rec);
+  if (ks != rsa::kOk) {  // BAD_KEY, or UNSUPPORTED for a key the GPU path declines: what a generic lane gets
+    *key_id = kVkeyNoId;
+    *key_status = ks;
+    return CORDAHIP_SUCCESS;
+  }
+  auto& reg = ctx->vkeys;
+  std::lock_guard<std::mutex> g(reg.mu);
+  uint32_t slot, id;
+  if (!reg.acquire(slot, id)) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  rec.id = id;
+  const int rc = on_each_device(
+      ctx, &Device::vkey_mu, [&](Device& d, size_t, bool&) { return rsa_vkey_put_on(d, rec); }, [] { return true; },
+      [&](Device& d) { (void)vkey_clear_record(d, slot); });  // no device keeps a record of a key the caller never got
+  if (rc != CORDAHIP_SUCCESS) return rc;
+  {
+    std::lock_guard<std::mutex> gm(ctx->rsa_mirror_mu);
+    ctx->rsa_mirror[slot] = {id, rec.words, rec.bits};
+  }
+  reg.commit(slot);
+  *key_id = id;
+  *key_status = CORDAHIP_STATUS_OK;
+  if (tracing())
+    fprintf(stderr, "[cordahip] vkey: RSA key id %u (%u bits) added (%u live)\n", id, rec.bits, reg.count);
+  return CORDAHIP_SUCCESS;
+}
+
 int vkey_remove_impl(cordahip_ctx* ctx, uint32_t key_id) {
   auto& reg = ctx->vkeys;
   std::lock_guard<std::mutex> g(reg.mu);
   uint32_t slot;
   if (!reg.release(key_id, slot)) return CORDAHIP_ERR_INVALID_ARG;
+  {
+    std::lock_guard<std::mutex> gm(ctx->rsa_mirror_mu);
+    ctx->rsa_mirror[slot] = {};
+  }
   // the id is dead from here on, whatever a device answers below
   const int rc = clear_on_each_device(ctx, &Device::vkey_mu, [&](Device& d) { return vkey_clear_record(d, slot); });
   if (tracing()) fprintf(stderr, "[cordahip] vkey: key id %u removed (%u live)\n", key_id, reg.count);
@@ -640,6 +707,130 @@ int keyed_verify(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b, bool ec) 
 }
 int verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) { return keyed_verify(ctx, b, false); }
 int ec_verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) { return keyed_verify(ctx, b, true); }
+
+// The RSA keyed verifier on stream s (rsa_mu and vkey_mu held, device current, the RSA
+// workspace grown for the call: rsa_ws_grow): behind the workspace's and the RSA table's
+// previous users, followed by both fences. A device without an RSA table passes none:
+// every lane is then UNKNOWN_KEY.
+hipError_t rsa_vkey_enqueue(Device& d, const uint32_t* key_id, const uint8_t* sigs, const uint16_t* sig_len,
+                            const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len, uint32_t W, uint64_t n,
+                            uint32_t flags, uint8_t* status, unsigned long long* verdict, hipStream_t s) {
+  RsaWork& w = d.rsa;
+  const size_t rb = rsa_ws_row_bytes(W);
+  hipError_t e = w.ev.wait(s);
+  e = e ? e : d.rsa_vkeys.ev.wait(s);
+  e = e ? e
+        : launch_rsa_verify_keyed(d.rsa_vkeys.tab.as<uint32_t>(), key_id, sigs, sig_len, msgs, msg_off, msg_len, W, n,
+                                  status, verdict, w.ws.as<uint8_t>(), w.ws.cap / rb / 64 * 64, flags, s);
+  const hipError_t r1 = w.ev.record(s), r2 = d.rsa_vkeys.ev.record(s);  // whatever was launched is fenced
+  return e ? e : r1 ? r1 : r2;
+}
+
+// cordahip_rsa_verify_keyed for lanes [lo, hi) on one device, a chunk of
+// CORDAHIP_HOST_CHUNK lanes at a time. A chunk's lanes are grouped by their key's width
+// class from the context's mirror of the registry (a lane whose id is not live there is
+// UNKNOWN_KEY now and is not sent); each class present runs over its rows only, in
+// launches of at most kRsaKeyedRows rows through the keyed stage -- key ids, signatures
+// right-sized to 4 W-byte slots, their lengths, the messages as a CSR of the launch's
+// rows -- and the statuses go back to their lanes. The stage is single: a launch's
+// statuses are read before the next one packs. rsa_mu is held for the run (the
+// workspace), outside the stage's lock; vkey_mu per launch.
+constexpr uint64_t kRsaKeyedRows = 1ull << 15;
+int rsa_keyed_shard(cordahip_ctx* ctx, Device& d, const cordahip_keyed_sig_batch* b, uint64_t lo, uint64_t hi) {
+  KeyedStage& st = d.vkey_stage;
+  std::lock_guard<std::mutex> gr(d.rsa_mu);
+  std::lock_guard<std::mutex> g(st.mu);
+  const NodeBind nb(d);
+  const Activity act(d);
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  const uint64_t chunk = (env_lanes("CORDAHIP_HOST_CHUNK", 1ull << 22) + 63) / 64 * 64;
+  HostPool& pool = pool_of(ctx, d);
+  hipStream_t s = d.stream;
+  std::vector<uint64_t> cl[3], mo;  // lanes by class: 64, 96, 128 words
+  cordahip_ctx::RsaVkeyMirror mir[kVkeySlots];
+  for (uint64_t a = lo; a < hi; a += chunk) {
+    const uint64_t m = std::min(chunk, hi - a);
+    const double t0 = now_ms();
+    {
+      std::lock_guard<std::mutex> gm(ctx->rsa_mirror_mu);
+      std::copy(ctx->rsa_mirror, ctx->rsa_mirror + kVkeySlots, mir);
+    }
+    for (auto& v : cl) v.clear();
+    for (uint64_t i = a; i < a + m; i++) {
+      const uint32_t id = b->key_id[i];
+      const auto& k = mir[vkey_slot(id)];
+      if (k.words && k.id == id) cl[k.words / 32 - 2].push_back(i);
+      else b->status[i] = CORDAHIP_VERIFY_UNKNOWN_KEY;
+    }
+    for (int c = 0; c < 3; c++) {
+      const uint32_t W = 64 + 32 * (uint32_t)c;
+      for (uint64_t r0 = 0; r0 < cl[c].size(); r0 += kRsaKeyedRows) {
+        const uint64_t rows = std::min<uint64_t>(kRsaKeyedRows, cl[c].size() - r0);
+        const uint64_t* lanes = cl[c].data() + r0;
+        mo.resize(rows + 1);
+        mo[0] = 0;
+        for (uint64_t r = 0; r < rows; r++) mo[r + 1] = mo[r] + (b->msg_off[lanes[r] + 1] - b->msg_off[lanes[r]]);
+        // the previous launch has drained: growing frees nothing in use
+        if (st.ids.ensure(rows * 4) || st.sig_rows.ensure(rows * 4 * W) || st.sig_len.ensure(rows * 2) ||
+            st.msgs.ensure(std::max<uint64_t>(mo[rows], 16)) || st.msg_off.ensure((rows + 1) * 8) ||
+            st.status.ensure(rows))
+          return CORDAHIP_ERR_OUT_OF_MEMORY;
+        std::memcpy(st.msg_off.h.p, mo.data(), (rows + 1) * 8);
+        pool.parallel_for(rows, 256, [&](uint64_t x, uint64_t y) {
+          for (uint64_t r = x; r < y; r++) {
+            const uint64_t i = lanes[r];
+            st.ids.h.as<uint32_t>()[r] = b->key_id[i];
+            // a signature longer than the slot is longer than the modulus: its length
+            // alone decides it (BAD_SIG), none of its bytes is sent
+            const uint64_t sl = b->sig_off[i + 1] - b->sig_off[i], fit = sl <= 4ull * W ? sl : 0;
+            uint8_t* row = st.sig_rows.h.as<uint8_t>() + r * 4ull * W;
+            if (fit) std::memcpy(row, b->sig + b->sig_off[i], fit);
+            std::memset(row + fit, 0, 4ull * W - fit);
+            st.sig_len.h.as<uint16_t>()[r] = (uint16_t)std::min<uint64_t>(sl, 4ull * W + 1);
+            if (mo[r + 1] != mo[r]) std::memcpy(st.msgs.h.as<uint8_t>() + mo[r], b->msg + b->msg_off[i], mo[r + 1] - mo[r]);
+          }
+        });
+        hipError_t e = st.ids.to_device(rows * 4, s);
+        e = e ? e : st.sig_rows.to_device(rows * 4 * W, s);
+        e = e ? e : st.sig_len.to_device(rows * 2, s);
+        if (mo[rows]) e = e ? e : st.msgs.to_device(mo[rows], s);
+        e = e ? e : st.msg_off.to_device((rows + 1) * 8, s);
+        if (e == hipSuccess && (e = rsa_ws_grow(d, W, rows)) == hipErrorOutOfMemory) {
+          (void)hipStreamSynchronize(s);
+          return CORDAHIP_ERR_OUT_OF_MEMORY;
+        }
+        if (e == hipSuccess) {
+          std::lock_guard<std::mutex> gv(d.vkey_mu);
+          e = rsa_vkey_enqueue(d, st.ids.d.as<uint32_t>(), st.sig_rows.d.as<uint8_t>(), st.sig_len.d.as<uint16_t>(),
+                               st.msgs.d.as<uint8_t>(), st.msg_off.d.as<uint64_t>(), 0, W, rows, b->flags,
+                               st.status.d.as<uint8_t>(), nullptr, s);
+        }
+        e = e ? e : st.status.to_host(rows, s);
+        e = e ? e : st.ev.record(s);
+        e = e ? e : st.ev.sync();
+        if (e != hipSuccess) {
+          (void)hipStreamSynchronize(s);  // no queued work outlives the call
+          return CORDAHIP_ERR_HIP;
+        }
+        const uint8_t* hs = st.status.h.as<uint8_t>();
+        for (uint64_t r = 0; r < rows; r++) b->status[lanes[r]] = hs[r];
+      }
+    }
+    if (tracing())
+      fprintf(stderr, "[cordahip] dev %d keyed RSA verify chunk: %llu lanes (%zu / %zu / %zu by class) in %.2f ms\n",
+              d.id, (unsigned long long)m, cl[0].size(), cl[1].size(), cl[2].size(), now_ms() - t0);
+  }
+  // the shard's verdict words (shards start at multiples of 64 lanes)
+  if (b->verdict) verdict_from_status(ctx, b->status + lo, hi - lo, b->verdict + lo / 64);
+  return CORDAHIP_SUCCESS;
+}
+
+int rsa_verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) {
+  if (b->n == 0) return CORDAHIP_SUCCESS;
+  if (!keyed_batch_ok(ctx, b)) return CORDAHIP_ERR_INVALID_ARG;
+  return for_shards(ctx->devs, b->n, 64,
+                    [&](Device& d, uint64_t lo, uint64_t hi) { return rsa_keyed_shard(ctx, d, b, lo, hi); });
+}
 
 // A device's cumulative counters of routed lanes: route_tot of the family's key table
 // (K14: d.vkeys, K15: d.ec_vkeys), written by kernels the table's fence follows.
@@ -827,6 +1018,66 @@ int cordahip_ecdsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void
                              static_cast<const uint8_t*>(d_sig_len), static_cast<const uint8_t*>(d_msgs), nullptr,
                              nullptr, msg_len, n, nullptr, 0u, static_cast<uint8_t*>(d_status),
                              static_cast<unsigned long long*>(d_verdict), s);
+    });
+  });
+}
+
+int cordahip_vkey_add_rsa(cordahip_ctx* ctx, const uint8_t* key, uint32_t key_len, uint32_t* key_id,
+                          uint8_t* key_status) {
+  if (!ctx || !key || !key_id || !key_status) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return rsa_vkey_add_impl(ctx, key, key_len, key_id, key_status); });
+}
+
+int cordahip_rsa_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch) {
+  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return rsa_verify_keyed_impl(ctx, batch); });
+}
+
+int cordahip_rsa_verify_keyed_submit(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch, uint64_t* ticket) {
+  return submit(ctx, ticket, rsa_verify_keyed_impl, batch);
+}
+
+int cordahip_rsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_sigs,
+                                     const void* d_sig_len, const void* d_msgs, uint32_t msg_len, uint32_t mod_words,
+                                     uint64_t n, void* d_status, void* d_verdict, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || (mod_words != 64 && mod_words != 96 && mod_words != 128) ||
+      (n && (!d_key_id || !d_sigs || !d_sig_len || !d_status || (msg_len && !d_msgs))))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_key_id) & 3) || (reinterpret_cast<uintptr_t>(d_sig_len) & 1) ||
+      (reinterpret_cast<uintptr_t>(d_verdict) & 7))
+    return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    std::lock_guard<std::mutex> g(d->rsa_mu);
+    return device_call(
+        *d, hip_stream, [&] { return rsa_ws_grow(*d, mod_words, n); },
+        [&](hipStream_t s) {
+          std::lock_guard<std::mutex> gv(d->vkey_mu);
+          return rsa_vkey_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_sigs),
+                                  static_cast<const uint16_t*>(d_sig_len), static_cast<const uint8_t*>(d_msgs),
+                                  nullptr, msg_len, mod_words, n, 0u, static_cast<uint8_t*>(d_status),
+                                  static_cast<unsigned long long*>(d_verdict), s);
+        });
+  });
+}
+
+int cordahip_rsa_public_op_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_in,
+                                        uint32_t mod_words, uint64_t n, void* d_out, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || (mod_words != 64 && mod_words != 96 && mod_words != 128) || (n && (!d_key_id || !d_in || !d_out)))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_key_id) | reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3)
+    return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    std::lock_guard<std::mutex> g(d->vkey_mu);  // no workspace: the table's lock and fence alone
+    return device_call(*d, hip_stream, [&](hipStream_t s) {
+      hipError_t e = d->rsa_vkeys.ev.wait(s);
+      e = e ? e
+            : launch_rsa_public_op_keyed(d->rsa_vkeys.tab.as<uint32_t>(), static_cast<const uint32_t*>(d_key_id),
+                                         static_cast<const uint32_t*>(d_in), mod_words, n,
+                                         static_cast<uint32_t*>(d_out), s);
+      const hipError_t r = d->rsa_vkeys.ev.record(s);
+      return e ? e : r;
     });
   });
 }

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rsa_vkey.hpp"
 #include "runtime.hpp"
 #include "sha2_device.hpp"
 #include "status.hpp"
@@ -491,5 +492,9 @@ hipError_t launch_rsa_pss_verify(const uint32_t* mod, const uint32_t* exp, const
   }
   return hipSuccess;
 }
+
+// K18, verification against registered keys: the kernels share this unit's device
+// functions (none of them changes; the generic kernels compile as before)
+#include "rsa_vkey.hip"
 
 }  // namespace cordahip

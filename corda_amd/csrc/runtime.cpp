@@ -334,15 +334,19 @@ hipError_t ec_verify_enqueue(Device& d, const uint8_t* scheme, const uint8_t* ke
 // current, d.rsa_mu held). The workspace holds at most kRsaWsRows rows (the
 // launches loop over it) and is reused only after its previous user's kernels.
 constexpr uint64_t kRsaWsRows = 1ull << 17;  // x 518 B (4096-bit rows) = 68 MB at most
+hipError_t rsa_ws_grow(Device& d, uint32_t W, uint64_t n) {
+  RsaWork& w = d.rsa;
+  const uint64_t rows = std::min<uint64_t>(kRsaWsRows, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
+  const size_t rb = rsa_ws_row_bytes(W);
+  return w.ev.grow(w.ws.cap < rows * rb, [&] { return w.ws.ensure(rows * rb) ? hipErrorOutOfMemory : hipSuccess; });
+}
 hipError_t rsa_verify_enqueue(Device& d, const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
                               const uint16_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len,
                               uint32_t W, uint64_t n, const uint8_t* pre, uint8_t* status,
                               unsigned long long* verdict, uint32_t flags, hipStream_t s) {
   RsaWork& w = d.rsa;
-  const uint64_t rows = std::min<uint64_t>(kRsaWsRows, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
   const size_t rb = rsa_ws_row_bytes(W);
-  hipError_t e = w.ev.grow(w.ws.cap < rows * rb,
-                           [&] { return w.ws.ensure(rows * rb) ? hipErrorOutOfMemory : hipSuccess; });
+  hipError_t e = rsa_ws_grow(d, W, n);
   e = e ? e : w.ev.wait(s);
   e = e ? e
         : launch_rsa_pss_verify(mod, exp, sigs, sig_len, msgs, msg_off, msg_len, W, n, pre, status, verdict,

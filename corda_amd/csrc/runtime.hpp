@@ -238,6 +238,19 @@ hipError_t launch_rsa_pss_verify(const uint32_t* mod, const uint32_t* exp, const
                                  uint32_t msg_len, uint32_t W, uint64_t n, const uint8_t* pre, uint8_t* status,
                                  unsigned long long* verdict, uint8_t* ws, uint64_t ws_rows, uint32_t flags,
                                  hipStream_t s);
+// rsa_vkey.hip (K18, in rsa.hip's unit): the same against registered keys. vtab: the
+// device's RSA key table (rsa_vkey.hpp: rsa_vkey_bytes(); null: no key was ever added,
+// every row is unknown); key_id[n]; one width class per launch. The raw op gives a zero
+// row for a key that is not live in class W or in >= n; the verifier answers
+// UNKNOWN_KEY first, then the statuses of launch_rsa_pss_verify.
+size_t rsa_vkey_bytes();
+hipError_t launch_rsa_public_op_keyed(const uint32_t* vtab, const uint32_t* key_id, const uint32_t* in, uint32_t W,
+                                      uint64_t n, uint32_t* out, hipStream_t s);
+hipError_t launch_rsa_verify_keyed(const uint32_t* vtab, const uint32_t* key_id, const uint8_t* sigs,
+                                   const uint16_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off,
+                                   uint32_t msg_len, uint32_t W, uint64_t n, uint8_t* status,
+                                   unsigned long long* verdict, uint8_t* ws, uint64_t ws_rows, uint32_t flags,
+                                   hipStream_t s);
 hipError_t launch_ecdsa_sign(const uint8_t* scheme, const uint8_t* seeds, const uint8_t* msgs, uint32_t msg_len,
                              uint64_t n, const uint32_t* gk1, const uint32_t* gr1, uint8_t* keys, uint8_t* key_len,
                              uint8_t* sigs, uint8_t* sig_len, hipStream_t s);
@@ -575,6 +588,12 @@ struct EcVerifyKeys : KeyTable {
   }
 };
 
+// The RSA verification keys' (rsa_vkey.hpp: 64 records of 1,056 bytes -- id, e, bit
+// length, width class, n', n and K = R^e mod n -- 67,584 bytes). The host builds a
+// record and it crosses in stage (1,056 bytes); no kernel builds anything. Allocated by
+// a device's first RSA add, under Device::vkey_mu like the other families' tables.
+struct RsaVerifyKeys : KeyTable {};
+
 // a page-locked buffer and its twin on the device (ensure: true when it failed)
 struct StageBuf {
   PinBuf h;
@@ -589,7 +608,9 @@ struct StageBuf {
 // when the chunk is not dense 32-byte rows) and status. cordahip_sign adds gate (gate
 // bytes in) and sig_rows (64-byte signatures out); the verifiers add sig_rows (in: 64
 // bytes a row, 72-byte DER slots for ECDSA), sig_len (ECDSA only), pre (the host's
-// pre-statuses) and verdict (words out). What a call does not use stays empty. mu is
+// pre-statuses) and verdict (words out); cordahip_rsa_verify_keyed uses sig_rows (4 W-byte
+// slots of one width class per launch), sig_len (uint16) and msg_off as a CSR of the
+// launch's rows. What a call does not use stays empty. mu is
 // held for a shard's run; ev follows a chunk's last copy.
 struct KeyedStage {
   std::mutex mu;
@@ -771,7 +792,7 @@ struct Device {
   // lock it did not take before.
   // Lock order of the locks met on these paths, outermost first:
   //   ped_mu / stream_mu / a SetLease (the pipelines) -> ed_mu[0] -> ed_mu[1] ->
-  //   ec_mu[0] -> ec_mu[1] -> ... -> sign_stage.mu -> vkey_stage.mu -> vkey_mu.
+  //   ec_mu[0] -> ec_mu[1] -> rsa_mu -> ... -> sign_stage.mu -> vkey_stage.mu -> vkey_mu.
   // trim_device takes them in that order up to vkey_stage.mu; a keyed host call holds
   // vkey_stage.mu and takes vkey_mu inside it; a routed enqueue holds ed_mu[slot]
   // (Ed25519, K14) or ec_mu[slot] (ECDSA, K15) and takes vkey_mu inside it. vkey_mu is
@@ -779,6 +800,10 @@ struct Device {
   // stats call, a keyed or routed enqueue) takes no other lock of the device but tmu
   // (the timing ring's, a leaf held for a few assignments), and a routed enqueue never
   // holds it while it waits for another lock, the slot's fence or the scratch's growth.
+  // The keyed RSA calls (K18) borrow the RSA workspace, so they take rsa_mu first, as
+  // every user of it does, and vkey_mu inside it: the host call rsa_mu -> vkey_stage.mu
+  // -> vkey_mu (per launch), the device calls rsa_mu -> vkey_mu (the raw op, which needs
+  // no workspace, vkey_mu alone). The workspace grows before vkey_mu is taken.
   VerifyKeys vkeys;
   std::mutex vkey_mu;
   std::atomic<uint32_t> route_on{0};
@@ -791,10 +816,13 @@ struct Device {
   // engine. With ec_route_on clear it takes no lock it did not take before.
   EcVerifyKeys ec_vkeys;
   std::atomic<uint32_t> ec_route_on{0};
+  // RSA verification against registered keys (K18): the records of the same registry's
+  // RSA keys, under the same vkey_mu, with a fence of their own.
+  RsaVerifyKeys rsa_vkeys;
   // the chunk stage of cordahip_verify_keyed and cordahip_ecdsa_verify_keyed (KeyedStage)
   KeyedStage vkey_stage;
 
-  // everything but `keys`, `ec_keys`, `vkeys` and `ec_vkeys`, which the idle release is never offered (visit_keys)
+  // everything but `keys`, `ec_keys`, `vkeys`, `ec_vkeys` and `rsa_vkeys`, which the idle release is never offered (visit_keys)
   template <class V>
   void visit(V& v) {
     for (DevBuf* b : {&btab, &gtab_k1, &gtab_r1}) v.dev(*b, kKept);
@@ -836,6 +864,7 @@ struct Device {
     ec_keys.visit(v);
     vkeys.visit(v);
     ec_vkeys.visit(v);
+    rsa_vkeys.visit(v);
   }
   struct Release : Visitor {  // the buffers; all: the kept ones too
     bool all = false;
@@ -1036,6 +1065,9 @@ hipError_t ec_verify_enqueue(Device& d, const uint8_t* scheme, const uint8_t* ke
                              const uint8_t* sigs, const uint8_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off,
                              uint32_t msg_len, uint64_t n, const uint8_t* pre, uint8_t* status,
                              unsigned long long* verdict, uint32_t flags, hipStream_t s, int slot = 0);
+// d.rsa_mu must be held: the RSA workspace grown for n rows of class W (at most the
+// workspace's row cap; the launches loop over it), after its previous user's kernels
+hipError_t rsa_ws_grow(Device& d, uint32_t W, uint64_t n);
 // d.rsa_mu must be held; one width class per call (rsa.hip launch_rsa_pss_verify)
 hipError_t rsa_verify_enqueue(Device& d, const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
                               const uint16_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len,
@@ -1124,7 +1156,14 @@ struct cordahip_ctx {
   // the two key registries (key_slots.hpp): which slots are live and each slot's reuse
   // counter; no key material. Their ids are namespaces of their own.
   cordahip::rt::SignerSlots signers;  // cordahip_signer_add_ed25519 / _remove
-  cordahip::rt::VkeySlots vkeys;      // cordahip_vkey_add_ed25519 / _add_ecdsa / _remove
+  cordahip::rt::VkeySlots vkeys;      // cordahip_vkey_add_ed25519 / _add_ecdsa / _add_rsa / _remove
+  // what the host knows of each slot's live RSA key (words 0: the slot holds none): the
+  // keyed RSA host call sizes and partitions its rows from it without a device read
+  struct RsaVkeyMirror {
+    uint32_t id = 0, words = 0, bits = 0;
+  };
+  std::mutex rsa_mirror_mu;
+  RsaVkeyMirror rsa_mirror[cordahip::kVkeySlots];
   // the notary commit logs (cordahip_commit_log_create / _destroy): id -> log; ids
   // count up and are never reused. logs_mu guards the map and the counter only.
   std::mutex logs_mu;

@@ -507,6 +507,62 @@ class Engine:
             verdict.data_ptr() if verdict is not None else None, s),
             "cordahip_ecdsa_verify_keyed_device")
 
+    # ---- RSA_SHA256 verification against registered keys (the same registry: one pool of ids) ----
+    def vkey_add_rsa(self, der: bytes):
+        """cordahip_vkey_add_rsa: the SPKI BIT STRING payload (DER RSAPublicKey) decoded as a generic lane's
+        key is, and its record (n', n, K = R^e mod n) copied to every device of the context. Returns
+        (key_id, key_status): (id, OK), or (VKEY_NO_ID, BAD_KEY / UNSUPPORTED) for bytes that do not decode
+        or a key the GPU path declines (no slot taken). vkey_remove removes the key."""
+        kid, st = ctypes.c_uint32(), ctypes.c_uint8()
+        check(lib().cordahip_vkey_add_rsa(self._ctx, bytes(der), len(der), ctypes.byref(kid), ctypes.byref(st)),
+              "cordahip_vkey_add_rsa")
+        return kid.value, st.value
+
+    def rsa_verify_keyed_batch(self, key_ids: Sequence[int], sigs: Sequence[bytes], msgs: Sequence[bytes],
+                               is_valid: bool = False, async_: bool = False):
+        """cordahip_rsa_verify_keyed / cordahip_rsa_verify_keyed_submit: lane i checks the RSASSA-PSS
+        signature sigs[i] over msgs[i] against the registered RSA key key_ids[i]. Returns (status[n], verdict)
+        -- or, async_, a Ticket whose wait() returns them. is_valid as in verify_batch."""
+        n = len(sigs)
+        assert len(key_ids) == n and len(msgs) == n
+        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
+        sb, so = self._csr(list(sigs))
+        mb, mo = self._csr(list(msgs))
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        verdict = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
+        b = _lib.KeyedSigBatch(n, _ptr(ids), _ptr(sb), _ptr(so), _ptr(mb), _ptr(mo), _ptr(status), _ptr(verdict),
+                               _lib.FLAG_IS_VALID if is_valid else 0, sb.size if n and so[n] else 0,
+                               mb.size if n and mo[n] else 0)
+        keep = (ids, sb, so, mb, mo, status, verdict, b)
+        if async_:
+            t = ctypes.c_uint64()
+            check(lib().cordahip_rsa_verify_keyed_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)),
+                  "cordahip_rsa_verify_keyed_submit")
+            return Ticket(self, t.value, lambda: (status[:n], verdict), keep)
+        check(lib().cordahip_rsa_verify_keyed(self._ctx, ctypes.byref(b)), "cordahip_rsa_verify_keyed")
+        return status[:n], verdict
+
+    def rsa_verify_keyed_device(self, key_ids, sigs, sig_len, msgs, status, verdict=None, device: int = 0,
+                                stream=None):
+        """cordahip_rsa_verify_keyed_device over device tensors, one width class W = sigs.shape[1] // 4 per
+        call: key_ids int32 [n], sigs uint8 [n, 4 W] big-endian, sig_len int16 [n], msgs uint8 [n, L];
+        outputs status uint8 [n] and verdict int64 [(n + 63) // 64] or None; doVerify statuses."""
+        n = key_ids.shape[0]
+        s = stream.cuda_stream if stream is not None else 0
+        check(lib().cordahip_rsa_verify_keyed_device(
+            self._ctx, device, key_ids.data_ptr(), sigs.data_ptr(), sig_len.data_ptr(),
+            msgs.data_ptr() if msgs.shape[1] else None, msgs.shape[1], sigs.shape[1] // 4, n, status.data_ptr(),
+            verdict.data_ptr() if verdict is not None else None, s), "cordahip_rsa_verify_keyed_device")
+
+    def rsa_public_op_keyed_device(self, key_ids, inp, out, device: int = 0, stream=None):
+        """out = inp^e mod n of the registered RSA key key_ids[i] per row. Device tensors: key_ids int32 [n],
+        inp / out [n, W] int32 (little-endian words, W = 64, 96 or 128: the call's width class). A row whose
+        id names no live RSA key of that class, or with inp >= n, comes back zero."""
+        s = stream.cuda_stream if stream is not None else 0
+        check(lib().cordahip_rsa_public_op_keyed_device(self._ctx, device, key_ids.data_ptr(), inp.data_ptr(),
+                                                        inp.shape[1], inp.shape[0], out.data_ptr(), s),
+              "cordahip_rsa_public_op_keyed_device")
+
     def ed25519_verify_keyed_device(self, key_ids, sigs, msgs, status, verdict=None, device: int = 0, stream=None):
         """cordahip_ed25519_verify_keyed_device over device tensors: key_ids int32 [n], sigs uint8 [n, 64],
         msgs uint8 [n, L]; outputs status uint8 [n] and verdict int64 [(n + 63) // 64] or None."""

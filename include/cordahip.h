@@ -664,6 +664,89 @@ int cordahip_ecdsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void
 int cordahip_vkey_set_routing_ecdsa(cordahip_ctx* ctx, uint32_t on);
 int cordahip_vkey_route_stats_ecdsa(cordahip_ctx* ctx, int device, uint64_t* keyed_lanes, uint64_t* generic_lanes);
 
+/* ---- RSA_SHA256 verification against registered public keys (kernel K18) -----
+ * Replaces, per lane, Crypto.doVerify / Crypto.isValid(RSA_SHA256, key, sig, clear)
+ * (Crypto.kt:472-541 -> BouncyCastle PSSSigner.verifySignature; the rules of
+ * CORDAHIP_FLAG_RSA_ON_DEVICE above) for the RSA keys a network keeps for years:
+ * TLS and legacy identity keys, certificate keys. A generic RSA lane derives its
+ * key's Montgomery constants again on the device (n', R^2 mod n by doublings and
+ * squarings, a conversion in and one out: 12 of the 29 modular products of a
+ * 3072-bit, e = 65537 verification) and its host side parses the key's DER and
+ * ships the modulus for every lane. A registered key keeps n' and one constant,
+ * K = R^e mod n (R = 2^(32 words)): a lane names the key by id and computes
+ * s^e mod n as the square-and-multiply chain over the UNCONVERTED signature
+ * followed by one product with K -- 18 products for e = 65537, 3 for e = 3 --
+ * then applies the PSS rules as the generic path does. Apart from UNKNOWN_KEY a
+ * lane answers exactly what cordahip_sig_verify with CORDAHIP_FLAG_RSA_ON_DEVICE
+ * answers for the same signature and message with that key's bytes, under both
+ * flags values.
+ *
+ * Key registry. cordahip_vkey_add_rsa takes the SPKI BIT STRING payload (DER
+ * RSAPublicKey), exactly what a generic batch lane carries, and decodes it by the
+ * generic path's rules. Bytes that do not decode are data, not an ABI error:
+ * CORDAHIP_SUCCESS with *key_status = CORDAHIP_STATUS_BAD_KEY, or
+ * CORDAHIP_STATUS_UNSUPPORTED for a key BouncyCastle accepts and the GPU path
+ * declines (even n, a modulus outside 1024..4096 bits, even e, e < 3, e >= 2^32)
+ * -- the statuses a generic lane with that key gets -- with *key_id = 0xFFFFFFFF
+ * and no slot taken. A NULL pointer is CORDAHIP_ERR_INVALID_ARG. Otherwise the
+ * host builds the key's record (id, e, bit length, width class, n', n, K: 1,056
+ * bytes) and copies it to every device of the context; no kernel runs.
+ * The registry is the Ed25519 / ECDSA one: ONE pool of CORDAHIP_VKEY_MAX_KEYS live
+ * keys per context and one id space for all three families; the 65th live key of
+ * any family is CORDAHIP_ERR_OUT_OF_MEMORY, and cordahip_vkey_remove removes a
+ * key of any family, with the ordering documented above (it waits for the RSA
+ * table's fence; an id is never reused). An RSA id given to cordahip_verify_keyed
+ * or cordahip_ecdsa_verify_keyed*, or an Ed25519 / ECDSA id given to the calls
+ * below, names no key of that family: the lane is CORDAHIP_VERIFY_UNKNOWN_KEY.
+ * The RSA table (64 records, 67,584 bytes per device) is allocated by a device's
+ * first RSA add that decodes -- a context that never registers an RSA key does
+ * not allocate it -- is counted in cordahip_device_mem, and is kept by
+ * cordahip_trim and the idle release. A public key is public: nothing here is
+ * constant-time.
+ *
+ * Per-lane statuses, by precedence:
+ *   CORDAHIP_VERIFY_UNKNOWN_KEY   key_id[i] names no live RSA key (device calls:
+ *                                 none of the call's width class); no record field
+ *                                 beyond the id and the class is read
+ *   CORDAHIP_STATUS_EMPTY         flags == 0 (doVerify) only: empty signature or
+ *                                 empty message (Crypto.kt:475-476)
+ *   CORDAHIP_STATUS_BAD_SIG       signature longer than the modulus, s >= n, or a
+ *                                 PSS rule fails
+ *   CORDAHIP_STATUS_OK
+ * verdict bit i = (status[i] == OK).
+ *
+ * cordahip_rsa_verify_keyed / _submit: cordahip_keyed_sig_batch with big-endian
+ * signatures of any length in the CSR; checks and sharding as for
+ * cordahip_verify_keyed. A device's lanes stream a chunk of CORDAHIP_HOST_CHUNK
+ * lanes at a time; a chunk's lanes are grouped by their key's width class (64, 96
+ * or 128 words: moduli of up to 2048, 3072, 4096 bits) and each class present
+ * runs over its rows only, 2^15 rows a launch; statuses and verdict words land in
+ * lane order.
+ *
+ * Device-resident forms, doVerify rules, one width class per call like the dense
+ * RSA calls (mod_words 64, 96 or 128, else CORDAHIP_ERR_INVALID_ARG): a live RSA
+ * key of another class is UNKNOWN_KEY. cordahip_rsa_verify_keyed_device:
+ * d_key_id uint32[n], d_sigs big-endian in 4*mod_words-byte slots, d_sig_len
+ * uint16[n], d_msgs dense rows of msg_len bytes, d_status [n], d_verdict
+ * [(n+63)/64] or NULL, all in HBM on `device`, on hip_stream. msg_len == 0 makes
+ * every lane with a live key EMPTY; a sig_len beyond the slot is BAD_SIG without
+ * reading past it. On a device where no RSA key was ever added every lane is
+ * UNKNOWN_KEY.
+ * cordahip_rsa_public_op_keyed_device is the kernel on its own: d_in / d_out rows
+ * of mod_words little-endian uint32 words (4-byte aligned; d_out may be d_in),
+ * out = in^e mod n of the lane's key; a ZERO ROW for an unknown key (or one of
+ * another class) and for in >= n. */
+int cordahip_vkey_add_rsa(cordahip_ctx* ctx, const uint8_t* key, uint32_t key_len, uint32_t* key_id,
+                          uint8_t* key_status);
+int cordahip_rsa_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch);
+int cordahip_rsa_verify_keyed_submit(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch, uint64_t* ticket);
+int cordahip_rsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_sigs,
+                                     const void* d_sig_len /* uint16[n] */, const void* d_msgs, uint32_t msg_len,
+                                     uint32_t mod_words, uint64_t n, void* d_status, void* d_verdict,
+                                     void* hip_stream);
+int cordahip_rsa_public_op_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_in,
+                                        uint32_t mod_words, uint64_t n, void* d_out, void* hip_stream);
+
 /* ECDSA keygen + sign (device memory), corpus generation: per lane scheme 2/3,
  * d = SHA-256(seed) mod n, k = SHA-256(seed || msg[:64]) mod n; writes the
  * uncompressed SEC1 key (65-byte slot, key_len = 65) and the DER signature

@@ -203,8 +203,10 @@ int main() {
     // and the registered ECDSA keys' tables with what the host knows of them (f)
     // and the two routing switches (route_on, ec_route_on: each padded to 8 bytes)
     // and the ECDSA signer's table with what the host knows of it (f)
+    // and the registered RSA keys' table (f)
     constexpr size_t kDeviceOwnPlain = 1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys) + 2 * sizeof(std::mutex) +
-                                       sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + 16 + sizeof(EcSignKeys);
+                                       sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + 16 + sizeof(EcSignKeys) +
+                                       sizeof(RsaVerifyKeys);
     const Count c = visited(*d, kDeviceOwnPlain + kTxSets * kTxSetPlain + kPackStages * kPackPlain, "Device");
     ndev = c.ndev, npin = c.npin, nev = c.nfence + c.nevent;
     CHECK(c.nstream == 7);
@@ -263,8 +265,8 @@ int main() {
     k->visit(gk);
     const size_t before = g.dev.size();
     k->visit_keys(gk);
-    // the four tables and the routed lanes' counters (VerifyKeys::route_tot, EcVerifyKeys::route_tot)
-    CHECK(g.dev.size() == before + 6 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
+    // the five tables and the routed lanes' counters (VerifyKeys::route_tot, EcVerifyKeys::route_tot)
+    CHECK(g.dev.size() == before + 7 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
     CHECK(k->ec_keys.tab.dev == 6 && k->ec_keys.tab.p && k->ec_keys.stage.p && k->ec_keys.ev.ev);
     CHECK(k->vkeys.route_tot.dev == 6 && k->vkeys.route_tot.p);
     CHECK(k->ec_vkeys.route_tot.dev == 6 && k->ec_vkeys.route_tot.p);
@@ -273,7 +275,10 @@ int main() {
     void *tab = k->keys.tab.p, *stage = k->keys.stage.p, *vtab = k->vkeys.tab.p, *vstage = k->vkeys.stage.p;
     void *etab = k->ec_vkeys.tab.p, *estage = k->ec_vkeys.stage.p;
     void *stab = k->ec_keys.tab.p, *sstage = k->ec_keys.stage.p;
+    CHECK(k->rsa_vkeys.tab.dev == 6 && k->rsa_vkeys.tab.p && k->rsa_vkeys.stage.p && k->rsa_vkeys.ev.ev);
+    void *rtab = k->rsa_vkeys.tab.p, *rstage = k->rsa_vkeys.stage.p;
     k->release_idle();
+    CHECK(k->rsa_vkeys.tab.p == rtab && k->rsa_vkeys.stage.p == rstage && g.dev.count(rtab) && g.pin.count(rstage));
     CHECK(k->ec_keys.tab.p == stab && k->ec_keys.stage.p == sstage && g.dev.count(stab) && g.pin.count(sstage));
     CHECK(k->keys.tab.p == tab && k->keys.stage.p == stage && g.dev.count(tab) && g.pin.count(stage));
     CHECK(k->vkeys.tab.p == vtab && k->vkeys.stage.p == vstage && g.dev.count(vtab) && g.pin.count(vstage));
@@ -283,7 +288,7 @@ int main() {
     CHECK(kk.devs.size() == kept.devs.size());
     CHECK(mem_acct(6).in_use.load() ==
           kk.bytes + k->keys.tab.cap + k->ec_keys.tab.cap + k->vkeys.tab.cap + k->vkeys.route_tot.cap +
-              k->ec_vkeys.tab.cap + k->ec_vkeys.route_tot.cap);
+              k->ec_vkeys.tab.cap + k->ec_vkeys.route_tot.cap + k->rsa_vkeys.tab.cap);
     delete k;
     CHECK(g.clean() && mem_acct(6).in_use.load() == 0);
   }

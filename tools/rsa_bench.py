@@ -20,6 +20,22 @@ with device events over >= 20 steps after warm-up. Prints ONE JSON line:
                         is a floor for the CPU, not its best), or the reason it could not run
 A run without a GPU fails; nothing falls back.
   python tools/rsa_bench.py [--rows-log2 18] [--steps 20] [--warmup 3] [--out profiles/NAME.json]
+
+--keyed: the registered-key verifier (K18) against the generic one, A/B in one process on one box.
+The same resident rows go through cordahip_rsa_pss_verify_device and, their keys registered,
+through cordahip_rsa_verify_keyed_device, the two calls alternating step by step on one stream,
+timed with device events; every lane's status is compared between the two. Four legs: the
+3072-bit rows above (some of their keys are shorter than their class), one 3072-bit key alone, then
+the 2048-bit class with a 1024-bit key and with a 2048-bit key. Per leg:
+  generic_ms, keyed_ms      median step times (min, max beside them), ratio = generic / keyed
+  generic_spread_ms         the largest difference between consecutive generic steps; the bar is
+                            generic_ms - keyed_ms > 3 x that (over_bar)
+  modexp_generic_ms, modexp_keyed_ms
+                            the modular exponentiations alone (the two raw ops), alternating too
+  products_generic, products_keyed, model_ratio
+                            the product counts of the two schedules and the step ratio they predict
+                            when only the modexp share of the generic step shrinks
+  differing_lanes           lanes whose statuses differ between the two calls (must be 0)
 """
 import argparse
 import json
@@ -46,6 +62,142 @@ def products(e):
     return sq + 1 + top + bin(e).count("1") - 1 + 1
 
 
+def products_at(e, w, keyed):
+    """Montgomery products of a wave of exponent e in class w: rsa_modexp_kernel (squarings for R^2, in
+    and out of Montgomery form, the chain) or rsa_modexp_keyed_kernel (the chain and the product with K)."""
+    chain = e.bit_length() - 1 + bin(e).count("1") - 1
+    if keyed:
+        return chain + 1
+    return (32 * w & -(32 * w)).bit_length() - 1 + 1 + chain + 1
+
+
+def keyed_leg(torch, eng, a, name, w, keys, rng):
+    """one A/B leg: n rows of class w over `keys`, generic and keyed alternating"""
+    import bc_rsa_pss as bc
+    n = 1 << a.rows_log2
+    dist = []
+    for i in range(a.distinct):
+        k = keys[i % len(keys)]
+        m = rng.randbytes(32)
+        em = bc.encode_em(m, k["n"].bit_length(), rng.randbytes(32))
+        sig = bc.sign_crt(em, k["p"], k["q"], k["d"]).to_bytes((k["n"].bit_length() + 7) // 8, "big")
+        dist.append((i % len(keys), sig, m))
+    ids = []
+    for k in keys:
+        kid, st = eng.vkey_add_rsa(bc.encode_key(k["n"], k["e"]))
+        assert st == 0, st
+        ids.append(kid)
+    mod = np.zeros((a.distinct, w), np.uint32)
+    exp = np.zeros(a.distinct, np.uint32)
+    kid = np.zeros(a.distinct, np.uint32)
+    sigs = np.zeros((a.distinct, 4 * w), np.uint8)
+    sl = np.zeros(a.distinct, np.uint16)
+    msgs = np.zeros((a.distinct, 32), np.uint8)
+    words = np.zeros((a.distinct, w), np.uint32)
+    for i, (ki, sig, m) in enumerate(dist):
+        k = keys[ki]
+        mod[i] = np.frombuffer(k["n"].to_bytes(4 * w, "little"), "<u4")
+        exp[i] = k["e"]
+        kid[i] = ids[ki]
+        sigs[i, :len(sig)] = np.frombuffer(sig, np.uint8)
+        sl[i] = len(sig)
+        msgs[i] = np.frombuffer(m, np.uint8)
+        words[i] = np.frombuffer(int.from_bytes(sig, "big").to_bytes(4 * w, "little"), "<u4")
+    idx = np.arange(n) % a.distinct
+    bad = np.zeros(n, bool)
+    bad[rng.sample(range(n), n // 100)] = True
+    rows_sig = sigs[idx]
+    rows_sig[bad, 100] ^= 0x10  # 1 % corrupted
+    dev = torch.device("cuda:0")
+    t = lambda x, ty: torch.from_numpy(np.ascontiguousarray(x).view(ty)).to(dev)  # noqa: E731
+    tm, te, tw, tk = t(mod[idx], np.int32), t(exp[idx], np.int32), t(words[idx], np.int32), t(kid[idx], np.int32)
+    ts, tl, tg = t(rows_sig, np.uint8), t(sl[idx], np.int16), t(msgs[idx], np.uint8)
+    st_g = torch.empty(n, dtype=torch.uint8, device=dev)
+    st_k = torch.empty(n, dtype=torch.uint8, device=dev)
+    verdict = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev)
+    out_g = torch.empty((n, w), dtype=torch.int32, device=dev)
+    out_k = torch.empty((n, w), dtype=torch.int32, device=dev)
+    stream = torch.cuda.Stream(device=dev)
+
+    def alternate(fa, fb):
+        ms = ([], [])
+        for step in range(a.warmup + a.steps):
+            for which, fn in enumerate((fa, fb)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                fn()
+                e1.record(stream)
+                e1.synchronize()
+                if step >= a.warmup:
+                    ms[which].append(e0.elapsed_time(e1))
+        return ms
+    gms, kms = alternate(lambda: eng.rsa_pss_verify_device(tm, te, ts, tl, tg, st_g, verdict, stream=stream),
+                         lambda: eng.rsa_verify_keyed_device(tk, ts, tl, tg, st_k, verdict, stream=stream))
+    sg, sk = st_g.cpu().numpy(), st_k.cpu().numpy()
+    differing = int((sg != sk).sum())
+    assert int((sg == 0).sum()) == n - int(bad.sum()) and (sg[bad] == 1).all(), "wrong statuses"
+    mg, mk = alternate(lambda: eng.rsa_public_op_device(tm, te, tw, out_g, stream=stream),
+                       lambda: eng.rsa_public_op_keyed_device(tk, tw, out_k, stream=stream))
+    rows_differ = int((out_g != out_k).any(dim=1).sum().item())
+    for i in ids:
+        eng.vkey_remove(i)
+    med = lambda v: float(np.median(v))  # noqa: E731
+    spread = max(abs(x - y) for x, y in zip(gms, gms[1:])) if len(gms) > 1 else 0.0
+    e = keys[0]["e"]
+    pg, pk = products_at(e, w, False), products_at(e, w, True)
+    share = med(mg) / med(gms)  # the modexp's share of the generic step, this run
+    return {"leg": name, "rows": n, "mod_words": w, "modulus_bits": sorted({k["n"].bit_length() for k in keys}),
+            "keys": len(keys), "e": e, "distinct_signatures": a.distinct, "corrupted_rows": int(bad.sum()),
+            "generic_ms": med(gms), "generic_ms_min": min(gms), "generic_ms_max": max(gms),
+            "keyed_ms": med(kms), "keyed_ms_min": min(kms), "keyed_ms_max": max(kms),
+            "generic_spread_ms": spread, "ratio": med(gms) / med(kms),
+            "over_bar": bool(med(gms) - med(kms) > 3 * spread),
+            "modexp_generic_ms": med(mg), "modexp_keyed_ms": med(mk), "modexp_ratio": med(mg) / med(mk),
+            "modexp_share_of_generic": share, "products_generic": pg, "products_keyed": pk,
+            "model_ratio": 1.0 / (1.0 - share + share * pk / pg),
+            "keyed_verifs_per_s": n / (med(kms) * 1e-3), "generic_verifs_per_s": n / (med(gms) * 1e-3),
+            "differing_lanes": differing, "differing_modexp_rows": rows_differ}
+
+
+def keyed_main(a):
+    import torch
+    if not torch.cuda.is_available():
+        print("rsa_bench.py: no GPU", file=sys.stderr)
+        return 2
+    from corda_amd.engine import Engine
+    with open(os.path.join(ROOT, "tests", "golden", "rsa_pss_vectors.json")) as f:
+        g = json.load(f)
+    fix = [{f: int(k[f], 16) for f in ("n", "e", "d", "p", "q")} for k in g["keys"]
+           if "d" in k and int(k["e"], 16) == 65537]
+    k3072 = [k for k in fix if 2048 < k["n"].bit_length() <= 3072]
+    try:
+        import openssl_rsa_pss as ossl
+        for _ in range(2):  # the same handful of keys as the plain run: two more from OpenSSL where it loads
+            h, k = ossl.keygen(3072)
+            ossl.free_key(h)
+            k3072.append(k)
+    except (OSError, AttributeError, AssertionError):
+        pass
+    legs = [("3072-bit rows", 96, k3072),
+            ("3072-bit class, a 3072-bit key", 96, [k for k in fix if k["n"].bit_length() == 3072][:1]),
+            ("2048-bit class, a 1024-bit key", 64, [k for k in fix if k["n"].bit_length() == 1024][:1]),
+            ("2048-bit class, a 2048-bit key", 64, [k for k in fix if k["n"].bit_length() == 2048][:1])]
+    rng = random.Random(0xBE7C)
+    res = {"workload": "rsa_verify_keyed_device against rsa_pss_verify_device, alternating", "steps": a.steps,
+           "warmup": a.warmup, "legs": []}
+    with Engine(1) as eng:
+        for name, w, keys in legs:
+            assert keys, name
+            res["legs"].append(keyed_leg(torch, eng, a, name, w, keys, rng))
+    res["differing_lanes"] = sum(l["differing_lanes"] for l in res["legs"])
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if res["differing_lanes"] == 0 else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows-log2", type=int, default=18)
@@ -55,7 +207,10 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-rows", type=int, default=1 << 14)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--keyed", action="store_true", help="A/B of the registered-key verifier against the generic one")
     a = ap.parse_args()
+    if a.keyed:
+        return keyed_main(a)
 
     import torch
     if not torch.cuda.is_available():
