@@ -65,6 +65,18 @@ inline Device* dev_at(cordahip_ctx* ctx, int device) {
   return ctx->devs[device].get();
 }
 
+// a *_device entry point's void pointers: p is not a multiple of `align` (a power of
+// two; NULL is aligned), and p as the kernels' element type
+inline bool misaligned(const void* p, uintptr_t align) { return (reinterpret_cast<uintptr_t>(p) & (align - 1)) != 0; }
+template <class T>
+const T* ptr(const void* p) {
+  return static_cast<const T*>(p);
+}
+template <class T>
+T* ptr(void* p) {
+  return static_cast<T*>(p);
+}
+
 }  // namespace rt
 }  // namespace cordahip
 #pragma GCC visibility pop

@@ -21,9 +21,33 @@
 using namespace cordahip;
 using namespace cordahip::rt;
 
+// What each family's table holds for a slot, and of the signer's what is secret
+// (runtime.hpp KeyTable), from the kernels' layouts.
+namespace cordahip {
+namespace rt {
+TabSpan SignKeys::record(uint32_t slot) const { return {(size_t)slot * kSignRecWords * 4, kSignRecWords * 4}; }
+TabSpan SignKeys::secrets() const { return {0, tab.cap}; }
+TabSpan EcSignKeys::record(uint32_t slot) const {
+  return {(kEcSignRecBase + (size_t)slot * kEcSignRecWords) * 4, kEcSignRecWords * 4};
+}
+TabSpan EcSignKeys::secrets() const {  // the records and the scratch; the comb tables before them are public
+  return {(size_t)kEcSignRecBase * 4, (size_t)(kEcSignAllWords - kEcSignRecBase) * 4};
+}
+TabSpan VerifyKeys::record(uint32_t slot) const {
+  return {(kVkeyRecBase + (size_t)slot * kVkeyRecWords) * 4, kVkeyRecWords * 4};
+}
+TabSpan EcVerifyKeys::record(uint32_t slot) const {
+  return {(kEcVkeyRecBase + (size_t)slot * kEcVkeyRecWords) * 4, kEcVkeyRecWords * 4};
+}
+TabSpan RsaVerifyKeys::record(uint32_t slot) const {
+  return {(size_t)slot * sizeof(rsa::VkeyRecord), sizeof(rsa::VkeyRecord)};
+}
+}  // namespace rt
+}  // namespace cordahip
+
 namespace {
 
-// What an add or a remove does on every device of the context, in order, each under its
+// What an add does on every device of the context, in order, each under its
 // lock `mu` (Device::sign_mu or Device::vkey_mu) and counted as activity: build(d, i,
 // more) on device i, which may clear `more` to end the round there; a later device
 // whose answer does not agree with device 0's (agrees()) is CORDAHIP_ERR_HIP. The first
@@ -49,47 +73,47 @@ int on_each_device(cordahip_ctx* ctx, std::mutex Device::*mu, Build build, Agree
   }
   return rc;
 }
-// a remove: clear(d) on every device, made current, whatever the devices before it
-// answered; the first HIP error
-template <class Clear>
-int clear_on_each_device(cordahip_ctx* ctx, std::mutex Device::*mu, Clear clear) {
+// A slot's record cleared on one device in every allocated family of a registry -- the
+// signer's (sign_mu held) or the verification keys' (vkey_mu held), device current: one
+// pool of slots, one remove. Each family's fence is waited for before its record is
+// zeroed, so no kernel still reads it, and the host's note of the slot goes with it
+// (KeyTable); every family is visited whatever an earlier one answered, and the stream
+// is drained before return. The first error.
+enum class Registry { kSigner, kVerify };
+hipError_t clear_slot(Device& d, Registry which, uint32_t slot) {
   hipError_t e = hipSuccess;
-  (void)on_each_device(
-      ctx, mu,
-      [&](Device& d, size_t, bool&) {
-        const hipError_t s = hipSetDevice(d.id);
-        const hipError_t z = s ? s : clear(d);
-        e = e ? e : z;
-        return (int)CORDAHIP_SUCCESS;
-      },
-      [] { return true; }, [](Device&) {});
+  bool any = false;
+  const auto clear = [&](auto& k) {
+    if (!k.tab.p) return;
+    any = true;
+    k.forget(slot);
+    hipError_t x = k.ev.sync();
+    const TabSpan r = k.record(slot);
+    x = x ? x : hipMemsetAsync(k.tab.template as<uint8_t>() + r.at, 0, r.bytes, d.stream);
+    e = e ? e : x;
+  };
+  if (which == Registry::kSigner) d.signer_keys(clear);
+  else d.verify_keys(clear);
+  if (!any) return hipSuccess;
+  const hipError_t f = hipStreamSynchronize(d.stream);
+  return e ? e : f;
+}
+// a remove: the slot cleared on every device, each made current under the registry's
+// lock, whatever the devices before it answered; the first HIP error
+int clear_slot_on_each_device(cordahip_ctx* ctx, Registry which, uint32_t slot) {
+  hipError_t e = hipSuccess;
+  for (auto& dp : ctx->devs) {
+    Device& d = *dp;
+    std::lock_guard<std::mutex> gd(which == Registry::kSigner ? d.sign_mu : d.vkey_mu);
+    const Activity act(d);
+    const hipError_t s = hipSetDevice(d.id);
+    const hipError_t z = s ? s : clear_slot(d, which, slot);
+    e = e ? e : z;
+  }
   return hip_err(e);
 }
 
 // ---- Ed25519 signing with registered keys (K11, ed25519_sign.hip) -------------
-// A key's record zeroed on one device (sign_mu held, device current): after every
-// signing kernel that may still read it; the stream is drained before return.
-hipError_t signer_zero_record(Device& d, uint32_t slot) {
-  if (!d.keys.tab.p && !d.ec_keys.tab.p) return hipSuccess;
-  hipError_t e = hipSuccess;
-  if (d.keys.tab.p) {
-    e = d.keys.ev.sync();
-    e = e ? e
-          : hipMemsetAsync(d.keys.tab.as<uint32_t>() + (size_t)slot * kSignRecWords, 0, kSignRecWords * 4, d.stream);
-  }
-  if (d.ec_keys.tab.p) {  // the slot's record of the other family (K17): one pool, one remove
-    EcSignKeys& k = d.ec_keys;
-    hipError_t x = k.ev.sync();
-    x = x ? x
-          : hipMemsetAsync(k.tab.as<uint32_t>() + kEcSignRecBase + (size_t)slot * kEcSignRecWords, 0,
-                           kEcSignRecWords * 4, d.stream);
-    e = e ? e : x;
-    if (k.scheme[slot]) k.live[k.scheme[slot] - 2]--;
-    k.scheme[slot] = 0;
-  }
-  const hipError_t f = hipStreamSynchronize(d.stream);
-  return e ? e : f;
-}
 
 // The seed expanded into the record of key_id's slot on one device (sign_mu held);
 // pub: the device's A. The seed crosses in the device's page-locked stage, wiped
@@ -125,7 +149,7 @@ int signer_add_impl(cordahip_ctx* ctx, const uint8_t seed[32], uint32_t* key_id,
       [&] { return std::memcmp(first, cur, 32) == 0; },
       [&](Device& d) {  // no device keeps a record of a key the caller never got
         if (!d.keys.tab.p) return;
-        (void)signer_zero_record(d, slot);
+        (void)clear_slot(d, Registry::kSigner, slot);
         (void)hipMemsetAsync(d.keys.tab.as<uint32_t>() + kSignSeedWord, 0, 32, d.stream);
         (void)hipStreamSynchronize(d.stream);
       });
@@ -143,7 +167,7 @@ int signer_remove_impl(cordahip_ctx* ctx, uint32_t key_id) {
   uint32_t slot;
   if (!reg.release(key_id, slot)) return CORDAHIP_ERR_INVALID_ARG;
   // the id is dead from here on, whatever a device answers below
-  const int rc = clear_on_each_device(ctx, &Device::sign_mu, [&](Device& d) { return signer_zero_record(d, slot); });
+  const int rc = clear_slot_on_each_device(ctx, Registry::kSigner, slot);
   if (tracing()) fprintf(stderr, "[cordahip] signer: key id %u removed (%u live)\n", key_id, reg.count);
   return rc;
 }
@@ -160,14 +184,13 @@ int ec_signer_add_on(Device& d, uint32_t scheme, const uint8_t key[32], uint32_t
   EcSignKeys& k = d.ec_keys;
   if (!k.tab.p) {
     if (k.tab.ensure(ecdsa_signtab_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-    k.comb[0] = k.comb[1] = k.live[0] = k.live[1] = 0;
-    std::memset(k.scheme, 0, sizeof k.scheme);
+    k.book = {};
     if (hipMemsetAsync(k.tab.as<uint32_t>() + kEcSignRecBase, 0, (size_t)(kEcSignAllWords - kEcSignRecBase) * 4,
                        d.stream) != hipSuccess)
       return CORDAHIP_ERR_HIP;
   }
   uint32_t* tab = k.tab.as<uint32_t>();
-  const bool build_comb = !k.comb[scheme - 2];  // marked built only once the stream has drained below
+  const bool build_comb = !k.book.table_built(scheme);  // marked built only once the stream has drained below
   if (build_comb && launch_ecdsa_sign_comb(tab, scheme, d.stream) != hipSuccess) return CORDAHIP_ERR_HIP;
   if (k.stage.ensure(128) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
   uint8_t* stage = k.stage.as<uint8_t>();
@@ -184,12 +207,8 @@ int ec_signer_add_on(Device& d, uint32_t scheme, const uint8_t key[32], uint32_t
     std::memcpy(&flag, stage + 32, 4);
     *taken = flag == 1u;
     std::memcpy(pub, stage + 32 + 16, 64);
-    if (build_comb) k.comb[scheme - 2] = 1;
-    if (*taken) {
-      const uint32_t slot = key_id & (kSignKeySlots - 1);
-      k.scheme[slot] = (uint8_t)scheme;
-      k.live[scheme - 2]++;
-    }
+    if (build_comb) k.book.mark_built(scheme);
+    if (*taken) k.book.take(key_id & (kSignKeySlots - 1), scheme);
   }
   return hip_err(e ? e : f);
 }
@@ -212,7 +231,7 @@ int ec_signer_add_impl(cordahip_ctx* ctx, uint32_t scheme, const uint8_t key[32]
       [&] { return cur == first && std::memcmp(pfirst, pcur, 64) == 0; },
       [&](Device& d) {  // no device keeps a record of a key the caller never got
         if (!d.ec_keys.tab.p) return;
-        (void)signer_zero_record(d, slot);
+        (void)clear_slot(d, Registry::kSigner, slot);
         (void)hipMemsetAsync(d.ec_keys.tab.as<uint32_t>() + kEcSignKeyWord, 0, 32, d.stream);
         (void)hipStreamSynchronize(d.stream);
       });
@@ -240,6 +259,38 @@ struct KeyedChunk {
   hipStream_t s;
 };
 
+// The prologue of a registered-key host call's shard on one device: the stage's lock,
+// held for the shard's run; the thread bound to the device's NUMA node; the run counted
+// as activity; the device current (ok: it is); the chunk size, CORDAHIP_HOST_CHUNK lanes
+// rounded up to `align`; the device's host pool.
+struct ShardRun {
+  std::lock_guard<std::mutex> g;
+  const NodeBind nb;
+  const Activity act;
+  const bool ok;
+  const uint64_t chunk;
+  HostPool& pool;
+  ShardRun(cordahip_ctx* ctx, Device& d, KeyedStage& st, uint64_t align)
+      : g(st.mu), nb(d), act(d), ok(hipSetDevice(d.id) == hipSuccess),
+        chunk((env_lanes("CORDAHIP_HOST_CHUNK", 1ull << 22) + align - 1) / align * align), pool(pool_of(ctx, d)) {}
+};
+
+// One round trip of packed rows through the stage on stream s: work() issues the copies
+// in, the kernel (under the key table's lock) and the call's own copies out; the `rows`
+// statuses follow, st.ev is recorded after that last copy and the host waits for it. On
+// any HIP error the stream is drained first -- no queued work outlives the call -- and
+// the answer is CORDAHIP_ERR_HIP.
+template <class Work>
+int round_trip(KeyedStage& st, uint64_t rows, hipStream_t s, Work work) {
+  hipError_t e = work();
+  e = e ? e : st.status.to_host(rows, s);
+  e = e ? e : st.ev.record(s);
+  e = e ? e : st.ev.sync();
+  if (e == hipSuccess) return CORDAHIP_SUCCESS;
+  (void)hipStreamSynchronize(s);
+  return CORDAHIP_ERR_HIP;
+}
+
 // A registered-key host call for lanes [lo, hi) on one device, a chunk of
 // CORDAHIP_HOST_CHUNK lanes (rounded up to `align`) at a time: the lanes packed into the
 // stage's page-locked buffers (dense 32-byte rows when every message of the chunk is 32
@@ -252,15 +303,11 @@ struct KeyedChunk {
 template <class Call>
 int keyed_chunks(cordahip_ctx* ctx, Device& d, KeyedStage& st, const uint64_t* msg_off, uint8_t* status, uint64_t lo,
                  uint64_t hi, uint64_t align, const char* what, Call call) {
-  std::lock_guard<std::mutex> g(st.mu);
-  const NodeBind nb(d);
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  const uint64_t chunk = (env_lanes("CORDAHIP_HOST_CHUNK", 1ull << 22) + align - 1) / align * align;
-  HostPool& pool = pool_of(ctx, d);
+  ShardRun run(ctx, d, st, align);
+  if (!run.ok) return CORDAHIP_ERR_HIP;
   std::vector<uint64_t> poff;
-  for (uint64_t a = lo; a < hi; a += chunk) {
-    const uint64_t m = std::min(chunk, hi - a);
+  for (uint64_t a = lo; a < hi; a += run.chunk) {
+    const uint64_t m = std::min(run.chunk, hi - a);
     const double t0 = now_ms();
     poff.resize(m);
     const KeyedChunk c{a, m, msg_chunk_layout(msg_off, a, m, poff.data()), poff.data(), d.stream};
@@ -269,22 +316,18 @@ int keyed_chunks(cordahip_ctx* ctx, Device& d, KeyedStage& st, const uint64_t* m
     if (st.ids.ensure(m * 4) || st.msgs.ensure(std::max<uint64_t>(bytes, 16)) || st.msg_off.ensure(m * 8) ||
         st.msg_len.ensure(m * 4) || st.status.ensure(m) || call.ensure(c))
       return CORDAHIP_ERR_OUT_OF_MEMORY;
-    pool.parallel_for(m, 1u << 14, [&](uint64_t x, uint64_t y) { call.pack(c, x, y); });
-    hipError_t e = st.ids.to_device(m * 4, c.s);
-    if (bytes) e = e ? e : st.msgs.to_device(bytes, c.s);
-    if (!c.lay.dense) {
-      e = e ? e : st.msg_off.to_device(m * 8, c.s);
-      e = e ? e : st.msg_len.to_device(m * 4, c.s);
-    }
-    e = e ? e : call.enqueue(c);
-    e = e ? e : call.fetch(c);
-    e = e ? e : st.status.to_host(m, c.s);
-    e = e ? e : st.ev.record(c.s);
-    e = e ? e : st.ev.sync();
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(c.s);  // no queued work outlives the call
-      return CORDAHIP_ERR_HIP;
-    }
+    run.pool.parallel_for(m, 1u << 14, [&](uint64_t x, uint64_t y) { call.pack(c, x, y); });
+    const int rc = round_trip(st, m, c.s, [&] {
+      hipError_t e = st.ids.to_device(m * 4, c.s);
+      if (bytes) e = e ? e : st.msgs.to_device(bytes, c.s);
+      if (!c.lay.dense) {
+        e = e ? e : st.msg_off.to_device(m * 8, c.s);
+        e = e ? e : st.msg_len.to_device(m * 4, c.s);
+      }
+      e = e ? e : call.enqueue(c);
+      return e ? e : call.fetch(c);
+    });
+    if (rc != CORDAHIP_SUCCESS) return rc;
     call.deliver(c);
     std::memcpy(status + a, st.status.h.p, m);
     if (tracing())
@@ -294,77 +337,53 @@ int keyed_chunks(cordahip_ctx* ctx, Device& d, KeyedStage& st, const uint64_t* m
   return CORDAHIP_SUCCESS;
 }
 
-// The keyed signer on stream s (sign_mu held, device current): behind the table's
-// previous user, followed by the table's fence. A device without a key table yet
-// passes none: every ungated lane is then UNKNOWN_KEY.
+// The keyed signers on stream s (sign_mu held, device current), each behind its table's
+// previous user and followed by the table's fence (fenced): Ed25519 (K11) and ECDSA
+// (K17). A device without the family's table yet passes none: every ungated lane is
+// then UNKNOWN_KEY.
 hipError_t sign_enqueue(Device& d, const uint32_t* key_id, const uint8_t* msgs, const uint64_t* moff,
                         const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* gate, uint8_t* sigs,
                         uint8_t* status, hipStream_t s) {
-  hipError_t e = d.keys.ev.wait(s);
-  e = e ? e
-        : launch_ed25519_sign_keyed(key_id, msgs, moff, mlen, msg_len, n, gate, d.keys.tab.as<uint32_t>(),
-                                    d.comb(), sigs, status, s);
-  return e ? e : d.keys.ev.record(s);
-}
-
-// cordahip_sign's part of a chunk (keyed_chunks): the gate bytes in, K11, the signature rows out.
-struct SignCall {
-  Device& d;
-  const cordahip_sign_batch* b;
-  KeyedStage& st;
-  bool ensure(const KeyedChunk& c) { return st.gate.ensure(c.m) || st.sig_rows.ensure(c.m * 64); }
-  void pack(const KeyedChunk& c, uint64_t x, uint64_t y) {
-    sign_pack_rows(b, c.a, x, y, c.lay, c.poff, st.ids.h.as<uint32_t>(), st.gate.h.as<uint8_t>(),
-                   st.msgs.h.as<uint8_t>(), st.msg_off.h.as<uint64_t>(), st.msg_len.h.as<uint32_t>());
-  }
-  hipError_t enqueue(const KeyedChunk& c) {
-    if (b->gate)
-      if (const hipError_t e = st.gate.to_device(c.m, c.s)) return e;
-    const bool dense = c.lay.dense;
-    std::lock_guard<std::mutex> gs(d.sign_mu);
-    return sign_enqueue(d, st.ids.d.as<uint32_t>(), st.msgs.d.as<uint8_t>(),
-                        dense ? nullptr : st.msg_off.d.as<uint64_t>(), dense ? nullptr : st.msg_len.d.as<uint32_t>(), 32,
-                        c.m, b->gate ? st.gate.d.as<uint8_t>() : nullptr, st.sig_rows.d.as<uint8_t>(),
-                        st.status.d.as<uint8_t>(), c.s);
-  }
-  hipError_t fetch(const KeyedChunk& c) { return st.sig_rows.to_host(c.m * 64, c.s); }
-  void deliver(const KeyedChunk& c) { std::memcpy(b->sig + c.a * 64, st.sig_rows.h.p, c.m * 64); }
-};
-
-int sign_impl(cordahip_ctx* ctx, const cordahip_sign_batch* b) {
-  const uint64_t n = b->n;
-  if (n == 0) return CORDAHIP_SUCCESS;
-  if (!b->key_id || !b->msg_off || !b->sig || !b->status) return CORDAHIP_ERR_INVALID_ARG;
-  if (!check_sign_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
-  if (b->msg_off[0] != b->msg_off[n] && !b->msg) return CORDAHIP_ERR_INVALID_ARG;
-  return for_shards(ctx->devs, n, 64, [&](Device& d, uint64_t lo, uint64_t hi) {
-    return keyed_chunks(ctx, d, d.sign_stage, b->msg_off, b->status, lo, hi, 1, "sign", SignCall{d, b, d.sign_stage});
+  return fenced({&d.keys.ev}, s, [&] {
+    return launch_ed25519_sign_keyed(key_id, msgs, moff, mlen, msg_len, n, gate, d.keys.tab.as<uint32_t>(), d.comb(),
+                                     sigs, status, s);
   });
 }
-
-// The ECDSA keyed signer on stream s (sign_mu held, device current): behind the ECDSA
-// table's previous user, followed by its fence. A device without that table passes
-// none: every ungated lane is then UNKNOWN_KEY.
 hipError_t ec_sign_enqueue(Device& d, const uint32_t* key_id, const uint8_t* msgs, const uint64_t* moff,
                            const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* gate, uint8_t* sigs,
                            uint8_t* sig_len, uint8_t* status, hipStream_t s) {
   const EcSignKeys& k = d.ec_keys;
-  const bool have = k.tab.p != nullptr;
-  hipError_t e = d.ec_keys.ev.wait(s);
-  e = e ? e
-        : launch_ecdsa_sign_keyed(key_id, msgs, moff, mlen, msg_len, n, gate, k.tab.as<uint32_t>(),
-                                  have && k.live[0] > 0, have && k.live[1] > 0, sigs, sig_len, status, s);
-  return e ? e : d.ec_keys.ev.record(s);
+  return fenced({&d.ec_keys.ev}, s, [&] {
+    return launch_ecdsa_sign_keyed(key_id, msgs, moff, mlen, msg_len, n, gate, k.tab.as<uint32_t>(),
+                                   k.book.has_live(CORDAHIP_SCHEME_ECDSA_SECP256K1_SHA256),
+                                   k.book.has_live(CORDAHIP_SCHEME_ECDSA_SECP256R1_SHA256), sigs, sig_len, status, s);
+  });
 }
 
-// cordahip_ecdsa_sign's part of a chunk (keyed_chunks): the gate bytes in, K17, the
-// 72-byte DER slots and their lengths out.
-struct EcSignCall {
+// What the two signing batches differ in: the signature row (64 bytes; a 72-byte DER
+// slot) and ECDSA's array of signature lengths (has_len; sig_len: the caller's).
+struct SignRows {
+  size_t row;
+  bool has_len;
+  uint8_t* sig_len;
+  const char* what;
+};
+inline SignRows sign_rows(const cordahip_sign_batch*) { return {64, false, nullptr, "sign"}; }
+inline SignRows sign_rows(const cordahip_ecdsa_sign_batch* b) {
+  return {kEcSignSigBytes, true, b->sig_len, "ECDSA sign"};
+}
+
+// A signing call's part of a chunk (keyed_chunks), B cordahip_sign_batch or
+// cordahip_ecdsa_sign_batch: the gate bytes in, K11 or K17, the signature rows -- and
+// ECDSA's lengths -- out.
+template <class B>
+struct SignCall {
   Device& d;
-  const cordahip_ecdsa_sign_batch* b;
+  const B* b;
   KeyedStage& st;
+  SignRows out;
   bool ensure(const KeyedChunk& c) {
-    return st.gate.ensure(c.m) || st.sig_rows.ensure(c.m * kEcSignSigBytes) || st.sig_len.ensure(c.m);
+    return st.gate.ensure(c.m) || st.sig_rows.ensure(c.m * out.row) || (out.has_len && st.sig_len.ensure(c.m));
   }
   void pack(const KeyedChunk& c, uint64_t x, uint64_t y) {
     sign_pack_rows(b, c.a, x, y, c.lay, c.poff, st.ids.h.as<uint32_t>(), st.gate.h.as<uint8_t>(),
@@ -373,70 +392,43 @@ struct EcSignCall {
   hipError_t enqueue(const KeyedChunk& c) {
     if (b->gate)
       if (const hipError_t e = st.gate.to_device(c.m, c.s)) return e;
-    const bool dense = c.lay.dense;
+    const uint32_t* ids = st.ids.d.as<uint32_t>();
+    const uint8_t *msgs = st.msgs.d.as<uint8_t>(), *gate = b->gate ? st.gate.d.as<uint8_t>() : nullptr;
+    const uint64_t* moff = c.lay.dense ? nullptr : st.msg_off.d.as<uint64_t>();
+    const uint32_t* mlen = c.lay.dense ? nullptr : st.msg_len.d.as<uint32_t>();
+    uint8_t *sigs = st.sig_rows.d.as<uint8_t>(), *status = st.status.d.as<uint8_t>();
     std::lock_guard<std::mutex> gs(d.sign_mu);
-    return ec_sign_enqueue(d, st.ids.d.as<uint32_t>(), st.msgs.d.as<uint8_t>(),
-                           dense ? nullptr : st.msg_off.d.as<uint64_t>(), dense ? nullptr : st.msg_len.d.as<uint32_t>(),
-                           32, c.m, b->gate ? st.gate.d.as<uint8_t>() : nullptr, st.sig_rows.d.as<uint8_t>(),
-                           st.sig_len.d.as<uint8_t>(), st.status.d.as<uint8_t>(), c.s);
+    return out.has_len
+               ? ec_sign_enqueue(d, ids, msgs, moff, mlen, 32, c.m, gate, sigs, st.sig_len.d.as<uint8_t>(), status, c.s)
+               : sign_enqueue(d, ids, msgs, moff, mlen, 32, c.m, gate, sigs, status, c.s);
   }
   hipError_t fetch(const KeyedChunk& c) {
-    const hipError_t e = st.sig_rows.to_host(c.m * kEcSignSigBytes, c.s);
-    return e ? e : st.sig_len.to_host(c.m, c.s);
+    const hipError_t e = st.sig_rows.to_host(c.m * out.row, c.s);
+    return e || !out.has_len ? e : st.sig_len.to_host(c.m, c.s);
   }
   void deliver(const KeyedChunk& c) {
-    std::memcpy(b->sig + c.a * kEcSignSigBytes, st.sig_rows.h.p, c.m * kEcSignSigBytes);
-    std::memcpy(b->sig_len + c.a, st.sig_len.h.p, c.m);
+    std::memcpy(b->sig + c.a * out.row, st.sig_rows.h.p, c.m * out.row);
+    if (out.has_len) std::memcpy(out.sig_len + c.a, st.sig_len.h.p, c.m);
   }
 };
 
-int ec_sign_impl(cordahip_ctx* ctx, const cordahip_ecdsa_sign_batch* b) {
+// cordahip_sign and cordahip_ecdsa_sign
+template <class B>
+int sign_impl(cordahip_ctx* ctx, const B* b) {
   const uint64_t n = b->n;
   if (n == 0) return CORDAHIP_SUCCESS;
-  if (!b->key_id || !b->msg_off || !b->sig || !b->sig_len || !b->status) return CORDAHIP_ERR_INVALID_ARG;
+  const SignRows out = sign_rows(b);
+  if (!b->key_id || !b->msg_off || !b->sig || !b->status || (out.has_len && !out.sig_len))
+    return CORDAHIP_ERR_INVALID_ARG;
   if (!check_sign_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
   if (b->msg_off[0] != b->msg_off[n] && !b->msg) return CORDAHIP_ERR_INVALID_ARG;
   return for_shards(ctx->devs, n, 64, [&](Device& d, uint64_t lo, uint64_t hi) {
-    return keyed_chunks(ctx, d, d.sign_stage, b->msg_off, b->status, lo, hi, 1, "ECDSA sign",
-                        EcSignCall{d, b, d.sign_stage});
+    return keyed_chunks(ctx, d, d.sign_stage, b->msg_off, b->status, lo, hi, 1, out.what,
+                        SignCall<B>{d, b, d.sign_stage, out});
   });
 }
 
 // ---- Ed25519 verification against registered keys (K12, ed25519_vkey.hip) --------
-// A key's record cleared on one device (vkey_mu held, device current): after every
-// keyed kernel that may still read it; the stream is drained before return. The
-// table's entries stay: without a record whose id matches, no lane reads them.
-hipError_t vkey_clear_record(Device& d, uint32_t slot) {
-  if (!d.vkeys.tab.p && !d.ec_vkeys.tab.p && !d.rsa_vkeys.tab.p) return hipSuccess;
-  hipError_t e = hipSuccess;
-  if (d.vkeys.tab.p) {
-    d.vkeys.live &= ~(1ull << slot);  // routed enqueues (K14) count the device's live Ed25519 keys
-    e = d.vkeys.ev.sync();
-    e = e ? e
-          : hipMemsetAsync(d.vkeys.tab.as<uint32_t>() + kVkeyRecBase + (size_t)slot * kVkeyRecWords, 0,
-                           kVkeyRecWords * 4, d.stream);
-  }
-  if (d.ec_vkeys.tab.p) {  // the slot's record of the other family (K13): one pool, one remove
-    hipError_t x = d.ec_vkeys.ev.sync();
-    x = x ? x
-          : hipMemsetAsync(d.ec_vkeys.tab.as<uint32_t>() + kEcVkeyRecBase + (size_t)slot * kEcVkeyRecWords, 0,
-                           kEcVkeyRecWords * 4, d.stream);
-    e = e ? e : x;
-    EcVkeyState& st = d.ec_vkeys.state;
-    if (st.scheme[slot]) st.live[st.scheme[slot] - 2]--;
-    st.scheme[slot] = 0;
-  }
-  if (d.rsa_vkeys.tab.p) {  // and of the RSA family (K18)
-    hipError_t x = d.rsa_vkeys.ev.sync();
-    x = x ? x
-          : hipMemsetAsync(d.rsa_vkeys.tab.as<uint8_t>() + (size_t)slot * sizeof(rsa::VkeyRecord), 0,
-                           sizeof(rsa::VkeyRecord), d.stream);
-    e = e ? e : x;
-  }
-  const hipError_t f = hipStreamSynchronize(d.stream);
-  return e ? e : f;
-}
-
 // The key's record and table built in key_id's slot on one device (vkey_mu held);
 // *decoded: whether the device took the bytes for a point.
 int vkey_build_on(Device& d, const uint8_t key[32], uint32_t key_id, bool* decoded) {
@@ -473,16 +465,16 @@ int vkey_build_on(Device& d, const uint8_t key[32], uint32_t key_id, bool* decod
 // SEC1 bytes for a point of the curve (BC ECCurve.decodePoint).
 int ec_vkey_build_on(Device& d, uint32_t scheme, const uint8_t* key, uint32_t key_len, uint32_t key_id, bool* decoded) {
   if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  EcVkeyState& st = d.ec_vkeys.state;
+  auto& book = d.ec_vkeys.book;
   if (!d.ec_vkeys.tab.p) {
     if (d.ec_vkeys.tab.ensure(ecdsa_vkey_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
-    st = EcVkeyState{};
+    book = {};
     if (hipMemsetAsync(d.ec_vkeys.tab.as<uint32_t>() + kEcVkeyRecBase, 0, (kEcVkeyAllWords - kEcVkeyRecBase) * 4,
                        d.stream) != hipSuccess)
       return CORDAHIP_ERR_HIP;
   }
   uint32_t* tab = d.ec_vkeys.tab.as<uint32_t>();
-  const bool build_base = !st.base[scheme - 2];  // marked built only once the stream has drained below
+  const bool build_base = !book.table_built(scheme);  // marked built only once the stream has drained below
   if (build_base && launch_ecdsa_vkey_build(tab, scheme, ec_vkey_base_slot(scheme), 0u, 0u, d.stream) != hipSuccess)
     return CORDAHIP_ERR_HIP;
   if (d.ec_vkeys.stage.ensure(128) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
@@ -498,11 +490,8 @@ int ec_vkey_build_on(Device& d, uint32_t scheme, const uint8_t* key, uint32_t ke
     uint32_t flag;
     std::memcpy(&flag, stage + 80, 4);
     *decoded = flag == 1u;
-    if (build_base) st.base[scheme - 2] = 1;
-    if (*decoded) {
-      st.scheme[vkey_slot(key_id)] = (uint8_t)scheme;
-      st.live[scheme - 2]++;
-    }
+    if (build_base) book.mark_built(scheme);
+    if (*decoded) book.take(vkey_slot(key_id), scheme);
   }
   return hip_err(e ? e : f);
 }
@@ -530,7 +519,7 @@ int vkey_add_impl(cordahip_ctx* ctx, uint32_t scheme, const uint8_t* key, uint32
         return r;
       },
       [&] { return cur == first; },
-      [&](Device& d) { (void)vkey_clear_record(d, slot); });  // no device keeps a record of a key the caller never got
+      [&](Device& d) { (void)clear_slot(d, Registry::kVerify, slot); });  // no device keeps a record of a key the caller never got
   if (rc != CORDAHIP_SUCCESS) return rc;
   if (!first) {
     *key_id = kVkeyNoId;
@@ -585,7 +574,7 @@ int rsa_vkey_add_impl(cordahip_ctx* ctx, const uint8_t* key, uint32_t key_len, u
   rec.id = id;
   const int rc = on_each_device(
       ctx, &Device::vkey_mu, [&](Device& d, size_t, bool&) { return rsa_vkey_put_on(d, rec); }, [] { return true; },
-      [&](Device& d) { (void)vkey_clear_record(d, slot); });  // no device keeps a record of a key the caller never got
+      [&](Device& d) { (void)clear_slot(d, Registry::kVerify, slot); });  // no device keeps a record of a key the caller never got
   if (rc != CORDAHIP_SUCCESS) return rc;
   {
     std::lock_guard<std::mutex> gm(ctx->rsa_mirror_mu);
@@ -609,39 +598,33 @@ int vkey_remove_impl(cordahip_ctx* ctx, uint32_t key_id) {
     ctx->rsa_mirror[slot] = {};
   }
   // the id is dead from here on, whatever a device answers below
-  const int rc = clear_on_each_device(ctx, &Device::vkey_mu, [&](Device& d) { return vkey_clear_record(d, slot); });
+  const int rc = clear_slot_on_each_device(ctx, Registry::kVerify, slot);
   if (tracing()) fprintf(stderr, "[cordahip] vkey: key id %u removed (%u live)\n", key_id, reg.count);
   return rc;
 }
 
-// The keyed verifier on stream s (vkey_mu held, device current): behind the tables'
-// previous user, followed by the tables' fence. A device without key tables yet
-// passes none: every lane is then UNKNOWN_KEY.
+// The keyed verifiers on stream s (vkey_mu held, device current), each behind its tables'
+// previous user and followed by the tables' fence (fenced): Ed25519 (K12) and ECDSA
+// (K13). A device without the family's tables yet passes none: every lane is then
+// UNKNOWN_KEY.
 hipError_t vkey_enqueue(Device& d, const uint32_t* key_id, const uint8_t* sigs, const uint8_t* msgs,
                         const uint64_t* moff, const uint32_t* mlen, uint32_t msg_len, uint64_t n, const uint8_t* pre,
                         uint32_t flags, uint8_t* status, unsigned long long* verdict, hipStream_t s) {
-  hipError_t e = d.vkeys.ev.wait(s);
-  e = e ? e
-        : launch_ed25519_verify_keyed(key_id, sigs, msgs, moff, mlen, msg_len, n, pre, flags,
-                                      d.vkeys.tab.as<uint32_t>(), status, verdict, s);
-  return e ? e : d.vkeys.ev.record(s);
+  return fenced({&d.vkeys.ev}, s, [&] {
+    return launch_ed25519_verify_keyed(key_id, sigs, msgs, moff, mlen, msg_len, n, pre, flags,
+                                       d.vkeys.tab.as<uint32_t>(), status, verdict, s);
+  });
 }
-
-// The ECDSA keyed verifier on stream s (vkey_mu held, device current): as vkey_enqueue,
-// behind the ECDSA tables' fence. A device without ECDSA tables passes none: every lane
-// is then UNKNOWN_KEY.
 hipError_t ec_vkey_enqueue(Device& d, const uint32_t* key_id, const uint8_t* sigs, const uint8_t* sig_len,
                            const uint8_t* msgs, const uint64_t* moff, const uint32_t* mlen, uint32_t msg_len,
                            uint64_t n, const uint8_t* pre, uint32_t flags, uint8_t* status,
                            unsigned long long* verdict, hipStream_t s) {
-  const EcVkeyState& st = d.ec_vkeys.state;
-  const bool have = d.ec_vkeys.tab.p != nullptr;
-  hipError_t e = d.ec_vkeys.ev.wait(s);
-  e = e ? e
-        : launch_ecdsa_verify_keyed(key_id, sigs, sig_len, msgs, moff, mlen, msg_len, n, pre, flags,
-                                    d.ec_vkeys.tab.as<uint32_t>(), have && st.live[0] > 0, have && st.live[1] > 0,
-                                    status, verdict, s);
-  return e ? e : d.ec_vkeys.ev.record(s);
+  const EcVerifyKeys& k = d.ec_vkeys;
+  return fenced({&d.ec_vkeys.ev}, s, [&] {
+    return launch_ecdsa_verify_keyed(key_id, sigs, sig_len, msgs, moff, mlen, msg_len, n, pre, flags,
+                                     k.tab.as<uint32_t>(), k.book.has_live(CORDAHIP_SCHEME_ECDSA_SECP256K1_SHA256),
+                                     k.book.has_live(CORDAHIP_SCHEME_ECDSA_SECP256R1_SHA256), status, verdict, s);
+  });
 }
 
 // The part of a chunk (keyed_chunks) of cordahip_verify_keyed (ec false: 64-byte
@@ -710,46 +693,40 @@ int ec_verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) {
 
 // The RSA keyed verifier on stream s (rsa_mu and vkey_mu held, device current, the RSA
 // workspace grown for the call: rsa_ws_grow): behind the workspace's and the RSA table's
-// previous users, followed by both fences. A device without an RSA table passes none:
-// every lane is then UNKNOWN_KEY.
+// previous users, followed by both fences (fenced). A device without an RSA table
+// passes none: every lane is then UNKNOWN_KEY.
 hipError_t rsa_vkey_enqueue(Device& d, const uint32_t* key_id, const uint8_t* sigs, const uint16_t* sig_len,
                             const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len, uint32_t W, uint64_t n,
                             uint32_t flags, uint8_t* status, unsigned long long* verdict, hipStream_t s) {
   RsaWork& w = d.rsa;
-  const size_t rb = rsa_ws_row_bytes(W);
-  hipError_t e = w.ev.wait(s);
-  e = e ? e : d.rsa_vkeys.ev.wait(s);
-  e = e ? e
-        : launch_rsa_verify_keyed(d.rsa_vkeys.tab.as<uint32_t>(), key_id, sigs, sig_len, msgs, msg_off, msg_len, W, n,
-                                  status, verdict, w.ws.as<uint8_t>(), w.ws.cap / rb / 64 * 64, flags, s);
-  const hipError_t r1 = w.ev.record(s), r2 = d.rsa_vkeys.ev.record(s);  // whatever was launched is fenced
-  return e ? e : r1 ? r1 : r2;
+  return fenced({&w.ev, &d.rsa_vkeys.ev}, s, [&] {
+    return launch_rsa_verify_keyed(d.rsa_vkeys.tab.as<uint32_t>(), key_id, sigs, sig_len, msgs, msg_off, msg_len, W, n,
+                                   status, verdict, w.ws.as<uint8_t>(), w.ws.cap / rsa_ws_row_bytes(W) / 64 * 64, flags,
+                                   s);
+  });
 }
 
 // cordahip_rsa_verify_keyed for lanes [lo, hi) on one device, a chunk of
 // CORDAHIP_HOST_CHUNK lanes at a time. A chunk's lanes are grouped by their key's width
 // class from the context's mirror of the registry (a lane whose id is not live there is
 // UNKNOWN_KEY now and is not sent); each class present runs over its rows only, in
-// launches of at most kRsaKeyedRows rows through the keyed stage -- key ids, signatures
-// right-sized to 4 W-byte slots, their lengths, the messages as a CSR of the launch's
-// rows -- and the statuses go back to their lanes. The stage is single: a launch's
-// statuses are read before the next one packs. rsa_mu is held for the run (the
-// workspace), outside the stage's lock; vkey_mu per launch.
+// launches of at most kRsaKeyedRows rows through the keyed stage (pack_rows.hpp
+// rsa_keyed_pack_rows, one round_trip each) and the statuses go back to their lanes.
+// The stage is single: a launch's statuses are read before the next one packs. rsa_mu
+// is held for the run (the workspace), outside the stage's lock; the workspace grows
+// before vkey_mu is taken, per launch. The verdict words come from the statuses at the
+// end of the shard (shards start at multiples of 64 lanes).
 constexpr uint64_t kRsaKeyedRows = 1ull << 15;
 int rsa_keyed_shard(cordahip_ctx* ctx, Device& d, const cordahip_keyed_sig_batch* b, uint64_t lo, uint64_t hi) {
   KeyedStage& st = d.vkey_stage;
   std::lock_guard<std::mutex> gr(d.rsa_mu);
-  std::lock_guard<std::mutex> g(st.mu);
-  const NodeBind nb(d);
-  const Activity act(d);
-  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
-  const uint64_t chunk = (env_lanes("CORDAHIP_HOST_CHUNK", 1ull << 22) + 63) / 64 * 64;
-  HostPool& pool = pool_of(ctx, d);
+  ShardRun run(ctx, d, st, 64);
+  if (!run.ok) return CORDAHIP_ERR_HIP;
   hipStream_t s = d.stream;
-  std::vector<uint64_t> cl[3], mo;  // lanes by class: 64, 96, 128 words
+  std::vector<uint64_t> cl[3];  // lanes by class: 64, 96, 128 words
   cordahip_ctx::RsaVkeyMirror mir[kVkeySlots];
-  for (uint64_t a = lo; a < hi; a += chunk) {
-    const uint64_t m = std::min(chunk, hi - a);
+  for (uint64_t a = lo; a < hi; a += run.chunk) {
+    const uint64_t m = std::min(run.chunk, hi - a);
     const double t0 = now_ms();
     {
       std::lock_guard<std::mutex> gm(ctx->rsa_mirror_mu);
@@ -767,51 +744,32 @@ int rsa_keyed_shard(cordahip_ctx* ctx, Device& d, const cordahip_keyed_sig_batch
       for (uint64_t r0 = 0; r0 < cl[c].size(); r0 += kRsaKeyedRows) {
         const uint64_t rows = std::min<uint64_t>(kRsaKeyedRows, cl[c].size() - r0);
         const uint64_t* lanes = cl[c].data() + r0;
-        mo.resize(rows + 1);
-        mo[0] = 0;
-        for (uint64_t r = 0; r < rows; r++) mo[r + 1] = mo[r] + (b->msg_off[lanes[r] + 1] - b->msg_off[lanes[r]]);
         // the previous launch has drained: growing frees nothing in use
+        if (st.msg_off.ensure((rows + 1) * 8)) return CORDAHIP_ERR_OUT_OF_MEMORY;
+        uint64_t* mo = st.msg_off.h.as<uint64_t>();
+        rsa_keyed_msg_offsets(b, lanes, rows, mo);
         if (st.ids.ensure(rows * 4) || st.sig_rows.ensure(rows * 4 * W) || st.sig_len.ensure(rows * 2) ||
-            st.msgs.ensure(std::max<uint64_t>(mo[rows], 16)) || st.msg_off.ensure((rows + 1) * 8) ||
-            st.status.ensure(rows))
+            st.msgs.ensure(std::max<uint64_t>(mo[rows], 16)) || st.status.ensure(rows))
           return CORDAHIP_ERR_OUT_OF_MEMORY;
-        std::memcpy(st.msg_off.h.p, mo.data(), (rows + 1) * 8);
-        pool.parallel_for(rows, 256, [&](uint64_t x, uint64_t y) {
-          for (uint64_t r = x; r < y; r++) {
-            const uint64_t i = lanes[r];
-            st.ids.h.as<uint32_t>()[r] = b->key_id[i];
-            // a signature longer than the slot is longer than the modulus: its length
-            // alone decides it (BAD_SIG), none of its bytes is sent
-            const uint64_t sl = b->sig_off[i + 1] - b->sig_off[i], fit = sl <= 4ull * W ? sl : 0;
-            uint8_t* row = st.sig_rows.h.as<uint8_t>() + r * 4ull * W;
-            if (fit) std::memcpy(row, b->sig + b->sig_off[i], fit);
-            std::memset(row + fit, 0, 4ull * W - fit);
-            st.sig_len.h.as<uint16_t>()[r] = (uint16_t)std::min<uint64_t>(sl, 4ull * W + 1);
-            if (mo[r + 1] != mo[r]) std::memcpy(st.msgs.h.as<uint8_t>() + mo[r], b->msg + b->msg_off[i], mo[r + 1] - mo[r]);
-          }
+        run.pool.parallel_for(rows, 256, [&](uint64_t x, uint64_t y) {
+          rsa_keyed_pack_rows(b, lanes, W, mo, x, y, st.ids.h.as<uint32_t>(), st.sig_rows.h.as<uint8_t>(),
+                              st.sig_len.h.as<uint16_t>(), st.msgs.h.as<uint8_t>());
         });
-        hipError_t e = st.ids.to_device(rows * 4, s);
-        e = e ? e : st.sig_rows.to_device(rows * 4 * W, s);
-        e = e ? e : st.sig_len.to_device(rows * 2, s);
-        if (mo[rows]) e = e ? e : st.msgs.to_device(mo[rows], s);
-        e = e ? e : st.msg_off.to_device((rows + 1) * 8, s);
-        if (e == hipSuccess && (e = rsa_ws_grow(d, W, rows)) == hipErrorOutOfMemory) {
-          (void)hipStreamSynchronize(s);
-          return CORDAHIP_ERR_OUT_OF_MEMORY;
-        }
-        if (e == hipSuccess) {
+        bool oom = false;
+        const int rc = round_trip(st, rows, s, [&] {
+          hipError_t e = st.ids.to_device(rows * 4, s);
+          e = e ? e : st.sig_rows.to_device(rows * 4 * W, s);
+          e = e ? e : st.sig_len.to_device(rows * 2, s);
+          if (mo[rows]) e = e ? e : st.msgs.to_device(mo[rows], s);
+          e = e ? e : st.msg_off.to_device((rows + 1) * 8, s);
+          if (e == hipSuccess) oom = (e = rsa_ws_grow(d, W, rows)) == hipErrorOutOfMemory;
+          if (e) return e;
           std::lock_guard<std::mutex> gv(d.vkey_mu);
-          e = rsa_vkey_enqueue(d, st.ids.d.as<uint32_t>(), st.sig_rows.d.as<uint8_t>(), st.sig_len.d.as<uint16_t>(),
-                               st.msgs.d.as<uint8_t>(), st.msg_off.d.as<uint64_t>(), 0, W, rows, b->flags,
-                               st.status.d.as<uint8_t>(), nullptr, s);
-        }
-        e = e ? e : st.status.to_host(rows, s);
-        e = e ? e : st.ev.record(s);
-        e = e ? e : st.ev.sync();
-        if (e != hipSuccess) {
-          (void)hipStreamSynchronize(s);  // no queued work outlives the call
-          return CORDAHIP_ERR_HIP;
-        }
+          return rsa_vkey_enqueue(d, st.ids.d.as<uint32_t>(), st.sig_rows.d.as<uint8_t>(), st.sig_len.d.as<uint16_t>(),
+                                  st.msgs.d.as<uint8_t>(), st.msg_off.d.as<uint64_t>(), 0, W, rows, b->flags,
+                                  st.status.d.as<uint8_t>(), nullptr, s);
+        });
+        if (rc != CORDAHIP_SUCCESS) return oom ? CORDAHIP_ERR_OUT_OF_MEMORY : rc;
         const uint8_t* hs = st.status.h.as<uint8_t>();
         for (uint64_t r = 0; r < rows; r++) b->status[lanes[r]] = hs[r];
       }
@@ -833,20 +791,41 @@ int rsa_verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) 
 }
 
 // A device's cumulative counters of routed lanes: route_tot of the family's key table
-// (K14: d.vkeys, K15: d.ec_vkeys), written by kernels the table's fence follows.
+// `keys` (K14: Device::vkeys, K15: Device::ec_vkeys), written by kernels the table's
+// fence follows.
 template <class Keys>
-int route_stats(Device& d, const Keys& keys, uint64_t* keyed_lanes, uint64_t* generic_lanes) {
-  std::lock_guard<std::mutex> g(d.vkey_mu);
-  uint64_t tot[2] = {0, 0};
-  if (keys.route_tot.p) {  // else: no routed enqueue of this family on this device yet
-    // every routed enqueue's partition pass is followed by the table's fence
-    if (hipSetDevice(d.id) != hipSuccess || keys.ev.sync() != hipSuccess ||
-        hipMemcpy(tot, keys.route_tot.p, sizeof tot, hipMemcpyDeviceToHost) != hipSuccess)
-      return CORDAHIP_ERR_HIP;
-  }
-  *keyed_lanes = tot[0];
-  *generic_lanes = tot[1];
+int route_stats(cordahip_ctx* ctx, int device, Keys Device::*keys, uint64_t* keyed_lanes, uint64_t* generic_lanes) {
+  Device* d = dev_at(ctx, device);
+  if (!d || !keyed_lanes || !generic_lanes) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    const Keys& k = d->*keys;
+    std::lock_guard<std::mutex> g(d->vkey_mu);
+    uint64_t tot[2] = {0, 0};
+    if (k.route_tot.p) {  // else: no routed enqueue of this family on this device yet
+      // every routed enqueue's partition pass is followed by the table's fence
+      if (hipSetDevice(d->id) != hipSuccess || k.ev.sync() != hipSuccess ||
+          hipMemcpy(tot, k.route_tot.p, sizeof tot, hipMemcpyDeviceToHost) != hipSuccess)
+        return CORDAHIP_ERR_HIP;
+    }
+    *keyed_lanes = tot[0];
+    *generic_lanes = tot[1];
+    return CORDAHIP_SUCCESS;
+  });
+}
+// a family's routing switch (Device::route_on, Device::ec_route_on) on every device
+int set_routing(cordahip_ctx* ctx, std::atomic<uint32_t> Device::*sw, uint32_t on) {
+  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
+  for (auto& dp : ctx->devs) ((*dp).*sw).store(on ? 1u : 0u);
   return CORDAHIP_SUCCESS;
+}
+
+// a *_keyed_device entry point that needs one lock: device_call under `mu`, guarded
+template <class F>
+int locked_device_call(Device& d, std::mutex& mu, void* hip_stream, F&& enqueue) {
+  return guarded([&]() -> int {
+    std::lock_guard<std::mutex> g(mu);
+    return device_call(d, hip_stream, enqueue);
+  });
 }
 
 }  // namespace
@@ -869,7 +848,7 @@ int cordahip_sign(cordahip_ctx* ctx, const cordahip_sign_batch* batch) {
 }
 
 int cordahip_sign_submit(cordahip_ctx* ctx, const cordahip_sign_batch* batch, uint64_t* ticket) {
-  return submit(ctx, ticket, sign_impl, batch);
+  return submit(ctx, ticket, sign_impl<cordahip_sign_batch>, batch);
 }
 
 int cordahip_ed25519_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
@@ -877,16 +856,11 @@ int cordahip_ed25519_sign_keyed_device(cordahip_ctx* ctx, int device, const void
                                        void* d_status, void* hip_stream) {
   Device* d = dev_at(ctx, device);
   if (!d || (n && (!d_key_id || !d_sigs || !d_status || (msg_len && !d_msgs)))) return CORDAHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_sigs) & 15) || (reinterpret_cast<uintptr_t>(d_key_id) & 3) ||
-      (msg_len == 32 && (reinterpret_cast<uintptr_t>(d_msgs) & 15)))
+  if (misaligned(d_sigs, 16) || misaligned(d_key_id, 4) || (msg_len == 32 && misaligned(d_msgs, 16)))
     return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&]() -> int {
-    std::lock_guard<std::mutex> g(d->sign_mu);
-    return device_call(*d, hip_stream, [&](hipStream_t s) {
-      return sign_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_msgs), nullptr,
-                          nullptr, msg_len, n, static_cast<const uint8_t*>(d_gate), static_cast<uint8_t*>(d_sigs),
-                          static_cast<uint8_t*>(d_status), s);
-    });
+  return locked_device_call(*d, d->sign_mu, hip_stream, [&](hipStream_t s) {
+    return sign_enqueue(*d, ptr<uint32_t>(d_key_id), ptr<uint8_t>(d_msgs), nullptr, nullptr, msg_len, n,
+                        ptr<uint8_t>(d_gate), ptr<uint8_t>(d_sigs), ptr<uint8_t>(d_status), s);
   });
 }
 
@@ -900,11 +874,11 @@ int cordahip_signer_add_ecdsa(cordahip_ctx* ctx, uint32_t scheme, const uint8_t 
 
 int cordahip_ecdsa_sign(cordahip_ctx* ctx, const cordahip_ecdsa_sign_batch* batch) {
   if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return ec_sign_impl(ctx, batch); });
+  return guarded([&] { return sign_impl(ctx, batch); });
 }
 
 int cordahip_ecdsa_sign_submit(cordahip_ctx* ctx, const cordahip_ecdsa_sign_batch* batch, uint64_t* ticket) {
-  return submit(ctx, ticket, ec_sign_impl, batch);
+  return submit(ctx, ticket, sign_impl<cordahip_ecdsa_sign_batch>, batch);
 }
 
 int cordahip_ecdsa_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
@@ -913,15 +887,11 @@ int cordahip_ecdsa_sign_keyed_device(cordahip_ctx* ctx, int device, const void* 
   Device* d = dev_at(ctx, device);
   if (!d || (n && (!d_key_id || !d_sigs || !d_sig_len || !d_status || (msg_len && !d_msgs))))
     return CORDAHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_sigs) & 3) || (reinterpret_cast<uintptr_t>(d_key_id) & 3))
-    return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&]() -> int {
-    std::lock_guard<std::mutex> g(d->sign_mu);
-    return device_call(*d, hip_stream, [&](hipStream_t s) {
-      return ec_sign_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_msgs), nullptr,
-                             nullptr, msg_len, n, static_cast<const uint8_t*>(d_gate), static_cast<uint8_t*>(d_sigs),
-                             static_cast<uint8_t*>(d_sig_len), static_cast<uint8_t*>(d_status), s);
-    });
+  if (misaligned(d_sigs, 4) || misaligned(d_key_id, 4)) return CORDAHIP_ERR_INVALID_ARG;
+  return locked_device_call(*d, d->sign_mu, hip_stream, [&](hipStream_t s) {
+    return ec_sign_enqueue(*d, ptr<uint32_t>(d_key_id), ptr<uint8_t>(d_msgs), nullptr, nullptr, msg_len, n,
+                           ptr<uint8_t>(d_gate), ptr<uint8_t>(d_sigs), ptr<uint8_t>(d_sig_len),
+                           ptr<uint8_t>(d_status), s);
   });
 }
 
@@ -943,28 +913,18 @@ int cordahip_vkey_remove(cordahip_ctx* ctx, uint32_t key_id) {
   return guarded([&] { return vkey_remove_impl(ctx, key_id); });
 }
 
-int cordahip_vkey_set_routing(cordahip_ctx* ctx, uint32_t on) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  for (auto& dp : ctx->devs) dp->route_on.store(on ? 1u : 0u);
-  return CORDAHIP_SUCCESS;
-}
+int cordahip_vkey_set_routing(cordahip_ctx* ctx, uint32_t on) { return set_routing(ctx, &Device::route_on, on); }
 
 int cordahip_vkey_route_stats(cordahip_ctx* ctx, int device, uint64_t* keyed_lanes, uint64_t* generic_lanes) {
-  Device* d = dev_at(ctx, device);
-  if (!d || !keyed_lanes || !generic_lanes) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return route_stats(*d, d->vkeys, keyed_lanes, generic_lanes); });
+  return route_stats(ctx, device, &Device::vkeys, keyed_lanes, generic_lanes);
 }
 
 int cordahip_vkey_set_routing_ecdsa(cordahip_ctx* ctx, uint32_t on) {
-  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
-  for (auto& dp : ctx->devs) dp->ec_route_on.store(on ? 1u : 0u);
-  return CORDAHIP_SUCCESS;
+  return set_routing(ctx, &Device::ec_route_on, on);
 }
 
 int cordahip_vkey_route_stats_ecdsa(cordahip_ctx* ctx, int device, uint64_t* keyed_lanes, uint64_t* generic_lanes) {
-  Device* d = dev_at(ctx, device);
-  if (!d || !keyed_lanes || !generic_lanes) return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&] { return route_stats(*d, d->ec_vkeys, keyed_lanes, generic_lanes); });
+  return route_stats(ctx, device, &Device::ec_vkeys, keyed_lanes, generic_lanes);
 }
 
 int cordahip_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch) {
@@ -981,16 +941,12 @@ int cordahip_ed25519_verify_keyed_device(cordahip_ctx* ctx, int device, const vo
                                          void* d_verdict, void* hip_stream) {
   Device* d = dev_at(ctx, device);
   if (!d || (n && (!d_key_id || !d_sigs || !d_status || (msg_len && !d_msgs)))) return CORDAHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_sigs) & 15) || (reinterpret_cast<uintptr_t>(d_key_id) & 3) ||
-      (reinterpret_cast<uintptr_t>(d_verdict) & 7) || (msg_len == 32 && (reinterpret_cast<uintptr_t>(d_msgs) & 15)))
+  if (misaligned(d_sigs, 16) || misaligned(d_key_id, 4) || misaligned(d_verdict, 8) ||
+      (msg_len == 32 && misaligned(d_msgs, 16)))
     return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&]() -> int {
-    std::lock_guard<std::mutex> g(d->vkey_mu);
-    return device_call(*d, hip_stream, [&](hipStream_t s) {
-      return vkey_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_sigs),
-                          static_cast<const uint8_t*>(d_msgs), nullptr, nullptr, msg_len, n, nullptr, 0u,
-                          static_cast<uint8_t*>(d_status), static_cast<unsigned long long*>(d_verdict), s);
-    });
+  return locked_device_call(*d, d->vkey_mu, hip_stream, [&](hipStream_t s) {
+    return vkey_enqueue(*d, ptr<uint32_t>(d_key_id), ptr<uint8_t>(d_sigs), ptr<uint8_t>(d_msgs), nullptr, nullptr,
+                        msg_len, n, nullptr, 0u, ptr<uint8_t>(d_status), ptr<unsigned long long>(d_verdict), s);
   });
 }
 
@@ -1009,16 +965,11 @@ int cordahip_ecdsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void
   Device* d = dev_at(ctx, device);
   if (!d || (n && (!d_key_id || !d_sigs || !d_sig_len || !d_status || (msg_len && !d_msgs))))
     return CORDAHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_key_id) & 3) || (reinterpret_cast<uintptr_t>(d_verdict) & 7))
-    return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&]() -> int {
-    std::lock_guard<std::mutex> g(d->vkey_mu);
-    return device_call(*d, hip_stream, [&](hipStream_t s) {
-      return ec_vkey_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_sigs),
-                             static_cast<const uint8_t*>(d_sig_len), static_cast<const uint8_t*>(d_msgs), nullptr,
-                             nullptr, msg_len, n, nullptr, 0u, static_cast<uint8_t*>(d_status),
-                             static_cast<unsigned long long*>(d_verdict), s);
-    });
+  if (misaligned(d_key_id, 4) || misaligned(d_verdict, 8)) return CORDAHIP_ERR_INVALID_ARG;
+  return locked_device_call(*d, d->vkey_mu, hip_stream, [&](hipStream_t s) {
+    return ec_vkey_enqueue(*d, ptr<uint32_t>(d_key_id), ptr<uint8_t>(d_sigs), ptr<uint8_t>(d_sig_len),
+                           ptr<uint8_t>(d_msgs), nullptr, nullptr, msg_len, n, nullptr, 0u, ptr<uint8_t>(d_status),
+                           ptr<unsigned long long>(d_verdict), s);
   });
 }
 
@@ -1044,8 +995,7 @@ int cordahip_rsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void* 
   if (!d || (mod_words != 64 && mod_words != 96 && mod_words != 128) ||
       (n && (!d_key_id || !d_sigs || !d_sig_len || !d_status || (msg_len && !d_msgs))))
     return CORDAHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_key_id) & 3) || (reinterpret_cast<uintptr_t>(d_sig_len) & 1) ||
-      (reinterpret_cast<uintptr_t>(d_verdict) & 7))
+  if (misaligned(d_key_id, 4) || misaligned(d_sig_len, 2) || misaligned(d_verdict, 8))
     return CORDAHIP_ERR_INVALID_ARG;
   return guarded([&]() -> int {
     std::lock_guard<std::mutex> g(d->rsa_mu);
@@ -1053,10 +1003,9 @@ int cordahip_rsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void* 
         *d, hip_stream, [&] { return rsa_ws_grow(*d, mod_words, n); },
         [&](hipStream_t s) {
           std::lock_guard<std::mutex> gv(d->vkey_mu);
-          return rsa_vkey_enqueue(*d, static_cast<const uint32_t*>(d_key_id), static_cast<const uint8_t*>(d_sigs),
-                                  static_cast<const uint16_t*>(d_sig_len), static_cast<const uint8_t*>(d_msgs),
-                                  nullptr, msg_len, mod_words, n, 0u, static_cast<uint8_t*>(d_status),
-                                  static_cast<unsigned long long*>(d_verdict), s);
+          return rsa_vkey_enqueue(*d, ptr<uint32_t>(d_key_id), ptr<uint8_t>(d_sigs), ptr<uint16_t>(d_sig_len),
+                                  ptr<uint8_t>(d_msgs), nullptr, msg_len, mod_words, n, 0u, ptr<uint8_t>(d_status),
+                                  ptr<unsigned long long>(d_verdict), s);
         });
   });
 }
@@ -1066,18 +1015,12 @@ int cordahip_rsa_public_op_keyed_device(cordahip_ctx* ctx, int device, const voi
   Device* d = dev_at(ctx, device);
   if (!d || (mod_words != 64 && mod_words != 96 && mod_words != 128) || (n && (!d_key_id || !d_in || !d_out)))
     return CORDAHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_key_id) | reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3)
-    return CORDAHIP_ERR_INVALID_ARG;
-  return guarded([&]() -> int {
-    std::lock_guard<std::mutex> g(d->vkey_mu);  // no workspace: the table's lock and fence alone
-    return device_call(*d, hip_stream, [&](hipStream_t s) {
-      hipError_t e = d->rsa_vkeys.ev.wait(s);
-      e = e ? e
-            : launch_rsa_public_op_keyed(d->rsa_vkeys.tab.as<uint32_t>(), static_cast<const uint32_t*>(d_key_id),
-                                         static_cast<const uint32_t*>(d_in), mod_words, n,
-                                         static_cast<uint32_t*>(d_out), s);
-      const hipError_t r = d->rsa_vkeys.ev.record(s);
-      return e ? e : r;
+  if (misaligned(d_key_id, 4) || misaligned(d_in, 4) || misaligned(d_out, 4)) return CORDAHIP_ERR_INVALID_ARG;
+  // no workspace: the table's lock and fence alone
+  return locked_device_call(*d, d->vkey_mu, hip_stream, [&](hipStream_t s) {
+    return fenced({&d->rsa_vkeys.ev}, s, [&] {
+      return launch_rsa_public_op_keyed(d->rsa_vkeys.tab.as<uint32_t>(), ptr<uint32_t>(d_key_id),
+                                        ptr<uint32_t>(d_in), mod_words, n, ptr<uint32_t>(d_out), s);
     });
   });
 }

@@ -262,5 +262,34 @@ inline void keyed_ec_pack_rows(const cordahip_keyed_sig_batch* b, uint64_t a, ui
   }
 }
 
+// ---- cordahip_rsa_verify_keyed launches (a batch that passed check_keyed_sig_batch) ----
+// A launch is `rows` lanes of one width class W (64, 96 or 128 words), lanes[r] the
+// batch's lane of row r. Its messages go out as a CSR of its rows: mo[rows + 1], the
+// prefix of the lanes' message lengths from 0.
+inline void rsa_keyed_msg_offsets(const cordahip_keyed_sig_batch* b, const uint64_t* lanes, uint64_t rows,
+                                  uint64_t* mo) {
+  mo[0] = 0;
+  for (uint64_t r = 0; r < rows; r++) mo[r + 1] = mo[r] + (b->msg_off[lanes[r] + 1] - b->msg_off[lanes[r]]);
+}
+// Rows [x, y) of the launch: key ids, the signatures right-sized to zero-padded 4 W-byte
+// slots with their lengths clamped to 4 W + 1, and each message at its CSR offset. A
+// signature longer than the slot is longer than the modulus: its length alone decides
+// it (BAD_SIG), none of its bytes is sent.
+inline void rsa_keyed_pack_rows(const cordahip_keyed_sig_batch* b, const uint64_t* lanes, uint32_t W,
+                                const uint64_t* mo, uint64_t x, uint64_t y, uint32_t* hid, uint8_t* hsig,
+                                uint16_t* hsl, uint8_t* hm) {
+  const uint64_t slot = 4ull * W;
+  for (uint64_t r = x; r < y; r++) {
+    const uint64_t i = lanes[r];
+    hid[r] = b->key_id[i];
+    const uint64_t sl = b->sig_off[i + 1] - b->sig_off[i], fit = sl <= slot ? sl : 0;
+    uint8_t* row = hsig + r * slot;
+    if (fit) std::memcpy(row, b->sig + b->sig_off[i], fit);
+    std::memset(row + fit, 0, slot - fit);
+    hsl[r] = (uint16_t)std::min<uint64_t>(sl, slot + 1);
+    if (mo[r + 1] != mo[r]) std::memcpy(hm + mo[r], b->msg + b->msg_off[i], mo[r + 1] - mo[r]);
+  }
+}
+
 }  // namespace rt
 }  // namespace cordahip

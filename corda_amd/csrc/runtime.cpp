@@ -12,7 +12,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "ecdsa_sign_core.hpp"
 #include "runtime.hpp"
 
 using namespace cordahip;
@@ -243,8 +242,8 @@ static hipError_t ec_route_and_keyed(Device& d, EcWork& w, const uint8_t* scheme
                                      const uint8_t* pre, uint8_t* status, uint32_t flags, hipStream_t s,
                                      bool* routed) {
   std::lock_guard<std::mutex> vk(d.vkey_mu);
-  const EcVkeyState& st = d.ec_vkeys.state;
-  if (!d.ec_vkeys.tab.p || !(st.live[0] || st.live[1])) return hipSuccess;
+  const auto& book = d.ec_vkeys.book;
+  if (!d.ec_vkeys.tab.p || !book.any_live()) return hipSuccess;
   if (!d.ec_vkeys.route_tot.p) {  // the device's first routed ECDSA enqueue
     if (d.ec_vkeys.route_tot.ensure(16) != hipSuccess) {
       (void)hipGetLastError();
@@ -255,16 +254,16 @@ static hipError_t ec_route_and_keyed(Device& d, EcWork& w, const uint8_t* scheme
   }
   *routed = true;
   const uint32_t* vtab = d.ec_vkeys.tab.as<uint32_t>();
-  hipError_t e = d.ec_vkeys.ev.wait(s);
-  e = e ? e
-        : launch_ecdsa_route(scheme, keys, key_len, n, vtab, w.route.as<uint32_t>(), w.counters.as<unsigned int>(),
-                             w.perm.as<unsigned int>(), d.ec_vkeys.route_tot.as<unsigned long long>(), s);
-  e = e ? e
-        : launch_ecdsa_verify_keyed_idx(w.route.as<uint32_t>(), w.perm.as<unsigned int>(),
-                                        w.counters.as<unsigned int>(), n, sigs, sig_len, msgs, msg_off, msg_len, pre,
-                                        flags, vtab, st.live[0] > 0, st.live[1] > 0, status, s);
-  const hipError_t r = d.ec_vkeys.ev.record(s);  // whatever was launched is fenced, also after a failure
-  return e ? e : r;
+  return fenced({&d.ec_vkeys.ev}, s, [&] {
+    const hipError_t e =
+        launch_ecdsa_route(scheme, keys, key_len, n, vtab, w.route.as<uint32_t>(), w.counters.as<unsigned int>(),
+                           w.perm.as<unsigned int>(), d.ec_vkeys.route_tot.as<unsigned long long>(), s);
+    return e ? e
+             : launch_ecdsa_verify_keyed_idx(w.route.as<uint32_t>(), w.perm.as<unsigned int>(),
+                                             w.counters.as<unsigned int>(), n, sigs, sig_len, msgs, msg_off, msg_len,
+                                             pre, flags, vtab, book.has_live(CORDAHIP_SCHEME_ECDSA_SECP256K1_SHA256),
+                                             book.has_live(CORDAHIP_SCHEME_ECDSA_SECP256R1_SHA256), status, s);
+  });
 }
 
 // Enqueue ECDSA verification of n slot-layout lanes on stream s (device current,
@@ -283,7 +282,7 @@ hipError_t ec_verify_enqueue(Device& d, const uint8_t* scheme, const uint8_t* ke
   bool want_route = d.ec_route_on.load(std::memory_order_relaxed) && n && n <= ecdsa_route_max_lanes();
   if (want_route) {  // a look at the registry; decided for good in ec_route_and_keyed
     std::lock_guard<std::mutex> vk(d.vkey_mu);
-    want_route = d.ec_vkeys.tab.p && (d.ec_vkeys.state.live[0] || d.ec_vkeys.state.live[1]);
+    want_route = d.ec_vkeys.tab.p && d.ec_vkeys.book.any_live();
   }
   // the scratch grows in powers of two from a floor, behind the workspace's fence; no
   // room for it: the batch is verified unrouted
@@ -405,13 +404,14 @@ static hipError_t ed_route_and_keyed(Device& d, DevBuf& sc, const uint8_t* keys,
   }
   *routed = true;
   const uint32_t* vtab = d.vkeys.tab.as<uint32_t>();
-  hipError_t e = d.vkeys.ev.wait(s);
-  e = e ? e : launch_ed25519_route(keys, n, vtab, sc.as<uint32_t>(), d.vkeys.route_tot.as<unsigned long long>(), s);
-  // the split-prep callers' messages: route and partition needed only the keys
-  if (e == hipSuccess && before_msgs) e = (*before_msgs)();
-  e = e ? e : launch_ed25519_verify_keyed_idx(sc.as<uint32_t>(), n, sigs, msgs, msg_len, pre, flags, vtab, status, s);
-  const hipError_t r = d.vkeys.ev.record(s);  // whatever was launched is fenced, also after a failure
-  return e ? e : r;
+  return fenced({&d.vkeys.ev}, s, [&] {
+    hipError_t e =
+        launch_ed25519_route(keys, n, vtab, sc.as<uint32_t>(), d.vkeys.route_tot.as<unsigned long long>(), s);
+    // the split-prep callers' messages: route and partition needed only the keys
+    if (e == hipSuccess && before_msgs) e = (*before_msgs)();
+    return e ? e
+             : launch_ed25519_verify_keyed_idx(sc.as<uint32_t>(), n, sigs, msgs, msg_len, pre, flags, vtab, status, s);
+  });
 }
 
 // Enqueue Ed25519 verification of n dense lanes on stream s (device already current).
@@ -551,19 +551,15 @@ void signer_wipe(cordahip_ctx* ctx) {
   for (auto& dp : ctx->devs) {
     Device& d = *dp;
     std::lock_guard<std::mutex> g(d.sign_mu);
-    if ((!d.keys.tab.p && !d.ec_keys.tab.p) || hipSetDevice(d.id) != hipSuccess) continue;
-    if (d.keys.tab.p) {
-      (void)d.keys.ev.sync();
-      (void)hipMemsetAsync(d.keys.tab.p, 0, d.keys.tab.cap, d.stream);
-    }
-    if (d.ec_keys.tab.p) {  // the ECDSA records (K17); the comb tables behind them are public
-      (void)d.ec_keys.ev.sync();
-      (void)hipMemsetAsync(d.ec_keys.tab.as<uint32_t>() + kEcSignRecBase, 0,
-                           (size_t)(kEcSignAllWords - kEcSignRecBase) * 4, d.stream);
-      std::memset(d.ec_keys.live, 0, sizeof d.ec_keys.live);
-      std::memset(d.ec_keys.scheme, 0, sizeof d.ec_keys.scheme);
-    }
-    (void)hipStreamSynchronize(d.stream);
+    bool any = false;
+    d.signer_keys([&](auto& k) {  // each family's secret bytes (KeyTable), behind its fence
+      if (!k.tab.p || hipSetDevice(d.id) != hipSuccess) return;
+      any = true;
+      (void)k.ev.sync();
+      const TabSpan z = k.secrets();
+      (void)hipMemsetAsync(k.tab.template as<uint8_t>() + z.at, 0, z.bytes, d.stream);
+    });
+    if (any) (void)hipStreamSynchronize(d.stream);
   }
 }
 

@@ -16,6 +16,7 @@
 #include <deque>
 #include <functional>
 #include <future>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -347,6 +348,21 @@ struct Fence {
     return e ? e : ensure();
   }
 };
+// The bracket of every launch that uses what the fences `fs` guard (the owner's lock
+// held): s waits for each fence's previous user, then `launch` -- if the waits
+// succeeded -- and each fence is recorded on s whatever the launch answered, so what
+// was launched is fenced also after a failure. The first error.
+template <class L>
+hipError_t fenced(std::initializer_list<Fence*> fs, hipStream_t s, L&& launch) {
+  hipError_t e = hipSuccess;
+  for (Fence* f : fs) e = e ? e : f->wait(s);
+  e = e ? e : launch();
+  for (Fence* f : fs) {
+    const hipError_t r = f->record(s);
+    e = e ? e : r;
+  }
+  return e;
+}
 
 // What a struct below owns, it names once: its visit(v) passes every such member to
 // one of these. A visitor derives from Visitor and redefines what it acts on; events,
@@ -522,10 +538,20 @@ struct RsaWork {
 // (Device::visit leaves it out; Device::visit_keys is for bind and ~Device), so nobody
 // loses registered keys to an idle timer. ev: the fence of the kernels that read the
 // table. stage: page-locked bytes a key goes out and its answer comes back in.
+// A family derives from it and says how a slot of it is cleared (keyed.cpp clear_slot):
+// record(slot), the bytes of tab to zero once ev has been waited for, and forget(slot),
+// the host's note of the slot dropped. A signer family adds secrets(), the bytes
+// cordahip_shutdown zeroes (signer_wipe). record() and secrets() are defined in
+// keyed.cpp, where the kernels' layouts are known. A new family is such a struct and one
+// line in Device::signer_keys or Device::verify_keys.
+struct TabSpan {
+  size_t at, bytes;
+};
 struct KeyTable {
   DevBuf tab;
   PinBuf stage;
   Fence ev;
+  void forget(uint32_t) {}
   template <class V>
   void visit(V& v) {
     v.dev(tab, kKept);
@@ -534,65 +560,89 @@ struct KeyTable {
   }
 };
 
+// What the host knows of a table of both ECDSA curves' keys, under the table's lock:
+// built: the curve's table (the signer's comb, the verifier's base-point table) has been
+// built; live: the curve's live keys on this device; of[slot]: the scheme of the slot's
+// live record (0: none). Only curve() knows the index (0: secp256k1, 1: P-256).
+template <uint32_t Slots>
+struct CurveBook {
+  uint32_t built[2] = {0, 0};
+  uint32_t live[2] = {0, 0};
+  uint8_t of[Slots] = {};
+  static constexpr uint32_t curve(uint32_t scheme) { return scheme - 2; }
+  bool table_built(uint32_t scheme) const { return built[curve(scheme)] != 0; }
+  void mark_built(uint32_t scheme) { built[curve(scheme)] = 1; }
+  void take(uint32_t slot, uint32_t scheme) {
+    of[slot] = (uint8_t)scheme;
+    live[curve(scheme)]++;
+  }
+  void drop(uint32_t slot) {
+    if (of[slot]) live[curve(of[slot])]--;
+    of[slot] = 0;
+  }
+  bool has_live(uint32_t scheme) const { return live[curve(scheme)] > 0; }
+  bool any_live() const { return live[0] || live[1]; }
+};
+
 // The Ed25519 signer's (ed25519_comb.hpp: 4,096 records of 128 bytes and the expansion
 // kernel's scratch): private keys, so cordahip_shutdown zeroes it before ~Device frees
 // it. stage: 64 bytes, the seed out and the public key back (wiped before add returns).
-struct SignKeys : KeyTable {};
+struct SignKeys : KeyTable {
+  TabSpan record(uint32_t slot) const;
+  TabSpan secrets() const;
+};
 
 // The ECDSA signer's (ecdsa_sign_core.hpp: the two curves' comb tables, 4,096 records of
 // 128 bytes and the add kernel's scratch): private keys, zeroed by cordahip_shutdown like
-// SignKeys. stage: 128 bytes, d out and the answer with Q back (d wiped before add
-// returns). comb[c]: the comb table of curve c (0: secp256k1, 1: P-256) has been built;
-// live[c]: that curve's live keys on this device; scheme[slot]: the curve of the slot's
-// live record (0: none) -- all under Device::sign_mu.
+// SignKeys (the comb tables are public and stay). stage: 128 bytes, d out and the answer
+// with Q back (d wiped before add returns). book: the curves' comb tables and live keys
+// (CurveBook), under Device::sign_mu.
 struct EcSignKeys : KeyTable {
-  uint32_t comb[2] = {0, 0};
-  uint32_t live[2] = {0, 0};
-  uint8_t scheme[kSignKeySlots] = {};
+  CurveBook<kSignKeySlots> book;
+  TabSpan record(uint32_t slot) const;
+  TabSpan secrets() const;
+  void forget(uint32_t slot) { book.drop(slot); }
 };
 
 // The Ed25519 verification keys' (ed25519_vkey.hpp: 64 window tables of 512 KiB and the
 // base point's, their records and the build kernel's scratch). stage: 64 bytes, the key
 // bytes out and the decode verdict back. live: the slots whose record is live on this
-// device (bit per slot, Device::vkey_mu). route_tot: the device's cumulative counters of
-// routed lanes (K14: keyed, generic; two 64-bit words, zeroed when allocated by the
-// first routed enqueue), written by kernels ordered by ev.
-struct VerifyKeys : KeyTable {
-  uint64_t live = 0;
+// device (bit per slot, Device::vkey_mu): routed enqueues (K14) ask for it. route_tot:
+// the device's cumulative counters of routed lanes (K14: keyed, generic; two 64-bit
+// words, zeroed when allocated by the first routed enqueue), written by kernels ordered
+// by ev. Clearing a slot leaves the window table: without a record whose id matches, no
+// lane reads it.
+struct RoutedKeyTable : KeyTable {
   DevBuf route_tot;
   template <class V>
   void visit(V& v) {
     KeyTable::visit(v);
     v.dev(route_tot, kKept);
   }
+};
+struct VerifyKeys : RoutedKeyTable {
+  uint64_t live = 0;
+  TabSpan record(uint32_t slot) const;
+  void forget(uint32_t slot) { live &= ~(1ull << slot); }
 };
 
 // The ECDSA verification keys' (ecdsa_vkey.hpp: 64 window tables of 320 KiB, the two
 // curves' base-point tables, the records and the build kernel's scratch). stage: 128
 // bytes, the SEC1 bytes out and the decode verdict back. route_tot: as VerifyKeys' (K15).
-// state: what the host knows of the table (Device::vkey_mu): base[c]: the base-point
-// table of curve c (0: secp256k1, 1: P-256) has been built; live[c]: that curve's live
-// keys on this device; scheme[slot]: the curve of the slot's live record (0: none).
-struct EcVkeyState {
-  uint32_t base[2] = {0, 0};
-  uint32_t live[2] = {0, 0};
-  uint8_t scheme[64] = {};
-};
-struct EcVerifyKeys : KeyTable {
-  DevBuf route_tot;
-  EcVkeyState state;
-  template <class V>
-  void visit(V& v) {
-    KeyTable::visit(v);
-    v.dev(route_tot, kKept);
-  }
+// book: the curves' base-point tables and live keys (CurveBook), under Device::vkey_mu.
+struct EcVerifyKeys : RoutedKeyTable {
+  CurveBook<kVkeySlots> book;
+  TabSpan record(uint32_t slot) const;
+  void forget(uint32_t slot) { book.drop(slot); }
 };
 
 // The RSA verification keys' (rsa_vkey.hpp: 64 records of 1,056 bytes -- id, e, bit
 // length, width class, n', n and K = R^e mod n -- 67,584 bytes). The host builds a
 // record and it crosses in stage (1,056 bytes); no kernel builds anything. Allocated by
 // a device's first RSA add, under Device::vkey_mu like the other families' tables.
-struct RsaVerifyKeys : KeyTable {};
+struct RsaVerifyKeys : KeyTable {
+  TabSpan record(uint32_t slot) const;
+};
 
 // a page-locked buffer and its twin on the device (ensure: true when it failed)
 struct StageBuf {
@@ -768,8 +818,9 @@ struct Device {
   // the B tables (comb()), built with them by cordahip_init. keys: the key records
   // (SignKeys). sign_mu orders every user of the key table: a signing call holds it
   // while it enqueues -- its stream waits for keys.ev, its kernel is followed by
-  // keys.ev -- and add / remove hold it for their whole run; remove waits for keys.ev
-  // first, so no kernel still reads the record it zeroes.
+  // keys.ev whatever the launch answered (fenced) -- and add / remove hold it for their
+  // whole run; remove waits for keys.ev first, so no kernel still reads the record it
+  // zeroes.
   SignKeys keys;
   // ECDSA signing (K17): the records of the same registry's ECDSA keys and the curves'
   // comb tables, an allocation of their own under the same sign_mu, with a fence of
@@ -793,11 +844,13 @@ struct Device {
   // Lock order of the locks met on these paths, outermost first:
   //   ped_mu / stream_mu / a SetLease (the pipelines) -> ed_mu[0] -> ed_mu[1] ->
   //   ec_mu[0] -> ec_mu[1] -> rsa_mu -> ... -> sign_stage.mu -> vkey_stage.mu -> vkey_mu.
+  // sign_mu stands where vkey_mu does, inside sign_stage.mu; no path holds both.
   // trim_device takes them in that order up to vkey_stage.mu; a keyed host call holds
-  // vkey_stage.mu and takes vkey_mu inside it; a routed enqueue holds ed_mu[slot]
-  // (Ed25519, K14) or ec_mu[slot] (ECDSA, K15) and takes vkey_mu inside it. vkey_mu is
-  // innermost: whoever holds it (add, remove, the
-  // stats call, a keyed or routed enqueue) takes no other lock of the device but tmu
+  // its stage's mu for a shard's run (keyed.cpp ShardRun) and takes sign_mu / vkey_mu
+  // inside it, around an enqueue only; a routed enqueue holds ed_mu[slot] (Ed25519, K14)
+  // or ec_mu[slot] (ECDSA, K15) and takes vkey_mu inside it. vkey_mu is innermost:
+  // whoever holds it (add, remove, the stats call, a keyed or routed enqueue) takes no
+  // other lock of the device but tmu
   // (the timing ring's, a leaf held for a few assignments), and a routed enqueue never
   // holds it while it waits for another lock, the slot's fence or the scratch's growth.
   // The keyed RSA calls (K18) borrow the RSA workspace, so they take rsa_mu first, as
@@ -810,7 +863,7 @@ struct Device {
   // ECDSA verification against registered keys (K13): the tables of the same registry's
   // ECDSA keys, under the same vkey_mu, with a fence of their own.
   // Routing (K15, cordahip_vkey_set_routing_ecdsa): with ec_route_on set and a live
-  // ECDSA key (ec_vkeys.state.live), ec_verify_enqueue is a keyed call too: under the
+  // ECDSA key (ec_vkeys.book), ec_verify_enqueue is a keyed call too: under the
   // caller's ec_mu[slot] it takes vkey_mu for the route pass and the K13 launches --
   // behind ec_vkeys.ev, followed by ec_vkeys.ev -- and drops it before the generic
   // engine. With ec_route_on clear it takes no lock it did not take before.
@@ -819,10 +872,12 @@ struct Device {
   // RSA verification against registered keys (K18): the records of the same registry's
   // RSA keys, under the same vkey_mu, with a fence of their own.
   RsaVerifyKeys rsa_vkeys;
-  // the chunk stage of cordahip_verify_keyed and cordahip_ecdsa_verify_keyed (KeyedStage)
+  // the chunk stage of cordahip_verify_keyed, cordahip_ecdsa_verify_keyed and
+  // cordahip_rsa_verify_keyed (KeyedStage)
   KeyedStage vkey_stage;
 
-  // everything but `keys`, `ec_keys`, `vkeys`, `ec_vkeys` and `rsa_vkeys`, which the idle release is never offered (visit_keys)
+  // everything but the key tables (signer_keys, verify_keys: visit_keys), which the idle
+  // release is never offered
   template <class V>
   void visit(V& v) {
     for (DevBuf* b : {&btab, &gtab_k1, &gtab_r1}) v.dev(*b, kKept);
@@ -856,15 +911,27 @@ struct Device {
     visit(v);
     visit_keys(v);
   }
-  // the signer's key table and the verification keys' tables: bound and destroyed with
-  // the rest, never released while the context lives
+  // The registered-key families as two walks, f(table) for each: the signer's registry's
+  // (sign_mu) and the verification keys' (vkey_mu). A remove clears its slot in every
+  // family of its walk (keyed.cpp clear_slot); cordahip_shutdown wipes the signer's.
+  template <class F>
+  void signer_keys(F&& f) {
+    f(keys);
+    f(ec_keys);
+  }
+  template <class F>
+  void verify_keys(F&& f) {
+    f(vkeys);
+    f(ec_vkeys);
+    f(rsa_vkeys);
+  }
+  // every key table: bound and destroyed with the rest, never released while the
+  // context lives
   template <class V>
   void visit_keys(V& v) {
-    keys.visit(v);
-    ec_keys.visit(v);
-    vkeys.visit(v);
-    ec_vkeys.visit(v);
-    rsa_vkeys.visit(v);
+    const auto visit_one = [&](auto& k) { k.visit(v); };
+    signer_keys(visit_one);
+    verify_keys(visit_one);
   }
   struct Release : Visitor {  // the buffers; all: the kept ones too
     bool all = false;

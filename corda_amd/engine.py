@@ -55,6 +55,51 @@ class Engine:
         blob = np.frombuffer(b"".join(items), dtype=np.uint8) if off[-1] else np.zeros(1, np.uint8)
         return np.ascontiguousarray(blob), off
 
+    @staticmethod
+    def _dev_args(stream, *tensors):
+        """what a *_keyed_device wrapper hands the library: each tensor's device pointer (None for no
+        tensor or one without elements) and the stream's handle (0: the null stream)"""
+        ptrs = [(t.data_ptr() or None) if t is not None else None for t in tensors]
+        return ptrs, (stream.cuda_stream if stream is not None else 0)
+
+    def _run(self, name: str, b, submit: bool, res, keep):
+        """the named host call on descriptor b, or its _submit: res(), or a Ticket whose wait() returns it"""
+        if submit:
+            t = ctypes.c_uint64()
+            check(getattr(lib(), name + "_submit")(self._ctx, ctypes.byref(b), ctypes.byref(t)), name + "_submit")
+            return Ticket(self, t.value, res, keep + (b,))
+        check(getattr(lib(), name)(self._ctx, ctypes.byref(b)), name)
+        return res()
+
+    def _keyed_verify(self, name: str, key_ids, sigs, msgs, is_valid: bool, submit: bool):
+        """a KeyedSigBatch of the lanes through the named call: (status[n], verdict) or a Ticket"""
+        n = len(sigs)
+        assert len(key_ids) == n and len(msgs) == n
+        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
+        sb, so = self._csr(list(sigs))
+        mb, mo = self._csr(list(msgs))
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        verdict = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
+        b = _lib.KeyedSigBatch(n, _ptr(ids), _ptr(sb), _ptr(so), _ptr(mb), _ptr(mo), _ptr(status), _ptr(verdict),
+                               _lib.FLAG_IS_VALID if is_valid else 0, sb.size if n and so[n] else 0,
+                               mb.size if n and mo[n] else 0)
+        return self._run(name, b, submit, lambda: (status[:n], verdict), (ids, sb, so, mb, mo, status, verdict))
+
+    def _keyed_sign(self, name: str, batch_type, row: int, with_len: bool, key_ids, msgs, gate, submit: bool):
+        """a signing batch (SignBatch; EcdsaSignBatch with_len) through the named call: (sigs[n, row],
+        [sig_len[n],] status[n]) or a Ticket"""
+        n = len(msgs)
+        assert len(key_ids) == n and (gate is None or len(gate) == n)
+        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
+        mb, mo = self._csr(list(msgs))
+        g = None if gate is None else np.ascontiguousarray(np.asarray(list(gate) or [0], dtype=np.uint8))
+        sig = np.zeros((max(n, 1), row), dtype=np.uint8)
+        sl = [np.zeros(max(n, 1), dtype=np.uint8)] if with_len else []
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        b = batch_type(n, _ptr(ids), _ptr(mb), _ptr(mo), _ptr(g) if g is not None else None, _ptr(sig),
+                       *[_ptr(a) for a in sl], _ptr(st), mb.size if n and mo[n] else 0)
+        return self._run(name, b, submit, lambda: (sig[:n], *[a[:n] for a in sl], st[:n]), (ids, mb, mo, g, sig, sl, st))
+
     def verify_batch(self, schemes: Sequence[int], keys: Sequence[bytes], sigs: Sequence[bytes],
                      msgs: Sequence[bytes], async_: bool = False, is_valid: bool = False, rsa: bool = False):
         """Per-lane statuses for (scheme, key, sig, msg) tuples; returns (status, verdict).
@@ -131,34 +176,15 @@ class Engine:
         """cordahip_sign / cordahip_sign_submit: lane i signs msgs[i] with key key_ids[i] unless gate[i]
         is nonzero. Returns (sigs[n, 64], status[n]) -- zero rows where status is not OK -- or,
         async_, a Ticket whose wait() returns them."""
-        n = len(msgs)
-        assert len(key_ids) == n and (gate is None or len(gate) == n)
-        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
-        mb, mo = self._csr(list(msgs))
-        g = None if gate is None else np.ascontiguousarray(np.asarray(list(gate) or [0], dtype=np.uint8))
-        sig = np.zeros((max(n, 1), 64), dtype=np.uint8)
-        st = np.zeros(max(n, 1), dtype=np.uint8)
-        b = _lib.SignBatch(n, _ptr(ids), _ptr(mb), _ptr(mo), _ptr(g) if g is not None else None, _ptr(sig), _ptr(st),
-                           mb.size if n and mo[n] else 0)
-        keep = (ids, mb, mo, g, sig, st, b)
-        res = lambda: (sig[:n], st[:n])  # noqa: E731
-        if async_:
-            t = ctypes.c_uint64()
-            check(lib().cordahip_sign_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)), "cordahip_sign_submit")
-            return Ticket(self, t.value, res, keep)
-        check(lib().cordahip_sign(self._ctx, ctypes.byref(b)), "cordahip_sign")
-        return res()
+        return self._keyed_sign("cordahip_sign", _lib.SignBatch, 64, False, key_ids, msgs, gate, async_)
 
     def ed25519_sign_keyed_device(self, key_ids, msgs, sigs, status, gate=None, device: int = 0, stream=None):
         """cordahip_ed25519_sign_keyed_device over device tensors: key_ids int32 [n], msgs uint8
         [n, L], gate uint8 [n] or None (typically the tx_status an earlier call on `stream` wrote);
         outputs sigs uint8 [n, 64] and status uint8 [n]."""
-        n = key_ids.shape[0]
-        s = stream.cuda_stream if stream is not None else 0
-        check(lib().cordahip_ed25519_sign_keyed_device(
-            self._ctx, device, key_ids.data_ptr(), msgs.data_ptr() if msgs.shape[1] else None, msgs.shape[1], n,
-            gate.data_ptr() if gate is not None else None, sigs.data_ptr(), status.data_ptr(), s),
-            "cordahip_ed25519_sign_keyed_device")
+        (k, m, g, sg, st), s = self._dev_args(stream, key_ids, msgs, gate, sigs, status)
+        check(lib().cordahip_ed25519_sign_keyed_device(self._ctx, device, k, m, msgs.shape[1], key_ids.shape[0], g, sg,
+                                                       st, s), "cordahip_ed25519_sign_keyed_device")
 
     # ---- ECDSA signing with registered keys (RFC 6979 nonces) ------------------------
     def signer_add_ecdsa(self, scheme: int, d: bytes):
@@ -186,37 +212,17 @@ class Engine:
         key_ids[i] unless gate[i] is nonzero. Returns (sigs[n, 72], sig_len[n], status[n]) -- DER in
         zero-padded 72-byte slots, zero rows and length 0 where status is not OK -- or, async_, a
         Ticket whose wait() returns them."""
-        n = len(msgs)
-        assert len(key_ids) == n and (gate is None or len(gate) == n)
-        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
-        mb, mo = self._csr(list(msgs))
-        g = None if gate is None else np.ascontiguousarray(np.asarray(list(gate) or [0], dtype=np.uint8))
-        sig = np.zeros((max(n, 1), _lib.ECDSA_SIG_SLOT), dtype=np.uint8)
-        sl = np.zeros(max(n, 1), dtype=np.uint8)
-        st = np.zeros(max(n, 1), dtype=np.uint8)
-        b = _lib.EcdsaSignBatch(n, _ptr(ids), _ptr(mb), _ptr(mo), _ptr(g) if g is not None else None, _ptr(sig),
-                                _ptr(sl), _ptr(st), mb.size if n and mo[n] else 0)
-        keep = (ids, mb, mo, g, sig, sl, st, b)
-        res = lambda: (sig[:n], sl[:n], st[:n])  # noqa: E731
-        if async_:
-            t = ctypes.c_uint64()
-            check(lib().cordahip_ecdsa_sign_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)),
-                  "cordahip_ecdsa_sign_submit")
-            return Ticket(self, t.value, res, keep)
-        check(lib().cordahip_ecdsa_sign(self._ctx, ctypes.byref(b)), "cordahip_ecdsa_sign")
-        return res()
+        return self._keyed_sign("cordahip_ecdsa_sign", _lib.EcdsaSignBatch, _lib.ECDSA_SIG_SLOT, True, key_ids, msgs,
+                                gate, async_)
 
     def ecdsa_sign_keyed_device(self, key_ids, msgs, sigs, sig_len, status, gate=None, device: int = 0,
                                 stream=None):
         """cordahip_ecdsa_sign_keyed_device over device tensors: key_ids int32 [n], msgs uint8 [n, L],
         gate uint8 [n] or None (typically the tx_status an earlier call on `stream` wrote); outputs
         sigs uint8 [n, 72], sig_len uint8 [n] and status uint8 [n]."""
-        n = key_ids.shape[0]
-        s = stream.cuda_stream if stream is not None else 0
-        check(lib().cordahip_ecdsa_sign_keyed_device(
-            self._ctx, device, key_ids.data_ptr(), msgs.data_ptr() if msgs.shape[1] else None, msgs.shape[1], n,
-            gate.data_ptr() if gate is not None else None, sigs.data_ptr(), sig_len.data_ptr(), status.data_ptr(), s),
-            "cordahip_ecdsa_sign_keyed_device")
+        (k, m, g, sg, sl, st), s = self._dev_args(stream, key_ids, msgs, gate, sigs, sig_len, status)
+        check(lib().cordahip_ecdsa_sign_keyed_device(self._ctx, device, k, m, msgs.shape[1], key_ids.shape[0], g, sg,
+                                                     sl, st, s), "cordahip_ecdsa_sign_keyed_device")
 
     # ---- notary commit log (validateTimeWindow + commitInputStates per transaction) ----
     def commit_log_create(self, capacity_log2: int, device: int = 0, salt: Optional[bytes] = None) -> int:
@@ -440,24 +446,7 @@ class Engine:
         """cordahip_verify_keyed / cordahip_verify_keyed_submit: lane i checks sigs[i] over msgs[i] against
         the registered key key_ids[i]. Returns (status[n], verdict) -- or, async_, a Ticket whose wait()
         returns them. is_valid as in verify_batch."""
-        n = len(sigs)
-        assert len(key_ids) == n and len(msgs) == n
-        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
-        sb, so = self._csr(list(sigs))
-        mb, mo = self._csr(list(msgs))
-        status = np.zeros(max(n, 1), dtype=np.uint8)
-        verdict = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
-        b = _lib.KeyedSigBatch(n, _ptr(ids), _ptr(sb), _ptr(so), _ptr(mb), _ptr(mo), _ptr(status), _ptr(verdict),
-                               _lib.FLAG_IS_VALID if is_valid else 0, sb.size if n and so[n] else 0,
-                               mb.size if n and mo[n] else 0)
-        keep = (ids, sb, so, mb, mo, status, verdict, b)
-        if async_:
-            t = ctypes.c_uint64()
-            check(lib().cordahip_verify_keyed_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)),
-                  "cordahip_verify_keyed_submit")
-            return Ticket(self, t.value, lambda: (status[:n], verdict), keep)
-        check(lib().cordahip_verify_keyed(self._ctx, ctypes.byref(b)), "cordahip_verify_keyed")
-        return status[:n], verdict
+        return self._keyed_verify("cordahip_verify_keyed", key_ids, sigs, msgs, is_valid, async_)
 
     # ---- ECDSA verification against registered keys (the same registry: one pool of ids) ----
     def vkey_add_ecdsa(self, scheme: int, key: bytes):
@@ -475,37 +464,17 @@ class Engine:
         """cordahip_ecdsa_verify_keyed / cordahip_ecdsa_verify_keyed_submit: lane i checks the DER signature
         sigs[i] over msgs[i] against the registered ECDSA key key_ids[i]. Returns (status[n], verdict) -- or,
         submit, a Ticket whose wait() returns them. is_valid as in verify_batch."""
-        n = len(sigs)
-        assert len(key_ids) == n and len(msgs) == n
-        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
-        sb, so = self._csr(list(sigs))
-        mb, mo = self._csr(list(msgs))
-        status = np.zeros(max(n, 1), dtype=np.uint8)
-        verdict = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
-        b = _lib.KeyedSigBatch(n, _ptr(ids), _ptr(sb), _ptr(so), _ptr(mb), _ptr(mo), _ptr(status), _ptr(verdict),
-                               _lib.FLAG_IS_VALID if is_valid else 0, sb.size if n and so[n] else 0,
-                               mb.size if n and mo[n] else 0)
-        keep = (ids, sb, so, mb, mo, status, verdict, b)
-        if submit:
-            t = ctypes.c_uint64()
-            check(lib().cordahip_ecdsa_verify_keyed_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)),
-                  "cordahip_ecdsa_verify_keyed_submit")
-            return Ticket(self, t.value, lambda: (status[:n], verdict), keep)
-        check(lib().cordahip_ecdsa_verify_keyed(self._ctx, ctypes.byref(b)), "cordahip_ecdsa_verify_keyed")
-        return status[:n], verdict
+        return self._keyed_verify("cordahip_ecdsa_verify_keyed", key_ids, sigs, msgs, is_valid, submit)
 
     def ecdsa_verify_keyed_device(self, key_ids, sigs, sig_len, msgs, status, verdict=None, device: int = 0,
                                   stream=None):
         """cordahip_ecdsa_verify_keyed_device over device tensors: key_ids int32 [n], sigs uint8 [n, 72],
         sig_len uint8 [n], msgs uint8 [n, L]; outputs status uint8 [n] and verdict int64 [(n + 63) // 64]
         or None."""
-        n = key_ids.shape[0]
-        s = stream.cuda_stream if stream is not None else 0
-        check(lib().cordahip_ecdsa_verify_keyed_device(
-            self._ctx, device, key_ids.data_ptr(), sigs.data_ptr(), sig_len.data_ptr(),
-            msgs.data_ptr() if msgs.shape[1] else None, msgs.shape[1], n, status.data_ptr(),
-            verdict.data_ptr() if verdict is not None else None, s),
-            "cordahip_ecdsa_verify_keyed_device")
+        (k, sg, sl, m, st, v), s = self._dev_args(stream, key_ids, sigs, sig_len, msgs, status, verdict)
+        check(lib().cordahip_ecdsa_verify_keyed_device(self._ctx, device, k, sg, sl, m, msgs.shape[1],
+                                                       key_ids.shape[0], st, v, s),
+              "cordahip_ecdsa_verify_keyed_device")
 
     # ---- RSA_SHA256 verification against registered keys (the same registry: one pool of ids) ----
     def vkey_add_rsa(self, der: bytes):
@@ -523,36 +492,17 @@ class Engine:
         """cordahip_rsa_verify_keyed / cordahip_rsa_verify_keyed_submit: lane i checks the RSASSA-PSS
         signature sigs[i] over msgs[i] against the registered RSA key key_ids[i]. Returns (status[n], verdict)
         -- or, async_, a Ticket whose wait() returns them. is_valid as in verify_batch."""
-        n = len(sigs)
-        assert len(key_ids) == n and len(msgs) == n
-        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
-        sb, so = self._csr(list(sigs))
-        mb, mo = self._csr(list(msgs))
-        status = np.zeros(max(n, 1), dtype=np.uint8)
-        verdict = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
-        b = _lib.KeyedSigBatch(n, _ptr(ids), _ptr(sb), _ptr(so), _ptr(mb), _ptr(mo), _ptr(status), _ptr(verdict),
-                               _lib.FLAG_IS_VALID if is_valid else 0, sb.size if n and so[n] else 0,
-                               mb.size if n and mo[n] else 0)
-        keep = (ids, sb, so, mb, mo, status, verdict, b)
-        if async_:
-            t = ctypes.c_uint64()
-            check(lib().cordahip_rsa_verify_keyed_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)),
-                  "cordahip_rsa_verify_keyed_submit")
-            return Ticket(self, t.value, lambda: (status[:n], verdict), keep)
-        check(lib().cordahip_rsa_verify_keyed(self._ctx, ctypes.byref(b)), "cordahip_rsa_verify_keyed")
-        return status[:n], verdict
+        return self._keyed_verify("cordahip_rsa_verify_keyed", key_ids, sigs, msgs, is_valid, async_)
 
     def rsa_verify_keyed_device(self, key_ids, sigs, sig_len, msgs, status, verdict=None, device: int = 0,
                                 stream=None):
         """cordahip_rsa_verify_keyed_device over device tensors, one width class W = sigs.shape[1] // 4 per
         call: key_ids int32 [n], sigs uint8 [n, 4 W] big-endian, sig_len int16 [n], msgs uint8 [n, L];
         outputs status uint8 [n] and verdict int64 [(n + 63) // 64] or None; doVerify statuses."""
-        n = key_ids.shape[0]
-        s = stream.cuda_stream if stream is not None else 0
-        check(lib().cordahip_rsa_verify_keyed_device(
-            self._ctx, device, key_ids.data_ptr(), sigs.data_ptr(), sig_len.data_ptr(),
-            msgs.data_ptr() if msgs.shape[1] else None, msgs.shape[1], sigs.shape[1] // 4, n, status.data_ptr(),
-            verdict.data_ptr() if verdict is not None else None, s), "cordahip_rsa_verify_keyed_device")
+        (k, sg, sl, m, st, v), s = self._dev_args(stream, key_ids, sigs, sig_len, msgs, status, verdict)
+        check(lib().cordahip_rsa_verify_keyed_device(self._ctx, device, k, sg, sl, m, msgs.shape[1],
+                                                     sigs.shape[1] // 4, key_ids.shape[0], st, v, s),
+              "cordahip_rsa_verify_keyed_device")
 
     def rsa_public_op_keyed_device(self, key_ids, inp, out, device: int = 0, stream=None):
         """out = inp^e mod n of the registered RSA key key_ids[i] per row. Device tensors: key_ids int32 [n],
@@ -566,12 +516,9 @@ class Engine:
     def ed25519_verify_keyed_device(self, key_ids, sigs, msgs, status, verdict=None, device: int = 0, stream=None):
         """cordahip_ed25519_verify_keyed_device over device tensors: key_ids int32 [n], sigs uint8 [n, 64],
         msgs uint8 [n, L]; outputs status uint8 [n] and verdict int64 [(n + 63) // 64] or None."""
-        n = key_ids.shape[0]
-        s = stream.cuda_stream if stream is not None else 0
-        check(lib().cordahip_ed25519_verify_keyed_device(
-            self._ctx, device, key_ids.data_ptr(), sigs.data_ptr(), msgs.data_ptr() if msgs.shape[1] else None,
-            msgs.shape[1], n, status.data_ptr(), verdict.data_ptr() if verdict is not None else None, s),
-            "cordahip_ed25519_verify_keyed_device")
+        (k, sg, m, st, v), s = self._dev_args(stream, key_ids, sigs, msgs, status, verdict)
+        check(lib().cordahip_ed25519_verify_keyed_device(self._ctx, device, k, sg, m, msgs.shape[1], key_ids.shape[0],
+                                                         st, v, s), "cordahip_ed25519_verify_keyed_device")
 
     def ecdsa_sign_device(self, scheme, seeds, msgs, keys, key_len, sigs, sig_len, device: int = 0, stream=None):
         """Device tensors: scheme[n] u8 (2/3), seeds[n,32], msgs[n,L] -> keys[n,65], key_len[n], sigs[n,72], sig_len[n]."""

@@ -1,8 +1,8 @@
 """RSA_SHA256 verification against registered public keys on the GPU (K18): the keyed modular
 exponentiation against Python's pow on adversarial moduli, the golden vectors
 (tests/golden/rsa_pss_vectors.json) through cordahip_rsa_verify_keyed under both flags values,
-keyed against generic on fresh CRT-signed lanes, the device call per width class, the registry
-across the three families, tickets and memory."""
+keyed against generic on fresh CRT-signed lanes, the host call in three chunks and in two launches,
+the device call per width class, the registry across the three families, tickets and memory."""
 import ctypes
 import json
 import os
@@ -282,6 +282,122 @@ def test_keyed_equals_generic(eng, golden, reg, corpus, is_valid):
     assert verdict_bits(verdict, len(corpus)) == verdict_bits(gv, len(corpus)) == [int(x == bc.OK) for x in want]
     assert sum(x == bc.OK for x in want[:240]) == 240 - 48
     assert (bc.EMPTY in want) == (not is_valid) and bc.BAD_SIG in want
+
+
+# ---- 3b. the host call's chunk and launch loops -----------------------------------------------------
+GUARD = 64
+
+
+def csr(items):
+    off = np.zeros(len(items) + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in items])
+    return np.frombuffer(b"".join(items) or b"\0", np.uint8).copy(), off
+
+
+def run_keyed_arrays(e, ids, sb, so, mb, mo, is_valid=False, with_verdict=True):
+    """cordahip_rsa_verify_keyed over a batch's arrays as they cross (ids uint32 [n], bytes with uint64
+    [n + 1] offsets), status and verdict between 0xA5 guards. Returns (status, verdict words or None)."""
+    from corda_amd import _lib
+    n = len(ids)
+    words = (n + 63) // 64
+    st = np.full(GUARD + n + GUARD, 0xA5, np.uint8)
+    vd = np.full(GUARD + words * 8 + GUARD, 0xA5, np.uint8)
+    p = lambda a: a.ctypes.data  # noqa: E731
+    b = _lib.KeyedSigBatch(n, p(ids), p(sb), p(so), p(mb), p(mo), p(st) + GUARD, p(vd) + GUARD if with_verdict else None,
+                           _lib.FLAG_IS_VALID if is_valid else 0, int(so[n]), int(mo[n]))
+    assert _lib.lib().cordahip_rsa_verify_keyed(e.ctx, ctypes.byref(b)) == 0
+    for buf in (st, vd):
+        assert (buf[:GUARD] == 0xA5).all() and (buf[-GUARD:] == 0xA5).all()
+    if not with_verdict:  # a NULL verdict pointer: statuses only
+        assert (vd == 0xA5).all()
+        return st[GUARD:GUARD + n].copy(), None
+    return st[GUARD:GUARD + n].copy(), vd[GUARD:GUARD + words * 8].copy().view(np.uint64)
+
+
+def verdict_words(statuses):
+    """the words a call owes for these statuses: bit i = lane i is OK, zero bits past n"""
+    w = np.zeros((len(statuses) + 63) // 64, np.uint64)
+    for i, x in enumerate(statuses):
+        if int(x) == bc.OK:
+            w[i // 64] |= np.uint64(1 << (i % 64))
+    return w
+
+
+@pytest.fixture(scope="module")
+def three_chunks(eng, golden, reg, corpus):
+    """130 lanes for CORDAHIP_HOST_CHUNK=64 (chunks of 64 / 64 / 2): the corpus' first lanes, their keys
+    alternating between the width classes, with a signature longer than every slot, an empty message
+    and the corpus' flipped signatures; ids nobody was issued on both sides of each chunk edge. The
+    statuses wanted are the generic path's for the same lanes with the keys spelled out (asked once,
+    under the default chunk size), UNKNOWN_KEY for the unknown ids."""
+    keys, _ = golden
+    lanes = [list(l) for l in corpus[:130]]
+    lanes[10][1] = lanes[10][1] + b"\x00" * 600
+    lanes[70][2] = b""
+    unknown = (63, 64, 127, 128)
+    for a in (0, 64):  # lanes of at least two classes alternate within each full chunk
+        cls = [class_words(keys[l[0]]["n"].bit_length()) for l in lanes[a:a + 64]]
+        assert len(set(cls)) >= 2 and sum(x != y for x, y in zip(cls, cls[1:])) >= 16
+    assert sum(i % 5 == 4 for i in range(130)) >= 20  # the corrupted signatures
+    ids = np.array([(reg[l[0]] & 63) | 0x3FFFF << 6 if i in unknown else reg[l[0]] for i, l in enumerate(lanes)],
+                   np.uint32)
+    sigs, msgs = [l[1] for l in lanes], [l[2] for l in lanes]
+    want = {}
+    for is_valid in (False, True):
+        gen, _ = eng.verify_batch([RSA] * 130, [keys[l[0]]["der"] for l in lanes], sigs, msgs, is_valid=is_valid,
+                                  rsa=True)
+        w = [UNKNOWN if i in unknown else int(x) for i, x in enumerate(gen)]
+        assert {bc.OK, bc.BAD_SIG, UNKNOWN} <= set(w) and w[10] == bc.BAD_SIG and w[129] != UNKNOWN
+        assert w[70] == (bc.BAD_SIG if is_valid else bc.EMPTY)
+        want[is_valid] = w
+    return (ids,) + csr(sigs) + csr(msgs), want
+
+
+@pytest.mark.parametrize("is_valid", (False, True))
+@pytest.mark.parametrize("with_verdict", (True, False))
+def test_three_chunks_classes_interleaved(eng, three_chunks, monkeypatch, with_verdict, is_valid):
+    """The chunk loop over a full, a second and a partial chunk, each grouped by class again, with and
+    without verdict words; with them, the last word is partial and has no bit set past lane 129."""
+    arrays, want = three_chunks
+    monkeypatch.setenv("CORDAHIP_HOST_CHUNK", "64")
+    st, vd = run_keyed_arrays(eng, *arrays, is_valid=is_valid, with_verdict=with_verdict)
+    bad = [(i, int(s), w) for i, (s, w) in enumerate(zip(st, want[is_valid])) if int(s) != w]
+    assert not bad, bad[:10]
+    if with_verdict:
+        assert vd.tolist() == verdict_words(want[is_valid]).tolist() and int(vd[2]) >> 2 == 0
+
+
+def test_two_launches_one_class(eng, golden, reg):
+    """2^15 + 65 lanes of the 2048-bit class in one chunk: a full launch of the keyed stage's 2^15 rows
+    and a second of 65 (a partial wave). The golden lanes of that class tiled; four signatures that
+    verify get a bit flipped, two on each side of row 2^15, and are judged by the Python model; every
+    other lane wants its golden status (the generic path agrees with those: test_keyed_equals_generic)."""
+    keys, vs = golden
+    base = [v for v in vs if v["key"] in reg and class_words(keys[v["key"]]["n"].bit_length()) == 64]
+    nb, n = len(base), (1 << 15) + 65
+    assert nb >= 32 and sum(v["status"] == bc.OK for v in base) >= 8
+    reps = -(-n // nb)
+    tile = lambda a: np.tile(np.asarray(a), reps)[:n]  # noqa: E731
+    sig_len, msg_len = tile([len(v["sig"]) for v in base]), tile([len(v["msg"]) for v in base])
+    so, mo = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+    so[1:], mo[1:] = np.cumsum(sig_len), np.cumsum(msg_len)
+    sb = np.tile(np.frombuffer(b"".join(v["sig"] for v in base), np.uint8), reps)[:int(so[n])].copy()
+    mb = np.tile(np.frombuffer(b"".join(v["msg"] for v in base), np.uint8), reps)[:int(mo[n])].copy()
+    ids = tile([reg[v["key"]] for v in base]).astype(np.uint32)
+    want = tile([v["status"] for v in base]).astype(np.uint8)
+    ok = np.nonzero(want == bc.OK)[0]
+    edge = int(np.searchsorted(ok, 1 << 15))
+    flipped = [int(ok[0]), int(ok[edge - 1]), int(ok[edge]), int(ok[-1])]
+    assert flipped[1] < (1 << 15) <= flipped[2] and (1 << 15) - flipped[1] <= nb and flipped[3] >= n - nb
+    for i in flipped:
+        sb[int(so[i + 1]) - 1] ^= 1
+        v = base[i % nb]
+        want[i] = bc.verify(keys[v["key"]]["der"], bytes(sb[int(so[i]):int(so[i + 1])]), v["msg"])
+        assert want[i] == bc.BAD_SIG
+    st, vd = run_keyed_arrays(eng, ids, sb, so, mb, mo)
+    bad = np.nonzero(st != want)[0]
+    assert not len(bad), [(int(i), int(st[i]), int(want[i])) for i in bad[:10]]
+    assert vd.tolist() == verdict_words(want).tolist()
 
 
 # ---- 4. the device call ------------------------------------------------------------------------------

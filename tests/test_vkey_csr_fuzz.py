@@ -5,7 +5,10 @@ sig_bytes, msg_bytes and n, and checks that check_keyed_sig_batch (csr_check.hpp
 exactly the batches the contract rejects -- and that a batch it accepts is packed chunk by
 chunk (pack_rows.hpp msg_chunk_layout / keyed_pack_rows, the code cordahip_verify_keyed
 runs) into exact-size stages without a read outside a caller buffer or a write outside a
-stage, with the statuses the host decides (EMPTY, MALFORMED_SIG) as the contract states."""
+stage, with the statuses the host decides (EMPTY, MALFORMED_SIG) as the contract states. Every
+accepted batch also goes through cordahip_rsa_verify_keyed's packer (rsa_keyed_msg_offsets /
+rsa_keyed_pack_rows): lanes grouped by a random width class, small launches, exact-size stages,
+every row compared with its lane."""
 import json
 import os
 import shutil
@@ -35,3 +38,9 @@ def test_vkey_csr_fuzz_asan_ubsan(tmp_path):
     # every host-decided status occurred
     assert st["pre_ok"] > 10000 and st["pre_empty"] > 1000 and st["pre_malformed"] > 1000, st
     assert st["lanes_packed"] > 100000, st
+    # the RSA walk ran: rows of every width class, lanes left out as unknown ids, signatures longer
+    # than their slot, slot-edge lengths (0, 4 W - 1, 4 W, 4 W + 1) and empty messages (floors a third
+    # or less of what the committed seed gives: they keep the walk exercised, they measure nothing)
+    assert len(st["rsa_rows"]) == 3 and all(x > 50000 for x in st["rsa_rows"]), st
+    assert st["rsa_launches"] > 30000 and st["rsa_unknown"] > 50000, st
+    assert st["rsa_oversize"] > 10000 and st["rsa_edge_lens"] > 10000 and st["rsa_empty_msgs"] > 10000, st

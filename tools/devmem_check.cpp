@@ -177,11 +177,15 @@ int main() {
     SignKeys sk;
     visited(sk, 0, "SignKeys");
     EcSignKeys esk;
-    visited(esk, 4 * sizeof(uint32_t) /* comb, live */ + cordahip::kSignKeySlots /* scheme */, "EcSignKeys");
+    visited(esk, sizeof(CurveBook<cordahip::kSignKeySlots>) /* book */, "EcSignKeys");
+    static_assert(sizeof(CurveBook<cordahip::kSignKeySlots>) == 4 * sizeof(uint32_t) + cordahip::kSignKeySlots,
+                  "built, live and a byte per slot");
     VerifyKeys vk;
     visited(vk, sizeof(uint64_t) /* live */, "VerifyKeys");
     EcVerifyKeys ek;
-    visited(ek, sizeof(EcVkeyState) /* state */, "EcVerifyKeys");
+    visited(ek, sizeof(CurveBook<cordahip::kVkeySlots>) /* book */, "EcVerifyKeys");
+    RsaVerifyKeys rk;
+    visited(rk, 0, "RsaVerifyKeys");
     KeyedStage ks;
     visited(ks, sizeof(std::mutex) /* mu */, "KeyedStage");
     visited(tw, 0, "TxWork");
@@ -265,6 +269,10 @@ int main() {
     k->visit(gk);
     const size_t before = g.dev.size();
     k->visit_keys(gk);
+    size_t nsign = 0, nver = 0;  // visit_keys is the two walks of the families
+    k->signer_keys([&](auto&) { nsign++; });
+    k->verify_keys([&](auto&) { nver++; });
+    CHECK(nsign == 2 && nver == 3);
     // the five tables and the routed lanes' counters (VerifyKeys::route_tot, EcVerifyKeys::route_tot)
     CHECK(g.dev.size() == before + 7 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
     CHECK(k->ec_keys.tab.dev == 6 && k->ec_keys.tab.p && k->ec_keys.stage.p && k->ec_keys.ev.ev);

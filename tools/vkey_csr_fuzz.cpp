@@ -8,6 +8,10 @@
 // / keyed_pack_rows (pack_rows.hpp) into stages of exactly the bytes the layout asks for
 // -- so a read outside a caller buffer or a write outside a stage is a sanitizer report.
 // The packed rows and the host-decided statuses are compared with the caller's lanes.
+// Every accepted batch is then walked as cordahip_rsa_verify_keyed walks it: each lane
+// gets a random width class or none (an unknown id), each class's lanes go in launches of
+// a small random size through rsa_keyed_msg_offsets / rsa_keyed_pack_rows into exact-size
+// stages, and every row is compared with its lane.
 // Usage: vkey_csr_fuzz <batches> <seed>; prints one JSON line, exit 0 = pass.
 #include <cstdint>
 #include <cstdio>
@@ -69,6 +73,8 @@ bool contract_ok(const cordahip_keyed_sig_batch& b) {
 struct Stats {
   uint64_t batches = 0, invalid = 0, lanes_packed = 0, dense_chunks = 0, csr_chunks = 0, empty_msgs = 0, pre_ok = 0,
            pre_empty = 0, pre_malformed = 0;
+  uint64_t rsa_rows[3] = {0, 0, 0}, rsa_launches = 0, rsa_unknown = 0, rsa_oversize = 0, rsa_empty_msgs = 0,
+           rsa_edge_lens = 0;
 };
 
 // the walk of an accepted batch: cordahip_verify_keyed's chunk loop with exact-size stages
@@ -116,6 +122,65 @@ bool walk(const cordahip_keyed_sig_batch& b, uint64_t chunk, Stats& st) {
   return true;
 }
 
+// the walk of an accepted batch as cordahip_rsa_verify_keyed's: lanes by width class, a
+// launch of at most `launch` rows at a time, exact-size stages filled with a byte no
+// packer writes, packed in two pieces as the pool would
+bool walk_rsa(const cordahip_keyed_sig_batch& b, Rng& r, Stats& st) {
+  std::vector<uint64_t> cl[3];
+  for (uint64_t i = 0; i < b.n; i++) {
+    const uint64_t k = r.below(4);
+    if (k < 3) cl[k].push_back(i);
+    else st.rsa_unknown++;  // an id the mirror does not know: not sent
+  }
+  const uint64_t launch = 1 + r.below(24);
+  for (int c = 0; c < 3; c++) {
+    const uint32_t W = 64 + 32 * (uint32_t)c;
+    const uint64_t slot = 4ull * W;
+    for (uint64_t r0 = 0; r0 < cl[c].size(); r0 += launch) {
+      const uint64_t rows = cl[c].size() - r0 < launch ? cl[c].size() - r0 : launch;
+      const uint64_t* lanes = cl[c].data() + r0;
+      Arr<uint64_t> mo;
+      mo.make(rows + 1);
+      rsa_keyed_msg_offsets(&b, lanes, rows, mo.get());
+      Arr<uint32_t> hid;
+      Arr<uint8_t> hsig, hm;
+      Arr<uint16_t> hsl;
+      hid.make(rows);
+      hsig.make(rows * slot);
+      hsl.make(rows);
+      hm.make(mo.p[rows]);
+      std::memset(hsig.get(), 0xA5, rows * slot);
+      const uint64_t mid = rows / 2;
+      rsa_keyed_pack_rows(&b, lanes, W, mo.get(), 0, mid, hid.get(), hsig.get(), hsl.get(), hm.get());
+      rsa_keyed_pack_rows(&b, lanes, W, mo.get(), mid, rows, hid.get(), hsig.get(), hsl.get(), hm.get());
+      uint64_t sum = 0;
+      if (mo.p[0] != 0) return false;
+      for (uint64_t q = 0; q < rows; q++) {
+        const uint64_t i = lanes[q];
+        const uint64_t o = b.msg_off[i], len = b.msg_off[i + 1] - o;
+        const uint64_t so = b.sig_off[i], sl = b.sig_off[i + 1] - so;
+        if (hid.p[q] != b.key_id[i]) return false;
+        if (mo.p[q] != sum || mo.p[q + 1] != sum + len) return false;
+        if (len && std::memcmp(hm.get() + sum, b.msg + o, len) != 0) return false;
+        sum += len;
+        const uint64_t sent = sl <= slot ? sl : 0;  // a signature longer than its slot sends no bytes
+        const uint8_t* row = hsig.get() + q * slot;
+        if (sent && std::memcmp(row, b.sig + so, sent) != 0) return false;
+        for (uint64_t j = sent; j < slot; j++)
+          if (row[j]) return false;
+        if (hsl.p[q] != (sl < slot + 1 ? sl : slot + 1)) return false;
+        st.rsa_oversize += sl > slot;
+        st.rsa_empty_msgs += len == 0;
+        st.rsa_edge_lens += sl == 0 || sl + 1 == slot || sl == slot || sl == slot + 1;
+      }
+      if (mo.p[rows] != sum) return false;
+      st.rsa_rows[c] += rows;
+      st.rsa_launches++;
+    }
+  }
+  return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -134,7 +199,15 @@ int main(int argc, char** argv) {
       moff.p[i] = x;
       soff.p[i] = y;
       x += ids32 ? 32 : (r.chance(15) ? 0 : r.chance(30) ? 32 : r.below(300));
-      y += r.chance(80) ? 64 : r.chance(30) ? 0 : r.below(130);
+      // mostly Ed25519's 64 bytes; one in eight at an RSA slot's edge (4 W - 1, 4 W, 4 W + 1)
+      // or well beyond it, for each width class W
+      if (r.chance(12)) {
+        const uint64_t slot = 4 * (64 + 32 * r.below(3));
+        const uint64_t k = r.below(4);
+        y += k < 3 ? slot - 1 + k : slot + 2 + r.below(700);
+      } else {
+        y += r.chance(80) ? 64 : r.chance(30) ? 0 : r.below(130);
+      }
     }
     moff.p[n] = x;
     soff.p[n] = y;
@@ -195,13 +268,20 @@ int main(int argc, char** argv) {
     if (!walk(b, chunk, st)) {
       fprintf(stderr, "batch %llu: packed rows differ from the caller's lanes\n", (unsigned long long)it);
       ok = false;
+    } else if (!walk_rsa(b, r, st)) {
+      fprintf(stderr, "batch %llu: packed RSA rows differ from the caller's lanes\n", (unsigned long long)it);
+      ok = false;
     }
   }
   printf("{\"batches\": %llu, \"invalid\": %llu, \"lanes_packed\": %llu, \"dense_chunks\": %llu, \"csr_chunks\": %llu, "
-         "\"empty_msgs\": %llu, \"pre_ok\": %llu, \"pre_empty\": %llu, \"pre_malformed\": %llu, \"ok\": %s}\n",
+         "\"empty_msgs\": %llu, \"pre_ok\": %llu, \"pre_empty\": %llu, \"pre_malformed\": %llu, "
+         "\"rsa_rows\": [%llu, %llu, %llu], \"rsa_launches\": %llu, \"rsa_unknown\": %llu, \"rsa_oversize\": %llu, "
+         "\"rsa_empty_msgs\": %llu, \"rsa_edge_lens\": %llu, \"ok\": %s}\n",
          (unsigned long long)st.batches, (unsigned long long)st.invalid, (unsigned long long)st.lanes_packed,
          (unsigned long long)st.dense_chunks, (unsigned long long)st.csr_chunks, (unsigned long long)st.empty_msgs,
          (unsigned long long)st.pre_ok, (unsigned long long)st.pre_empty, (unsigned long long)st.pre_malformed,
-         ok ? "true" : "false");
+         (unsigned long long)st.rsa_rows[0], (unsigned long long)st.rsa_rows[1], (unsigned long long)st.rsa_rows[2],
+         (unsigned long long)st.rsa_launches, (unsigned long long)st.rsa_unknown, (unsigned long long)st.rsa_oversize,
+         (unsigned long long)st.rsa_empty_msgs, (unsigned long long)st.rsa_edge_lens, ok ? "true" : "false");
   return ok ? 0 : 1;
 }
