@@ -44,6 +44,7 @@ EXPORTS = [
     "cordahip_ed25519_sign_keyed_device",
     "cordahip_signer_add_ecdsa", "cordahip_ecdsa_sign", "cordahip_ecdsa_sign_submit",
     "cordahip_ecdsa_sign_keyed_device",
+    "cordahip_signer_add_rsa", "cordahip_rsa_sign", "cordahip_rsa_sign_submit", "cordahip_rsa_sign_keyed_device",
     "cordahip_vkey_add_ed25519", "cordahip_vkey_remove", "cordahip_verify_keyed", "cordahip_verify_keyed_submit",
     "cordahip_ed25519_verify_keyed_device",
     "cordahip_vkey_add_ecdsa", "cordahip_ecdsa_verify_keyed", "cordahip_ecdsa_verify_keyed_submit",
@@ -86,6 +87,11 @@ ERR_INVALID_ARG, ERR_OUT_OF_MEMORY = -1, -4
 VERIFY_UNKNOWN_KEY = 16
 VKEY_MAX_KEYS = 64  # live verification keys per context (a full registry: CORDAHIP_ERR_OUT_OF_MEMORY)
 VKEY_NO_ID = 0xFFFFFFFF  # the id cordahip_vkey_add_ed25519 reports for bytes that are not a key
+# RSA signing with registered private keys (cordahip_rsa_sign): live RSA signing keys per context, the
+# signature slot of the host call, a device's signer table (rsa_sign.hpp)
+RSA_SIGNER_MAX_KEYS = 64
+RSA_SIG_SLOT = 512
+RSA_SIGN_TABLE_BYTES = 232496
 RSA_VKEY_TABLE_BYTES = 67584  # a device's RSA verification-key table: 64 records of 1,056 bytes (rsa_vkey.hpp)
 # notary commit log (cordahip_commit_inputs): tx_status besides OK; ref_state values; an absent window side
 COMMIT_CONFLICT, COMMIT_TIME_WINDOW_INVALID, COMMIT_SKIPPED = 16, 17, 18
@@ -207,6 +213,27 @@ class EcdsaSignBatch(ctypes.Structure):
         ("key_id", ctypes.c_void_p),
         ("msg", ctypes.c_void_p), ("msg_off", ctypes.c_void_p),
         ("gate", ctypes.c_void_p),
+        ("sig", ctypes.c_void_p), ("sig_len", ctypes.c_void_p), ("status", ctypes.c_void_p),
+        ("msg_bytes", ctypes.c_uint64),
+    ]
+
+
+class RsaPrivateKey(ctypes.Structure):
+    _fields_ = [
+        ("p", ctypes.c_char_p), ("q", ctypes.c_char_p), ("dp", ctypes.c_char_p), ("dq", ctypes.c_char_p),
+        ("qinv", ctypes.c_char_p),
+        ("p_len", ctypes.c_uint32), ("q_len", ctypes.c_uint32), ("dp_len", ctypes.c_uint32),
+        ("dq_len", ctypes.c_uint32), ("qinv_len", ctypes.c_uint32),
+        ("e", ctypes.c_uint32),
+    ]
+
+
+class RsaSignBatch(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("key_id", ctypes.c_void_p),
+        ("msg", ctypes.c_void_p), ("msg_off", ctypes.c_void_p),
+        ("gate", ctypes.c_void_p), ("salt", ctypes.c_void_p),
         ("sig", ctypes.c_void_p), ("sig_len", ctypes.c_void_p), ("status", ctypes.c_void_p),
         ("msg_bytes", ctypes.c_uint64),
     ]
@@ -380,6 +407,11 @@ def lib() -> ctypes.CDLL:
         "cordahip_ecdsa_sign": (i32, [vp, ctypes.POINTER(EcdsaSignBatch)]),
         "cordahip_ecdsa_sign_submit": (i32, [vp, ctypes.POINTER(EcdsaSignBatch), ctypes.POINTER(u64)]),
         "cordahip_ecdsa_sign_keyed_device": (i32, [vp, i32, vp, vp, u32, u64, vp, vp, vp, vp, vp]),
+        "cordahip_signer_add_rsa": (i32, [vp, ctypes.POINTER(RsaPrivateKey), ctypes.POINTER(u32),
+                                          ctypes.POINTER(ctypes.c_uint8), vp, ctypes.POINTER(u32)]),
+        "cordahip_rsa_sign": (i32, [vp, ctypes.POINTER(RsaSignBatch)]),
+        "cordahip_rsa_sign_submit": (i32, [vp, ctypes.POINTER(RsaSignBatch), ctypes.POINTER(u64)]),
+        "cordahip_rsa_sign_keyed_device": (i32, [vp, i32, vp, vp, u32, vp, u32, u64, vp, vp, vp, vp, vp]),
         "cordahip_vkey_add_ed25519": (i32, [vp, vp, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint8)]),
         "cordahip_vkey_remove": (i32, [vp, u32]),
         "cordahip_vkey_set_routing": (i32, [vp, u32]),

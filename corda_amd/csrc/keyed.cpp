@@ -1,7 +1,7 @@
 // libcordahip.so's registered-key calls: the signer's and the verification keys'
 // registries (cordahip_signer_*, cordahip_vkey_*), the host calls that sign and verify
 // with them a chunk at a time (cordahip_sign, cordahip_ecdsa_sign, cordahip_verify_keyed,
-// cordahip_ecdsa_verify_keyed, cordahip_rsa_verify_keyed) and their *_device forms. The shared runtime types are in
+// cordahip_ecdsa_verify_keyed, cordahip_rsa_verify_keyed, cordahip_rsa_sign) and their *_device forms. The shared runtime types are in
 // runtime.hpp; the routed enqueues of the generic paths (K14, K15) in runtime.cpp.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +16,7 @@
 #include "ed25519_comb.hpp"
 #include "ed25519_vkey.hpp"
 #include "pack_rows.hpp"
+#include "rsa_sign.hpp"
 #include "rsa_vkey.hpp"
 
 using namespace cordahip;
@@ -32,6 +33,13 @@ TabSpan EcSignKeys::record(uint32_t slot) const {
 }
 TabSpan EcSignKeys::secrets() const {  // the records and the scratch; the comb tables before them are public
   return {(size_t)kEcSignRecBase * 4, (size_t)(kEcSignAllWords - kEcSignRecBase) * 4};
+}
+TabSpan RsaSignKeys::record(uint32_t slot) const {  // no RSA key in the slot: its index word, a hint no lane trusts
+  if (!rec_of[slot]) return {(size_t)(rsa::kSignTabIdxWord + slot) * 4, 4};
+  return {(rsa::kSignTabRecBase + (size_t)(rec_of[slot] - 1) * rsa::kSignRecWords) * 4, sizeof(rsa::SignRecord)};
+}
+TabSpan RsaSignKeys::secrets() const {  // the records and the scratch; the index before them is public
+  return {(size_t)rsa::kSignTabRecBase * 4, rsa::kSignTabBytes - (size_t)rsa::kSignTabRecBase * 4};
 }
 TabSpan VerifyKeys::record(uint32_t slot) const {
   return {(kVkeyRecBase + (size_t)slot * kVkeyRecWords) * 4, kVkeyRecWords * 4};
@@ -86,9 +94,9 @@ hipError_t clear_slot(Device& d, Registry which, uint32_t slot) {
   const auto clear = [&](auto& k) {
     if (!k.tab.p) return;
     any = true;
+    const TabSpan r = k.record(slot);  // before the note goes: the RSA signer's says where the record is
     k.forget(slot);
     hipError_t x = k.ev.sync();
-    const TabSpan r = k.record(slot);
     x = x ? x : hipMemsetAsync(k.tab.template as<uint8_t>() + r.at, 0, r.bytes, d.stream);
     e = e ? e : x;
   };
@@ -166,6 +174,11 @@ int signer_remove_impl(cordahip_ctx* ctx, uint32_t key_id) {
   std::lock_guard<std::mutex> g(reg.mu);
   uint32_t slot;
   if (!reg.release(key_id, slot)) return CORDAHIP_ERR_INVALID_ARG;
+  {
+    std::lock_guard<std::mutex> gm(ctx->rsa_mirror_mu);
+    if (ctx->rsa_sign_mirror[slot].words) ctx->rsa_signers--;
+    ctx->rsa_sign_mirror[slot] = {};
+  }
   // the id is dead from here on, whatever a device answers below
   const int rc = clear_slot_on_each_device(ctx, Registry::kSigner, slot);
   if (tracing()) fprintf(stderr, "[cordahip] signer: key id %u removed (%u live)\n", key_id, reg.count);
@@ -247,6 +260,139 @@ int ec_signer_add_impl(cordahip_ctx* ctx, uint32_t scheme, const uint8_t key[32]
   pub[0] = 4;
   std::memcpy(pub + 1, pfirst, 64);
   if (tracing()) fprintf(stderr, "[cordahip] signer: ECDSA key id %u (scheme %u) added (%u live)\n", id, scheme, reg.count);
+  return CORDAHIP_SUCCESS;
+}
+
+
+// ---- RSA signing with registered private keys (K19, rsa_sign_keyed.hip) ----------
+// The key's record, built by the host (rsa_sign.hpp build_sign_record), put into a free
+// record of the table on one device (sign_mu held) with the slot's index word, and
+// tried: the kernel signs the fixed EM of rsa_sign.hpp consistency_em in the table's
+// scratch and checks it with the public key, which is what catches a dP, dQ or qInv
+// that does not belong to p, q and e. *consistent: whether it did; if not, the record
+// and the slot's index word are zeroed again here. A table that this add allocated is
+// released whenever the add does not end in an accepted key on this device -- turned
+// down, out of memory for the stage, or a HIP error: such an add leaves no memory behind. The device's first RSA signing key allocates the
+// table, zeroed.
+// The record crosses in the table's page-locked stage, wiped here whatever happens.
+int rsa_signer_put_on(Device& d, const rsa::SignRecord& rec, uint32_t slot, bool* consistent) {
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  RsaSignKeys& k = d.rsa_keys;
+  const bool fresh = !k.tab.p;
+  if (fresh) {
+    if (k.tab.ensure(rsa_signtab_bytes()) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+    std::memset(k.rec_of, 0, sizeof k.rec_of);
+    std::memset(k.used, 0, sizeof k.used);
+    if (hipMemsetAsync(k.tab.p, 0, k.tab.cap, d.stream) != hipSuccess) {
+      k.tab.release();  // never a table that was not zeroed
+      return CORDAHIP_ERR_HIP;
+    }
+  }
+  // a table this add allocated goes again with an add that fails or is turned down: the
+  // stream drained first, so no copy or kernel still has it (sign_mu is held)
+  const auto drop_fresh = [&] {
+    if (!fresh) return;
+    k.forget(slot);
+    (void)hipStreamSynchronize(d.stream);
+    k.tab.release();
+  };
+  constexpr size_t kScr = (size_t)(rsa::kSignTabWords - rsa::kSignTabScratch) * 4;
+  if (k.stage.ensure(sizeof rec + kScr + 16) != hipSuccess) {
+    drop_fresh();
+    return CORDAHIP_ERR_OUT_OF_MEMORY;
+  }
+  const int r = k.take(slot);
+  if (r < 0) {
+    drop_fresh();
+    return CORDAHIP_ERR_OUT_OF_MEMORY;
+  }
+  uint8_t* st = k.stage.as<uint8_t>();
+  uint32_t* scr = reinterpret_cast<uint32_t*>(st + sizeof rec);
+  uint32_t* tail = scr + kScr / 4;  // the index word out, the answer back
+  std::memcpy(st, &rec, sizeof rec);
+  std::memset(scr, 0, kScr + 16);
+  scr[rsa::kSignScrIdWord - rsa::kSignTabScratch] = rec.id;
+  rsa::consistency_em(rec.bits, rec.words, scr + (rsa::kSignScrEmWord - rsa::kSignTabScratch));
+  tail[0] = (uint32_t)r + 1;
+  tail[1] = 0xffu;
+  uint32_t* tab = k.tab.as<uint32_t>();
+  uint32_t* drec = tab + rsa::kSignTabRecBase + (size_t)r * rsa::kSignRecWords;
+  hipError_t e = k.ev.sync();  // a removed key's record: no kernel still reads it
+  e = e ? e : hipMemcpyAsync(drec, st, sizeof rec, hipMemcpyHostToDevice, d.stream);
+  e = e ? e : hipMemcpyAsync(tab + rsa::kSignTabIdxWord + slot, tail, 4, hipMemcpyHostToDevice, d.stream);
+  e = e ? e : hipMemcpyAsync(tab + rsa::kSignTabScratch, scr, kScr, hipMemcpyHostToDevice, d.stream);
+  e = e ? e : launch_rsa_sign_selftest(tab, rec.words, d.stream);
+  e = e ? e : hipMemcpyAsync(tail + 1, tab + rsa::kSignScrStatusWord, 4, hipMemcpyDeviceToHost, d.stream);
+  hipError_t f = hipStreamSynchronize(d.stream);
+  secure_wipe(st, sizeof rec);
+  if (e == hipSuccess && f == hipSuccess) {
+    *consistent = (tail[1] & 0xffu) == CORDAHIP_STATUS_OK;
+    if (!*consistent) {  // the record and the slot's index word zeroed again
+      k.forget(slot);
+      e = hipMemsetAsync(drec, 0, sizeof rec, d.stream);
+      e = e ? e : hipMemsetAsync(tab + rsa::kSignTabIdxWord + slot, 0, 4, d.stream);
+      f = hipStreamSynchronize(d.stream);
+      drop_fresh();
+    }
+  } else {
+    drop_fresh();  // else the caller's undo clears the slot in the table that stays
+  }
+  return hip_err(e ? e : f);
+}
+
+int rsa_signer_add_impl(cordahip_ctx* ctx, const cordahip_rsa_private_key* key, uint32_t* key_id,
+                        uint8_t* key_status, uint8_t modulus[512], uint32_t* modulus_len) {
+  rsa::SignRecord rec;
+  struct Wipe {  // the host's copy of the components goes whatever the add answers
+    rsa::SignRecord& r;
+    ~Wipe() { secure_wipe(&r, sizeof r); }
+  } wipe{rec};
+  const rsa::PrivateKeyIn in{key->p,     key->q,      key->dp,     key->dq,       key->qinv, key->p_len,
+                             key->q_len, key->dp_len, key->dq_len, key->qinv_len, key->e};
+  uint8_t ks = rsa::build_sign_record(in, rec);
+  const auto declined = [&] {  // BAD_KEY, or UNSUPPORTED for a key the GPU path declines: data, no slot taken
+    *key_id = 0xFFFFFFFFu;
+    *key_status = ks;
+    return CORDAHIP_SUCCESS;
+  };
+  if (ks != rsa::kOk) return declined();
+  auto& reg = ctx->signers;
+  std::lock_guard<std::mutex> g(reg.mu);
+  if (ctx->rsa_signers >= CORDAHIP_RSA_SIGNER_MAX_KEYS) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  uint32_t slot, id;
+  if (!reg.acquire(slot, id)) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  rec.id = id;
+  bool first = false, cur = false;
+  const int rc = on_each_device(
+      ctx, &Device::sign_mu,
+      [&](Device& d, size_t i, bool& more) {
+        const int r = rsa_signer_put_on(d, rec, slot, i ? &cur : &first);
+        if (r == CORDAHIP_SUCCESS && !first) more = false;  // inconsistent: no device keeps the record
+        return r;
+      },
+      [&] { return cur == first; },
+      [&](Device& d) {  // no device keeps a record of a key the caller never got
+        if (d.rsa_keys.tab.p) (void)clear_slot(d, Registry::kSigner, slot);
+      });
+  if (rc != CORDAHIP_SUCCESS) return rc;
+  if (!first) {
+    ks = CORDAHIP_STATUS_BAD_KEY;
+    return declined();
+  }
+  {
+    std::lock_guard<std::mutex> gm(ctx->rsa_mirror_mu);
+    ctx->rsa_sign_mirror[slot] = {id, rec.words, rec.bits};
+  }
+  ctx->rsa_signers++;
+  reg.commit(slot);
+  *key_id = id;
+  *key_status = CORDAHIP_STATUS_OK;
+  const uint32_t k = (rec.bits + 7) / 8;
+  std::memset(modulus, 0, 512);
+  for (uint32_t b = 0; b < k; b++) modulus[k - 1 - b] = (uint8_t)(rec.n[b >> 2] >> (8 * (b & 3)));
+  *modulus_len = k;
+  if (tracing())
+    fprintf(stderr, "[cordahip] signer: RSA key id %u (%u bits) added (%u live)\n", id, rec.bits, reg.count);
   return CORDAHIP_SUCCESS;
 }
 
@@ -790,6 +936,122 @@ int rsa_verify_keyed_impl(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* b) 
                     [&](Device& d, uint64_t lo, uint64_t hi) { return rsa_keyed_shard(ctx, d, b, lo, hi); });
 }
 
+
+// The RSA keyed signer on stream s (rsa_mu and sign_mu held, device current, the RSA
+// workspace grown for the call: rsa_ws_grow): behind the workspace's and the RSA signer
+// table's previous users, followed by both fences (fenced). A device without an RSA
+// signer table passes none: every ungated lane is then UNKNOWN_KEY.
+hipError_t rsa_sign_enqueue(Device& d, const uint32_t* key_id, const uint8_t* msgs, const uint64_t* msg_off,
+                            uint32_t msg_len, const uint8_t* salts, const uint8_t* gate, uint32_t W, uint64_t n,
+                            uint8_t* sigs, uint16_t* sig_len, uint8_t* status, hipStream_t s) {
+  RsaWork& w = d.rsa;
+  return fenced({&w.ev, &d.rsa_keys.ev}, s, [&] {
+    return launch_rsa_sign_keyed(d.rsa_keys.tab.as<uint32_t>(), key_id, msgs, msg_off, msg_len, salts, gate, W, n, sigs,
+                                 sig_len, status, w.ws.as<uint8_t>(), w.ws.cap / rsa_ws_row_bytes(W), s);
+  });
+}
+
+// cordahip_rsa_sign for lanes [lo, hi) on one device, rsa_keyed_shard's shape: a chunk of
+// CORDAHIP_HOST_CHUNK lanes at a time; a gated lane is SKIPPED and a lane whose id is not
+// a live RSA signer's in the context's mirror UNKNOWN_KEY now, neither is sent; the rest
+// are grouped by their key's width class and each class present runs over its rows only,
+// in launches of at most kRsaSignRows rows through the signer's stage (one round_trip
+// each); signatures, lengths and statuses go back to their lanes. rsa_mu is held for the
+// run (the workspace), outside the stage's lock; the workspace grows before sign_mu is
+// taken, per launch.
+constexpr uint64_t kRsaSignRows = 1ull << 14;
+int rsa_sign_shard(cordahip_ctx* ctx, Device& d, const cordahip_rsa_sign_batch* b, uint64_t lo, uint64_t hi) {
+  KeyedStage& st = d.sign_stage;
+  std::lock_guard<std::mutex> gr(d.rsa_mu);
+  ShardRun run(ctx, d, st, 1);
+  if (!run.ok) return CORDAHIP_ERR_HIP;
+  hipStream_t s = d.stream;
+  std::vector<uint64_t> cl[3];  // lanes by class: 64, 96, 128 words
+  std::vector<cordahip_ctx::RsaVkeyMirror> mir(kSignKeySlots);
+  for (uint64_t a = lo; a < hi; a += run.chunk) {
+    const uint64_t m = std::min(run.chunk, hi - a);
+    const double t0 = now_ms();
+    {
+      std::lock_guard<std::mutex> gm(ctx->rsa_mirror_mu);
+      std::copy(ctx->rsa_sign_mirror, ctx->rsa_sign_mirror + kSignKeySlots, mir.begin());
+    }
+    for (auto& v : cl) v.clear();
+    std::memset(b->sig + a * CORDAHIP_RSA_SIG_SLOT, 0, m * CORDAHIP_RSA_SIG_SLOT);
+    for (uint64_t i = a; i < a + m; i++) {
+      const uint32_t id = b->key_id[i];
+      const auto& k = mir[id & (kSignKeySlots - 1)];
+      b->sig_len[i] = 0;
+      if (b->gate && b->gate[i]) b->status[i] = CORDAHIP_SIGN_SKIPPED;
+      else if (k.words && k.id == id) cl[k.words / 32 - 2].push_back(i);
+      else b->status[i] = CORDAHIP_SIGN_UNKNOWN_KEY;
+    }
+    for (int c = 0; c < 3; c++) {
+      const uint32_t W = 64 + 32 * (uint32_t)c;
+      for (uint64_t r0 = 0; r0 < cl[c].size(); r0 += kRsaSignRows) {
+        const uint64_t rows = std::min<uint64_t>(kRsaSignRows, cl[c].size() - r0);
+        const uint64_t* lanes = cl[c].data() + r0;
+        // the previous launch has drained: growing frees nothing in use
+        if (st.msg_off.ensure((rows + 1) * 8)) return CORDAHIP_ERR_OUT_OF_MEMORY;
+        uint64_t* mo = st.msg_off.h.as<uint64_t>();
+        mo[0] = 0;
+        for (uint64_t r = 0; r < rows; r++) mo[r + 1] = mo[r] + (b->msg_off[lanes[r] + 1] - b->msg_off[lanes[r]]);
+        if (st.ids.ensure(rows * 4) || st.salt.ensure(rows * 32) || st.sig_rows.ensure(rows * 4 * W) ||
+            st.sig_len.ensure(rows * 2) || st.msgs.ensure(std::max<uint64_t>(mo[rows], 16)) || st.status.ensure(rows))
+          return CORDAHIP_ERR_OUT_OF_MEMORY;
+        run.pool.parallel_for(rows, 256, [&](uint64_t x, uint64_t y) {
+          uint32_t* hid = st.ids.h.as<uint32_t>();
+          uint8_t *hs = st.salt.h.as<uint8_t>(), *hm = st.msgs.h.as<uint8_t>();
+          for (uint64_t r = x; r < y; r++) {
+            const uint64_t i = lanes[r];
+            hid[r] = b->key_id[i];
+            std::memcpy(hs + r * 32, b->salt + i * 32, 32);
+            if (mo[r + 1] != mo[r]) std::memcpy(hm + mo[r], b->msg + b->msg_off[i], mo[r + 1] - mo[r]);
+          }
+        });
+        bool oom = false;
+        const int rc = round_trip(st, rows, s, [&] {
+          hipError_t e = st.ids.to_device(rows * 4, s);
+          e = e ? e : st.salt.to_device(rows * 32, s);
+          if (mo[rows]) e = e ? e : st.msgs.to_device(mo[rows], s);
+          e = e ? e : st.msg_off.to_device((rows + 1) * 8, s);
+          if (e == hipSuccess) oom = (e = rsa_ws_grow(d, W, rows)) == hipErrorOutOfMemory;
+          if (e) return e;
+          {
+            std::lock_guard<std::mutex> gs(d.sign_mu);
+            e = rsa_sign_enqueue(d, st.ids.d.as<uint32_t>(), st.msgs.d.as<uint8_t>(), st.msg_off.d.as<uint64_t>(), 0,
+                                 st.salt.d.as<uint8_t>(), nullptr, W, rows, st.sig_rows.d.as<uint8_t>(),
+                                 st.sig_len.d.as<uint16_t>(), st.status.d.as<uint8_t>(), s);
+          }
+          e = e ? e : st.sig_rows.to_host(rows * 4 * W, s);
+          return e ? e : st.sig_len.to_host(rows * 2, s);
+        });
+        if (rc != CORDAHIP_SUCCESS) return oom ? CORDAHIP_ERR_OUT_OF_MEMORY : rc;
+        const uint8_t *hst = st.status.h.as<uint8_t>(), *hsig = st.sig_rows.h.as<uint8_t>();
+        const uint16_t* hl = st.sig_len.h.as<uint16_t>();
+        for (uint64_t r = 0; r < rows; r++) {
+          b->status[lanes[r]] = hst[r];
+          b->sig_len[lanes[r]] = hl[r];
+          std::memcpy(b->sig + lanes[r] * CORDAHIP_RSA_SIG_SLOT, hsig + r * 4 * W, 4 * W);
+        }
+      }
+    }
+    if (tracing())
+      fprintf(stderr, "[cordahip] dev %d RSA sign chunk: %llu lanes (%zu / %zu / %zu by class) in %.2f ms\n", d.id,
+              (unsigned long long)m, cl[0].size(), cl[1].size(), cl[2].size(), now_ms() - t0);
+  }
+  return CORDAHIP_SUCCESS;
+}
+
+int rsa_sign_impl(cordahip_ctx* ctx, const cordahip_rsa_sign_batch* b) {
+  const uint64_t n = b->n;
+  if (n == 0) return CORDAHIP_SUCCESS;
+  if (!b->key_id || !b->msg_off || !b->salt || !b->sig || !b->sig_len || !b->status) return CORDAHIP_ERR_INVALID_ARG;
+  if (!check_sign_batch(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
+  if (b->msg_off[0] != b->msg_off[n] && !b->msg) return CORDAHIP_ERR_INVALID_ARG;
+  return for_shards(ctx->devs, n, 64,
+                    [&](Device& d, uint64_t lo, uint64_t hi) { return rsa_sign_shard(ctx, d, b, lo, hi); });
+}
+
 // A device's cumulative counters of routed lanes: route_tot of the family's key table
 // `keys` (K14: Device::vkeys, K15: Device::ec_vkeys), written by kernels the table's
 // fence follows.
@@ -892,6 +1154,44 @@ int cordahip_ecdsa_sign_keyed_device(cordahip_ctx* ctx, int device, const void* 
     return ec_sign_enqueue(*d, ptr<uint32_t>(d_key_id), ptr<uint8_t>(d_msgs), nullptr, nullptr, msg_len, n,
                            ptr<uint8_t>(d_gate), ptr<uint8_t>(d_sigs), ptr<uint8_t>(d_sig_len),
                            ptr<uint8_t>(d_status), s);
+  });
+}
+
+int cordahip_signer_add_rsa(cordahip_ctx* ctx, const cordahip_rsa_private_key* key, uint32_t* key_id,
+                            uint8_t* key_status, uint8_t modulus[512], uint32_t* modulus_len) {
+  if (!ctx || !key || !key_id || !key_status || !modulus || !modulus_len) return CORDAHIP_ERR_INVALID_ARG;
+  if (!key->p || !key->q || !key->dp || !key->dq || !key->qinv) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return rsa_signer_add_impl(ctx, key, key_id, key_status, modulus, modulus_len); });
+}
+
+int cordahip_rsa_sign(cordahip_ctx* ctx, const cordahip_rsa_sign_batch* batch) {
+  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return rsa_sign_impl(ctx, batch); });
+}
+
+int cordahip_rsa_sign_submit(cordahip_ctx* ctx, const cordahip_rsa_sign_batch* batch, uint64_t* ticket) {
+  return submit(ctx, ticket, rsa_sign_impl, batch);
+}
+
+int cordahip_rsa_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
+                                   uint32_t msg_len, const void* d_salts, uint32_t mod_words, uint64_t n,
+                                   const void* d_gate, void* d_sigs, void* d_sig_len, void* d_status,
+                                   void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || (mod_words != 64 && mod_words != 96 && mod_words != 128) ||
+      (n && (!d_key_id || !d_salts || !d_sigs || !d_sig_len || !d_status || (msg_len && !d_msgs))))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if (misaligned(d_key_id, 4) || misaligned(d_sig_len, 2)) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    std::lock_guard<std::mutex> g(d->rsa_mu);
+    return device_call(
+        *d, hip_stream, [&] { return rsa_ws_grow(*d, mod_words, n); },
+        [&](hipStream_t s) {
+          std::lock_guard<std::mutex> gs(d->sign_mu);
+          return rsa_sign_enqueue(*d, ptr<uint32_t>(d_key_id), ptr<uint8_t>(d_msgs), nullptr, msg_len,
+                                  ptr<uint8_t>(d_salts), ptr<uint8_t>(d_gate), mod_words, n, ptr<uint8_t>(d_sigs),
+                                  ptr<uint16_t>(d_sig_len), ptr<uint8_t>(d_status), s);
+        });
   });
 }
 

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rsa_sign.hpp"
 #include "rsa_vkey.hpp"
 #include "runtime.hpp"
 #include "sha2_device.hpp"
@@ -496,5 +497,9 @@ hipError_t launch_rsa_pss_verify(const uint32_t* mod, const uint32_t* exp, const
 // K18, verification against registered keys: the kernels share this unit's device
 // functions (none of them changes; the generic kernels compile as before)
 #include "rsa_vkey.hip"
+
+// K19, signing with registered private keys: shares the group layout and SHA-256; its
+// Montgomery product is a constant-time variant of its own
+#include "rsa_sign_keyed.hip"
 
 }  // namespace cordahip

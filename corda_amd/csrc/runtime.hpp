@@ -252,6 +252,18 @@ hipError_t launch_rsa_verify_keyed(const uint32_t* vtab, const uint32_t* key_id,
                                    uint32_t msg_len, uint32_t W, uint64_t n, uint8_t* status,
                                    unsigned long long* verdict, uint8_t* ws, uint64_t ws_rows, uint32_t flags,
                                    hipStream_t s);
+// rsa_sign_keyed.hip (K19, in rsa.hip's unit): RSASSA-PSS signatures with registered
+// private keys. stab: the device's RSA signer table (rsa_sign.hpp: rsa_signtab_bytes();
+// null: no key was ever added, every ungated row is unknown); key_id[n], salts[n * 32],
+// gate[n] or null; one width class per launch; sigs: 4 W-byte slots, sig_len uint16[n].
+// ws as for launch_rsa_pss_verify. launch_rsa_sign_selftest: an add's consistency run
+// over the one row the host has put into the table's scratch.
+size_t rsa_signtab_bytes();
+hipError_t launch_rsa_sign_keyed(const uint32_t* stab, const uint32_t* key_id, const uint8_t* msgs,
+                                 const uint64_t* msg_off, uint32_t msg_len, const uint8_t* salts, const uint8_t* gate,
+                                 uint32_t W, uint64_t n, uint8_t* sigs, uint16_t* sig_len, uint8_t* status,
+                                 uint8_t* ws, uint64_t ws_rows, hipStream_t s);
+hipError_t launch_rsa_sign_selftest(uint32_t* stab, uint32_t W, hipStream_t s);
 hipError_t launch_ecdsa_sign(const uint8_t* scheme, const uint8_t* seeds, const uint8_t* msgs, uint32_t msg_len,
                              uint64_t n, const uint32_t* gk1, const uint32_t* gr1, uint8_t* keys, uint8_t* key_len,
                              uint8_t* sigs, uint8_t* sig_len, hipStream_t s);
@@ -604,6 +616,33 @@ struct EcSignKeys : KeyTable {
   void forget(uint32_t slot) { book.drop(slot); }
 };
 
+// The RSA signer's (rsa_sign.hpp: a slot -> record index over the pool's 4,096 slots, 64
+// records of 3,360 bytes -- n, n', K, qR and the secret p, q, dP, dQ, qInv with their
+// Montgomery constants -- and the scratch of an add's consistency run; 232,496 bytes):
+// private keys, zeroed by cordahip_shutdown like SignKeys (the index stays). The host
+// builds a record and it crosses in stage (wiped before add returns). rec_of / used:
+// which record a slot's key took (index + 1; 0: none) and which records are taken,
+// under Device::sign_mu.
+struct RsaSignKeys : KeyTable {
+  uint8_t rec_of[kSignKeySlots] = {};
+  uint8_t used[64] = {};
+  int take(uint32_t slot) {  // the first free record for the slot's key, or -1
+    for (int r = 0; r < 64; r++)
+      if (!used[r]) {
+        used[r] = 1;
+        rec_of[slot] = (uint8_t)(r + 1);
+        return r;
+      }
+    return -1;
+  }
+  TabSpan record(uint32_t slot) const;
+  TabSpan secrets() const;
+  void forget(uint32_t slot) {
+    if (rec_of[slot]) used[rec_of[slot] - 1] = 0;
+    rec_of[slot] = 0;
+  }
+};
+
 // The Ed25519 verification keys' (ed25519_vkey.hpp: 64 window tables of 512 KiB and the
 // base point's, their records and the build kernel's scratch). stage: 64 bytes, the key
 // bytes out and the decode verdict back. live: the slots whose record is live on this
@@ -660,15 +699,17 @@ struct StageBuf {
 // bytes a row, 72-byte DER slots for ECDSA), sig_len (ECDSA only), pre (the host's
 // pre-statuses) and verdict (words out); cordahip_rsa_verify_keyed uses sig_rows (4 W-byte
 // slots of one width class per launch), sig_len (uint16) and msg_off as a CSR of the
-// launch's rows. What a call does not use stays empty. mu is
+// launch's rows; cordahip_rsa_sign the same with sig_rows and sig_len (uint16) out, gate
+// and salt (32 bytes a row) in. What a call does not use stays empty. mu is
 // held for a shard's run; ev follows a chunk's last copy.
 struct KeyedStage {
   std::mutex mu;
-  StageBuf ids, msgs, msg_off, msg_len, status, gate, sig_rows, sig_len, pre, verdict;
+  StageBuf ids, msgs, msg_off, msg_len, status, gate, sig_rows, sig_len, pre, verdict, salt;
   Fence ev;
   template <class V>
   void visit(V& v) {
-    for (StageBuf* b : {&ids, &msgs, &msg_off, &msg_len, &status, &gate, &sig_rows, &sig_len, &pre, &verdict}) {
+    for (StageBuf* b :
+         {&ids, &msgs, &msg_off, &msg_len, &status, &gate, &sig_rows, &sig_len, &pre, &verdict, &salt}) {
       v.pin(b->h, kFreed);
       v.dev(b->d, kFreed);
     }
@@ -826,6 +867,12 @@ struct Device {
   // comb tables, an allocation of their own under the same sign_mu, with a fence of
   // their own (ec_keys.ev) that add, remove and every signing call use as keys.ev is used.
   EcSignKeys ec_keys;
+  // RSA signing (K19): the records of the same registry's RSA keys, an allocation of
+  // their own under the same sign_mu, with a fence of their own. The signing calls borrow
+  // the RSA workspace, so they take rsa_mu first, as every user of it does, and sign_mu
+  // inside it: the host call rsa_mu -> sign_stage.mu -> sign_mu (per launch), the device
+  // call rsa_mu -> sign_mu. The workspace grows before sign_mu is taken.
+  RsaSignKeys rsa_keys;
   std::mutex sign_mu;
   uint32_t* comb() const { return reinterpret_cast<uint32_t*>(static_cast<char*>(btab.p) + ed25519_btable_bytes()); }
   // the chunk stage of cordahip_sign and cordahip_ecdsa_sign (KeyedStage)
@@ -918,6 +965,7 @@ struct Device {
   void signer_keys(F&& f) {
     f(keys);
     f(ec_keys);
+    f(rsa_keys);
   }
   template <class F>
   void verify_keys(F&& f) {
@@ -1231,6 +1279,11 @@ struct cordahip_ctx {
   };
   std::mutex rsa_mirror_mu;
   RsaVkeyMirror rsa_mirror[cordahip::kVkeySlots];
+  // the same of the signer's live RSA keys (id, class and bits only: no key material),
+  // under rsa_mirror_mu; rsa_signers: how many (at most CORDAHIP_RSA_SIGNER_MAX_KEYS),
+  // under signers.mu
+  RsaVkeyMirror rsa_sign_mirror[cordahip::kSignKeySlots];
+  uint32_t rsa_signers = 0;
   // the notary commit logs (cordahip_commit_log_create / _destroy): id -> log; ids
   // count up and are never reused. logs_mu guards the map and the counter only.
   std::mutex logs_mu;

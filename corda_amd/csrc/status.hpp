@@ -14,7 +14,7 @@ static constexpr uint8_t kStatusEmpty = 5;        // IllegalArgumentException (e
 // signing lanes (CORDAHIP_SIGN_*)
 static constexpr uint8_t kSignUnknownKey = 14;    // no such key in the registry (KMS lookup fails)
 static constexpr uint8_t kSignSkipped = 15;       // the lane's gate byte was nonzero
-static constexpr uint8_t kSignFailed = 16;        // ECDSA: every nonce candidate of the bounded loop was rejected
+static constexpr uint8_t kSignFailed = 16;        // ECDSA: every nonce candidate of the bounded loop was rejected; RSA: the fault check failed
 // keyed verification lanes (CORDAHIP_VERIFY_UNKNOWN_KEY)
 static constexpr uint8_t kVerifyUnknownKey = 16;  // no such key in the verification-key registry
 }  // namespace cordahip

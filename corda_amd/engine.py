@@ -204,7 +204,7 @@ class Engine:
 
     def signer_family(self, key_id: int):
         """The family of a signer id this engine registered and has not removed: "ed25519", 2
-        (ECDSA secp256k1) or 3 (ECDSA P-256); None for any other id."""
+        (ECDSA secp256k1), 3 (ECDSA P-256) or "rsa"; None for any other id."""
         return self._signer_family.get(int(key_id))
 
     def ecdsa_sign_batch(self, key_ids: Sequence[int], msgs: Sequence[bytes], gate=None, async_: bool = False):
@@ -223,6 +223,59 @@ class Engine:
         (k, m, g, sg, sl, st), s = self._dev_args(stream, key_ids, msgs, gate, sigs, sig_len, status)
         check(lib().cordahip_ecdsa_sign_keyed_device(self._ctx, device, k, m, msgs.shape[1], key_ids.shape[0], g, sg,
                                                      sl, st, s), "cordahip_ecdsa_sign_keyed_device")
+
+    # ---- RSA_SHA256 signing with registered private keys (RSASSA-PSS, caller's salts) ------
+    def signer_add_rsa(self, p: int, q: int, dp: int, dq: int, qinv: int, e: int):
+        """cordahip_signer_add_rsa: the CRT components of an RSA private key (integers) and its public
+        exponent registered on every device of the context. Returns (key_id, key_status, modulus):
+        modulus is n = p q as k big-endian bytes; (SIGNER_NO_ID, UNSUPPORTED or BAD_KEY, None) for a
+        key the GPU path declines or that is not one (no slot taken). An e that does not fit 32 bits
+        cannot be expressed in the C call and is UNSUPPORTED here, as the verifier has it. Ids share the
+        signer's pool; signer_remove serves all three families."""
+        if not 0 <= e < 1 << 32:
+            return _lib.SIGNER_NO_ID, _lib.UNSUPPORTED, None
+        comp = [int(v).to_bytes(max((int(v).bit_length() + 7) // 8, 1), "big") for v in (p, q, dp, dq, qinv)]
+        key = _lib.RsaPrivateKey(*comp, *[len(c) for c in comp], e)
+        kid, st, ml = ctypes.c_uint32(), ctypes.c_uint8(), ctypes.c_uint32()
+        mod = ctypes.create_string_buffer(512)
+        check(lib().cordahip_signer_add_rsa(self._ctx, ctypes.byref(key), ctypes.byref(kid), ctypes.byref(st), mod,
+                                            ctypes.byref(ml)), "cordahip_signer_add_rsa")
+        if st.value != 0:
+            return kid.value, st.value, None
+        self._signer_family[kid.value] = "rsa"
+        return kid.value, st.value, mod.raw[:ml.value]
+
+    def rsa_sign_batch(self, key_ids: Sequence[int], msgs: Sequence[bytes], salts: Sequence[bytes], gate=None,
+                       async_: bool = False):
+        """cordahip_rsa_sign / cordahip_rsa_sign_submit: lane i signs msgs[i] with the RSA key key_ids[i]
+        under the 32-byte salt salts[i] unless gate[i] is nonzero. Returns (sigs[n, 512], sig_len[n],
+        status[n]) -- k bytes at the start of each slot, zero rows and length 0 where status is not OK
+        -- or, async_, a Ticket whose wait() returns them."""
+        n = len(msgs)
+        assert len(key_ids) == n and len(salts) == n and (gate is None or len(gate) == n)
+        assert all(len(x) == 32 for x in salts)
+        ids = np.ascontiguousarray(np.asarray(list(key_ids) or [0], dtype=np.uint32))
+        mb, mo = self._csr(list(msgs))
+        sa = np.frombuffer(b"".join(bytes(x) for x in salts) or bytes(32), dtype=np.uint8).copy()
+        g = None if gate is None else np.ascontiguousarray(np.asarray(list(gate) or [0], dtype=np.uint8))
+        sig = np.zeros((max(n, 1), _lib.RSA_SIG_SLOT), dtype=np.uint8)
+        sl = np.zeros(max(n, 1), dtype=np.uint16)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        b = _lib.RsaSignBatch(n, _ptr(ids), _ptr(mb), _ptr(mo), _ptr(g) if g is not None else None, _ptr(sa),
+                              _ptr(sig), _ptr(sl), _ptr(st), mb.size if n and mo[n] else 0)
+        return self._run("cordahip_rsa_sign", b, async_, lambda: (sig[:n], sl[:n], st[:n]),
+                         (ids, mb, mo, sa, g, sig, sl, st))
+
+    def rsa_sign_keyed_device(self, key_ids, msgs, salts, sigs, sig_len, status, gate=None, device: int = 0,
+                              stream=None):
+        """cordahip_rsa_sign_keyed_device over device tensors, one width class W = sigs.shape[1] // 4 per
+        call: key_ids int32 [n], msgs uint8 [n, L], salts uint8 [n, 32], gate uint8 [n] or None
+        (typically the tx_status an earlier call on `stream` wrote); outputs sigs uint8 [n, 4 W],
+        sig_len int16 [n] and status uint8 [n]."""
+        (k, m, sa, g, sg, sl, st), s = self._dev_args(stream, key_ids, msgs, salts, gate, sigs, sig_len, status)
+        check(lib().cordahip_rsa_sign_keyed_device(self._ctx, device, k, m, msgs.shape[1], sa, sigs.shape[1] // 4,
+                                                   key_ids.shape[0], g, sg, sl, st, s),
+              "cordahip_rsa_sign_keyed_device")
 
     # ---- notary commit log (validateTimeWindow + commitInputStates per transaction) ----
     def commit_log_create(self, capacity_log2: int, device: int = 0, salt: Optional[bytes] = None) -> int:

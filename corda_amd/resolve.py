@@ -24,6 +24,8 @@ of this (the Kotlin a maintainer adds) is sketched in INTEGRATION.md §3.
 """
 from __future__ import annotations
 
+import os
+
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence, Tuple, Union
 
@@ -237,12 +239,19 @@ def build_filtered_transactions(engine, wtxs, filtering: Callable[[bytes], bool]
     return out
 
 
-def _sign_with(engine, key_id: int, msgs, gate):
+def _sign_with(engine, key_id: int, msgs, gate, salts=None):
     """One signing call over msgs with the registered key `key_id`, gated: Engine.sign_batch for an
-    Ed25519 signer id, Engine.ecdsa_sign_batch for an ECDSA one (Engine.signer_family). Returns
-    (sigs, status): sigs[t] the signature bytes -- 64 bytes R || S, or the DER bytes of an ECDSA
-    signature -- for a lane whose status is OK."""
+    Ed25519 signer id, Engine.ecdsa_sign_batch for an ECDSA one, Engine.rsa_sign_batch for an RSA
+    one (Engine.signer_family). An RSA signature needs a 32-byte salt per lane: `salts`, else
+    os.urandom -- the JVM's SecureRandom in this mirror. Returns (sigs, status): sigs[t] the
+    signature bytes -- 64 bytes R || S, the DER bytes of an ECDSA signature, or the k bytes of an
+    RSA one -- for a lane whose status is OK."""
     family = getattr(engine, "signer_family", lambda k: None)(key_id)
+    if family == "rsa":
+        if salts is None:
+            salts = [os.urandom(32) for _ in msgs]
+        rows, lens, sst = engine.rsa_sign_batch([key_id] * len(msgs), msgs, salts, gate=gate)
+        return [bytes(rows[t][:int(lens[t])]) for t in range(len(msgs))], sst
     if family in (2, 3):
         rows, lens, sst = engine.ecdsa_sign_batch([key_id] * len(msgs), msgs, gate=gate)
         return [bytes(rows[t][:int(lens[t])]) for t in range(len(msgs))], sst

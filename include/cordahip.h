@@ -272,8 +272,8 @@ int cordahip_ed25519_sign_device(cordahip_ctx* ctx, int device, const void* d_se
  * (keyManagementService.sign(ftx.rootHash.bytes, key), NodeInterestRates.kt:149-180)
  * and ServiceHub.kt:138,179 reach it: a handful of long-lived keys, many 32-byte
  * ids. Ed25519 signing is deterministic (RFC 8032; i2p EdDSAEngine), so every
- * signature is bit-identical to the JVM's. ECDSA signing with registered keys is
- * the section after this one; RSA signing and CompositeSignature assembly are not
+ * signature is bit-identical to the JVM's. ECDSA and RSA signing with registered
+ * keys are the two sections after this one; CompositeSignature assembly is not
  * offered.
  *
  * Key registry. cordahip_signer_add_ed25519 expands the 32-byte seed on every
@@ -420,6 +420,105 @@ int cordahip_ecdsa_sign_submit(cordahip_ctx* ctx, const cordahip_ecdsa_sign_batc
 int cordahip_ecdsa_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
                                      uint32_t msg_len, uint64_t n, const void* d_gate, void* d_sigs,
                                      void* d_sig_len, void* d_status, void* hip_stream);
+
+/* ---- RSA_SHA256 batch signing with registered private keys (RSASSA-PSS) ---------- *
+ * Replaces, per lane, Crypto.doSign(RSA_SHA256, key, clearData) (Crypto.kt:394-401 ->
+ * JCA "SHA256WITHRSAANDMGF1" -> BouncyCastle PSSSigner.generateSignature) for a notary,
+ * oracle or issuer whose identity key is an RSA key. BouncyCastle draws the 32-byte
+ * salt from SecureRandom, so no implementation can reproduce the JVM's bytes; a
+ * signature is judged by its verifier. Here the caller draws the salt of every lane
+ * and passes it in: no random number generator on the GPU, and the output is a pure
+ * function of (key, message, salt). Per lane, with key (n, e, p, q, dP, dQ, qInv):
+ *   mHash = SHA-256(m), H = SHA-256(0x00 * 8 || mHash || salt),
+ *   DB = 0x00 .. || 0x01 || salt (emLen - 33 bytes; emBits = bits(n) - 1,
+ *   emLen = ceil(emBits / 8)), EM = (DB xor MGF1-SHA256(H)) with the bits above emBits
+ *   cleared || H || 0xBC (RFC 8017 9.1.1),
+ *   s = EM^d mod n by the CRT: m1 = EM^dP mod p, m2 = EM^dQ mod q,
+ *   h = qInv (m1 - m2) mod p, s = m2 + q h (RFC 8017 5.1.2 2.b),
+ *   sig = s as k = ceil(bits(n) / 8) big-endian bytes, left-padded with zeros (I2OSP).
+ * PARITY UNPINNED, like every PSS rule of this header: neither BouncyCastle's sources
+ * nor an RSA signature exist in the reference; the k-byte length is what RFC 8017 gives
+ * and what BC's engine is believed to return. The signatures verify under
+ * cordahip_sig_verify (CORDAHIP_FLAG_RSA_ON_DEVICE), cordahip_rsa_verify_keyed and
+ * OpenSSL.
+ * Before a signature leaves the device the kernel checks s^e mod n == EM with the key's
+ * public half; a lane that fails answers CORDAHIP_SIGN_FAILED with a zero slot (a CRT
+ * signature with one faulty half gives away a factor of n).
+ *
+ * Key registry. cordahip_signer_add_rsa takes the CRT components as big-endian
+ * magnitudes (any leading zeros) and e = RSAPrivateCrtKey.publicExponent; the host
+ * derives n = p q and the Montgomery constants. Ids come from the signer's one pool (the
+ * same id form), and cordahip_signer_remove serves all three families with the ordering
+ * stated above. A context holds at most CORDAHIP_RSA_SIGNER_MAX_KEYS live RSA signing
+ * keys; one more is CORDAHIP_ERR_OUT_OF_MEMORY. Data, not ABI errors (CORDAHIP_SUCCESS,
+ * *key_id = 0xFFFFFFFF, no slot taken):
+ *   CORDAHIP_STATUS_UNSUPPORTED  what the GPU path declines: bits(n) outside 1024..4096,
+ *                                or the larger prime above half the width class
+ *                                (16 * mod_words bits: unbalanced primes)
+ *   CORDAHIP_STATUS_BAD_KEY      a zero-length component; p or q even or < 3; p = q;
+ *                                e even or < 3; dP >= p, dQ >= q or qInv >= p; or the
+ *                                consistency run fails: every device signs a fixed EM with
+ *                                the new record and checks it with (n, e), which catches a
+ *                                dP, dQ or qInv that does not belong to p, q and e.
+ * Primality is not checked. A NULL pointer is CORDAHIP_ERR_INVALID_ARG. On success
+ * modulus receives n as k big-endian bytes (the rest of the 512 zero) and
+ * *modulus_len = k; every device must agree. The RSA signer table (a slot -> record
+ * index over the pool's 4096 slots and 64 records of 3360 bytes: 232,496 bytes per
+ * device) is an allocation of its own, made by the first RSA add that reaches a device,
+ * counted in cordahip_device_mem and kept by cordahip_trim and the idle release.
+ * Custody is the other signers': the components cross through page-locked staging wiped
+ * before add returns; the host keeps id, width class and bit length only; remove and
+ * shutdown zero the record on every device; the kernel keeps m1, m2 and h in registers
+ * and zeroes its LDS table before it ends; CORDAHIP_TRACE never prints key material. The
+ * kernel reads no address and takes no branch that depends on p, q, dP, dQ, qInv, their
+ * window digits or any intermediate mod p or mod q.
+ *
+ * Per-lane statuses, by precedence: CORDAHIP_SIGN_SKIPPED, CORDAHIP_SIGN_UNKNOWN_KEY (no
+ * live RSA signer of that id -- also an Ed25519 or ECDSA signer id, and in the device
+ * call a key of another width class; an RSA id handed to cordahip_sign* or
+ * cordahip_ecdsa_sign* answers the same), CORDAHIP_STATUS_EMPTY, CORDAHIP_SIGN_FAILED,
+ * then CORDAHIP_STATUS_OK: sig[i*512 .. i*512+sig_len[i]) is the signature, the rest of
+ * the slot zero. Every lane that is not OK gets a zero slot and length 0; no secret is
+ * read for it.
+ *
+ * cordahip_rsa_sign / _submit: host memory, CSR checked whole before any enqueue (a NULL
+ * salt is CORDAHIP_ERR_INVALID_ARG, outputs untouched), sharding, CORDAHIP_HOST_CHUNK
+ * chunking and tickets as for cordahip_sign; a chunk's lanes are grouped by their key's
+ * width class and each class runs over its rows only. */
+#define CORDAHIP_RSA_SIGNER_MAX_KEYS 64
+#define CORDAHIP_RSA_SIG_SLOT 512
+typedef struct {              /* big-endian magnitudes, any leading zeros */
+  const uint8_t *p, *q, *dp, *dq, *qinv;
+  uint32_t p_len, q_len, dp_len, dq_len, qinv_len;
+  uint32_t e;                 /* RSAPrivateCrtKey.publicExponent */
+} cordahip_rsa_private_key;
+int cordahip_signer_add_rsa(cordahip_ctx* ctx, const cordahip_rsa_private_key* key, uint32_t* key_id,
+                            uint8_t* key_status, uint8_t modulus[512], uint32_t* modulus_len);
+typedef struct {
+  uint64_t n;
+  const uint32_t* key_id;  /* [n] ids from cordahip_signer_add_rsa */
+  const uint8_t* msg;
+  const uint64_t* msg_off; /* [n+1] into msg */
+  const uint8_t* gate;     /* [n] nonzero: skip the lane; may be NULL */
+  const uint8_t* salt;     /* [n*32], required */
+  uint8_t* sig;            /* [n*512] out: k bytes at the start of the slot, rest zero */
+  uint16_t* sig_len;       /* [n] out: k, or 0 */
+  uint8_t* status;         /* [n] out */
+  uint64_t msg_bytes;      /* bytes at msg; msg_off[n] <= msg_bytes */
+} cordahip_rsa_sign_batch;
+int cordahip_rsa_sign(cordahip_ctx* ctx, const cordahip_rsa_sign_batch* batch);
+int cordahip_rsa_sign_submit(cordahip_ctx* ctx, const cordahip_rsa_sign_batch* batch, uint64_t* ticket);
+/* Device-resident form, one width class per call (mod_words = 64 / 96 / 128 for moduli
+ * of up to 2048 / 3072 / 4096 bits): d_key_id uint32[n], d_msgs dense rows of msg_len
+ * bytes, d_salts [n*32], d_gate uint8[n] or NULL, d_sigs [n] slots of 4*mod_words
+ * bytes, d_sig_len uint16[n], d_status [n], all in HBM on `device`, on hip_stream. d_gate
+ * is typically the tx_status an earlier call on the same stream wrote. A key of another
+ * class is CORDAHIP_SIGN_UNKNOWN_KEY; msg_len == 0 makes every ungated lane with a live
+ * key EMPTY. */
+int cordahip_rsa_sign_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_msgs,
+                                   uint32_t msg_len, const void* d_salts, uint32_t mod_words, uint64_t n,
+                                   const void* d_gate, void* d_sigs /* 4*mod_words-byte slots */,
+                                   void* d_sig_len /* uint16[n] */, void* d_status, void* hip_stream);
 
 /* ---- Ed25519 batch verification against registered public keys ----------------- *
  * Replaces, per lane, Crypto.doVerify / Crypto.isValid(EDDSA_ED25519_SHA512, key,

@@ -180,6 +180,8 @@ int main() {
     visited(esk, sizeof(CurveBook<cordahip::kSignKeySlots>) /* book */, "EcSignKeys");
     static_assert(sizeof(CurveBook<cordahip::kSignKeySlots>) == 4 * sizeof(uint32_t) + cordahip::kSignKeySlots,
                   "built, live and a byte per slot");
+    RsaSignKeys rsk;
+    visited(rsk, cordahip::kSignKeySlots /* rec_of */ + 64 /* used */, "RsaSignKeys");
     VerifyKeys vk;
     visited(vk, sizeof(uint64_t) /* live */, "VerifyKeys");
     EcVerifyKeys ek;
@@ -208,9 +210,10 @@ int main() {
     // and the two routing switches (route_on, ec_route_on: each padded to 8 bytes)
     // and the ECDSA signer's table with what the host knows of it (f)
     // and the registered RSA keys' table (f)
+    // and the RSA signer's table with what the host knows of it (f)
     constexpr size_t kDeviceOwnPlain = 1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys) + 2 * sizeof(std::mutex) +
                                        sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + 16 + sizeof(EcSignKeys) +
-                                       sizeof(RsaVerifyKeys);
+                                       sizeof(RsaVerifyKeys) + sizeof(RsaSignKeys);
     const Count c = visited(*d, kDeviceOwnPlain + kTxSets * kTxSetPlain + kPackStages * kPackPlain, "Device");
     ndev = c.ndev, npin = c.npin, nev = c.nfence + c.nevent;
     CHECK(c.nstream == 7);
@@ -272,10 +275,11 @@ int main() {
     size_t nsign = 0, nver = 0;  // visit_keys is the two walks of the families
     k->signer_keys([&](auto&) { nsign++; });
     k->verify_keys([&](auto&) { nver++; });
-    CHECK(nsign == 2 && nver == 3);
-    // the five tables and the routed lanes' counters (VerifyKeys::route_tot, EcVerifyKeys::route_tot)
-    CHECK(g.dev.size() == before + 7 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
+    CHECK(nsign == 3 && nver == 3);
+    // the six tables and the routed lanes' counters (VerifyKeys::route_tot, EcVerifyKeys::route_tot)
+    CHECK(g.dev.size() == before + 8 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
     CHECK(k->ec_keys.tab.dev == 6 && k->ec_keys.tab.p && k->ec_keys.stage.p && k->ec_keys.ev.ev);
+    CHECK(k->rsa_keys.tab.dev == 6 && k->rsa_keys.tab.p && k->rsa_keys.stage.p && k->rsa_keys.ev.ev);
     CHECK(k->vkeys.route_tot.dev == 6 && k->vkeys.route_tot.p);
     CHECK(k->ec_vkeys.route_tot.dev == 6 && k->ec_vkeys.route_tot.p);
     CHECK(k->vkeys.tab.dev == 6 && k->vkeys.tab.p && k->vkeys.stage.p && k->vkeys.ev.ev);
@@ -285,7 +289,9 @@ int main() {
     void *stab = k->ec_keys.tab.p, *sstage = k->ec_keys.stage.p;
     CHECK(k->rsa_vkeys.tab.dev == 6 && k->rsa_vkeys.tab.p && k->rsa_vkeys.stage.p && k->rsa_vkeys.ev.ev);
     void *rtab = k->rsa_vkeys.tab.p, *rstage = k->rsa_vkeys.stage.p;
+    void *rstab = k->rsa_keys.tab.p, *rsstage = k->rsa_keys.stage.p;
     k->release_idle();
+    CHECK(k->rsa_keys.tab.p == rstab && k->rsa_keys.stage.p == rsstage && g.dev.count(rstab) && g.pin.count(rsstage));
     CHECK(k->rsa_vkeys.tab.p == rtab && k->rsa_vkeys.stage.p == rstage && g.dev.count(rtab) && g.pin.count(rstage));
     CHECK(k->ec_keys.tab.p == stab && k->ec_keys.stage.p == sstage && g.dev.count(stab) && g.pin.count(sstage));
     CHECK(k->keys.tab.p == tab && k->keys.stage.p == stage && g.dev.count(tab) && g.pin.count(stage));
@@ -296,7 +302,7 @@ int main() {
     CHECK(kk.devs.size() == kept.devs.size());
     CHECK(mem_acct(6).in_use.load() ==
           kk.bytes + k->keys.tab.cap + k->ec_keys.tab.cap + k->vkeys.tab.cap + k->vkeys.route_tot.cap +
-              k->ec_vkeys.tab.cap + k->ec_vkeys.route_tot.cap + k->rsa_vkeys.tab.cap);
+              k->ec_vkeys.tab.cap + k->ec_vkeys.route_tot.cap + k->rsa_vkeys.tab.cap + k->rsa_keys.tab.cap);
     delete k;
     CHECK(g.clean() && mem_acct(6).in_use.load() == 0);
   }
