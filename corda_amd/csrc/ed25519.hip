@@ -39,7 +39,9 @@ namespace cordahip {
 // ---------------------------------------------------------------------------
 // B table (layout: ed25519_ws.hpp), built once per context by a kernel
 // (ge_base, store_niels_entry: ed25519_ops.hpp).
-// tab: entries [0, kBTableEntries) = [k]B, then [k]B' with B' = [2^128]B
+// tab: entries [0, kBTableEntries) = [k]B, then [k]B' with B' = [2^(kBDigitsLo kBBits)]B.
+// One thread per entry: 2 (2^(kBBits-1) + 1) of them, so g and g * kBEntryWords
+// stay far below 2^31 (ed25519_ws.hpp asserts the latter).
 __global__ void __launch_bounds__(64) ed25519_btable_kernel(uint32_t* __restrict__ tab) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= 2 * kBTableEntries) return;
@@ -47,7 +49,7 @@ __global__ void __launch_bounds__(64) ed25519_btable_kernel(uint32_t* __restrict
   ge_p3 B, P;
   ge_base(B);
   if (g >= kBTableEntries)
-    for (int t = 0; t < kBDigits * kBBits; t++) ge_dbl<true>(B, B);
+    for (int t = 0; t < kBDigitsLo * kBBits; t++) ge_dbl<true>(B, B);
   ge_cached bc;
   ge_to_cached(bc, B);
   ge_identity(P);
@@ -475,7 +477,8 @@ CDEV void prep_msg_phase(const uint8_t* __restrict__ sigs, const uint8_t* __rest
   // what the ladder consumes (ed25519_sel.hpp): window selectors, B digits, window count
   uint32_t sel[32];
   sel_recode(sel, ka, kr, e, c0neg);
-  sel[kSelWords] = 0;
+#pragma unroll
+  for (int q = kSelWords; q < 32; q++) sel[q] = 0;
   uint4* o4 = reinterpret_cast<uint4*>(rec + kWhSel);
 #pragma unroll
   for (int q = 0; q < 8; q++) o4[q] = make_uint4(sel[4 * q], sel[4 * q + 1], sel[4 * q + 2], sel[4 * q + 3]);

@@ -9,9 +9,14 @@
 // once: one addition per window of an entry i(-A) + j(-R) of the per-lane joint
 // table (ed25519_joint.hpp; gathered from the workspace one window ahead, so
 // the two doublings hide the load; which entry, and the fixed-base digits, come
-// recoded from the prep: ed25519_sel.hpp), 16-bit Booth windows over B and
-// B' = [2^128]B from L2/MALL-resident tables (ed25519_ws.hpp). Digit positions are the same in every lane, so the
-// ladder never diverges; P == O is X == 0 and Y == Z (no inversion).
+// recoded from the prep: ed25519_sel.hpp), kBBits-bit Booth windows over B and
+// B' = [2^(kBDigitsLo kBBits)]B from shared tables (ed25519_ws.hpp). Digit
+// positions are the same in every lane, so the ladder never diverges. Three
+// group operations are cut to what the verdict needs: the top window's entry
+// is loaded as the accumulator instead of added to the identity
+// (ED_LADDER_TOP_LOAD), the high half of e has one digit fewer than the low
+// half at 20 and 18 bits, and the last addition stops at E, F, H
+// (ED_LADDER_LAST_EH, ge25519.hpp ge_madd_is_identity; no inversion either way).
 // A wave runs the windows of its longest lane, so a block hands its lanes to its
 // four waves in window-count order (ED_LADDER_ORDER); verdict words by ballot,
 // by the block's last wave.
@@ -52,6 +57,16 @@ static_assert(512 / ED_LADDER_WAVES >= 168, "fe25519_asm.hpp's v160..v167 accumu
 #if ED_LADDER_ORDER && !ED_SEL_STREAM
 #error "ED_LADDER_ORDER ranks the lanes by the selector stream's window count"
 #endif
+// ED_LADDER_TOP_LOAD: the top window sets P from its entry (ge_from_cached)
+// instead of adding the entry to the identity; 0: the addition.
+// ED_LADDER_LAST_EH: the verdict comes from the last addition's E, F, H
+// without its output stage; 0: from X, Y, Z of the full addition.
+#ifndef ED_LADDER_TOP_LOAD
+#define ED_LADDER_TOP_LOAD 1
+#endif
+#ifndef ED_LADDER_LAST_EH
+#define ED_LADDER_LAST_EH 1
+#endif
 static constexpr int kOrderLo = 60, kOrderHi = 74, kOrderKeys = kOrderHi - kOrderLo + 2;
 static_assert(kOrderKeys <= 64, "one lane of a wave per key");
 
@@ -80,11 +95,13 @@ CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict
     uint4 v[(kSelWords + 3) / 4];
 #pragma unroll
     for (int q = 0; q < (kSelWords + 3) / 4; q++) v[q] = r4[q];
-    static_assert(kSelMeta == 30 && (kSelWords + 3) / 4 == 8, "the count is in the last quad's third word");
+    static_assert(kSelMeta / 4 == 7 && (kSelWords + 3) / 4 == 8, "the count is in the last quad");
+    const uint32_t meta = kSelMeta % 4 == 2 ? v[7].z : v[7].w;
+    static_assert(kSelMeta % 4 >= 2, "its third or fourth word");
     // a stable counting rank over the keys: the window count clamped to
     // [kOrderLo, kOrderHi] (fewer or more are rare and only order less well),
     // lanes past the batch last: they lengthen no wave (W below skips them)
-    const int cnt = (int)(v[7].z >> 16);
+    const int cnt = (int)(meta >> 16);
     const int key = l0 < m ? min(max(cnt, kOrderLo), kOrderHi) - kOrderLo : kOrderKeys - 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t before = 0, mine = 0;
@@ -149,15 +166,17 @@ CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict
   }
 #endif
   const uint32_t* col = &sk[0][threadIdx.x];
-  // at least the windows the fixed-base digits need (e's low half: kBDigits
-  // digits of kBBits bits); |c0|, c1 ~ 2^128 give 65. Lanes with fewer windows
-  // of their own select the identity above them. (A count is at most 129.)
+  // at least the windows the fixed-base digits need (kBDigitsLo digits of
+  // kBBits bits over B: kBMinWindows); |c0|, c1 ~ 2^128 give 65. Lanes with
+  // fewer windows of their own select the identity above them. (A count is at
+  // most 129.)
 #if ED_LADDER_ORDER
   const int own = active ? (int)(col[kSelMeta * 256] >> 16) : 0;  // a lane past the batch follows its wave
 #else
   const int own = (int)(col[kSelMeta * 256] >> 16);
 #endif
-  const int W = min(max(wave_max(own), (kBDigits - 1) * (kBBits / 2) + 1), kSelWindows);
+  const int W = min(max(wave_max(own), kBMinWindows), kSelWindows);
+  bool zero = false;
   // window j's selector is read while window j + 1 computes; its word and
   // field are the same in every lane
   uint32_t selw = col[((W - 1) / kSelPerWord) * 256];
@@ -170,42 +189,62 @@ CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict
     ge_cached c;  // issued before the doublings, consumed after them
     load_cached(c, idx == kSelIdentity ? ident : rec + kWhTab + idx * kWhEntryWords);
     // fixed-base window (W is the wave's maximum and may exceed 65: the low
-    // half's windows end at digit kBDigits - 1, the high half's digits ride on
-    // B'): its digits are read here, ahead of the doublings
-    const bool bwin = j % (kBBits / 2) == 0 && j < kBDigits * (kBBits / 2);
+    // digits' windows end at digit kBDigitsLo - 1, the high digits ride on B';
+    // the windows from kBDigitsHi up have a low digit only): its digits are
+    // read here, ahead of the doublings
+    const bool bwin = j % kBWin == 0 && j < kBDigitsLo * kBWin;
+    const int t = j / kBWin;
+    const bool hi = t < kBDigitsHi;
     uint32_t m0 = 0, m1 = 0, sg = 0;
-    const int t = j / (kBBits / 2);
     if (bwin) {
-      m0 = col[(kSelMag + (t >> 1)) * 256];
-      m1 = col[(kSelMag + ((t + kBDigits) >> 1)) * 256];
+      m0 = sel_bmag(col, 256, t);
+      if (hi) m1 = sel_bmag(col, 256, t + kBDigitsLo);
       sg = col[kSelMeta * 256];
     }
-    if (j != W - 1) {
+    const bool top = j == W - 1;
+    if (!top) {
       ge_dbl<false>(P, P);
       ge_dbl<true>(P, P);
     }
     cached_cneg(c, neg);
     if (bwin) {
-      // the L2 gather of each niels entry is issued one addition ahead of its
-      // use (registers allow no more)
-      const int sh = 16 * (t & 1);
-      ge_niels nb0, nb1;
-      uint32_t pad0[2], pad1[2];
-      load_niels(nb0, btab, (int)((m0 >> sh) & 0xffffu), pad0);
-      ge_add<true>(P, P, c);
-      load_niels(nb1, btab2, (int)((m1 >> sh) & 0xffffu), pad1);
-      niels_pad_use(pad0);
-      niels_cneg(nb0, (sg >> t) & 1u);
-      ge_madd<true>(P, P, nb0);
-      niels_pad_use(pad1);
-      niels_cneg(nb1, (sg >> (t + kBDigits)) & 1u);
-      ge_madd<false>(P, P, nb1);
+      // the gather of each niels entry is issued one addition ahead of its use
+      // (registers allow no more). The low digit's addition comes last, so the
+      // windows without a high digit skip the middle one and share the rest.
+      ge_niels nb;
+      uint32_t pad[2];
+      bool nbneg = sel_bneg(sg, hi ? t + kBDigitsLo : t);
+      load_niels(nb, hi ? btab2 : btab, (int)(hi ? m1 : m0), pad);
+      ge_add<true>(P, P, c);  // the top window too: it is one only in a wave without scalars of its own
+      if (hi) {
+        ge_niels nb0;
+        uint32_t pad0[2];
+        load_niels(nb0, btab, (int)m0, pad0);
+        niels_pad_use(pad);
+        niels_cneg(nb, nbneg);
+        ge_madd<true>(P, P, nb);
+        nb = nb0;
+        pad[0] = pad0[0];
+        pad[1] = pad0[1];
+        nbneg = sel_bneg(sg, t);
+      }
+      niels_pad_use(pad);
+      niels_cneg(nb, nbneg);
+#if ED_LADDER_LAST_EH
+      if (j == 0) zero = ge_madd_is_identity(P, nb);
+      else ge_madd<false>(P, P, nb);
+#else
+      ge_madd<false>(P, P, nb);
+#endif
+    } else if (ED_LADDER_TOP_LOAD && top) {
+      ge_from_cached(P, c);  // the two doublings that follow need no T
     } else {
       ge_add<false>(P, P, c);
     }
     selw = selw_next;
   }
 #else
+  static_assert(kBBits == 16 && kBDigitsLo == kBDigitsHi, "without the selector stream the ladder is 16-bit only");
   // |c0|, c1 and e live in LDS (word-major, one column per thread): each window
   // reads two words of each, and the 24 VGPRs they would pin across the loop
   // go to the group formulas' wider product blocks instead
@@ -228,9 +267,9 @@ CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict
     bits = max(mp8_bitlen(ka), mp8_bitlen(kr));
   }
   const bool c0neg = rec[kWhFlags] & 1u;  // [c0](-A) with c0 < 0 is [|c0|]A: flip the digit signs
-  // at least the windows the fixed-base digits need (e's low half: kBDigits
+  // at least the windows the fixed-base digits need (e's low half: kBDigitsLo
   // digits of kBBits bits); |c0|, c1 ~ 2^128 give 65
-  const int W = max(wave_max((bits + 2) / 2), (kBDigits - 1) * (kBBits / 2) + 1);
+  const int W = max(wave_max((bits + 2) / 2), kBMinWindows);
   for (int j = W - 1; j >= 0; j--) {
     const joint_sel sel = joint_select(joint_booth2(ska, 256, 8, j), joint_booth2(skr, 256, 8, j), c0neg);
     ge_cached c;  // issued before the doublings, consumed after them
@@ -243,11 +282,11 @@ CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict
     // fixed-base window: the L2 gather of each niels entry is issued one
     // addition ahead of its use (registers allow no more)
     // (W is the wave's maximum and may exceed 65: the low half's windows end at
-    // digit kBDigits - 1, the high half's digits ride on B')
-    const bool bwin = j % (kBBits / 2) == 0 && j < kBDigits * (kBBits / 2);
+    // digit kBDigitsLo - 1, the high half's digits ride on B')
+    const bool bwin = j % (kBBits / 2) == 0 && j < kBDigitsLo * (kBBits / 2);
     if (bwin) {
       const int d0 = booth_digit_col<kBBits>(ske, j / (kBBits / 2));
-      const int d1 = booth_digit_col<kBBits>(ske, j / (kBBits / 2) + kBDigits);
+      const int d1 = booth_digit_col<kBBits>(ske, j / (kBBits / 2) + kBDigitsLo);
       ge_niels nb0, nb1;
       load_niels(nb0, btab, d0 < 0 ? -d0 : d0);
       ge_add<true>(P, P, c);
@@ -260,10 +299,17 @@ CDEV void ladder_half_lane(uint64_t base, uint64_t m, const uint32_t* __restrict
       ge_add<false>(P, P, c);
     }
   }
-#endif
   fe d;
   fe_sub(d, P.Y, P.Z);
   const bool zero = fe_iszero(P.X) && fe_iszero(d);
+#endif
+#if ED_SEL_STREAM && !ED_LADDER_LAST_EH
+  {
+    fe d;
+    fe_sub(d, P.Y, P.Z);
+    zero = fe_iszero(P.X) && fe_iszero(d);  // P == O is X == 0 and Y == Z
+  }
+#endif
   const uint64_t i = kIdx ? (active ? list[base + li] : 0) : base + li;
   uint8_t st = kStatusBadSig;
   if (active) {

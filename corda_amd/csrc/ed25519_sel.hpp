@@ -9,12 +9,20 @@
 //                   bit 4 (kSelNeg) set when the window adds the entry's negative.
 //                   The digits past a scalar's last window are zero, so the
 //                   windows at or above the lane's own count select the identity.
-//   words 22 .. 29  the 16 fixed-base Booth digits of e (width 16: 8 over the
-//                   low half for B, 8 over the high half for B' = [2^128]B) as
-//                   magnitudes 0 .. 32768, digit t in half t & 1 of word
-//                   22 + (t >> 1)
-//   word  30        bit t: digit t is negative; bits 16 .. 23: the lane's window
-//                   count (bitlen(max(|c0|, c1)) + 2) / 2
+//   words 22 ..     the kBDigits fixed-base Booth digits of e of width kBBits
+//                   (ED_B_BITS: 20, 18 or 16): kBDigitsLo over B, then kBDigitsHi
+//                   over B' = [2^(kBDigitsLo kBBits)]B, as magnitudes
+//                   0 .. 2^(kBBits - 1), one bit string of kBBits-bit fields:
+//                   digit t at bit kBBits t of the kSelMagWords words (9, 9, 8;
+//                   at width 16 that is half t & 1 of word 22 + (t >> 1))
+//   word kSelMeta   (31, 31, 30) bit t: digit t is negative; bits 16 .. 23: the
+//                   lane's window count (bitlen(max(|c0|, c1)) + 2) / 2
+//
+// The number of fixed-base additions is the number of digits, ceil(254 / kBBits)
+// (e < 2^253 and the Booth carry), whatever the tables cost: 13 at width 20 (7 + 6),
+// 15 at 18 (8 + 7), 16 at 16 (8 + 8). The low digits end at the ladder's window
+// (kBDigitsLo - 1) kBBits / 2, which has to be a window every lane has anyway
+// (64 of them: |c0|, c1 ~ 2^128), hence the uneven splits.
 //
 // 132 windows, because the scalars are not always half-size: |c0|, c1 < 8L <
 // 2^256 need up to 129. Where Euclid's short vector has an even c1 the prep
@@ -39,10 +47,26 @@ static constexpr int kSelPerWord = 6, kSelBits = 5;
 static constexpr int kSelWindows = 132;                       // >= 129, whole words
 static constexpr uint32_t kSelIdentity = 15;
 static constexpr uint32_t kSelNeg = 16;
-static constexpr int kSelBDigits = 16;                        // both halves of e
-static constexpr int kSelMag = kSelWindows / kSelPerWord;     // word of the first magnitude pair
-static constexpr int kSelMeta = kSelMag + kSelBDigits / 2;    // signs and window count
-static constexpr int kSelWords = kSelMeta + 1;                // 31
+// width of the fixed-base Booth windows over e: a multiple of the ladder's 2-bit
+// window, so both share the doublings
+#ifndef ED_B_BITS
+#define ED_B_BITS 20
+#endif
+static constexpr int kBBits = ED_B_BITS;
+static_assert(kBBits == 16 || kBBits == 18 || kBBits == 20, "ED_B_BITS: 16, 18 or 20");
+static constexpr int kBWin = kBBits / 2;                      // ladder windows per fixed-base window
+static constexpr int kBDigitsLo = 63 / kBWin + 1;             // over B: 8, 8, 7
+static constexpr int kBDigitsHi = (254 + kBBits - 1) / kBBits - kBDigitsLo;  // over B': 8, 7, 6
+static constexpr int kBDigits = kBDigitsLo + kBDigitsHi;
+static constexpr int kBMinWindows = (kBDigitsLo - 1) * kBWin + 1;  // the low digits' top window, counted
+static_assert(kBDigits * kBBits >= 254, "e < 2^253 and the Booth carry");
+static_assert(kBMinWindows <= 64, "the digits force no window a normal lane does not have");
+static_assert(kBDigitsHi >= 1 && kBDigitsHi <= kBDigitsLo, "a window's high digit has a low digit beside it");
+static constexpr int kSelMag = kSelWindows / kSelPerWord;     // word of the first magnitude
+static constexpr int kSelMagWords = (kBDigits * kBBits + 31) / 32;
+static constexpr int kSelMeta = kSelMag + kSelMagWords;       // signs and window count
+static constexpr int kSelWords = kSelMeta + 1;                // 32 (width 16: 31)
+static_assert(kBDigits <= 16, "the meta word's sign bits");
 static constexpr int kSelAlways = 80;                         // windows recoded for every lane: scalar words 0 .. 4
 static_assert(kSelWindows % kSelPerWord == 0 && kSelWindows >= 129 && kSelWords <= 32,
               "the stream lives in the record's 32 scalar words");
@@ -108,15 +132,24 @@ JOINT_HD void sel_recode(uint32_t out[kSelWords], const uint32_t c0abs[8], const
     for (int w = kSelAlways / 16; w <= 8; w++)
       sel_word(out, w, (w < 8 ? c0abs[w] : 0u) ^ flip, w < 8 ? c1[w] : 0u, (c0abs[w - 1] ^ flip) >> 31, c1[w - 1] >> 31);
   }
-  // fixed-base digits of width 16 (sc25519.hpp booth_digit<16>): digit t reads
-  // the bits 16 t - 1 .. 16 t + 15, half a word and the bit below it
+  // fixed-base digits of width kBBits (sc25519.hpp booth_digit<kBBits>): digit t
+  // reads the bits kBBits t - 1 .. kBBits t + kBBits - 1 (bit -1 and the bits
+  // from 256 up are zero), every position a constant
   uint32_t signs = 0;
 #pragma unroll
-  for (int w = 0; w < kSelBDigits / 2; w++) {
-    const uint32_t v0 = ((e[w] << 1) | (w ? e[w - 1] >> 31 : 0u)) & 0x1ffffu, v1 = e[w] >> 15;
-    const int d0 = (int)((v0 + 1) >> 1) - (int)((v0 >> 16) << 16), d1 = (int)((v1 + 1) >> 1) - (int)((v1 >> 16) << 16);
-    signs |= (d0 < 0 ? 1u : 0u) << (2 * w) | (d1 < 0 ? 1u : 0u) << (2 * w + 1);
-    out[kSelMag + w] = (uint32_t)(d0 < 0 ? -d0 : d0) | (uint32_t)(d1 < 0 ? -d1 : d1) << 16;
+  for (int w = 0; w < kSelMagWords; w++) out[kSelMag + w] = 0;
+#pragma unroll
+  for (int t = 0; t < kBDigits; t++) {
+    const int lo = kBBits * t - 1, w = lo < 0 ? 0 : lo >> 5, sh = lo < 0 ? 0 : lo & 31;
+    uint32_t v = lo < 0 ? e[0] << 1 : e[w] >> sh;
+    if (sh && w + 1 < 8) v |= e[w + 1] << (32 - sh);
+    v &= (2u << kBBits) - 1;
+    const int d = (int)((v + 1) >> 1) - (int)((v >> kBBits) << kBBits);
+    const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+    signs |= (d < 0 ? 1u : 0u) << t;
+    const int ow = (kBBits * t) >> 5, osh = (kBBits * t) & 31;
+    out[kSelMag + ow] |= mag << osh;
+    if (osh + kBBits > 32) out[kSelMag + ow + 1] |= mag >> (32 - osh);
   }
   // bitlen(max(|c0|, c1)) is the bit length of their OR
   int bits = 0;
@@ -133,9 +166,18 @@ JOINT_HD uint32_t sel_window(const uint32_t s[kSelWords], int j) {
   return (s[j / kSelPerWord] >> (kSelBits * (j % kSelPerWord))) & ((1u << kSelBits) - 1);
 }
 JOINT_HD int sel_count(const uint32_t s[kSelWords]) { return (int)((s[kSelMeta] >> 16) & 0xffu); }
+// magnitude of fixed-base digit t of a stream whose word w is s[w * stride] (the
+// ladder keeps it word-major in LDS): the field may straddle two words; the word
+// behind the last field's first is at most the meta word
+JOINT_HD uint32_t sel_bmag(const uint32_t* s, int stride, int t) {
+  const int w = kSelMag + ((kBBits * t) >> 5), sh = (kBBits * t) & 31;
+  const uint64_t two = (uint64_t)s[(w + 1) * stride] << 32 | s[w * stride];
+  return (uint32_t)(two >> sh) & ((1u << kBBits) - 1);
+}
+JOINT_HD bool sel_bneg(uint32_t meta, int t) { return (meta >> t) & 1u; }
 JOINT_HD int sel_bdigit(const uint32_t s[kSelWords], int t) {
-  const int mag = (int)((s[kSelMag + (t >> 1)] >> (16 * (t & 1))) & 0xffffu);
-  return (s[kSelMeta] >> t) & 1u ? -mag : mag;
+  const int mag = (int)sel_bmag(s, 1, t);
+  return sel_bneg(s[kSelMeta], t) ? -mag : mag;
 }
 
 }  // namespace cordahip

@@ -19,21 +19,24 @@
 
 namespace cordahip {
 
-// B tables for Booth windows of kBBits over e = e_lo + 2^128 e_hi: entry k
-// (0..2^15) = [k]B as affine niels (y+x, y-x, 2d*x*y), 32 u32 per entry (30
-// limbs + 2 pad); entries [kBTableEntries, 2 kBTableEntries) = [k]B',
-// B' = [2^(kBDigits kBBits)]B = [2^128]B. 2 x 4.2 MB, L2/MALL-resident. 16-bit
-// windows give 16 fixed-base additions per verification (12-bit: 22, 8-bit
-// from LDS: 32; profiles/r02_c2_bwin12_ab.json); the window is a multiple of
-// the ladder's 4-bit one so both share the doublings.
-static constexpr int kBBits = 16;
-static constexpr int kBDigits = 8;  // per half: 8 x 16 = 128 bits
+// B tables for Booth windows of kBBits over e (kBBits, the digit counts and the
+// reasons for them: ed25519_sel.hpp): entry k (0..2^(kBBits-1)) = [k]B as affine
+// niels (y+x, y-x, 2d*x*y), 32 u32 per entry (30 limbs + 2 pad); entries
+// [kBTableEntries, 2 kBTableEntries) = [k]B', B' = [2^(kBDigitsLo kBBits)]B.
+// Fixed-base additions per verification and table size by window width:
+//   20 bits  13 (7 over B + 6 over B' = [2^140]B)  2 x 67.1 MB, gathered from HBM
+//   18 bits  15 (8 + 7, B' = [2^144]B)             2 x 16.8 MB
+//   16 bits  16 (8 + 8, B' = [2^128]B)             2 x 4.2 MB, L2/MALL-resident
+// (12-bit: 22, 8-bit from LDS: 32; profiles/r02_c2_bwin12_ab.json; 16 against
+// 18 and 20: profiles/r24_c2_ladder_ops_ab.json.) The table is built once per
+// context and sits outside the workspace budget. The window is a multiple of
+// the ladder's 2-bit one so both share the doublings.
 static constexpr int kBTableEntries = (1 << (kBBits - 1)) + 1;
 static constexpr int kBEntryWords = 32;
 // the identity in cached form follows the two tables in their allocation (one
 // padded entry of the joint table's format, written by ed25519_btable_kernel)
 static constexpr int kBIdentityWord = 2 * kBTableEntries * kBEntryWords;
-static_assert(kSelBDigits == 2 * kBDigits, "ed25519_sel.hpp recodes both halves of e");
+static_assert((long long)2 * kBTableEntries * kBEntryWords + 64 < (1ll << 31), "table word offsets are ints");
 static constexpr uint8_t kStatusPending = 0xff;
 
 // Per-lane workspace record (2,432 B = 38 x 64 B, so every record and every
@@ -45,7 +48,7 @@ static constexpr uint8_t kStatusPending = 0xff;
 // (L2-resident) instead of a per-lane copy.
 //
 // The 32 words behind the table hold the ladder's selector stream
-// (ED_SEL_STREAM, ed25519_sel.hpp: 31 words) or, without it, |c0|, c1, e and
+// (ED_SEL_STREAM, ed25519_sel.hpp: kSelWords <= 32 words) or, without it, |c0|, c1, e and
 // the sign of c0. Between the two launches of the split prep the first 8 hold
 // Abyte.
 #ifndef ED_SEL_STREAM

@@ -166,6 +166,35 @@ CDEV void ge_madd(ge_p3& r, const ge_p3& p, const ge_niels& q) {
   ge_out_stage<WANT_T>(r, f, e, g, h);
 }
 
+// Whether p + q is the identity, without the sum: it is (F E : H G : F G), and
+// the formulas are complete on the curve, so for p, q on it Z = F G != 0; then
+// X == 0 is E == 0 and Y == Z is H == F (mod p), and the output stage's three
+// products are not needed. H - F = (B + A) - (2Z - C) as (A + B + C) - 2Z: a
+// sum of three tight values minus a 2x one, within fe_sub's bounds.
+CDEV bool ge_madd_is_identity(const ge_p3& p, const ge_niels& q) {
+  fe a, b, c, d, e, s, t, u;
+  fe_sub_loose(t, p.Y, p.X);
+  fe_add(u, p.Y, p.X);
+  fe_mul_triple(a, t, q.ymx, b, u, q.ypx, c, p.T, q.xy2d);
+  fe_sub(e, b, a);
+  fe_add(s, b, a);
+  fe_add(s, s, c);
+  fe_add(d, p.Z, p.Z);
+  fe_sub(s, s, d);
+  return fe_iszero(e) && fe_iszero(s);
+}
+
+// r = q as a projective point (2X : 2Y : 2Z) from the cached form, without T:
+// for a doubling<false> to follow. The identity entry (1, 1, 1, 0) gives
+// (0 : 2 : 2). Carried, so the coordinates are tight like an addition's.
+CDEV void ge_from_cached(ge_p3& r, const ge_cached& q) {
+  fe_sub(r.X, q.YpX, q.YmX);
+  fe_add(r.Y, q.YpX, q.YmX);
+  fe_carry(r.Y);
+  fe_add(r.Z, q.Z, q.Z);
+  fe_carry(r.Z);
+}
+
 // Canonical encoding (i2p GroupElement.toByteArray / ref10 ge_tobytes):
 // y = Y/Z reduced mod p, bit 255 = parity of x = X/Z.
 CDEV void ge_tobytes(uint32_t w[8], const ge_p3& p) {

@@ -5,10 +5,12 @@
 //   1. every window's selector with joint_select(joint_booth2(|c0|, j), joint_booth2(c1, j),
 //      c0neg); the windows at or above the lane's count select the identity;
 //   2. the window count with (bitlen(max(|c0|, c1)) + 2) / 2;
-//   3. the 16 fixed-base digits (magnitude 0 .. 32768 and sign) with booth_digit<16>(e, t);
+//   3. the kBDigits fixed-base digits (magnitude 0 .. 2^(kBBits - 1) and sign) with
+//      booth_digit<kBBits>(e, t) (the header's width, ED_B_BITS; tools/ed_bdigit_check.cpp
+//      covers the digits' extremes at every width);
 //   4. the stream alone gives the scalars back: decoding each byte to its digit
 //      pair, sum_j da_j 4^j == |c0| and sum_j dr_j 4^j == c1 over the count's
-//      windows, and sum_t d_t 2^(16 t) == e.
+//      windows, and sum_t d_t 2^(kBBits t) == e.
 // Usage: ed_sel_check <random cases> <seed>; prints one JSON line, exit 0 = pass.
 #include <stdint.h>
 #include <stdio.h>
@@ -124,15 +126,16 @@ static const char* check_case(const scalar& c0abs, const scalar& c1, const scala
   }
   if (!sa.equals(c0abs) || !sr.equals(c1)) return "sum of 2-bit digits";
   acc320 se;
-  for (int t = kSelBDigits - 1; t >= 0; t--) {
-    const int want = booth_digit<16>(e.w, t), got = sel_bdigit(s, t);
+  for (int t = kBDigits - 1; t >= 0; t--) {
+    const int want = booth_digit<kBBits>(e.w, t), got = sel_bdigit(s, t);
     if (got != want) return "fixed-base digit";
-    const int mag = (int)((s[kSelMag + (t >> 1)] >> (16 * (t & 1))) & 0xffffu);
-    if (mag > 32768 || mag != (want < 0 ? -want : want)) return "fixed-base magnitude";
+    const int mag = (int)sel_bmag(s, 1, t);
+    if (mag > (1 << (kBBits - 1)) || mag != (want < 0 ? -want : want)) return "fixed-base magnitude";
     if ((((s[kSelMeta] >> t) & 1u) != 0) != (want < 0)) return "fixed-base sign";
-    se.step(16, got);
+    se.step(kBBits, got);
   }
-  if (!se.equals(e)) return "sum of 16-bit digits";
+  if (!se.equals(e)) return "sum of the fixed-base digits";
+  if ((s[kSelMeta] & 0xffffu) >> kBDigits) return "sign bits past the digits";
   if ((s[kSelMeta] >> 24) != 0) return "meta word's spare bits";
   return nullptr;
 }

@@ -4,7 +4,7 @@ reference of tests/test_ed_half_choice.py and tests/test_gpu_ed_ladder_order.py)
 The prep (ed25519.hip half_scalars) runs Euclid on (8L, h) to the first
 remainder below sqrt(8L) and hands (rp, rc, tp, tc) to half_choose
 (ed25519_half.hpp), which picks (c0, c1) with c0 == c1 h (mod 8L), c1 odd.
-A lane then needs max((bitlen(max(|c0|, c1)) + 2) / 2, 57) ladder windows, and
+A lane then needs max((bitlen(max(|c0|, c1)) + 2) / 2, 61) ladder windows, and
 a wave of 64 lanes runs its longest lane's count. `choose` below is that
 selection rule, candidate for candidate and tie for tie; `choose_old` is the
 rule before the previous Euclid vector v0 = (rp, tp) was considered.
@@ -24,7 +24,7 @@ import sys
 L = 2**252 + 27742317777372353535851937790883648493
 M = 8 * L
 T = math.isqrt(M) + 1
-MIN_WINDOWS = 57  # the fixed-base digits of e's low half need them (ed25519_ladder.hip)
+MIN_WINDOWS = 61  # the fixed-base digits of e over B need them (ed25519_sel.hpp kBMinWindows; 57 at 16-bit windows)
 
 
 def euclid_state(h):
