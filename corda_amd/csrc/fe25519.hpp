@@ -14,7 +14,8 @@
 //   tight : even limbs <= 2^26 + 2^10, odd limbs <= 2^25 + 2^17
 //           (outputs of fe_mul/fe_sq/fe_carry/fe_sub)
 //   loose : <= 3.3 x the tight bound (sum of up to three tight values)
-//   fe_mul/fe_sq accept loose inputs: 19*g < 2^32 and every 64-bit column
+//   fe_mul/fe_sq accept loose inputs: 19*g < 2^32 (fe_sq: 38*f < 2^32 for
+//   odd limbs, which leaves 1.7 % above loose) and every 64-bit column
 //   sum < 2^62.5.
 //   fe_sub(a, b) = a + 4p - b followed by a 32-bit carry pass: b may be
 //   loose (4p limbs >= 2^27), output tight.
@@ -158,8 +159,32 @@ CDEV void fe_mul(fe& r, const fe& f, const fe& g) {
   r = o;  // r may alias f or g
 }
 
-// h = f^2 (55 products)
+// h = f^2 (55 products). A term f_i f_j (i <= j) carries 2 when i < j, 2 when
+// both are odd and 19 when it wraps. FE_SQ_SCALED13 (ref10's choice) gives the
+// cross term's 2 to f_i, the odd*odd 2 to f_j (or, on the diagonal and for an
+// even i under a wrap, whichever 2 there is), and the 19 to f_j: 13 scaled
+// operands, 2 f_0..7 and 38 f_5, 19 f_6, 38 f_7, 19 f_8, 38 f_9, where
+// 2 f_0..9, 4 f_1,3,5,7 and 19 f_5..9 were 19. Every term is the same integer,
+// so the limbs are bit-identical. 38 f < 2^32 for odd limbs <= 113,025,455;
+// the loose bound is 111,162,163 (tools/proto/fe_bounds.py).
+#ifndef FE_SQ_SCALED13
+#define FE_SQ_SCALED13 1
+#endif
+CDEV uint32_t mul38(uint32_t x) {  // opaque like mul19
+  uint32_t r;
+  asm("v_mul_lo_u32 %0, %1, 38" : "=v"(r) : "v"(x));
+  return r;
+}
+
 CDEV void fe_sq(fe& r, const fe& f) {
+#if FE_SQ_SCALED13
+  uint32_t f2[10], f19[10];  // f19: 19 f_i for even i, 38 f_i for odd i
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    f2[i] = f.v[i] << 1;
+    f19[i] = (i & 1) ? mul38(f.v[i]) : mul19(f.v[i]);
+  }
+#else
   uint32_t f2[10], f4[10], f19[10];
 #pragma unroll
   for (int i = 0; i < 10; i++) {
@@ -167,6 +192,7 @@ CDEV void fe_sq(fe& r, const fe& f) {
     f4[i] = f.v[i] << 2;
     f19[i] = mul19(f.v[i]);
   }
+#endif
   fe o;
   uint64_t c = 0;
 #pragma unroll
@@ -178,9 +204,23 @@ CDEV void fe_sq(fe& r, const fe& f) {
       if (j < i) continue;
       const bool wrap = (i + j) >= 10;
       const bool oo = (i & 1) && (j & 1);
+#if FE_SQ_SCALED13
+      uint32_t a, b;
+      if (i == j) {
+        a = f.v[i];
+        b = wrap ? f19[j] : (oo ? f2[j] : f.v[j]);
+      } else if (j & 1) {
+        a = (oo || !wrap) ? f2[i] : f.v[i];
+        b = wrap ? f19[j] : (oo ? f2[j] : f.v[j]);
+      } else {
+        a = f2[i];
+        b = wrap ? f19[j] : f.v[j];
+      }
+#else
       const int mult = (i < j ? 2 : 1) * (oo ? 2 : 1);  // 1, 2 or 4
       const uint32_t a = mult == 1 ? f.v[i] : (mult == 2 ? f2[i] : f4[i]);
       const uint32_t b = wrap ? f19[j] : f.v[j];
+#endif
       acc = mac64(a, b, acc);
     }
     o.v[k] = (uint32_t)acc & ((k & 1) ? M25 : M26);

@@ -253,10 +253,26 @@ CDEV bool ge_frombytes_i2p(ge_p3& r, const uint32_t w[8]) {
 // z^(2^252 - 3) for two independent inputs (the decompression exponent of
 // ge_frombytes_i2p), every step a pair: the two square chains run interleaved
 // instead of one serial chain per lane (fe25519.hpp fe_pow22523).
+// ED_SQ_CHAIN2: the loop runs fe_sqsq2 (fe25519_asm.hpp), two squarings of each
+// chain per iteration with the limbs as read-write operands, so the loop-carried
+// values stay in their registers; around fe_sq2, whose outputs are registers of
+// their own, every iteration copied all 20 limbs back. An odd n ends with one
+// fe_sq2. Bit-identical.
+#ifndef ED_SQ_CHAIN2
+#define ED_SQ_CHAIN2 1
+#endif
 CDEV void fe_sqn_pair(fe& r0, const fe& a0, fe& r1, const fe& a1, int n) {
+#if FE_USE_ASM2 && ED_SQ_CHAIN2
+  r0 = a0;
+  r1 = a1;
+#pragma unroll 1
+  for (int i = 0; i + 2 <= n; i += 2) fe_sqsq2(r0, r1);
+  if (n & 1) fe_sq_pair(r0, r0, r1, r1);
+#else
   fe_sq_pair(r0, a0, r1, a1);
 #pragma unroll 1
   for (int i = 1; i < n; i++) fe_sq_pair(r0, r0, r1, r1);
+#endif
 }
 CDEV void fe_pow22523_pair(fe& r0, const fe& z0, fe& r1, const fe& z1) {
   fe z2_0, z2_1, z9_0, z9_1, z11_0, z11_1, t0, t1, a0, a1, b0, b1;

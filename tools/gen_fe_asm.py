@@ -2,8 +2,9 @@
 """Generate corda_amd/csrc/fe25519_asm.hpp: GF(2^255-19) products of TWO,
 THREE or FOUR independent operand pairs as one gfx950 inline-asm block each
 (fe_mul2, fe_sq2, fe_mul3, fe_mul4, fe_sq4), plus the outer-product blocks
-fe_mul3x / fe_mul4x of the formulas' output stage, in the radix-2^25.5
-representation of fe25519.hpp.
+fe_mul3x / fe_mul4x of the formulas' output stage and the in-place chain block
+fe_sqsq2 of the square chains, in the radix-2^25.5 representation of
+fe25519.hpp. tests/test_fe25519_asm.py emulates every block on the CPU.
 
 Why asm: the column accumulation wants the incoming carry as the addend of the
 column's first v_mad_u64_u32, so carries cost no instruction. LLVM re-associates
@@ -52,7 +53,14 @@ def mul_terms(k):
     return out
 
 
-def sq_terms(k):
+def sq_terms(k, scaled13=True):
+    """(a, b) operand names of column k of f^2, in fe25519.hpp's order.
+
+    scaled13 (FE_SQ_SCALED13, ref10's choice): the factor 2 of a cross term and
+    the factor 2 of an odd*odd term go one to each operand, the wrap's 19 to
+    the second, so 13 scaled operands serve all 55 terms: f2_0..7 and
+    38 f_5, 19 f_6, 38 f_7, 19 f_8, 38 f_9. Otherwise the 19-operand scheme
+    (f2_0..9, f4_1,3,5,7, f19_5..9). Each term is the same integer either way."""
     out = []
     for i in range(10):
         j = (k - i + 10) % 10
@@ -60,33 +68,57 @@ def sq_terms(k):
             continue
         wrap = i + j >= 10
         oo = (i & 1) and (j & 1)
-        mult = (2 if i < j else 1) * (2 if oo else 1)
-        a = {1: "f_%d", 2: "f2_%d", 4: "f4_%d"}[mult] % i
-        out.append((a, "f19_%d" % j if wrap else "f_%d" % j))
+        if not scaled13:
+            mult = (2 if i < j else 1) * (2 if oo else 1)
+            a = {1: "f_%d", 2: "f2_%d", 4: "f4_%d"}[mult] % i
+            out.append((a, "f19_%d" % j if wrap else "f_%d" % j))
+            continue
+        if i == j:  # f_i^2, times 2 (odd) and 19 (wrap)
+            a = "f_%d" % i
+            b = ("f38_%d" if oo else "f19_%d") % j if wrap else ("f2_%d" if oo else "f_%d") % j
+        elif j & 1:  # odd j takes the odd*odd 2 (and with a wrap the cross 2 when i is even)
+            a = "f2_%d" % i if oo or not wrap else "f_%d" % i
+            b = "f38_%d" % j if wrap else ("f2_%d" if oo else "f_%d") % j
+        else:
+            a = "f2_%d" % i
+            b = "f19_%d" % j if wrap else "f_%d" % j
+        out.append((a, b))
     return out
 
 
-def gen(kind, n):
+SCALED = ("f2", "f4", "g19", "f19", "f38")
+
+
+def scale_lines(need, p, f="f"):
+    """The scaled operands of product p: f2 = 2 f, f4 = 4 f, g19 / f19 = 19 x,
+    f38 = 38 f; f names the operand set the f-limbs are read from."""
+    lines = []
+    for nm in need:
+        base, idx = nm.split("_")
+        if base not in SCALED:
+            continue
+        src = ("g_%s" % idx) if base == "g19" else ("%s_%s" % (f, idx))
+        # doublings as adds: v_add_u32 issues at ~2.3 cycles per wave64
+        # instruction, v_lshlrev_b32 at ~4.0 (profiles/r02_valu_rates.jsonl)
+        if base == "f2":
+            lines.append("v_add_u32 %%[%s%d], %%[%s%d], %%[%s%d]" % (nm, p, src, p, src, p))
+        elif base == "f4" and ("f2_" + idx) in need:  # sorted: f2_i is already there
+            lines.append("v_add_u32 %%[%s%d], %%[f2_%s%d], %%[f2_%s%d]" % (nm, p, idx, p, idx, p))
+        elif base == "f4":
+            lines.append("v_lshlrev_b32 %%[%s%d], 2, %%[%s%d]" % (nm, p, src, p))
+        else:
+            lines.append("v_mul_lo_u32 %%[%s%d], %%[%s%d], %s" % (nm, p, src, p, base[1:]))
+    return lines
+
+
+def gen(kind, n, scaled13=True):
     """One asm statement for n products; operand names carry a product suffix."""
-    terms = [mul_terms(k) if kind == "mul" else sq_terms(k) for k in range(10)]
+    terms = [mul_terms(k) if kind == "mul" else sq_terms(k, scaled13) for k in range(10)]
     need = sorted({x for col in terms for t in col for x in t})
     lines = []
     P = range(n)
-    # scaled operands: f2 = 2 f, f4 = 4 f, g19 / f19 = 19 x
     for p in P:
-        for nm in need:
-            base, idx = nm.split("_")
-            src = ("g_%s" % idx) if base == "g19" else ("f_%s" % idx)
-            # doublings as adds: v_add_u32 issues at ~2.3 cycles per wave64
-            # instruction, v_lshlrev_b32 at ~4.0 (profiles/r02_valu_rates.jsonl)
-            if base == "f2":
-                lines.append("v_add_u32 %%[%s%d], %%[%s%d], %%[%s%d]" % (nm, p, src, p, src, p))
-            elif base == "f4" and ("f2_" + idx) in need:  # sorted: f2_i is already there
-                lines.append("v_add_u32 %%[%s%d], %%[f2_%s%d], %%[f2_%s%d]" % (nm, p, idx, p, idx, p))
-            elif base == "f4":
-                lines.append("v_lshlrev_b32 %%[%s%d], 2, %%[%s%d]" % (nm, p, src, p))
-            elif base in ("g19", "f19"):
-                lines.append("v_mul_lo_u32 %%[%s%d], %%[%s%d], 19" % (nm, p, src, p))
+        lines += scale_lines(need, p)
     for k in range(10):
         col = terms[k]
         for t, (a, b) in enumerate(col):
@@ -96,12 +128,89 @@ def gen(kind, n):
         for p in P:
             lines.append("v_and_b32 %%[r%d_%d], %s, %s" % (p, k, MASK[k & 1], ACC_LO[p]))
             lines.append("v_lshrrev_b64 %%[c%d], %d, %s" % (p, bits(k), ACC[p]))
-    scaled = [nm for nm in need if nm.split("_")[0] in ("f2", "f4", "g19", "f19")]
+    scaled = [nm for nm in need if nm.split("_")[0] in SCALED]
     return lines, scaled
 
 
-def asm_block(kind, n):
-    lines, scaled = gen(kind, n)
+# Chain block fe_sqsq2: f <- (f^2)^2 for two independent values in ONE asm
+# statement, the limbs as read-write operands. A square chain is loop-carried,
+# and fe_sq2's outputs are early-clobber registers distinct from its inputs,
+# so a loop around it copies every limb back once per iteration; here the first
+# squaring goes f -> t and the second t -> f, and the loop carries f in place.
+# Both top folds are inside the block. Limb 0 of a squaring waits for the fold
+# in the low register of a second fixed pair (TOP: the accumulators of the 3rd
+# and 4th chain, free in a two-chain block), whose high register takes
+# 19 * (carry's high word), so that ONE v_mad_u64_u32 forms
+# t = limb0 + 19 * carry exactly as fe_fold_top does (carry < 2^38: its high
+# word is < 2^6 and v_mul_u32_u24 is exact; t >> 26 < 2^17).
+TOP = ACC[2:]
+TOP_LO = ACC_LO[2:]
+TOP_HI = ("v165", "v167")
+ACC_HI = ("v161", "v163")
+
+
+def gen_sqsq():
+    terms = [sq_terms(k) for k in range(10)]
+    need = sorted({x for col in terms for t in col for x in t})
+    lines = []
+    P = range(2)
+    for src, dst in (("f", "t"), ("t", "f")):
+        def nm(x, p):
+            base, idx = x.split("_")
+            return "%%[%s_%s%d]" % (src, idx, p) if base == "f" else "%%[%s%d]" % (x, p)
+        for p in P:
+            lines += scale_lines(need, p, src)
+        for k in range(10):
+            for t, (a, b) in enumerate(terms[k]):
+                for p in P:
+                    addend = ("0" if k == 0 else "%%[c%d]" % p) if t == 0 else ACC[p]
+                    lines.append("v_mad_u64_u32 %s, vcc, %s, %s, %s" % (ACC[p], nm(a, p), nm(b, p), addend))
+            for p in P:
+                out = TOP_LO[p] if k == 0 else "%%[%s_%d%d]" % (dst, k, p)
+                lines.append("v_and_b32 %s, %s, %s" % (out, MASK[k & 1], ACC_LO[p]))
+                if k < 9:
+                    lines.append("v_lshrrev_b64 %%[c%d], %d, %s" % (p, bits(k), ACC[p]))
+                else:
+                    lines.append("v_lshrrev_b64 %s, %d, %s" % (ACC[p], bits(k), ACC[p]))
+        for p in P:
+            lines.append("v_mul_u32_u24 %s, 19, %s" % (TOP_HI[p], ACC_HI[p]))
+        for p in P:
+            lines.append("v_mad_u64_u32 %s, vcc, %s, 19, %s" % (TOP[p], ACC_LO[p], TOP[p]))
+        for p in P:
+            lines.append("v_and_b32 %%[%s_0%d], %s, %s" % (dst, p, MASK[0], TOP_LO[p]))
+            lines.append("v_lshrrev_b64 %s, 26, %s" % (TOP[p], TOP[p]))
+        for p in P:
+            lines.append("v_add_u32 %%[%s_1%d], %%[%s_1%d], %s" % (dst, p, dst, p, TOP_LO[p]))
+    scaled = [x for x in need if x.split("_")[0] in SCALED]
+    return lines, scaled
+
+
+def sqsq_block():
+    lines, scaled = gen_sqsq()
+    body = "\n".join('        "%s\\n"' % l for l in lines)
+    outs = []
+    for p in range(2):
+        outs += ['[f_%d%d] "+v"(f%d.v[%d])' % (k, p, p, k) for k in range(10)]
+        outs += ['[t_%d%d] "=&v"(t%d.v[%d])' % (k, p, p, k) for k in range(10)]
+        outs += ['[c%d] "=&v"(c%d)' % (p, p)]
+        outs += ['[%s%d] "=&v"(t%d_%s)' % (nm, p, p, nm) for nm in scaled]
+    decl = "\n".join("  uint32_t %s;" % ", ".join("t%d_%s" % (p, nm) for nm in scaled) for p in range(2))
+    return '''// f0 <- f0^4, f1 <- f1^4: two successive squarings of each, limbs in place
+CDEV void fe_sqsq2(fe& f0, fe& f1) {
+  fe t0, t1;
+  uint64_t c0, c1;
+%s
+  asm(
+%s
+      : %s
+      :
+      : "vcc", FE_ASM_ACC_CLOBBERS4);
+}
+''' % (decl, body, ",\n        ".join(outs))
+
+
+def asm_block(kind, n, scaled13=True):
+    lines, scaled = gen(kind, n, scaled13)
     body = "\n".join('        "%s\\n"' % l for l in lines)
     outs = []
     for p in range(n):
@@ -222,11 +331,9 @@ def signature(kind, n):
     return "CDEV void fe_%s%d(%s)" % (kind, n, args)
 
 
-def render():
-    parts = [HEADER]
-    for kind, n in (("mul", 2), ("sq", 2), ("mul", 3), ("mul", 4), ("sq", 4)):
-        body, outs, ins, decl = asm_block(kind, n)
-        parts.append('''%s {
+def product_block(kind, n, scaled13=True):
+    body, outs, ins, decl = asm_block(kind, n, scaled13)
+    return '''%s {
   fe %s;
   uint64_t %s;
 %s
@@ -241,7 +348,18 @@ def render():
 ''' % (signature(kind, n), ", ".join("o%d" % p for p in range(n)), ", ".join("c%d" % p for p in range(n)),
        decl, body, outs, ins, CLOBBERS[n],
        "\n".join("  fe_fold_top(o%d, c%d);" % (p, p) for p in range(n)),
-       "\n".join("  r%d = o%d;" % (p, p) for p in range(n))))
+       "\n".join("  r%d = o%d;" % (p, p) for p in range(n)))
+
+
+def render():
+    parts = [HEADER]
+    for kind, n in (("mul", 2), ("sq", 2), ("mul", 3), ("mul", 4), ("sq", 4)):
+        if kind == "sq":  # FE_SQ_SCALED13: fe25519.hpp (fe_sq takes the same terms)
+            parts.append("#if FE_SQ_SCALED13\n%s#else\n%s#endif\n" % (product_block(kind, n, True),
+                                                                     product_block(kind, n, False)))
+        else:
+            parts.append(product_block(kind, n))
+    parts.append(sqsq_block())
     for n in (3, 4):
         parts.append(outer_block(n))
     parts.append("}  // namespace cordahip\n")

@@ -1,12 +1,15 @@
 // GPU check + timing of the generated multi-product field multiplies
-// (corda_amd/csrc/fe25519_asm.hpp: fe_mul2/3/4, fe_sq2/4, fe_mul3x/4x) against fe25519.hpp's
-// carry-chained C versions: identical limbs for random loose operands (limbs
-// < 2^27, the group formulas' bound), then the issue cost of long chains.
+// (corda_amd/csrc/fe25519_asm.hpp: fe_mul2/3/4, fe_sq2/4, fe_mul3x/4x, the chain block
+// fe_sqsq2 through ge25519.hpp's fe_sqn_pair) against fe25519.hpp's carry-chained C
+// versions: identical limbs for random loose operands (multiplies: limbs < 2^27, the
+// group formulas' bound; squarings: up to fe25519.hpp's loose bound, 3.3 x tight, above
+// which 38 f no longer fits 32 bits), then the issue cost of long chains.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../../corda_amd/csrc/fe25519_asm.hpp"
+#define FE_USE_ASM2 1
+#include "../../corda_amd/csrc/ge25519.hpp"
 
 using namespace cordahip;
 
@@ -23,6 +26,11 @@ __device__ void rnd(fe& a, uint32_t& s, int lbits) {
   for (int i = 0; i < 10; i++) a.v[i] = xs(s) & ((1u << lbits) - 1);
 }
 
+// a squaring's operand: limbs up to the loose bound, 3.3 x (2^26 + 2^10) / 3.3 x (2^25 + 2^17)
+__device__ void rnd_loose(fe& a, uint32_t& s) {
+  for (int i = 0; i < 10; i++) a.v[i] = xs(s) % ((i & 1) ? 111162164u : 221462631u);
+}
+
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) check(uint32_t* bad, uint32_t seed) {
   uint32_t s = seed ^ (blockIdx.x * 256 + threadIdx.x) * 2654435761u;
   for (int it = 0; it < 64; it++) {
@@ -34,7 +42,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
     fe_mul2(b0, f0, g0, b1, f1, g1);
     uint32_t d = 0;
     for (int i = 0; i < 10; i++) d |= (a0.v[i] ^ b0.v[i]) | (a1.v[i] ^ b1.v[i]);
-    rnd(f0, s, 27); rnd(f1, s, 26);
+    rnd_loose(f0, s); rnd(f1, s, 26);
     fe_sq(a0, f0);
     fe_sq(a1, f1);
     fe_sq2(b0, f0, b1, f1);
@@ -49,6 +57,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
       d |= ((a0.v[i] ^ b0.v[i]) | (a1.v[i] ^ b1.v[i]) | (a2.v[i] ^ b2.v[i]) | (a3.v[i] ^ b3.v[i])) ? 4u : 0u;
     fe_mul3(b0, f0, g0, b1, f1, g1, b2, f2, g2);
     for (int i = 0; i < 10; i++) d |= ((a0.v[i] ^ b0.v[i]) | (a1.v[i] ^ b1.v[i]) | (a2.v[i] ^ b2.v[i])) ? 8u : 0u;
+    rnd_loose(f0, s); rnd_loose(f2, s);
     fe_sq(a0, f0); fe_sq(a1, f1); fe_sq(a2, f2); fe_sq(a3, f3);
     fe_sq4(b0, f0, b1, f1, b2, f2, b3, f3);
     for (int i = 0; i < 10; i++)
@@ -65,11 +74,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
     fe_mul(a1, g1, f1); fe_mul(a3, g0, f1);
     fe_mul4x(b0, b1, b2, b3, f0, f1, g0, g1);
     for (int i = 0; i < 10; i++) d |= ((a1.v[i] ^ b1.v[i]) | (a3.v[i] ^ b3.v[i])) ? 128u : 0u;
+    // square chains of n = 1, 2, 3, 5, 10: fe_sqn_pair (fe_sqsq2 per two squarings, one
+    // fe_sq2 for an odd n) against n x fe_sq; the first squaring takes loose operands
+    rnd_loose(f0, s); rnd(f1, s, 26);
+    a0 = f0; a1 = f1;
+    int done = 0;
+    for (int n : {1, 2, 3, 5, 10}) {
+      for (; done < n; done++) { fe_sq(a0, a0); fe_sq(a1, a1); }
+      fe_sqn_pair(b0, f0, b1, f1, n);
+      for (int i = 0; i < 10; i++) d |= ((a0.v[i] ^ b0.v[i]) | (a1.v[i] ^ b1.v[i])) ? 256u : 0u;
+    }
     if (d) atomicOr(bad, d);
   }
 }
 
-// 0: fe_mul x4 (C), 1: 2 x fe_mul2, 2: fe_mul4, 3: 2 x fe_sq2, 4: fe_sq4 (four products per iteration)
+// 0: fe_mul x4 (C), 1: 2 x fe_mul2, 2: fe_mul4, 3: 2 x fe_sq2, 4: fe_sq4, 5: 2 x fe_sqsq2 (four products per iteration)
 template <int MODE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) chain(uint32_t* out, uint32_t seed,
                                                                                    int iters) {
@@ -82,6 +101,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) c
     if (MODE == 2) fe_mul4(x, x, y, z, z, w, u, u, y, v, v, w);
     if (MODE == 3) { fe_sq2(x, x, z, z); fe_sq2(u, u, v, v); }
     if (MODE == 4) fe_sq4(x, x, z, z, u, u, v, v);
+    if (MODE == 5) { fe_sqsq2(x, z); fe_sqsq2(u, v); it++; }  // two iterations' work (iters is even)
   }
   uint32_t a = 0;
   for (int i = 0; i < 10; i++) a ^= x.v[i] ^ z.v[i] ^ u.v[i] ^ v.v[i];
@@ -120,17 +140,19 @@ int main() {
   hipLaunchKernelGGL(check, dim3(4096), dim3(256), 0, 0, dbad, 12345u);
   uint32_t bad = 0;
   CHECK(hipMemcpy(&bad, dbad, 4, hipMemcpyDeviceToHost));
-  printf("{\"check\": \"fe_mul2/3/4, fe_sq2/4, fe_mul3x/4x vs fe_mul/fe_sq\", \"lanes\": %d, \"mul2_mismatch\": %d, "
+  printf("{\"check\": \"fe_mul2/3/4, fe_sq2/4, fe_mul3x/4x, fe_sqn_pair vs fe_mul/fe_sq\", \"lanes\": %d, \"mul2_mismatch\": %d, "
          "\"sq2_mismatch\": %d, \"mul4_mismatch\": %d, \"mul3_mismatch\": %d, \"sq4_mismatch\": %d, "
-         "\"mul4x_mismatch\": %d, \"mul3x_mismatch\": %d, \"mul4x_swapped_mismatch\": %d}\n",
+         "\"mul4x_mismatch\": %d, \"mul3x_mismatch\": %d, \"mul4x_swapped_mismatch\": %d, "
+         "\"sq_chain_mismatch\": %d}\n",
          4096 * 256 * 64, bad & 1, (bad >> 1) & 1, (bad >> 2) & 1, (bad >> 3) & 1, (bad >> 4) & 1, (bad >> 5) & 1,
-         (bad >> 6) & 1, (bad >> 7) & 1);
+         (bad >> 6) & 1, (bad >> 7) & 1, (bad >> 8) & 1);
   for (int w : {2, 4}) {
     if (time_chain<0>("fe_mul x4 (C)", dout, p.multiProcessorCount, w)) return 1;
     if (time_chain<1>("2 x fe_mul2 (asm)", dout, p.multiProcessorCount, w)) return 1;
     if (time_chain<2>("fe_mul4 (asm)", dout, p.multiProcessorCount, w)) return 1;
     if (time_chain<3>("2 x fe_sq2 (asm)", dout, p.multiProcessorCount, w)) return 1;
     if (time_chain<4>("fe_sq4 (asm)", dout, p.multiProcessorCount, w)) return 1;
+    if (time_chain<5>("2 x fe_sqsq2 (asm, in place)", dout, p.multiProcessorCount, w)) return 1;
   }
   return bad ? 2 : 0;
 }
