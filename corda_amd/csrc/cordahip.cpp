@@ -784,9 +784,11 @@ int signed_tx_device_once(cordahip_ctx* ctx, Device& d, const cordahip_signed_tx
     };
     MsgView mv{b->tx.txid, nullptr, tx_of};
     mv.dev = &di;
-    // checkSignaturesAreValid -> sig.verify -> Crypto.doVerify: doVerify semantics
+    // checkSignaturesAreValid -> sig.verify -> Crypto.doVerify: doVerify semantics. The
+    // struct carries no flags: cordahip_set_rsa_on_device stands for CORDAHIP_FLAG_RSA_ON_DEVICE
+    const uint32_t sig_flags = ctx->rsa_on_device.load(std::memory_order_relaxed) ? CORDAHIP_FLAG_RSA_ON_DEVICE : 0u;
     cordahip_sig_batch sb{b->tx_sig_off[b->tx.ntx], b->scheme, b->key, b->key_off, b->sig, b->sig_off, b->tx.txid,
-                          nullptr, b->sig_status, nullptr, 0u, b->key_bytes, b->sig_bytes, 0};
+                          nullptr, b->sig_status, nullptr, sig_flags, b->key_bytes, b->sig_bytes, 0};
     try {
       r = sig_verify_range(ctx, d, S, &sb, mv, s0, s1);
     } catch (const std::bad_alloc&) {
@@ -1440,6 +1442,12 @@ int cordahip_rsa_pss_verify_device(cordahip_ctx* ctx, int device, const void* d_
                               static_cast<const uint8_t*>(d_msgs), nullptr, msg_len, mod_words, n, nullptr,
                               static_cast<uint8_t*>(d_status), static_cast<unsigned long long*>(d_verdict), 0u, s);
   });
+}
+
+int cordahip_set_rsa_on_device(cordahip_ctx* ctx, uint32_t on) {
+  if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
+  ctx->rsa_on_device.store(on ? 1u : 0u);
+  return CORDAHIP_SUCCESS;
 }
 
 int cordahip_tx_cover_device(cordahip_ctx* ctx, int device, uint64_t ntx, void* d_tx_status,

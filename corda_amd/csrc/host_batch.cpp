@@ -259,6 +259,7 @@ struct PieceInfo {
   std::vector<std::pair<uint64_t, uint64_t>> ed;  // (message length, lanes), piece-local group order
   std::vector<uint32_t> ed_global;               // piece-local group -> chunk group
   uint64_t ec = 0, ec_bytes = 0;                 // ECDSA lanes and their message bytes
+  uint64_t rsa[3] = {0, 0, 0};                   // RSA lanes of the chunk's own section, by width class
   bool too_long = false;
   bool bad_csr = false;                          // a lane's CSR ranges outside the batch's buffers
 };
@@ -274,6 +275,15 @@ struct PieceInfo {
 // status D2H on each section's stream. Classification and packing of chunk k
 // run while the GPU verifies chunks k-1 and k-2; a stage's statuses go back to
 // the caller's lanes when the stage comes round again.
+// Signed-tx batches with cordahip_set_rsa_on_device on (rsa_in_chunks): a chunk's RSA
+// lanes are a third section of that chunk. Their messages are ids in HBM, tx_of is filled
+// only up to the current chunk and a chunk's transactions are reduced as soon as its
+// statuses are back, so the lanes are classified and packed with the chunk (by width
+// class, the classes' rows one after the other), gathered from the ids after the id
+// slice's event and enqueued on s_rsa after the chunk's Ed25519 and ECDSA work, one
+// rsa_verify_enqueue per class present under rsa_mu, and the stage's finish waits for
+// them before the chunk is reduced. The stage's buffers are the call's own (its TxSet),
+// so two calls in flight share only the RSA workspace, which rsa_mu and its fence order.
 int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_batch* b, const MsgView& mv,
                  uint64_t lo, uint64_t hi) {
   if (lo >= hi) return CORDAHIP_SUCCESS;
@@ -301,7 +311,8 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
   // the shard's RSA lanes, beside the chunks below (joined after they have drained)
   RsaResult rsa_out;
   std::future<int> rsa_job;
-  if (rsa_on_device(b, mv))
+  const bool rsa_chunks = rsa_in_chunks(b, mv) && dev;
+  if (rsa_on_device(b, mv) && !mv.tx_of)
     rsa_job = std::async(std::launch::async, [&, lo, hi] { return rsa_section(ctx, d, b, mv, lo, hi, rsa_out); });
   // Chunks whose rows are the lanes in order (one message length, Ed25519 only:
   // the common JVM batch) skip the host scatter: a kernel stores the statuses
@@ -320,6 +331,9 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
     st.pending = false;
     hipError_t e = blocked("chunk verified", [&] { return hipEventSynchronize(st.ed_done); });
     e = e ? e : hipEventSynchronize(st.ec_done);
+    const uint64_t nr = st.rsa_rows;
+    st.rsa_rows = 0;
+    if (nr) e = e ? e : hipEventSynchronize(st.rsa_done);
     if (e != hipSuccess) return e;
     if (st.direct) return hipSuccess;  // statuses and verdict words are already in the caller's arrays
     const uint8_t *se = st.h[4].as<uint8_t>(), *sc = st.h[13].as<uint8_t>();
@@ -330,6 +344,8 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
         else b->status[st.ec_lanes[r - ne]] = sc[r - ne];
       }
     });
+    // the chunk's RSA section: final before the chunk's transactions are reduced below
+    for (uint64_t r = 0; r < nr; r++) b->status[st.rsa_lanes[r]] = st.rh[5].as<uint8_t>()[r];
     // the chunk's verdict words now (its lanes' statuses are final: the direct
     // ones were written at classification), overlapped with later chunks' GPU
     // work; chunks start 64-aligned (shard starts and chunk sizes are)
@@ -349,6 +365,7 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
   std::vector<PieceInfo> pieces;
   std::vector<uint64_t> lens, grow, gmsg, ec_row0, ec_mo0;  // chunk groups: length, first row, message offset
   std::vector<std::vector<uint64_t>> prow;                   // [piece][group]: the piece's first row in the group
+  std::vector<uint64_t> rsa_row0[3];                         // [class][piece]: the piece's first row in the class
   hipError_t e = hipSuccess;
   int rc = CORDAHIP_SUCCESS;
   const double t_start = tracing() ? now_ms() : 0;
@@ -373,6 +390,7 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
         PieceInfo& P = pieces[q];
         P.ed.clear();
         P.ec = P.ec_bytes = 0;
+        P.rsa[0] = P.rsa[1] = P.rsa[2] = 0;
         P.too_long = P.bad_csr = false;
         // length -> group: the previous lane's group first (batches are mostly
         // one message length), a hash map once a piece has many lengths, so a
@@ -381,10 +399,14 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
         size_t last = 0;
         for (uint64_t r = q * kGrain; r < std::min(m, (q + 1) * kGrain); r++) {
           uint64_t mlen = 0;
-          uint16_t c = classify(b, mv, a + r, mlen);
+          uint32_t rcls = 0;
+          uint16_t c = classify(b, mv, a + r, mlen, &rcls);
           if (c == kBadCsr) {
             P.bad_csr = true;
             c = kDirect;  // not packed: the chunk is not enqueued
+          } else if (c == kRsa && rsa_chunks) {
+            P.rsa[rcls]++;
+            c = (uint16_t)(kRsaBase + rcls);  // a row of the chunk's RSA section
           } else if (c == kRsa) {
             c = kDirect;  // not a row of the chunk: the RSA section owns the lane
           } else if (c == kEc) {
@@ -458,6 +480,26 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
       ec_mo0[q + 1] = ec_mo0[q] + pieces[q].ec_bytes;
     }
     const uint64_t ne = grow[ng], nc = ec_row0[np], mb = ec_mo0[np];
+    // the RSA section: class c's rows are [rrow[c], rrow[c + 1]), piece q's of them from rsa_row0[c][q]
+    uint64_t rrow[4] = {0, 0, 0, 0};
+    for (int c = 0; c < 3; c++) {
+      rsa_row0[c].assign(np + 1, 0);
+      for (uint64_t q = 0; q < np; q++) rsa_row0[c][q + 1] = rsa_row0[c][q] + pieces[q].rsa[c];
+      rrow[c + 1] = rrow[c] + rsa_row0[c][np];
+    }
+    const uint64_t nr = rrow[3];
+    // byte offsets of a class's moduli (and signatures: the same 4 W bytes a row)
+    const uint64_t rmod[4] = {0, rrow[1] * 256, rrow[1] * 256 + (rrow[2] - rrow[1]) * 384,
+                              rrow[1] * 256 + (rrow[2] - rrow[1]) * 384 + (rrow[3] - rrow[2]) * 512};
+    if (nr) {
+      const size_t rsz[7] = {rmod[3], nr * 4, rmod[3], nr * 2, nr * 4, nr, nr * 32};
+      for (int q = 0; q < 7; q++)
+        if ((q < 6 && st.rh[q].ensure(rsz[q]) != hipSuccess) || st.rd[q].ensure(rsz[q]) != hipSuccess)
+          rc = CORDAHIP_ERR_OUT_OF_MEMORY;
+      if (!st.rsa_done && hipEventCreateWithFlags(&st.rsa_done, hipEventDisableTiming) != hipSuccess)
+        rc = CORDAHIP_ERR_HIP;
+    }
+    st.rsa_lanes.resize(nr);
     const size_t sz[14] = {ne * 32, ne * 64, std::max<uint64_t>(gmsg[ng], 16), ne, ne,
                            nc, nc * 65, nc, nc * 72, nc, std::max<uint64_t>(mb, 16), (nc + 1) * 8, nc, nc};
     for (int q = 0; q < 14; q++) {
@@ -496,6 +538,7 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
           row.assign(P.ed.size(), 0);
           for (size_t j = 0; j < P.ed.size(); j++) row[j] = prow[q][P.ed_global[j]];
           uint64_t er = ec_row0[q], mo = ec_mo0[q];
+          uint64_t rr3[3] = {nr ? rsa_row0[0][q] : 0, nr ? rsa_row0[1][q] : 0, nr ? rsa_row0[2][q] : 0};
           for (uint64_t r = q * kGrain; r < std::min(m, (q + 1) * kGrain); r++) {
             const uint16_t c = cls[r];
             const uint64_t i = a + r;
@@ -506,6 +549,16 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
                           st.h[11].as<uint64_t>(), st.h[12].as<uint8_t>(), mo,
                           dev ? st.hidx[1].as<uint32_t>() : nullptr, dev ? dev->t0 : 0);
               er++;
+            } else if (c >= kRsaBase && c < kRsaBase + 3) {
+              const uint32_t k3 = c - kRsaBase, W = 64 + 32 * k3;
+              const uint64_t rc3 = rr3[k3]++, rg = rrow[k3] + rc3;  // row in its class, row in the section
+              rsa::PublicKey pk;
+              (void)rsa_lane_pre(b, mv, do_verify, i, pk);
+              st.rsa_lanes[rg] = i;
+              pack_rsa_row(b, i, pk, W, rc3, reinterpret_cast<uint32_t*>(st.rh[0].as<uint8_t>() + rmod[k3]),
+                           st.rh[1].as<uint32_t>() + rrow[k3], st.rh[2].as<uint8_t>() + rmod[k3],
+                           st.rh[3].as<uint16_t>() + rrow[k3]);
+              st.rh[4].as<uint32_t>()[rg] = (uint32_t)(mv.tx_of[i] - dev->t0);
             } else if (c >= kEdBase) {
               const size_t j = c - kEdBase, gi = P.ed_global[j];
               const uint64_t rr = row[j]++;
@@ -551,6 +604,11 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
       } else {
         h2d(10, ec_mo0[q0], ec_mo0[q1] - ec_mo0[q0]);
       }
+    }
+    if (nr) {  // the RSA section's rows, whole, behind the chunk's other copies
+      const size_t rbytes[5] = {rmod[3], nr * 4, rmod[3], nr * 2, nr * 4};
+      for (int q = 0; q < 5; q++)
+        e = e ? e : hipMemcpyAsync(st.rd[q].p, st.rh[q].p, rbytes[q], hipMemcpyHostToDevice, d.s_copy);
     }
     const double t3b = tracing() ? now_ms() : 0;
     if (dev && dev->advance) e = e ? e : dev->advance(a + m, true);
@@ -616,6 +674,28 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
     }
     if (nc) e = e ? e : launch_store_to_host(st.d[13].p, st.h[13].p, nc, xs);
     e = e ? e : hipEventRecord(st.ec_done, xs);
+    // the RSA section, after the chunk's Ed25519 and ECDSA work: the GPU is busy while
+    // the host packs the next chunk. rsa_mu: the stream's creation, the workspace.
+    if (nr && e == hipSuccess) {
+      std::lock_guard<std::mutex> gr(d.rsa_mu);
+      if (!d.s_rsa && hipStreamCreateWithFlags(&d.s_rsa, hipStreamNonBlocking) != hipSuccess) e = hipErrorUnknown;
+      e = e ? e : hipStreamWaitEvent(d.s_rsa, st.copied, 0);
+      e = e ? e : hipStreamWaitEvent(d.s_rsa, ids_ready, 0);
+      e = e ? e : launch_gather_rows32(dev->txid, st.rd[4].as<uint32_t>(), nr, st.rd[6].as<uint8_t>(), d.s_rsa);
+      for (int c = 0; c < 3 && e == hipSuccess; c++) {
+        const uint64_t cnt = rrow[c + 1] - rrow[c];
+        if (!cnt) continue;
+        e = rsa_verify_enqueue(d, reinterpret_cast<const uint32_t*>(st.rd[0].as<uint8_t>() + rmod[c]),
+                               st.rd[1].as<uint32_t>() + rrow[c], st.rd[2].as<uint8_t>() + rmod[c],
+                               st.rd[3].as<uint16_t>() + rrow[c], st.rd[6].as<uint8_t>() + rrow[c] * 32, nullptr, 32,
+                               64 + 32 * (uint32_t)c, cnt, nullptr, st.rd[5].as<uint8_t>() + rrow[c], nullptr,
+                               b->flags & CORDAHIP_FLAG_IS_VALID, d.s_rsa);
+      }
+      e = e ? e : launch_store_to_host(st.rd[5].p, st.rh[5].p, nr, d.s_rsa);
+      const hipError_t er = hipEventRecord(st.rsa_done, d.s_rsa);  // whatever was enqueued is waited for
+      e = e ? e : er;
+      if (er == hipSuccess) st.rsa_rows = nr;
+    }
     if (e == hipSuccess) {
       st.pending = true;
       st.a = a;
@@ -641,8 +721,11 @@ int sig_pipeline(cordahip_ctx* ctx, Device& d, TxSet& set, const cordahip_sig_ba
   if (e != hipSuccess || rc != CORDAHIP_SUCCESS) {
     for (hipStream_t x : {d.s_copy, d.s_ed, d.s_ed2, d.s_ec, d.s_ec2})  // s_ec2: the id-copy stream
       if (x) (void)hipStreamSynchronize(x);
-    for (BatchStage& st : set.pb)
+    for (BatchStage& st : set.pb) {
       for (hipEvent_t ev : {st.copied, st.ed_done, st.ec_done}) (void)hipEventSynchronize(ev);
+      if (st.rsa_rows && st.rsa_done) (void)hipEventSynchronize(st.rsa_done);
+      st.rsa_rows = 0;
+    }
   }
   if (rsa_job.valid()) {
     // the RSA lanes' statuses, and their bits of the verdict words the chunks wrote

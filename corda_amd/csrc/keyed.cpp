@@ -699,6 +699,7 @@ int rsa_vkey_put_on(Device& d, const rsa::VkeyRecord& rec) {
         : hipMemcpyAsync(k.tab.as<uint8_t>() + (size_t)vkey_slot(rec.id) * sizeof rec, k.stage.p, sizeof rec,
                          hipMemcpyHostToDevice, d.stream);
   const hipError_t f = hipStreamSynchronize(d.stream);
+  if (e == hipSuccess && f == hipSuccess) k.live |= 1ull << vkey_slot(rec.id);
   return hip_err(e ? e : f);
 }
 
@@ -1053,7 +1054,7 @@ int rsa_sign_impl(cordahip_ctx* ctx, const cordahip_rsa_sign_batch* b) {
 }
 
 // A device's cumulative counters of routed lanes: route_tot of the family's key table
-// `keys` (K14: Device::vkeys, K15: Device::ec_vkeys), written by kernels the table's
+// `keys` (K14: Device::vkeys, K15: Device::ec_vkeys, K20: Device::rsa_vkeys), written by kernels the table's
 // fence follows.
 template <class Keys>
 int route_stats(cordahip_ctx* ctx, int device, Keys Device::*keys, uint64_t* keyed_lanes, uint64_t* generic_lanes) {
@@ -1074,7 +1075,7 @@ int route_stats(cordahip_ctx* ctx, int device, Keys Device::*keys, uint64_t* key
     return CORDAHIP_SUCCESS;
   });
 }
-// a family's routing switch (Device::route_on, Device::ec_route_on) on every device
+// a family's routing switch (Device::route_on, Device::ec_route_on, Device::rsa_route_on) on every device
 int set_routing(cordahip_ctx* ctx, std::atomic<uint32_t> Device::*sw, uint32_t on) {
   if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
   for (auto& dp : ctx->devs) ((*dp).*sw).store(on ? 1u : 0u);
@@ -1225,6 +1226,14 @@ int cordahip_vkey_set_routing_ecdsa(cordahip_ctx* ctx, uint32_t on) {
 
 int cordahip_vkey_route_stats_ecdsa(cordahip_ctx* ctx, int device, uint64_t* keyed_lanes, uint64_t* generic_lanes) {
   return route_stats(ctx, device, &Device::ec_vkeys, keyed_lanes, generic_lanes);
+}
+
+int cordahip_vkey_set_routing_rsa(cordahip_ctx* ctx, uint32_t on) {
+  return set_routing(ctx, &Device::rsa_route_on, on);
+}
+
+int cordahip_vkey_route_stats_rsa(cordahip_ctx* ctx, int device, uint64_t* keyed_rows, uint64_t* generic_rows) {
+  return route_stats(ctx, device, &Device::rsa_vkeys, keyed_rows, generic_rows);
 }
 
 int cordahip_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch) {

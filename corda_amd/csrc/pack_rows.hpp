@@ -42,7 +42,9 @@ inline void pack_ed_row(const cordahip_sig_batch* b, const MV& mv, bool do_verif
 // CORDAHIP_ERR_INVALID_ARG before its chunk is packed).
 // kRsa: an RSA_SHA256 lane the GPU verifies (CORDAHIP_FLAG_RSA_ON_DEVICE): not a row
 // of the chunk, its status comes from the batch's RSA section (host_batch.cpp).
-enum : uint16_t { kDirect = 0, kEc = 1, kEdBase = 2, kRsa = 0xfffe, kBadCsr = 0xffff };
+// kRsaBase + c: such a lane of width class c (0, 1, 2: 64, 96, 128 words) where it is a
+// row of its chunk's RSA section (rsa_in_chunks; classify's rsa_class says which).
+enum : uint16_t { kDirect = 0, kEc = 1, kEdBase = 2, kRsaBase = 0xfff0, kRsa = 0xfffe, kBadCsr = 0xffff };
 
 // the lane's ranges, before any byte of it is read: non-decreasing and inside
 // the declared buffers (key_off[i + 1] <= key_bytes, ...; messages of a signed-tx
@@ -54,10 +56,18 @@ inline bool lane_ranges_ok(const cordahip_sig_batch* b, const MV& mv, uint64_t i
   return mv.tx_of || (mv.off[i + 1] >= mv.off[i] && mv.off[i + 1] <= b->msg_bytes);
 }
 
-// does the batch route its RSA_SHA256 lanes to the GPU? (signed-tx batches carry no flags)
+// does the batch send its RSA_SHA256 lanes to the GPU? A generic batch says so in its
+// flags; the signed-tx calls, whose structs carry no flags, set the same bit in the
+// batch they hand to the pipeline while cordahip_set_rsa_on_device is on.
 template <class MV>
-inline bool rsa_on_device(const cordahip_sig_batch* b, const MV& mv) {
-  return (b->flags & CORDAHIP_FLAG_RSA_ON_DEVICE) && !mv.tx_of;
+inline bool rsa_on_device(const cordahip_sig_batch* b, const MV&) {
+  return (b->flags & CORDAHIP_FLAG_RSA_ON_DEVICE) != 0;
+}
+// ... as a third section of each chunk (signed-tx batches: the messages are ids in HBM,
+// known chunk by chunk) instead of a section of the whole shard beside the chunks
+template <class MV>
+inline bool rsa_in_chunks(const cordahip_sig_batch* b, const MV& mv) {
+  return (b->flags & CORDAHIP_FLAG_RSA_ON_DEVICE) && mv.tx_of;
 }
 
 // What the host decides of RSA lane i (ranges checked): BAD_KEY / UNSUPPORTED from
@@ -89,7 +99,8 @@ inline void pack_rsa_row(const cordahip_sig_batch* b, uint64_t i, const rsa::Pub
 }
 
 template <class MV>
-inline uint16_t classify(const cordahip_sig_batch* b, const MV& mv, uint64_t i, uint64_t& mlen) {
+inline uint16_t classify(const cordahip_sig_batch* b, const MV& mv, uint64_t i, uint64_t& mlen,
+                         uint32_t* rsa_class = nullptr) {
   mlen = 0;
   if (!lane_ranges_ok(b, mv, i)) return kBadCsr;
   const uint64_t k0 = b->key_off[i], k1 = b->key_off[i + 1];
@@ -106,7 +117,10 @@ inline uint16_t classify(const cordahip_sig_batch* b, const MV& mv, uint64_t i, 
   if (sch == CORDAHIP_SCHEME_RSA_SHA256 && rsa_on_device(b, mv)) {
     rsa::PublicKey pk;
     const uint8_t st = rsa_lane_pre(b, mv, !(b->flags & CORDAHIP_FLAG_IS_VALID), i, pk);
-    if (st == kRsaToDevice) return kRsa;
+    if (st == kRsaToDevice) {
+      if (rsa_class) *rsa_class = pk.words / 32 - 2;
+      return kRsa;
+    }
     b->status[i] = st;
     return kDirect;
   }

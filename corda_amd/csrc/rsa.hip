@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rsa_route.hpp"
 #include "rsa_sign.hpp"
 #include "rsa_vkey.hpp"
 #include "runtime.hpp"
@@ -140,19 +141,38 @@ CDEV void dbl_mod(uint32_t (&x)[L], const uint32_t (&n)[L], int gl, int gbase) {
 // out[row] = in[row]^exp[row] mod mod[row], rows of W little-endian words. A row
 // that breaks the contract (even or zero modulus, exp 0, in >= mod) or has a
 // nonzero skip[row] gives a zero row and bad[row] = 1. in may alias out.
-template <int W>
+// kIdx (K20, the generic list of a routed launch): the grid covers the launch's rows and
+// nrows is not used; the list's length is read from *count, a block wholly past it
+// returns at once, as a block, and group j below it takes row perm[j] of the launch. The
+// list holds rows the prep left OK only, so skip is not read.
+// The two forms are instances of one kernel, as rsa_modexp_keyed_kernel's are
+// (rsa_vkey.hip says why); both instances take the registers, LDS and waves per SIMD the
+// kernel took before the template (70 / 97 / 130 VGPRs, 7 / 4 / 3 waves).
+template <int W, bool kIdx>
 __global__ void __launch_bounds__(kBlock) rsa_modexp_kernel(const uint32_t* __restrict__ mod,
                                                              const uint32_t* __restrict__ exp, const uint32_t* in,
                                                              uint64_t nrows, uint32_t* out, uint8_t* __restrict__ bad,
-                                                             const uint8_t* __restrict__ skip) {
+                                                             const uint8_t* __restrict__ skip,
+                                                             const unsigned int* __restrict__ perm,
+                                                             const unsigned int* __restrict__ count) {
   constexpr int L = W / kT;
   static_assert(W % kT == 0, "width class");
+  if (kIdx) {
+    nrows = *count;
+    if (!rsa_route_idx_block_live(blockIdx.x, nrows)) return;
+  }
   const int gl = threadIdx.x & (kT - 1);
   const int gbase = (threadIdx.x & 63) & ~(kT - 1);
-  const uint64_t row = (uint64_t)blockIdx.x * kGroupsPerBlock + threadIdx.x / kT;
+  uint64_t row = (uint64_t)blockIdx.x * kGroupsPerBlock + threadIdx.x / kT;
   // rows past the end and skipped rows load nothing and store nothing, and take
   // part in every cross-lane step with the stand-in operands below
-  bool ok = row < nrows && !(skip && skip[row]);
+  bool ok;
+  if (kIdx) {
+    ok = row < nrows;
+    row = ok ? perm[row] : 0;
+  } else {
+    ok = row < nrows && !(skip && skip[row]);
+  }
   const uint64_t base = row * W + (uint64_t)gl * L;
   uint32_t n[L], acc[L], other[L];
   uint32_t e = 1;
@@ -429,8 +449,8 @@ template <int W>
 hipError_t launch_modexp(const uint32_t* mod, const uint32_t* exp, const uint32_t* in, uint64_t n, uint32_t* out,
                          uint8_t* bad, const uint8_t* skip, hipStream_t s) {
   const uint64_t blocks = (n + kGroupsPerBlock - 1) / kGroupsPerBlock;
-  hipLaunchKernelGGL(rsa_modexp_kernel<W>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, mod, exp, in, n, out, bad,
-                     skip);
+  hipLaunchKernelGGL((rsa_modexp_kernel<W, false>), dim3((uint32_t)blocks), dim3(kBlock), 0, s, mod, exp, in, n, out,
+                     bad, skip, (const unsigned int*)nullptr, (const unsigned int*)nullptr);
   return hipGetLastError();
 }
 
@@ -497,6 +517,10 @@ hipError_t launch_rsa_pss_verify(const uint32_t* mod, const uint32_t* exp, const
 // K18, verification against registered keys: the kernels share this unit's device
 // functions (none of them changes; the generic kernels compile as before)
 #include "rsa_vkey.hip"
+
+// K20, routing of rows to K18's exponentiation on the GPU: the route pass and the launch
+// parts of a routed batch
+#include "rsa_route.hip"
 
 // K19, signing with registered private keys: shares the group layout and SHA-256; its
 // Montgomery product is a constant-time variant of its own

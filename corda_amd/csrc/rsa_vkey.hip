@@ -37,18 +37,38 @@ CDEV const uint32_t* rsa_vkey_record(const uint32_t* __restrict__ tab, uint32_t 
 // out[row] = in[row]^e mod n of the key key_id[row] names, rows of W little-endian
 // words. A row whose key is not live in class W, or with in >= n, gives a zero row
 // and bad[row] = 1; a row with a nonzero skip[row] is left alone. in may alias out.
-template <int W>
+// kIdx (K20, the keyed list of a routed launch): the grid covers the launch's rows and
+// nrows is not used; the list's length is read from *count, a block wholly past it
+// returns at once, as a block, and group j below it takes row perm[j] of the launch;
+// key_id is then route[], indexed by row like the rest. A keyed wave holds keyed rows only.
+// The two forms are instances of one kernel, not of a device function the kernels
+// inline: as a function's, K's wait in LDS is optimised away and K is carried in
+// registers through the chain (83 / 146 / 158 VGPRs for 72 / 106 / 142, 5 / 3 / 3 waves
+// per SIMD for 7 / 4 / 3).
+template <int W, bool kIdx>
 __global__ void __launch_bounds__(kBlock) rsa_modexp_keyed_kernel(const uint32_t* __restrict__ tab,
                                                                    const uint32_t* __restrict__ key_id,
                                                                    const uint32_t* in, uint64_t nrows, uint32_t* out,
                                                                    uint8_t* __restrict__ bad,
-                                                                   const uint8_t* __restrict__ skip) {
+                                                                   const uint8_t* __restrict__ skip,
+                                                                   const unsigned int* __restrict__ perm,
+                                                                   const unsigned int* __restrict__ count) {
   constexpr int L = W / kT;
+  if (kIdx) {
+    nrows = *count;
+    if (!rsa_route_idx_block_live(blockIdx.x, nrows)) return;
+  }
   static_assert(W % kT == 0 && L % 4 == 0, "width class");
   const int gl = threadIdx.x & (kT - 1);
   const int gbase = (threadIdx.x & 63) & ~(kT - 1);
-  const uint64_t row = (uint64_t)blockIdx.x * kGroupsPerBlock + threadIdx.x / kT;
-  bool ok = row < nrows && !(skip && skip[row]);
+  uint64_t row = (uint64_t)blockIdx.x * kGroupsPerBlock + threadIdx.x / kT;
+  bool ok;
+  if (kIdx) {
+    ok = row < nrows;
+    row = ok ? perm[row] : 0;
+  } else {
+    ok = row < nrows && !(skip && skip[row]);
+  }
   const uint64_t base = row * W + (uint64_t)gl * L;
   const uint32_t* rec = ok ? rsa_vkey_record(tab, key_id[row], W) : nullptr;
   // K waits in LDS for the last product, each lane's words in a column of its own
@@ -186,8 +206,8 @@ template <int W>
 hipError_t launch_modexp_keyed(const uint32_t* tab, const uint32_t* key_id, const uint32_t* in, uint64_t n,
                                uint32_t* out, uint8_t* bad, const uint8_t* skip, hipStream_t s) {
   const uint64_t blocks = (n + kGroupsPerBlock - 1) / kGroupsPerBlock;
-  hipLaunchKernelGGL(rsa_modexp_keyed_kernel<W>, dim3((uint32_t)blocks), dim3(kBlock), 0, s, tab, key_id, in, n, out,
-                     bad, skip);
+  hipLaunchKernelGGL((rsa_modexp_keyed_kernel<W, false>), dim3((uint32_t)blocks), dim3(kBlock), 0, s, tab, key_id, in,
+                     n, out, bad, skip, (const unsigned int*)nullptr, (const unsigned int*)nullptr);
   return hipGetLastError();
 }
 

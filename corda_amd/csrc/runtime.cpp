@@ -333,24 +333,106 @@ hipError_t ec_verify_enqueue(Device& d, const uint8_t* scheme, const uint8_t* ke
 // current, d.rsa_mu held). The workspace holds at most kRsaWsRows rows (the
 // launches loop over it) and is reused only after its previous user's kernels.
 constexpr uint64_t kRsaWsRows = 1ull << 17;  // x 518 B (4096-bit rows) = 68 MB at most
+// CORDAHIP_RSA_WS_ROWS (a multiple of 64, at least 64; tests): the rows the RSA workspace
+// holds at most and a launch takes at most, so that the launch loop runs with a few
+// hundred rows. 0: unset, the workspace's own size decides as before.
+static uint64_t rsa_ws_rows_env() {
+  static const uint64_t v = env_lanes("CORDAHIP_RSA_WS_ROWS", 0);
+  return v;
+}
+// the rows of class W a launch takes from the workspace as it is
+static uint64_t rsa_ws_rows(const RsaWork& w, uint32_t W) {
+  const uint64_t rows = w.ws.cap / rsa_ws_row_bytes(W) / 64 * 64;
+  return rsa_ws_rows_env() ? std::min(rows, rsa_ws_rows_env()) : rows;
+}
 hipError_t rsa_ws_grow(Device& d, uint32_t W, uint64_t n) {
   RsaWork& w = d.rsa;
-  const uint64_t rows = std::min<uint64_t>(kRsaWsRows, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
+  const uint64_t cap = rsa_ws_rows_env() ? rsa_ws_rows_env() : kRsaWsRows;
+  const uint64_t rows = std::min<uint64_t>(cap, (std::max<uint64_t>(n, 1) + 63) / 64 * 64);
   const size_t rb = rsa_ws_row_bytes(W);
   return w.ev.grow(w.ws.cap < rows * rb, [&] { return w.ws.ensure(rows * rb) ? hipErrorOutOfMemory : hipSuccess; });
 }
+
+// The keyed part of one launch of a routed RSA enqueue (K20; d.rsa_mu held, the
+// workspace's scratch large enough, s behind the workspace's fence and the launch's
+// prep): under d.vkey_mu, as every keyed call -- behind rsa_vkeys.ev, followed by
+// rsa_vkeys.ev -- the route pass and K18's exponentiation over the keyed list. *routed
+// stays false, and nothing is launched, when no RSA key is live any more or the
+// counters cannot be allocated: the launch then runs unrouted, which is always right.
+static hipError_t rsa_route_and_keyed(Device& d, const uint32_t* mod, const uint32_t* exp, uint32_t W, uint64_t lo,
+                                      uint64_t m, uint64_t ws_rows, uint64_t cap_rows, hipStream_t s, bool* routed) {
+  RsaWork& w = d.rsa;
+  std::lock_guard<std::mutex> vk(d.vkey_mu);
+  RsaVerifyKeys& k = d.rsa_vkeys;
+  if (!k.live || !k.tab.p) return hipSuccess;
+  if (!k.route_tot.p) {  // the device's first routed RSA enqueue
+    if (k.route_tot.ensure(16) != hipSuccess) {
+      (void)hipGetLastError();
+      return hipSuccess;
+    }
+    const hipError_t z = hipMemsetAsync(k.route_tot.p, 0, 16, s);
+    if (z != hipSuccess) return z;
+  }
+  *routed = true;
+  return fenced({&k.ev}, s, [&] {
+    return launch_rsa_routed_keyed(mod, exp, W, lo, m, k.tab.as<uint32_t>(), w.ws.as<uint8_t>(), ws_rows,
+                                   w.route.as<uint32_t>(), cap_rows, k.route_tot.as<unsigned long long>(), s);
+  });
+}
+
+// With RSA routing on and a live RSA key (K20), per launch: the prep, the route pass
+// and K18's exponentiation over the keyed list, K8's over the generic list, the check
+// -- all on s, no count read back. Lock order: rsa_mu (the caller's), then vkey_mu;
+// vkey_mu is never held while this function waits for a lock, a fence or an allocation.
 hipError_t rsa_verify_enqueue(Device& d, const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
                               const uint16_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len,
                               uint32_t W, uint64_t n, const uint8_t* pre, uint8_t* status,
                               unsigned long long* verdict, uint32_t flags, hipStream_t s) {
   RsaWork& w = d.rsa;
-  const size_t rb = rsa_ws_row_bytes(W);
+  bool want_route = d.rsa_route_on.load(std::memory_order_relaxed) && n;
+  if (want_route) {  // a look at the registry; decided for good, per launch, in rsa_route_and_keyed
+    std::lock_guard<std::mutex> vk(d.vkey_mu);
+    want_route = d.rsa_vkeys.live && d.rsa_vkeys.tab.p;
+  }
   hipError_t e = rsa_ws_grow(d, W, n);
+  if (e != hipSuccess) return e;
+  const uint64_t ws_rows = rsa_ws_rows(w, W);
+  // the scratch follows the largest launch of this call, behind the workspace's fence; no
+  // room for it: the batch is verified unrouted
+  const uint64_t cap_rows = std::min<uint64_t>(rsa_launch_rows(ws_rows), (n + 63) / 64 * 64);
+  const size_t sc_bytes = want_route ? rsa_route_scratch_bytes(cap_rows) : 0;
+  e = w.ev.grow(w.route.cap < sc_bytes, [&] {
+    if (w.route.ensure(sc_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      want_route = false;
+    }
+    return hipSuccess;
+  });
   e = e ? e : w.ev.wait(s);
-  e = e ? e
-        : launch_rsa_pss_verify(mod, exp, sigs, sig_len, msgs, msg_off, msg_len, W, n, pre, status, verdict,
-                                w.ws.as<uint8_t>(), w.ws.cap / rb / 64 * 64, flags, s);
-  return e ? e : w.ev.record(s);
+  if (e == hipSuccess && !want_route) {
+    e = launch_rsa_pss_verify(mod, exp, sigs, sig_len, msgs, msg_off, msg_len, W, n, pre, status, verdict,
+                              w.ws.as<uint8_t>(), ws_rows, flags, s);
+    return e ? e : w.ev.record(s);
+  }
+  const uint64_t lr = rsa_launch_rows(ws_rows);
+  if (e == hipSuccess && !lr) e = hipErrorInvalidValue;
+  bool launched = false;
+  for (uint64_t lo = 0; lo < n && e == hipSuccess; lo += lr) {
+    const uint64_t m = std::min(lr, n - lo);
+    launched = true;
+    e = launch_rsa_routed_head(mod, exp, sigs, sig_len, msg_off, msg_len, W, lo, m, pre, w.ws.as<uint8_t>(), ws_rows,
+                               flags, s);
+    bool routed = false;
+    e = e ? e : rsa_route_and_keyed(d, mod, exp, W, lo, m, ws_rows, cap_rows, s, &routed);
+    e = e ? e
+          : launch_rsa_routed_tail(mod, exp, msgs, msg_off, msg_len, W, lo, m, status, verdict, w.ws.as<uint8_t>(),
+                                   ws_rows, w.route.as<uint32_t>(), cap_rows, routed, s);
+  }
+  if (launched) {  // whatever was launched is fenced, also after a failure
+    const hipError_t r = w.ev.record(s);
+    return e ? e : r;
+  }
+  return e;
 }
 
 // The Ed25519 workspace of a slot grown for n lanes (d.ed_mu[slot] held); `more`

@@ -252,6 +252,26 @@ hipError_t launch_rsa_verify_keyed(const uint32_t* vtab, const uint32_t* key_id,
                                    uint32_t msg_len, uint32_t W, uint64_t n, uint8_t* status,
                                    unsigned long long* verdict, uint8_t* ws, uint64_t ws_rows, uint32_t flags,
                                    hipStream_t s);
+// rsa_route.hip (K20, in rsa.hip's unit): one launch of a routed batch in three parts --
+// the prep; the counts cleared, the route pass (rsa_route.hpp) and K18's exponentiation
+// over the keyed list; K8's over the generic list and the check -- so that the caller
+// holds the key table's lock around the middle one only. m rows from row lo, at most
+// rsa_launch_rows(ws_rows); scratch: rsa_route_scratch_bytes(cap_rows), cap_rows >= m;
+// totals: the device's cumulative (keyed, generic) row counters. routed false in the
+// tail: the middle part did not run, K8's kernel takes every row as in an unrouted launch.
+size_t rsa_route_scratch_bytes(uint64_t cap_rows);
+uint64_t rsa_launch_rows(uint64_t ws_rows);
+hipError_t launch_rsa_routed_head(const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
+                                  const uint16_t* sig_len, const uint64_t* msg_off, uint32_t msg_len, uint32_t W,
+                                  uint64_t lo, uint64_t m, const uint8_t* pre, uint8_t* ws, uint64_t ws_rows,
+                                  uint32_t flags, hipStream_t s);
+hipError_t launch_rsa_routed_keyed(const uint32_t* mod, const uint32_t* exp, uint32_t W, uint64_t lo, uint64_t m,
+                                   const uint32_t* vtab, uint8_t* ws, uint64_t ws_rows, uint32_t* scratch,
+                                   uint64_t cap_rows, unsigned long long* totals, hipStream_t s);
+hipError_t launch_rsa_routed_tail(const uint32_t* mod, const uint32_t* exp, const uint8_t* msgs,
+                                  const uint64_t* msg_off, uint32_t msg_len, uint32_t W, uint64_t lo, uint64_t m,
+                                  uint8_t* status, unsigned long long* verdict, uint8_t* ws, uint64_t ws_rows,
+                                  const uint32_t* scratch, uint64_t cap_rows, bool routed, hipStream_t s);
 // rsa_sign_keyed.hip (K19, in rsa.hip's unit): RSASSA-PSS signatures with registered
 // private keys. stab: the device's RSA signer table (rsa_sign.hpp: rsa_signtab_bytes();
 // null: no key was ever added, every ungated row is unknown); key_id[n], salts[n * 32],
@@ -443,25 +463,34 @@ constexpr int kTxStages = CORDAHIP_TX_STAGES;
 // batch's lanes, classified and packed into BOTH sections' pinned buffers
 // (h/d[0..4] Ed25519 keys, sigs, msgs, pre-status, status; [5..13] ECDSA
 // scheme, keys, key_len, sigs, sig_len, msgs, msg_off, pre-status, status);
-// the lane lists say where each row's status goes back
+// the lane lists say where each row's status goes back.
+// Signed-tx chunks with cordahip_set_rsa_on_device on carry a third section, the
+// chunk's RSA_SHA256 lanes (rh/rd[0..5]: moduli, exponents, signatures, signature
+// lengths, each row's id index, statuses; rd[6]: the gathered ids; the width classes'
+// rows one class after the other); rsa_rows: its rows in flight (rsa_done follows them).
 struct BatchStage {
-  hipEvent_t copied = nullptr, ed_done = nullptr, ec_done = nullptr;
+  hipEvent_t copied = nullptr, ed_done = nullptr, ec_done = nullptr, rsa_done = nullptr;
   PinBuf h[14];
   DevBuf d[14];
   PinBuf hidx[2];  // device-id messages (MsgView::dev): per Ed25519 / ECDSA row, its tx's id index
   DevBuf didx[2];
-  std::vector<uint64_t> ed_lanes, ec_lanes;
+  PinBuf rh[6];
+  DevBuf rd[7];
+  std::vector<uint64_t> ed_lanes, ec_lanes, rsa_lanes;
+  uint64_t rsa_rows = 0;
   uint64_t a = 0, b = 0;  // the chunk's lanes [a, b) (per-chunk verdict words)
   bool direct = false;    // rows == lanes: statuses / verdict words went straight to the caller's pinned arrays
   DevBuf dverdict;        // the direct chunks' verdict words (wave ballots of the Ed25519 kernel)
   bool pending = false;
   template <class V>
   void visit(V& v) {
-    for (hipEvent_t* e : {&copied, &ed_done, &ec_done}) v.event(*e, true);
+    for (hipEvent_t* e : {&copied, &ed_done, &ec_done, &rsa_done}) v.event(*e, true);
     for (PinBuf& b : h) v.pin(b, kFreed);
     for (DevBuf& b : d) v.dev(b, kFreed);
     for (PinBuf& b : hidx) v.pin(b, kFreed);
     for (DevBuf& b : didx) v.dev(b, kFreed);
+    for (PinBuf& b : rh) v.pin(b, kFreed);
+    for (DevBuf& b : rd) v.dev(b, kFreed);
     v.dev(dverdict, kFreed);
   }
 };
@@ -529,15 +558,19 @@ struct EcWork {  // device buffers of the ECDSA paths (grow-only)
 // RSA (rsa.hip): the verify launches' workspace and the single stage of the
 // generic batches' RSA section (h/d[0..6]: moduli, exponents, signatures,
 // signature lengths, messages, message offsets, statuses). Nothing here is
-// allocated before a device's first RSA lane.
+// allocated before a device's first RSA lane. route: the workspace's routing scratch
+// (K20, rsa_route.hpp: a 64-byte header and 12 bytes per row of the largest launch),
+// behind the same lock and fence, released with the workspace.
 struct RsaWork {
   DevBuf ws;
-  Fence ev;  // last enqueued user of ws (cross-stream reuse)
+  DevBuf route;
+  Fence ev;  // last enqueued user of ws and route (cross-stream reuse)
   PinBuf h[7];
   DevBuf d[7];
   template <class V>
   void visit(V& v) {
     v.dev(ws, kFreed);
+    v.dev(route, kFreed);
     v.fence(ev);
     for (PinBuf& b : h) v.pin(b, kFreed);
     for (DevBuf& b : d) v.dev(b, kFreed);
@@ -679,8 +712,12 @@ struct EcVerifyKeys : RoutedKeyTable {
 // length, width class, n', n and K = R^e mod n -- 67,584 bytes). The host builds a
 // record and it crosses in stage (1,056 bytes); no kernel builds anything. Allocated by
 // a device's first RSA add, under Device::vkey_mu like the other families' tables.
-struct RsaVerifyKeys : KeyTable {
+// live: the slots whose record is live on this device (bit per slot, Device::vkey_mu):
+// routed enqueues (K20) ask for it. route_tot: as VerifyKeys' (K20).
+struct RsaVerifyKeys : RoutedKeyTable {
+  uint64_t live = 0;
   TabSpan record(uint32_t slot) const;
+  void forget(uint32_t slot) { live &= ~(1ull << slot); }
 };
 
 // a page-locked buffer and its twin on the device (ensure: true when it failed)
@@ -918,7 +955,14 @@ struct Device {
   std::atomic<uint32_t> ec_route_on{0};
   // RSA verification against registered keys (K18): the records of the same registry's
   // RSA keys, under the same vkey_mu, with a fence of their own.
+  // Routing (K20, cordahip_vkey_set_routing_rsa): with rsa_route_on set and a live RSA
+  // key (rsa_vkeys.live), every launch of rsa_verify_enqueue is a keyed call too: under the
+  // caller's rsa_mu it takes vkey_mu for the route pass and K18's exponentiation -- behind
+  // rsa_vkeys.ev, followed by rsa_vkeys.ev -- and drops it before the generic
+  // exponentiation and the check. With rsa_route_on clear it takes no lock it did not
+  // take before.
   RsaVerifyKeys rsa_vkeys;
+  std::atomic<uint32_t> rsa_route_on{0};
   // the chunk stage of cordahip_verify_keyed, cordahip_ecdsa_verify_keyed and
   // cordahip_rsa_verify_keyed (KeyedStage)
   KeyedStage vkey_stage;
@@ -1284,6 +1328,9 @@ struct cordahip_ctx {
   // under signers.mu
   RsaVkeyMirror rsa_sign_mirror[cordahip::kSignKeySlots];
   uint32_t rsa_signers = 0;
+  // cordahip_set_rsa_on_device: the signed-tx host calls, whose structs carry no flags,
+  // verify their RSA_SHA256 lanes on the GPU (CORDAHIP_FLAG_RSA_ON_DEVICE's counterpart)
+  std::atomic<uint32_t> rsa_on_device{0};
   // the notary commit logs (cordahip_commit_log_create / _destroy): id -> log; ids
   // count up and are never reused. logs_mu guards the map and the counter only.
   std::mutex logs_mu;

@@ -494,6 +494,27 @@ class Engine:
               "cordahip_vkey_route_stats_ecdsa")
         return k.value, g.value
 
+    def vkey_set_routing_rsa(self, on: bool):
+        """cordahip_vkey_set_routing_rsa: on, every generic RSA launch (the dense device call, the RSA section
+        of a generic batch with FLAG_RSA_ON_DEVICE) sends the rows whose width class, exponent and modulus
+        words are a registered RSA key's to the keyed exponentiation, on the GPU; statuses are those of the
+        unrouted call. Off (the default): nothing changes. The other families' switches are their own."""
+        check(lib().cordahip_vkey_set_routing_rsa(self._ctx, 1 if on else 0), "cordahip_vkey_set_routing_rsa")
+
+    def set_rsa_on_device(self, on: bool):
+        """cordahip_set_rsa_on_device: on, the signed-transaction host calls (signed_tx_verify, tx_submit,
+        their covered and component forms) verify RSA_SHA256 signatures on the GPU, each over its
+        transaction's id under doVerify rules, instead of answering UNSUPPORTED. Off: the default."""
+        check(lib().cordahip_set_rsa_on_device(self._ctx, 1 if on else 0), "cordahip_set_rsa_on_device")
+
+    def vkey_route_stats_rsa(self, device: int = 0):
+        """cordahip_vkey_route_stats_rsa: (keyed_rows, generic_rows) that routed RSA enqueues on `device`
+        have matched and not matched since init; waits for the routed work already enqueued there."""
+        k, g = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().cordahip_vkey_route_stats_rsa(self._ctx, device, ctypes.byref(k), ctypes.byref(g)),
+              "cordahip_vkey_route_stats_rsa")
+        return k.value, g.value
+
     def verify_keyed_batch(self, key_ids: Sequence[int], sigs: Sequence[bytes], msgs: Sequence[bytes],
                            is_valid: bool = False, async_: bool = False):
         """cordahip_verify_keyed / cordahip_verify_keyed_submit: lane i checks sigs[i] over msgs[i] against

@@ -846,6 +846,85 @@ int cordahip_rsa_verify_keyed_device(cordahip_ctx* ctx, int device, const void* 
 int cordahip_rsa_public_op_keyed_device(cordahip_ctx* ctx, int device, const void* d_key_id, const void* d_in,
                                         uint32_t mod_words, uint64_t n, void* d_out, void* hip_stream);
 
+/* ---- Routing registered-key RSA rows to the keyed exponentiation (kernel K20) ----
+ * What kernels K14 and K15 do for Ed25519 and ECDSA lanes, for RSA rows and K18:
+ * the calls that carry key bytes -- cordahip_rsa_pss_verify_device, the RSA
+ * section of cordahip_sig_verify / _submit with CORDAHIP_FLAG_RSA_ON_DEVICE and the
+ * RSA lanes of the signed-tx host calls (cordahip_set_rsa_on_device below) --
+ * recognise the rows of registered RSA keys themselves, on the GPU, and run K18's
+ * 18 modular products on them where the generic kernel runs 29 to 31. A switch and
+ * counters of their own: the Ed25519 and ECDSA switches and counters keep their
+ * meaning.
+ *
+ * cordahip_vkey_set_routing_rsa(ctx, on): on != 0 turns RSA routing on for every
+ * device of the context, 0 (the default) off. It takes effect with the next RSA
+ * enqueue. Off, every call does exactly what it did before this switch existed:
+ * nothing more is launched, allocated or locked (one relaxed atomic load decides).
+ *
+ * The rule, while RSA routing is on and the device holds at least one live RSA
+ * verification key: a row of a launch of width class W (mod_words) is keyed exactly
+ * when some live RSA record has width class W, the row's exponent and the row's W
+ * modulus words. Nothing else enters the decision. A registered 2048-bit key whose
+ * modulus sits zero-padded in a 96- or 128-word row misses (its class is 64) and
+ * stays generic, which answers exactly what it answers today, as does the registered
+ * modulus under another exponent. Of two live records of one key either may serve.
+ * The row still carries its modulus, so the generic prep and check kernels serve
+ * every row unchanged -- the bit length, the UNSUPPORTED, EMPTY and sig_len rules
+ * and the PSS rules are the generic path's -- and only the exponentiation between
+ * them differs. Every row's status and verdict bit equal the unrouted call's under
+ * both flags values; no row of these calls ever answers
+ * CORDAHIP_VERIFY_UNKNOWN_KEY. cordahip_rsa_public_op_device is not routed, and
+ * the K18 calls that take ids are untouched.
+ * Per launch (at most the RSA workspace's rows) the route pass writes each row's key
+ * id and compacts the rows that need an exponentiation into a keyed and a generic
+ * list; K18's kernel runs over the keyed list and K8's over the generic list, so a
+ * keyed wave holds keyed rows only. All of it runs on the caller's stream and the
+ * host reads no count back. It needs 64 bytes and 12 bytes per row of the largest
+ * launch of scratch beside the RSA workspace, counted in cordahip_device_mem and
+ * released by cordahip_trim and the idle release with the workspace, and 16 bytes of
+ * counters per device, which are kept. A batch whose scratch does not fit in device
+ * memory is verified unrouted, not failed, as is a launch enqueued after the
+ * device's last RSA key was removed.
+ *
+ * Ordering: a routed launch is a keyed call. cordahip_vkey_remove waits for the
+ * routed launches already enqueued before it clears a record, so no record dies
+ * between a row's match and its exponentiation; an add or a remove that races a
+ * batch decides only which kernel a row takes, never its status.
+ *
+ * cordahip_vkey_route_stats_rsa: the rows that routed RSA enqueues on `device` have
+ * matched to a registered key and not matched since cordahip_init, whether the prep
+ * decided the row or not: keyed + generic is the number of rows enqueued while RSA
+ * routing was on and the device held a live RSA key. The call waits for the routed
+ * work already enqueued on the device. A device the context does not have, or a NULL
+ * pointer, is CORDAHIP_ERR_INVALID_ARG.
+ *
+ * CORDAHIP_RSA_WS_ROWS (environment, tests): a multiple of 64, at least 64, caps the
+ * rows of the RSA workspace and of a launch, so that the launch loop runs with a few
+ * hundred rows. Unset, nothing changes. */
+int cordahip_vkey_set_routing_rsa(cordahip_ctx* ctx, uint32_t on);
+int cordahip_vkey_route_stats_rsa(cordahip_ctx* ctx, int device, uint64_t* keyed_rows, uint64_t* generic_rows);
+
+/* ---- RSA_SHA256 lanes in the signed-transaction host calls -------------------
+ * cordahip_set_rsa_on_device(ctx, on): the context-level counterpart of
+ * CORDAHIP_FLAG_RSA_ON_DEVICE for the entry points whose structs carry no flags:
+ * cordahip_signed_tx_verify, cordahip_tx_submit, their _covered forms and the four
+ * txcomp forms. 0 (the default): an RSA_SHA256 signature of a transaction is
+ * CORDAHIP_STATUS_UNSUPPORTED there, exactly as before this switch existed. on != 0:
+ * it gets exactly the status cordahip_sig_verify with CORDAHIP_FLAG_RSA_ON_DEVICE
+ * and flags 0 (doVerify rules, as checkSignaturesAreValid uses) gives for the same
+ * key and signature with the transaction's id as message; first_bad_sig and
+ * tx_status follow from it, and a transaction whose id threw still answers the
+ * id's status on every lane. It takes effect with the next call; a NULL context is
+ * CORDAHIP_ERR_INVALID_ARG. cordahip_sig_verify keeps its flag and is not changed.
+ * A chunk's RSA lanes are a third section of that chunk: classified and packed
+ * with it by width class, their messages gathered from the ids in HBM, verified
+ * on the device's RSA stream after the chunk's Ed25519 and ECDSA work and waited
+ * for before the chunk's transactions are reduced. They go through the generic RSA
+ * enqueue, so cordahip_vkey_set_routing_rsa applies to them.
+ * Not covered: cordahip_stream_verify (its struct has no RSA section; adding one is
+ * an ABI change) and the two Ed25519-only device-resident signed-tx calls. */
+int cordahip_set_rsa_on_device(cordahip_ctx* ctx, uint32_t on);
+
 /* ECDSA keygen + sign (device memory), corpus generation: per lane scheme 2/3,
  * d = SHA-256(seed) mod n, k = SHA-256(seed || msg[:64]) mod n; writes the
  * uncompressed SEC1 key (65-byte slot, key_len = 65) and the DER signature

@@ -123,7 +123,9 @@ Count visited(T& t, size_t plain, const char* name) {
 
 // the plain members of the structs that have some (bool: with its padding)
 constexpr size_t kPackPlain = 8 /* pending */ + 3 * sizeof(uint64_t);
-constexpr size_t kBatchPlain = 2 * sizeof(std::vector<uint64_t>) + 2 * sizeof(uint64_t) + 8 /* direct */ + 8 /* pending */;
+// the lane lists (ed, ec, rsa), a and b, rsa_rows, direct, pending
+constexpr size_t kBatchPlain =
+    3 * sizeof(std::vector<uint64_t>) + 3 * sizeof(uint64_t) + 8 /* direct */ + 8 /* pending */;
 constexpr size_t kTxSetPlain = sizeof(uint32_t*) /* kryo_usage_dev */ + kTxStages * kBatchPlain;
 
 struct Grow : Visitor {  // every buffer a few bytes, every event and stream created
@@ -187,7 +189,7 @@ int main() {
     EcVerifyKeys ek;
     visited(ek, sizeof(CurveBook<cordahip::kVkeySlots>) /* book */, "EcVerifyKeys");
     RsaVerifyKeys rk;
-    visited(rk, 0, "RsaVerifyKeys");
+    visited(rk, sizeof(uint64_t) /* live */, "RsaVerifyKeys");
     KeyedStage ks;
     visited(ks, sizeof(std::mutex) /* mu */, "KeyedStage");
     visited(tw, 0, "TxWork");
@@ -207,12 +209,12 @@ int main() {
     // stage's and its key table, which has a visit of its own (f)
     // and the verification keys' mutex, their chunk stage's and their tables, visited with the signer's (f)
     // and the registered ECDSA keys' tables with what the host knows of them (f)
-    // and the two routing switches (route_on, ec_route_on: each padded to 8 bytes)
+    // and the three routing switches (route_on, ec_route_on, rsa_route_on: each padded to 8 bytes)
     // and the ECDSA signer's table with what the host knows of it (f)
     // and the registered RSA keys' table (f)
     // and the RSA signer's table with what the host knows of it (f)
     constexpr size_t kDeviceOwnPlain = 1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys) + 2 * sizeof(std::mutex) +
-                                       sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + 16 + sizeof(EcSignKeys) +
+                                       sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + 24 + sizeof(EcSignKeys) +
                                        sizeof(RsaVerifyKeys) + sizeof(RsaSignKeys);
     const Count c = visited(*d, kDeviceOwnPlain + kTxSets * kTxSetPlain + kPackStages * kPackPlain, "Device");
     ndev = c.ndev, npin = c.npin, nev = c.nfence + c.nevent;
@@ -276,12 +278,13 @@ int main() {
     k->signer_keys([&](auto&) { nsign++; });
     k->verify_keys([&](auto&) { nver++; });
     CHECK(nsign == 3 && nver == 3);
-    // the six tables and the routed lanes' counters (VerifyKeys::route_tot, EcVerifyKeys::route_tot)
-    CHECK(g.dev.size() == before + 8 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
+    // the six tables and the routed lanes' counters (route_tot of VerifyKeys, EcVerifyKeys, RsaVerifyKeys)
+    CHECK(g.dev.size() == before + 9 && k->keys.tab.p && k->keys.stage.p && k->keys.ev.ev);
     CHECK(k->ec_keys.tab.dev == 6 && k->ec_keys.tab.p && k->ec_keys.stage.p && k->ec_keys.ev.ev);
     CHECK(k->rsa_keys.tab.dev == 6 && k->rsa_keys.tab.p && k->rsa_keys.stage.p && k->rsa_keys.ev.ev);
     CHECK(k->vkeys.route_tot.dev == 6 && k->vkeys.route_tot.p);
     CHECK(k->ec_vkeys.route_tot.dev == 6 && k->ec_vkeys.route_tot.p);
+    CHECK(k->rsa_vkeys.route_tot.dev == 6 && k->rsa_vkeys.route_tot.p);
     CHECK(k->vkeys.tab.dev == 6 && k->vkeys.tab.p && k->vkeys.stage.p && k->vkeys.ev.ev);
     CHECK(k->ec_vkeys.tab.dev == 6 && k->ec_vkeys.tab.p && k->ec_vkeys.stage.p && k->ec_vkeys.ev.ev);
     void *tab = k->keys.tab.p, *stage = k->keys.stage.p, *vtab = k->vkeys.tab.p, *vstage = k->vkeys.stage.p;
@@ -302,7 +305,8 @@ int main() {
     CHECK(kk.devs.size() == kept.devs.size());
     CHECK(mem_acct(6).in_use.load() ==
           kk.bytes + k->keys.tab.cap + k->ec_keys.tab.cap + k->vkeys.tab.cap + k->vkeys.route_tot.cap +
-              k->ec_vkeys.tab.cap + k->ec_vkeys.route_tot.cap + k->rsa_vkeys.tab.cap + k->rsa_keys.tab.cap);
+              k->ec_vkeys.tab.cap + k->ec_vkeys.route_tot.cap + k->rsa_vkeys.tab.cap + k->rsa_vkeys.route_tot.cap +
+              k->rsa_keys.tab.cap);
     delete k;
     CHECK(g.clean() && mem_acct(6).in_use.load() == 0);
   }

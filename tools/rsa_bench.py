@@ -36,6 +36,23 @@ the 2048-bit class with a 1024-bit key and with a 2048-bit key. Per leg:
                             the product counts of the two schedules and the step ratio they predict
                             when only the modexp share of the generic step shrinks
   differing_lanes           lanes whose statuses differ between the two calls (must be 0)
+
+--routed: routing of registered-key rows (K20, cordahip_vkey_set_routing_rsa) A/B in one process on one
+box. The same resident rows go through cordahip_rsa_pss_verify_device with routing off and on, the
+two alternating step by step on one stream, timed with device events; every lane's status is compared
+between the legs. Legs: one 3072-bit key and one 2048-bit key registered, with f = 0, 0.5 and 1 of the
+rows (interleaved) on the registered key and the others on an unregistered key of the same size; at
+f = 1 cordahip_rsa_verify_keyed_device is a third alternating leg. Per leg:
+  off_ms, on_ms (and keyed_ms)   median step times with min and max
+  off_spread_ms                  the largest difference between consecutive off steps; the bar is
+                                 off_ms - on_ms > 3 x that (over_bar)
+  keyed_rows, generic_rows       cordahip_vkey_route_stats_rsa's movement over one routed step
+  differing_lanes                must be 0
+and per key model_half_ms = 0.5 on_ms(f = 0) + 0.5 on_ms(f = 1) beside the measured on_ms(f = 0.5).
+
+--ab A.so A2.so B.so: the routing-off path alone. The dense call through three copies of the library
+loaded side by side (A and A2 the same build, e.g. the parent commit's, B this one), alternating;
+b_vs_a must sit inside a2_vs_a's size.
 """
 import argparse
 import json
@@ -198,6 +215,226 @@ def keyed_main(a):
     return 0 if res["differing_lanes"] == 0 else 1
 
 
+def fixture_keys():
+    with open(os.path.join(ROOT, "tests", "golden", "rsa_pss_vectors.json")) as f:
+        g = json.load(f)
+    return [{f: int(k[f], 16) for f in ("n", "e", "d", "p", "q")} for k in g["keys"]
+            if "d" in k and int(k["e"], 16) == 65537]
+
+
+def stats(v):
+    return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))}
+
+
+_SIGNED = {}
+
+
+def dense_rows(torch, a, w, keys, share, rng):
+    """n resident rows of class w: `share` of them (interleaved) on keys[0], the others on keys[1];
+    a.distinct CRT signatures per key tiled, 1 % of the rows corrupted. Device tensors and the bad mask."""
+    import bc_rsa_pss as bc
+    n = 1 << a.rows_log2
+    per = []
+    for k in keys:
+        if (k["n"], w) in _SIGNED:  # a key's signatures are made once per run
+            per.append(_SIGNED[(k["n"], w)])
+            continue
+        mod = np.frombuffer(k["n"].to_bytes(4 * w, "little"), "<u4")
+        sigs = np.zeros((a.distinct, 4 * w), np.uint8)
+        sl = np.zeros(a.distinct, np.uint16)
+        msgs = np.zeros((a.distinct, 32), np.uint8)
+        for i in range(a.distinct):
+            m = rng.randbytes(32)
+            em = bc.encode_em(m, k["n"].bit_length(), rng.randbytes(32))
+            sig = bc.sign_crt(em, k["p"], k["q"], k["d"]).to_bytes((k["n"].bit_length() + 7) // 8, "big")
+            sigs[i, :len(sig)] = np.frombuffer(sig, np.uint8)
+            sl[i] = len(sig)
+            msgs[i] = np.frombuffer(m, np.uint8)
+        _SIGNED[(k["n"], w)] = (mod, sigs, sl, msgs)
+        per.append(_SIGNED[(k["n"], w)])
+    r = np.arange(n)
+    on_first = np.floor((r + 1) * share) > np.floor(r * share)  # interleaved: every 1 / share-th row
+    which = np.where(on_first, 0, 1)
+    idx = r % a.distinct
+    mod = np.stack([per[0][0], per[1][0]])[which]
+    exp = np.array([keys[0]["e"], keys[1]["e"]], np.uint32)[which]
+    sigs = np.where(on_first[:, None], per[0][1][idx], per[1][1][idx])
+    sl = np.where(on_first, per[0][2][idx], per[1][2][idx]).astype(np.uint16)
+    msgs = np.where(on_first[:, None], per[0][3][idx], per[1][3][idx])
+    bad = np.zeros(n, bool)
+    bad[rng.sample(range(n), n // 100)] = True
+    sigs[bad, 100] ^= 0x10  # 1 % corrupted
+    dev = torch.device("cuda:0")
+    t = lambda x, ty: torch.from_numpy(np.ascontiguousarray(x).view(ty)).to(dev)  # noqa: E731
+    return (t(mod, np.int32), t(exp, np.int32), t(sigs, np.uint8), t(sl, np.int16), t(msgs, np.uint8)), bad, on_first
+
+
+def routed_main(a):
+    import torch
+    if not torch.cuda.is_available():
+        print("rsa_bench.py: no GPU", file=sys.stderr)
+        return 2
+    import bc_rsa_pss as bc
+    from corda_amd.engine import Engine
+    fix = fixture_keys()
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.Stream(device=dev)
+    rng = random.Random(0xBE20)
+    n = 1 << a.rows_log2
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    res = {"workload": "rsa_pss_verify_device, RSA routing off and on alternating", "rows": n, "steps": a.steps,
+           "warmup": a.warmup, "distinct_signatures_per_key": a.distinct, "legs": [], "models": []}
+    with Engine(1) as eng:
+        for bits, w in ((3072, 96), (2048, 64)):
+            same = [k for k in fix if k["n"].bit_length() == bits]
+            other = same[1:2]
+            if not other:  # the fixture has one such key: another of the size from OpenSSL, else the nearest
+                try:
+                    import openssl_rsa_pss as ossl
+                    h, k = ossl.keygen(bits)
+                    ossl.free_key(h)
+                    other = [k]
+                except (OSError, AttributeError, AssertionError):
+                    other = [k for k in fix if k["n"].bit_length() == bits - 1][:1]
+            keys = [same[0], other[0]]
+            kid, st = eng.vkey_add_rsa(bc.encode_key(keys[0]["n"], keys[0]["e"]))
+            assert st == 0, st
+            on_ms = {}
+            for share in (0.0, 0.5, 1.0):
+                (tm, te, ts, tl, tg), bad, on_first = dense_rows(torch, a, w, keys, share, rng)
+                st_off = torch.empty(n, dtype=torch.uint8, device=dev)
+                st_on = torch.empty(n, dtype=torch.uint8, device=dev)
+                st_k = torch.empty(n, dtype=torch.uint8, device=dev)
+                verdict = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev)
+                tk = torch.full((n,), kid, dtype=torch.int64, device=dev).to(torch.int32)
+
+                def leg_off():
+                    eng.vkey_set_routing_rsa(False)
+                    eng.rsa_pss_verify_device(tm, te, ts, tl, tg, st_off, verdict, stream=stream)
+
+                def leg_on():
+                    eng.vkey_set_routing_rsa(True)
+                    eng.rsa_pss_verify_device(tm, te, ts, tl, tg, st_on, verdict, stream=stream)
+
+                def leg_keyed():
+                    eng.rsa_verify_keyed_device(tk, ts, tl, tg, st_k, verdict, stream=stream)
+
+                fns = [leg_off, leg_on] + ([leg_keyed] if share == 1.0 else [])
+                ms = [[] for _ in fns]
+                for step in range(a.warmup + a.steps):
+                    for q, fn in enumerate(fns):
+                        v = timed(fn)
+                        if step >= a.warmup:
+                            ms[q].append(v)
+                before = eng.vkey_route_stats_rsa()
+                leg_on()
+                stream.synchronize()
+                after = eng.vkey_route_stats_rsa()
+                eng.vkey_set_routing_rsa(False)
+                s_off, s_on = st_off.cpu().numpy(), st_on.cpu().numpy()
+                differing = int((s_off != s_on).sum())
+                assert int((s_off == 0).sum()) == n - int(bad.sum()) and (s_off[bad] == 1).all(), "wrong statuses"
+                if share == 1.0:
+                    differing += int((st_k.cpu().numpy() != s_off).sum())
+                off, on = stats(ms[0]), stats(ms[1])
+                spread = max(abs(x - y) for x, y in zip(ms[0], ms[0][1:])) if len(ms[0]) > 1 else 0.0
+                leg = {"modulus_bits": bits, "mod_words": w, "other_key_bits": keys[1]["n"].bit_length(), "f": share,
+                       "off_ms": off, "on_ms": on, "off_spread_ms": spread, "ratio": off["median"] / on["median"],
+                       "margin_ms": off["median"] - on["median"],
+                       "over_bar": bool(off["median"] - on["median"] > 3 * spread),
+                       "keyed_rows": after[0] - before[0], "generic_rows": after[1] - before[1],
+                       "rows_on_registered_key": int(on_first.sum()), "differing_lanes": differing,
+                       "off_verifs_per_s": n / (off["median"] * 1e-3), "on_verifs_per_s": n / (on["median"] * 1e-3)}
+                if share == 1.0:
+                    kd = stats(ms[2])
+                    leg.update({"keyed_ms": kd, "routed_over_id_keyed": on["median"] / kd["median"],
+                                "off_over_id_keyed": off["median"] / kd["median"]})
+                assert leg["keyed_rows"] == leg["rows_on_registered_key"] and leg["keyed_rows"] + leg["generic_rows"] == n
+                on_ms[share] = on["median"]
+                res["legs"].append(leg)
+            eng.vkey_remove(kid)
+            res["models"].append({"modulus_bits": bits, "on_half_ms": on_ms[0.5],
+                                  "model_half_ms": 0.5 * on_ms[0.0] + 0.5 * on_ms[1.0]})
+    res["differing_lanes"] = sum(l["differing_lanes"] for l in res["legs"])
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if res["differing_lanes"] == 0 else 1
+
+
+def ab_main(a):
+    """the dense call, routing never touched, through three side-by-side copies of the library"""
+    import ctypes
+
+    import torch
+    if not torch.cuda.is_available():
+        print("rsa_bench.py: no GPU", file=sys.stderr)
+        return 2
+    vp, u64, u32, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
+    libs = []
+    for path in a.ab:
+        l = ctypes.CDLL(os.path.abspath(path))
+        l.cordahip_init.argtypes, l.cordahip_init.restype = [u32, ctypes.POINTER(vp)], i32
+        l.cordahip_shutdown.argtypes, l.cordahip_shutdown.restype = [vp], None
+        l.cordahip_rsa_pss_verify_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp]
+        l.cordahip_rsa_pss_verify_device.restype = i32
+        ctx = vp()
+        assert l.cordahip_init(1, ctypes.byref(ctx)) == 0, path
+        libs.append((l, ctx))
+    fix = fixture_keys()
+    keys = [k for k in fix if k["n"].bit_length() == 3072][:1] + [k for k in fix if k["n"].bit_length() == 3071][:1]
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.Stream(device=dev)
+    n = 1 << a.rows_log2
+    (tm, te, ts, tl, tg), bad, _ = dense_rows(torch, a, 96, keys, 0.5, random.Random(0xBEAB))
+    outs = [(torch.empty(n, dtype=torch.uint8, device=dev), torch.empty((n + 63) // 64, dtype=torch.int64, device=dev))
+            for _ in libs]
+
+    def call(k):
+        l, ctx = libs[k]
+        rc = l.cordahip_rsa_pss_verify_device(ctx, 0, tm.data_ptr(), te.data_ptr(), ts.data_ptr(), tl.data_ptr(),
+                                              tg.data_ptr(), 32, 96, n, outs[k][0].data_ptr(), outs[k][1].data_ptr(),
+                                              stream.cuda_stream)
+        assert rc == 0
+
+    ms = [[], [], []]
+    for step in range(a.warmup + a.steps):
+        for k in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            call(k)
+            e1.record(stream)
+            e1.synchronize()
+            if step >= a.warmup:
+                ms[k].append(e0.elapsed_time(e1))
+    differ = sum(int((outs[0][j] != outs[k][j]).sum()) for k in (1, 2) for j in (0, 1))
+    st = [stats(x) for x in ms]
+    res = {"workload": "rsa_pss_verify_device (3072-bit class), routing off, three libraries side by side", "rows": n,
+           "steps": a.steps, "warmup": a.warmup,
+           "libs": [os.path.basename(os.path.dirname(os.path.abspath(p))) for p in a.ab], "ab_ms": st,
+           "a2_vs_a": st[1]["median"] / st[0]["median"] - 1, "b_vs_a": st[2]["median"] / st[0]["median"] - 1,
+           "b_vs_a2": st[2]["median"] / st[1]["median"] - 1, "rejected_rows": int((outs[0][0] != 0).sum()),
+           "differing_lanes": differ}
+    for l, ctx in libs:
+        l.cordahip_shutdown(ctx)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if differ == 0 else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows-log2", type=int, default=18)
@@ -208,9 +445,16 @@ def main():
     ap.add_argument("--cpu-rows", type=int, default=1 << 14)
     ap.add_argument("--out", default=None)
     ap.add_argument("--keyed", action="store_true", help="A/B of the registered-key verifier against the generic one")
+    ap.add_argument("--routed", action="store_true", help="A/B of RSA routing (K20) off against on")
+    ap.add_argument("--ab", nargs=3, default=None, metavar=("A.so", "A2.so", "B.so"),
+                    help="the routing-off dense call through three libraries side by side")
     a = ap.parse_args()
     if a.keyed:
         return keyed_main(a)
+    if a.routed:
+        return routed_main(a)
+    if a.ab:
+        return ab_main(a)
 
     import torch
     if not torch.cuda.is_available():
