@@ -58,12 +58,14 @@ EXPORTS = [
     "cordahip_commit_log_stats", "cordahip_commit_log_load", "cordahip_commit_log_lookup",
     "cordahip_commit_inputs", "cordahip_commit_inputs_submit", "cordahip_commit_inputs_device",
     "cordahip_commit_log_revoke", "cordahip_commit_log_export",
+    "cordahip_notary_tearoff_verify", "cordahip_notary_tearoff_submit", "cordahip_notary_tearoff_device",
+    "cordahip_notary_tearoff_commit", "cordahip_notary_tearoff_commit_submit",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
 KRYO_KINDS = {"raw": 0, "char": 1, "short": 2, "int": 3, "long": 4, "byte": 5, "boolean": 6, "float": 7,
               "double": 8, "String": 9, "ed25519_key": 10, "public_key": 11, "kotlin_object": 12, "party": 13,
-              "issue_command": 14, "cash_state": 15}
+              "issue_command": 14, "cash_state": 15, "state_ref": 16, "time_window": 17}
 ABI_VERSION = 4
 FLAG_IS_VALID = 1  # CORDAHIP_FLAG_IS_VALID: Crypto.isValid semantics (no emptiness checks)
 FLAG_RSA_ON_DEVICE = 2  # CORDAHIP_FLAG_RSA_ON_DEVICE: RSA_SHA256 lanes verified on the GPU, not UNSUPPORTED
@@ -277,6 +279,22 @@ class CommitBatch(ctypes.Structure):
     ]
 
 
+class NotaryTearoffBatch(ctypes.Structure):
+    _fields_ = [
+        ("ntx", ctypes.c_uint64),
+        ("refs", ctypes.c_void_p), ("tx_ref_off", ctypes.c_void_p), ("n_refs", ctypes.c_uint64),
+        ("tw_flags", ctypes.c_void_p),
+        ("tw_from_s", ctypes.c_void_p), ("tw_from_nano", ctypes.c_void_p),
+        ("tw_until_s", ctypes.c_void_p), ("tw_until_nano", ctypes.c_void_p),
+        ("tok", ctypes.c_void_p), ("tok_hash", ctypes.c_void_p), ("tx_tok_off", ctypes.c_void_p),
+        ("ntok", ctypes.c_uint64),
+        ("root", ctypes.c_void_p), ("tx_status", ctypes.c_void_p), ("leaf_hash", ctypes.c_void_p),
+    ]
+
+
+TW_PRESENT = 0x80  # cordahip_notary_tearoff_batch.tw_flags bit 7: the transaction has a TimeWindow
+
+
 # numpy images of cordahip_state_ref (36 bytes), cordahip_consuming_tx (40) and cordahip_commit_row (76)
 STATE_REF_DTYPE = np.dtype([("txhash", "u1", 32), ("index", "<u4")])
 CONSUMING_TX_DTYPE = np.dtype([("id", "u1", 32), ("input_index", "<u4"), ("caller", "<u4")])
@@ -445,6 +463,13 @@ def lib() -> ctypes.CDLL:
         "cordahip_commit_inputs_device": (i32, [vp, u32, ctypes.POINTER(CommitBatch), vp]),
         "cordahip_commit_log_revoke": (i32, [vp, u32, vp, u64, vp, ctypes.POINTER(u64)]),
         "cordahip_commit_log_export": (i32, [vp, u32, u64, vp, vp, u64, ctypes.POINTER(u64)]),
+        "cordahip_notary_tearoff_verify": (i32, [vp, ctypes.POINTER(NotaryTearoffBatch)]),
+        "cordahip_notary_tearoff_submit": (i32, [vp, ctypes.POINTER(NotaryTearoffBatch), ctypes.POINTER(u64)]),
+        "cordahip_notary_tearoff_device": (i32, [vp, i32, ctypes.POINTER(NotaryTearoffBatch), vp, vp, vp]),
+        "cordahip_notary_tearoff_commit": (i32, [vp, u32, ctypes.POINTER(NotaryTearoffBatch), vp, ctypes.c_int64,
+                                                 ctypes.c_int64, vp, vp, vp, vp]),
+        "cordahip_notary_tearoff_commit_submit": (i32, [vp, u32, ctypes.POINTER(NotaryTearoffBatch), vp, ctypes.c_int64,
+                                                        ctypes.c_int64, vp, vp, vp, vp, ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(l, name)
@@ -505,6 +530,21 @@ def pack_cash_state(d):
             + (0 if enc is None else int(enc)).to_bytes(4, "little", signed=True))
 
 
+def pack_state_ref(txhash, index):
+    """The CORDAHIP_KRYO_STATE_REF payload: one cordahip_state_ref row (index: a Java int or its u32 image)."""
+    assert len(txhash) == 32
+    return bytes(txhash) + (int(index) & 0xFFFFFFFF).to_bytes(4, "little")
+
+
+def pack_time_window(from_time, until_time):
+    """The CORDAHIP_KRYO_TIME_WINDOW payload; a side is None or (epochSecond, nano)."""
+    fs, fn = from_time if from_time is not None else (0, 0)
+    us, un = until_time if until_time is not None else (0, 0)
+    flags = (from_time is not None) | ((until_time is not None) << 1)
+    return (bytes([flags]) + int(fs).to_bytes(8, "little", signed=True) + int(fn).to_bytes(4, "little", signed=True)
+            + int(us).to_bytes(8, "little", signed=True) + int(un).to_bytes(4, "little", signed=True))
+
+
 def kryo_pack(items):
     """(kind, value, class_id) tuples -> (payload blob uint8, KRYO_ITEM_DTYPE[n] whose `data` are
     OFFSETS into the blob, bool[n]: the item has a payload). kind: a KRYO_KINDS key; value: bytes
@@ -521,7 +561,7 @@ def kryo_pack(items):
         if kind in ("String", "kotlin_object"):
             b = value.encode("utf-16-le")
             arr[i]["len"] = len(b) // 2
-        elif kind in ("raw", "ed25519_key", "public_key"):
+        elif kind in ("raw", "ed25519_key", "public_key", "state_ref", "time_window"):  # the payload as bytes
             b = bytes(value)
             arr[i]["len"] = len(b)
         elif kind == "party":  # value = (X.500 name DER, key bytes, key class id); class_id = X500Name's id

@@ -10,6 +10,7 @@
 
 #include "api_support.hpp"
 #include "csr_check.hpp"
+#include "notary_stage.hpp"
 
 using namespace cordahip;
 using namespace cordahip::rt;
@@ -38,9 +39,10 @@ bool commit_log_full(const CommitLog& L, uint64_t more) {
 
 // the log's host stage of at least `bytes` on both sides (mu held; the previous host
 // call has drained, so growing frees nothing in use)
-int commit_stage(CommitLog& L, size_t bytes) {
+int commit_stage(CommitLog& L, size_t bytes, size_t dev_bytes = 0) {  // dev_bytes: a longer device side
   bytes = std::max<size_t>(bytes, 64);
-  if (L.stage_h.ensure(bytes) != hipSuccess || L.stage_d.ensure(bytes) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  if (L.stage_h.ensure(bytes) != hipSuccess || L.stage_d.ensure(std::max(bytes, dev_bytes)) != hipSuccess)
+    return CORDAHIP_ERR_OUT_OF_MEMORY;
   return CORDAHIP_SUCCESS;
 }
 
@@ -398,17 +400,17 @@ int commit_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch*
 // The ticketed form: the call takes the log's next turn at submit, and the queued
 // jobs of one log run in turn order whichever worker picks them up (the pool's queue
 // is first in, first out, so the job whose turn it is has always been picked up).
-int commit_submit_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* b, uint64_t* ticket) {
-  const auto L = log_at(ctx, log_id);
+template <class F>
+int submit_in_turn(cordahip_ctx* ctx, const std::shared_ptr<CommitLog>& L, uint64_t* ticket, F run) {
   if (!L) return CORDAHIP_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> g(L->turn_mu);
   const uint64_t turn = L->turn_next;
-  *ticket = submit_job(ctx, [ctx, L, turn, copy = *b] {
+  *ticket = submit_job(ctx, [L, turn, run] {
     {
       std::unique_lock<std::mutex> w(L->turn_mu);
       L->turn_cv.wait(w, [&] { return L->turn_now == turn; });
     }
-    const int rc = guarded([&] { return commit_on(ctx, *L, &copy); });
+    const int rc = guarded([&] { return run(*L); });
     {
       std::lock_guard<std::mutex> w(L->turn_mu);
       L->turn_now++;
@@ -417,6 +419,96 @@ int commit_submit_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit
     return rc;
   });
   L->turn_next++;  // only once the job is queued: a failed submit leaves no gap in the turns
+  return CORDAHIP_SUCCESS;
+}
+int commit_submit_impl(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* b, uint64_t* ticket) {
+  return submit_in_turn(ctx, log_at(ctx, log_id), ticket,
+                        [ctx, copy = *b](CommitLog& L) { return commit_on(ctx, L, &copy); });
+}
+
+// ---- typed notary tear-offs: K21 + K6, then K16 over the same device rows -----------
+// What cordahip_notary_tearoff_commit takes beside the batch (by value in a ticket's job).
+struct NotaryCommitArgs {
+  const uint32_t* caller;
+  int64_t now_ns, tolerance_ns;
+  const uint8_t* gate;
+  uint8_t* committed;
+  uint8_t* ref_state;
+  cordahip_consuming_tx* ref_by;
+};
+
+int notary_commit_on(cordahip_ctx* ctx, CommitLog& L, const cordahip_notary_tearoff_batch* b,
+                     const NotaryCommitArgs& a) {
+  cordahip_commit_batch scal{};
+  scal.now_ns = a.now_ns, scal.tolerance_ns = a.tolerance_ns;
+  if (!commit_scalars_ok(&scal) || !check_notary_tearoff(PoolPar{*ctx->host}, b))
+    return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
+  const uint64_t ntx = b->ntx;
+  if (ntx == 0) return CORDAHIP_SUCCESS;
+  if (!notary_pointers_ok(b) || !a.caller || !a.committed) return CORDAHIP_ERR_INVALID_ARG;
+  NotaryStage st(b, 0, ntx);
+  const uint64_t nr = st.nr;
+  if (nr && (!a.ref_state || !a.ref_by)) return CORDAHIP_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> g(L.mu);
+  if (commit_log_full(L, b->n_refs)) return CORDAHIP_ERR_LOG_FULL;
+  Device& d = *L.dev;
+  const Activity act(d);
+  if (hipSetDevice(d.id) != hipSuccess) return CORDAHIP_ERR_HIP;
+  // K16's arrays behind the tear-offs': two more inputs, its gate and statuses, its outputs
+  const size_t o_caller = st.take(ntx * 4), o_cgate = st.take(a.gate ? ntx : 0), in2_end = st.pos,
+               o_gate = st.take(ntx), o_cst = st.take(ntx), o_status = st.take(ntx), o_comm = st.take(ntx),
+               o_state = st.take(nr), o_by = st.take(nr * kCommitByBytes), out2_end = st.pos;
+  st.scratch();
+  if (const int rc = commit_stage(L, st.host_bytes, st.pos)) return rc;
+  if (commit_scratch(L, ntx, nr) != hipSuccess) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  uint8_t *h = L.stage_h.as<uint8_t>(), *dv = L.stage_d.as<uint8_t>();
+  st.fill(b, h);
+  std::memcpy(h + o_caller, a.caller, ntx * 4);
+  if (a.gate) std::memcpy(h + o_cgate, a.gate, ntx);
+  commit::Batch B{};
+  B.ntx = ntx;
+  B.txid = reinterpret_cast<const uint32_t*>(dv + st.o_root);  // FilteredTransaction.rootHash is the id
+  B.caller = reinterpret_cast<const uint32_t*>(dv + o_caller);
+  B.refs = reinterpret_cast<const uint32_t*>(dv + st.o_refs);  // the rows K21 hashed
+  B.off = reinterpret_cast<const uint64_t*>(dv + st.o_off);
+  B.tw_from = reinterpret_cast<const int64_t*>(dv + st.o_twf);
+  B.tw_until = reinterpret_cast<const int64_t*>(dv + st.o_twu);
+  B.now_ns = a.now_ns;
+  B.tolerance_ns = a.tolerance_ns;
+  B.gate = dv + o_gate;
+  B.tx_status = dv + o_cst;
+  B.committed = dv + o_comm;
+  B.ref_state = dv + o_state;
+  B.ref_by = reinterpret_cast<uint32_t*>(dv + o_by);
+  hipStream_t s = d.stream;
+  const double t0 = now_ms();
+  hipError_t e = hipMemcpyAsync(dv, h, st.in_bytes, hipMemcpyHostToDevice, s);
+  e = e ? e : hipMemcpyAsync(dv + o_caller, h + o_caller, in2_end - o_caller, hipMemcpyHostToDevice, s);
+  e = e ? e : st.enqueue_verify(dv, b->leaf_hash != nullptr, s);
+  e = e ? e : launch_notary_gate(dv + st.o_vst, a.gate ? dv + o_cgate : nullptr, dv + o_gate, ntx, s);
+  if (e == hipSuccess) {
+    e = commit_enqueue(L, B, nr, s);
+    L.bound += b->n_refs - nr;  // the bound counts the call's n_refs, as cordahip_commit_inputs's
+  }
+  e = e ? e : launch_notary_status(dv + st.o_vst, dv + o_cst, dv + o_status, ntx, s);
+  if (b->leaf_hash) e = e ? e : hipMemcpyAsync(h + st.o_lh, dv + st.o_lh, st.out_end - st.o_lh, hipMemcpyDeviceToHost, s);
+  e = e ? e : hipMemcpyAsync(h + o_status, dv + o_status, out2_end - o_status, hipMemcpyDeviceToHost, s);
+  e = e ? e : L.stage_ev.record(s);
+  e = e ? e : L.stage_ev.sync();
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);  // no queued work outlives the call
+    return CORDAHIP_ERR_HIP;
+  }
+  std::memcpy(b->tx_status, h + o_status, ntx);
+  std::memcpy(a.committed, h + o_comm, ntx);
+  if (nr) {
+    std::memcpy(a.ref_state + st.r0, h + o_state, nr);
+    std::memcpy(a.ref_by + st.r0, h + o_by, nr * kCommitByBytes);
+  }
+  if (b->leaf_hash) std::memcpy(b->leaf_hash, h + st.o_lh, NotaryStage::leaves_before(b, ntx) * 32);
+  if (tracing())
+    fprintf(stderr, "[cordahip] dev %d notary tear-offs on log %u: %llu txs, %llu refs in %.2f ms\n", d.id, L.id,
+            (unsigned long long)ntx, (unsigned long long)nr, now_ms() - t0);
   return CORDAHIP_SUCCESS;
 }
 
@@ -519,6 +611,29 @@ int cordahip_commit_inputs_device(cordahip_ctx* ctx, uint32_t log_id, const cord
                                   void* hip_stream) {
   if (!ctx || !d_batch) return CORDAHIP_ERR_INVALID_ARG;
   return guarded([&] { return commit_device_impl(ctx, log_id, d_batch, hip_stream); });
+}
+
+int cordahip_notary_tearoff_commit(cordahip_ctx* ctx, uint32_t log_id, const cordahip_notary_tearoff_batch* batch,
+                                   const uint32_t* caller, int64_t now_ns, int64_t tolerance_ns, const uint8_t* gate,
+                                   uint8_t* committed, uint8_t* ref_state, cordahip_consuming_tx* ref_by) {
+  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
+  const NotaryCommitArgs a{caller, now_ns, tolerance_ns, gate, committed, ref_state, ref_by};
+  return guarded([&] {
+    const auto L = log_at(ctx, log_id);
+    return L ? notary_commit_on(ctx, *L, batch, a) : (int)CORDAHIP_ERR_INVALID_ARG;
+  });
+}
+
+int cordahip_notary_tearoff_commit_submit(cordahip_ctx* ctx, uint32_t log_id,
+                                          const cordahip_notary_tearoff_batch* batch, const uint32_t* caller,
+                                          int64_t now_ns, int64_t tolerance_ns, const uint8_t* gate, uint8_t* committed,
+                                          uint8_t* ref_state, cordahip_consuming_tx* ref_by, uint64_t* ticket) {
+  if (!ctx || !batch || !ticket) return CORDAHIP_ERR_INVALID_ARG;
+  const NotaryCommitArgs a{caller, now_ns, tolerance_ns, gate, committed, ref_state, ref_by};
+  return guarded([&] {
+    return submit_in_turn(ctx, log_at(ctx, log_id), ticket,
+                          [ctx, copy = *batch, a](CommitLog& L) { return notary_commit_on(ctx, L, &copy, a); });
+  });
 }
 
 }  // extern "C"

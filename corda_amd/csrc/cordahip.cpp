@@ -26,6 +26,7 @@
 #include "api_support.hpp"
 #include "cover_core.hpp"
 #include "csr_check.hpp"
+#include "notary_stage.hpp"
 #include "kryo_core.hpp"
 #include "runtime.hpp"
 #include "status.hpp"
@@ -1161,6 +1162,97 @@ int filtered_tx_impl(cordahip_ctx* ctx, const cordahip_filtered_tx_batch* b) {
   return for_shards(ctx->devs, n, 1, [&](Device& d, uint64_t t0, uint64_t t1) { return filtered_tx_shard(d, b, t0, t1); });
 }
 
+// Typed notary tear-offs [t0, t1) on one device: K21 hashes the StateRef / TimeWindow
+// leaves from their rows, K6 evaluates each partial tree over them (notary_stage.hpp).
+int notary_tearoff_shard(Device& d, const cordahip_notary_tearoff_batch* b, uint64_t t0, uint64_t t1) {
+  SetLease lease(d);
+  TxSet& S = lease.get();
+  const NodeBind nb(d);
+  const Activity act(d);
+  if (int rc = tx_acquire_host(d, S)) return rc;
+  NotaryStage st(b, t0, t1);
+  st.scratch();
+  TxWork& w = S.tx;
+  if (w.leaf_bytes.ensure(st.pos)) return CORDAHIP_ERR_OUT_OF_MEMORY;
+  std::vector<uint8_t> h(st.out_end);
+  st.fill(b, h.data());
+  uint8_t* dv = w.leaf_bytes.as<uint8_t>();
+  hipStream_t s = d.stream;
+  hipError_t e = hipMemcpyAsync(dv, h.data(), st.in_bytes, hipMemcpyHostToDevice, s);
+  e = e ? e : st.enqueue_verify(dv, b->leaf_hash != nullptr, s);
+  e = e ? e : hipMemcpyAsync(h.data() + st.o_vst, dv + st.o_vst, (b->leaf_hash ? st.out_end : st.o_lh) - st.o_vst,
+                             hipMemcpyDeviceToHost, s);
+  e = e ? e : S.tx_ev.record(s);
+  e = e ? e : S.tx_ev.sync();
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);
+    return hip_err(e);
+  }
+  std::memcpy(b->tx_status + t0, h.data() + st.o_vst, st.ntx);
+  if (b->leaf_hash) {
+    const uint64_t l0 = NotaryStage::leaves_before(b, t0), l1 = NotaryStage::leaves_before(b, t1);
+    std::memcpy(b->leaf_hash + l0 * 32, h.data() + st.o_lh, (l1 - l0) * 32);
+  }
+  return CORDAHIP_SUCCESS;
+}
+
+int notary_tearoff_impl(cordahip_ctx* ctx, const cordahip_notary_tearoff_batch* b) {
+  if (!check_notary_tearoff(PoolPar{*ctx->host}, b)) return CORDAHIP_ERR_INVALID_ARG;  // before any enqueue
+  const uint64_t n = b->ntx;
+  if (n == 0) return CORDAHIP_SUCCESS;
+  if (!notary_pointers_ok(b)) return CORDAHIP_ERR_INVALID_ARG;
+  return for_shards(ctx->devs, n, 1,
+                    [&](Device& d, uint64_t t0, uint64_t t1) { return notary_tearoff_shard(d, b, t0, t1); });
+}
+
+int notary_tearoff_device_impl(cordahip_ctx* ctx, int device, const cordahip_notary_tearoff_batch* b, void* d_tw_from,
+                               void* d_tw_until, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d) return CORDAHIP_ERR_INVALID_ARG;
+  const int given = (b->tw_flags != nullptr) + (b->tw_from_s != nullptr) + (b->tw_from_nano != nullptr) +
+                    (b->tw_until_s != nullptr) + (b->tw_until_nano != nullptr);
+  if (given != 0 && given != 5) return CORDAHIP_ERR_INVALID_ARG;
+  const uint64_t ntx = b->ntx;
+  if (ntx == 0) return CORDAHIP_SUCCESS;
+  if (!b->tx_ref_off || !b->tx_tok_off || !b->root || !b->tx_status || !d_tw_from || !d_tw_until ||
+      (b->n_refs && !b->refs) || (b->ntok && (!b->tok || !b->tok_hash)) || b->n_refs > (1ull << 56) ||
+      ntx > (1ull << 56) || b->ntok > (1ull << 56))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if (misaligned(b->refs, 4) || misaligned(b->tx_ref_off, 8) || misaligned(b->tx_tok_off, 8) ||
+      misaligned(b->tw_from_s, 8) || misaligned(b->tw_until_s, 8) || misaligned(b->tw_from_nano, 4) ||
+      misaligned(b->tw_until_nano, 4) || misaligned(b->leaf_hash, 4) || misaligned(d_tw_from, 8) ||
+      misaligned(d_tw_until, 8))
+    return CORDAHIP_ERR_INVALID_ARG;
+  SetLease lease(*d);
+  TxSet& S = lease.get();
+  TxWork& w = S.tx;
+  const uint64_t nl = b->n_refs + ntx, nk = std::max<uint64_t>(b->ntok, 1);
+  const NotaryRows R{ntx,          b->n_refs,    b->refs,       b->tx_ref_off,   b->tw_flags,
+                     b->tw_from_s, b->tw_from_nano, b->tw_until_s, b->tw_until_nano};
+  return device_call(
+      *d, hip_stream,
+      [&] {
+        return S.tx_ev.grow(w.hashes.cap < nl * 32 || w.tx_leaf_off.cap < (ntx + 1) * 8 || w.stack.cap < nk * 32 ||
+                                w.pmt_has.cap < ntx,
+                            [&] {
+                              return w.hashes.ensure(nl * 32) || w.tx_leaf_off.ensure((ntx + 1) * 8) ||
+                                             w.stack.ensure(nk * 32) || w.pmt_has.ensure(ntx)
+                                         ? hipErrorOutOfMemory
+                                         : hipSuccess;
+                            });
+      },
+      [&](hipStream_t s) {
+        hipError_t e = S.tx_ev.wait(s);  // the set's previous user is done
+        e = e ? e : launch_notary_leaves(R, w.tx_leaf_off.as<uint64_t>(), w.hashes.as<uint32_t>(), b->leaf_hash,
+                                         static_cast<int64_t*>(d_tw_from), static_cast<int64_t*>(d_tw_until),
+                                         w.pmt_has.as<uint8_t>(), s);
+        e = e ? e : launch_pmt_verify(w.hashes.as<uint32_t>(), w.tx_leaf_off.as<uint64_t>(), b->tok, b->tok_hash,
+                                      b->tx_tok_off, b->root, ntx, w.stack.as<uint32_t>(), b->tx_status, s,
+                                      w.pmt_has.as<uint8_t>());
+        return e ? e : S.tx_ev.record(s);
+      });
+}
+
 // FilteredTransaction build for txs [t0, t1) on one device: K3 hashes the
 // leaves, K10 builds each tree and writes its tokens into the caller's slot.
 // The shard's slots are the contiguous token range [tx_tok_off[t0], tx_tok_off[t1]),
@@ -1516,6 +1608,21 @@ int cordahip_ed25519_verify_host(cordahip_ctx* ctx, const uint8_t* keys, const u
 int cordahip_filtered_tx_verify(cordahip_ctx* ctx, const cordahip_filtered_tx_batch* batch) {
   if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
   return guarded([&] { return filtered_tx_impl(ctx, batch); });
+}
+
+int cordahip_notary_tearoff_verify(cordahip_ctx* ctx, const cordahip_notary_tearoff_batch* batch) {
+  if (!ctx || !batch) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return notary_tearoff_impl(ctx, batch); });
+}
+
+int cordahip_notary_tearoff_submit(cordahip_ctx* ctx, const cordahip_notary_tearoff_batch* batch, uint64_t* ticket) {
+  return submit(ctx, ticket, notary_tearoff_impl, batch);
+}
+
+int cordahip_notary_tearoff_device(cordahip_ctx* ctx, int device, const cordahip_notary_tearoff_batch* d_batch,
+                                   void* d_tw_from, void* d_tw_until, void* hip_stream) {
+  if (!ctx || !d_batch) return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&] { return notary_tearoff_device_impl(ctx, device, d_batch, d_tw_from, d_tw_until, hip_stream); });
 }
 
 int cordahip_filtered_tx_build(cordahip_ctx* ctx, const cordahip_filtered_build_batch* batch) {

@@ -156,6 +156,19 @@ bool check_commit(Par&& par, const cordahip_commit_batch* b) {
   return b->tx_ref_off && csr_ok(par, b->tx_ref_off, 0, b->ntx, b->n_refs);
 }
 
+// a typed notary tear-off batch: the window arrays all given or all null,
+// tx_ref_off[0..ntx] non-decreasing and within n_refs, tx_tok_off[0..ntx]
+// non-decreasing and within ntok (both whole, whatever a shard will read)
+template <class Par>
+bool check_notary_tearoff(Par&& par, const cordahip_notary_tearoff_batch* b) {
+  const int given = (b->tw_flags != nullptr) + (b->tw_from_s != nullptr) + (b->tw_from_nano != nullptr) +
+                    (b->tw_until_s != nullptr) + (b->tw_until_nano != nullptr);
+  if (given != 0 && given != 5) return false;
+  if (b->ntx == 0) return true;
+  if (!b->tx_ref_off || !b->tx_tok_off) return false;
+  return csr_ok(par, b->tx_ref_off, 0, b->ntx, b->n_refs) && csr_ok(par, b->tx_tok_off, 0, b->ntx, b->ntok);
+}
+
 // a cover (required-signer coverage): tx_req_off[0..ntx] non-decreasing and
 // within nreq, req_tok_off over the required keys it spans within ntok, the
 // whole key table's ckey_off[0..nckey] within ckey_bytes (any leaf may name any

@@ -108,6 +108,15 @@ KRYO_HD inline bool operator<(const Sv& a, const Sv& b) {  // std::string order 
 constexpr uint32_t kSymConst = 0u << 30, kSymPayload = 1u << 30, kSymValZz = 2u << 30, kSymValBe = 3u << 30;
 constexpr uint32_t kSymTypeMask = 3u << 30;
 constexpr uint32_t kSymOr80 = 1u << 29;
+// A kSymValZz symbol whose varint comes from the item's payload, not its value
+// (STATE_REF's index, TIME_WINDOW's seconds and nanos): bits 12..17 the payload
+// offset of a little-endian integer, kSymVarWide 8 bytes of it (else 4),
+// kSymVarPlain written as it stands (writeVarLong(v, true); else zig-zag of the
+// sign-extended 4 bytes)
+constexpr uint32_t kSymVarData = 1u << 28, kSymVarWide = 1u << 18, kSymVarPlain = 1u << 19;
+KRYO_HD constexpr uint32_t sym_var(uint32_t off, bool wide, bool plain) {
+  return kSymValZz | kSymVarData | (off << 12) | (wide ? kSymVarWide : 0u) | (plain ? kSymVarPlain : 0u);
+}
 constexpr uint32_t kMaxPayloadOff = 1u << 21;  // payload offsets a symbol can name (bits 8..28)
 
 // Level-0 byte sink (KoutT's Sink): NoSink for the leaf in memory (or counting);
@@ -122,8 +131,13 @@ struct NoSink {
   KRYO_HD void mark() {}
 };
 
-template <bool Trace, class Sink = NoSink>
+// Stride / Levels: the caller's level buffers hold Levels - 1 levels of Stride bytes
+// each (the framing still cuts chunks at kChunk). A kernel that encodes only kinds
+// whose fields stay short keeps them small (K21: LDS); a write past either fails the
+// leaf instead of leaving the buffer.
+template <bool Trace, class Sink = NoSink, uint32_t Stride = kChunk, uint32_t Levels = kMaxDepth>
 struct KoutT {
+  static_assert(Stride <= kChunk && Levels <= kMaxDepth, "level buffers no larger than Kryo's");
   using Sym = typename std::conditional<Trace, uint32_t, uint8_t>::type;
   Sink* sink = nullptr;  // level 0 into this sink instead of `out` (out must be nullptr, buf set)
   Sym* out;          // level 0 (the leaf); nullptr: counting
@@ -139,7 +153,16 @@ struct KoutT {
   uint64_t src_len = 0;
   uint32_t vtag = 0;
   KRYO_HD KoutT(Sym* o, uint64_t c, Sym* levels) : out(o), cap(c), buf(levels) { len[0] = 0; }
-  KRYO_HD Sym& at(uint32_t k, uint32_t i) { return buf[(size_t)(k - 1) * kChunk + i]; }  // k >= 1
+  KRYO_HD Sym& at(uint32_t k, uint32_t i) { return buf[(size_t)(k - 1) * Stride + i]; }  // k >= 1
+  KRYO_HD bool room(uint32_t k, uint32_t n) {  // level k's buffer takes n more (always, at full size)
+    if constexpr (Stride < kChunk) {
+      if (len[k] + n > Stride) {
+        failed = true;
+        return false;
+      }
+    }
+    return true;
+  }
   KRYO_HD void set_vtag(uint32_t t) {
     if constexpr (Trace) vtag = t;
     else (void)t;
@@ -164,7 +187,7 @@ struct KoutT {
       if ((x & kSymTypeMask) == kSymPayload) x |= kSymOr80;
   }
   KRYO_HD uint32_t push_level() {
-    if (depth + 1 >= kMaxDepth) {
+    if (depth + 1 >= Levels) {
       failed = true;
       return depth;  // keeps writing into the deepest level; the leaf is rejected
     }
@@ -183,7 +206,7 @@ struct KoutT {
     if (k == 0) {
       put0(b);
     } else {
-      if (buf) at(k, len[k]) = b;
+      if (buf && room(k, 1)) at(k, len[k]) = b;
       len[k]++;
     }
   }
@@ -191,7 +214,7 @@ struct KoutT {
     if (k == 0) {
       if constexpr (Sink::kActive) sink->mark();
       else if (out && pos - 1 < cap) mark(out[pos - 1]);
-    } else if (buf) {
+    } else if (buf && room(k, 0)) {
       mark(at(k, len[k] - 1));
     }
   }
@@ -213,7 +236,7 @@ struct KoutT {
       }
       pos += n;
     } else {
-      if (buf) {
+      if (buf && room(k, n)) {
         if constexpr (!Trace) {
           __builtin_memcpy(&at(k, len[k]), p, n);
         } else {
@@ -290,7 +313,9 @@ struct KoutT {
     prim(k, t, m);
   }
   KRYO_HD void varlong_zigzag(uint32_t k, int64_t x) {  // Output.writeVarLong(v, false)
-    uint64_t v = ((uint64_t)x << 1) ^ (uint64_t)(x >> 63);
+    varlong(k, ((uint64_t)x << 1) ^ (uint64_t)(x >> 63));
+  }
+  KRYO_HD void varlong(uint32_t k, uint64_t v) {  // Output.writeVarLong(v, true): the 9th byte takes 8 bits
     uint8_t t[9];
     uint32_t m = 0;
     for (int i = 0; i < 8 && (v >> 7); i++) {
@@ -313,6 +338,12 @@ struct KoutT {
       if (len[k] == 0) continue;
       const uint32_t n = len[k];
       len[k] = 0;
+      if constexpr (Stride < kChunk) {
+        if (n > Stride) {  // the level was cut short (room): nothing of it to copy out
+          failed = true;
+          continue;
+        }
+      }
       uint32_t sz = n;
       while (sz >> 7) {  // writeChunkSize: one stream.write(int) per byte
         require<D + 1>(k - 1, 1);
@@ -335,7 +366,7 @@ struct KoutT {
     }
     uint32_t c = kmin(kChunk - len[k], n);
     for (;;) {
-      if (buf) __builtin_memcpy(&at(k, len[k]), &at(from, s), (size_t)c * sizeof(Sym));
+      if (buf && room(k, c)) __builtin_memcpy(&at(k, len[k]), &at(from, s), (size_t)c * sizeof(Sym));
       len[k] += c;
       s += c;
       n -= c;
@@ -761,6 +792,93 @@ KRYO_HD inline bool issue_command(O& o, const cordahip_kryo_item& it) {
   return true;
 }
 
+// ---- the components a non-validating notary sees (NotaryFlow.kt:62) ------------------
+// PARITY UNPINNED, like the kinds above: the bytes follow Kryo 4.0.0's published
+// format as restated here, unconfirmed by any reference output.
+//
+// net.corda.core.contracts.StateRef(txhash: SecureHash, index: Int) (Structures.kt:247):
+// implicit NAME registration, CompatibleFieldSerializer over StateRef.index (a
+// primitive int: writeInt(v, false), the zig-zag varint, as Amount.quantity's long
+// above) and StateRef.txhash (declared SecureHash, not final: the class
+// SecureHash$SHA256 by name, then opaque_bytes' body). data = one cordahip_state_ref
+// row: 32 bytes txhash, u32 LE index read as a Java int.
+KRYO_HD inline uint32_t le32(const uint8_t* p) {
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+KRYO_HD inline uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
+KRYO_HD inline uint32_t zigzag32(uint32_t x) { return (x << 1) ^ (uint32_t)((int32_t)x >> 31); }
+constexpr uint32_t kStateRefLen = 36, kStateRefIndexOff = 32;
+
+template <class O>
+KRYO_HD inline bool state_ref(O& o, const cordahip_kryo_item& it) {
+  if (!it.data || it.len != kStateRefLen) return false;
+  const uint8_t* d = it.data;
+  Graph g;
+  g.class_name(o, 0, "net.corda.core.contracts.StateRef");
+  g.cfs(o, 0, "net.corda.core.contracts.StateRef", {"StateRef.index", "StateRef.txhash"},
+        [&](uint32_t k) {  // the varint of payload bytes 32..35: VAR symbols when tracing
+          o.set_vtag(sym_var(kStateRefIndexOff, false, false));
+          o.varlong(k, zigzag32(le32(d + kStateRefIndexOff)));
+          o.set_vtag(0);
+        },
+        [&](uint32_t k) { opaque_bytes(o, g, k, "net.corda.core.crypto.SecureHash$SHA256", d, 32); });
+  return true;
+}
+
+// net.corda.core.contracts.TimeWindow(fromTime: Instant?, untilTime: Instant?)
+// (Structures.kt:336-341): implicit NAME registration, CompatibleFieldSerializer over
+// TimeWindow.fromTime and TimeWindow.untilTime. java.time.Instant is final: no class,
+// NULL (00) or NOT_NULL (01) + the body. The body is taken to be Kryo 4.0.0's
+// TimeSerializers.InstantSerializer -- writeLong(getEpochSecond(), true),
+// writeInt(getNano(), true): plain varints, a negative second in 9 bytes -- which
+// Kryo 4.0.0 adds to its default serializers when java.time is present; that is
+// recalled from Kryo's published source and not checked against it (none is at hand).
+// data (25 bytes): u8 flags (bit 0 fromTime, bit 1 untilTime), i64 LE from-second,
+// i32 LE from-nano, i64 LE until-second, i32 LE until-nano.
+constexpr uint32_t kTimeWindowLen = 25, kTwFromS = 1, kTwFromN = 9, kTwUntilS = 13, kTwUntilN = 21;
+constexpr int64_t kInstantMinSecond = -31557014167219200ll, kInstantMaxSecond = 31556889864403199ll;
+struct TimeWindowRow {
+  uint32_t flags = 0;
+  int64_t s[2] = {0, 0};  // from, until
+  int32_t n[2] = {0, 0};
+  bool ok = false;
+};
+KRYO_HD inline TimeWindowRow time_window_row(const cordahip_kryo_item& it) {
+  TimeWindowRow r;
+  if (!it.data || it.len != kTimeWindowLen) return r;
+  const uint8_t* d = it.data;
+  r.flags = d[0];
+  r.s[0] = (int64_t)le64(d + kTwFromS), r.n[0] = (int32_t)le32(d + kTwFromN);
+  r.s[1] = (int64_t)le64(d + kTwUntilS), r.n[1] = (int32_t)le32(d + kTwUntilN);
+  r.ok = !(r.flags & ~3u);
+  for (int i = 0; i < 2; i++)
+    if (r.flags & (1u << i))
+      r.ok = r.ok && r.n[i] >= 0 && r.n[i] <= 999999999 && r.s[i] >= kInstantMinSecond && r.s[i] <= kInstantMaxSecond;
+  return r;
+}
+template <class O>
+KRYO_HD inline bool time_window(O& o, const cordahip_kryo_item& it) {
+  const TimeWindowRow r = time_window_row(it);
+  if (!r.ok) return false;
+  auto side = [&](uint32_t k, int i) {
+    if (!(r.flags & (1u << i))) {
+      o.byte(k, 0);  // NULL
+      return;
+    }
+    o.byte(k, 1);  // NOT_NULL
+    o.set_vtag(sym_var(i ? kTwUntilS : kTwFromS, true, true));
+    o.varlong(k, (uint64_t)r.s[i]);
+    o.set_vtag(sym_var(i ? kTwUntilN : kTwFromN, false, true));
+    o.varlong(k, (uint32_t)r.n[i]);
+    o.set_vtag(0);
+  };
+  Graph g;
+  g.class_name(o, 0, "net.corda.core.contracts.TimeWindow");
+  g.cfs(o, 0, "net.corda.core.contracts.TimeWindow", {"TimeWindow.fromTime", "TimeWindow.untilTime"},
+        [&](uint32_t k) { side(k, 0); }, [&](uint32_t k) { side(k, 1); });
+  return true;
+}
+
 // One component's leaf preimage through o (RAW: the bytes as given); false for
 // an unknown kind or a missing / malformed payload.
 template <class O>
@@ -826,6 +944,8 @@ KRYO_HD inline bool encode_leaf(O& o, const cordahip_kryo_item& it) {
     }
     case CORDAHIP_KRYO_ISSUE_COMMAND: ok = issue_command(o, it); break;
     case CORDAHIP_KRYO_CASH_STATE: ok = it.data && cash_state(o, it); break;
+    case CORDAHIP_KRYO_STATE_REF: ok = state_ref(o, it); break;
+    case CORDAHIP_KRYO_TIME_WINDOW: ok = time_window(o, it); break;
     default: return false;
   }
   return ok && !o.failed;

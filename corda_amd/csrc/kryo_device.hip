@@ -47,6 +47,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "kryo_template.hpp"
+#include "notary_rows.hpp"
 #include "sha2_device.hpp"
 
 namespace cordahip {
@@ -942,7 +943,7 @@ __device__ inline void leaf_piece(const HashSrc& h, uint32_t p, uint64_t desc, u
     for (uint32_t t = 0; t < 16; t++) {
       const uint32_t x = sy[t], ty = x & kryo::kSymTypeMask;
       uint32_t b = ty == kryo::kSymPayload ? (pb[t] | ((x & kryo::kSymOr80) ? 0x80u : 0u))
-                   : ty == kryo::kSymConst ? (x & 0xffu) : (uint32_t)kryo::sym_byte(x, nullptr, h.value);
+                   : ty == kryo::kSymConst ? (x & 0xffu) : (uint32_t)kryo::sym_byte(x, h.data, h.value);
       v[t >> 2] |= (t <= last ? b : 0u) << (8 * (t & 3));
     }
     return;
@@ -998,7 +999,7 @@ __device__ inline void leaf_piece_uniform(TmplPtr T, uint32_t len, const uint8_t
   for (uint32_t t = 0; t < 16; t++) {
     const uint32_t x = sy[t], ty = x & kryo::kSymTypeMask;
     uint32_t b = ty == kryo::kSymPayload ? (pb[t] | ((x & kryo::kSymOr80) ? 0x80u : 0u))
-                 : ty == kryo::kSymConst ? (x & 0xffu) : (uint32_t)kryo::sym_byte(x, nullptr, value);
+                 : ty == kryo::kSymConst ? (x & 0xffu) : (uint32_t)kryo::sym_byte(x, data, value);
     v[t >> 2] |= (t <= last ? b : 0u) << (8 * (t & 3));
   }
 }
@@ -1204,7 +1205,193 @@ kryo_hash_kernel(ItemSrc items, uint64_t n, uint32_t group,
   o[1] = make_uint4(st[4], st[5], st[6], st[7]);
 }
 
+// ---- K21: a notary tear-off's leaf hashes from typed rows ------------------------------
+// What a non-validating notary is shown of a transaction is its StateRef inputs and
+// its TimeWindow (NotaryFlow.kt:62), in availableComponents order
+// (MerkleTransaction.kt:51-62): the refs in list order, then the window. The caller
+// hands over the refs as the 36-byte rows K16 commits and the window as two Instants;
+// one lane per revealed leaf forms the STATE_REF / TIME_WINDOW item in registers and
+// runs the encoder core (encode_leaf) into a SHA-256 sink, as kryo_dhash does for the
+// direct items -- no item array, no leaf bytes and no level workspace in HBM: both kinds
+// nest two OutputChunked levels whose chunks stay under 96 bytes (a StateRef's txhash
+// field: 93), so the level buffers are 192 bytes of LDS per lane (KoutT's Stride /
+// Levels; a leaf that would pass them fails instead of writing outside). The hashes
+// land where K6 (pmt_verify_kernel) reads its leaf_hashes, under the tx_leaf_off that
+// notary_prep_kernel derives, so the refs K16 commits afterwards are the rows whose
+// hashes the partial tree proved.
+constexpr uint32_t kNotaryStride = 96, kNotaryLevels = 3;
+constexpr uint32_t kNotaryLaneBytes = 196;  // 2 x 96, and an odd number of dwords per lane (LDS banks)
+constexpr int64_t kAbsent = INT64_MIN;
+
+// a transaction's rows: its refs [r0, r1) cut to n_refs (the device form's offsets are
+// untrusted), and whether it has a window
+struct NotaryTx {
+  uint64_t r0, nref;
+  bool win;
+};
+__device__ inline NotaryTx notary_tx(const NotaryRows& R, uint64_t t) {
+  const uint64_t a = R.tx_ref_off[t], b = R.tx_ref_off[t + 1];
+  NotaryTx x;
+  x.r0 = a < R.n_refs ? a : R.n_refs;
+  const uint64_t r1 = b < R.n_refs ? b : R.n_refs;
+  x.nref = r1 > x.r0 ? r1 - x.r0 : 0;
+  x.win = R.tw_flags && (R.tw_flags[t] & 0x80);
+  return x;
+}
+
+// tx_leaf_off[t] = (refs before t, cut to n_refs) + (windows before t): one block, each
+// thread a run of consecutive transactions, the 1024 run totals scanned by one thread.
+// Also the defaults of the per-transaction outputs K21's window lanes overwrite.
+__global__ void __launch_bounds__(1024) notary_prep_kernel(NotaryRows R, uint64_t* __restrict__ tx_leaf_off,
+                                                           int64_t* __restrict__ tw_from, int64_t* __restrict__ tw_until,
+                                                           uint8_t* __restrict__ bad) {
+  __shared__ uint64_t s_r[1024], s_w[1024];
+  const uint64_t per = (R.ntx + 1023) / 1024;
+  const uint64_t t0 = threadIdx.x * per < R.ntx ? threadIdx.x * per : R.ntx, t1 = t0 + per < R.ntx ? t0 + per : R.ntx;
+  uint64_t r = 0, w = 0;
+  for (uint64_t t = t0; t < t1; t++) {
+    const NotaryTx x = notary_tx(R, t);
+    r += x.nref;
+    w += x.win;
+  }
+  s_r[threadIdx.x] = r;
+  s_w[threadIdx.x] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t ar = 0, aw = 0;
+    for (uint32_t i = 0; i < 1024; i++) {
+      const uint64_t cr = s_r[i], cw = s_w[i];
+      s_r[i] = ar, s_w[i] = aw;
+      ar += cr, aw += cw;
+    }
+    tx_leaf_off[R.ntx] = (ar < R.n_refs ? ar : R.n_refs) + aw;
+  }
+  __syncthreads();
+  r = s_r[threadIdx.x], w = s_w[threadIdx.x];
+  for (uint64_t t = t0; t < t1; t++) {
+    const NotaryTx x = notary_tx(R, t);
+    tx_leaf_off[t] = (r < R.n_refs ? r : R.n_refs) + w;
+    tw_from[t] = tw_until[t] = kAbsent;
+    bad[t] = 0;
+    r += x.nref;
+    w += x.win;
+  }
+}
+
+// an Instant as cordahip_commit_batch's bounds: ns since the epoch, saturated at +-2^62
+// (|s| <= 4611686019: the product and the sum stay inside int64)
+__device__ inline int64_t instant_ns(int64_t s, int32_t nano) {
+  const int64_t lim = (int64_t)1 << 62;
+  if (s > 4611686018ll) return lim;
+  if (s < -4611686019ll) return -lim;
+  const int64_t v = s * 1000000000ll + nano;
+  return v > lim ? lim : v < -lim ? -lim : v;
+}
+
+__global__ void __launch_bounds__(256) notary_leaf_kernel(NotaryRows R, const uint64_t* __restrict__ tx_leaf_off,
+                                                          uint32_t* __restrict__ hashes, uint32_t* __restrict__ leaf_hash,
+                                                          int64_t* __restrict__ tw_from, int64_t* __restrict__ tw_until,
+                                                          uint8_t* __restrict__ bad) {
+  __shared__ uint8_t levels_s[256 * kNotaryLaneBytes];
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= tx_leaf_off[R.ntx]) return;
+  uint64_t lo = 0, hi = R.ntx;  // tx_leaf_off[lo] <= j < tx_leaf_off[hi]
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (tx_leaf_off[mid] <= j) lo = mid;
+    else hi = mid;
+  }
+  const uint64_t t = lo, k = j - tx_leaf_off[t];
+  const NotaryTx x = notary_tx(R, t);
+  const bool is_win = x.win && k + 1 == tx_leaf_off[t + 1] - tx_leaf_off[t];
+  // the encoder into a SHA-256 sink; called once per kind with the kind a constant, so
+  // each call keeps only its own kind's branch of encode_leaf (the generic instance,
+  // cash states and all, took 248 VGPRs and 1,168 bytes of scratch)
+  uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  auto leaf = [&](const cordahip_kryo_item& it) {
+    ShaSink sink;
+    kryo::KoutT<false, ShaSink, kNotaryStride, kNotaryLevels> o(nullptr, 0, levels_s + threadIdx.x * kNotaryLaneBytes);
+    o.sink = &sink;
+    const bool ok = kryo::encode_leaf(o, it);
+    if (ok) {
+      sink.finish(o.pos);
+      for (int q = 0; q < 8; q++) h[q] = sink.st[q];
+    }
+    return ok;
+  };
+  uint8_t row[kryo::kTimeWindowLen];
+  bool ok;
+  if (!is_win) {
+    cordahip_kryo_item it{};
+    it.kind = CORDAHIP_KRYO_STATE_REF;
+    it.data = reinterpret_cast<const uint8_t*>(R.refs + x.r0 + k);
+    it.len = kryo::kStateRefLen;
+    ok = leaf(it);
+  } else {
+    const uint64_t fs = (uint64_t)R.tw_from_s[t], us = (uint64_t)R.tw_until_s[t];
+    const uint32_t fn = (uint32_t)R.tw_from_nano[t], un = (uint32_t)R.tw_until_nano[t];
+    row[0] = R.tw_flags[t] & 0x7f;
+#pragma unroll
+    for (int q = 0; q < 8; q++) row[kryo::kTwFromS + q] = (uint8_t)(fs >> (8 * q)), row[kryo::kTwUntilS + q] = (uint8_t)(us >> (8 * q));
+#pragma unroll
+    for (int q = 0; q < 4; q++) row[kryo::kTwFromN + q] = (uint8_t)(fn >> (8 * q)), row[kryo::kTwUntilN + q] = (uint8_t)(un >> (8 * q));
+    cordahip_kryo_item it{};
+    it.kind = CORDAHIP_KRYO_TIME_WINDOW;
+    it.data = row;
+    it.len = kryo::kTimeWindowLen;
+    ok = leaf(it);
+  }
+  if (is_win) {
+    const uint32_t f = row[0];
+    tw_from[t] = ok && (f & 1) ? instant_ns(R.tw_from_s[t], R.tw_from_nano[t]) : kAbsent;
+    tw_until[t] = ok && (f & 2) ? instant_ns(R.tw_until_s[t], R.tw_until_nano[t]) : kAbsent;
+    bad[t] = ok ? 0 : 1;
+  }
+  uint4* out = reinterpret_cast<uint4*>(hashes + j * 8);
+  out[0] = make_uint4(h[0], h[1], h[2], h[3]);
+  out[1] = make_uint4(h[4], h[5], h[6], h[7]);
+  if (leaf_hash)
+    for (int q = 0; q < 8; q++) leaf_hash[j * 8 + q] = bswap32(h[q]);
+}
+
+__global__ void __launch_bounds__(256) notary_gate_kernel(const uint8_t* __restrict__ verify,
+                                                          const uint8_t* __restrict__ caller_gate,
+                                                          uint8_t* __restrict__ gate, uint64_t ntx) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < ntx) gate[t] = verify[t] != 0 || (caller_gate && caller_gate[t] != 0);
+}
+__global__ void __launch_bounds__(256) notary_status_kernel(const uint8_t* __restrict__ verify,
+                                                            const uint8_t* __restrict__ commit,
+                                                            uint8_t* __restrict__ status, uint64_t ntx) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < ntx) status[t] = verify[t] ? verify[t] : commit[t];
+}
+
 }  // namespace
+
+hipError_t launch_notary_leaves(const NotaryRows& R, uint64_t* tx_leaf_off, uint32_t* hashes, uint8_t* leaf_hash,
+                                int64_t* tw_from, int64_t* tw_until, uint8_t* bad, hipStream_t s) {
+  if (!R.ntx) return hipSuccess;
+  hipLaunchKernelGGL(notary_prep_kernel, dim3(1), dim3(1024), 0, s, R, tx_leaf_off, tw_from, tw_until, bad);
+  const uint64_t lanes = R.n_refs + R.ntx;  // at least the leaves: every ref and at most a window each
+  hipLaunchKernelGGL(notary_leaf_kernel, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, s, R, tx_leaf_off, hashes,
+                     reinterpret_cast<uint32_t*>(leaf_hash), tw_from, tw_until, bad);
+  return hipGetLastError();
+}
+hipError_t launch_notary_gate(const uint8_t* verify, const uint8_t* caller_gate, uint8_t* gate, uint64_t ntx,
+                              hipStream_t s) {
+  if (!ntx) return hipSuccess;
+  hipLaunchKernelGGL(notary_gate_kernel, dim3((uint32_t)((ntx + 255) / 256)), dim3(256), 0, s, verify, caller_gate, gate,
+                     ntx);
+  return hipGetLastError();
+}
+hipError_t launch_notary_status(const uint8_t* verify, const uint8_t* commit, uint8_t* status, uint64_t ntx,
+                                hipStream_t s) {
+  if (!ntx) return hipSuccess;
+  hipLaunchKernelGGL(notary_status_kernel, dim3((uint32_t)((ntx + 255) / 256)), dim3(256), 0, s, verify, commit, status,
+                     ntx);
+  return hipGetLastError();
+}
 
 // The encoder's persistent per-device state (cordahip.cpp allocates
 // kryo_fixed_scratch_bytes() once, zeroed; kryo_clear() empties it).

@@ -7,7 +7,9 @@
 // whether the owner and issuer keys are equal -- and through *content* bytes
 // that the encoder copies verbatim (key bytes, X.500 name bytes, the reference,
 // the legal-contract hash) or writes from the item's value (the quantity /
-// nonce varlong, a primitive's big-endian bytes). Items with equal structure
+// nonce varlong, a primitive's big-endian bytes) or from a payload integer as a
+// varint (a StateRef's index, a TimeWindow's seconds and nanos: the varint's
+// LENGTH is structure, its bytes are content). Items with equal structure
 // ("one shape") produce leaves of the same length whose bytes differ only where
 // content lands, and the positions of that content are the same. So the GPU
 // encodes ONE representative per shape in trace mode (KoutT<true>: every byte
@@ -40,6 +42,15 @@ namespace kryo {
 // outsized content go to the direct encoder, which also decides their
 // validity).
 
+// bytes of Output.writeVarLong(v, true) (1..9)
+KRYO_HD inline uint32_t varlong_len(uint64_t v) {
+  uint32_t m = 1;
+  for (int i = 0; i < 8 && (v >> 7); i++) {
+    v >>= 7;
+    m++;
+  }
+  return m;
+}
 // bytes of Output.writeVarLong(zigzag(v)) (1..9): part of the shape of a VALUE_ZZ kind
 KRYO_HD inline uint32_t varlong_zz_len(int64_t x) {
   uint64_t v = ((uint64_t)x << 1) ^ (uint64_t)(x >> 63);
@@ -136,6 +147,22 @@ KRYO_HD inline bool shape_walk(const cordahip_kryo_item& it, V& v) {
       v.word(flags);
       v.word((flags & 1u) ? (uint32_t)(enc[0] | (enc[1] << 8) | (enc[2] << 16) | ((uint32_t)enc[3] << 24)) : 0);
       v.word(same_key(owner, issuer));  // exitKeys has one element or two
+      return true;
+    }
+    case CORDAHIP_KRYO_STATE_REF:  // the index's varint length; the hash and the index bytes are content
+      if (!it.data || it.len != kStateRefLen) return false;
+      v.word(varlong_len(zigzag32(le32(it.data + kStateRefIndexOff))));
+      return true;
+    case CORDAHIP_KRYO_TIME_WINDOW: {  // the flags and the four varint lengths (valid rows only:
+                                       // the encoder validates seconds and nanos, see rejected_outright)
+      const TimeWindowRow r = time_window_row(it);
+      if (!r.ok) return false;
+      v.word(r.flags);
+      for (int i = 0; i < 2; i++) {
+        const bool on = (r.flags >> i) & 1u;
+        v.word(on ? varlong_len((uint64_t)r.s[i]) : 0);
+        v.word(on ? varlong_len((uint32_t)r.n[i]) : 0);
+      }
       return true;
     }
     default: return false;  // RAW (copied directly) and unknown kinds
@@ -300,6 +327,8 @@ KRYO_HD inline bool rejected_outright(const cordahip_kryo_item& it) {
     case CORDAHIP_KRYO_PARTY: return !it.data || it.len < 3;
     case CORDAHIP_KRYO_ISSUE_COMMAND: return !it.data || it.len < 2;
     case CORDAHIP_KRYO_CASH_STATE: return !it.data;
+    case CORDAHIP_KRYO_STATE_REF: return !it.data || it.len != kStateRefLen;
+    case CORDAHIP_KRYO_TIME_WINDOW: return !time_window_row(it).ok;  // every invalid row: it has no shape
     default: return true;
   }
 }
@@ -315,8 +344,13 @@ KRYO_HD inline uint8_t sym_byte(uint32_t sym, const uint8_t* data, int64_t value
   switch (sym & kSymTypeMask) {
     case kSymConst: return (uint8_t)sym;
     case kSymPayload: return (uint8_t)(data[(sym >> 8) & (kMaxPayloadOff - 1)] | ((sym & kSymOr80) ? 0x80 : 0));
-    case kSymValZz: {  // byte j of Output.writeVarLong(zigzag(value)) (varlong_zigzag)
-      const uint64_t u = ((uint64_t)value << 1) ^ (uint64_t)(value >> 63);
+    case kSymValZz: {  // byte j of Output.writeVarLong(zigzag(value)) (varlong_zigzag), or of the
+                       // varint of a payload integer (sym_var: STATE_REF, TIME_WINDOW)
+      uint64_t u = ((uint64_t)value << 1) ^ (uint64_t)(value >> 63);
+      if (sym & kSymVarData) {
+        const uint8_t* q = data + ((sym >> 12) & 63);
+        u = (sym & kSymVarWide) ? le64(q) : (sym & kSymVarPlain) ? le32(q) : zigzag32(le32(q));
+      }
       if (j >= 8) return (uint8_t)(u >> 56);
       const uint64_t x = u >> (7 * j);
       return (x >> 7) ? (uint8_t)((x & 0x7f) | 0x80) : (uint8_t)x;

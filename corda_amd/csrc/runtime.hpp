@@ -26,6 +26,7 @@
 #include "../../include/cordahip.h"
 #include "commit_core.hpp"
 #include "key_slots.hpp"
+#include "notary_rows.hpp"
 #include "numa_place.hpp"
 
 namespace cordahip {
@@ -176,7 +177,20 @@ hipError_t launch_tx_cover(const cordahip_cover& c, uint64_t ntx, uint8_t* tx_st
                            uint64_t* stack, hipStream_t s);
 hipError_t launch_pmt_verify(const uint32_t* leaf_hashes, const uint64_t* tx_leaf_off, const uint8_t* tok,
                              const uint8_t* tok_hash, const uint64_t* tx_tok_off, const uint8_t* root, uint64_t ntx,
-                             uint32_t* stack, uint8_t* tx_status, hipStream_t s);
+                             uint32_t* stack, uint8_t* tx_status, hipStream_t s,
+                             const uint8_t* bad_component = nullptr);
+// K21 (kryo_device.hip): a notary tear-off's leaf hashes from typed rows. R holds device
+// pointers (tw_flags nullptr: no windows). tx_leaf_off [ntx+1], hashes [(n_refs + ntx) * 8]
+// words as K6 reads them, leaf_hash (may be nullptr) the same hashes as bytes, tw_from /
+// tw_until / bad [ntx]: the windows as cordahip_commit_batch takes them and the
+// transactions whose window row is no valid item.
+hipError_t launch_notary_leaves(const NotaryRows& R, uint64_t* tx_leaf_off, uint32_t* hashes, uint8_t* leaf_hash,
+                                int64_t* tw_from, int64_t* tw_until, uint8_t* bad, hipStream_t s);
+// gate[t] = verify[t] != OK or caller_gate[t] (may be nullptr) set; status[t] = verify[t] if not OK, else commit[t]
+hipError_t launch_notary_gate(const uint8_t* verify, const uint8_t* caller_gate, uint8_t* gate, uint64_t ntx,
+                              hipStream_t s);
+hipError_t launch_notary_status(const uint8_t* verify, const uint8_t* commit, uint8_t* status, uint64_t ntx,
+                                hipStream_t s);
 // K10 (tx.hip): up = 2 * nleaves hashes, has = 3 * nleaves bytes of workspace (pmt_core.hpp)
 hipError_t launch_pmt_build(const uint32_t* hashes, const uint64_t* tx_leaf_off, uint64_t ntx, const uint8_t* include,
                             const uint64_t* tx_tok_off, uint64_t ntok, uint32_t* up, uint8_t* has, uint8_t* txid,

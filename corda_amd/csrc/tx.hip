@@ -405,9 +405,14 @@ __global__ void __launch_bounds__(256) pmt_verify_kernel(const uint32_t* __restr
                                                         const uint8_t* __restrict__ tok_hash,
                                                         const uint64_t* __restrict__ tx_tok_off,
                                                         const uint8_t* __restrict__ root, uint64_t ntx,
-                                                        uint32_t* __restrict__ stack, uint8_t* __restrict__ tx_status) {
+                                                        uint32_t* __restrict__ stack, uint8_t* __restrict__ tx_status,
+                                                        const uint8_t* __restrict__ bad_component) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ntx) return;
+  if (bad_component && bad_component[t]) {  // K21: a typed leaf that is no valid item has no hash
+    tx_status[t] = kTxBadComponent;
+    return;
+  }
   const uint64_t l0 = tx_leaf_off[t], l1 = tx_leaf_off[t + 1];
   if (l0 == l1) {  // filteredLeaves.availableComponentHashes empty: MerkleTreeException
     tx_status[t] = kTxNoLeaves;
@@ -463,10 +468,10 @@ __global__ void __launch_bounds__(256) pmt_verify_kernel(const uint32_t* __restr
 
 hipError_t launch_pmt_verify(const uint32_t* leaf_hashes, const uint64_t* tx_leaf_off, const uint8_t* tok,
                              const uint8_t* tok_hash, const uint64_t* tx_tok_off, const uint8_t* root, uint64_t ntx,
-                             uint32_t* stack, uint8_t* tx_status, hipStream_t s) {
+                             uint32_t* stack, uint8_t* tx_status, hipStream_t s, const uint8_t* bad_component) {
   if (!ntx) return hipSuccess;
   hipLaunchKernelGGL(pmt_verify_kernel, dim3((uint32_t)((ntx + 255) / 256)), dim3(256), 0, s, leaf_hashes,
-                     tx_leaf_off, tok, tok_hash, tx_tok_off, root, ntx, stack, tx_status);
+                     tx_leaf_off, tok, tok_hash, tx_tok_off, root, ntx, stack, tx_status, bad_component);
   return hipGetLastError();
 }
 

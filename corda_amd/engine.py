@@ -887,6 +887,113 @@ class Engine:
         check(lib().cordahip_filtered_tx_verify(self._ctx, ctypes.byref(b)), "cordahip_filtered_tx_verify")
         return st[:len(ftxs)]
 
+    # ---- notary tear-offs from typed refs and windows (K21 + K6, then K16) ------
+    def _tearoff_arrays(self, tearoffs, leaf_hash: bool):
+        """tearoffs[t] = (refs: [(txhash, index)], window: None or (from, until) with a side None or
+        (epochSecond, nano), tokens: [(tok, hash32 or None)], root: bytes32) as the arrays of a
+        cordahip_notary_tearoff_batch; returns (batch, keep, off, st, lh)."""
+        n = len(tearoffs)
+        flat = [r for f in tearoffs for r in f[0]]
+        nr = len(flat)
+        refs = self._state_refs(flat)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        ko = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            off[1:] = np.cumsum([len(f[0]) for f in tearoffs], dtype=np.uint64)
+            ko[1:] = np.cumsum([len(f[2]) for f in tearoffs], dtype=np.uint64)
+        fl = fs = fn = us = un = None
+        nwin = sum(1 for f in tearoffs if f[1] is not None)
+        if nwin:
+            fl = np.zeros(n, dtype=np.uint8)
+            fs, us = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+            fn, un = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+            for t, f in enumerate(tearoffs):
+                if f[1] is None:
+                    continue
+                a, z = f[1]
+                fl[t] = _lib.TW_PRESENT | (a is not None) | ((z is not None) << 1)
+                if a is not None:
+                    fs[t], fn[t] = a
+                if z is not None:
+                    us[t], un[t] = z
+        toks = [t for f in tearoffs for t in f[2]]
+        tok = np.ascontiguousarray(np.array([t[0] for t in toks] or [0], dtype=np.uint8))
+        th = np.frombuffer(b"".join((t[1] or bytes(32)) for t in toks) or bytes(32), dtype=np.uint8).copy()
+        root = np.frombuffer(b"".join(bytes(f[3]) for f in tearoffs) or bytes(32), dtype=np.uint8).copy()
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        lh = np.zeros((max(nr + nwin, 1), 32), dtype=np.uint8) if leaf_hash else None
+        p = lambda x: _ptr(x) if x is not None else None  # noqa: E731
+        b = _lib.NotaryTearoffBatch(n, refs.ctypes.data if nr else None, _ptr(off), nr, p(fl), p(fs), p(fn), p(us),
+                                    p(un), _ptr(tok), _ptr(th), _ptr(ko), len(toks), _ptr(root), _ptr(st), p(lh))
+        return b, (refs, off, ko, fl, fs, fn, us, un, tok, th, root, st, lh, b), off, st, lh
+
+    def notary_tearoff_verify(self, tearoffs, leaf_hash: bool = False, async_: bool = False):
+        """cordahip_notary_tearoff_verify / _submit: FilteredTransaction.verify of tear-offs given as
+        typed components (tearoffs as _tearoff_arrays takes them), their StateRef / TimeWindow leaves
+        hashed on the GPU. Returns tx_status[ntx] -- with leaf_hash, (tx_status, hashes [leaves, 32])
+        in availableComponents order -- or, async_, a Ticket whose wait() returns that."""
+        n = len(tearoffs)
+        b, keep, _, st, lh = self._tearoff_arrays(tearoffs, leaf_hash)
+        nl = sum(len(f[0]) + (f[1] is not None) for f in tearoffs)
+        res = (lambda: (st[:n], lh[:nl])) if leaf_hash else (lambda: st[:n])
+        if async_:
+            t = ctypes.c_uint64()
+            check(lib().cordahip_notary_tearoff_submit(self._ctx, ctypes.byref(b), ctypes.byref(t)),
+                  "cordahip_notary_tearoff_submit")
+            return Ticket(self, t.value, res, keep)
+        check(lib().cordahip_notary_tearoff_verify(self._ctx, ctypes.byref(b)), "cordahip_notary_tearoff_verify")
+        return res()
+
+    def notary_tearoff_commit(self, log_id: int, tearoffs, callers, now_ns: int = 0, tolerance_ns: int = 0,
+                              gate=None, async_: bool = False):
+        """cordahip_notary_tearoff_commit / _commit_submit: verify the typed tear-offs and commit the
+        refs of those that verify, on the log's device, gated by `gate` (nonzero: skip) as well.
+        Returns (tx_status, committed, ref_state, ref_by) shaped as commit_inputs returns them;
+        tx_status is the verify status where that is not OK, else the commit's."""
+        n = len(tearoffs)
+        assert len(callers) == n and (gate is None or len(gate) == n)
+        b, keep, off, st, _ = self._tearoff_arrays(tearoffs, False)
+        nr = int(off[n])
+        caller = np.ascontiguousarray(np.asarray(list(callers) or [0], dtype=np.uint32))
+        g = None if gate is None else np.ascontiguousarray(np.asarray(list(gate) or [0], dtype=np.uint8))
+        cm = np.zeros(max(n, 1), dtype=np.uint8)
+        rs = np.zeros(max(nr, 1), dtype=np.uint8)
+        rb = np.zeros(max(nr, 1), dtype=_lib.CONSUMING_TX_DTYPE)
+        args = (self._ctx, log_id, ctypes.byref(b), _ptr(caller), now_ns, tolerance_ns,
+                _ptr(g) if g is not None else None, _ptr(cm), _ptr(rs), rb.ctypes.data)
+
+        def res():
+            states, bys = [], []
+            for t in range(n):
+                a, z = int(off[t]), int(off[t + 1])
+                states.append([int(x) for x in rs[a:z]])
+                bys.append([(rb[i]["id"].tobytes(), int(rb[i]["input_index"]), int(rb[i]["caller"])) if rs[i] else None
+                            for i in range(a, z)])
+            return st[:n], cm[:n], states, bys
+
+        if async_:
+            t = ctypes.c_uint64()
+            check(lib().cordahip_notary_tearoff_commit_submit(*args, ctypes.byref(t)),
+                  "cordahip_notary_tearoff_commit_submit")
+            return Ticket(self, t.value, res, keep + (caller, g, cm, rs, rb))
+        check(lib().cordahip_notary_tearoff_commit(*args), "cordahip_notary_tearoff_commit")
+        return res()
+
+    def notary_tearoff_device(self, refs, tx_ref_off, tok, tok_hash, tx_tok_off, root, tx_status, tw_from, tw_until,
+                              tw_flags=None, tw_from_s=None, tw_from_nano=None, tw_until_s=None, tw_until_nano=None,
+                              leaf_hash=None, device: int = 0, stream=None):
+        """cordahip_notary_tearoff_device over device tensors: refs uint8 [n_refs, 36], tx_ref_off /
+        tx_tok_off int64 [ntx + 1], tok uint8 [ntok], tok_hash uint8 [ntok, 32], root uint8 [ntx, 32],
+        the window rows (uint8 / int64 / int32 [ntx], all or none); outputs tx_status uint8 [ntx],
+        tw_from / tw_until int64 [ntx], leaf_hash uint8 [leaves, 32] or None."""
+        s = stream.cuda_stream if stream is not None else 0
+        p = lambda x: x.data_ptr() if x is not None and x.numel() else None  # noqa: E731
+        b = _lib.NotaryTearoffBatch(root.shape[0], p(refs), p(tx_ref_off), refs.shape[0], p(tw_flags), p(tw_from_s),
+                                    p(tw_from_nano), p(tw_until_s), p(tw_until_nano), p(tok), p(tok_hash),
+                                    p(tx_tok_off), tok.shape[0], p(root), p(tx_status), p(leaf_hash))
+        check(lib().cordahip_notary_tearoff_device(self._ctx, device, ctypes.byref(b), p(tw_from), p(tw_until), s),
+              "cordahip_notary_tearoff_device")
+
     # ---- FilteredTransaction build / PartialMerkleTree.build -------------------
     def filtered_tx_build(self, txs, async_: bool = False):
         """txs[t] = (leaves: [bytes], include: [bool]), one include flag per leaf (the filter predicate's

@@ -417,6 +417,69 @@ def notarise_filtered_transactions_persisted(engine, log_id: int, ftxs, inputs, 
     return answers, rows
 
 
+_COMMIT_STATUSES = (OK, _COMMIT_CONFLICT, _COMMIT_TIME_WINDOW_INVALID, 18)  # what K16 answers; the rest are verify statuses
+
+
+def notarise_tearoffs(engine, log_id: int, tearoffs, callers, key_id: int, now: int, tolerance: int):
+    """notarise_filtered_transactions for tear-offs given as TYPED components, the way
+    NonValidatingNotaryFlow.receiveAndVerifyTx uses them (NonValidatingNotaryFlow.kt:21-27): the
+    refs and the window that are committed are the ones ftx.verify() hashed, not separate arguments.
+    tearoffs[t] = (refs, window, tokens, root): refs = [(txhash, index)] (FilteredLeaves.inputs),
+    window None or (from, until) with a side None or (epochSecond, nano) (FilteredLeaves.timeWindow),
+    tokens the partial tree as filtered_tx_verify takes it, root the transaction id. One
+    Engine.notary_tearoff_commit (K21 + K6 + K16 on the log's device, no leaf serialised anywhere),
+    then the signing call gated on its statuses.
+
+    Returns (answers, committed_rows) exactly as notarise_filtered_transactions does for the same
+    tear-offs with their leaves serialised and the same refs and windows; a window row that is no
+    Instant pair (CORDAHIP_TX_BAD_COMPONENT) is a TransactionInvalid."""
+    n = len(tearoffs)
+    assert len(callers) == n
+    if n == 0:
+        return [], []
+    ids = [bytes(f[3]) for f in tearoffs]
+    status, committed, ref_state, ref_by = engine.notary_tearoff_commit(log_id, tearoffs, callers, now, tolerance)
+    sigs, sst = _sign_with(engine, key_id, ids, status)
+    answers, rows = [], []
+    for t in range(n):
+        st = int(status[t])
+        refs = tearoffs[t][0]
+        if st not in _COMMIT_STATUSES:
+            answers.append(NotaryError("TransactionInvalid", ids[t]))
+        elif st == _COMMIT_TIME_WINDOW_INVALID:
+            answers.append(NotaryError("TimeWindowInvalid", ids[t]))
+        elif st == _COMMIT_CONFLICT:
+            hist = {}
+            for r, by in zip(refs, ref_by[t]):
+                if by is not None:
+                    hist.setdefault((bytes(r[0]), int(r[1])), by)
+            answers.append(NotaryError("Conflict", ids[t], hist))
+        elif int(sst[t]) == _SIGN_UNKNOWN_KEY:
+            raise NoSuchElementException("no registered key %d" % key_id)
+        else:
+            answers.append(bytes(sigs[t]))
+        if committed[t]:
+            last = {}
+            for i, r in enumerate(refs):
+                last[(bytes(r[0]), int(r[1]))] = (ids[t], i, int(callers[t]))
+            rows.extend(last.items())
+    return answers, rows
+
+
+def notarise_tearoffs_persisted(engine, log_id: int, tearoffs, callers, key_id: int, now: int, tolerance: int, persist):
+    """notarise_tearoffs with the database write inside the call, on the terms of
+    notarise_filtered_transactions_persisted: persist(committed_rows) before anything is returned;
+    if it raises, exactly those rows are revoked and the exception is re-raised."""
+    answers, rows = notarise_tearoffs(engine, log_id, tearoffs, callers, key_id, now, tolerance)
+    try:
+        persist(rows)
+    except BaseException:
+        revoked, removed = engine.commit_log_revoke(log_id, rows)
+        assert all(revoked) and removed == len(rows), "rows of a failed write that the log no longer holds"
+        raise
+    return answers, rows
+
+
 def validate_notary_signatures(engine, key_id: int, ids: Sequence[bytes], sigs: Sequence[bytes],
                                ecdsa: bool = False):
     """What a notary client does with the notary's answers (NotaryFlow.Client.call,

@@ -1182,6 +1182,38 @@ int cordahip_filtered_tx_build_device(cordahip_ctx* ctx, int device, const void*
 #define CORDAHIP_KRYO_PARTY 13
 #define CORDAHIP_KRYO_ISSUE_COMMAND 14
 #define CORDAHIP_KRYO_CASH_STATE 15
+/* The two components a non-validating notary is shown (NotaryFlow.kt:62 reveals
+ * `it is StateRef || it is TimeWindow`). Both classes are @CordaSerializable and
+ * unregistered: NAME registration, CompatibleFieldSerializer with EXTENDED names.
+ *   STATE_REF      net.corda.core.contracts.StateRef(txhash, index)
+ *                  (Structures.kt:247). Fields in name order: StateRef.index, a
+ *                  primitive int: Output.writeInt(v, false), the zig-zag varint;
+ *                  StateRef.txhash, declared SecureHash (not final): the class
+ *                  net.corda.core.crypto.SecureHash$SHA256 by name, then its one
+ *                  field OpaqueBytes.bytes (varint(33), the 32 bytes). data = one
+ *                  cordahip_state_ref row (32 bytes txhash, u32 LE index read as a
+ *                  Java int), len = 36; class_id and value unused. 173..177 bytes.
+ *   TIME_WINDOW    net.corda.core.contracts.TimeWindow(fromTime, untilTime)
+ *                  (Structures.kt:336-341), two nullable java.time.Instant fields
+ *                  TimeWindow.fromTime, TimeWindow.untilTime. Instant is final, so
+ *                  no class is written: a side is NULL (00) or NOT_NULL (01) and the
+ *                  Instant body. THE BODY IS TAKEN TO BE Kryo 4.0.0's
+ *                  TimeSerializers.InstantSerializer: writeLong(epochSecond, true),
+ *                  writeInt(nano, true) -- plain varints, a negative second takes 9
+ *                  bytes. That TimeSerializers is among Kryo 4.0.0's default
+ *                  serializers is recalled from its published source, not checked
+ *                  against it here (no Kryo source, no JVM). data, len = 25: u8
+ *                  flags (bit 0 fromTime present, bit 1 untilTime present), i64 LE
+ *                  from-epochSecond, i32 LE from-nano, i64 LE until-epochSecond, i32
+ *                  LE until-nano. Invalid: another len, flags & ~3, a present side
+ *                  with nano outside [0, 999999999] or seconds outside Instant's
+ *                  range [-31557014167219200, 31556889864403199]. flags == 0 is
+ *                  encoded (two NULL markers). 91..119 bytes.
+ * Both are PARITY UNPINNED like PARTY / ISSUE_COMMAND / CASH_STATE; the vectors
+ * in tests/golden/notary_leaf_vectors.json are derived from the same published
+ * rules by the test model, not taken from a JVM. */
+#define CORDAHIP_KRYO_STATE_REF 16
+#define CORDAHIP_KRYO_TIME_WINDOW 17
 typedef struct {
   uint32_t kind;       /* CORDAHIP_KRYO_* */
   uint32_t class_id;   /* Kryo registration id (ED25519_KEY, PUBLIC_KEY) */
@@ -1563,6 +1595,75 @@ int cordahip_commit_inputs_submit(cordahip_ctx* ctx, uint32_t log_id, const cord
  * Stream-ordered on hip_stream; returns once enqueued. */
 int cordahip_commit_inputs_device(cordahip_ctx* ctx, uint32_t log_id, const cordahip_commit_batch* d_batch,
                                   void* hip_stream);
+
+/* ---- notary tear-offs from typed inputs and time windows (K21) ---------------------- *
+ * What NonValidatingNotaryFlow.receiveAndVerifyTx does with a request
+ * (NonValidatingNotaryFlow.kt:21-27): ftx.verify(), then commitInputStates over
+ * ftx.filteredLeaves.inputs and .timeWindow -- the SAME objects whose serializedHash
+ * verify() checked (MerkleTransaction.kt:69,135-140). NotaryFlow.Client reveals exactly
+ * StateRefs and the TimeWindow (NotaryFlow.kt:62), so a tear-off arrives here as typed
+ * rows: the cordahip_state_ref rows cordahip_commit_inputs takes, the window's two
+ * Instants, the partial tree and the root. K21 hashes the rows' Kryo leaves on the GPU
+ * (kinds STATE_REF / TIME_WINDOW above; bit-identical to SHA-256 of cordahip_kryo_encode's
+ * leaf; no leaf bytes cross PCIe or touch HBM), K6 checks them against the partial tree,
+ * and the commit form hands K16 the same device copies of the rows: the refs that are
+ * committed are the refs that were proven. Leaf order is availableComponents order
+ * (MerkleTransaction.kt:51-62): a transaction's refs in list order, then its window.
+ * tx_status[t] is what cordahip_filtered_tx_verify answers for the same tear-off with
+ * its leaves serialised by cordahip_kryo_encode -- OK, BAD_SIG, CORDAHIP_TX_NO_LEAVES
+ * (no ref and no window), CORDAHIP_TX_BAD_TREE -- and CORDAHIP_TX_BAD_COMPONENT for a
+ * window row that is no valid TIME_WINDOW item (its leaf hash is zero). The multiset
+ * rule of PartialMerkleTree.verify (PartialMerkleTree.kt:132-139) is K6's: refs in
+ * another order still verify; a tear-off that reveals any other component (a command)
+ * cannot, as the typed form cannot name it. Both kinds are PARITY UNPINNED (see above).
+ * tw_flags[t]: bit 7 the transaction has a TimeWindow; bits 0..6 the TIME_WINDOW item's
+ * flags (bit 0 fromTime, bit 1 untilTime present); without bit 7 the row is ignored.
+ * leaf_hash (may be NULL): the leaf hashes, packed, transaction by transaction -- leaf j
+ * of transaction t at (tx_ref_off[t] - tx_ref_off[0]) + (windows before t) + j.
+ * CSR: tx_ref_off[0..ntx] non-decreasing and within n_refs, tx_tok_off[0..ntx]
+ * non-decreasing and within ntok, the five window arrays all given or all NULL: checked
+ * whole before any enqueue, else CORDAHIP_ERR_INVALID_ARG (host forms). The verify
+ * forms shard over the devices by transaction like cordahip_filtered_tx_verify. */
+typedef struct {
+  uint64_t ntx;
+  const cordahip_state_ref* refs;  /* [n_refs] FilteredLeaves.inputs, list order */
+  const uint64_t* tx_ref_off;      /* [ntx+1] */
+  uint64_t n_refs;
+  const uint8_t* tw_flags;         /* [ntx] bit 7: timeWindow present; bits 0/1 as the TIME_WINDOW item; NULL: no windows */
+  const int64_t* tw_from_s;  const int32_t* tw_from_nano;    /* [ntx] */
+  const int64_t* tw_until_s; const int32_t* tw_until_nano;   /* [ntx] */
+  const uint8_t* tok; const uint8_t* tok_hash; const uint64_t* tx_tok_off; uint64_t ntok;  /* as cordahip_filtered_tx_batch */
+  const uint8_t* root;             /* [ntx*32] FilteredTransaction.rootHash = the id */
+  uint8_t* tx_status;              /* [ntx] out */
+  uint8_t* leaf_hash;              /* [(n_refs + windows)*32] out, may be NULL */
+} cordahip_notary_tearoff_batch;
+int cordahip_notary_tearoff_verify(cordahip_ctx* ctx, const cordahip_notary_tearoff_batch* batch);
+int cordahip_notary_tearoff_submit(cordahip_ctx* ctx, const cordahip_notary_tearoff_batch* batch, uint64_t* ticket);
+/* The device-resident form: `d_batch` is a HOST struct whose pointers are DEVICE memory
+ * on `device` (4-byte aligned; the int64 / uint64 arrays 8-byte aligned), stream-ordered
+ * on hip_stream; returns once enqueued. d_tw_from / d_tw_until [ntx] int64 receive each
+ * transaction's window as cordahip_commit_batch takes it: ns since the epoch as
+ * seconds * 10^9 + nano, saturated at +-2^62, INT64_MIN for an absent side, an absent
+ * window or an invalid window row. Offsets beyond n_refs are cut to n_refs on the
+ * device, and a token range is read as given: tx_tok_off must lie within ntok. */
+int cordahip_notary_tearoff_device(cordahip_ctx* ctx, int device, const cordahip_notary_tearoff_batch* d_batch,
+                                   void* d_tw_from, void* d_tw_until, void* hip_stream);
+/* Verify and commit in one call, wholly on the log's device and on one stream, no host
+ * round trip between the stages: K21, K6, then K16 over the same device copies of refs /
+ * tx_ref_off with txid = root, the windows K21 derived, and the gate (caller's gate[t]
+ * != 0) OR (verify status != OK). batch->tx_status[t] is the verify status where that is
+ * not OK, else K16's (OK / COMMIT_CONFLICT / COMMIT_TIME_WINDOW_INVALID / COMMIT_SKIPPED:
+ * the two code sets do not overlap); it goes in as the signer's gate. caller, now_ns,
+ * tolerance_ns, gate (may be NULL), committed, ref_state, ref_by (indexed like refs) and
+ * the ordering on the log, CORDAHIP_ERR_LOG_FULL and the bound bookkeeping are
+ * cordahip_commit_inputs's. */
+int cordahip_notary_tearoff_commit(cordahip_ctx* ctx, uint32_t log_id, const cordahip_notary_tearoff_batch* batch,
+                                   const uint32_t* caller, int64_t now_ns, int64_t tolerance_ns, const uint8_t* gate,
+                                   uint8_t* committed, uint8_t* ref_state, cordahip_consuming_tx* ref_by);
+int cordahip_notary_tearoff_commit_submit(cordahip_ctx* ctx, uint32_t log_id,
+                                          const cordahip_notary_tearoff_batch* batch, const uint32_t* caller,
+                                          int64_t now_ns, int64_t tolerance_ns, const uint8_t* gate, uint8_t* committed,
+                                          uint8_t* ref_state, cordahip_consuming_tx* ref_by, uint64_t* ticket);
 
 /* Device time (ms) of the calling thread's most recent *_device call on
  * `device`, from HIP events recorded around its launches on the stream it ran
