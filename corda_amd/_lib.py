@@ -60,12 +60,14 @@ EXPORTS = [
     "cordahip_commit_log_revoke", "cordahip_commit_log_export",
     "cordahip_notary_tearoff_verify", "cordahip_notary_tearoff_submit", "cordahip_notary_tearoff_device",
     "cordahip_notary_tearoff_commit", "cordahip_notary_tearoff_commit_submit",
+    "cordahip_txcomp_inputs_device",
 ]
 ERR_BUFFER_TOO_SMALL = -8
 # cordahip_kryo_item kinds (CORDAHIP_KRYO_*)
 KRYO_KINDS = {"raw": 0, "char": 1, "short": 2, "int": 3, "long": 4, "byte": 5, "boolean": 6, "float": 7,
               "double": 8, "String": 9, "ed25519_key": 10, "public_key": 11, "kotlin_object": 12, "party": 13,
-              "issue_command": 14, "cash_state": 15, "state_ref": 16, "time_window": 17}
+              "issue_command": 14, "cash_state": 15, "state_ref": 16, "time_window": 17,
+              "move_command": 18, "secure_hash": 19}
 ABI_VERSION = 4
 FLAG_IS_VALID = 1  # CORDAHIP_FLAG_IS_VALID: Crypto.isValid semantics (no emptiness checks)
 FLAG_RSA_ON_DEVICE = 2  # CORDAHIP_FLAG_RSA_ON_DEVICE: RSA_SHA256 lanes verified on the GPU, not UNSUPPORTED
@@ -470,6 +472,7 @@ def lib() -> ctypes.CDLL:
                                                  ctypes.c_int64, vp, vp, vp, vp]),
         "cordahip_notary_tearoff_commit_submit": (i32, [vp, u32, ctypes.POINTER(NotaryTearoffBatch), vp, ctypes.c_int64,
                                                         ctypes.c_int64, vp, vp, vp, vp, ctypes.POINTER(u64)]),
+        "cordahip_txcomp_inputs_device": (i32, [vp, i32, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(l, name)
@@ -545,6 +548,25 @@ def pack_time_window(from_time, until_time):
             + int(us).to_bytes(8, "little", signed=True) + int(un).to_bytes(4, "little", signed=True))
 
 
+MOVE_HAS_HASH, MOVE_ARRAY_LIST = 1, 2  # CORDAHIP_KRYO_MOVE_COMMAND's flags byte
+
+
+def _pack_command_head(cls, keys):
+    """The head ISSUE_COMMAND and MOVE_COMMAND payloads share: the class name and the signer keys."""
+    nm = cls.encode("ascii")
+    return bytes([len(nm)]) + nm + bytes([len(keys)]) + b"".join(
+        int(kc).to_bytes(2, "little") + len(k).to_bytes(2, "little") + bytes(k) for kc, k in keys)
+
+
+def pack_move_command(cls, keys, contract_hash=None, array_list=True):
+    """The CORDAHIP_KRYO_MOVE_COMMAND payload: cls the Move class's binary name, keys
+    [(key class id, key bytes)], contract_hash None or 32 bytes, array_list: the signers are a
+    java.util.ArrayList (OnLedgerAsset.generateSpend) rather than addCommand's Arrays$ArrayList."""
+    assert contract_hash is None or len(contract_hash) == 32
+    flags = (MOVE_HAS_HASH if contract_hash is not None else 0) | (MOVE_ARRAY_LIST if array_list else 0)
+    return _pack_command_head(cls, keys) + bytes([flags]) + bytes(contract_hash or b"")
+
+
 def kryo_pack(items):
     """(kind, value, class_id) tuples -> (payload blob uint8, KRYO_ITEM_DTYPE[n] whose `data` are
     OFFSETS into the blob, bool[n]: the item has a payload). kind: a KRYO_KINDS key; value: bytes
@@ -561,7 +583,8 @@ def kryo_pack(items):
         if kind in ("String", "kotlin_object"):
             b = value.encode("utf-16-le")
             arr[i]["len"] = len(b) // 2
-        elif kind in ("raw", "ed25519_key", "public_key", "state_ref", "time_window"):  # the payload as bytes
+        elif kind in ("raw", "ed25519_key", "public_key", "state_ref", "time_window", "move_command",
+                      "secure_hash"):  # the payload as bytes (pack_state_ref, pack_time_window, pack_move_command)
             b = bytes(value)
             arr[i]["len"] = len(b)
         elif kind == "party":  # value = (X.500 name DER, key bytes, key class id); class_id = X500Name's id
@@ -571,9 +594,7 @@ def kryo_pack(items):
             arr[i]["value"] = key_class
         elif kind == "issue_command":  # value = (class name, nonce, [(key class id, key bytes)]); class_id = Arrays$ArrayList's
             cls, nonce, keys = value
-            nm = cls.encode("ascii")
-            b = bytes([len(nm)]) + nm + bytes([len(keys)]) + b"".join(
-                int(kc).to_bytes(2, "little") + len(k).to_bytes(2, "little") + bytes(k) for kc, k in keys)
+            b = _pack_command_head(cls, keys)
             arr[i]["len"] = len(b)
             arr[i]["value"] = nonce
         elif kind == "cash_state":  # value = a dict (pack_cash_state); class_id = X500Name's id

@@ -368,6 +368,132 @@ def cash_issue_items(issuer_keys: np.ndarray, owner_keys: np.ndarray, notary_key
     return blob, items, layout
 
 
+# ---- cash payments (K22) ------------------------------------------------------------
+CASH_MOVE_COMMAND = "net.corda.contracts.asset.Cash$Commands$Move"  # Cash.kt:142
+ZERO_HASH = bytes(32)
+
+
+def merkle_root(leaf_hashes) -> bytes:
+    """MerkleTree.getMerkleTree's root (MerkleTree.kt:27-66): the hashes padded with zero hashes to a
+    power of two, parents SHA-256(left || right). The transaction id over the components' leaf hashes."""
+    sha = __import__("hashlib").sha256
+    level = list(leaf_hashes)
+    n = 1
+    while n < len(level):
+        n *= 2
+    level += [ZERO_HASH] * (n - len(level))
+    while len(level) > 1:
+        level = [sha(level[i] + level[i + 1]).digest() for i in range(0, len(level), 2)]
+    return level[0]
+
+
+def cash_payment_items(owner_keys: np.ndarray, notary_key: bytes, ntx: int, seed: int, window_frac: float = 0.25,
+                       array_list: bool = True, now_s: int = 1500000000, with_components: bool = False):
+    """The components of ntx cash PAYMENTS, deterministic from `seed`, each in availableComponents
+    order (MerkleTransaction.kt:51-62): 1 to 3 STATE_REF inputs, 1 or 2 CASH_STATE outputs (the
+    payment and the change, AnonymousParty owners), one MOVE_COMMAND signed by the distinct input
+    owners' keys (java.util.ArrayList as OnLedgerAsset.generateSpend builds it, or -- array_list
+    False -- addCommand's Arrays$ArrayList), the notary PARTY, the mustSign keys (the signers, then
+    the notary's key), TransactionType$General and, on a seeded `window_frac` of the transactions, a
+    TIME_WINDOW around now_s. Inputs spend outputs of earlier transactions of the corpus or, while
+    those last, of issues (ids derived from the seed); no output is spent twice. owner_keys [nkeys,
+    32]: the Ed25519 keys states are owned by. Ids are computed here, on the host
+    (cordahip_kryo_encode, SHA-256, merkle_root), since an input names an earlier id.
+
+    Returns a dict: blob (uint8), items (KRYO_ITEM_DTYPE, flat, `data` OFFSETS into blob),
+    tx_item_off (uint64 [ntx + 1]), ids (uint8 [ntx, 32]), signers (per transaction the owner_keys
+    indices whose owners sign, in signer order), refs (per transaction [(txhash, index)]), windows
+    (per transaction None or ((s, nano) | None, (s, nano) | None)) and, with_components, components
+    (per transaction its (kind, value, class_id) tuples in _lib.kryo_pack's form)."""
+    import hashlib
+
+    from corda_amd import _lib
+    rng = np.random.default_rng(seed)
+    ok = np.ascontiguousarray(owner_keys, np.uint8).reshape(-1, 32)
+    nkeys = len(ok)
+    keys = [ok[i].tobytes() for i in range(nkeys)]
+    ed, x5 = KRYO_IDS["ed25519_key"], KRYO_IDS["x500_name"]
+    K = _lib.KRYO_KINDS
+    bank = x500_name("Bank A", "London", "GB")
+    notary = x500_name("Notary Service", "Zurich", "CH")
+    legal = hashlib.sha256(b"https://www.big-book-of-banking-law.gov/cash-claims.html").digest()
+    issuer_key = hashlib.sha256(b"payment corpus issuer %d" % seed).digest()
+    party = notary + bytes(notary_key)
+    gen = TRANSACTION_TYPE_GENERAL.encode("utf-16-le")
+    shared = party + gen
+    # unspent outputs (txhash, index, owner): the issues' first
+    pool = [(hashlib.sha256(b"payment corpus issue %d %d" % (seed, i)).digest(), 0, int(o))
+            for i, o in enumerate(rng.integers(0, nkeys, ntx + 8))]
+    parts, pos = [shared], len(shared)
+    rows, tio, ids, signers, refs, windows, components = [], [0], [], [], [], [], []
+    party_item = ("party", (notary, bytes(notary_key), ed), x5)
+    type_item = ("kotlin_object", TRANSACTION_TYPE_GENERAL, 0)
+
+    def put(kind, class_id, value, b):
+        nonlocal pos
+        rows.append((kind, class_id, value, pos, len(b)))
+        parts.append(b)
+        pos += len(b)
+
+    done = 0
+    while done < ntx:
+        wave = min(ntx - done, max(1, len(pool) // 4))  # every input of a wave is unspent before it
+        first_row, outs = len(rows), []
+        for _ in range(wave):
+            k = int(rng.integers(1, 4))
+            ins = [pool.pop(int(rng.integers(0, len(pool)))) for _ in range(k)]
+            sg = list(dict.fromkeys(o for _, _, o in ins))  # the distinct owners, in input order
+            comps = [("state_ref", _lib.pack_state_ref(h, ix), 0) for h, ix, _ in ins]
+            for c in comps:
+                put(K["state_ref"], 0, 0, c[1])
+            new_owners = [int(x) for x in rng.integers(0, nkeys, int(rng.integers(1, 3)))]
+            for o in new_owners:
+                d = {"issuer": (bank, issuer_key, ed), "reference": b"\x01", "owner": (b"", keys[o], ed),
+                     "notary": (notary, bytes(notary_key), ed), "currency": "USD", "digits": 2, "legal_ref": legal,
+                     "encumbrance": None, "quantity": int(rng.integers(1, 10**9))}
+                put(K["cash_state"], x5, d["quantity"], _lib.pack_cash_state(d))
+                comps.append(("cash_state", d, x5))
+            move = _lib.pack_move_command(CASH_MOVE_COMMAND, [(ed, keys[o]) for o in sg], None, array_list)
+            put(K["move_command"], KRYO_IDS["arrays_as_list"], 0, move)
+            rows.append((K["party"], x5, ed, 0, len(party)))
+            comps += [("move_command", move, KRYO_IDS["arrays_as_list"]), party_item]
+            for key in [keys[o] for o in sg] + [bytes(notary_key)]:
+                put(K["ed25519_key"], ed, 0, key)
+                comps.append(("ed25519_key", key, ed))
+            rows.append((K["kotlin_object"], 0, 0, len(party), len(gen) // 2))
+            comps.append(type_item)
+            w = None
+            if rng.random() < window_frac:
+                w = ((now_s - 30, 0), (now_s + 30, int(rng.integers(0, 10**9))))
+                w = (w[0] if rng.random() < 0.8 else None, w[1])
+                put(K["time_window"], 0, 0, _lib.pack_time_window(*w))
+                comps.append(("time_window", _lib.pack_time_window(*w), 0))
+            if with_components:
+                components.append(comps)
+            tio.append(len(rows))
+            signers.append(sg)
+            refs.append([(h, ix) for h, ix, _ in ins])
+            windows.append(w)
+            outs.append(new_owners)
+        # the wave's ids: its leaves through the host encoder, then the Merkle roots
+        blob_w = np.frombuffer(b"".join(parts), np.uint8)
+        arr = np.array([(k_, c, v, d, n) for k_, c, v, d, n in rows[first_row:]], _lib.KRYO_ITEM_DTYPE)
+        arr["data"] += np.uint64(blob_w.ctypes.data)
+        leaves, off = _lib.kryo_encode_array(arr)
+        lb = leaves.tobytes()
+        for j in range(wave):
+            a, b = tio[done + j] - first_row, tio[done + j + 1] - first_row
+            txid = merkle_root([hashlib.sha256(lb[int(off[i]):int(off[i + 1])]).digest() for i in range(a, b)])
+            ids.append(txid)
+            pool.extend((txid, ix, o) for ix, o in enumerate(outs[j]))
+        done += wave
+    items = np.array(rows, _lib.KRYO_ITEM_DTYPE) if rows else np.zeros(0, _lib.KRYO_ITEM_DTYPE)
+    return {"blob": np.frombuffer(b"".join(parts), np.uint8).copy(), "items": items,
+            "tx_item_off": np.asarray(tio, np.uint64),
+            "ids": np.frombuffer(b"".join(ids), np.uint8).reshape(ntx, 32).copy() if ntx else np.zeros((0, 32), np.uint8),
+            "signers": signers, "refs": refs, "windows": windows, "components": components}
+
+
 def make_cash_issue_leaves(issuer_keys: np.ndarray, owner_keys: np.ndarray, notary_key: bytes,
                            quantities: np.ndarray, nonces: np.ndarray, threads: int = 8):
     """CSR leaf bytes of the ntx cash-issue transactions of cash_issue_items, encoded on the host

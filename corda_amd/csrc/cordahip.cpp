@@ -1577,6 +1577,30 @@ int cordahip_tx_cover_device(cordahip_ctx* ctx, int device, uint64_t ntx, void* 
   });
 }
 
+int cordahip_txcomp_inputs_device(cordahip_ctx* ctx, int device, const void* d_items, uint64_t n_items,
+                                  const void* d_payload, uint64_t payload_len, const void* d_tx_item_off, uint64_t ntx,
+                                  const void* d_tx_status, void* d_refs, uint64_t ref_cap, void* d_tx_ref_off,
+                                  void* d_tw_from, void* d_tw_until, void* d_gate, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || n_items >= 0x7fffffffull) return CORDAHIP_ERR_INVALID_ARG;
+  if (ntx && (!d_tx_item_off || !d_tx_ref_off || !d_tw_from || !d_tw_until || !d_gate || (n_items && !d_items) ||
+              (ref_cap && !d_refs) || (payload_len && !d_payload)))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_tx_item_off) | reinterpret_cast<uintptr_t>(d_tx_ref_off) |
+       reinterpret_cast<uintptr_t>(d_tw_from) | reinterpret_cast<uintptr_t>(d_tw_until) |
+       reinterpret_cast<uintptr_t>(d_items)) & 7 ||
+      reinterpret_cast<uintptr_t>(d_refs) & 3)
+    return CORDAHIP_ERR_INVALID_ARG;
+  return device_call(*d, hip_stream, [&](hipStream_t s) {
+    return launch_txcomp_inputs(static_cast<const cordahip_kryo_item*>(d_items), n_items,
+                                static_cast<const uint8_t*>(d_payload), payload_len,
+                                static_cast<const uint64_t*>(d_tx_item_off), ntx,
+                                static_cast<const uint8_t*>(d_tx_status), static_cast<uint32_t*>(d_refs), ref_cap,
+                                static_cast<uint64_t*>(d_tx_ref_off), static_cast<int64_t*>(d_tw_from),
+                                static_cast<int64_t*>(d_tw_until), static_cast<uint8_t*>(d_gate), s);
+  });
+}
+
 double cordahip_last_kernel_ms(cordahip_ctx* ctx, int device) {
   Device* d = dev_at(ctx, device);
   if (!d) return -1.0;

@@ -737,48 +737,66 @@ KRYO_HD inline bool cash_state(O& o, const cordahip_kryo_item& it) {
 // the command class's binary name, u8 key count, per key u16 LE registration id,
 // u16 LE length, the key bytes; class_id = the Arrays$ArrayList registration
 // (ArraysAsListSerializer); value = the nonce.
-template <class O>
-KRYO_HD inline bool issue_command(O& o, const cordahip_kryo_item& it) {
-  if (!it.data || it.len < 2) return false;
-  Reader r(it.data, it.data + it.len);
-  const uint32_t nlen = r.u8();
-  const uint8_t* nm = r.span(nlen);
-  const uint32_t nkeys = r.u8();
-  if (!r.ok || nlen < 2 || nkeys == 0) return false;  // Command: require(signers.isNotEmpty())
-  const uint8_t* keys = r.p;  // validated here, read again while writing
-  for (uint32_t i = 0; i < nkeys; i++) {
+// The head of a command payload (ISSUE_COMMAND, MOVE_COMMAND): the class name and
+// the signer keys, validated; r is left after the last key.
+struct CommandHead {
+  const uint8_t* nm = nullptr;
+  uint32_t nlen = 0;
+  const uint8_t* keys = nullptr;  // validated by command_head, read again while writing
+  uint32_t nkeys = 0;
+};
+KRYO_HD inline bool command_head(Reader& r, CommandHead& h) {
+  h.nlen = r.u8();
+  h.nm = r.span(h.nlen);
+  h.nkeys = r.u8();
+  if (!r.ok || h.nlen < 2 || h.nkeys == 0) return false;  // Command: require(signers.isNotEmpty())
+  h.keys = r.p;
+  for (uint32_t i = 0; i < h.nkeys; i++) {
     r.u16();
     const uint32_t kl = r.u16();
     if (!r.span(kl) || kl == 0) return false;
   }
-  if (!r.ok || r.p != r.end) return false;
-  const Sv name((const char*)nm, nlen);
-  uint32_t cut = nlen;  // the simple name follows the last '$' or '.'
-  while (cut > 0 && nm[cut - 1] != '$' && nm[cut - 1] != '.') cut--;
-  // "<Simple>.nonce" (EXTENDED field name) in a small local buffer
-  char field[264];
-  const uint32_t sl = nlen - cut;
-  if (sl + 6 > sizeof(field)) return false;
-  for (uint32_t i = 0; i < sl; i++) field[i] = (char)nm[cut + i];
-  const char* suffix = ".nonce";
-  for (uint32_t i = 0; i < 6; i++) field[sl + i] = suffix[i];
-  const Sv simple(field, sl + 6);
+  return r.ok;
+}
+// "<Simple><suffix>" (EXTENDED field name): the simple name follows the last '$' or '.'
+constexpr uint32_t kCommandFieldBytes = 272;
+KRYO_HD inline uint32_t command_field(const CommandHead& h, const char* suffix, uint32_t ns, char* field) {
+  uint32_t cut = h.nlen;
+  while (cut > 0 && h.nm[cut - 1] != '$' && h.nm[cut - 1] != '.') cut--;
+  const uint32_t sl = h.nlen - cut;
+  for (uint32_t i = 0; i < sl; i++) field[i] = (char)h.nm[cut + i];
+  for (uint32_t i = 0; i < ns; i++) field[sl + i] = suffix[i];
+  return sl + ns;
+}
+// Command.signers as java.util.Arrays$ArrayList -- ArraysAsListSerializer
+// (kryo-serializers 0.41): writeInt(length, true), writeClass(component type) --
+// java.security.PublicKey, implicit NAME -- then writeClassAndObject per element
+template <class O>
+KRYO_HD inline void signers_as_list(O& o, Graph& g, uint32_t k, uint32_t list_class, const CommandHead& h,
+                                    const uint8_t* end) {
+  Graph::class_id(o, k, list_class);
+  o.varint(k, h.nkeys);
+  g.class_name(o, k, "java.security.PublicKey");
+  Reader kr(h.keys, end);
+  for (uint32_t i = 0; i < h.nkeys; i++) {
+    const uint32_t kc = kr.u16(), kl = kr.u16();
+    key_value(o, k, kc, kr.span(kl), kl);
+  }
+}
+
+template <class O>
+KRYO_HD inline bool issue_command(O& o, const cordahip_kryo_item& it) {
+  if (!it.data || it.len < 2) return false;
+  Reader r(it.data, it.data + it.len);
+  CommandHead h;
+  if (!command_head(r, h) || r.p != r.end) return false;
+  const Sv name((const char*)h.nm, h.nlen);
+  char field[kCommandFieldBytes];
+  const Sv simple(field, command_field(h, ".nonce", 6, field));
   Graph g;
   g.class_name(o, 0, "net.corda.core.contracts.Command");
   g.cfs(o, 0, "net.corda.core.contracts.Command", {"Command.signers", "Command.value"},
-        [&](uint32_t k) {
-          // ArraysAsListSerializer (kryo-serializers 0.41): writeInt(length, true),
-          // writeClass(component type) -- java.security.PublicKey, implicit NAME --
-          // then writeClassAndObject per element
-          Graph::class_id(o, k, it.class_id);
-          o.varint(k, nkeys);
-          g.class_name(o, k, "java.security.PublicKey");
-          Reader kr(keys, it.data + it.len);
-          for (uint32_t i = 0; i < nkeys; i++) {
-            const uint32_t kc = kr.u16(), kl = kr.u16();
-            key_value(o, k, kc, kr.span(kl), kl);
-          }
-        },
+        [&](uint32_t k) { signers_as_list(o, g, k, it.class_id, h, it.data + it.len); },
         [&](uint32_t k) {
           // the command data: implicit NAME, its own CompatibleFieldSerializer (a
           // primitive long nonce: writeVarLong(v, false)) -- a nested OutputChunked
@@ -879,6 +897,71 @@ KRYO_HD inline bool time_window(O& o, const cordahip_kryo_item& it) {
   return true;
 }
 
+// ---- a payment's command and an attachment id (K22) ------------------------------------
+// PARITY UNPINNED, like the kinds above.
+//
+// Command(value = <a Move data class>(contractHash: SecureHash?), signers)
+// (Structures.kt:285; Cash.kt:142, CommodityContract.kt:125, Obligation.kt:348,
+// CommercialPaper.kt:190). The outer object and Command.value's class are written as
+// issue_command writes them; the Move class's one field "<Simple>.contractHash" is
+// declared SecureHash? (not final): null is writeClass(null), one byte 00; a hash is the
+// class SecureHash$SHA256 by name, then opaque_bytes' body, as StateRef.txhash.
+// Command.signers is either addCommand's Arrays$ArrayList (signers_as_list) or, from
+// OnLedgerAsset.generateSpend (OnLedgerAsset.kt:93,121: gathered.map { }), a
+// java.util.ArrayList: unregistered, so by NAME through Kryo's CollectionSerializer --
+// varint(size), then class and object per element, as Cash.State.exitKeys above.
+// data = issue_command's layout (name, keys), then u8 flags (bit 0: contractHash
+// present, bit 1: the signers are a java.util.ArrayList), then the 32 hash bytes iff bit
+// 0; class_id = Arrays$ArrayList's registration (ignored with bit 1); value unused.
+constexpr uint32_t kMoveHasHash = 1, kMoveArrayList = 2;
+template <class O>
+KRYO_HD inline bool move_command(O& o, const cordahip_kryo_item& it) {
+  if (!it.data || it.len < 2) return false;
+  Reader r(it.data, it.data + it.len);
+  CommandHead h;
+  if (!command_head(r, h)) return false;
+  const uint32_t flags = r.u8();
+  const uint8_t* hash = (flags & kMoveHasHash) ? r.span(32) : nullptr;
+  if (!r.ok || r.p != r.end || (flags & ~(kMoveHasHash | kMoveArrayList))) return false;
+  const Sv name((const char*)h.nm, h.nlen);
+  char field[kCommandFieldBytes];
+  const Sv simple(field, command_field(h, ".contractHash", 13, field));
+  Graph g;
+  g.class_name(o, 0, "net.corda.core.contracts.Command");
+  g.cfs(o, 0, "net.corda.core.contracts.Command", {"Command.signers", "Command.value"},
+        [&](uint32_t k) {
+          if (!(flags & kMoveArrayList)) {
+            signers_as_list(o, g, k, it.class_id, h, it.data + it.len);
+            return;
+          }
+          g.class_name(o, k, "java.util.ArrayList");
+          o.varint(k, h.nkeys);
+          Reader kr(h.keys, it.data + it.len);
+          for (uint32_t i = 0; i < h.nkeys; i++) {
+            const uint32_t kc = kr.u16(), kl = kr.u16();
+            key_value(o, k, kc, kr.span(kl), kl);
+          }
+        },
+        [&](uint32_t k) {
+          g.class_name(o, k, name);
+          g.cfs(o, k, name, {simple}, [&](uint32_t c) {
+            if (hash) opaque_bytes(o, g, c, "net.corda.core.crypto.SecureHash$SHA256", hash, 32);
+            else o.byte(c, 0);  // writeClass(null)
+          });
+        });
+  return true;
+}
+
+// An attachment id as a component (WireTransaction.attachments: List<SecureHash>):
+// SecureHash$SHA256 by name, then OpaqueBytes.bytes. data = the 32 bytes.
+template <class O>
+KRYO_HD inline bool secure_hash(O& o, const cordahip_kryo_item& it) {
+  if (!it.data || it.len != 32) return false;
+  Graph g;
+  opaque_bytes(o, g, 0, "net.corda.core.crypto.SecureHash$SHA256", it.data, 32);
+  return true;
+}
+
 // One component's leaf preimage through o (RAW: the bytes as given); false for
 // an unknown kind or a missing / malformed payload.
 template <class O>
@@ -946,6 +1029,8 @@ KRYO_HD inline bool encode_leaf(O& o, const cordahip_kryo_item& it) {
     case CORDAHIP_KRYO_CASH_STATE: ok = it.data && cash_state(o, it); break;
     case CORDAHIP_KRYO_STATE_REF: ok = state_ref(o, it); break;
     case CORDAHIP_KRYO_TIME_WINDOW: ok = time_window(o, it); break;
+    case CORDAHIP_KRYO_MOVE_COMMAND: ok = move_command(o, it); break;
+    case CORDAHIP_KRYO_SECURE_HASH: ok = secure_hash(o, it); break;
     default: return false;
   }
   return ok && !o.failed;

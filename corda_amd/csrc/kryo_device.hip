@@ -49,6 +49,7 @@
 #include "kryo_template.hpp"
 #include "notary_rows.hpp"
 #include "sha2_device.hpp"
+#include "txcomp_inputs_core.hpp"
 
 namespace cordahip {
 
@@ -1278,15 +1279,7 @@ __global__ void __launch_bounds__(1024) notary_prep_kernel(NotaryRows R, uint64_
   }
 }
 
-// an Instant as cordahip_commit_batch's bounds: ns since the epoch, saturated at +-2^62
-// (|s| <= 4611686019: the product and the sum stay inside int64)
-__device__ inline int64_t instant_ns(int64_t s, int32_t nano) {
-  const int64_t lim = (int64_t)1 << 62;
-  if (s > 4611686018ll) return lim;
-  if (s < -4611686019ll) return -lim;
-  const int64_t v = s * 1000000000ll + nano;
-  return v > lim ? lim : v < -lim ? -lim : v;
-}
+using txin::instant_ns;  // an Instant as cordahip_commit_batch's bounds (shared with K22)
 
 __global__ void __launch_bounds__(256) notary_leaf_kernel(NotaryRows R, const uint64_t* __restrict__ tx_leaf_off,
                                                           uint32_t* __restrict__ hashes, uint32_t* __restrict__ leaf_hash,

@@ -165,6 +165,29 @@ KRYO_HD inline bool shape_walk(const cordahip_kryo_item& it, V& v) {
       }
       return true;
     }
+    case CORDAHIP_KRYO_MOVE_COMMAND: {  // the name, each key's class and length, the flags; the key
+                                        // bytes and the hash are content
+      if (!it.data || it.len < 2 || it.len >= kMaxPayloadOff) return false;
+      Reader r(it.data, it.data + it.len);
+      const uint32_t nlen = r.u8();
+      const uint8_t* nm = r.span(nlen);
+      const uint32_t nkeys = r.u8();
+      if (!r.ok || nkeys > 12) return false;
+      v.word(nlen);
+      v.span(nm, nlen);
+      v.word(nkeys);
+      for (uint32_t i = 0; i < nkeys && r.ok; i++) {
+        v.word(r.u16());
+        const uint32_t kl = r.u16();
+        v.word(kl);
+        r.span(kl);
+      }
+      const uint32_t flags = r.u8();
+      v.word(flags);
+      if (flags & kMoveHasHash) r.span(32);
+      return r.ok && r.p == r.end;
+    }
+    case CORDAHIP_KRYO_SECURE_HASH: return it.data && it.len == 32;  // the kind alone
     default: return false;  // RAW (copied directly) and unknown kinds
   }
 }
@@ -329,6 +352,8 @@ KRYO_HD inline bool rejected_outright(const cordahip_kryo_item& it) {
     case CORDAHIP_KRYO_CASH_STATE: return !it.data;
     case CORDAHIP_KRYO_STATE_REF: return !it.data || it.len != kStateRefLen;
     case CORDAHIP_KRYO_TIME_WINDOW: return !time_window_row(it).ok;  // every invalid row: it has no shape
+    case CORDAHIP_KRYO_MOVE_COMMAND: return !it.data || it.len < 2;
+    case CORDAHIP_KRYO_SECURE_HASH: return !it.data || it.len != 32;
     default: return true;
   }
 }

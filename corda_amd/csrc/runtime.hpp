@@ -191,6 +191,12 @@ hipError_t launch_notary_gate(const uint8_t* verify, const uint8_t* caller_gate,
                               hipStream_t s);
 hipError_t launch_notary_status(const uint8_t* verify, const uint8_t* commit, uint8_t* status, uint64_t ntx,
                                 hipStream_t s);
+// K22 (txcomp_inputs.hip): a component batch's STATE_REF items as commit rows and its
+// TIME_WINDOW items as window bounds (txcomp_inputs_core.hpp); tx_status may be nullptr
+hipError_t launch_txcomp_inputs(const cordahip_kryo_item* d_items, uint64_t n_items, const uint8_t* d_payload,
+                                uint64_t payload_len, const uint64_t* d_tx_item_off, uint64_t ntx,
+                                const uint8_t* d_tx_status, uint32_t* d_refs, uint64_t ref_cap, uint64_t* d_tx_ref_off,
+                                int64_t* d_tw_from, int64_t* d_tw_until, uint8_t* d_gate, hipStream_t s);
 // K10 (tx.hip): up = 2 * nleaves hashes, has = 3 * nleaves bytes of workspace (pmt_core.hpp)
 hipError_t launch_pmt_build(const uint32_t* hashes, const uint64_t* tx_leaf_off, uint64_t ntx, const uint8_t* include,
                             const uint64_t* tx_tok_off, uint64_t ntok, uint32_t* up, uint8_t* has, uint8_t* txid,

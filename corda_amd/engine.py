@@ -783,6 +783,21 @@ class Engine:
             keys.data_ptr(), sigs.data_ptr(), keys.shape[0], txid.data_ptr(), tx_status.data_ptr(),
             first_bad.data_ptr(), sig_status.data_ptr(), s), "cordahip_signed_txcomp_verify_ed25519_device")
 
+    def txcomp_inputs_device(self, items, n_items: int, payload, tx_item_off, refs, tx_ref_off, tw_from, tw_until,
+                             gate, tx_status=None, ref_cap: Optional[int] = None, device: int = 0, stream=None):
+        """cordahip_txcomp_inputs_device (K22): the STATE_REF and TIME_WINDOW items of the component
+        batch signed_txcomp_verify_ed25519_device takes (items, n_items, payload, tx_item_off) as the
+        device rows commit_inputs_device takes. Outputs: refs uint8 [ref_cap, 36] (ref_cap: its rows
+        unless given), tx_ref_off int64 [ntx + 1], tw_from / tw_until int64 [ntx], gate uint8 [ntx]
+        (tx_status -- uint8 [ntx] or None, typically the verify call's -- where that is nonzero, else
+        TX_BAD_COMPONENT for a transaction whose items or range were flagged, else 0)."""
+        s = stream.cuda_stream if stream is not None else 0
+        p = lambda x: x.data_ptr() if x is not None and x.numel() else None  # noqa: E731
+        check(lib().cordahip_txcomp_inputs_device(
+            self._ctx, device, p(items), n_items, p(payload), payload.numel(), p(tx_item_off),
+            tx_item_off.shape[0] - 1, p(tx_status), p(refs), refs.shape[0] if ref_cap is None else ref_cap,
+            p(tx_ref_off), p(tw_from), p(tw_until), p(gate), s), "cordahip_txcomp_inputs_device")
+
     def device_mem(self, device: int = 0):
         """cordahip_device_mem: (bytes the library holds on the device's GPU, their peak, the budget)"""
         a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()

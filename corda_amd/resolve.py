@@ -480,6 +480,111 @@ def notarise_tearoffs_persisted(engine, log_id: int, tearoffs, callers, key_id: 
     return answers, rows
 
 
+def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_id: int, now: int, tolerance: int,
+                          device: int = 0, stream=None, detail: Optional[dict] = None):
+    """What a VALIDATING notary (ValidatingNotaryFlow) or any node that commits what it resolved does
+    with full transactions, on torch device tensors and ONE stream, with no device-to-host copy
+    before the final download (K22):
+      1. Engine.signed_txcomp_verify_ed25519_device  components -> ids -> signature verdicts
+      2. Engine.txcomp_inputs_device                 the STATE_REF / TIME_WINDOW items of the same
+                                                     device batch -> refs, offsets, windows, gate
+      3. Engine.commit_inputs_device                 txid = the ids of step 1, gated
+      4. Engine.ed25519_sign_keyed_device            over the ids, gated by the commit status
+    so the inputs that are committed are the components whose hashes made the id that was signed.
+    Ed25519 only, like the device-resident signed-tx calls it stands on: every transaction signature
+    and the notary's key `key_id`. Contract verification and required-signer coverage
+    (Engine.tx_cover_device between steps 1 and 2) are the caller's.
+
+    stxs_as_components[t] = (components, sigs): components as (kind, value, class_id) tuples
+    (_lib.kryo_pack's form, availableComponents order), sigs = [(key 32 bytes, signature 64 bytes)].
+    callers[t]: the requesting party's id; now / tolerance in ns; `device` is the log's.
+
+    Returns (answers, committed_rows) in notarise_tearoffs's shape: answers[t] the notary's signature
+    over the id, or NotaryError -- TransactionInvalid (tx_id None where the id could not be
+    computed) for a transaction whose signatures or components do not verify, TimeWindowInvalid,
+    Conflict with its state history. detail, if given, receives the raw arrays: ids, status (the
+    verify status where that is not OK, else the commit's), committed, refs, tx_ref_off."""
+    import numpy as np
+    import torch
+
+    from corda_amd import _lib
+    n = len(stxs_as_components)
+    assert len(callers) == n
+    if n == 0:
+        return [], []
+    dev = torch.device("cuda", device)
+    s = stream if stream is not None else torch.cuda.Stream(dev)
+    blob, items, has = _lib.kryo_pack([c for comps, _ in stxs_as_components for c in comps])
+    items = items.copy()
+    items["data"] = np.where(has, items["data"], 0)  # offsets into the payload
+    tio = np.zeros(n + 1, np.int64)
+    tio[1:] = np.cumsum([len(comps) for comps, _ in stxs_as_components])
+    tso = np.zeros(n + 1, np.int64)
+    tso[1:] = np.cumsum([len(sg) for _, sg in stxs_as_components])
+    flat = [x for _, sg in stxs_as_components for x in sg]
+    assert all(len(k) == 32 and len(g) == 64 for k, g in flat), "Ed25519 keys and signatures only"
+    keys = np.frombuffer(b"".join(bytes(k) for k, _ in flat) or bytes(32), np.uint8).reshape(-1, 32)
+    sigs = np.frombuffer(b"".join(bytes(g) for _, g in flat) or bytes(64), np.uint8).reshape(-1, 64)
+    nsig, n_items = len(flat), len(items)
+    ref_cap = int((items["kind"] == _lib.KRYO_KINDS["state_ref"]).sum())
+    with torch.cuda.stream(s):
+        up = lambda a: torch.from_numpy(np.array(a, copy=True)).to(dev)  # noqa: E731
+        z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        d_items = up(items.view(np.uint8).reshape(-1, _lib.KRYO_ITEM_DTYPE.itemsize)) if n_items else z(1, 32)
+        d_blob, d_tio, d_tso = up(blob), up(tio), up(tso)
+        d_keys, d_sigs = up(keys)[:max(nsig, 1)], up(sigs)[:max(nsig, 1)]
+        d_caller = up(np.asarray(callers, np.int32))
+        d_key_id = torch.full((n,), key_id, dtype=torch.int32, device=dev)
+        txid, v_status, first_bad, sig_status = z(n, 32), z(n), z(n, dt=torch.int64), z(max(nsig, 1))
+        refs, tx_ref_off = z(max(ref_cap, 1), 36), z(n + 1, dt=torch.int64)
+        tw_from, tw_until, gate = z(n, dt=torch.int64), z(n, dt=torch.int64), z(n)
+        c_status, committed = z(n), z(n)
+        ref_state, ref_by = z(max(ref_cap, 1)), z(max(ref_cap, 1), 40)
+        n_sigs, s_status = z(n, 64), z(n)
+        engine.signed_txcomp_verify_ed25519_device(d_items, n_items, d_blob, d_tio, d_tso, d_keys[:nsig], d_sigs[:nsig],
+                                                   txid, v_status, first_bad, sig_status, device=device, stream=s)
+        engine.txcomp_inputs_device(d_items, n_items, d_blob, d_tio, refs, tx_ref_off, tw_from, tw_until, gate,
+                                    tx_status=v_status, ref_cap=ref_cap, device=device, stream=s)
+        engine.commit_inputs_device(log_id, txid, d_caller, refs[:ref_cap], tx_ref_off, c_status, committed,
+                                    ref_state, ref_by, tw_from, tw_until, now, tolerance, gate=gate, stream=s)
+        engine.ed25519_sign_keyed_device(d_key_id, txid, n_sigs, s_status, gate=c_status, device=device, stream=s)
+        status = torch.where(gate != 0, gate, c_status)
+        # the one download
+        out = [x.cpu().numpy() for x in (txid, status, committed, refs, tx_ref_off, ref_by, ref_state, n_sigs,
+                                         s_status, v_status)]
+    ids_a, status_a, committed_a, refs_a, off_a, by_a, state_a, sig_a, sst_a, verify_a = out
+    if detail is not None:
+        detail.update(ids=ids_a, status=status_a, committed=committed_a, refs=refs_a[:ref_cap], tx_ref_off=off_a,
+                      ref_state=state_a[:ref_cap], verify_status=verify_a)
+    answers, rows = [], []
+    for t in range(n):
+        st, txid_t = int(status_a[t]), ids_a[t].tobytes()
+        mine = [(refs_a[i, :32].tobytes(), int.from_bytes(refs_a[i, 32:].tobytes(), "little"))
+                for i in range(int(off_a[t]), int(off_a[t + 1]))]
+        if st not in _COMMIT_STATUSES or st == 18:
+            answers.append(NotaryError("TransactionInvalid", txid_t if int(verify_a[t]) in (OK, BAD_SIG) else None))
+        elif st == _COMMIT_TIME_WINDOW_INVALID:
+            answers.append(NotaryError("TimeWindowInvalid", txid_t))
+        elif st == _COMMIT_CONFLICT:
+            hist = {}
+            for k, i in enumerate(range(int(off_a[t]), int(off_a[t + 1]))):
+                if int(state_a[i]):
+                    b = by_a[i]
+                    hist.setdefault(mine[k], (b[:32].tobytes(), int.from_bytes(b[32:36].tobytes(), "little"),
+                                              int.from_bytes(b[36:40].tobytes(), "little")))
+            answers.append(NotaryError("Conflict", txid_t, hist))
+        elif int(sst_a[t]) == _SIGN_UNKNOWN_KEY:
+            raise NoSuchElementException("no registered key %d" % key_id)
+        else:
+            answers.append(sig_a[t].tobytes())
+        if committed_a[t]:
+            last = {}
+            for i, r in enumerate(mine):
+                last[r] = (txid_t, i, int(callers[t]))
+            rows.extend(last.items())
+    return answers, rows
+
+
 def validate_notary_signatures(engine, key_id: int, ids: Sequence[bytes], sigs: Sequence[bytes],
                                ecdsa: bool = False):
     """What a notary client does with the notary's answers (NotaryFlow.Client.call,

@@ -1214,6 +1214,49 @@ int cordahip_filtered_tx_build_device(cordahip_ctx* ctx, int device, const void*
  * rules by the test model, not taken from a JVM. */
 #define CORDAHIP_KRYO_STATE_REF 16
 #define CORDAHIP_KRYO_TIME_WINDOW 17
+/* What a payment adds to a cash issue's components (K22): its command, and an
+ * attachment id.
+ *   MOVE_COMMAND   net.corda.core.contracts.Command(value, signers)
+ *                  (Structures.kt:285) whose value is a Move data class with the one
+ *                  field contractHash: SecureHash? (Cash.kt:142,
+ *                  CommodityContract.kt:125, Obligation.kt:348,
+ *                  CommercialPaper.kt:190). Command and the Move class by NAME, each
+ *                  through CompatibleFieldSerializer, as ISSUE_COMMAND; the Move
+ *                  class's field is "<Simple>.contractHash", <Simple> the class name
+ *                  after its last '$' or '.'. The field is declared SecureHash? and not
+ *                  final: null is writeClass(null), one byte 00; a hash is the class
+ *                  net.corda.core.crypto.SecureHash$SHA256 by NAME and then
+ *                  OpaqueBytes.bytes, as STATE_REF's txhash. Command.signers comes in
+ *                  two list forms: TransactionBuilder.addCommand(data, vararg keys)
+ *                  gives java.util.Arrays$ArrayList (ArraysAsListSerializer, as
+ *                  ISSUE_COMMAND: class_id, length, component class
+ *                  java.security.PublicKey by NAME, the elements);
+ *                  OnLedgerAsset.generateSpend (OnLedgerAsset.kt:93,121) passes
+ *                  gathered.map { }, a java.util.ArrayList, which is unregistered
+ *                  (DefaultKryoCustomizer.kt): by NAME through Kryo's
+ *                  CollectionSerializer, varint(size) then class and object per
+ *                  element, as CASH_STATE's exitKeys. data = ISSUE_COMMAND's layout
+ *                  (u8 name length, the binary class name, u8 key count, per key u16 LE
+ *                  registration id, u16 LE length, key bytes), then u8 flags (bit 0:
+ *                  contractHash present, bit 1: the signers are a java.util.ArrayList,
+ *                  else Arrays$ArrayList), then the 32 hash bytes iff bit 0. class_id =
+ *                  Arrays$ArrayList's registration id, ignored with bit 1; value
+ *                  unused. Invalid: name length < 2, no key, a zero-length key,
+ *                  flags & ~3, a payload that does not end where the layout ends. With
+ *                  one to three Ed25519 signers a Cash move is 199 / 233 / 267 bytes
+ *                  (java.util.ArrayList, no hash) up to 300 / 334 / 369
+ *                  (Arrays$ArrayList, with the hash): 4 to 6 SHA-256 blocks (the table
+ *                  is in DESIGN §4 K22). Cash.Commands.Exit and the non-cash commands
+ *                  are not covered.
+ *   SECURE_HASH    an attachment id as a component (WireTransaction.attachments:
+ *                  List<SecureHash>): SecureHash$SHA256 by NAME (name id 0), then
+ *                  OpaqueBytes.bytes. data = the 32 bytes, len = 32, anything else is
+ *                  invalid; class_id and value unused. 102 bytes.
+ * Both are PARITY UNPINNED like every composite kind above; the vectors in
+ * tests/golden/payment_leaf_vectors.json are derived from the same published rules
+ * by the test model (tests/kryo_payment_model.py), not taken from a JVM. */
+#define CORDAHIP_KRYO_MOVE_COMMAND 18
+#define CORDAHIP_KRYO_SECURE_HASH 19
 typedef struct {
   uint32_t kind;       /* CORDAHIP_KRYO_* */
   uint32_t class_id;   /* Kryo registration id (ED25519_KEY, PUBLIC_KEY) */
@@ -1664,6 +1707,53 @@ int cordahip_notary_tearoff_commit_submit(cordahip_ctx* ctx, uint32_t log_id,
                                           const cordahip_notary_tearoff_batch* batch, const uint32_t* caller,
                                           int64_t now_ns, int64_t tolerance_ns, const uint8_t* gate, uint8_t* committed,
                                           uint8_t* ref_state, cordahip_consuming_tx* ref_by, uint64_t* ticket);
+
+/* ---- a full transaction's inputs and time window as commit rows (K22) ---------------- *
+ * A validating notary (ValidatingNotaryFlow) and any node that commits what it
+ * resolved see the whole transaction: its inputs are the STATE_REF items, and its window
+ * the TIME_WINDOW item, of the very component batch whose id and signatures
+ * cordahip_signed_txcomp_verify_ed25519_device has just computed and checked. This call
+ * takes them out of those items in HBM as the rows cordahip_commit_inputs_device takes,
+ * so the refs that are committed are the refs that were hashed into the id, and nothing
+ * is read back to the host in between:
+ *   components -> ids -> signatures -> (coverage) -> inputs and window -> commit -> sign
+ * d_items, d_payload and d_tx_item_off are exactly what
+ * cordahip_signed_txcomp_verify_ed25519_device takes (items[i].data OFFSETS into
+ * d_payload). Per transaction t, its item range cut to n_items (the offsets are
+ * untrusted; a reversed range is empty):
+ *   inputs  its STATE_REF items in item order, copied as 36-byte cordahip_state_ref
+ *           rows to d_refs at d_tx_ref_off[t]. d_tx_ref_off[t] is the running count of
+ *           refs clamped to ref_cap, d_tx_ref_off[ntx] the clamped total. A STATE_REF
+ *           item whose len != 36 or whose payload runs past payload_len flags the
+ *           transaction.
+ *   window  no TIME_WINDOW item: both sides INT64_MIN. Exactly one valid item (as
+ *           CORDAHIP_KRYO_TIME_WINDOW defines valid): each present side as
+ *           cordahip_commit_batch takes it, seconds * 10^9 + nano saturated at +-2^62,
+ *           INT64_MIN for an absent side. Two or more TIME_WINDOW items, an invalid
+ *           row or a payload out of range flag the transaction.
+ *   A transaction flagged by its items has an empty ref range and both window sides
+ *   INT64_MIN. A transaction whose unclamped ref range ends beyond ref_cap is flagged
+ *   too and its range is cut at ref_cap; nothing is written at or past d_refs[ref_cap].
+ *   gate    d_gate[t] = d_tx_status[t] if that is given and nonzero, else
+ *           CORDAHIP_TX_BAD_COMPONENT if the transaction is flagged, else 0. It goes in
+ *           as cordahip_commit_batch.gate. cordahip_tx_cover_device rewrites
+ *           d_tx_status in place: run before this call it brings required-signer
+ *           coverage into the gate.
+ * Items of every other kind are skipped; a transaction with no STATE_REF item (an
+ * issue) has an empty range, which cordahip_commit_inputs commits as a transaction
+ * with no inputs. d_refs is 4-byte aligned, the 64-bit arrays 8-byte aligned; d_gate is
+ * an array of its own (not d_tx_status).
+ * CORDAHIP_ERR_INVALID_ARG before any enqueue: NULL ctx, unknown device, a NULL or
+ * misaligned output or NULL d_tx_item_off with ntx > 0, NULL d_items with n_items > 0,
+ * NULL d_refs with ref_cap > 0, n_items >= 2^31 - 1. Stream-ordered on hip_stream;
+ * returns once enqueued; ntx == 0 is a successful no-op. No device scratch. */
+int cordahip_txcomp_inputs_device(cordahip_ctx* ctx, int device, const void* d_items, uint64_t n_items,
+                                  const void* d_payload, uint64_t payload_len, const void* d_tx_item_off, uint64_t ntx,
+                                  const void* d_tx_status /* uint8[ntx] or NULL */,
+                                  void* d_refs, uint64_t ref_cap /* cordahip_state_ref[ref_cap] out */,
+                                  void* d_tx_ref_off /* uint64[ntx+1] out */,
+                                  void* d_tw_from, void* d_tw_until /* int64[ntx] out */,
+                                  void* d_gate /* uint8[ntx] out */, void* hip_stream);
 
 /* Device time (ms) of the calling thread's most recent *_device call on
  * `device`, from HIP events recorded around its launches on the stream it ran

@@ -88,7 +88,7 @@ Mutant mutate(const Seed& sd, Rng& r) {
     } else if (op == 3) {  // extended with random bytes
       len += 1 + r.below(r.below(8) ? 16 : 600);
     } else if (op == 4) {  // another kind (its own payload semantics over these bytes)
-      kind = (uint32_t)r.below(18);
+      kind = (uint32_t)r.below(20);
     } else if (op == 5) {
       cls = r.below(2) ? (uint32_t)r.below(300) : (uint32_t)r.next();
     } else if (op == 6) {
