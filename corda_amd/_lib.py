@@ -36,7 +36,8 @@ EXPORTS = [
     "cordahip_tx_submit", "cordahip_txid_submit", "cordahip_filtered_tx_submit", "cordahip_shard_range",
     "cordahip_kryo_encode", "cordahip_kryo_encode_device", "cordahip_signed_txcomp_verify", "cordahip_txcomp_submit",
     "cordahip_signed_txcomp_verify_ed25519_device", "cordahip_device_mem", "cordahip_trim",
-    "cordahip_rsa_public_op_device", "cordahip_rsa_pss_verify_device",
+    "cordahip_rsa_public_op_device", "cordahip_rsa_pss_verify_device", "cordahip_sig_verify_device",
+    "cordahip_signed_tx_verify_device", "cordahip_signed_txcomp_verify_device",
     "cordahip_cover_eval_host", "cordahip_signed_tx_verify_covered", "cordahip_tx_submit_covered",
     "cordahip_signed_txcomp_verify_covered", "cordahip_txcomp_submit_covered", "cordahip_tx_cover_device",
     "cordahip_filtered_tx_build", "cordahip_filtered_tx_build_submit", "cordahip_filtered_tx_build_device",
@@ -71,6 +72,7 @@ KRYO_KINDS = {"raw": 0, "char": 1, "short": 2, "int": 3, "long": 4, "byte": 5, "
 ABI_VERSION = 4
 FLAG_IS_VALID = 1  # CORDAHIP_FLAG_IS_VALID: Crypto.isValid semantics (no emptiness checks)
 FLAG_RSA_ON_DEVICE = 2  # CORDAHIP_FLAG_RSA_ON_DEVICE: RSA_SHA256 lanes verified on the GPU, not UNSUPPORTED
+BAD_RANGE = 19  # CORDAHIP_STATUS_BAD_RANGE: a device-resident lane whose CSR ranges or message row are out of bounds
 RSA_GROUP_LANES = 8  # lanes that share one signature in rsa_modexp_kernel (corda_amd/csrc/rsa.hip kT)
 TX_NO_LEAVES, TX_NO_SIGNATURES, TX_BAD_TREE, TX_BAD_COMPONENT = 6, 7, 8, 9
 # required-signer coverage (cordahip_cover): tx statuses and req_status values
@@ -406,6 +408,12 @@ def lib() -> ctypes.CDLL:
         "cordahip_trim": (i32, [vp]),
         "cordahip_rsa_public_op_device": (i32, [vp, i32, vp, vp, vp, u32, u64, vp, vp]),
         "cordahip_rsa_pss_verify_device": (i32, [vp, i32, vp, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp]),
+        "cordahip_sig_verify_device": (i32, [vp, i32, vp, vp, vp, u64, vp, vp, u64, vp, u32, vp, u64, u64, u32, vp, vp,
+                                             vp]),
+        "cordahip_signed_tx_verify_device": (i32, [vp, i32, vp, vp, u64, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64, u64,
+                                                   vp, vp, vp, vp, vp]),
+        "cordahip_signed_txcomp_verify_device": (i32, [vp, i32, vp, u64, u32, vp, u64, vp, u64, vp, vp, vp, vp, u64, vp,
+                                                       vp, u64, u64, vp, vp, vp, vp, vp]),
         "cordahip_cover_eval_host": (i32, [ctypes.POINTER(Cover), u64, vp, vp, vp, vp, vp, u64, u64]),
         "cordahip_signed_tx_verify_covered": (i32, [vp, ctypes.POINTER(SignedTxBatch), ctypes.POINTER(Cover)]),
         "cordahip_tx_submit_covered": (i32, [vp, ctypes.POINTER(SignedTxBatch), ctypes.POINTER(Cover),

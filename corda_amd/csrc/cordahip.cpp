@@ -29,6 +29,7 @@
 #include "notary_stage.hpp"
 #include "kryo_core.hpp"
 #include "runtime.hpp"
+#include "sig_pack.hpp"
 #include "status.hpp"
 
 using namespace cordahip;
@@ -146,6 +147,9 @@ struct DeviceSignedTx {
   const void *d_tx_sig_off, *d_keys, *d_sigs;
   uint64_t nsig;
   void *d_txid, *d_tx_status, *d_first_bad, *d_sig_status;
+  // K23, the mixed-scheme forms: the signatures as a CSR batch with a scheme byte each
+  // (d_keys / d_sigs unused); its message rows are the ids, indexed by transaction
+  const sigpack::In* mixed = nullptr;
   static bool split() {
     static const bool on = getenv("CORDAHIP_DEVICE_SPLIT") && getenv("CORDAHIP_DEVICE_SPLIT")[0] == '1';
     return on;
@@ -175,6 +179,21 @@ struct DeviceSignedTx {
     const uint8_t *keys = static_cast<const uint8_t*>(d_keys), *sigs = static_cast<const uint8_t*>(d_sigs);
     uint8_t* sig_status = static_cast<uint8_t*>(d_sig_status);
     hipError_t e = split() ? hipEventRecord(S.ids, x) : hipSuccess;
+    if (mixed) {
+      // the ids first; every signature's message row is its transaction's index (the set's
+      // message buffer holds the indices: nothing is gathered per signature here), then the
+      // packer and the three families' generic verifiers (runtime.cpp sig_device_enqueue)
+      if (split()) e = e ? e : hipStreamWaitEvent(s, S.ids, 0);
+      sigpack::In in = *mixed;
+      in.msg_row = w.msgs.as<uint32_t>();
+      in.msg_rows = ntx;
+      in.msg_len = 32;
+      e = e ? e : launch_sig_tx_rows(static_cast<const uint64_t*>(d_tx_sig_off), ntx, nsig, w.msgs.as<uint32_t>(), s);
+      e = e ? e : sig_device_enqueue(d, in, static_cast<const uint8_t*>(d_txid), sig_status, nullptr, s);
+      e = e ? e : S.tx_ev.record(s);
+      return e ? e : launch_tx_reduce(sig_status, static_cast<const uint64_t*>(d_tx_sig_off), ntx,
+                                      static_cast<int64_t*>(d_first_bad), static_cast<uint8_t*>(d_tx_status), s);
+    }
     const std::function<hipError_t()> join = [&]() -> hipError_t {  // the ids, then the signatures' messages
       hipError_t r = split() ? hipStreamWaitEvent(s, S.ids, 0) : hipSuccess;
       return r ? r : launch_gather_txid(static_cast<const uint8_t*>(d_txid), static_cast<const uint64_t*>(d_tx_sig_off),
@@ -1536,6 +1555,42 @@ int cordahip_rsa_pss_verify_device(cordahip_ctx* ctx, int device, const void* d_
   });
 }
 
+// K23: the generic batch resident in device memory (runtime.cpp sig_device_enqueue)
+int cordahip_sig_verify_device(cordahip_ctx* ctx, int device, const void* d_scheme, const void* d_key,
+                               const void* d_key_off, uint64_t key_bytes, const void* d_sig, const void* d_sig_off,
+                               uint64_t sig_bytes, const void* d_msgs, uint32_t msg_len, const void* d_msg_row,
+                               uint64_t msg_rows, uint64_t n, uint32_t flags, void* d_status, void* d_verdict,
+                               void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  if (!d || n >= sigpack::kMaxLanes || (flags & ~(CORDAHIP_FLAG_IS_VALID | CORDAHIP_FLAG_RSA_ON_DEVICE)))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if (n && (!d_scheme || !d_key_off || !d_sig_off || !d_status || (key_bytes && !d_key) || (sig_bytes && !d_sig) ||
+            (msg_len && msg_rows && !d_msgs)))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if (misaligned(d_key_off, 8) || misaligned(d_sig_off, 8) || misaligned(d_msg_row, 4) || misaligned(d_verdict, 8))
+    return CORDAHIP_ERR_INVALID_ARG;
+  sigpack::In in{};
+  in.scheme = ptr<uint8_t>(d_scheme);
+  in.key = ptr<uint8_t>(d_key);
+  in.key_off = ptr<uint64_t>(d_key_off);
+  in.key_bytes = key_bytes;
+  in.sig = ptr<uint8_t>(d_sig);
+  in.sig_off = ptr<uint64_t>(d_sig_off);
+  in.sig_bytes = sig_bytes;
+  in.msg_row = ptr<uint32_t>(d_msg_row);
+  in.msg_rows = msg_rows;
+  in.msg_len = msg_len;
+  in.n = n;
+  in.do_verify = (flags & CORDAHIP_FLAG_IS_VALID) ? 0u : 1u;
+  in.rsa_on = (flags & CORDAHIP_FLAG_RSA_ON_DEVICE) ? 1u : 0u;
+  return guarded([&] {
+    return device_call(*d, hip_stream, [&](hipStream_t s) {
+      return sig_device_enqueue(*d, in, ptr<uint8_t>(d_msgs), ptr<uint8_t>(d_status),
+                                ptr<unsigned long long>(d_verdict), s);
+    });
+  });
+}
+
 int cordahip_set_rsa_on_device(cordahip_ctx* ctx, uint32_t on) {
   if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
   ctx->rsa_on_device.store(on ? 1u : 0u);
@@ -1766,6 +1821,59 @@ int cordahip_signed_tx_verify_ed25519_device(cordahip_ctx* ctx, int device, cons
       });
 }
 
+// the signatures of a mixed-scheme device signed-tx call as the packer's input, or false
+static bool mixed_sigs(cordahip_ctx* ctx, const void* d_scheme, const void* d_key, const void* d_key_off,
+                       uint64_t key_bytes, const void* d_sig, const void* d_sig_off, uint64_t sig_bytes, uint64_t nsig,
+                       const void* d_sig_status, sigpack::In& in) {
+  if (nsig >= sigpack::kMaxLanes) return false;
+  if (nsig && (!d_scheme || !d_key_off || !d_sig_off || !d_sig_status || (key_bytes && !d_key) || (sig_bytes && !d_sig)))
+    return false;
+  if (misaligned(d_key_off, 8) || misaligned(d_sig_off, 8)) return false;
+  in = sigpack::In{};
+  in.scheme = ptr<uint8_t>(d_scheme);
+  in.key = ptr<uint8_t>(d_key);
+  in.key_off = ptr<uint64_t>(d_key_off);
+  in.key_bytes = key_bytes;
+  in.sig = ptr<uint8_t>(d_sig);
+  in.sig_off = ptr<uint64_t>(d_sig_off);
+  in.sig_bytes = sig_bytes;
+  in.n = nsig;
+  in.do_verify = 1;  // checkSignaturesAreValid: doVerify rules
+  in.rsa_on = ctx->rsa_on_device.load() ? 1u : 0u;
+  return true;
+}
+
+int cordahip_signed_tx_verify_device(cordahip_ctx* ctx, int device, const void* d_leaf_bytes, const void* d_leaf_off,
+                                     uint64_t nleaves, const void* d_tx_leaf_off, uint64_t ntx,
+                                     const void* d_tx_sig_off, const void* d_scheme, const void* d_key,
+                                     const void* d_key_off, uint64_t key_bytes, const void* d_sig,
+                                     const void* d_sig_off, uint64_t sig_bytes, uint64_t nsig, void* d_txid,
+                                     void* d_tx_status, void* d_first_bad, void* d_sig_status, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  sigpack::In in;
+  if (!d || (ntx && (!d_leaf_off || !d_tx_leaf_off || !d_tx_sig_off || !d_txid || !d_tx_status || !d_first_bad)) ||
+      !mixed_sigs(ctx, d_scheme, d_key, d_key_off, key_bytes, d_sig, d_sig_off, sig_bytes, nsig, d_sig_status, in))
+    return CORDAHIP_ERR_INVALID_ARG;
+  return guarded([&]() -> int {
+    SetLease lease(*d);
+    TxSet& S = lease.get();
+    TxWork& w = S.tx;
+    const DeviceSignedTx c{*d,   S,      ntx,         d_tx_sig_off, nullptr,      nullptr,
+                           nsig, d_txid, d_tx_status, d_first_bad,  d_sig_status, &in};
+    return device_call(
+        *d, hip_stream, [&] { return c.prepare(nleaves, false); },
+        [&](hipStream_t s) {
+          hipStream_t x = nullptr;
+          hipError_t e = c.fork(s, x);
+          e = e ? e : launch_sha256_leaves(static_cast<const uint8_t*>(d_leaf_bytes),
+                                           static_cast<const uint64_t*>(d_leaf_off), nleaves, w.hashes.as<uint32_t>(), x);
+          e = e ? e : launch_merkle_root(w.hashes.as<uint32_t>(), static_cast<const uint64_t*>(d_tx_leaf_off), ntx,
+                                         static_cast<uint8_t*>(d_txid), static_cast<uint8_t*>(d_tx_status), x);
+          return e ? e : c.join_and_verify(s, x);
+        });
+  });
+}
+
 int cordahip_kryo_encode_device(cordahip_ctx* ctx, int device, const void* d_items, uint64_t n, uint32_t group,
                                 void* d_out, uint64_t cap, void* d_off, void* d_status, void* hip_stream) {
   Device* d = dev_at(ctx, device);
@@ -1831,6 +1939,56 @@ int cordahip_signed_txcomp_verify_ed25519_device(cordahip_ctx* ctx, int device, 
           // leaf hashes from the templates (misses impossible: new shapes are built, the rest
           // hashed by the direct encoder), then the ids, with a rejected component making its
           // transaction CORDAHIP_TX_BAD_COMPONENT
+          e = e ? e
+                : launch_kryo_hash_chain(static_cast<const cordahip_kryo_item*>(d_items),
+                                         static_cast<const uint8_t*>(d_payload), payload_len, n_items, group,
+                                         d->kryo_fixed.as<uint8_t>(), slots, slots + n_items,
+                                         d->kryo_sizes.as<uint64_t>(), w.comp_status.as<uint8_t>(),
+                                         w.hashes.as<uint32_t>(), d->kryo_ws.as<uint8_t>(), kKryoDirectWriters, x);
+          e = e ? e : kryo_usage_report(*d, nullptr, x);
+          e = e ? e : d->kryo_ev.record(x);
+          e = e ? e : launch_merkle_root(w.hashes.as<uint32_t>(), static_cast<const uint64_t*>(d_tx_item_off), ntx,
+                                         static_cast<uint8_t*>(d_txid), static_cast<uint8_t*>(d_tx_status), x,
+                                         w.comp_status.as<uint8_t>());
+          return e ? e : c.join_and_verify(s, x);
+        });
+  });
+}
+
+int cordahip_signed_txcomp_verify_device(cordahip_ctx* ctx, int device, const void* d_items, uint64_t n_items,
+                                         uint32_t group, const void* d_payload, uint64_t payload_len,
+                                         const void* d_tx_item_off, uint64_t ntx, const void* d_tx_sig_off,
+                                         const void* d_scheme, const void* d_key, const void* d_key_off,
+                                         uint64_t key_bytes, const void* d_sig, const void* d_sig_off,
+                                         uint64_t sig_bytes, uint64_t nsig, void* d_txid, void* d_tx_status,
+                                         void* d_first_bad, void* d_sig_status, void* hip_stream) {
+  Device* d = dev_at(ctx, device);
+  sigpack::In in;
+  if (!d || (ntx && (!d_tx_item_off || !d_tx_sig_off || !d_txid || !d_tx_status || !d_first_bad)) ||
+      (n_items && !d_items) || (payload_len && !d_payload) ||
+      !mixed_sigs(ctx, d_scheme, d_key, d_key_off, key_bytes, d_sig, d_sig_off, sig_bytes, nsig, d_sig_status, in))
+    return CORDAHIP_ERR_INVALID_ARG;
+  if (n_items >= (1ull << 31) - 1) return CORDAHIP_ERR_INVALID_ARG;  // the encoder's item slots and lists are 32-bit
+  return guarded([&]() -> int {
+    // as cordahip_signed_txcomp_verify_ed25519_device: a buffer set and the encoder's scratch
+    SetLease lease(*d);
+    TxSet& S = lease.get();
+    std::lock_guard<std::mutex> gk(d->kryo_mu);
+    TxWork& w = S.tx;
+    const DeviceSignedTx c{*d,   S,      ntx,         d_tx_sig_off, nullptr,      nullptr,
+                           nsig, d_txid, d_tx_status, d_first_bad,  d_sig_status, &in};
+    return device_call(
+        *d, hip_stream,
+        [&] {
+          const hipError_t e = c.prepare(n_items, true);
+          return e ? e : kryo_scratch_ensure(*d, n_items, 0);
+        },
+        [&](hipStream_t s) {
+          uint32_t* slots = d->kryo_items.as<uint32_t>();
+          hipStream_t x = nullptr;
+          hipError_t e = d->kryo_ev.wait(s);  // the previous users of the encoder's scratch are done
+          e = e ? e : c.fork(s, x);
+          e = e ? e : kryo_state_ready(*d, x);
           e = e ? e
                 : launch_kryo_hash_chain(static_cast<const cordahip_kryo_item*>(d_items),
                                          static_cast<const uint8_t*>(d_payload), payload_len, n_items, group,

@@ -702,20 +702,23 @@ hipError_t launch_ed25519_verify(const uint8_t* keys, const uint8_t* sigs, const
 // ed25519_route.hpp): one fused-prep / ladder pair per ws_lanes list positions. The
 // host does not know the list's length, so the pairs cover all n positions; the
 // kernels read the count, and a pair wholly past it does nothing. No verdict words:
-// the caller gathers them from the statuses.
+// the caller gathers them from the statuses. layout_lanes: the lanes the scratch was
+// laid out for when that is not n (~0, runtime.hpp kEdIdxLayoutOfN: n; K23 passes 0, a
+// header with the list right behind it).
 hipError_t launch_ed25519_verify_idx(const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
                                      uint64_t n, const uint32_t* btab, const uint8_t* pre_status, uint8_t* status,
                                      uint32_t* ws, uint64_t ws_lanes, uint32_t flags, const uint32_t* scratch,
-                                     hipStream_t s) {
+                                     hipStream_t s, uint64_t layout_lanes) {
   if (n == 0) return hipSuccess;
+  const uint64_t lanes = layout_lanes == ~0ull ? n : layout_lanes;
   if (!ws || ws_lanes < 64 || ws_lanes % 64 || !scratch) return hipErrorInvalidValue;
   for (uint64_t base = 0; base < n; base += ws_lanes) {
     const uint64_t m = n - base < ws_lanes ? n - base : ws_lanes;
     const uint32_t blocks = (uint32_t)((m + 255) / 256);
     hipLaunchKernelGGL(ed25519_prep_half_idx_kernel, dim3(blocks), dim3(256), 0, s, keys, sigs, msgs, msg_len, base, m,
-                       pre_status, status, ws, (flags & 1u) ? 0u : 1u, scratch, n);
+                       pre_status, status, ws, (flags & 1u) ? 0u : 1u, scratch, lanes);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = launch_ed25519_ladder_idx(base, m, btab, ws, status, scratch, n, s);
+    if (e == hipSuccess) e = launch_ed25519_ladder_idx(base, m, btab, ws, status, scratch, lanes, s);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

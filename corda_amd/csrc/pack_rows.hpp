@@ -2,7 +2,9 @@
 // (cordahip_sig_batch, the Crypto.isValid / doVerify batch of Crypto.kt:472-541):
 // the host side of host_batch.cpp's pipelines, in a header of its own so that
 // tools/pack_bench.cpp measures exactly this code on the CPU (the host budget
-// of one process driving several GPUs). No HIP here.
+// of one process driving several GPUs). No HIP here. Every decision about a
+// lane -- its class, a direct status, a row's pre-status -- is sig_pack.hpp's, the rule
+// the GPU packer (K23) runs too: one rule, not two.
 //
 // MV is the message view (runtime.hpp MsgView): len(i), ptr(i).
 #pragma once
@@ -13,6 +15,7 @@
 #include "../../include/cordahip.h"
 #include "der.hpp"
 #include "rsa_key.hpp"
+#include "sig_pack.hpp"
 
 namespace cordahip {
 namespace rt {
@@ -25,9 +28,7 @@ inline void pack_ed_row(const cordahip_sig_batch* b, const MV& mv, bool do_verif
                         uint8_t* key, uint8_t* sig, uint8_t* msg, uint8_t* pre) {
   std::memcpy(key, b->key + b->key_off[i], 32);
   const uint64_t sl = b->sig_off[i + 1] - b->sig_off[i];
-  uint8_t st = CORDAHIP_STATUS_OK;
-  if (do_verify && (sl == 0 || L == 0)) st = CORDAHIP_STATUS_EMPTY;  // Crypto.kt:475-476
-  else if (sl != 64) st = CORDAHIP_STATUS_MALFORMED_SIG;           // EdDSAEngine: signature length
+  const uint8_t st = sigpack::ed_pre(do_verify, sl, L);  // Crypto.kt:475-476, then EdDSAEngine: signature length
   if (st == CORDAHIP_STATUS_OK) std::memcpy(sig, b->sig + b->sig_off[i], 64);
   else std::memset(sig, 0, 64);
   *pre = st;
@@ -52,7 +53,7 @@ enum : uint16_t { kDirect = 0, kEc = 1, kEdBase = 2, kRsaBase = 0xfff0, kRsa = 0
 template <class MV>
 inline bool lane_ranges_ok(const cordahip_sig_batch* b, const MV& mv, uint64_t i) {
   const uint64_t k0 = b->key_off[i], k1 = b->key_off[i + 1], s0 = b->sig_off[i], s1 = b->sig_off[i + 1];
-  if (k1 < k0 || k1 > b->key_bytes || s1 < s0 || s1 > b->sig_bytes) return false;
+  if (!sigpack::ranges_ok(k0, k1, b->key_bytes, s0, s1, b->sig_bytes)) return false;
   return mv.tx_of || (mv.off[i + 1] >= mv.off[i] && mv.off[i + 1] <= b->msg_bytes);
 }
 
@@ -74,16 +75,15 @@ inline bool rsa_in_chunks(const cordahip_sig_batch* b, const MV& mv) {
 // the key (rsa_key.hpp parse_public_key), then EMPTY under doVerify rules, then
 // BAD_SIG for a signature longer than the modulus (PSSSigner: false); kRsaToDevice
 // with pk filled for the lanes whose verdict needs the arithmetic.
-constexpr uint8_t kRsaToDevice = 0xff;
+constexpr uint8_t kRsaToDevice = sigpack::kRsaToDevice;
 template <class MV>
 inline uint8_t rsa_lane_pre(const cordahip_sig_batch* b, const MV& mv, bool do_verify, uint64_t i,
                             rsa::PublicKey& pk) {
-  const uint8_t ks = rsa::parse_public_key(b->key + b->key_off[i], b->key_off[i + 1] - b->key_off[i], pk);
-  if (ks != rsa::kOk) return ks;
-  const uint64_t sl = b->sig_off[i + 1] - b->sig_off[i];
-  if (do_verify && (sl == 0 || mv.len(i) == 0)) return CORDAHIP_STATUS_EMPTY;  // Crypto.kt:475-476
-  if (sl > (pk.bits + 7) / 8) return CORDAHIP_STATUS_BAD_SIG;
-  return kRsaToDevice;
+  rsa::KeyView kv;
+  const uint8_t st = sigpack::rsa_pre(b->key + b->key_off[i], b->key_off[i + 1] - b->key_off[i],
+                                      b->sig_off[i + 1] - b->sig_off[i], mv.len(i), do_verify, kv);
+  if (st == kRsaToDevice) rsa::key_of_view(kv, pk);  // the modulus materialised, for pack_rsa_row
+  return st;
 }
 
 // RSA row r of a class-W stage: the modulus padded to W words, e, the signature
@@ -104,35 +104,19 @@ inline uint16_t classify(const cordahip_sig_batch* b, const MV& mv, uint64_t i, 
   mlen = 0;
   if (!lane_ranges_ok(b, mv, i)) return kBadCsr;
   const uint64_t k0 = b->key_off[i], k1 = b->key_off[i + 1];
-  const uint8_t sch = b->scheme[i];
-  const uint64_t kl = k1 - k0;
   mlen = mv.len(i);
-  if (sch == CORDAHIP_SCHEME_ECDSA_SECP256K1_SHA256 || sch == CORDAHIP_SCHEME_ECDSA_SECP256R1_SHA256) {
-    if (kl != 33 && kl != 65) {
-      b->status[i] = CORDAHIP_STATUS_BAD_KEY;  // ECCurve.decodePoint: invalid point encoding
-      return kDirect;
-    }
-    return kEc;
-  }
-  if (sch == CORDAHIP_SCHEME_RSA_SHA256 && rsa_on_device(b, mv)) {
-    rsa::PublicKey pk;
-    const uint8_t st = rsa_lane_pre(b, mv, !(b->flags & CORDAHIP_FLAG_IS_VALID), i, pk);
-    if (st == kRsaToDevice) {
-      if (rsa_class) *rsa_class = pk.words / 32 - 2;
-      return kRsa;
-    }
-    b->status[i] = st;
+  rsa::KeyView kv;
+  const sigpack::Lane l =
+      sigpack::lane_rule(b->scheme[i], b->key + k0, k1 - k0, b->sig_off[i + 1] - b->sig_off[i], mlen,
+                         !(b->flags & CORDAHIP_FLAG_IS_VALID), rsa_on_device(b, mv), kv);
+  if (l.cls == sigpack::kEd) return kEdBase;  // + the piece-local message-length group
+  if (l.cls == sigpack::kEc) return kEc;
+  if (l.cls == sigpack::kDirect) {
+    b->status[i] = l.status;
     return kDirect;
   }
-  if (sch != CORDAHIP_SCHEME_EDDSA_ED25519_SHA512) {
-    b->status[i] = CORDAHIP_STATUS_UNSUPPORTED;  // Crypto.kt:474 require(isSupportedSignatureScheme)
-    return kDirect;
-  }
-  if (kl != 32) {
-    b->status[i] = CORDAHIP_STATUS_BAD_KEY;  // EdDSAPublicKeySpec: "public-key length is wrong"
-    return kDirect;
-  }
-  return kEdBase;  // + the piece-local message-length group
+  if (rsa_class) *rsa_class = l.cls - sigpack::kRsa0;
+  return kRsa;
 }
 
 // ECDSA slot packing of lane i into row r (messages CSR at *mo)
@@ -156,11 +140,7 @@ inline void pack_ec_row(const cordahip_sig_batch* b, const MV& mv, bool do_verif
     // longer than the slot: no r, s < n fits, so the DER rules alone decide (BC:
     // well-formed -> false, else SignatureException); the kernel still decodes
     // the key first, so key errors keep precedence
-    DerInt dr, ds;
-    pre = (ml == 0 && do_verify) ? CORDAHIP_STATUS_EMPTY
-          : der_decode_sig(b->sig + b->sig_off[i], (uint32_t)std::min<uint64_t>(sl, 0xffffffffu), dr, ds)
-              ? CORDAHIP_STATUS_BAD_SIG
-              : CORDAHIP_STATUS_MALFORMED_SIG;
+    pre = sigpack::ec_pre(do_verify, b->sig + b->sig_off[i], sl, ml);
     std::memset(hs + r * 72, 0, 72);
     hsl[r] = 72;
   }

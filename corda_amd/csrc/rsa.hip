@@ -144,7 +144,10 @@ CDEV void dbl_mod(uint32_t (&x)[L], const uint32_t (&n)[L], int gl, int gbase) {
 // kIdx (K20, the generic list of a routed launch): the grid covers the launch's rows and
 // nrows is not used; the list's length is read from *count, a block wholly past it
 // returns at once, as a block, and group j below it takes row perm[j] of the launch. The
-// list holds rows the prep left OK only, so skip is not read.
+// list holds rows the prep left OK only, so skip is not read. (K23's counted launch lists
+// every row below its count: the packer sends only lanes whose key and lengths it has
+// checked, so the prep leaves them OK but for a signature value >= n, which the contract
+// check below turns into a zero row and bad[row] = 1 at no exponentiation's cost.)
 // The two forms are instances of one kernel, as rsa_modexp_keyed_kernel's are
 // (rsa_vkey.hip says why); both instances take the registers, LDS and waves per SIMD the
 // kernel took before the template (70 / 97 / 130 VGPRs, 7 / 4 / 3 waves).
@@ -294,8 +297,10 @@ __global__ void __launch_bounds__(256) rsa_pss_prep_kernel(const uint32_t* __res
                                                            const uint64_t* __restrict__ msg_off, uint32_t msg_len,
                                                            uint32_t W, uint64_t n, const uint8_t* __restrict__ pre,
                                                            uint32_t flags, uint32_t* __restrict__ words,
-                                                           uint32_t* __restrict__ bits_out, uint8_t* __restrict__ st) {
+                                                           uint32_t* __restrict__ bits_out, uint8_t* __restrict__ st,
+                                                           const unsigned int* __restrict__ count) {
   const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (count) n = *count;  // K23: the launch's rows are known on the device only
   if (row >= n) return;
   const uint32_t* m = mod + row * W;
   uint32_t bits = 0;
@@ -347,8 +352,10 @@ __global__ void __launch_bounds__(256) rsa_pss_check_kernel(const uint32_t* __re
                                                             const uint8_t* __restrict__ msgs,
                                                             const uint64_t* __restrict__ msg_off, uint32_t msg_len,
                                                             uint32_t W, uint64_t n, uint8_t* __restrict__ status,
-                                                            unsigned long long* __restrict__ verdict) {
+                                                            unsigned long long* __restrict__ verdict,
+                                                            const unsigned int* __restrict__ count) {
   const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (count) n = *count;  // K23, as in the prep
   uint8_t s = kStatusBadSig;
   if (row < n) {
     s = st[row];
@@ -502,12 +509,76 @@ hipError_t launch_rsa_pss_verify(const uint32_t* mod, const uint32_t* exp, const
     const dim3 grid((uint32_t)((m + 255) / 256));
     hipLaunchKernelGGL(rsa_pss_prep_kernel, grid, dim3(256), 0, s, mod + lo * W, exp + lo, sigs + lo * 4 * W,
                        sig_len + lo, msg_off ? msg_off + lo : nullptr, msg_len, W, m, pre ? pre + lo : nullptr, flags,
-                       words, bits, st);
+                       words, bits, st, (const unsigned int*)nullptr);
     hipError_t e = modexp_any(W, mod + lo * W, exp + lo, words, m, words, bad, st, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rsa_pss_check_kernel, grid, dim3(256), 0, s, words, bits, st, bad,
                        msg_off ? msgs : msgs + lo * msg_len, msg_off ? msg_off + lo : nullptr, msg_len, W, m,
-                       status + lo, verdict ? verdict + lo / 64 : nullptr);
+                       status + lo, verdict ? verdict + lo / 64 : nullptr, (const unsigned int*)nullptr);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// K23: the same over rows whose number only the device knows (*count <= n, the host's
+// upper bound; every row's pre-status is OK: the packer sent the decided lanes elsewhere).
+// Per launch of the workspace loop a one-thread kernel leaves the launch's rows in
+// launch_count[j]; the prep and the check return past it, and the exponentiation is the
+// indexed instance (K20's, over iota: row j of the list is row j), whose blocks wholly
+// past the count return as blocks. iota: at least min(ws_rows, n) words.
+__global__ void rsa_launch_count_kernel(const unsigned int* __restrict__ count, uint64_t lo, uint64_t m,
+                                        unsigned int* __restrict__ out) {
+  const uint64_t c = *count;
+  *out = (unsigned int)(c > lo ? (c - lo < m ? c - lo : m) : 0);
+}
+
+template <int W>
+static hipError_t launch_modexp_counted(const uint32_t* mod, const uint32_t* exp, uint32_t* words, uint64_t m,
+                                        uint8_t* bad, const unsigned int* iota, const unsigned int* count,
+                                        hipStream_t s) {
+  hipLaunchKernelGGL((rsa_modexp_kernel<W, true>), dim3((uint32_t)rsa_route_idx_blocks(m)), dim3(kBlock), 0, s, mod,
+                     exp, words, (uint64_t)0, words, bad, (const uint8_t*)nullptr, iota, count);
+  return hipGetLastError();
+}
+
+uint64_t rsa_counted_launches(uint64_t n, uint64_t ws_rows) {
+  ws_rows = std::min(ws_rows, kMaxLaunchRows) / 64 * 64;
+  return ws_rows ? (n + ws_rows - 1) / ws_rows : 0;
+}
+
+hipError_t launch_rsa_pss_verify_counted(const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
+                                         const uint16_t* sig_len, const uint8_t* msgs, uint32_t msg_len, uint32_t W,
+                                         uint64_t n, const unsigned int* count, const unsigned int* iota,
+                                         unsigned int* launch_count, uint8_t* status, uint8_t* ws, uint64_t ws_rows,
+                                         uint32_t flags, hipStream_t s) {
+  if (W != 64 && W != 96 && W != 128) return hipErrorInvalidValue;
+  ws_rows = std::min(ws_rows, kMaxLaunchRows) / 64 * 64;
+  if (n && (!ws_rows || !count || !iota || !launch_count)) return hipErrorInvalidValue;
+  uint32_t* words = reinterpret_cast<uint32_t*>(ws);
+  uint32_t* bits = words + ws_rows * W;
+  uint8_t* st = reinterpret_cast<uint8_t*>(bits + ws_rows);
+  uint8_t* bad = st + ws_rows;
+  uint64_t j = 0;
+  for (uint64_t lo = 0; lo < n; lo += ws_rows, j++) {
+    const uint64_t m = std::min(ws_rows, n - lo);
+    const dim3 grid((uint32_t)((m + 255) / 256));
+    unsigned int* lc = launch_count + j;
+    hipLaunchKernelGGL(rsa_launch_count_kernel, dim3(1), dim3(1), 0, s, count, lo, m, lc);
+    hipLaunchKernelGGL(rsa_pss_prep_kernel, grid, dim3(256), 0, s, mod + lo * W, exp + lo, sigs + lo * 4 * W,
+                       sig_len + lo, (const uint64_t*)nullptr, msg_len, W, m, (const uint8_t*)nullptr, flags, words,
+                       bits, st, (const unsigned int*)lc);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    switch (W) {
+      case 64: e = launch_modexp_counted<64>(mod + lo * W, exp + lo, words, m, bad, iota, lc, s); break;
+      case 96: e = launch_modexp_counted<96>(mod + lo * W, exp + lo, words, m, bad, iota, lc, s); break;
+      default: e = launch_modexp_counted<128>(mod + lo * W, exp + lo, words, m, bad, iota, lc, s); break;
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rsa_pss_check_kernel, grid, dim3(256), 0, s, words, bits, st, bad, msgs + lo * msg_len,
+                       (const uint64_t*)nullptr, msg_len, W, m, status + lo, (unsigned long long*)nullptr,
+                       (const unsigned int*)lc);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

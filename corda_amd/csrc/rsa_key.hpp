@@ -35,13 +35,13 @@ struct PublicKey {
 // Width class of a modulus of `bits` bits: the operand width W (32-bit words) its
 // lanes run at; the modulus is zero-padded to W words (Montgomery with
 // R = 2^(32 W) holds for every odd n < R). 0: outside 1024..4096 bits.
-inline uint32_t class_words(uint32_t bits) {
+CHD uint32_t class_words(uint32_t bits) {
   if (bits < kMinBits || bits > kMaxBits) return 0;
   return bits <= 2048 ? 64 : bits <= 3072 ? 96 : 128;
 }
 
 // One DER INTEGER at b[i..n): body pointer and length; strict (minimal, non-empty).
-inline bool der_integer(const uint8_t* b, uint32_t n, uint32_t& i, const uint8_t*& body, uint32_t& len) {
+CHD bool der_integer(const uint8_t* b, uint32_t n, uint32_t& i, const uint8_t*& body, uint32_t& len) {
   if (i >= n || b[i++] != 0x02) return false;
   if (!der_read_len(b, n, i, len) || len == 0 || len > n - i) return false;
   body = b + i;
@@ -50,11 +50,34 @@ inline bool der_integer(const uint8_t* b, uint32_t n, uint32_t& i, const uint8_t
   return true;
 }
 
+// A decoded key without a copy of its modulus: the modulus' significant bytes where they
+// lie in the key (big-endian, nb[0] != 0), its bit length and width class, and e. What
+// the device packer (sig_pack.hpp, K23) keeps of a lane's key: it writes the modulus
+// words straight into the lane's row.
+struct KeyView {
+  const uint8_t* nb = nullptr;
+  uint32_t nl = 0;
+  uint32_t e = 0;
+  uint32_t bits = 0;
+  uint32_t words = 0;
+};
+
+// word k (little-endian) of the view's modulus, zero above it
+CHD uint32_t key_view_word(const KeyView& kv, uint32_t k) {
+  uint32_t w = 0;
+  for (uint32_t q = 0; q < 4; q++) {
+    const uint32_t sgn = 4 * k + q;  // significance
+    if (sgn < kv.nl) w |= (uint32_t)kv.nb[kv.nl - 1 - sgn] << (8 * q);
+  }
+  return w;
+}
+
 // Decode the key of one lane. kBadKey: not a SEQUENCE of exactly two INTEGERs,
 // trailing bytes, non-minimal / indefinite lengths, n <= 0 or e <= 0.
 // kUnsupported: a key BouncyCastle accepts and the GPU path declines (even n,
-// bit length outside 1024..4096, even e, e < 3, e >= 2^32). kOk: pk is filled.
-inline uint8_t parse_public_key(const uint8_t* der, uint64_t len64, PublicKey& pk) {
+// bit length outside 1024..4096, even e, e < 3, e >= 2^32). kOk: kv is filled.
+// Reads der[0 .. len64) only. Host and device: the one rule of both packers.
+CHD uint8_t parse_public_key_view(const uint8_t* der, uint64_t len64, KeyView& kv) {
   if (len64 < 2 || len64 > 0xffffffu) return kBadKey;
   const uint32_t n = (uint32_t)len64;
   uint32_t i = 1, len = 0;
@@ -74,12 +97,28 @@ inline uint8_t parse_public_key(const uint8_t* der, uint64_t len64, PublicKey& p
   uint32_t e = 0;
   for (uint32_t k = 0; k < el; k++) e = (e << 8) | eb[k];
   if (e < 3) return kUnsupported;
-  pk.e = e;
-  pk.bits = (uint32_t)bits;
-  pk.words = class_words(pk.bits);
-  std::memset(pk.n, 0, sizeof(pk.n));
-  for (uint32_t k = 0; k < nl; k++) pk.n[k >> 2] |= (uint32_t)nb[nl - 1 - k] << (8 * (k & 3));
+  kv.nb = nb;
+  kv.nl = nl;
+  kv.e = e;
+  kv.bits = (uint32_t)bits;
+  kv.words = class_words(kv.bits);
   return kOk;
+}
+
+// a view's key with the modulus materialised
+inline void key_of_view(const KeyView& kv, PublicKey& pk) {
+  pk.e = kv.e;
+  pk.bits = kv.bits;
+  pk.words = kv.words;
+  std::memset(pk.n, 0, sizeof(pk.n));
+  for (uint32_t k = 0; k < kv.nl; k++) pk.n[k >> 2] |= (uint32_t)kv.nb[kv.nl - 1 - k] << (8 * (k & 3));
+}
+// The same with the modulus materialised (the host packers, the word-serial reference)
+inline uint8_t parse_public_key(const uint8_t* der, uint64_t len64, PublicKey& pk) {
+  KeyView kv;
+  const uint8_t ks = parse_public_key_view(der, len64, kv);
+  if (ks == kOk) key_of_view(kv, pk);
+  return ks;
 }
 
 // big-endian bytes -> w little-endian words; false if the value needs more

@@ -119,7 +119,7 @@ hipError_t launch_rsa_routed_head(const uint32_t* mod, const uint32_t* exp, cons
   const dim3 grid((uint32_t)((m + 255) / 256));
   hipLaunchKernelGGL(rsa_pss_prep_kernel, grid, dim3(256), 0, s, mod + lo * W, exp + lo, sigs + lo * 4 * W,
                      sig_len + lo, msg_off ? msg_off + lo : nullptr, msg_len, W, m, pre ? pre + lo : nullptr, flags,
-                     words, bits, st);
+                     words, bits, st, (const unsigned int*)nullptr);
   return hipGetLastError();
 }
 
@@ -163,6 +163,6 @@ hipError_t launch_rsa_routed_tail(const uint32_t* mod, const uint32_t* exp, cons
   const dim3 grid((uint32_t)((m + 255) / 256));
   hipLaunchKernelGGL(rsa_pss_check_kernel, grid, dim3(256), 0, s, words, bits, st, bad,
                      msg_off ? msgs : msgs + lo * msg_len, msg_off ? msg_off + lo : nullptr, msg_len, W, m, status + lo,
-                     verdict ? verdict + lo / 64 : nullptr);
+                     verdict ? verdict + lo / 64 : nullptr, (const unsigned int*)nullptr);
   return hipGetLastError();
 }

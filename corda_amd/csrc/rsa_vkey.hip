@@ -256,7 +256,7 @@ hipError_t launch_rsa_verify_keyed(const uint32_t* tab, const uint32_t* key_id, 
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rsa_pss_check_kernel, grid, dim3(256), 0, s, words, bits, st, bad,
                        msg_off ? msgs : msgs + lo * msg_len, msg_off ? msg_off + lo : nullptr, msg_len, W, m,
-                       status + lo, verdict ? verdict + lo / 64 : nullptr);
+                       status + lo, verdict ? verdict + lo / 64 : nullptr, (const unsigned int*)nullptr);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

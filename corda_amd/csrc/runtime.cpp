@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "runtime.hpp"
+#include "sig_pack.hpp"
 
 using namespace cordahip;
 using namespace cordahip::rt;
@@ -578,6 +579,159 @@ hipError_t ed_verify_device_chunks(Device& d, TxSet& S, const uint8_t* keys, con
   return e ? e : hipStreamWaitEvent(s, S.ed_join, 0);
 }
 
+// K23: a mixed-scheme CSR batch resident in device memory. The packer's three passes
+// (sig_pack.hip) leave every class's dense rows and its count in the device's scratch;
+// each class's message rows are gathered, its generic engine runs over the rows -- the
+// indexed instances, which read the count on the device: Ed25519 over the counter block's
+// route-format header with iota as its list, ECDSA over the packer's perm and counters,
+// RSA per width class over launch_rsa_pss_verify_counted -- and the rows' statuses go
+// back to lane order. One stream, no read-back; the host sizes every launch and every
+// buffer for its upper bound (n lanes; an RSA class key_bytes / the smallest key of the
+// class). The routing switches are not consulted.
+hipError_t sig_device_enqueue(Device& d, const sigpack::In& in, const uint8_t* msgs, uint8_t* status,
+                              unsigned long long* verdict, hipStream_t s) {
+  using namespace sigpack;
+  const uint64_t n = in.n, ml = in.msg_len;
+  if (n == 0) return hipSuccess;
+  if (n >= kMaxLanes) return hipErrorInvalidValue;
+  std::lock_guard<std::mutex> g(d.sigpack_mu);
+  SigPackWork& w = d.sigpack;
+  const uint64_t nt = tiles(n);
+  struct Carve {  // offsets of 256-byte-aligned pieces
+    size_t at = 0;
+    size_t take(size_t bytes) {
+      const size_t o = at;
+      at += (bytes + 255) / 256 * 256;
+      return o;
+    }
+  } c, rc;
+  const size_t o_hdr = c.take(4 * (kHdrWords + n)), o_code = c.take(n), o_btot = c.take(4 * kCounts * nt),
+               o_boff = c.take(4 * kCounts * nt);
+  const size_t o_edk = c.take(32 * n), o_eds = c.take(64 * n), o_edp = c.take(n), o_edl = c.take(4 * n),
+               o_edm = c.take(4 * n), o_edmsg = c.take(ml * n), o_edst = c.take(n);
+  const size_t o_ecsch = c.take(n), o_eck = c.take(65 * n), o_eckl = c.take(n), o_ecs = c.take(72 * n),
+               o_ecsl = c.take(n), o_ecp = c.take(n), o_ecl = c.take(4 * n), o_ecm = c.take(4 * n),
+               o_ecperm = c.take(4 * n), o_ecmsg = c.take(ml * n), o_ecst = c.take(n);
+  uint64_t cap[3] = {0, 0, 0};
+  size_t o_rmod[3], o_rexp[3], o_rsig[3], o_rsl[3], o_rpre[3], o_rlane[3], o_rmsg[3], o_rmsgs[3], o_rst[3], o_rlc[3];
+  for (uint32_t k = 0; k < 3 && in.rsa_on; k++) {
+    const uint64_t r = cap[k] = rsa_cap_rows(kRsa0 + k, n, in.key_bytes), W = rsa_words(kRsa0 + k);
+    o_rmod[k] = rc.take(4 * W * r), o_rexp[k] = rc.take(4 * r), o_rsig[k] = rc.take(4 * W * r);
+    o_rsl[k] = rc.take(2 * r), o_rpre[k] = rc.take(r), o_rlane[k] = rc.take(4 * r), o_rmsg[k] = rc.take(4 * r);
+    o_rmsgs[k] = rc.take(ml * r), o_rst[k] = rc.take(r), o_rlc[k] = rc.take(4 * (r / 64 + 1));
+  }
+  hipError_t e = w.ev.grow(w.rows.cap < c.at || w.rsa_rows.cap < rc.at, [&] {
+    if (w.rows.ensure(c.at) || w.rsa_rows.ensure(rc.at)) return hipErrorOutOfMemory;
+    return hipSuccess;
+  });
+  if (e != hipSuccess) return e;
+  e = w.ev.wait(s);
+  if (e != hipSuccess) return e;
+  uint8_t* base = w.rows.as<uint8_t>();
+  uint8_t* rbase = w.rsa_rows.as<uint8_t>();
+  const auto at = [](uint8_t* b, size_t o) { return b + o; };
+  const auto at32 = [](uint8_t* b, size_t o) { return reinterpret_cast<uint32_t*>(b + o); };
+  Out out{};
+  out.hdr = at32(base, o_hdr);
+  out.code = at(base, o_code);
+  out.btot = at32(base, o_btot);
+  out.boff = at32(base, o_boff);
+  out.status = status;
+  out.ed_key = at32(base, o_edk), out.ed_sig = at32(base, o_eds), out.ed_pre = at(base, o_edp);
+  out.ed_lane = at32(base, o_edl), out.ed_msg = at32(base, o_edm);
+  out.ec_scheme = at(base, o_ecsch), out.ec_key = at(base, o_eck), out.ec_key_len = at(base, o_eckl);
+  out.ec_sig = at(base, o_ecs), out.ec_sig_len = at(base, o_ecsl), out.ec_pre = at(base, o_ecp);
+  out.ec_lane = at32(base, o_ecl), out.ec_msg = at32(base, o_ecm), out.ec_perm = at32(base, o_ecperm);
+  for (uint32_t k = 0; k < 3; k++) {
+    out.rsa_cap[k] = cap[k];
+    if (!cap[k]) continue;
+    out.rsa_mod[k] = at32(rbase, o_rmod[k]), out.rsa_exp[k] = at32(rbase, o_rexp[k]);
+    out.rsa_sig[k] = at32(rbase, o_rsig[k]);
+    out.rsa_sig_len[k] = reinterpret_cast<uint16_t*>(rbase + o_rsl[k]);
+    out.rsa_pre[k] = at(rbase, o_rpre[k]);
+    out.rsa_lane[k] = at32(rbase, o_rlane[k]), out.rsa_msg[k] = at32(rbase, o_rmsg[k]);
+  }
+  const uint32_t* hdr = out.hdr;
+  const uint32_t flags = in.do_verify ? 0u : (uint32_t)CORDAHIP_FLAG_IS_VALID;
+  bool launched = false;
+  const auto run = [&]() -> hipError_t {
+    launched = true;
+    hipError_t r = launch_sig_pack(in, out, s);
+    if (r != hipSuccess) return r;
+    {  // Ed25519: K1's indexed instance over rows 0 .. count
+      uint8_t* em = at(base, o_edmsg);
+      uint8_t* est = at(base, o_edst);
+      r = launch_sig_gather(msgs, in.msg_len, out.ed_msg, hdr + kHdrClass + kEd, n, em, s);
+      if (r != hipSuccess) return r;
+      std::lock_guard<std::mutex> ge(d.ed_mu[0]);
+      r = ed_ws_grow(d, 0, n, false, [] { return hipSuccess; });
+      if (r != hipSuccess) return r;
+      const uint64_t lane_bytes = ed25519_ws_lane_bytes();
+      r = fenced({&d.ed_ev[0]}, s, [&] {
+        return launch_ed25519_verify_idx(reinterpret_cast<const uint8_t*>(out.ed_key),
+                                         reinterpret_cast<const uint8_t*>(out.ed_sig), em, in.msg_len, n,
+                                         d.btab.as<uint32_t>(), out.ed_pre, est, d.ed_ws[0].as<uint32_t>(),
+                                         d.ed_ws[0].cap / lane_bytes / 64 * 64, flags, hdr + kHdrEd, s, 0);
+      });
+      if (r != hipSuccess) return r;
+      r = launch_sig_scatter(est, out.ed_lane, hdr + kHdrClass + kEd, n, status, s);
+      if (r != hipSuccess) return r;
+    }
+    {  // ECDSA: K2's indexed instance over perm and the engine's counters
+      uint8_t* cm = at(base, o_ecmsg);
+      uint8_t* cst = at(base, o_ecst);
+      r = launch_sig_gather(msgs, in.msg_len, out.ec_msg, hdr + kHdrClass + kEc, n, cm, s);
+      if (r != hipSuccess) return r;
+      std::lock_guard<std::mutex> gc(d.ec_mu[0]);
+      EcWork& ew = d.ec[0];
+      const uint64_t slots = std::min<uint64_t>(d.ec_ws_slots, (n + 63) / 64 * 64);
+      const bool ws_needed = ew.ws.cap < slots * ecdsa_ws_slot_bytes();
+      r = ew.ev.grow(ws_needed, [&] {
+        const uint64_t want = std::max<uint64_t>(slots, std::min<uint64_t>(d.ec_ws_slots, kWsMinLanes));
+        return ew.ws.ensure(want * ecdsa_ws_slot_bytes()) ? hipErrorOutOfMemory : hipSuccess;
+      });
+      if (r != hipSuccess) return r;
+      r = fenced({&ew.ev}, s, [&] {
+        return launch_ecdsa_verify_routed(out.ec_scheme, out.ec_key, out.ec_key_len, out.ec_sig, out.ec_sig_len, cm,
+                                          nullptr, in.msg_len, n, d.gtab_k1.as<uint32_t>(), d.gtab_r1.as<uint32_t>(),
+                                          out.ec_pre, cst, nullptr, hdr + kHdrEc, out.ec_perm, ew.ws.as<uint32_t>(),
+                                          ew.ws.cap / ecdsa_ws_slot_bytes() / 64 * 64, flags, s);
+      });
+      if (r != hipSuccess) return r;
+      r = launch_sig_scatter(cst, out.ec_lane, hdr + kHdrClass + kEc, n, status, s);
+      if (r != hipSuccess) return r;
+    }
+    for (uint32_t k = 0; k < 3; k++) {  // RSA: one width class per launch set
+      if (!cap[k]) continue;
+      const uint32_t W = rsa_words(kRsa0 + k);
+      const uint32_t* cnt = hdr + kHdrClass + kRsa0 + k;
+      uint8_t* rm = at(rbase, o_rmsgs[k]);
+      uint8_t* rst = at(rbase, o_rst[k]);
+      r = launch_sig_gather(msgs, in.msg_len, out.rsa_msg[k], cnt, cap[k], rm, s);
+      if (r != hipSuccess) return r;
+      std::lock_guard<std::mutex> gr(d.rsa_mu);
+      r = rsa_ws_grow(d, W, cap[k]);
+      if (r != hipSuccess) return r;
+      r = fenced({&d.rsa.ev}, s, [&] {
+        return launch_rsa_pss_verify_counted(out.rsa_mod[k], out.rsa_exp[k],
+                                             reinterpret_cast<const uint8_t*>(out.rsa_sig[k]), out.rsa_sig_len[k], rm,
+                                             in.msg_len, W, cap[k], cnt, hdr + kHdrWords, at32(rbase, o_rlc[k]), rst,
+                                             d.rsa.ws.as<uint8_t>(), rsa_ws_rows(d.rsa, W), flags, s);
+      });
+      if (r != hipSuccess) return r;
+      r = launch_sig_scatter(rst, out.rsa_lane[k], cnt, cap[k], status, s);
+      if (r != hipSuccess) return r;
+    }
+    return verdict ? launch_ed25519_status_verdict(status, n, verdict, s) : hipSuccess;
+  };
+  e = run();
+  if (launched) {  // whatever was launched is fenced, also after a failure
+    const hipError_t r = w.ev.record(s);
+    return e ? e : r;
+  }
+  return e;
+}
+
 // CORDAHIP_DEVICE_MEM_BUDGET (bytes, K/M/G suffixes; default 128 GiB, at most 90%
 // of the device): the workspaces it sizes -- Ed25519 slot 0 45% of it, slot 1 20%
 // (and half of slot 0 at most), ECDSA 15% -- each also capped by its r05 maximum
@@ -615,7 +769,8 @@ void device_budget(Device& d) {  // device current
 // encoder's shape table and the ECDSA counters stay: derived data, 18 MB).
 void trim_device(Device& d) {
   SetLease l0(d, 0, true), l1(d, 1, true);
-  std::lock_guard<std::mutex> gk(d.kryo_mu), gs(d.stream_mu), gp(d.ped_mu), ge0(d.ed_mu[0]), ge1(d.ed_mu[1]),
+  std::lock_guard<std::mutex> gk(d.kryo_mu), gs(d.stream_mu), gp(d.ped_mu), gsp(d.sigpack_mu), ge0(d.ed_mu[0]),
+      ge1(d.ed_mu[1]),
       gc0(d.ec_mu[0]), gc1(d.ec_mu[1]), gr(d.rsa_mu), gv(d.cover_mu), gh(d.sign_stage.mu), gvh(d.vkey_stage.mu);
   if (hipSetDevice(d.id) != hipSuccess) return;
   d.release_idle();

@@ -110,10 +110,11 @@ hipError_t launch_ed25519_route(const uint8_t* keys, uint64_t n, const uint32_t*
 hipError_t launch_ed25519_verify_keyed_idx(const uint32_t* scratch, uint64_t lanes, const uint8_t* sigs,
                                            const uint8_t* msgs, uint32_t msg_len, const uint8_t* pre, uint32_t flags,
                                            const uint32_t* vtab, uint8_t* status, hipStream_t s);
+constexpr uint64_t kEdIdxLayoutOfN = ~0ull;  // launch_ed25519_verify_idx: the scratch is laid out for n lanes
 hipError_t launch_ed25519_verify_idx(const uint8_t* keys, const uint8_t* sigs, const uint8_t* msgs, uint32_t msg_len,
                                      uint64_t n, const uint32_t* btab, const uint8_t* pre_status, uint8_t* status,
                                      uint32_t* ws, uint64_t ws_lanes, uint32_t flags, const uint32_t* scratch,
-                                     hipStream_t s);
+                                     hipStream_t s, uint64_t layout_lanes = kEdIdxLayoutOfN);
 hipError_t launch_ed25519_status_verdict(const uint8_t* status, uint64_t n, unsigned long long* verdict,
                                          hipStream_t s);
 hipError_t launch_sha256_leaves(const uint8_t* bytes, const uint64_t* off, uint64_t nleaves, uint32_t* hashes,
@@ -307,6 +308,30 @@ hipError_t launch_rsa_sign_selftest(uint32_t* stab, uint32_t W, hipStream_t s);
 hipError_t launch_ecdsa_sign(const uint8_t* scheme, const uint8_t* seeds, const uint8_t* msgs, uint32_t msg_len,
                              uint64_t n, const uint32_t* gk1, const uint32_t* gr1, uint8_t* keys, uint8_t* key_len,
                              uint8_t* sigs, uint8_t* sig_len, hipStream_t s);
+// K23 (sig_pack.hip, sig_pack.hpp): a mixed-scheme CSR batch in device memory classified
+// and packed into the dense rows of the engines above -- count, scan and pack passes on
+// s, nothing read back; the class counts stay in out.hdr. launch_sig_gather: a class's
+// message rows (rows[r] = msgs[idx[r]], r below *count; cap: the host's upper bound).
+// launch_sig_scatter: status[lane_of_row[r]] = row_status[r] for the same rows.
+// launch_rsa_pss_verify_counted (rsa.hip): launch_rsa_pss_verify over dense messages and
+// *count <= n rows; launch_count: rsa_counted_launches(n, ws_rows) words of scratch.
+namespace sigpack {
+struct In;
+struct Out;
+}  // namespace sigpack
+hipError_t launch_sig_pack(const sigpack::In& in, const sigpack::Out& out, hipStream_t s);
+hipError_t launch_sig_gather(const uint8_t* msgs, uint32_t msg_len, const uint32_t* idx, const uint32_t* count,
+                             uint64_t cap, uint8_t* rows, hipStream_t s);
+hipError_t launch_sig_scatter(const uint8_t* row_status, const uint32_t* lane_of_row, const uint32_t* count,
+                              uint64_t cap, uint8_t* status, hipStream_t s);
+// rows[s] = the transaction whose signature s is (tx_sig_off[ntx + 1]), s < nsig
+hipError_t launch_sig_tx_rows(const uint64_t* tx_sig_off, uint64_t ntx, uint64_t nsig, uint32_t* rows, hipStream_t s);
+uint64_t rsa_counted_launches(uint64_t n, uint64_t ws_rows);
+hipError_t launch_rsa_pss_verify_counted(const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
+                                         const uint16_t* sig_len, const uint8_t* msgs, uint32_t msg_len, uint32_t W,
+                                         uint64_t n, const unsigned int* count, const unsigned int* iota,
+                                         unsigned int* launch_count, uint8_t* status, uint8_t* ws, uint64_t ws_rows,
+                                         uint32_t flags, hipStream_t s);
 
 namespace rt {
 
@@ -597,6 +622,21 @@ struct RsaWork {
   }
 };
 
+// The mixed-scheme device calls' scratch (K23, cordahip_sig_verify_device): the counter
+// block, the lanes' code bytes, the block totals and every class's packed rows, message
+// rows and row statuses in `rows`; the RSA classes' in rsa_rows, which stays empty until
+// a call asks for RSA on the device. Grow-only, behind Device::sigpack_mu and ev.
+struct SigPackWork {
+  DevBuf rows, rsa_rows;
+  Fence ev;
+  template <class V>
+  void visit(V& v) {
+    v.dev(rows, kFreed);
+    v.dev(rsa_rows, kFreed);
+    v.fence(ev);
+  }
+};
+
 // The key table of one registered-key family on one device. It is allocated (zeroed) by
 // the context's first add of the family, counted in the device's account like every
 // DevBuf, and then kept until ~Device: the idle release and cordahip_trim never see it
@@ -841,6 +881,10 @@ struct Device {
   // included); s_rsa is that section's stream, created with its first lane
   std::mutex rsa_mu;
   RsaWork rsa;
+  // the mixed-scheme device calls (K23): sigpack_mu is held while such a call enqueues,
+  // outside ed_mu[0], ec_mu[0] and rsa_mu, which it takes one after the other
+  std::mutex sigpack_mu;
+  SigPackWork sigpack;
   hipStream_t s_rsa = nullptr;
   hipStream_t stream = nullptr;  // context stream (init-time work and host tx paths)
   std::mutex tmu;
@@ -946,7 +990,7 @@ struct Device {
   // vkeys.ev -- and drops it before the generic engine. With route_on clear it takes no
   // lock it did not take before.
   // Lock order of the locks met on these paths, outermost first:
-  //   ped_mu / stream_mu / a SetLease (the pipelines) -> ed_mu[0] -> ed_mu[1] ->
+  //   ped_mu / stream_mu / a SetLease (the pipelines) -> sigpack_mu -> ed_mu[0] -> ed_mu[1] ->
   //   ec_mu[0] -> ec_mu[1] -> rsa_mu -> ... -> sign_stage.mu -> vkey_stage.mu -> vkey_mu.
   // sign_mu stands where vkey_mu does, inside sign_stage.mu; no path holds both.
   // trim_device takes them in that order up to vkey_stage.mu; a keyed host call holds
@@ -996,6 +1040,7 @@ struct Device {
     sign_stage.visit(v);
     for (EcWork& w : ec) w.visit(v);
     rsa.visit(v);
+    sigpack.visit(v);
     for (hipStream_t* s : {&s_rsa, &stream, &s_copy, &s_ed, &s_ec, &s_ed2, &s_idcopy}) v.stream(*s);  // s_ec2 is s_idcopy
     for (TimedCall& tc : ring)
       for (hipEvent_t* e : {&tc.a, &tc.b}) v.event(*e, false);
@@ -1252,6 +1297,12 @@ hipError_t rsa_verify_enqueue(Device& d, const uint32_t* mod, const uint32_t* ex
                               const uint16_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len,
                               uint32_t W, uint64_t n, const uint8_t* pre, uint8_t* status,
                               unsigned long long* verdict, uint32_t flags, hipStream_t s);
+// K23: a mixed-scheme batch in device memory (in: device pointers; msgs: in.msg_rows dense
+// rows of in.msg_len bytes) packed and verified on s by the generic engines, whatever the
+// routing switches say: statuses in lane order, verdict words when verdict is non-null.
+// Takes sigpack_mu and, inside it, ed_mu[0], ec_mu[0] and rsa_mu in turn.
+hipError_t sig_device_enqueue(Device& d, const sigpack::In& in, const uint8_t* msgs, uint8_t* status,
+                              unsigned long long* verdict, hipStream_t s);
 void shard_range(uint64_t n, uint64_t nshards, uint64_t shard, uint64_t align, uint64_t& lo, uint64_t& hi);
 uint64_t env_lanes(const char* name, uint64_t dflt);
 

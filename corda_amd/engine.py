@@ -783,6 +783,32 @@ class Engine:
             keys.data_ptr(), sigs.data_ptr(), keys.shape[0], txid.data_ptr(), tx_status.data_ptr(),
             first_bad.data_ptr(), sig_status.data_ptr(), s), "cordahip_signed_txcomp_verify_ed25519_device")
 
+    def signed_tx_verify_device(self, leaf_bytes, leaf_off, tx_leaf_off, tx_sig_off, scheme, key, key_off, sig,
+                                sig_off, txid, tx_status, first_bad, sig_status, device: int = 0, stream=None):
+        """cordahip_signed_tx_verify_device (K23): signed_tx_verify_ed25519_device with signatures of
+        any scheme -- scheme uint8 [nsig], key / sig uint8 byte buffers, key_off / sig_off int64
+        [nsig + 1]; RSA lanes follow set_rsa_on_device."""
+        s = stream.cuda_stream if stream is not None else 0
+        p = lambda x: x.data_ptr() if x.numel() else None  # noqa: E731
+        check(lib().cordahip_signed_tx_verify_device(
+            self._ctx, device, p(leaf_bytes), leaf_off.data_ptr(), leaf_off.shape[0] - 1, tx_leaf_off.data_ptr(),
+            tx_leaf_off.shape[0] - 1, tx_sig_off.data_ptr(), p(scheme), p(key), key_off.data_ptr(), key.numel(),
+            p(sig), sig_off.data_ptr(), sig.numel(), scheme.numel(), txid.data_ptr(), tx_status.data_ptr(),
+            first_bad.data_ptr(), p(sig_status), s), "cordahip_signed_tx_verify_device")
+
+    def signed_txcomp_verify_device(self, items, n_items: int, payload, tx_item_off, tx_sig_off, scheme, key, key_off,
+                                    sig, sig_off, txid, tx_status, first_bad, sig_status, group: int = 1,
+                                    device: int = 0, stream=None):
+        """cordahip_signed_txcomp_verify_device (K23): signed_txcomp_verify_ed25519_device with the
+        signatures as signed_tx_verify_device takes them."""
+        s = stream.cuda_stream if stream is not None else 0
+        p = lambda x: x.data_ptr() if x.numel() else None  # noqa: E731
+        check(lib().cordahip_signed_txcomp_verify_device(
+            self._ctx, device, items.data_ptr(), n_items, group, p(payload), payload.numel(), tx_item_off.data_ptr(),
+            tx_item_off.shape[0] - 1, tx_sig_off.data_ptr(), p(scheme), p(key), key_off.data_ptr(), key.numel(),
+            p(sig), sig_off.data_ptr(), sig.numel(), scheme.numel(), txid.data_ptr(), tx_status.data_ptr(),
+            first_bad.data_ptr(), p(sig_status), s), "cordahip_signed_txcomp_verify_device")
+
     def txcomp_inputs_device(self, items, n_items: int, payload, tx_item_off, refs, tx_ref_off, tw_from, tw_until,
                              gate, tx_status=None, ref_cap: Optional[int] = None, device: int = 0, stream=None):
         """cordahip_txcomp_inputs_device (K22): the STATE_REF and TIME_WINDOW items of the component
@@ -875,6 +901,26 @@ class Engine:
             msgs.data_ptr() if msgs.shape[1] else None, msgs.shape[1], mod.shape[1], mod.shape[0],
             status.data_ptr(), verdict.data_ptr() if verdict is not None else None, s),
             "cordahip_rsa_pss_verify_device")
+
+    def sig_verify_device(self, scheme, key, key_off, sig, sig_off, msgs, status, verdict=None, msg_row=None,
+                          is_valid: bool = False, rsa_on_device: bool = False, device: int = 0, stream=None,
+                          key_bytes=None, sig_bytes=None):
+        """The generic mixed-scheme batch resident in HBM (K23): scheme [n] uint8, key / sig uint8 byte
+        buffers with key_off / sig_off [n + 1] int64 CSR offsets, msgs [rows, L] uint8, msg_row [n] int32
+        (None: lane i signs row i). Classified, packed and verified on the GPU; statuses in lane order
+        (BAD_RANGE for a lane whose ranges or message row are out of bounds). key_bytes / sig_bytes:
+        the buffers' declared sizes (default: the tensors')."""
+        s = stream.cuda_stream if stream is not None else 0
+        flags = (_lib.FLAG_IS_VALID if is_valid else 0) | (_lib.FLAG_RSA_ON_DEVICE if rsa_on_device else 0)
+        kb = key.numel() if key_bytes is None else key_bytes
+        sb = sig.numel() if sig_bytes is None else sig_bytes
+        check(lib().cordahip_sig_verify_device(
+            self._ctx, device, scheme.data_ptr() if scheme.numel() else None, key.data_ptr() if key.numel() else None,
+            key_off.data_ptr(), kb, sig.data_ptr() if sig.numel() else None, sig_off.data_ptr(), sb,
+            msgs.data_ptr() if msgs.numel() else None, msgs.shape[1], msg_row.data_ptr() if msg_row is not None else None,
+            msgs.shape[0], scheme.numel(), flags, status.data_ptr() if status.numel() else None,
+            verdict.data_ptr() if verdict is not None else None, s),
+            "cordahip_sig_verify_device")
 
     # ---- FilteredTransaction.verify / PartialMerkleTree.verify ----------------
     def filtered_tx_verify(self, ftxs, async_: bool = False):

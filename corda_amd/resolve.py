@@ -481,7 +481,7 @@ def notarise_tearoffs_persisted(engine, log_id: int, tearoffs, callers, key_id: 
 
 
 def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_id: int, now: int, tolerance: int,
-                          device: int = 0, stream=None, detail: Optional[dict] = None):
+                          device: int = 0, stream=None, detail: Optional[dict] = None, notary_family: str = "ed25519"):
     """What a VALIDATING notary (ValidatingNotaryFlow) or any node that commits what it resolved does
     with full transactions, on torch device tensors and ONE stream, with no device-to-host copy
     before the final download (K22):
@@ -491,12 +491,17 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
       3. Engine.commit_inputs_device                 txid = the ids of step 1, gated
       4. Engine.ed25519_sign_keyed_device            over the ids, gated by the commit status
     so the inputs that are committed are the components whose hashes made the id that was signed.
-    Ed25519 only, like the device-resident signed-tx calls it stands on: every transaction signature
-    and the notary's key `key_id`. Contract verification and required-signer coverage
-    (Engine.tx_cover_device between steps 1 and 2) are the caller's.
+    Contract verification and required-signer coverage (Engine.tx_cover_device between steps 1
+    and 2) are the caller's.
 
     stxs_as_components[t] = (components, sigs): components as (kind, value, class_id) tuples
-    (_lib.kryo_pack's form, availableComponents order), sigs = [(key 32 bytes, signature 64 bytes)].
+    (_lib.kryo_pack's form, availableComponents order), sigs = [(key 32 bytes, signature 64 bytes)]
+    -- Ed25519 pairs, the dense path above -- or (scheme, key, sig) triples of any scheme (K23). When
+    any triple is present, step 1 is Engine.signed_txcomp_verify_device over all of the batch's
+    signatures (a pair counts as an Ed25519 triple): classified and packed on the GPU, RSA_SHA256
+    following Engine.set_rsa_on_device. notary_family: "ed25519" (step 4 as above, 64-byte answers)
+    or "ecdsa" (key_id is an ECDSA signer's: Engine.ecdsa_sign_keyed_device, DER answers). RSA
+    notary keys need caller-drawn salts and stay out.
     callers[t]: the requesting party's id; now / tolerance in ns; `device` is the log's.
 
     Returns (answers, committed_rows) in notarise_tearoffs's shape: answers[t] the notary's signature
@@ -521,10 +526,21 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
     tio[1:] = np.cumsum([len(comps) for comps, _ in stxs_as_components])
     tso = np.zeros(n + 1, np.int64)
     tso[1:] = np.cumsum([len(sg) for _, sg in stxs_as_components])
+    assert notary_family in ("ed25519", "ecdsa")
     flat = [x for _, sg in stxs_as_components for x in sg]
-    assert all(len(k) == 32 and len(g) == 64 for k, g in flat), "Ed25519 keys and signatures only"
-    keys = np.frombuffer(b"".join(bytes(k) for k, _ in flat) or bytes(32), np.uint8).reshape(-1, 32)
-    sigs = np.frombuffer(b"".join(bytes(g) for _, g in flat) or bytes(64), np.uint8).reshape(-1, 64)
+    mixed = any(len(x) == 3 for x in flat)
+    if mixed:  # every signature as a (scheme, key, sig) triple, CSR
+        flat = [x if len(x) == 3 else (4, x[0], x[1]) for x in flat]
+        sch = np.asarray([x[0] for x in flat], np.uint8)
+        key_off, sig_off = np.zeros(len(flat) + 1, np.int64), np.zeros(len(flat) + 1, np.int64)
+        key_off[1:] = np.cumsum([len(x[1]) for x in flat])
+        sig_off[1:] = np.cumsum([len(x[2]) for x in flat])
+        keys = np.frombuffer(b"".join(bytes(x[1]) for x in flat), np.uint8)
+        sigs = np.frombuffer(b"".join(bytes(x[2]) for x in flat), np.uint8)
+    else:
+        assert all(len(k) == 32 and len(g) == 64 for k, g in flat), "Ed25519 keys and signatures only"
+        keys = np.frombuffer(b"".join(bytes(k) for k, _ in flat) or bytes(32), np.uint8).reshape(-1, 32)
+        sigs = np.frombuffer(b"".join(bytes(g) for _, g in flat) or bytes(64), np.uint8).reshape(-1, 64)
     nsig, n_items = len(flat), len(items)
     ref_cap = int((items["kind"] == _lib.KRYO_KINDS["state_ref"]).sum())
     with torch.cuda.stream(s):
@@ -532,7 +548,10 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
         z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
         d_items = up(items.view(np.uint8).reshape(-1, _lib.KRYO_ITEM_DTYPE.itemsize)) if n_items else z(1, 32)
         d_blob, d_tio, d_tso = up(blob), up(tio), up(tso)
-        d_keys, d_sigs = up(keys)[:max(nsig, 1)], up(sigs)[:max(nsig, 1)]
+        if mixed:
+            d_sch, d_keys, d_sigs, d_key_off, d_sig_off = up(sch), up(keys), up(sigs), up(key_off), up(sig_off)
+        else:
+            d_keys, d_sigs = up(keys)[:max(nsig, 1)], up(sigs)[:max(nsig, 1)]
         d_caller = up(np.asarray(callers, np.int32))
         d_key_id = torch.full((n,), key_id, dtype=torch.int32, device=dev)
         txid, v_status, first_bad, sig_status = z(n, 32), z(n), z(n, dt=torch.int64), z(max(nsig, 1))
@@ -540,19 +559,29 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
         tw_from, tw_until, gate = z(n, dt=torch.int64), z(n, dt=torch.int64), z(n)
         c_status, committed = z(n), z(n)
         ref_state, ref_by = z(max(ref_cap, 1)), z(max(ref_cap, 1), 40)
-        n_sigs, s_status = z(n, 64), z(n)
-        engine.signed_txcomp_verify_ed25519_device(d_items, n_items, d_blob, d_tio, d_tso, d_keys[:nsig], d_sigs[:nsig],
-                                                   txid, v_status, first_bad, sig_status, device=device, stream=s)
+        ecdsa_notary = notary_family == "ecdsa"
+        n_sigs, n_sig_len, s_status = z(n, 72 if ecdsa_notary else 64), z(n), z(n)
+        if mixed:
+            engine.signed_txcomp_verify_device(d_items, n_items, d_blob, d_tio, d_tso, d_sch, d_keys, d_key_off, d_sigs,
+                                               d_sig_off, txid, v_status, first_bad, sig_status, device=device, stream=s)
+        else:
+            engine.signed_txcomp_verify_ed25519_device(d_items, n_items, d_blob, d_tio, d_tso, d_keys[:nsig],
+                                                       d_sigs[:nsig], txid, v_status, first_bad, sig_status,
+                                                       device=device, stream=s)
         engine.txcomp_inputs_device(d_items, n_items, d_blob, d_tio, refs, tx_ref_off, tw_from, tw_until, gate,
                                     tx_status=v_status, ref_cap=ref_cap, device=device, stream=s)
         engine.commit_inputs_device(log_id, txid, d_caller, refs[:ref_cap], tx_ref_off, c_status, committed,
                                     ref_state, ref_by, tw_from, tw_until, now, tolerance, gate=gate, stream=s)
-        engine.ed25519_sign_keyed_device(d_key_id, txid, n_sigs, s_status, gate=c_status, device=device, stream=s)
+        if ecdsa_notary:
+            engine.ecdsa_sign_keyed_device(d_key_id, txid, n_sigs, n_sig_len, s_status, gate=c_status, device=device,
+                                           stream=s)
+        else:
+            engine.ed25519_sign_keyed_device(d_key_id, txid, n_sigs, s_status, gate=c_status, device=device, stream=s)
         status = torch.where(gate != 0, gate, c_status)
         # the one download
         out = [x.cpu().numpy() for x in (txid, status, committed, refs, tx_ref_off, ref_by, ref_state, n_sigs,
-                                         s_status, v_status)]
-    ids_a, status_a, committed_a, refs_a, off_a, by_a, state_a, sig_a, sst_a, verify_a = out
+                                         s_status, v_status, n_sig_len)]
+    ids_a, status_a, committed_a, refs_a, off_a, by_a, state_a, sig_a, sst_a, verify_a, sig_len_a = out
     if detail is not None:
         detail.update(ids=ids_a, status=status_a, committed=committed_a, refs=refs_a[:ref_cap], tx_ref_off=off_a,
                       ref_state=state_a[:ref_cap], verify_status=verify_a)
@@ -562,7 +591,9 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
         mine = [(refs_a[i, :32].tobytes(), int.from_bytes(refs_a[i, 32:].tobytes(), "little"))
                 for i in range(int(off_a[t]), int(off_a[t + 1]))]
         if st not in _COMMIT_STATUSES or st == 18:
-            answers.append(NotaryError("TransactionInvalid", txid_t if int(verify_a[t]) in (OK, BAD_SIG) else None))
+            # the id exists unless the tree or a component failed (mixed: a signature may fail in more ways)
+            has_id = int(verify_a[t]) not in (6, 9) if mixed and st not in _COMMIT_STATUSES else int(verify_a[t]) in (OK, BAD_SIG)
+            answers.append(NotaryError("TransactionInvalid", txid_t if has_id else None))
         elif st == _COMMIT_TIME_WINDOW_INVALID:
             answers.append(NotaryError("TimeWindowInvalid", txid_t))
         elif st == _COMMIT_CONFLICT:
@@ -576,7 +607,7 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
         elif int(sst_a[t]) == _SIGN_UNKNOWN_KEY:
             raise NoSuchElementException("no registered key %d" % key_id)
         else:
-            answers.append(sig_a[t].tobytes())
+            answers.append(sig_a[t, :int(sig_len_a[t])].tobytes() if ecdsa_notary else sig_a[t].tobytes())
         if committed_a[t]:
             last = {}
             for i, r in enumerate(mine):

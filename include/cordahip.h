@@ -226,6 +226,43 @@ int cordahip_rsa_pss_verify_device(cordahip_ctx* ctx, int device, const void* d_
                                    const void* d_sigs, const void* d_sig_len, const void* d_msgs, uint32_t msg_len,
                                    uint32_t mod_words, uint64_t n, void* d_status, void* d_verdict, void* hip_stream);
 
+/* ---- the generic batch resident in device memory (K23) ------------------------- *
+ * cordahip_sig_verify for a batch that already sits in HBM: scheme[n], the keys and
+ * signatures as CSR (d_key_off / d_sig_off: uint64[n + 1], 8-byte aligned; the byte
+ * buffers at any alignment, key_bytes / sig_bytes their declared sizes) and the
+ * messages as msg_rows dense rows of msg_len bytes. d_msg_row (uint32[n], or NULL:
+ * lane i signs row i) says which row a lane signs, so many signatures may share one
+ * row (a transaction's id) without a copy per lane. The batch is classified and
+ * packed into the verifiers' dense rows on the GPU, by the rule of cordahip_sig_verify
+ * lane for lane, each family's generic verifier runs over its rows only, and the
+ * statuses come back in lane order: enqueued on hip_stream, asynchronous to the host,
+ * nothing read back. flags: CORDAHIP_FLAG_IS_VALID and / or CORDAHIP_FLAG_RSA_ON_DEVICE
+ * with the meanings of cordahip_sig_batch; without the latter RSA_SHA256 lanes are
+ * UNSUPPORTED and no RSA memory is allocated. d_verdict (uint64[(n + 63) / 64], bit =
+ * status OK) may be NULL. Registered keys are not consulted: the call runs the generic
+ * verifiers whatever cordahip_vkey_set_routing* say.
+ *
+ * The host cannot see the offsets, so what is CORDAHIP_ERR_INVALID_ARG for a host batch
+ * is a per-lane status here, as CORDAHIP_TX_BAD_COVER is for cordahip_tx_cover_device:
+ * a lane whose key or signature range is reversed or reaches past key_bytes / sig_bytes,
+ * or whose message row is >= msg_rows, gets CORDAHIP_STATUS_BAD_RANGE, and not one byte
+ * of it is read. (The value is parenthesised like the error codes: the six statuses at
+ * the top are Crypto.kt's, this one exists for device-resident batches only.)
+ * Key ranges may overlap (many lanes over one key's bytes). The RSA rows are sized from
+ * key_bytes (a key of 1024..2048 / ..3072 / ..4096 bits takes more than 131 / 260 / 388
+ * bytes), so with overlapping ranges a width class can hold more RSA lanes than rows: the
+ * lanes past key_bytes / 131 (260, 388) of their class, in lane order, are
+ * CORDAHIP_STATUS_BAD_RANGE too. Disjoint ranges never meet this.
+ * n >= 2^31 is CORDAHIP_ERR_INVALID_ARG (row indices are 32-bit). Scratch is per device
+ * and grow-only (about 330 + 2 msg_len bytes a lane; with the RSA flag up to
+ * key_bytes / 131 rows of 1.1 KB and fewer, wider ones), released by cordahip_trim. */
+#define CORDAHIP_STATUS_BAD_RANGE (19)
+int cordahip_sig_verify_device(cordahip_ctx* ctx, int device, const void* d_scheme, const void* d_key,
+                               const void* d_key_off, uint64_t key_bytes, const void* d_sig, const void* d_sig_off,
+                               uint64_t sig_bytes, const void* d_msgs, uint32_t msg_len, const void* d_msg_row,
+                               uint64_t msg_rows, uint64_t n, uint32_t flags, void* d_status, void* d_verdict,
+                               void* hip_stream);
+
 /* ---- streaming mixed-scheme drain (verifier-module queue) ----- *
  * Replaces the per-request Crypto.isValid calls a verifier would make for a
  * queue of mixed-scheme requests (Crypto.kt:534-541; the out-of-process
@@ -989,6 +1026,25 @@ int cordahip_signed_tx_verify_ed25519_device(cordahip_ctx* ctx, int device, cons
                                              const void* d_sigs, uint64_t nsig, void* d_txid, void* d_tx_status,
                                              void* d_first_bad, void* d_sig_status, void* hip_stream);
 
+/* The same for signatures of any scheme (K23): d_keys / d_sigs become a scheme byte per
+ * signature and CSR keys and signatures in HBM (as cordahip_sig_verify_device takes them;
+ * key_bytes / sig_bytes the byte buffers' declared sizes). The id chain is unchanged.
+ * The signatures are classified and packed on the GPU, a signature's message row being
+ * its transaction's id (expanded from d_tx_sig_off on the device, the ids are not copied
+ * per signature), and verified by doVerify rules with the generic verifiers -- RSA_SHA256
+ * on the GPU while cordahip_set_rsa_on_device is on, UNSUPPORTED otherwise, as in
+ * cordahip_signed_tx_verify; registered keys are not consulted whatever
+ * cordahip_vkey_set_routing* say. Then K5's reduce as above: the signatures of a
+ * transaction whose id failed carry that status. A signature whose ranges are out of
+ * bounds is CORDAHIP_STATUS_BAD_RANGE. The _ed25519_device call stays the fast path for a
+ * caller who knows the batch is dense Ed25519. */
+int cordahip_signed_tx_verify_device(cordahip_ctx* ctx, int device, const void* d_leaf_bytes, const void* d_leaf_off,
+                                     uint64_t nleaves, const void* d_tx_leaf_off, uint64_t ntx,
+                                     const void* d_tx_sig_off, const void* d_scheme, const void* d_key,
+                                     const void* d_key_off, uint64_t key_bytes, const void* d_sig,
+                                     const void* d_sig_off, uint64_t sig_bytes, uint64_t nsig, void* d_txid,
+                                     void* d_tx_status, void* d_first_bad, void* d_sig_status, void* hip_stream);
+
 /* FilteredTransaction.verify over many filtered transactions:
  *   FilteredTransaction.verify   core/.../transactions/MerkleTransaction.kt:134-140
  *   PartialMerkleTree.verify     core/.../crypto/PartialMerkleTree.kt:132-158
@@ -1358,6 +1414,15 @@ int cordahip_signed_txcomp_verify_ed25519_device(cordahip_ctx* ctx, int device, 
                                                  const void* d_tx_sig_off, const void* d_keys, const void* d_sigs,
                                                  uint64_t nsig, void* d_txid, void* d_tx_status, void* d_first_bad,
                                                  void* d_sig_status, void* hip_stream);
+/* ... and for signatures of any scheme (K23): the component-level call with the
+ * signatures as cordahip_signed_tx_verify_device takes them, and its rules. */
+int cordahip_signed_txcomp_verify_device(cordahip_ctx* ctx, int device, const void* d_items, uint64_t n_items,
+                                         uint32_t group, const void* d_payload, uint64_t payload_len,
+                                         const void* d_tx_item_off, uint64_t ntx, const void* d_tx_sig_off,
+                                         const void* d_scheme, const void* d_key, const void* d_key_off,
+                                         uint64_t key_bytes, const void* d_sig, const void* d_sig_off,
+                                         uint64_t sig_bytes, uint64_t nsig, void* d_txid, void* d_tx_status,
+                                         void* d_first_bad, void* d_sig_status, void* hip_stream);
 
 /* ---- required-signer coverage (the second half of verifySignatures) ---------- *
  * SignedTransaction.verifySignatures (SignedTransaction.kt:70-85) is

@@ -199,6 +199,8 @@ int main() {
     visited(ts, kTxSetPlain, "TxSet");
     visited(ew, 0, "EcWork");
     visited(rw, 0, "RsaWork");
+    SigPackWork sp;
+    visited(sp, 0, "SigPackWork");
   }
   auto* d = new Device;
   d->bind(3);
@@ -213,9 +215,10 @@ int main() {
     // and the ECDSA signer's table with what the host knows of it (f)
     // and the registered RSA keys' table (f)
     // and the RSA signer's table with what the host knows of it (f)
+    // and the mixed-scheme device calls' mutex (sigpack_mu; their scratch is visited)
     constexpr size_t kDeviceOwnPlain = 1288 + 2 * sizeof(std::mutex) + sizeof(SignKeys) + 2 * sizeof(std::mutex) +
                                        sizeof(VerifyKeys) + sizeof(EcVerifyKeys) + 24 + sizeof(EcSignKeys) +
-                                       sizeof(RsaVerifyKeys) + sizeof(RsaSignKeys);
+                                       sizeof(RsaVerifyKeys) + sizeof(RsaSignKeys) + sizeof(std::mutex);
     const Count c = visited(*d, kDeviceOwnPlain + kTxSets * kTxSetPlain + kPackStages * kPackPlain, "Device");
     ndev = c.ndev, npin = c.npin, nev = c.nfence + c.nevent;
     CHECK(c.nstream == 7);
