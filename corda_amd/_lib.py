@@ -55,6 +55,7 @@ EXPORTS = [
     "cordahip_vkey_set_routing", "cordahip_vkey_route_stats",
     "cordahip_vkey_set_routing_ecdsa", "cordahip_vkey_route_stats_ecdsa",
     "cordahip_vkey_set_routing_rsa", "cordahip_vkey_route_stats_rsa", "cordahip_set_rsa_on_device",
+    "cordahip_vkey_set_routing_device",
     "cordahip_commit_log_create", "cordahip_commit_log_destroy", "cordahip_commit_log_reserve",
     "cordahip_commit_log_stats", "cordahip_commit_log_load", "cordahip_commit_log_lookup",
     "cordahip_commit_inputs", "cordahip_commit_inputs_submit", "cordahip_commit_inputs_device",
@@ -448,6 +449,7 @@ def lib() -> ctypes.CDLL:
         "cordahip_vkey_set_routing_ecdsa": (i32, [vp, u32]),
         "cordahip_vkey_route_stats_ecdsa": (i32, [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "cordahip_vkey_set_routing_rsa": (i32, [vp, u32]),
+        "cordahip_vkey_set_routing_device": (i32, [vp, u32]),
         "cordahip_set_rsa_on_device": (i32, [vp, u32]),
         "cordahip_vkey_route_stats_rsa": (i32, [vp, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "cordahip_verify_keyed": (i32, [vp, ctypes.POINTER(KeyedSigBatch)]),

@@ -48,14 +48,18 @@ __global__ void __launch_bounds__(64) ecdsa_route_gather_kernel(const uint32_t* 
 
 // hdr: the scratch header the gather kernel filled; route: route[n] behind it.
 // counts: the partition's seven class counts (zeroed by the launcher). totals: the
-// device's cumulative keyed / generic lane counters.
+// device's cumulative keyed / generic lane counters. count (K24, the mixed device calls;
+// null: every one of the n lanes): the rows to partition, known on the device only and
+// clipped to n before anything is indexed; rows at or past it enter no class.
 __global__ void __launch_bounds__(256) ecdsa_route_kernel(const uint8_t* __restrict__ scheme,
                                                          const uint8_t* __restrict__ keys,
                                                          const uint8_t* __restrict__ key_len, uint64_t n,
                                                          const uint32_t* __restrict__ hdr,
                                                          uint32_t* __restrict__ route,
                                                          unsigned int* __restrict__ counts,
-                                                         unsigned long long* __restrict__ totals) {
+                                                         unsigned long long* __restrict__ totals,
+                                                         const uint32_t* __restrict__ count) {
+  if (count) n = route_count_clip(*count, n);
   __shared__ uint32_t recs[kVkeySlots * kEcRouteRecWords];
   __shared__ unsigned int part[kEcRouteClasses][4];
   const uint32_t nlive = hdr[kEcRouteCntLive] < kVkeySlots ? hdr[kEcRouteCntLive] : kVkeySlots;
@@ -97,7 +101,9 @@ __global__ void __launch_bounds__(256) ecdsa_scatter_routed_kernel(const uint8_t
                                                                   const uint32_t* __restrict__ route, uint64_t n,
                                                                   const unsigned int* __restrict__ counts,
                                                                   unsigned int* __restrict__ cursors,
-                                                                  unsigned int* __restrict__ perm) {
+                                                                  unsigned int* __restrict__ perm,
+                                                                  const uint32_t* __restrict__ count) {
+  if (count) n = route_count_clip(*count, n);  // K24, as in the route kernel
   const int lane = threadIdx.x & 63;
   unsigned int tot[kEcRouteClasses] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
 #pragma unroll 4
@@ -185,16 +191,16 @@ uint64_t ecdsa_route_max_lanes() { return kRouteMaxLanes; }
 // and cursors[7], zeroed here) and perm[n] filled; totals += (keyed, generic)
 hipError_t launch_ecdsa_route(const uint8_t* scheme, const uint8_t* keys, const uint8_t* key_len, uint64_t n,
                               const uint32_t* vtab, uint32_t* scratch, unsigned int* counters, unsigned int* perm,
-                              unsigned long long* totals, hipStream_t s) {
+                              unsigned long long* totals, hipStream_t s, const uint32_t* count) {
   if (n == 0 || n > kRouteMaxLanes || !vtab || !scratch || !counters || !perm || !totals) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(counters, 0, 2 * kEcRouteClasses * sizeof(unsigned int), s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(ecdsa_route_gather_kernel, dim3(1), dim3(64), 0, s, vtab, scratch);
   const dim3 pgrid((uint32_t)((n + kEcRouteTile - 1) / kEcRouteTile));
   hipLaunchKernelGGL(ecdsa_route_kernel, pgrid, dim3(256), 0, s, scheme, keys, key_len, n, scratch,
-                     scratch + ec_route_off_route(), counters, totals);
+                     scratch + ec_route_off_route(), counters, totals, count);
   hipLaunchKernelGGL(ecdsa_scatter_routed_kernel, pgrid, dim3(256), 0, s, scheme, key_len,
-                     scratch + ec_route_off_route(), n, counters, counters + kEcRouteClasses, perm);
+                     scratch + ec_route_off_route(), n, counters, counters + kEcRouteClasses, perm, count);
   return hipGetLastError();
 }
 

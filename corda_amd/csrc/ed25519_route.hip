@@ -18,10 +18,15 @@ namespace cordahip {
 
 // scratch: ed25519_route.hpp's layout for n lanes, its two counts zeroed by the
 // launcher. totals: the device's cumulative keyed / generic lane counters.
+// count (K24, the mixed device calls; null: every one of the n lanes): the rows to
+// partition are known on the device only. It is clipped to n, the bound the launch and
+// the scratch were sized for, before anything is indexed; rows at or past it enter
+// neither list and neither total.
 __global__ void __launch_bounds__(256) ed25519_route_kernel(const uint8_t* __restrict__ keys, uint64_t n,
                                                            const uint32_t* __restrict__ vtab,
                                                            uint32_t* __restrict__ scratch,
-                                                           unsigned long long* __restrict__ totals) {
+                                                           unsigned long long* __restrict__ totals,
+                                                           const uint32_t* __restrict__ count) {
   __shared__ uint32_t recs[kVkeySlots * kRouteRecWords];
   __shared__ uint32_t nlive_s;
   const uint32_t lane = threadIdx.x & 63;
@@ -39,6 +44,7 @@ __global__ void __launch_bounds__(256) ed25519_route_kernel(const uint8_t* __res
   }
   __syncthreads();
   const uint32_t nlive = nlive_s;
+  const uint64_t m = count ? route_count_clip(*count, n) : n;
   uint32_t* route = scratch + route_off_route(n);
   uint32_t* keyed = scratch + route_off_keyed(n);
   uint32_t* generic = scratch + route_off_generic(n);
@@ -48,15 +54,15 @@ __global__ void __launch_bounds__(256) ed25519_route_kernel(const uint8_t* __res
   for (int it = 0; it < kRouteIter; it++) {
     const uint64_t i = route_tile_lane(blockIdx.x, it, threadIdx.x);
     id[it] = kVkeyNoId;
-    if (i < n) {
+    if (i < m) {
       const uint4* k4 = reinterpret_cast<const uint4*>(keys + i * 32);
       const uint4 a = k4[0], b = k4[1];
       const uint32_t key[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
       id[it] = route_match(key, recs, nlive);
       route[i] = id[it];
     }
-    nk += (uint32_t)__popcll(__ballot(i < n && id[it] != kVkeyNoId));
-    ng += (uint32_t)__popcll(__ballot(i < n && id[it] == kVkeyNoId));
+    nk += (uint32_t)__popcll(__ballot(i < m && id[it] != kVkeyNoId));
+    ng += (uint32_t)__popcll(__ballot(i < m && id[it] == kVkeyNoId));
   }
   // the wave's range of each list: one atomic per list (and per cumulative counter)
   uint32_t sk = 0, sg = 0;
@@ -75,7 +81,7 @@ __global__ void __launch_bounds__(256) ed25519_route_kernel(const uint8_t* __res
 #pragma unroll
   for (int it = 0; it < kRouteIter; it++) {
     const uint64_t i = route_tile_lane(blockIdx.x, it, threadIdx.x);
-    const bool in = i < n, hit = in && id[it] != kVkeyNoId, miss = in && id[it] == kVkeyNoId;
+    const bool in = i < m, hit = in && id[it] != kVkeyNoId, miss = in && id[it] == kVkeyNoId;
     const unsigned long long bk = __ballot(hit), bg = __ballot(miss);
     if (hit) keyed[sk + route_rank(bk, lane)] = (uint32_t)i;
     if (miss) generic[sg + route_rank(bg, lane)] = (uint32_t)i;
@@ -100,12 +106,13 @@ size_t ed25519_route_scratch_bytes(uint64_t n) {
 uint64_t ed25519_route_max_lanes() { return kRouteMaxLanes; }
 
 hipError_t launch_ed25519_route(const uint8_t* keys, uint64_t n, const uint32_t* vtab, uint32_t* scratch,
-                                unsigned long long* totals, hipStream_t s) {
+                                unsigned long long* totals, hipStream_t s, const uint32_t* count) {
   if (n == 0 || n > kRouteMaxLanes || !vtab || !scratch || !totals) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(scratch, 0, 2 * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
   const uint64_t blocks = (n + kRouteTile - 1) / kRouteTile;
-  hipLaunchKernelGGL(ed25519_route_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, keys, n, vtab, scratch, totals);
+  hipLaunchKernelGGL(ed25519_route_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, keys, n, vtab, scratch, totals,
+                     count);
   return hipGetLastError();
 }
 

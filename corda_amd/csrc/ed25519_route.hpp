@@ -80,6 +80,11 @@ VKEY_HD uint32_t route_match(const uint32_t key[8], const uint32_t* gathered, ui
   return kVkeyNoId;
 }
 
+// K24, the counted instances of the three families' route passes: a row count read
+// from device memory is the caller's data, so it is clipped to the bound the launch
+// and its scratch were sized for before anything is indexed
+VKEY_HD constexpr uint64_t route_count_clip(uint64_t count, uint64_t bound) { return count < bound ? count : bound; }
+
 // the lane that thread t (0..255) of the block owning `tile` visits in stride `it`
 VKEY_HD constexpr uint64_t route_tile_lane(uint64_t tile, int it, uint32_t t) {
   return tile * kRouteTile + (uint64_t)it * 256 + t;

@@ -1075,7 +1075,8 @@ int route_stats(cordahip_ctx* ctx, int device, Keys Device::*keys, uint64_t* key
     return CORDAHIP_SUCCESS;
   });
 }
-// a family's routing switch (Device::route_on, Device::ec_route_on, Device::rsa_route_on) on every device
+// a routing switch (Device::route_on, Device::ec_route_on, Device::rsa_route_on, Device::sig_route_on) on
+// every device
 int set_routing(cordahip_ctx* ctx, std::atomic<uint32_t> Device::*sw, uint32_t on) {
   if (!ctx) return CORDAHIP_ERR_INVALID_ARG;
   for (auto& dp : ctx->devs) ((*dp).*sw).store(on ? 1u : 0u);
@@ -1234,6 +1235,11 @@ int cordahip_vkey_set_routing_rsa(cordahip_ctx* ctx, uint32_t on) {
 
 int cordahip_vkey_route_stats_rsa(cordahip_ctx* ctx, int device, uint64_t* keyed_rows, uint64_t* generic_rows) {
   return route_stats(ctx, device, &Device::rsa_vkeys, keyed_rows, generic_rows);
+}
+
+// K24: whether the mixed device calls (runtime.cpp sig_device_enqueue) consult the three switches above
+int cordahip_vkey_set_routing_device(cordahip_ctx* ctx, uint32_t on) {
+  return set_routing(ctx, &Device::sig_route_on, on);
 }
 
 int cordahip_verify_keyed(cordahip_ctx* ctx, const cordahip_keyed_sig_batch* batch) {

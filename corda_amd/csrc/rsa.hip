@@ -529,8 +529,7 @@ hipError_t launch_rsa_pss_verify(const uint32_t* mod, const uint32_t* exp, const
 // past the count return as blocks. iota: at least min(ws_rows, n) words.
 __global__ void rsa_launch_count_kernel(const unsigned int* __restrict__ count, uint64_t lo, uint64_t m,
                                         unsigned int* __restrict__ out) {
-  const uint64_t c = *count;
-  *out = (unsigned int)(c > lo ? (c - lo < m ? c - lo : m) : 0);
+  *out = (unsigned int)rsa_route_launch_count(*count, lo, m);
 }
 
 template <int W>
@@ -540,6 +539,17 @@ static hipError_t launch_modexp_counted(const uint32_t* mod, const uint32_t* exp
   hipLaunchKernelGGL((rsa_modexp_kernel<W, true>), dim3((uint32_t)rsa_route_idx_blocks(m)), dim3(kBlock), 0, s, mod,
                      exp, words, (uint64_t)0, words, bad, (const uint8_t*)nullptr, iota, count);
   return hipGetLastError();
+}
+
+static hipError_t modexp_counted_any(uint32_t W, const uint32_t* mod, const uint32_t* exp, uint32_t* words, uint64_t m,
+                                     uint8_t* bad, const unsigned int* iota, const unsigned int* count,
+                                     hipStream_t s) {
+  switch (W) {
+    case 64: return launch_modexp_counted<64>(mod, exp, words, m, bad, iota, count, s);
+    case 96: return launch_modexp_counted<96>(mod, exp, words, m, bad, iota, count, s);
+    case 128: return launch_modexp_counted<128>(mod, exp, words, m, bad, iota, count, s);
+  }
+  return hipErrorInvalidValue;
 }
 
 uint64_t rsa_counted_launches(uint64_t n, uint64_t ws_rows) {
@@ -570,11 +580,7 @@ hipError_t launch_rsa_pss_verify_counted(const uint32_t* mod, const uint32_t* ex
                        bits, st, (const unsigned int*)lc);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    switch (W) {
-      case 64: e = launch_modexp_counted<64>(mod + lo * W, exp + lo, words, m, bad, iota, lc, s); break;
-      case 96: e = launch_modexp_counted<96>(mod + lo * W, exp + lo, words, m, bad, iota, lc, s); break;
-      default: e = launch_modexp_counted<128>(mod + lo * W, exp + lo, words, m, bad, iota, lc, s); break;
-    }
+    e = modexp_counted_any(W, mod + lo * W, exp + lo, words, m, bad, iota, lc, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rsa_pss_check_kernel, grid, dim3(256), 0, s, words, bits, st, bad, msgs + lo * msg_len,
                        (const uint64_t*)nullptr, msg_len, W, m, status + lo, (unsigned long long*)nullptr,

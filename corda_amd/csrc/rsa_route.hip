@@ -17,7 +17,9 @@ namespace {
 
 // One lane per row (rsa_route.hpp). hdr: the scratch's header (the two list counts,
 // cleared by the launcher); totals: the device's cumulative keyed / generic row
-// counters. 1 KiB of LDS for the candidates.
+// counters. 1 KiB of LDS for the candidates. count (K24, the mixed device calls; null:
+// every one of the n rows): the launch's rows, known on the device only and clipped to n
+// before anything is indexed; rows at or past it enter neither list and neither total.
 __global__ void __launch_bounds__(kRsaRouteBlock) rsa_route_kernel(const uint32_t* __restrict__ mod,
                                                                   const uint32_t* __restrict__ exp,
                                                                   const uint8_t* __restrict__ st, uint32_t W,
@@ -26,7 +28,8 @@ __global__ void __launch_bounds__(kRsaRouteBlock) rsa_route_kernel(const uint32_
                                                                   uint32_t* __restrict__ route,
                                                                   unsigned int* __restrict__ keyed,
                                                                   unsigned int* __restrict__ generic,
-                                                                  unsigned long long* __restrict__ totals) {
+                                                                  unsigned long long* __restrict__ totals,
+                                                                  const unsigned int* __restrict__ count) {
   __shared__ uint32_t cand[kVkeySlots * kRsaRouteCandWords];
   __shared__ uint32_t ncand_s;
   if (threadIdx.x < 64) {  // wave 0: one lane per slot, the live records in slot order
@@ -39,6 +42,7 @@ __global__ void __launch_bounds__(kRsaRouteBlock) rsa_route_kernel(const uint32_
   }
   __syncthreads();
   const uint32_t ncand = ncand_s;
+  if (count) n = route_count_clip(*count, n);
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t i = rsa_route_row(blockIdx.x, threadIdx.x);
   bool is_keyed = false, is_generic = false, listed = false;
@@ -106,26 +110,33 @@ uint64_t rsa_launch_rows(uint64_t ws_rows) { return std::min(ws_rows, kMaxLaunch
 //   keyed: the counts cleared, the route pass, K18's exponentiation over the keyed list
 //   tail:  K8's exponentiation over the generic list, the check; routed false (no key was
 //          live any more when the middle part's turn came): K8's over every row, as unrouted
+// count (K24, K23's convention; null for the dense calls): the batch's rows are known on
+// the device only, n is the host's bound. The head leaves the launch's rows, clipped to
+// m, in *launch_count (rsa_launch_count_kernel); the prep, the route pass and the check
+// stop there, and an unrouted tail runs K8's indexed instance over iota.
 hipError_t launch_rsa_routed_head(const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
                                   const uint16_t* sig_len, const uint64_t* msg_off, uint32_t msg_len, uint32_t W,
                                   uint64_t lo, uint64_t m, const uint8_t* pre, uint8_t* ws, uint64_t ws_rows,
-                                  uint32_t flags, hipStream_t s) {
+                                  uint32_t flags, hipStream_t s, const unsigned int* count,
+                                  unsigned int* launch_count) {
   if (W != 64 && W != 96 && W != 128) return hipErrorInvalidValue;
   ws_rows = rsa_launch_rows(ws_rows);
-  if (!m || m > ws_rows) return hipErrorInvalidValue;
+  if (!m || m > ws_rows || (count && !launch_count)) return hipErrorInvalidValue;
   uint32_t* words = reinterpret_cast<uint32_t*>(ws);
   uint32_t* bits = words + ws_rows * W;
   uint8_t* st = reinterpret_cast<uint8_t*>(bits + ws_rows);
   const dim3 grid((uint32_t)((m + 255) / 256));
+  if (count) hipLaunchKernelGGL(rsa_launch_count_kernel, dim3(1), dim3(1), 0, s, count, lo, m, launch_count);
   hipLaunchKernelGGL(rsa_pss_prep_kernel, grid, dim3(256), 0, s, mod + lo * W, exp + lo, sigs + lo * 4 * W,
                      sig_len + lo, msg_off ? msg_off + lo : nullptr, msg_len, W, m, pre ? pre + lo : nullptr, flags,
-                     words, bits, st, (const unsigned int*)nullptr);
+                     words, bits, st, count ? (const unsigned int*)launch_count : nullptr);
   return hipGetLastError();
 }
 
 hipError_t launch_rsa_routed_keyed(const uint32_t* mod, const uint32_t* exp, uint32_t W, uint64_t lo, uint64_t m,
                                    const uint32_t* tab, uint8_t* ws, uint64_t ws_rows, uint32_t* scratch,
-                                   uint64_t cap_rows, unsigned long long* totals, hipStream_t s) {
+                                   uint64_t cap_rows, unsigned long long* totals, hipStream_t s,
+                                   const unsigned int* launch_count) {
   ws_rows = rsa_launch_rows(ws_rows);
   if (!m || m > ws_rows || m > cap_rows || !tab || !scratch || !totals) return hipErrorInvalidValue;
   uint32_t* words = reinterpret_cast<uint32_t*>(ws);
@@ -138,7 +149,7 @@ hipError_t launch_rsa_routed_keyed(const uint32_t* mod, const uint32_t* exp, uin
   unsigned int* generic = scratch + rsa_route_off_generic(cap_rows);
   hipLaunchKernelGGL(rsa_route_kernel, dim3((uint32_t)((m + kRsaRouteBlock - 1) / kRsaRouteBlock)),
                      dim3(kRsaRouteBlock), 0, s, mod + lo * W, exp + lo, st, W, m, tab, scratch, route, keyed, generic,
-                     totals);
+                     totals, launch_count);
   e = hipGetLastError();
   return e ? e
            : modexp_routed_any(W, mod + lo * W, exp + lo, words, m, bad, tab, scratch, route, keyed, generic, true, s);
@@ -147,9 +158,11 @@ hipError_t launch_rsa_routed_keyed(const uint32_t* mod, const uint32_t* exp, uin
 hipError_t launch_rsa_routed_tail(const uint32_t* mod, const uint32_t* exp, const uint8_t* msgs,
                                   const uint64_t* msg_off, uint32_t msg_len, uint32_t W, uint64_t lo, uint64_t m,
                                   uint8_t* status, unsigned long long* verdict, uint8_t* ws, uint64_t ws_rows,
-                                  const uint32_t* scratch, uint64_t cap_rows, bool routed, hipStream_t s) {
+                                  const uint32_t* scratch, uint64_t cap_rows, bool routed, hipStream_t s,
+                                  const unsigned int* launch_count, const unsigned int* iota) {
   ws_rows = rsa_launch_rows(ws_rows);
   if (!m || m > ws_rows || (routed && (m > cap_rows || !scratch))) return hipErrorInvalidValue;
+  if (launch_count && !routed && !iota) return hipErrorInvalidValue;
   uint32_t* words = reinterpret_cast<uint32_t*>(ws);
   uint32_t* bits = words + ws_rows * W;
   uint8_t* st = reinterpret_cast<uint8_t*>(bits + ws_rows);
@@ -158,11 +171,12 @@ hipError_t launch_rsa_routed_tail(const uint32_t* mod, const uint32_t* exp, cons
       routed ? modexp_routed_any(W, mod + lo * W, exp + lo, words, m, bad, nullptr, scratch,
                                  scratch + rsa_route_off_route(cap_rows), scratch + rsa_route_off_keyed(cap_rows),
                                  scratch + rsa_route_off_generic(cap_rows), false, s)
-             : modexp_any(W, mod + lo * W, exp + lo, words, m, words, bad, st, s);
+      : launch_count ? modexp_counted_any(W, mod + lo * W, exp + lo, words, m, bad, iota, launch_count, s)
+                     : modexp_any(W, mod + lo * W, exp + lo, words, m, words, bad, st, s);
   if (e != hipSuccess) return e;
   const dim3 grid((uint32_t)((m + 255) / 256));
   hipLaunchKernelGGL(rsa_pss_check_kernel, grid, dim3(256), 0, s, words, bits, st, bad,
                      msg_off ? msgs : msgs + lo * msg_len, msg_off ? msg_off + lo : nullptr, msg_len, W, m, status + lo,
-                     verdict ? verdict + lo / 64 : nullptr, (const unsigned int*)nullptr);
+                     verdict ? verdict + lo / 64 : nullptr, launch_count);
   return hipGetLastError();
 }

@@ -115,4 +115,11 @@ VKEY_HD constexpr uint64_t rsa_route_launch_rows(uint64_t ws_rows, uint64_t n, u
   return n - lo < ws_rows ? n - lo : ws_rows;
 }
 
+// K23 / K24: the batch's rows are known on the device only (count); the rows of the launch
+// that holds rows lo .. lo + m of the host's bound, clipped to m (rsa.hip
+// rsa_launch_count_kernel). The route pass clips what it reads once more (route_count_clip).
+VKEY_HD constexpr uint64_t rsa_route_launch_count(uint64_t count, uint64_t lo, uint64_t m) {
+  return count > lo ? (count - lo < m ? count - lo : m) : 0;
+}
+
 }  // namespace cordahip

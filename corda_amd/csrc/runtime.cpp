@@ -236,12 +236,13 @@ uint64_t env_lanes(const char* name, uint64_t dflt) {
 // call -- behind ec_vkeys.ev, followed by ec_vkeys.ev -- the gather, route and scatter
 // passes and K13 over each live curve's run. *routed stays false, and nothing is
 // launched, when no ECDSA key is live any more or the counters cannot be allocated:
-// the caller then takes the unrouted path, which is always right.
+// the caller then takes the unrouted path, which is always right. count (K24, the mixed
+// device call; null for the dense calls): the device's word with the rows below n to route.
 static hipError_t ec_route_and_keyed(Device& d, EcWork& w, const uint8_t* scheme, const uint8_t* keys,
                                      const uint8_t* key_len, const uint8_t* sigs, const uint8_t* sig_len,
                                      const uint8_t* msgs, const uint64_t* msg_off, uint32_t msg_len, uint64_t n,
                                      const uint8_t* pre, uint8_t* status, uint32_t flags, hipStream_t s,
-                                     bool* routed) {
+                                     bool* routed, const uint32_t* count = nullptr) {
   std::lock_guard<std::mutex> vk(d.vkey_mu);
   const auto& book = d.ec_vkeys.book;
   if (!d.ec_vkeys.tab.p || !book.any_live()) return hipSuccess;
@@ -258,7 +259,7 @@ static hipError_t ec_route_and_keyed(Device& d, EcWork& w, const uint8_t* scheme
   return fenced({&d.ec_vkeys.ev}, s, [&] {
     const hipError_t e =
         launch_ecdsa_route(scheme, keys, key_len, n, vtab, w.route.as<uint32_t>(), w.counters.as<unsigned int>(),
-                           w.perm.as<unsigned int>(), d.ec_vkeys.route_tot.as<unsigned long long>(), s);
+                           w.perm.as<unsigned int>(), d.ec_vkeys.route_tot.as<unsigned long long>(), s, count);
     return e ? e
              : launch_ecdsa_verify_keyed_idx(w.route.as<uint32_t>(), w.perm.as<unsigned int>(),
                                              w.counters.as<unsigned int>(), n, sigs, sig_len, msgs, msg_off, msg_len,
@@ -360,8 +361,11 @@ hipError_t rsa_ws_grow(Device& d, uint32_t W, uint64_t n) {
 // rsa_vkeys.ev -- the route pass and K18's exponentiation over the keyed list. *routed
 // stays false, and nothing is launched, when no RSA key is live any more or the
 // counters cannot be allocated: the launch then runs unrouted, which is always right.
+// launch_count (K24, the mixed device call; null for the dense calls): the device's word
+// with the launch's rows below m, as launch_rsa_routed_head left it.
 static hipError_t rsa_route_and_keyed(Device& d, const uint32_t* mod, const uint32_t* exp, uint32_t W, uint64_t lo,
-                                      uint64_t m, uint64_t ws_rows, uint64_t cap_rows, hipStream_t s, bool* routed) {
+                                      uint64_t m, uint64_t ws_rows, uint64_t cap_rows, hipStream_t s, bool* routed,
+                                      const unsigned int* launch_count = nullptr) {
   RsaWork& w = d.rsa;
   std::lock_guard<std::mutex> vk(d.vkey_mu);
   RsaVerifyKeys& k = d.rsa_vkeys;
@@ -377,7 +381,8 @@ static hipError_t rsa_route_and_keyed(Device& d, const uint32_t* mod, const uint
   *routed = true;
   return fenced({&k.ev}, s, [&] {
     return launch_rsa_routed_keyed(mod, exp, W, lo, m, k.tab.as<uint32_t>(), w.ws.as<uint8_t>(), ws_rows,
-                                   w.route.as<uint32_t>(), cap_rows, k.route_tot.as<unsigned long long>(), s);
+                                   w.route.as<uint32_t>(), cap_rows, k.route_tot.as<unsigned long long>(), s,
+                                   launch_count);
   });
 }
 
@@ -470,11 +475,13 @@ static hipError_t ed_ws_grow(Device& d, int slot, uint64_t n, bool more_needed, 
 // behind vkeys.ev, followed by vkeys.ev -- the route and partition pass and K12 over
 // the keyed list. *routed stays false, and nothing is launched, when no Ed25519 key
 // is live any more or the counters cannot be allocated: the caller then takes the
-// unrouted path, which is always right.
+// unrouted path, which is always right. count (K24, the mixed device call; null for the
+// dense calls): the device's word with the rows below n to route.
 static hipError_t ed_route_and_keyed(Device& d, DevBuf& sc, const uint8_t* keys, const uint8_t* sigs,
                                      const uint8_t* msgs, uint32_t msg_len, uint64_t n, const uint8_t* pre,
                                      uint8_t* status, uint32_t flags, hipStream_t s,
-                                     const std::function<hipError_t()>* before_msgs, bool* routed) {
+                                     const std::function<hipError_t()>* before_msgs, bool* routed,
+                                     const uint32_t* count = nullptr) {
   std::lock_guard<std::mutex> vk(d.vkey_mu);
   if (!d.vkeys.live || !d.vkeys.tab.p) return hipSuccess;
   if (!d.vkeys.route_tot.p) {  // the device's first routed enqueue
@@ -489,7 +496,7 @@ static hipError_t ed_route_and_keyed(Device& d, DevBuf& sc, const uint8_t* keys,
   const uint32_t* vtab = d.vkeys.tab.as<uint32_t>();
   return fenced({&d.vkeys.ev}, s, [&] {
     hipError_t e =
-        launch_ed25519_route(keys, n, vtab, sc.as<uint32_t>(), d.vkeys.route_tot.as<unsigned long long>(), s);
+        launch_ed25519_route(keys, n, vtab, sc.as<uint32_t>(), d.vkeys.route_tot.as<unsigned long long>(), s, count);
     // the split-prep callers' messages: route and partition needed only the keys
     if (e == hipSuccess && before_msgs) e = (*before_msgs)();
     return e ? e
@@ -587,7 +594,16 @@ hipError_t ed_verify_device_chunks(Device& d, TxSet& S, const uint8_t* keys, con
 // RSA per width class over launch_rsa_pss_verify_counted -- and the rows' statuses go
 // back to lane order. One stream, no read-back; the host sizes every launch and every
 // buffer for its upper bound (n lanes; an RSA class key_bytes / the smallest key of the
-// class). The routing switches are not consulted.
+// class).
+// K24, cordahip_vkey_set_routing_device on: each family's section follows that family's
+// routing switch and live keys, as the dense calls do, through the same helpers
+// (ed_route_and_keyed, ec_route_and_keyed, rsa_route_and_keyed) and the counted instances
+// of the route passes, which read the class's row count where the packer left it. The
+// family's scratch (d.ed_route[0], d.ec[0].route / perm / counters, d.rsa.route) sits
+// behind the family's lock and fence, taken here anyway. Lock order: sigpack_mu, the
+// family's mutex, vkey_mu; vkey_mu is never held across a wait for a lock, a fence or an
+// allocation. No live key, the family's switch off, no room for the scratch: the family
+// takes the unrouted launches. Off (the default): the switches are not consulted.
 hipError_t sig_device_enqueue(Device& d, const sigpack::In& in, const uint8_t* msgs, uint8_t* status,
                               unsigned long long* verdict, hipStream_t s) {
   using namespace sigpack;
@@ -653,52 +669,108 @@ hipError_t sig_device_enqueue(Device& d, const sigpack::In& in, const uint8_t* m
   }
   const uint32_t* hdr = out.hdr;
   const uint32_t flags = in.do_verify ? 0u : (uint32_t)CORDAHIP_FLAG_IS_VALID;
+  const bool dev_route = d.sig_route_on.load(std::memory_order_relaxed) != 0;
   bool launched = false;
   const auto run = [&]() -> hipError_t {
     launched = true;
     hipError_t r = launch_sig_pack(in, out, s);
     if (r != hipSuccess) return r;
-    {  // Ed25519: K1's indexed instance over rows 0 .. count
+    {  // Ed25519: K1's indexed instance over rows 0 .. count; routed (K24): K14's counted
+       // partition of those rows, K12 over the keyed list, K1 over the generic list
       uint8_t* em = at(base, o_edmsg);
       uint8_t* est = at(base, o_edst);
-      r = launch_sig_gather(msgs, in.msg_len, out.ed_msg, hdr + kHdrClass + kEd, n, em, s);
+      const uint32_t* cnt = hdr + kHdrClass + kEd;
+      r = launch_sig_gather(msgs, in.msg_len, out.ed_msg, cnt, n, em, s);
       if (r != hipSuccess) return r;
       std::lock_guard<std::mutex> ge(d.ed_mu[0]);
-      r = ed_ws_grow(d, 0, n, false, [] { return hipSuccess; });
+      DevBuf& sc = d.ed_route[0];
+      bool want_route = dev_route && d.route_on.load(std::memory_order_relaxed) && n <= ed25519_route_max_lanes();
+      if (want_route) {  // a look at the registry; decided for good in ed_route_and_keyed
+        std::lock_guard<std::mutex> vk(d.vkey_mu);
+        want_route = d.vkeys.live && d.vkeys.tab.p;
+      }
+      const size_t sc_bytes = want_route ? ed25519_route_scratch_bytes(n) : 0;
+      r = ed_ws_grow(d, 0, n, sc.cap < sc_bytes, [&] {
+        if (sc.cap < sc_bytes && sc.ensure(sc_bytes) != hipSuccess) {  // no room: verified unrouted
+          (void)hipGetLastError();
+          want_route = false;
+        }
+        return hipSuccess;
+      });
       if (r != hipSuccess) return r;
       const uint64_t lane_bytes = ed25519_ws_lane_bytes();
       r = fenced({&d.ed_ev[0]}, s, [&] {
-        return launch_ed25519_verify_idx(reinterpret_cast<const uint8_t*>(out.ed_key),
-                                         reinterpret_cast<const uint8_t*>(out.ed_sig), em, in.msg_len, n,
-                                         d.btab.as<uint32_t>(), out.ed_pre, est, d.ed_ws[0].as<uint32_t>(),
-                                         d.ed_ws[0].cap / lane_bytes / 64 * 64, flags, hdr + kHdrEd, s, 0);
+        const uint8_t* ek = reinterpret_cast<const uint8_t*>(out.ed_key);
+        const uint8_t* es = reinterpret_cast<const uint8_t*>(out.ed_sig);
+        bool routed = false;
+        const hipError_t q = want_route ? ed_route_and_keyed(d, sc, ek, es, em, in.msg_len, n, out.ed_pre, est, flags,
+                                                             s, nullptr, &routed, cnt)
+                                        : hipSuccess;
+        if (q != hipSuccess) return q;
+        // unrouted: the counter block's route-format header with iota as its list
+        return launch_ed25519_verify_idx(ek, es, em, in.msg_len, n, d.btab.as<uint32_t>(), out.ed_pre, est,
+                                         d.ed_ws[0].as<uint32_t>(), d.ed_ws[0].cap / lane_bytes / 64 * 64, flags,
+                                         routed ? sc.as<uint32_t>() : hdr + kHdrEd, s, routed ? kEdIdxLayoutOfN : 0);
       });
       if (r != hipSuccess) return r;
-      r = launch_sig_scatter(est, out.ed_lane, hdr + kHdrClass + kEd, n, status, s);
+      r = launch_sig_scatter(est, out.ed_lane, cnt, n, status, s);
       if (r != hipSuccess) return r;
     }
-    {  // ECDSA: K2's indexed instance over perm and the engine's counters
+    {  // ECDSA: K2's indexed instance over perm and the engine's counters; routed (K24):
+       // K15's seven classes rebuilt over rows 0 .. count in the slot's own perm and
+       // counters, K13 over each live curve's run, K2 over the generic list
       uint8_t* cm = at(base, o_ecmsg);
       uint8_t* cst = at(base, o_ecst);
-      r = launch_sig_gather(msgs, in.msg_len, out.ec_msg, hdr + kHdrClass + kEc, n, cm, s);
+      const uint32_t* cnt = hdr + kHdrClass + kEc;
+      r = launch_sig_gather(msgs, in.msg_len, out.ec_msg, cnt, n, cm, s);
       if (r != hipSuccess) return r;
       std::lock_guard<std::mutex> gc(d.ec_mu[0]);
       EcWork& ew = d.ec[0];
+      bool want_route = dev_route && d.ec_route_on.load(std::memory_order_relaxed) && n <= ecdsa_route_max_lanes();
+      if (want_route) {  // a look at the registry; decided for good in ec_route_and_keyed
+        std::lock_guard<std::mutex> vk(d.vkey_mu);
+        want_route = d.ec_vkeys.tab.p && d.ec_vkeys.book.any_live();
+      }
+      const size_t sc_bytes = want_route ? ecdsa_route_scratch_bytes(n) : 0;
+      const size_t perm_bytes = want_route ? (size_t)n * 4 : 0;
       const uint64_t slots = std::min<uint64_t>(d.ec_ws_slots, (n + 63) / 64 * 64);
       const bool ws_needed = ew.ws.cap < slots * ecdsa_ws_slot_bytes();
-      r = ew.ev.grow(ws_needed, [&] {
-        const uint64_t want = std::max<uint64_t>(slots, std::min<uint64_t>(d.ec_ws_slots, kWsMinLanes));
-        return ew.ws.ensure(want * ecdsa_ws_slot_bytes()) ? hipErrorOutOfMemory : hipSuccess;
+      r = ew.ev.grow(ws_needed || ew.route.cap < sc_bytes || ew.perm.cap < perm_bytes, [&] {
+        if (ws_needed) {
+          const uint64_t want = std::max<uint64_t>(slots, std::min<uint64_t>(d.ec_ws_slots, kWsMinLanes));
+          if (ew.ws.ensure(want * ecdsa_ws_slot_bytes())) return hipErrorOutOfMemory;
+        }
+        // no room for the route ids or the routed perm: the rows are verified unrouted
+        if ((ew.route.cap < sc_bytes && ew.route.ensure(sc_bytes) != hipSuccess) ||
+            (ew.perm.cap < perm_bytes && ew.perm.ensure(perm_bytes) != hipSuccess)) {
+          (void)hipGetLastError();
+          want_route = false;
+        }
+        return hipSuccess;
       });
       if (r != hipSuccess) return r;
+      if (want_route && ew.counters.ensure(64) != hipSuccess) {
+        (void)hipGetLastError();
+        want_route = false;
+      }
       r = fenced({&ew.ev}, s, [&] {
+        bool routed = false;
+        const hipError_t q =
+            want_route ? ec_route_and_keyed(d, ew, out.ec_scheme, out.ec_key, out.ec_key_len, out.ec_sig,
+                                            out.ec_sig_len, cm, nullptr, in.msg_len, n, out.ec_pre, cst, flags, s,
+                                            &routed, cnt)
+                       : hipSuccess;
+        if (q != hipSuccess) return q;
+        // unrouted: the packer's perm and the counters it left in the engine's format
         return launch_ecdsa_verify_routed(out.ec_scheme, out.ec_key, out.ec_key_len, out.ec_sig, out.ec_sig_len, cm,
                                           nullptr, in.msg_len, n, d.gtab_k1.as<uint32_t>(), d.gtab_r1.as<uint32_t>(),
-                                          out.ec_pre, cst, nullptr, hdr + kHdrEc, out.ec_perm, ew.ws.as<uint32_t>(),
+                                          out.ec_pre, cst, nullptr,
+                                          routed ? ew.counters.as<unsigned int>() : hdr + kHdrEc,
+                                          routed ? ew.perm.as<unsigned int>() : out.ec_perm, ew.ws.as<uint32_t>(),
                                           ew.ws.cap / ecdsa_ws_slot_bytes() / 64 * 64, flags, s);
       });
       if (r != hipSuccess) return r;
-      r = launch_sig_scatter(cst, out.ec_lane, hdr + kHdrClass + kEc, n, status, s);
+      r = launch_sig_scatter(cst, out.ec_lane, cnt, n, status, s);
       if (r != hipSuccess) return r;
     }
     for (uint32_t k = 0; k < 3; k++) {  // RSA: one width class per launch set
@@ -710,13 +782,51 @@ hipError_t sig_device_enqueue(Device& d, const sigpack::In& in, const uint8_t* m
       r = launch_sig_gather(msgs, in.msg_len, out.rsa_msg[k], cnt, cap[k], rm, s);
       if (r != hipSuccess) return r;
       std::lock_guard<std::mutex> gr(d.rsa_mu);
+      RsaWork& rw = d.rsa;
       r = rsa_ws_grow(d, W, cap[k]);
       if (r != hipSuccess) return r;
-      r = fenced({&d.rsa.ev}, s, [&] {
-        return launch_rsa_pss_verify_counted(out.rsa_mod[k], out.rsa_exp[k],
-                                             reinterpret_cast<const uint8_t*>(out.rsa_sig[k]), out.rsa_sig_len[k], rm,
-                                             in.msg_len, W, cap[k], cnt, hdr + kHdrWords, at32(rbase, o_rlc[k]), rst,
-                                             d.rsa.ws.as<uint8_t>(), rsa_ws_rows(d.rsa, W), flags, s);
+      bool want_route = dev_route && d.rsa_route_on.load(std::memory_order_relaxed);
+      if (want_route) {  // a look at the registry; decided for good, per launch, in rsa_route_and_keyed
+        std::lock_guard<std::mutex> vk(d.vkey_mu);
+        want_route = d.rsa_vkeys.live && d.rsa_vkeys.tab.p;
+      }
+      const uint64_t ws_rows = rsa_ws_rows(rw, W), lr = rsa_launch_rows(ws_rows);
+      const uint64_t cap_rows = std::min<uint64_t>(lr, (cap[k] + 63) / 64 * 64);
+      want_route = want_route && lr;
+      const size_t sc_bytes = want_route ? rsa_route_scratch_bytes(cap_rows) : 0;
+      r = rw.ev.grow(rw.route.cap < sc_bytes, [&] {
+        if (rw.route.ensure(sc_bytes) != hipSuccess) {  // no room: the class is verified unrouted
+          (void)hipGetLastError();
+          want_route = false;
+        }
+        return hipSuccess;
+      });
+      if (r != hipSuccess) return r;
+      const uint8_t* rsig = reinterpret_cast<const uint8_t*>(out.rsa_sig[k]);
+      unsigned int* rlc = at32(rbase, o_rlc[k]);
+      r = fenced({&rw.ev}, s, [&]() -> hipError_t {
+        if (!want_route)
+          return launch_rsa_pss_verify_counted(out.rsa_mod[k], out.rsa_exp[k], rsig, out.rsa_sig_len[k], rm,
+                                               in.msg_len, W, cap[k], cnt, hdr + kHdrWords, rlc, rst,
+                                               rw.ws.as<uint8_t>(), ws_rows, flags, s);
+        // K20's head / keyed / tail per launch of the workspace loop, each launch's rows
+        // clipped on the device (K23's convention: launch j's in rlc[j])
+        hipError_t q = hipSuccess;
+        uint64_t j = 0;
+        for (uint64_t lo = 0; lo < cap[k] && q == hipSuccess; lo += lr, j++) {
+          const uint64_t m = std::min(lr, cap[k] - lo);
+          q = launch_rsa_routed_head(out.rsa_mod[k], out.rsa_exp[k], rsig, out.rsa_sig_len[k], nullptr, in.msg_len, W,
+                                     lo, m, nullptr, rw.ws.as<uint8_t>(), ws_rows, flags, s, cnt, rlc + j);
+          bool routed = false;
+          q = q ? q
+                : rsa_route_and_keyed(d, out.rsa_mod[k], out.rsa_exp[k], W, lo, m, ws_rows, cap_rows, s, &routed,
+                                      rlc + j);
+          q = q ? q
+                : launch_rsa_routed_tail(out.rsa_mod[k], out.rsa_exp[k], rm, nullptr, in.msg_len, W, lo, m, rst,
+                                         nullptr, rw.ws.as<uint8_t>(), ws_rows, rw.route.as<uint32_t>(), cap_rows,
+                                         routed, s, rlc + j, hdr + kHdrWords);
+        }
+        return q;
       });
       if (r != hipSuccess) return r;
       r = launch_sig_scatter(rst, out.rsa_lane[k], cnt, cap[k], status, s);

@@ -105,8 +105,10 @@ hipError_t launch_ed25519_verify_keyed(const uint32_t* key_id, const uint8_t* si
 // device; the verdict words are gathered from the statuses afterwards.
 size_t ed25519_route_scratch_bytes(uint64_t n);  // a capacity: powers of two from a floor
 uint64_t ed25519_route_max_lanes();              // larger batches are not routed (32-bit lane indices)
+// count (K24): null, or the device's word holding how many of the n rows to partition
+// (clipped to n on the device); rows past it enter neither list.
 hipError_t launch_ed25519_route(const uint8_t* keys, uint64_t n, const uint32_t* vtab, uint32_t* scratch,
-                                unsigned long long* totals, hipStream_t s);
+                                unsigned long long* totals, hipStream_t s, const uint32_t* count = nullptr);
 hipError_t launch_ed25519_verify_keyed_idx(const uint32_t* scratch, uint64_t lanes, const uint8_t* sigs,
                                            const uint8_t* msgs, uint32_t msg_len, const uint8_t* pre, uint32_t flags,
                                            const uint32_t* vtab, uint8_t* status, hipStream_t s);
@@ -230,12 +232,13 @@ hipError_t launch_ecdsa_verify_keyed(const uint32_t* key_id, const uint8_t* sigs
 // least that large), the seven class counts and cursors in `counters` (64 bytes) and
 // perm[n] -- the generic list first, then each curve's keyed run -- and adds to the
 // device's cumulative counters; the indexed instances of K13 and K2 run over the
-// lists, their lane counts read on the device.
+// lists, their lane counts read on the device. count (K24): as launch_ed25519_route's;
+// rows past it enter no class.
 size_t ecdsa_route_scratch_bytes(uint64_t n);  // a capacity: powers of two from a floor
 uint64_t ecdsa_route_max_lanes();              // larger batches are not routed (32-bit lane indices)
 hipError_t launch_ecdsa_route(const uint8_t* scheme, const uint8_t* keys, const uint8_t* key_len, uint64_t n,
                               const uint32_t* vtab, uint32_t* scratch, unsigned int* counters, unsigned int* perm,
-                              unsigned long long* totals, hipStream_t s);
+                              unsigned long long* totals, hipStream_t s, const uint32_t* count = nullptr);
 hipError_t launch_ecdsa_verify_keyed_idx(const uint32_t* scratch, const unsigned int* perm,
                                          const unsigned int* counters, uint64_t n, const uint8_t* sigs,
                                          const uint8_t* sig_len, const uint8_t* msgs, const uint64_t* msg_off,
@@ -280,19 +283,27 @@ hipError_t launch_rsa_verify_keyed(const uint32_t* vtab, const uint32_t* key_id,
 // rsa_launch_rows(ws_rows); scratch: rsa_route_scratch_bytes(cap_rows), cap_rows >= m;
 // totals: the device's cumulative (keyed, generic) row counters. routed false in the
 // tail: the middle part did not run, K8's kernel takes every row as in an unrouted launch.
+// count (K24; null for the dense calls): the batch's rows are known on the device only
+// and m is the host's bound; the head writes the launch's rows, clipped to m, to
+// *launch_count, which the other two parts take (iota: row j of the list is row j, at
+// least m words, for a tail that is not routed).
 size_t rsa_route_scratch_bytes(uint64_t cap_rows);
 uint64_t rsa_launch_rows(uint64_t ws_rows);
 hipError_t launch_rsa_routed_head(const uint32_t* mod, const uint32_t* exp, const uint8_t* sigs,
                                   const uint16_t* sig_len, const uint64_t* msg_off, uint32_t msg_len, uint32_t W,
                                   uint64_t lo, uint64_t m, const uint8_t* pre, uint8_t* ws, uint64_t ws_rows,
-                                  uint32_t flags, hipStream_t s);
+                                  uint32_t flags, hipStream_t s, const unsigned int* count = nullptr,
+                                  unsigned int* launch_count = nullptr);
 hipError_t launch_rsa_routed_keyed(const uint32_t* mod, const uint32_t* exp, uint32_t W, uint64_t lo, uint64_t m,
                                    const uint32_t* vtab, uint8_t* ws, uint64_t ws_rows, uint32_t* scratch,
-                                   uint64_t cap_rows, unsigned long long* totals, hipStream_t s);
+                                   uint64_t cap_rows, unsigned long long* totals, hipStream_t s,
+                                   const unsigned int* launch_count = nullptr);
 hipError_t launch_rsa_routed_tail(const uint32_t* mod, const uint32_t* exp, const uint8_t* msgs,
                                   const uint64_t* msg_off, uint32_t msg_len, uint32_t W, uint64_t lo, uint64_t m,
                                   uint8_t* status, unsigned long long* verdict, uint8_t* ws, uint64_t ws_rows,
-                                  const uint32_t* scratch, uint64_t cap_rows, bool routed, hipStream_t s);
+                                  const uint32_t* scratch, uint64_t cap_rows, bool routed, hipStream_t s,
+                                  const unsigned int* launch_count = nullptr,
+                                  const unsigned int* iota = nullptr);
 // rsa_sign_keyed.hip (K19, in rsa.hip's unit): RSASSA-PSS signatures with registered
 // private keys. stab: the device's RSA signer table (rsa_sign.hpp: rsa_signtab_bytes();
 // null: no key was ever added, every ungated row is unknown); key_id[n], salts[n * 32],
@@ -1027,6 +1038,12 @@ struct Device {
   // take before.
   RsaVerifyKeys rsa_vkeys;
   std::atomic<uint32_t> rsa_route_on{0};
+  // Routing inside the mixed device calls (K24, cordahip_vkey_set_routing_device): with
+  // sig_route_on set, each family's section of sig_device_enqueue follows that family's
+  // switch above and its live keys, with the family's scratch behind the family's lock
+  // and fence: sigpack_mu -> the family's mutex -> vkey_mu, as the dense calls. Clear,
+  // the mixed calls launch, allocate and lock what they did before K24.
+  std::atomic<uint32_t> sig_route_on{0};
   // the chunk stage of cordahip_verify_keyed, cordahip_ecdsa_verify_keyed and
   // cordahip_rsa_verify_keyed (KeyedStage)
   KeyedStage vkey_stage;

@@ -501,6 +501,13 @@ class Engine:
         unrouted call. Off (the default): nothing changes. The other families' switches are their own."""
         check(lib().cordahip_vkey_set_routing_rsa(self._ctx, 1 if on else 0), "cordahip_vkey_set_routing_rsa")
 
+    def vkey_set_routing_device(self, on: bool):
+        """cordahip_vkey_set_routing_device: on, the mixed device-resident calls (sig_verify_device,
+        signed_tx_verify_device, signed_txcomp_verify_device, and resolve.notarise_transactions over them)
+        let each family's packed rows follow that family's routing switch above and its live keys;
+        statuses are those of the unrouted call. Off (the default): those calls ignore the switches."""
+        check(lib().cordahip_vkey_set_routing_device(self._ctx, 1 if on else 0), "cordahip_vkey_set_routing_device")
+
     def set_rsa_on_device(self, on: bool):
         """cordahip_set_rsa_on_device: on, the signed-transaction host calls (signed_tx_verify, tx_submit,
         their covered and component forms) verify RSA_SHA256 signatures on the GPU, each over its

@@ -481,7 +481,8 @@ def notarise_tearoffs_persisted(engine, log_id: int, tearoffs, callers, key_id: 
 
 
 def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_id: int, now: int, tolerance: int,
-                          device: int = 0, stream=None, detail: Optional[dict] = None, notary_family: str = "ed25519"):
+                          device: int = 0, stream=None, detail: Optional[dict] = None, notary_family: str = "ed25519",
+                          salts=None):
     """What a VALIDATING notary (ValidatingNotaryFlow) or any node that commits what it resolved does
     with full transactions, on torch device tensors and ONE stream, with no device-to-host copy
     before the final download (K22):
@@ -500,8 +501,14 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
     any triple is present, step 1 is Engine.signed_txcomp_verify_device over all of the batch's
     signatures (a pair counts as an Ed25519 triple): classified and packed on the GPU, RSA_SHA256
     following Engine.set_rsa_on_device. notary_family: "ed25519" (step 4 as above, 64-byte answers)
-    or "ecdsa" (key_id is an ECDSA signer's: Engine.ecdsa_sign_keyed_device, DER answers). RSA
-    notary keys need caller-drawn salts and stay out.
+    or "ecdsa" (key_id is an ECDSA signer's: Engine.ecdsa_sign_keyed_device, DER answers) or "rsa"
+    (K24: key_id is an RSA signer's and salts[t] the caller-drawn 32-byte salt of transaction t, as
+    Engine.rsa_sign_keyed_device takes them; the call is enqueued once per width class, a key answers
+    in its own; the answers are the signature bytes at their sig_len). salts without "rsa", or "rsa"
+    without salts, is an AssertionError.
+    Registered verification keys: with the family switches and Engine.vkey_set_routing_device on,
+    the mixed step 1 sends the signatures of registered keys to the keyed verifiers; the answers
+    and the committed rows are those of the unrouted call.
     callers[t]: the requesting party's id; now / tolerance in ns; `device` is the log's.
 
     Returns (answers, committed_rows) in notarise_tearoffs's shape: answers[t] the notary's signature
@@ -526,7 +533,10 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
     tio[1:] = np.cumsum([len(comps) for comps, _ in stxs_as_components])
     tso = np.zeros(n + 1, np.int64)
     tso[1:] = np.cumsum([len(sg) for _, sg in stxs_as_components])
-    assert notary_family in ("ed25519", "ecdsa")
+    assert notary_family in ("ed25519", "ecdsa", "rsa")
+    assert (salts is not None) == (notary_family == "rsa"), "salts go with notary_family='rsa', and only with it"
+    if salts is not None:
+        assert len(salts) == n and all(len(x) == 32 for x in salts)
     flat = [x for _, sg in stxs_as_components for x in sg]
     mixed = any(len(x) == 3 for x in flat)
     if mixed:  # every signature as a (scheme, key, sig) triple, CSR
@@ -559,8 +569,11 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
         tw_from, tw_until, gate = z(n, dt=torch.int64), z(n, dt=torch.int64), z(n)
         c_status, committed = z(n), z(n)
         ref_state, ref_by = z(max(ref_cap, 1)), z(max(ref_cap, 1), 40)
-        ecdsa_notary = notary_family == "ecdsa"
+        ecdsa_notary, rsa_notary = notary_family == "ecdsa", notary_family == "rsa"
         n_sigs, n_sig_len, s_status = z(n, 72 if ecdsa_notary else 64), z(n), z(n)
+        if rsa_notary:  # a slot, a length and a status per width class
+            d_salts = up(np.frombuffer(b"".join(bytes(x) for x in salts), np.uint8).reshape(n, 32))
+            rsa_out = [(z(n, 4 * w), z(n, dt=torch.int16), z(n)) for w in (64, 96, 128)]
         if mixed:
             engine.signed_txcomp_verify_device(d_items, n_items, d_blob, d_tio, d_tso, d_sch, d_keys, d_key_off, d_sigs,
                                                d_sig_off, txid, v_status, first_bad, sig_status, device=device, stream=s)
@@ -575,12 +588,18 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
         if ecdsa_notary:
             engine.ecdsa_sign_keyed_device(d_key_id, txid, n_sigs, n_sig_len, s_status, gate=c_status, device=device,
                                            stream=s)
+        elif rsa_notary:
+            for sg_w, sl_w, st_w in rsa_out:  # a key of another class answers SIGN_UNKNOWN_KEY there
+                engine.rsa_sign_keyed_device(d_key_id, txid, d_salts, sg_w, sl_w, st_w, gate=c_status, device=device,
+                                             stream=s)
         else:
             engine.ed25519_sign_keyed_device(d_key_id, txid, n_sigs, s_status, gate=c_status, device=device, stream=s)
         status = torch.where(gate != 0, gate, c_status)
         # the one download
         out = [x.cpu().numpy() for x in (txid, status, committed, refs, tx_ref_off, ref_by, ref_state, n_sigs,
                                          s_status, v_status, n_sig_len)]
+        if rsa_notary:
+            rsa_host = [tuple(x.cpu().numpy() for x in o) for o in rsa_out]
     ids_a, status_a, committed_a, refs_a, off_a, by_a, state_a, sig_a, sst_a, verify_a, sig_len_a = out
     if detail is not None:
         detail.update(ids=ids_a, status=status_a, committed=committed_a, refs=refs_a[:ref_cap], tx_ref_off=off_a,
@@ -604,6 +623,11 @@ def notarise_transactions(engine, log_id: int, stxs_as_components, callers, key_
                     hist.setdefault(mine[k], (b[:32].tobytes(), int.from_bytes(b[32:36].tobytes(), "little"),
                                               int.from_bytes(b[36:40].tobytes(), "little")))
             answers.append(NotaryError("Conflict", txid_t, hist))
+        elif rsa_notary:
+            mine_w = [o for o in rsa_host if int(o[2][t]) != _SIGN_UNKNOWN_KEY]
+            if not mine_w:
+                raise NoSuchElementException("no registered key %d" % key_id)
+            answers.append(mine_w[0][0][t, :int(mine_w[0][1][t]) & 0xFFFF].tobytes())
         elif int(sst_a[t]) == _SIGN_UNKNOWN_KEY:
             raise NoSuchElementException("no registered key %d" % key_id)
         else:

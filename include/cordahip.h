@@ -240,7 +240,8 @@ int cordahip_rsa_pss_verify_device(cordahip_ctx* ctx, int device, const void* d_
  * with the meanings of cordahip_sig_batch; without the latter RSA_SHA256 lanes are
  * UNSUPPORTED and no RSA memory is allocated. d_verdict (uint64[(n + 63) / 64], bit =
  * status OK) may be NULL. Registered keys are not consulted: the call runs the generic
- * verifiers whatever cordahip_vkey_set_routing* say.
+ * verifiers whatever cordahip_vkey_set_routing* say, unless
+ * cordahip_vkey_set_routing_device is on.
  *
  * The host cannot see the offsets, so what is CORDAHIP_ERR_INVALID_ARG for a host batch
  * is a per-lane status here, as CORDAHIP_TX_BAD_COVER is for cordahip_tx_cover_device:
@@ -941,6 +942,37 @@ int cordahip_rsa_public_op_keyed_device(cordahip_ctx* ctx, int device, const voi
 int cordahip_vkey_set_routing_rsa(cordahip_ctx* ctx, uint32_t on);
 int cordahip_vkey_route_stats_rsa(cordahip_ctx* ctx, int device, uint64_t* keyed_rows, uint64_t* generic_rows);
 
+/* ---- Routing inside the mixed device-resident calls (K24) ---------------------
+ * cordahip_sig_verify_device, cordahip_signed_tx_verify_device and
+ * cordahip_signed_txcomp_verify_device classify and pack their lanes on the GPU; only
+ * the device knows how many rows each family got. K24 gives the three route passes
+ * (K14, K15, K20) instances that read that count from device memory, clip it to the
+ * bound the launch was sized for and partition the rows below it.
+ *
+ * cordahip_vkey_set_routing_device(ctx, on): on != 0 lets the three mixed device calls
+ * consult the family switches on every device of the context; 0 (the default) off. It
+ * takes effect with the next enqueue. Off, the three calls do exactly what they did
+ * before this switch existed: nothing more is launched, allocated or locked (one
+ * relaxed atomic load decides) and no route counter moves. On, each family's packed
+ * rows follow that family's own switch -- cordahip_vkey_set_routing (Ed25519),
+ * cordahip_vkey_set_routing_ecdsa, cordahip_vkey_set_routing_rsa -- and its own live
+ * keys, by the rules stated at those switches: Ed25519 rows below the count are split
+ * between K12 and K1, ECDSA rows between K13 (one run per live curve) and K2, the rows
+ * of each launch of an RSA width class between K18's and K8's exponentiation. A
+ * family with its switch off, with no live key or whose scratch does not fit in device
+ * memory takes the unrouted launches; no batch fails because it could not be routed.
+ * Every lane's status and verdict bit equal the unrouted call's under both flags
+ * values. The scratch is the family's own (the dense calls' slot 0 and the RSA
+ * workspace's), counted in cordahip_device_mem and released by cordahip_trim.
+ *
+ * Ordering: a routed mixed batch is a keyed call; cordahip_vkey_remove waits for the
+ * batches already enqueued before it clears a record.
+ * Counters: cordahip_vkey_route_stats, _ecdsa and _rsa also count the rows the mixed
+ * calls routed, by match, with the meaning they have for the dense calls: the rows
+ * below each family's count, RSA whether the prep decided the row or not.
+ * A NULL context is CORDAHIP_ERR_INVALID_ARG. */
+int cordahip_vkey_set_routing_device(cordahip_ctx* ctx, uint32_t on);
+
 /* ---- RSA_SHA256 lanes in the signed-transaction host calls -------------------
  * cordahip_set_rsa_on_device(ctx, on): the context-level counterpart of
  * CORDAHIP_FLAG_RSA_ON_DEVICE for the entry points whose structs carry no flags:
@@ -1034,7 +1066,8 @@ int cordahip_signed_tx_verify_ed25519_device(cordahip_ctx* ctx, int device, cons
  * per signature), and verified by doVerify rules with the generic verifiers -- RSA_SHA256
  * on the GPU while cordahip_set_rsa_on_device is on, UNSUPPORTED otherwise, as in
  * cordahip_signed_tx_verify; registered keys are not consulted whatever
- * cordahip_vkey_set_routing* say. Then K5's reduce as above: the signatures of a
+ * cordahip_vkey_set_routing* say, unless cordahip_vkey_set_routing_device is on. Then
+ * K5's reduce as above: the signatures of a
  * transaction whose id failed carry that status. A signature whose ranges are out of
  * bounds is CORDAHIP_STATUS_BAD_RANGE. The _ed25519_device call stays the fast path for a
  * caller who knows the batch is dense Ed25519. */
